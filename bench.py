@@ -2,13 +2,19 @@
 """Headline benchmark: SimulGen-VAE preset-1 `small` training step, per-GPU batch 16, on synthetic
 [P x 95008 nodes x 200 timesteps] data (BASELINE.json configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = augment+collate from the HBM-resident dataset -> VAE forward (spectral-norm power
 iteration, encoder, reparameterisation, decoder, recon head + loss) -> backward -> [RCCL gradient
 all-reduce, N>1] -> fused AdamW.  Nothing is skipped inside the timed region.  Rank 0 prints ONE
 JSON line.  Data: synthetic U(-0.7,0.7); weights: random init of the named architecture.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else
+the line can carry: the CPU baseline and its ELBO parity, the per-kernel timing pass (rooflines),
+the stream-overlap probe and the finite-loss check.  --dump-outputs DIR writes what the last timed
+step computed (its loss scalars, gradient norm and a seeded sample of every updated parameter) as
+DIR/<name>.npy; the inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -16,6 +22,7 @@ import os
 import random
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -30,6 +37,23 @@ ALPHA, LR = 1e6, 1e-3                # condition.txt alpha / LearningR
 HBM_PEAK_GBS = 8000.0                # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 MFMA_BF16_PEAK_TF = 2500.0           # dense bf16 MFMA peak
 MFMA_F32_PEAK_TF = 157.3
+DUMP_PARAM_BYTES = 48 << 20          # --dump-outputs: budget of the parameter samples (the whole dump stays under 64 MB)
+DUMP_PARAM_CAP = 1 << 15             # entries kept per parameter tensor
+
+
+def dump_outputs(out_dir, scalars, params):
+    """scalars: name -> float or list of floats (written as float64); params: name -> array of one updated parameter
+    tensor, written whole when small and as a fixed sample (indices seeded by the name) otherwise, as float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in scalars.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.atleast_1d(np.asarray(v, dtype=np.float64)))
+    cap = max(1, min(DUMP_PARAM_CAP, DUMP_PARAM_BYTES // 4 // max(1, len(params))))
+    for name, a in params.items():
+        flat = np.asarray(a).reshape(-1)
+        if flat.size > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            flat = flat[np.sort(rng.integers(0, flat.size, size=cap))]
+        np.save(os.path.join(out_dir, "param." + name + ".npy"), flat.astype(np.float32))
 
 
 def gemm_flops(cfg, batch):
@@ -121,16 +145,20 @@ def bench_latent_conditioner(args):
 
     def step():
         opt.zero_grad()
-        m.loss_backward(x, y1, y2)
-        opt.clip_and_step(10.0, 1e-3)
+        losses = m.loss_backward(x, y1, y2)
+        return losses, opt.clip_and_step(10.0, 1e-3)
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        (loss, la, lb), gn = last
+        dump_outputs(args.dump_outputs, {"loss": loss, "loss_a": la, "loss_b": lb, "grad_norm": float(gn)},
+                     {k: v.float().numpy() for k, v in m.state_dict().items()})
     fwd_gf = {256: 304.9, 512: 1218.0}.get(side)       # SURVEY 8(f) N1, measured on the reference at batch 16
     res = {"metric": "latent-conditioner training samples/sec (preset filters, batch 16)", "value": round(B * args.steps / el, 2), "unit": "samples/s",
            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True,
@@ -138,6 +166,9 @@ def bench_latent_conditioner(args):
            "config": {"workload": f"LatentConditionerImg training step, {side}x{side} images, batch {B} (BASELINE.json configs[4])",
                       "filters": filters, "image": side, "per_gpu_batch": B},
            "step_tflops": round(3 * fwd_gf * (B / 16) / (el / args.steps) / 1e3, 2) if fwd_gf else None, "roofline": None, "cpu_baseline": None}
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        return
     # roofline of the dominant GEMM class: events on torch's current stream (the operators' stream) around every GEMM operator
     # call of two extra steps; algorithmic FLOPs 2*M*N*K per call (convolutions: M = output pixels, K = kh*kw*Cin)
     from simulgen_vae_amd import ops as _ops
@@ -221,6 +252,13 @@ def main():
     ap.add_argument("--workload", default="vae", choices=["vae", "lc"],
                     help="vae = the headline hot path; lc = image latent-conditioner training step (BASELINE.json configs[4], secondary)")
     ap.add_argument("--image", type=int, default=512, help="lc: image side (configs[4] names 512x512)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure: CPU baseline (--cpu-baseline) and the ELBO "
+                         "parity against it, the per-kernel timing pass and rooflines (--no-kernel-timing), the stream-overlap probe, "
+                         "the finite-loss check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (loss scalars, gradient "
+                         "norm, a seeded sample of every updated parameter; < 64 MB)")
     args = ap.parse_args()
     if args.workload == "lc":
         return bench_latent_conditioner(args)
@@ -283,7 +321,7 @@ def main():
     # and the weight-gradient side stream always exist; the optimizer / communication streams only on the data-parallel path
     if ddp:
         ddp_info["aux_streams_overlap"] = eng.stream_overlaps()
-    else:
+    elif args.full:
         so = eng.stream_overlaps_existing()
         ddp_info["aux_streams_overlap"] = so
 
@@ -356,8 +394,17 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    sc = eng.forward(train=False)   # sanity: losses are finite after the timed steps
-    finite = bool(np.isfinite(sc["recon"]) and all(np.isfinite(k) for k in sc["kls"]))
+    if args.dump_outputs and rank == 0:
+        # what modules/train.py's loop reads back for a step (its scalars and gradient norm), then the updated weights
+        eng.read_accumulated(reset=True)
+        eng.accumulate_scalars()
+        acc = eng.read_accumulated(reset=True)
+        dump_outputs(args.dump_outputs, {"loss_recon": acc["recon"], "loss_kls": acc["kls"], "loss_mse": acc["mse"],
+                                         "grad_norm": acc["grad_norm"]}, eng.state_dict())
+    finite = None
+    if args.full:
+        sc = eng.forward(train=False)   # sanity: losses are finite after the timed steps
+        finite = bool(np.isfinite(sc["recon"]) and all(np.isfinite(k) for k in sc["kls"]))
 
     result = None
     if rank == 0:
@@ -387,7 +434,7 @@ def main():
             result["config"]["recompute_activations"] = True
             result["config"]["recompute_gib"] = round(eng.recompute_bytes() / 2 ** 30, 3)
     # per-kernel durations (hipEvents on the engine's stream around each GEMM's main kernel), outside the timed region
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         eng.kernel_time_reset(2)
         nt = 2
         for i in range(nt):
@@ -480,7 +527,7 @@ def main():
         for tms, cls, layer, shape, tf in sorted(rows, reverse=True):
             print(f"  {tms * 1e3:8.1f} us  {tf:7.1f} TF/s  {cls:8s} {layer:58s} {shape}", file=sys.stderr)
     if rank == 0:
-        if world == 1 and args.cpu_baseline == "auto":
+        if args.full and world == 1 and args.cpu_baseline == "auto":
             eng.close()
             del data
             torch.cuda.empty_cache()

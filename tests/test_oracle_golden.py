@@ -187,20 +187,34 @@ def test_lc_torch_port_matches_reference_golden():
     m.training = False
     with torch.no_grad():
         e1, e2 = m.forward(torch.from_numpy(g["x"]))
-    assert np.abs(e1.numpy() - g["eval_main"]).max() < 1e-5 and np.abs(e2.numpy() - g["eval_xs"]).max() < 1e-5
+    # the fp32 CPU convolutions sum in an order that depends on the host's ISA and thread count: a few ulps of the largest
+    # output (|eval_main| reaches ~2.9e3), so the bound is relative to each output's scale, as for the loss below
+    for got, ref in ((e1, g["eval_main"]), (e2, g["eval_xs"])):
+        assert np.abs(got.numpy() - ref).max() < 1e-5 * max(1.0, np.abs(ref).max())
     m = TorchPortLC(g["filters"], latent_end, latent, size2, state)
     masks = [torch.from_numpy(g[f"mask{i}"]) for i in range(7)]
     loss, A, Bl, p1, p2 = m.loss_backward(torch.from_numpy(g["x"]), g["y1"], g["y2"], masks)
     assert abs(loss - g["loss"][0]) < 1e-5 * g["loss"][0]
     gmax = max(np.abs(g[k]).max() for k in g.files if k.startswith("g."))
+    noise = {"latent_main_layer1.0.bias", "latent_main_layer2.0.bias", "xs_layer1.0.bias", "xs_layer2.0.bias"}   # zero true gradient
     for k in m.trainable:
+        if k in noise:
+            # in front of a training-mode BatchNorm: both sides hold only rounding noise, whose pattern follows the host's
+            # summation order, so each must be zero to fp32 precision of the largest gradient entry
+            assert max(np.abs(m.S[k].grad.numpy()).max(), np.abs(g["g." + k]).max()) <= 2e-7 * gmax, k
+            continue
         d = np.abs(m.S[k].grad.numpy() - g["g." + k]).max()
         assert d <= 1e-4 * max(np.abs(g["g." + k]).max(), 1e-4 * gmax), k
     total = m.clip_and_step(1e-3, 1e-4)
     assert abs(total - g["total_norm"][0]) < 1e-4 * g["total_norm"][0]
-    noise = {"latent_main_layer1.0.bias", "latent_main_layer2.0.bias", "xs_layer1.0.bias", "xs_layer2.0.bias"}   # zero true gradient
+    # AdamW's first step moves an entry by lr * g / (|g| + eps): where the reference gradient is below the resolution of the
+    # gradient check above (1e-4 of the tensor's largest entry; after clipping such entries come near eps) the step follows
+    # the host's rounding of that gradient, so those entries are held to one step (lr) and the resolved ones to 5e-5
     for k in m.trainable:
         if k not in noise:
-            assert np.abs(m.S[k].detach().numpy() - g["s1." + k]).max() <= 5e-5 * max(1.0, np.abs(g["s1." + k]).max()), k
+            d = np.abs(m.S[k].detach().numpy() - g["s1." + k])
+            resolved = np.abs(g["g." + k]) > 1e-4 * np.abs(g["g." + k]).max()
+            assert d[resolved].max() <= 5e-5 * max(1.0, np.abs(g["s1." + k]).max()), k
+            assert d.max() <= 1e-3, k
     for k in ("initial_conv.0.weight_u", "layers.3.conv2.weight_v", "xs_layer1.1.running_var"):
         assert np.abs(m.S[k].detach().numpy() - g["s1." + k]).max() < 1e-5, k

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 10 --warmup 3 --cpu-baseline skip > $O/stats.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 10 --warmup 3 --cpu-baseline skip > $O/stats.log 2>&1 || exit 1
 echo "[profile] stats pass done"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 $R/bench.py --steps 2 --warmup 1 --cpu-baseline skip --no-kernel-timing > $O/fetch.log 2>&1 || exit 1
 echo "[profile] FETCH_SIZE pass done"

@@ -55,7 +55,7 @@ commit this file belongs to.  Un-profiled bench on the same box (`profiles/{TAG}
 
 ## Kernel time per training step, one stream (`SGV_DW_SIDE=0 SGV_LANES=0`; comparable with bench.py's hipEvent numbers)
 
-Command: `SGV_DW_SIDE=0 SGV_LANES=0 rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 3 --cpu-baseline skip`
+Command: `SGV_DW_SIDE=0 SGV_LANES=0 rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline skip`
 (raw: `profiles/{TAG}_bench_kernel_stats.csv`).  The 256x256 kernel appears as four template instances (<OUT, MT>: bf16 / fp32-slab
 output, one / several taps); its class in bench.py also counts the 128-row tail launch (`gemm_nt_wide64p_kernel`) and the
 split-K combine (`t256_reduce_kernel`) of a planned launch.
@@ -63,7 +63,7 @@ split-K combine (`t256_reduce_kernel`) of a planned launch.
 {serial}
 ## Kernel time per training step, default mode (weight-gradient side stream + second compute lane)
 
-Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 3 --cpu-baseline skip`
+Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline skip`
 (raw: `profiles/{TAG}_bench_kernel_stats_overlapped.csv`); kernels overlap, so their sum exceeds the step time.
 
 {overl}
@@ -93,7 +93,7 @@ MFMA pipe busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x duration x 2.4 GHz) = 
 ## Latent conditioner (`bench.py --workload lc`, 512 x 512, batch 16, bf16)
 
 Un-profiled: {lb["value"]:.0f} samples/s, {lb["ms_per_step"]:.2f} ms/step (`profiles/{TAG}_lc_bench_line.json`); dominant GEMM class
-{lb["roofline"]["achieved"] if lb.get("roofline") else None} TFLOP/s.  Kernel stats of `rocprofv3 --kernel-trace --stats -- python3 bench.py --workload lc --steps 10 --warmup 3 --cpu-baseline skip`
+{lb["roofline"]["achieved"] if lb.get("roofline") else None} TFLOP/s.  Kernel stats of `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --workload lc --steps 10 --warmup 3 --cpu-baseline skip`
 (raw: `profiles/{TAG}_lc_kernel_stats.csv`; whole run of 15 steps):
 
 {lc_tab}

@@ -45,7 +45,7 @@ about ±3 %.  The GPU runs at ≈2.2 GHz / 1.13-1.16 kW under this load (rocm-sm
 
 ## Kernel time per training step, one stream (comparable with bench.py's roofline numbers)
 
-Command: `SGV_DW_SIDE=0 rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 3 --cpu-baseline skip`
+Command: `SGV_DW_SIDE=0 rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline skip`
 (raw: `profiles/r01_bench_kernel_stats.csv`).  bench.py's kernel-timing pass also runs on one stream, so its `avg_launch_ms`
 (hipEvents; {b["roofline"]["avg_launch_ms"] * 1e3:.0f} µs for gemm_nt_wide64p, {b["roofline_gemm_tn"]["avg_launch_ms"] * 1e3:.0f} µs for the weight-gradient class in the
 un-profiled run) is to be compared with the averages below (the profiled run is slower by the tool's clock effect; the events
@@ -55,7 +55,7 @@ layers with < 256 input channels).
 {serial}
 ## Kernel time per training step, default mode (second stream active)
 
-Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 3 --cpu-baseline skip`
+Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline skip`
 (raw: `profiles/r01_bench_kernel_stats_overlapped.csv`).  Small weight-gradient GEMMs and the AdamW of finished buckets
 run on a second stream, so per-kernel durations stretch and their sum exceeds the step time.
 

@@ -187,6 +187,42 @@ int sgv_pset_power_iteration(sgv_pset* ps, int train, void* stream);
 const float* sgv_pset_sigma(const sgv_pset* ps, int entry);
 int sgv_pset_step(sgv_pset* ps, float lr, float weight_decay, float max_norm, float* total_norm_host, void* stream);
 
+/* Parametric (CSV) latent conditioner (modules/latent_conditioner_model_parametric.py:25-213): fused fp32 dense layers on
+ * row-major [B][features] activations, any B, K, O (edge tiles masked); every reduction in a fixed order (results replay
+ * bitwise).  Each call takes up to two independent problems of the same batch and runs them in one launch.
+ *   sgv_op_mlp_gemm_fwd: z[B][O] = x[B][K] . W[O][K]^T + bias[O] (bias may be NULL), tanh applied when tanh_out != 0
+ *     (the last Linear of each head).
+ *   sgv_op_mlp_rows_fwd: per row, out = drop(LNc(act(LNa(za) + (LNb(zb) | r | 0))))  -- LN = LayerNorm(O, eps 1e-5, biased
+ *     variance) with affine (ga, ba); zb / r optional and exclusive (skip Linear + LayerNorm of a ResidualBlock, or its
+ *     identity), act = exact GELU when gelu != 0, LNc (gc, bc) optional (feature_projection folded into the last block),
+ *     drop: out *= (mask[i] >= mask_thr ? mask_scale : 0) when mask != NULL (uniform draws with thr = p, or injected 0/1
+ *     masks with thr = 0.5).  stats [B][6] receives the row statistics {mean, rstd} of a, b, c.
+ *   sgv_op_mlp_rows_bwd: the same row chain backwards from dout (forward inputs and stats as in the forward): dza, dzb
+ *     (may be NULL), dr = the gradient at the residual sum (may be NULL), and five [B][O] planes of per-row partials in part:
+ *     ds*xhat_a, ds (dbeta_a = dbeta_b), ds*xhat_b, dw*uhat_c, dw (ds: gradient at the pre-activation sum, dw: at LNc's output).
+ *   sgv_op_mlp_gemm_bwd: dW[O][K] = dz^T . x, db[O] = sum_b dz (dz times 1 - y_tanh^2 when y_tanh != NULL: the Tanh of the
+ *     forward), dx[B][K] = dz . W -- per problem, or with dx_sum != 0 the sum over all problems (same K) plus dx_addend (may be
+ *     NULL) written to problem 0's dx; and the batch sums out[n] = sum_b src[b][n] of up to 12 [B][n] arrays (the row
+ *     partials -> dgamma / dbeta).  Any of dx, dW, db may be NULL. */
+typedef struct sgv_mlp_gemm { const float* x; const float* W; const float* bias; float* z; int K, O; } sgv_mlp_gemm;
+typedef struct sgv_mlp_rows {
+    const float* za; const float* ga; const float* ba;
+    const float* zb; const float* gb; const float* bb;
+    const float* r;
+    const float* gc; const float* bc;
+    const float* mask; float mask_thr, mask_scale;
+    int gelu, O;
+    float* out; float* stats;
+    const float* dout; float* dza; float* dzb; float* dr; float* part;
+} sgv_mlp_rows;
+typedef struct sgv_mlp_gemm_bwd { const float* dz; const float* y_tanh; const float* x; const float* W; float* dx; float* dW; float* db; int K, O; } sgv_mlp_gemm_bwd;
+typedef struct sgv_mlp_colsum { const float* src; float* out; int n; } sgv_mlp_colsum;
+int sgv_op_mlp_gemm_fwd(const sgv_mlp_gemm* probs, int n_probs, int B, int tanh_out, void* stream);
+int sgv_op_mlp_rows_fwd(const sgv_mlp_rows* probs, int n_probs, int B, void* stream);
+int sgv_op_mlp_rows_bwd(const sgv_mlp_rows* probs, int n_probs, int B, void* stream);
+int sgv_op_mlp_gemm_bwd(const sgv_mlp_gemm_bwd* probs, int n_probs, int dx_sum, const float* dx_addend, const sgv_mlp_colsum* sums, int n_sums,
+                        int B, void* stream);
+
 /* [Bn][I][J] -> [Bn][J][I] with dtype conversion (reference NCHW fp32 <-> channels-last compute dtype). */
 int sgv_op_transpose(int src_dtype, int dst_dtype, const void* src, void* dst, int Bn, int I, int J, void* stream);
 

@@ -98,6 +98,16 @@ def lc_synthetic(seed: int, P: int, pixels: int, latent_dim_end: int, size2: int
     return x, y1, y2
 
 
+def lc_csv_synthetic(seed: int, P: int, input_shape: int, latent_dim_end: int, size2: int, latent_dim: int):
+    """Synthetic tabular conditioner data set: parameter rows as latent_conditioner_scaler leaves them, U(-0.7, 0.7)
+    [P, input_shape]; main latents N(0, .5) [P, latent_dim_end]; hierarchical latents N(0, .5) [P, size2, latent_dim]."""
+    rng = np.random.Generator(np.random.Philox(key=[seed, 11]))
+    x = rng.uniform(-0.7, 0.7, (P, input_shape)).astype(np.float32)
+    y1 = (0.5 * rng.standard_normal((P, latent_dim_end))).astype(np.float32)
+    y2 = (0.5 * rng.standard_normal((P, size2, latent_dim))).astype(np.float32)
+    return x, y1, y2
+
+
 def noise_call(seed: int, k: int, shape) -> np.ndarray:
     """The k-th standard-normal draw of a run with injected noise (flat order, any shape of that size)."""
     n = int(np.prod(shape))

@@ -22,6 +22,15 @@ import torch
 from .. import ops
 
 
+# ---- data ------------------------------------------------------------------------------------------------------------
+def read_latent_conditioner_dataset(param_dir, param_data_type):
+    """latent_conditioner.py:100-104 (the `csv` input type): the whole file as a [rows, columns] array.  No header row is
+    read (pd.read_csv(..., header=None), as the reference's code does); the values are scaled later by
+    latent_conditioner_scaler, not remapped here."""
+    import pandas as pd
+    return pd.read_csv(param_dir, header=None).values
+
+
 # ---- schedule --------------------------------------------------------------------------------------------------------
 def lc_learning_rate(base_lr, epochs, epoch, warmup_epochs=100, eta_min=1e-8):
     """LR in effect during `epoch` (0-based) when the reference steps `warmup_scheduler` for epoch < 100 and `main_scheduler`

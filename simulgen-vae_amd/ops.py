@@ -19,7 +19,7 @@ OPS_SYMBOLS = [
     "sgv_op_layernorm_bwd", "sgv_op_batchnorm_fwd", "sgv_op_batchnorm_bwd", "sgv_op_mask_scale", "sgv_op_addf",
     "sgv_op_mse", "sgv_op_loss_value", "sgv_op_cols_sub_div", "sgv_op_multi_copy", "sgv_op_transpose", "sgv_op_l2_normalize", "sgv_op_dot", "sgv_op_sn_grad", "sgv_op_conv_weight_pack",
     "sgv_op_conv_weight_unpack", "sgv_op_sumsq", "sgv_op_clip_coef", "sgv_op_adamw", "sgv_op_flip_roll", "sgv_op_affine_sample",
-    "sgv_op_mixup_rows", "sgv_pset_create", "sgv_pset_destroy", "sgv_pset_power_iteration", "sgv_pset_sigma", "sgv_pset_step",
+    "sgv_op_mixup_rows", "sgv_op_mlp_gemm_fwd", "sgv_op_mlp_rows_fwd", "sgv_op_mlp_rows_bwd", "sgv_op_mlp_gemm_bwd", "sgv_pset_create", "sgv_pset_destroy", "sgv_pset_power_iteration", "sgv_pset_sigma", "sgv_pset_step",
 ]
 ACT_NONE, ACT_RELU_GN = 0, 3            # GroupNorm activation ids (ew.hip)
 LIN_NONE, LIN_RELU, LIN_SIGMOID = 0, 1, 2
@@ -89,6 +89,10 @@ def lib():
             "sgv_op_affine_sample": [vp, vp, i, i, i, vp, vp],
             "sgv_op_mixup_rows": [vp, vp, f, vp, i, lg, vp],
         }
+        sig["sgv_op_mlp_gemm_fwd"] = [vp, i, i, i, vp]
+        sig["sgv_op_mlp_rows_fwd"] = [vp, i, i, vp]
+        sig["sgv_op_mlp_rows_bwd"] = [vp, i, i, vp]
+        sig["sgv_op_mlp_gemm_bwd"] = [vp, i, i, vp, vp, i, i, vp]
         sig["sgv_pset_create"] = [vp, i, vp]
         sig["sgv_pset_destroy"] = [vp]
         sig["sgv_pset_power_iteration"] = [vp, i, vp]
@@ -628,3 +632,97 @@ class ParamSet:
         _ck(lib().sgv_pset_step(self.h, float(lr), float(weight_decay), float(max_norm), C.byref(out) if want_norm else None, _stream()),
             "sgv_pset_step")
         return out.value if want_norm else None
+
+
+# ---- fused dense layers of the parametric conditioner (sgv_op_mlp_*) ----
+class MlpGemm(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("z", C.c_void_p), ("K", C.c_int), ("O", C.c_int)]
+
+
+class MlpRows(C.Structure):
+    _fields_ = [("za", C.c_void_p), ("ga", C.c_void_p), ("ba", C.c_void_p), ("zb", C.c_void_p), ("gb", C.c_void_p), ("bb", C.c_void_p),
+                ("r", C.c_void_p), ("gc", C.c_void_p), ("bc", C.c_void_p), ("mask", C.c_void_p), ("mask_thr", C.c_float),
+                ("mask_scale", C.c_float), ("gelu", C.c_int), ("O", C.c_int), ("out", C.c_void_p), ("stats", C.c_void_p),
+                ("dout", C.c_void_p), ("dza", C.c_void_p), ("dzb", C.c_void_p), ("dr", C.c_void_p), ("part", C.c_void_p)]
+
+
+class MlpGemmBwd(C.Structure):
+    _fields_ = [("dz", C.c_void_p), ("y_tanh", C.c_void_p), ("x", C.c_void_p), ("W", C.c_void_p), ("dx", C.c_void_p), ("dW", C.c_void_p),
+                ("db", C.c_void_p), ("K", C.c_int), ("O", C.c_int)]
+
+
+class MlpColsum(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("n", C.c_int)]
+
+
+def _addr(t):
+    return None if t is None else (t if isinstance(t, int) else t.data_ptr())
+
+
+def _struct(cls, **kw):
+    s = cls()
+    for k, v in kw.items():
+        setattr(s, k, _addr(v) if (torch.is_tensor(v) or v is None) else v)
+    return s
+
+
+def mlp_gemm_fwd(problems, B, tanh_out=False):
+    """problems: up to two dicts(x [B, K], W [O, K], bias [O] or None) -> list of z [B, O] (one launch)."""
+    zs = [torch.empty((B, p["W"].shape[0]), dtype=torch.float32, device=p["x"].device) for p in problems]
+    arr = (MlpGemm * len(problems))(*[_struct(MlpGemm, x=p["x"], W=p["W"], bias=p.get("bias"), z=z, K=p["W"].shape[1], O=p["W"].shape[0])
+                                      for p, z in zip(problems, zs)])
+    _ck(lib().sgv_op_mlp_gemm_fwd(arr, len(problems), B, int(bool(tanh_out)), _stream()), "sgv_op_mlp_gemm_fwd")
+    return zs
+
+
+_ROW_KEYS = ("za", "ga", "ba", "zb", "gb", "bb", "r", "gc", "bc", "mask")
+
+
+def _rows(problems, extra):
+    out = []
+    for p, e in zip(problems, extra):
+        kw = {k: p.get(k) for k in _ROW_KEYS}
+        kw.update(mask_thr=float(p.get("mask_thr", 0.5)), mask_scale=float(p.get("mask_scale", 1.0)), gelu=int(bool(p.get("gelu", False))),
+                  O=int(p["za"].shape[1]), stats=p.get("stats"))
+        kw.update(e)
+        out.append(_struct(MlpRows, **kw))
+    return (MlpRows * len(out))(*out)
+
+
+def mlp_rows_fwd(problems, B):
+    """problems: up to two dicts of include/sgvae_ops.h's sgv_mlp_rows inputs (za, ga, ba [, zb, gb, bb | r] [, gc, bc]
+    [, mask, mask_thr, mask_scale], gelu) -> list of (out [B, O], stats [B, 6]) (one launch)."""
+    res = []
+    for p in problems:
+        O = p["za"].shape[1]
+        res.append((torch.empty((B, O), dtype=torch.float32, device=p["za"].device), torch.empty((B, 6), dtype=torch.float32, device=p["za"].device)))
+    for p, (_, st) in zip(problems, res):
+        p["stats"] = st
+    arr = _rows(problems, [dict(out=o) for o, _ in res])
+    _ck(lib().sgv_op_mlp_rows_fwd(arr, len(problems), B, _stream()), "sgv_op_mlp_rows_fwd")
+    return res
+
+
+def mlp_rows_bwd(problems, B):
+    """problems: the forward dicts (with their stats) plus dout, and flags need_dza / need_dzb / need_dr ->
+    list of dicts(dza, dzb, dr, part [5, B, O]) (one launch)."""
+    res = []
+    for p in problems:
+        shp, dev = p["za"].shape, p["za"].device
+        e = lambda want: torch.empty(shp, dtype=torch.float32, device=dev) if want else None
+        res.append(dict(dza=e(p.get("need_dza", True)), dzb=e(p.get("zb") is not None and p.get("need_dzb", True)), dr=e(p.get("need_dr", False)),
+                        part=torch.empty((5,) + tuple(shp), dtype=torch.float32, device=dev)))
+    arr = _rows(problems, [dict(dout=p["dout"], **r) for p, r in zip(problems, res)])
+    _ck(lib().sgv_op_mlp_rows_bwd(arr, len(problems), B, _stream()), "sgv_op_mlp_rows_bwd")
+    return res
+
+
+def mlp_gemm_bwd(problems, B, dx_sum=False, dx_addend=None, colsums=()):
+    """problems: up to two dicts(dz [B, O], y_tanh or None, x [B, K], W [O, K], dx, dW, db: output tensors or None);
+    colsums: (src [B, n], out [n]) pairs.  Everything in one launch; outputs are written into the given tensors."""
+    arr = (MlpGemmBwd * max(1, len(problems)))(*[_struct(MlpGemmBwd, dz=p["dz"], y_tanh=p.get("y_tanh"), x=p.get("x"), W=p.get("W"), dx=p.get("dx"),
+                                                         dW=p.get("dW"), db=p.get("db"), K=int(p["W"].shape[1] if p.get("W") is not None else p["x"].shape[1]),
+                                                         O=int(p["dz"].shape[1])) for p in problems])
+    cs = (MlpColsum * max(1, len(colsums)))(*[_struct(MlpColsum, src=s, out=o, n=int(o.numel())) for s, o in colsums])
+    _ck(lib().sgv_op_mlp_gemm_bwd(arr if problems else None, len(problems), int(bool(dx_sum)), _p(dx_addend), cs if colsums else None, len(colsums), B,
+                                  _stream()), "sgv_op_mlp_gemm_bwd")

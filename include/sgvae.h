@@ -86,7 +86,8 @@ int sgv_load_state(sgv_engine* e, const char* name, const float* host, size_t co
 int sgv_export_state(sgv_engine* e, const char* name, float* host, size_t count);
 /* p.grad of a parameter after sgv_backward (wrt weight_orig, i.e. with the spectral-norm chain
  * rule applied), reference layout; *is_none = 1 for parameters that never get a gradient
- * (train.py:157 `if p.grad is not None`).  [sync] */
+ * (train.py:157 `if p.grad is not None`).  The chain rule uses the current weight: read it before the AdamW step moves the
+ * weight.  [sync] */
 int sgv_export_grad(sgv_engine* e, const char* name, float* host, size_t count, int* is_none);
 /* Adam exp_avg / exp_avg_sq of a parameter (torch.optim.AdamW state), reference layout. [sync] */
 int sgv_export_adam(sgv_engine* e, const char* name, float* host_m, float* host_v, size_t count);
@@ -118,7 +119,10 @@ int sgv_set_shard(sgv_engine* e, int rank, int world);
  * the layers whose weight-gradient GEMM is the 256 x 256 kernel reach the optimizer as bf16 -- rounded to nearest even in the
  * GEMM's epilogue, the rounding the data-parallel step's bf16 wire format applies to every weight gradient -- 4 bytes less written
  * and read per parameter; sgv_export_grad / sgv_grad_norm refresh the fp32 arena from the bf16 copy on demand; ignored while a
- * communicator or a bucket callback is registered). */
+ * communicator or a bucket callback is registered.  Rule: after any call that exposes or changes the fp32 arena (sgv_scale_grads,
+ * sgv_grad_buffer), in any order with sgv_grad_norm / sgv_export_grad, the next AdamW reads exactly the arena's values and
+ * sgv_grad_norm / sgv_export_grad agree with them -- both calls refresh the arena first, and AdamW reads the fp32 arena for every
+ * layer until the next backward). */
 int sgv_set_option(sgv_engine* e, const char* key, int value);
 
 /* VAE.forward (VAE_network.py:79-121) on the current input.  train != 0: spectral-norm power

@@ -155,6 +155,9 @@ struct sgv_engine {
     int grad_bf16 = 0;
     bool lp_classified = false;
     std::vector<char> lp_dirty;          // per layer: its gradient of the last backward was stored as bf16 into grads_lp (not into the fp32 arena)
+    // sgv_scale_grads / sgv_grad_buffer changed or exposed the fp32 arena after an lp_sync: until the next backward the AdamW pass
+    // reads the fp32 arena for every layer (the mirror no longer holds the gradient)
+    bool lp_fp32 = false;
     std::vector<std::vector<int>> bucket_lp_layers;     // per weight bucket: its Layer::lp layers in arena order
     bool dw_chunk_direct = false;        // chunked first-layer gradient (data-parallel): the chunk GEMMs write the wire copy themselves
     // data-parallel optimizer overlap: the <G,W_eff> scalars of a weight bucket's layers sit together at the head of the small zone
@@ -847,14 +850,16 @@ static int tag_id(sgv_engine* e, const std::string& name) {
 // Times the MAIN kernel of a GEMM launch (split-K combine passes are excluded so the numbers line up with the
 // rocprofv3 per-kernel averages in profiles/).
 struct ScopedTimer {
-    sgv_engine* e; TimerRec r; bool on; bool ended = false;
+    sgv_engine* e; TimerRec r; bool on; bool ended = false; std::string name;
     void end_now() { if (on && !ended) { hipEventRecord(r.b, e->stream); ended = true; } }
+    // detail only: a fact the launch decided after the timer started (e.g. " out=bf16": the 256 x 256 kernel's bf16 epilogue)
+    void retag(const char* suffix) { if (on && e->timing_detail) r.tag = tag_id(e, name + suffix); }
     // detail (sgv_kernel_time_reset(e, 2)): one tag per (class, layer, shape) instead of one per class
     ScopedTimer(sgv_engine* e_, const char* cls, const Layer* l, int M = 0, int N = 0, int K = 0, int taps = 0, int sk = 0)
         : e(e_), on(e_->timing) {
         if (!on) return;
         hipEventCreate(&r.a); hipEventCreate(&r.b);
-        std::string name(cls);
+        name = cls;
         if (e->timing_detail && l) {
             char buf[160];
             snprintf(buf, sizeof(buf), "|%s|M=%d N=%d K=%d taps=%d splitk=%d", l->prefix.c_str(), M, N, K, taps, sk);
@@ -999,8 +1004,9 @@ static int join_side(sgv_engine* e) {
 }
 // ---- bf16 weight gradients straight from the 256 x 256 kernel (see the grad_bf16 member) ----
 static bool comm_is_single(void* comm);
-// which layers: those whose weight-gradient GEMM takes that kernel, unsplit, at the engine's full batch (fixed once: the AdamW table
-// points the layer at the mirror arena)
+// which layers: those whose weight-gradient GEMM takes that kernel, unsplit, at the engine's full batch, and whose mirror range the
+// launcher accepts as its bf16 output (alignment, offset ranges: a refused launch must never be left to write the mirror) -- fixed
+// once: the AdamW table points the layer at the mirror arena
 static void classify_lp(sgv_engine* e) {
     if (e->lp_classified) return;
     const long M = (long)e->maxB * e->T;
@@ -1009,7 +1015,8 @@ static void classify_lp(sgv_engine* e) {
         if (!(l.used && l.has_grad && l.op != OP_LINEAR && l.cin % 4 == 0) || e->dt != SGV_DTYPE_BF16 || !e->use_tr) continue;
         GemmTN q; memset(&q, 0, sizeof(q));
         q.M = (int)M; q.N1 = l.cout; q.N2 = l.cin; q.taps = l.k; q.pad = (l.k - 1) / 2; q.Tlen = e->T; q.lda = l.cout; q.ldb = l.cin; q.ldo = l.cin; q.use_tr = 1; q.splitk = 1;
-        l.lp = gemm_tn_uses_t256(e->dt, q) && gemm_tn_pick_splitk(q.M, q.N1, q.N2, q.taps, e->dt, e->T) == 1;
+        q.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw); q.out_bf16 = 1;
+        l.lp = gemm_tn_uses_t256(e->dt, q) && gemm_tn256_accepts(q) && gemm_tn_pick_splitk(q.M, q.N1, q.N2, q.taps, e->dt, e->T) == 1;
     }
     e->bucket_lp_layers.assign(e->buckets.size(), {});
     for (size_t b = 0; b + 1 < e->buckets.size(); ++b) {
@@ -1088,7 +1095,8 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
     if (e->dw_chunks > 1 && (int)(&l - e->layers.data()) == e->dw_chunk_layer && sk == 1 && !side && l.k == 1 && l.cout % (128 * e->dw_chunks) == 0) {
         const int rows = l.cout / e->dw_chunks;
         GemmTN q0 = p; q0.splitk = 1; q0.N1 = rows;
-        const bool direct = l.lp && wire_lp_active(e) && gemm_tn_uses_t256(e->dt, q0);       // the chunks' wire copy straight from the GEMM
+        q0.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw); q0.out_bf16 = 1;
+        const bool direct = l.lp && wire_lp_active(e) && gemm_tn_uses_t256(e->dt, q0) && gemm_tn256_accepts(q0);     // the chunks' wire copy straight from the GEMM
         e->dw_chunk_direct = direct;
         e->lp_dirty[(int)(&l - e->layers.data())] = direct ? 1 : 0;
         for (int c = 0; c < e->dw_chunks; ++c) {
@@ -1112,8 +1120,10 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
         static const int steal_on = getenv("SGV_TN256_STEAL") ? atoi(getenv("SGV_TN256_STEAL")) : 1;
         if (steal_on && e->coll_inflight && e->tn_sched) p.sched = e->tn_sched + 520 * (e->tn_sched_next++ & 7);
         const bool opt_lp = l.lp && grad_lp_active(e), wire_lp = l.lp && !opt_lp && wire_lp_active(e);
-        const bool lp = (opt_lp || wire_lp) && gemm_tn_uses_t256(e->dt, p);
-        if (lp) { p.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw); p.out_bf16 = 1; }
+        GemmTN plp = p;
+        plp.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw); plp.out_bf16 = 1;
+        const bool lp = (opt_lp || wire_lp) && gemm_tn_uses_t256(e->dt, plp) && gemm_tn256_accepts(plp);
+        if (lp) { p = plp; tm.retag(" out=bf16"); }
         if (launch_gemm_tn(e->dt, p, st)) return fail(SGV_ERR_ARG, "gemm_tn launch failed for %s", l.prefix.c_str());
         // a smaller batch than the one the layer was classified at took another kernel: the optimizer still reads the mirror, so the
         // fp32 result goes there in a pass (the wire copy gets it with the rest of the bucket: pack_bucket)
@@ -2286,12 +2296,21 @@ int sgv_set_bucket_callback(sgv_engine* e, sgv_bucket_cb cb, void* user) {
 }
 int sgv_grad_buffer(sgv_engine* e, float** dev_ptr, size_t* count_elems) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
+    // grad_bf16: the caller may read or write the arena from here on -- it gets the gradients of the last backward, and what it
+    // leaves there is what the next AdamW reads (the refresh is finished before the pointer is handed out)
+    if (std::find(e->lp_dirty.begin(), e->lp_dirty.end(), 1) != e->lp_dirty.end()) {
+        CHK(lp_sync(e));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    e->lp_fp32 = true;
     if (dev_ptr) *dev_ptr = e->grads;
     if (count_elems) *count_elems = e->n_grads;
     return SGV_OK;
 }
 int sgv_scale_grads(sgv_engine* e, float factor) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
+    CHK(lp_sync(e));                     // grad_bf16: the gradient of the mirrored layers into the fp32 arena, scaled there with the rest
+    e->lp_fp32 = true;
     ew_scale(e->grads, factor, (long)e->n_grads, e->stream);
     return SGV_OK;
 }
@@ -2307,6 +2326,7 @@ int sgv_adamw_step(sgv_engine* e, float lr);
 static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
     if (!e->have_fwd || !e->fwd_train) return fail(SGV_ERR_STATE, "sgv_backward needs a preceding sgv_forward(train=1)");
+    e->lp_fp32 = false;                  // grad_bf16: this backward's gradients of the mirrored layers go to the mirror again
     const bool fuse = fuse_lr >= 0.f;
     static const int early_on = getenv("SGV_EARLY_ADAM") ? atoi(getenv("SGV_EARLY_ADAM")) : 1;
     const bool early = early_on && fuse && !e->cb && !e->comm && e->side && e->use_side && !e->timing;
@@ -2619,7 +2639,7 @@ static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, 
     for (int a = t0; a < t1; a += slice) {
         const int b = std::min(t1, a + slice);
         if (opt_adamw_sn(e->adam_dev, e->sn_dev, e->items_adam_2d + a, b - a, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + e->n_items_adam_flat + a, e->dt, st,
-                         e->grads, from_lp ? e->grads_lp : nullptr, (!from_lp && grad_lp_active(e)) ? 1 : 0))
+                         e->grads, from_lp ? e->grads_lp : nullptr, (!from_lp && grad_lp_active(e) && !e->lp_fp32) ? 1 : 0))
             return fail(SGV_ERR_HIP, "adamw launch failed");
     }
     return 0;

@@ -1489,6 +1489,8 @@ int launch_gemm_tn(int dtype, const GemmTN& p, hipStream_t s) {
         const int r = launch_gemm_tn256(p, s);
         if (r != -1) return r;                       // -1: shape refused after all (offset ranges): the kernels below take it
     }
+    // a bf16 output exists only in the 256 x 256 kernel: the kernels below would store fp32 over a region half that size
+    if (p.out_bf16) return -1;
     if (c2d && p.use_tr && (gemm_tn_uses_w2(dtype, p.M, p.N1, p.N2, p.M) || (p.force_w2 && gemm_tn_w2_eligible(dtype, p.M, p.N1, p.N2, p.M)))) {
         dim3 gridw(tn_w2_schedule(q, cdiv(p.N1, 128), cdiv(p.N2, 256), 1));
         hipLaunchKernelGGL(gemm_tn_w2_kernel<true>, gridw, dim3(256), 0, s, q);

@@ -494,20 +494,25 @@ bool gemm_tn_uses_t256(int dtype, const GemmTN& p) {
     const long items = (long)q256_cdiv(p.N1, 256) * q256_cdiv(p.N2, 256) * p.taps;
     return items >= 200 && 2.0e-9 * p.M * p.N1 * p.N2 * p.taps >= min_gf;
 }
+bool gemm_tn256_accepts(const GemmTN& p) {
+    if (!gemm_tn256_eligible(1, p)) return false;
+    if (p.splitk < 1 || (p.splitk > 1 && p.out_slab_stride <= 0)) return false;
+    if (p.out_bf16 && (p.splitk != 1 || p.ldo % 4)) return false;      // bf16 output: direct stores only (slabs stay fp32)
+    if (q256_cdiv(p.M, 64) / p.splitk < 4) return false;              // every item keeps >= 4 K-tiles (prologue + counted waits)
+    if (((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15) || ((uintptr_t)p.out & 15)) return false;
+    const long a_bytes = ((long)(p.M - 1) * p.lda + p.N1) * 2, b_bytes = ((long)(p.M - 1) * p.ldb + p.N2) * 2;
+    // 32-bit buffer offsets; a lane's offset + scalar offset (incl. the tap shift and 63 rows of run-ahead) must stay below 2^31
+    if (a_bytes + 64L * p.lda * 2 >= 0x7FFFFFF0L || b_bytes + (64L + 2 * p.taps) * p.ldb * 2 >= 0x7FFFFFF0L) return false;
+    if (((long)(p.N1 - 1) * p.ldo + p.N2) * 4 >= 0x7FFFFFF0L) return false;
+    return true;
+}
 int launch_gemm_tn256(const GemmTN& p, hipStream_t s) {
-    if (!gemm_tn256_eligible(1, p)) return -1;
-    if (p.splitk < 1 || (p.splitk > 1 && p.out_slab_stride <= 0)) return -1;
-    if (p.out_bf16 && (p.splitk != 1 || p.ldo % 4)) return -1;         // bf16 output: direct stores only (slabs stay fp32)
-    if (q256_cdiv(p.M, 64) / p.splitk < 4) return -1;                 // every item keeps >= 4 K-tiles (prologue + counted waits)
-    if (((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15) || ((uintptr_t)p.out & 15)) return -1;
+    if (!gemm_tn256_accepts(p)) return -1;
     GemmTN q = p;
     static const int order_env = getenv("SGV_TN256_ORDER") ? atoi(getenv("SGV_TN256_ORDER")) : -1;
     q.order = order_env >= 0 ? order_env : 2;        // measured (one box, order 0 / 2): 665 / 650, 652 / 620, 837 / 826 us on the three big shapes
     q.a_bytes = ((long)(p.M - 1) * p.lda + p.N1) * 2;
     q.b_bytes = ((long)(p.M - 1) * p.ldb + p.N2) * 2;
-    // 32-bit buffer offsets; a lane's offset + scalar offset (incl. the tap shift and 63 rows of run-ahead) must stay below 2^31
-    if (q.a_bytes + 64L * p.lda * 2 >= 0x7FFFFFF0L || q.b_bytes + (64L + 2 * p.taps) * p.ldb * 2 >= 0x7FFFFFF0L) return -1;
-    if (((long)(p.N1 - 1) * p.ldo + p.N2) * 4 >= 0x7FFFFFF0L) return -1;
     const int nitems = q256_cdiv(p.N1, 256) * q256_cdiv(p.N2, 256) * p.taps * p.splitk;
     int grid = ((nitems + 7) / 8) * 8;
     if (grid > 256) grid = 256;

@@ -215,6 +215,8 @@ struct GemmTN {
 // gemm256tn.hip: 256 x 256 persistent weight-gradient kernel (bf16; same GemmTN contract, fp32 output / split-K slabs)
 bool gemm_tn256_eligible(int dtype, const GemmTN& p);
 bool gemm_tn_uses_t256(int dtype, const GemmTN& p);       // the launcher's choice: enough items to fill the chip, >= 150 GFLOP
+// everything launch_gemm_tn256 checks before it launches (eligibility, split-K, bf16 output, pointer alignment, offset ranges)
+bool gemm_tn256_accepts(const GemmTN& p);
 int launch_gemm_tn256(const GemmTN& p, hipStream_t s);
 int launch_gemm_nt(int dtype, const GemmNT& p, hipStream_t s);
 int launch_gemm_tn(int dtype, const GemmTN& p, hipStream_t s);

@@ -3,6 +3,8 @@ which imports /root/reference in the build container and records one training st
 
   g2_preset_4096   preset filters [1024, 512, 256, 128], N = 4096, T = 32, B = 4   (BASELINE.json configs[0]'s shape)
   g3_fullsize_b2   preset filters, N = 95008, T = 200, B = 2                       (configs[1]'s full size)
+  g4_fullsize_b16_steps  configs[1]'s full size at the bench batch B = 16: four AdamW steps (the last a ragged batch of 2), replayed on
+                   the fp32 and bf16 engines and on the bf16 engine with grad_bf16 (test_training_steps_match_reference, bounds below)
 
 Weights / inputs / noise are regenerated here from the same numpy Philox streams, so the engine runs the very step the
 reference ran.  Stated tolerances:
@@ -121,3 +123,159 @@ def test_engine_matches_reference_fullwidth(tag, dtype):
             d = np.abs(sd[name].reshape(-1)[pos].astype(np.float64) - g[k]).max()
             assert d <= (1e-5 if f32 else 2e-3) * max(float(np.abs(g[k]).max()), 1e-3), (name, d)
     eng.close()
+
+
+# ---- g4_fullsize_b16_steps: four reference training steps at the bench's shape (B = 16, AdamW lr 1e-3), the last a ragged batch of 2 ----
+# Replayed as forward(train) -> backward -> (gradients read) -> adamw_step: sgv_export_grad applies the spectral-norm chain rule with
+# the CURRENT weight, so the gradients are read before the optimizer moves it.  The bench's fused backward_step leaves bitwise the
+# same state as these separate calls (test_fullsize_gpu.py: test_fullsize_fused_step_is_bitwise_equal_to_separate_calls, and
+# test_fullsize_bf16_gradient_storage with grad_bf16).
+# Modes: the fp32 engine, the bf16 engine, and the bf16 engine with option grad_bf16 (what bench.py and modules/train.py run on one
+# GPU: at B = 16 the four big layers' weight gradients leave the 256 x 256 kernel as bf16 and AdamW reads them there).
+G4 = "g4_fullsize_b16_steps"
+STEP_MODES = {"f32": ("f32", 0), "bf16": ("bf16", 0), "bf16_grad_bf16": ("bf16", 1)}
+# the layers whose weight-gradient GEMM is the 256 x 256 kernel at B = 16 (the grad_bf16 layers)
+BIG4 = ["encoder.encoder_blocks.0.module_list.0._seq.0.weight_orig", "decoder.recon.0.weight_orig",
+        "decoder.decoder_residual_blocks.2.seq.3.weight_orig", "decoder.decoder_residual_blocks.1.seq.3.weight_orig"]
+# per asserted quantity, the worst value over the four steps: measured (MI355X) x margin.  elbo / recon / kl: relative error of the ELBO,
+# the two reconstruction terms, the three KL terms; gn: last_grad_norm(); gnorm: per-tensor gradient 2-norms; gsamp: sampled gradient
+# entries / the tensor's scale; dbig / dother: rel-L2 of the weight deltas W_s - W_0 at the sampled positions (the four big layers /
+# every other parameter) after steps 1, 3, 4; uv: sampled u / v entries / their scale.
+# Measured worst (fp32 | bf16 | bf16 + grad_bf16): elbo 1.1e-6 | 1.8e-4 | 1.6e-4, recon 1.2e-6 | 1.9e-4 | 1.7e-4, kl 9.4e-5 | 4.0e-2 | 4.0e-2,
+# gn 7.5e-6 | 5.0e-4 | 4.8e-4, gnorm 1.4e-4 | 3.6e-2 | 3.9e-2, gsamp 3.4e-3 | 0.11 | 0.12, dbig 7.0e-4 | 0.20 | 0.20, dother 2.3e-3 | 0.29 | 0.29,
+# uv 9.7e-4 | 7.5e-2 | 7.5e-2.  Past step 1 the sampled entries and the deltas carry Adam's sign-like first steps: an entry whose
+# gradient is near zero moves by +-lr on either side, so a re-drawn rounding of its gradient shows there at full size.
+STEP_BOUNDS = {
+    "f32": dict(elbo=5e-6, recon=5e-6, kl=2e-4, gn=3e-5, gnorm=4e-4, gsamp=1e-2, dbig=2e-3, dother=5e-3, uv=3e-3),
+    "bf16": dict(elbo=4e-4, recon=4e-4, kl=1e-1, gn=1.5e-3, gnorm=1e-1, gsamp=3e-1, dbig=0.4, dother=0.5, uv=0.15),
+}
+# grad_bf16 must add no error of its own: every quantity within max(2 x the plain bf16 engine's, this floor)
+LP_FLOOR = dict(elbo=1e-5, recon=1e-5, kl=1e-4, gn=1e-4, gnorm=1e-3, gsamp=1e-3, dbig=1e-3, dother=1e-3, uv=1e-4)
+_STEP_RUNS = {}
+
+
+def _rel_l2(a, b):
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def _replay_steps(mode):
+    """Deviations from the reference per step (dict quantity -> list over steps), and what shows that grad_bf16 engaged."""
+    if mode in _STEP_RUNS:
+        return _STEP_RUNS[mode]
+    import hashlib
+    g = np.load(os.path.join(GOLD, G4 + ".npz"))
+    alpha, beta, lr, sseed, dseed, eseed, B, N, T = g["meta"]
+    B, N, T = int(B), int(N), int(T)
+    cfg = VAEConfig(32, 8, ENC, ENC[::-1], N, T, "MSE", True)
+    state = init_state(cfg, int(sseed))
+    dtype, lp = STEP_MODES[mode]
+    names, p_names, uv_names = g["grad_names"].tolist(), g["p_names"].tolist(), g["uv_names"].tolist()
+    dev = {k: [] for k in STEP_BOUNDS["f32"]}
+    info = {}
+    eng = E.Engine(cfg, max_batch=B, compute_dtype=dtype)
+    try:
+        eng.load_state(state)
+        eng.set_option("write_xhat", 0)
+        if lp:
+            eng.set_option("grad_bf16", 1)
+        for s, (start, n, es) in enumerate(g["steps"].tolist(), start=1):
+            x = synthetic_samples(int(dseed), range(start, start + n), N, T)
+            eps = synthetic_eps(int(eseed), es, cfg, n)
+            eng.set_input(torch.from_numpy(x).cuda())
+            eng.set_eps([torch.from_numpy(e).cuda() for e in eps])
+            sc = eng.forward(train=True)
+            eng.backward(float(alpha), float(beta))
+            ref = g[f"scalars{s}"]             # recon, kl, kl2_0, kl2_1, mse, loss, grad norm
+            elbo = float(alpha) * sc["recon"] + float(beta) * sum(sc["kls"])
+            dev["elbo"].append(abs(elbo - ref[5]) / abs(ref[5]))
+            dev["recon"].append(max(abs(sc["recon"] - ref[0]) / abs(ref[0]), abs(sc["mse"] - ref[4]) / abs(ref[4])))
+            dev["kl"].append(max(abs(a - b) / abs(b) for a, b in zip(sc["kls"], ref[1:4])))
+            worst_n, worst_s, off = 0.0, 0.0, 0
+            samp = g[f"gradsamp{s}"]
+            for name, rn in zip(names, g[f"gradnorm{s}"]):
+                eg = eng.grad(name)
+                assert eg is not None, name
+                pos = sample_positions(name, eg.size)
+                rs = samp[off:off + pos.size].astype(np.float64)
+                off += pos.size
+                worst_n = max(worst_n, abs(float(np.linalg.norm(eg.astype(np.float64))) - rn) / (rn + 1e-30))
+                scale = max(float(np.abs(rs).max()), rn / np.sqrt(eg.size))
+                worst_s = max(worst_s, float(np.abs(eg.reshape(-1)[pos] - rs).max()) / scale)
+            assert off == samp.size
+            eng.adamw_step(float(lr))
+            dev["gn"].append(abs(eng.last_grad_norm() - ref[6]) / ref[6])
+            dev["gnorm"].append(worst_n)
+            dev["gsamp"].append(worst_s)
+            for name in g["nograd"].tolist():
+                assert eng.grad(name) is None, name
+            if f"p{s}samp" not in g.files:
+                continue
+            sd = eng.state_dict()
+            dbig, dother, off = 0.0, 0.0, 0
+            ps = g[f"p{s}samp"]
+            for k in p_names:
+                pos = sample_positions(k, sd[k].size)
+                w0 = state[k].reshape(-1)[pos].astype(np.float64)
+                dref = ps[off:off + pos.size].astype(np.float64) - w0
+                off += pos.size
+                if not np.any(dref):           # no gradient: AdamW leaves it (no weight decay either)
+                    assert np.array_equal(sd[k].reshape(-1)[pos], ps[off - pos.size:off]), k
+                    continue
+                d = _rel_l2(sd[k].reshape(-1)[pos].astype(np.float64) - w0, dref)
+                if k in BIG4:
+                    dbig = max(dbig, d)
+                else:
+                    dother = max(dother, d)
+            dev["dbig"].append(dbig)
+            dev["dother"].append(dother)
+            uvs, off, wu = g[f"uv{s}samp"], 0, 0.0
+            for k in uv_names:
+                pos = sample_positions(k, sd[k].size, 32)
+                r = uvs[off:off + pos.size].astype(np.float64)
+                off += pos.size
+                wu = max(wu, float(np.abs(sd[k].reshape(-1)[pos] - r).max()) / max(float(np.abs(r).max()), 1e-3))
+            dev["uv"].append(wu)
+            if s == 1:
+                info["big_after_1"] = {k: hashlib.sha256(sd[k].tobytes()).hexdigest() for k in BIG4}
+            del sd
+        # one more full-batch backward under the per-layer kernel timer (no optimizer step): which launches stored bf16
+        start, n, es = g["steps"][0].tolist()
+        eng.set_input(torch.from_numpy(synthetic_samples(int(dseed), range(start, start + n), N, T)).cuda())
+        eng.set_eps([torch.from_numpy(e).cuda() for e in synthetic_eps(int(eseed), es, cfg, n)])
+        eng.forward(train=True)
+        eng.kernel_time_reset(2)
+        eng.backward(float(alpha), float(beta))
+        info["bf16_out_layers"] = sorted({t.split("|")[1] for t, _, _ in eng.kernel_time_tags() if t.startswith("gemm_tn|") and "out=bf16" in t})
+        eng.kernel_time_reset(False)
+    finally:
+        eng.close()
+    print(f"[{G4} {mode}] per-step deviations from the reference:")
+    for k, v in dev.items():
+        print(f"    {k:7s} " + " ".join(f"{x:.2e}" for x in v))
+    print(f"    bf16-output weight-gradient launches: {info['bf16_out_layers']}")
+    _STEP_RUNS[mode] = (dev, info)
+    return dev, info
+
+
+@pytest.mark.parametrize("mode", list(STEP_MODES))
+def test_training_steps_match_reference(mode):
+    """Four training steps at the bench's shape against the reference's torch AdamW loop: scalars, gradient norm, every
+    gradient tensor (norm and samples, through sgv_export_grad -- which also refreshes the fp32 arena from the grad_bf16 mirror), the
+    weight deltas W_s - W_0 and the spectral-norm vectors after steps 1, 3, 4.  Pins the multi-step machinery at full size: AdamW
+    sliced under backward, the power-iteration state carried across steps, the ragged last batch."""
+    dev, info = _replay_steps(mode)
+    bounds = STEP_BOUNDS["f32" if mode == "f32" else "bf16"]
+    if mode == "bf16_grad_bf16":
+        # the option engaged on exactly the four big layers: they took the bf16 epilogue, and their weights after one step differ
+        # from the plain bf16 engine's (a run where the 256 x 256 kernel is never picked -- SGV_TN256_MIN_GF=1e9 -- fails here)
+        plain_dev, plain_info = _replay_steps("bf16")
+        assert info["bf16_out_layers"] == sorted(k.rsplit(".", 1)[0] for k in BIG4), info["bf16_out_layers"]
+        assert plain_info["bf16_out_layers"] == []
+        for k in BIG4:
+            assert info["big_after_1"][k] != plain_info["big_after_1"][k], k
+        for q, v in dev.items():
+            for s, (a, b) in enumerate(zip(v, plain_dev[q]), start=1):
+                assert a <= max(2 * b, LP_FLOOR[q]), (q, s, a, b)
+    for q, v in dev.items():
+        assert max(v) <= bounds[q], (q, v)
+    assert max(dev["elbo"][1:3]) <= 1e-4, dev["elbo"]         # the north-star bound, past the first step

@@ -10,6 +10,7 @@ import torch
 import simulgen_vae_amd  # noqa: F401
 from simulgen_vae_amd import engine as E
 from simulgen_vae_amd.init import init_state
+from simulgen_vae_amd.modules.train import _DevArray
 from simulgen_vae_amd.spec import VAEConfig
 from tests.gpu_common import rel_l2
 
@@ -260,6 +261,85 @@ def test_fullsize_bf16_gradient_storage():
     assert abs(fused[0][0][2] - plain[0][0][2]) <= 1e-3 * plain[0][0][2]
     assert rel_l2(sep[2][0], plain[2][0]) < 4e-3, rel_l2(sep[2][0], plain[2][0])
     assert abs(sep[2][1] - plain[2][1]) <= 1e-3 * plain[2][1]
+
+
+@pytest.mark.parametrize("grad_bf16", [0, 1])
+def test_fullsize_scaled_and_exposed_gradients_reach_adamw(grad_bf16):
+    """sgv_scale_grads and sgv_grad_buffer act on the fp32 gradient arena; with grad_bf16 the four big layers' gradients of the last
+    backward sit in the bf16 mirror.  Rule (include/sgvae.h): after either call the next AdamW reads exactly the arena's values, and
+    sgv_grad_norm / sgv_export_grad agree with them.  Batch 8: the big layers take the 256 x 256 kernel (the mirror is written).
+      zero scale: forward, backward, scale_grads(0), AdamW step 1 -> every parameter with a gradient is W0 (1 - lr wd), bitwise up to
+                  that product's rounding (Adam's moments are zero); the others stay W0
+      half:       grad_norm / grad(big) after scale_grads(0.5) are exactly half the unscaled ones, whether or not grad_norm ran before
+      buffer:     zeroing the arena through a torch view of grad_buffer() gives the zero-scale step's parameters bitwise"""
+    cfg = VAEConfig(32, 8, ENC, ENC[::-1], N, T, "MSE", True)
+    state = init_state(cfg, 7, reference_init=True)
+    uv = {k: v for k, v in state.items() if k.endswith("weight_u") or k.endswith("weight_v")}
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand((B, N, T), generator=g, device="cuda") * 1.4 - 0.7
+    dec = cfg.num_filter_dec
+    eps = [torch.randn((B, cfg.latent_dim), generator=g, device="cuda")] + \
+          [torch.randn((B, dec[i + 1], T), generator=g, device="cuda") for i in range(len(dec) - 2)]
+    lr = 1e-3
+    params = [k for k in state if k not in uv]
+
+    def engine():
+        eng = E.Engine(cfg, max_batch=B, compute_dtype="bf16")
+        eng.load_state(state)
+        if grad_bf16:
+            eng.set_option("grad_bf16", 1)
+        return eng
+
+    def fwd_bwd(eng):
+        eng.load_state(uv, partial=True)        # the same power-iteration start: a bitwise replay of the step
+        eng.set_input(x)
+        eng.set_eps([e.contiguous() for e in eps])
+        eng.forward(train=True)
+        eng.backward(ALPHA, BETA)
+
+    after = []
+    for how in ("scale", "buffer"):
+        eng = engine()
+        try:
+            fwd_bwd(eng)
+            if how == "scale":
+                eng.scale_grads(0.0)
+            else:
+                ptr, n = eng.grad_buffer()
+                torch.as_tensor(_DevArray(ptr, n), device="cuda").zero_()
+                torch.cuda.synchronize()
+            eng.adamw_step(lr)
+            sd = eng.state_dict()
+            has_grad = {k: eng.grad(k) is not None for k in params}
+            after.append({k: sd[k] for k in params})
+            if how == "scale":
+                bad = []
+                for k in params:
+                    w0 = state[k].astype(np.float32)
+                    want = w0 * np.float32(1.0 - lr * 0.01) if has_grad[k] else w0
+                    # fp32 rounding of p (1 - lr wd) however the kernel orders it: one ulp of the result
+                    if not np.all(np.abs(sd[k] - want) <= np.spacing(np.abs(want))):
+                        bad.append((k, float(np.abs(sd[k] - want).max())))
+                assert not bad, bad
+                # half: the same step again (weights moved by the decay only), unscaled reference first
+                fwd_bwd(eng)
+                n1 = eng.grad_norm()
+                g1 = {k: eng.grad(k) for k in BIG[:4]}
+                eng.scale_grads(0.5)
+                n2 = eng.grad_norm()
+                for k in BIG[:4]:
+                    assert np.array_equal(eng.grad(k), 0.5 * g1[k]), k
+                assert abs(n2 - 0.5 * n1) <= 1e-12 * n1, (n1, n2)
+                fwd_bwd(eng)                        # no grad_norm between backward and the scale
+                eng.scale_grads(0.5)
+                n3 = eng.grad_norm()
+                for k in BIG[:4]:
+                    assert np.array_equal(eng.grad(k), 0.5 * g1[k]), k
+                assert abs(n3 - 0.5 * n1) <= 1e-12 * n1, (n1, n3)
+        finally:
+            eng.close()
+    for k in params:
+        assert np.array_equal(after[0][k], after[1][k]), k
 
 
 @pytest.mark.parametrize("payload", ["f32", "bf16"])

@@ -452,6 +452,25 @@ def test_gemm_tn256_bf16_output(case):
     assert bool((out[n:] == -7.0).all())
 
 
+def test_gemm_tn256_bf16_output_refused_is_an_error():
+    """A bf16-output launch the 256 x 256 launcher refuses (here: `out` 8 bytes past a 16-byte boundary) is an error, and nothing is
+    written: no other kernel has a bf16 epilogue, and one storing fp32 would cover twice the bf16 region.  The buffer is 4 nw + 64
+    bytes, so that even an fp32 store of the whole result from the offset stays inside it."""
+    import torch
+    lib = E.load_library()
+    M, N1, N2, taps, Tlen, _ = TN256_CASES[0]
+    rng = np.random.default_rng(31)
+    ddY = _dev(_bf16_round(rng.standard_normal((M, N1)).astype(np.float32)), 1)
+    dX = _dev(_bf16_round(rng.standard_normal((M, N2)).astype(np.float32)), 1)
+    nw = taps * N1 * N2
+    buf = torch.full((4 * nw + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    rc = lib.sgv_test_gemm_tn(1, ddY.data_ptr(), dX.data_ptr(), buf.data_ptr() + 8, M, N1, N2, taps, Tlen, 1, 6, None)
+    torch.cuda.synchronize()
+    assert rc != 0
+    assert bool((buf == 0xA5).all()), int((buf != 0xA5).sum())
+
+
 @pytest.mark.parametrize("case", [TN256_CASES[0], TN256_CASES[2], TN256_CASES[3], TN256_CASES[4], TN256_CASES[7], (3200, 2560, 2560, 5, 200, 1)])
 @pytest.mark.parametrize("occupied", [0, 48])
 def test_gemm_tn256_work_stealing(case, occupied):

@@ -103,6 +103,9 @@ struct StateEntry {
 
 struct TimerRec { hipEvent_t a, b; int tag; };
 
+constexpr double DW_SIDE_MAX_GF = 250.0;   // weight-gradient GEMMs up to this size go to the side stream (sgv_engine::side)
+constexpr long CONVGN_MAXK = 4096;         // widest K * taps of a fused Conv -> GroupNorm -> GELU stage (sgv_engine::use_convgn)
+
 struct sgv_engine {
     sgv_config cfg;
     hipStream_t stream = nullptr;
@@ -188,7 +191,6 @@ struct sgv_engine {
     // bf16 wire format: the conv-weight AdamW reads a packed bucket straight from the averaged bf16 copy (no unpack pass; the fp32
     // arena keeps this rank's own gradients); only the few weights of a bucket that the flat pass updates (Linear heads:
     // bucket_flat_w) are unpacked.  bucket_packed[b]: bit 0 = conv-weight part still packed, bit 1 = flat part still packed.
-    int lp_direct = getenv("SGV_LP_DIRECT") ? atoi(getenv("SGV_LP_DIRECT")) : 1;
     std::vector<std::vector<std::pair<size_t, size_t>>> bucket_flat_w;
     float* partial_tn = nullptr; size_t partial_tn_floats = 0;
     std::vector<hipEvent_t> ev_pool; size_t ev_next = 0;
@@ -228,7 +230,7 @@ struct sgv_engine {
     float *last = nullptr, *d_last = nullptr, *zlat = nullptr, *d_z = nullptr;
     int batch = 0;
     bool have_fwd = false, fwd_train = false, write_xhat = true, copies_fresh = false;
-    int deterministic = getenv("SGV_DETERMINISTIC") ? atoi(getenv("SGV_DETERMINISTIC")) : 1;   // 1: no float-atomic accumulation anywhere in the step; option "deterministic"
+    int deterministic = 1;             // 1: no float-atomic accumulation anywhere in the step; option "deterministic"
     float* gn_part = nullptr; size_t gn_part_floats = 0;   // per-(tile, wave) GroupNorm partial sums of the 256x256 GEMM epilogue
     // deterministic reductions: block partials that nobody needs before the optimizer (GroupNorm affine / bias gradients,
     // <G,W_eff>) stay in this arena until the bucket they belong to is released, then two table-driven passes sum them
@@ -242,9 +244,9 @@ struct sgv_engine {
     int* tn_sched = nullptr;           // 8 x 520 ints: work-stealing state of the 256 x 256 weight-gradient launches issued while coll_inflight
     unsigned tn_sched_next = 0;
     int use_lanes = getenv("SGV_LANES") ? atoi(getenv("SGV_LANES")) : 1;
-    // small Conv1d -> GroupNorm -> GELU stages in one launch (convgn.hip); SGV_CONVGN=0 restores GEMM + combine + GroupNorm kernels
+    // small Conv1d -> GroupNorm -> GELU stages in one launch (convgn.hip, K * taps <= CONVGN_MAXK); SGV_CONVGN=0 restores GEMM +
+    // combine + GroupNorm kernels
     int use_convgn = getenv("SGV_CONVGN") ? atoi(getenv("SGV_CONVGN")) : 1;
-    long convgn_maxk = getenv("SGV_CONVGN_MAXK") ? atol(getenv("SGV_CONVGN_MAXK")) : 4096;
     float* red = nullptr; size_t red_floats = 0;
     std::vector<FinDot> fin_dots; std::vector<FinAffine> fin_affine;
     int dot_counts[512];
@@ -1081,8 +1083,7 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
     // side stream: dY and X are final once the kernels enqueued so far on the main stream have run; nothing on the
     // main stream reads G before join_side().  (Kernel-timing passes keep everything on one stream.)
     // only the small launches go to the side stream: big GEMMs fill every CU on their own and co-running them costs L2
-    static const double side_max_gf = getenv("SGV_DW_SIDE_MAXGF") ? atof(getenv("SGV_DW_SIDE_MAXGF")) : 250.0;
-    const bool side = e->use_side && !e->timing && 2.0e-9 * p.M * p.N1 * p.N2 * p.taps <= side_max_gf;
+    const bool side = e->use_side && !e->timing && 2.0e-9 * p.M * p.N1 * p.N2 * p.taps <= DW_SIDE_MAX_GF;
     hipStream_t st = e->stream;
     float* slabs = e->partial;
     if (side) {
@@ -1105,7 +1106,7 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
             q.A = (const char*)dy.p + (size_t)c * rows * e->esz;
             q.out = G + (size_t)c * rows * l.cin;
             if (direct) { q.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw + (size_t)c * rows * l.cin); q.out_bf16 = 1; }
-            if (e->coll_inflight && e->tn_sched && !(getenv("SGV_TN256_STEAL") && atoi(getenv("SGV_TN256_STEAL")) == 0)) q.sched = e->tn_sched + 520 * (e->tn_sched_next++ & 7);
+            if (e->coll_inflight && e->tn_sched) q.sched = e->tn_sched + 520 * (e->tn_sched_next++ & 7);
             if (launch_gemm_tn(e->dt, q, st)) return fail(SGV_ERR_ARG, "gemm_tn launch failed for %s (rows %d..%d)", l.prefix.c_str(), c * rows, (c + 1) * rows);
             if (e->dw_chunk_hook && e->dw_chunk_hook(c, e->dw_chunks, c * rows, (c + 1) * rows)) return fail(SGV_ERR_HIP, "weight-gradient chunk exchange failed for %s", l.prefix.c_str());
         }
@@ -1117,8 +1118,7 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
         p.splitk = 1; p.out = G;
         // grad_bf16: the 256 x 256 kernel rounds its accumulators to bf16 on the way out; the AdamW pass reads them there
         // a resident collective may keep some of the persistent kernel's workgroups off the chip: the work-stealing form (gemm256tn.hip)
-        static const int steal_on = getenv("SGV_TN256_STEAL") ? atoi(getenv("SGV_TN256_STEAL")) : 1;
-        if (steal_on && e->coll_inflight && e->tn_sched) p.sched = e->tn_sched + 520 * (e->tn_sched_next++ & 7);
+        if (e->coll_inflight && e->tn_sched) p.sched = e->tn_sched + 520 * (e->tn_sched_next++ & 7);
         const bool opt_lp = l.lp && grad_lp_active(e), wire_lp = l.lp && !opt_lp && wire_lp_active(e);
         GemmTN plp = p;
         plp.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw); plp.out_bf16 = 1;
@@ -1182,7 +1182,7 @@ static int block_fwd(sgv_engine* e, Block& b, const Tensor& in, int B) {
             ew_act(e->dt, 0, p, e->stream);
             cin = S.pre;
         }
-        if (S.gn >= 0 && S.act == 1 && e->use_convgn && e->dt == SGV_DTYPE_BF16 && !S.y.f32 && (long)L.cin * L.k <= e->convgn_maxk) {
+        if (S.gn >= 0 && S.act == 1 && e->use_convgn && e->dt == SGV_DTYPE_BF16 && !S.y.f32 && (long)L.cin * L.k <= CONVGN_MAXK) {
             // one workgroup per (group, sample): convolution, statistics, normalise + GELU (+ residual) in one launch
             const GNLayer& g = e->gns[S.gn];
             ConvGN q; memset(&q, 0, sizeof(q));
@@ -1226,7 +1226,7 @@ static int block_fwd(sgv_engine* e, Block& b, const Tensor& in, int B) {
 // queued), 0 when the shapes are not taken, < 0 on error.
 static int fused_dx_gn_bwd(sgv_engine* e, const Layer& L, const Tensor& dY, const Tensor* addend, Stage& P, int B, long M,
                            const Tensor* premul = nullptr, float rscale = 1.f, const Tensor* da_out = nullptr) {
-    if (!e->use_convgn || e->dt != SGV_DTYPE_BF16 || !L.need_wct || (long)L.cout * L.k > e->convgn_maxk) return 0;
+    if (!e->use_convgn || e->dt != SGV_DTYPE_BF16 || !L.need_wct || (long)L.cout * L.k > CONVGN_MAXK) return 0;
     if (P.gn < 0 || P.act != 1 || P.y.f32) return 0;
     const Layer& LP = e->layers[P.layer];
     const GNLayer& g = e->gns[P.gn];
@@ -1362,10 +1362,8 @@ const char* sgv_last_error(void) { return g_err; }
 // Auxiliary streams.  The HIP runtime maps streams onto a handful of hardware queues PER PRIORITY LEVEL (GPU_MAX_HW_QUEUES = 4),
 // round-robin in creation order, and two streams on one queue run their kernels strictly one after the other: a kernel trace showed
 // the second compute lane and the collective's stream sharing the main stream's queue (no overlap at all) depending on how many
-// streams the process had created before.  A stream of another priority level comes from another queue pool, so it can never land
-// on the main stream's queue: level -1 = high, 0 = normal (the main stream's), 1 = low; SGV_PRIO_* override the defaults.
-constexpr int SGV_PRIO_LANE_DEFAULT = 0, SGV_PRIO_SIDE_DEFAULT = 0, SGV_PRIO_OPT_DEFAULT = 0;
-static hipError_t make_stream(hipStream_t* s, const char* env, int level);
+// streams the process had created before.  Every auxiliary stream has the main stream's (normal) priority and is probed instead:
+// streams of another priority level come from another queue pool, but measured no faster.
 // ---- which hardware queue did a new stream land on? ----
 // Not visible through the API, but observable: a kernel on stream b cannot finish while a kernel on stream a spins if both sit
 // on one queue.  probe_spin_kernel waits on the constant-rate clock for a bounded time (always exits), probe_nop_kernel is empty.
@@ -1413,26 +1411,25 @@ static bool streams_overlap(hipStream_t a, hipStream_t b) {
 // queue (round-robin in a fresh process; in a process that has created and destroyed many streams the main stream's queue can be the
 // emptiest for many creations in a row), so the rejected candidates stay alive until a keeper is found -- every reject loads the
 // queue it sits on and steers the next candidate elsewhere -- and up to 32 candidates are tried (0.3 ms each per stream to avoid).
-// SGV_STREAM_PROBE=0: take the first.  If every candidate collides the last one is kept.
-static hipError_t make_aux_stream(hipStream_t* out, const char* env, int level, std::initializer_list<hipStream_t> avoid) {
-    static const int probe = getenv("SGV_STREAM_PROBE") ? atoi(getenv("SGV_STREAM_PROBE")) : 1;
+// If every candidate collides the last one is kept.
+static hipError_t make_aux_stream(hipStream_t* out, const char* label, std::initializer_list<hipStream_t> avoid) {
     std::vector<hipStream_t> rejected;
     hipStream_t s = nullptr;
     hipError_t rc = hipSuccess;
     constexpr int kAttempts = 32;
     for (int attempt = 0; attempt < kAttempts; ++attempt) {
         s = nullptr;
-        rc = make_stream(&s, env, level);
-        if (rc != hipSuccess || !probe) break;
+        rc = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (rc != hipSuccess) break;
         bool ok = true;
         for (hipStream_t a : avoid) if (a != s && !streams_overlap(a, s)) { ok = false; break; }      // a == nullptr is the null stream: probed too
-        if (getenv("SGV_STREAM_LOG")) fprintf(stderr, "[sgvae] %s: candidate %d %s\n", env, attempt, ok ? "kept" : "shares a hardware queue with a stream it must not, rejected");
+        if (getenv("SGV_STREAM_LOG")) fprintf(stderr, "[sgvae] %s stream: candidate %d %s\n", label, attempt, ok ? "kept" : "shares a hardware queue with a stream it must not, rejected");
         if (ok) break;
         if (attempt == kAttempts - 1) {
             // kept all the same: the engine stays correct, but this stream's kernels now run between the other stream's instead of
             // beside them (no lane / optimizer / communication overlap) -- say so once, the bench line reports it as well
-            fprintf(stderr, "[sgvae] warning: %s: all %d candidate streams share a hardware queue with a stream they must avoid "
-                            "(GPU_MAX_HW_QUEUES too small for this process?); overlap on this stream is lost\n", env, kAttempts);
+            fprintf(stderr, "[sgvae] warning: %s stream: all %d candidate streams share a hardware queue with a stream they must avoid "
+                            "(GPU_MAX_HW_QUEUES too small for this process?); overlap on this stream is lost\n", label, kAttempts);
             break;
         }
         rejected.push_back(s);
@@ -1443,24 +1440,24 @@ static hipError_t make_aux_stream(hipStream_t* out, const char* env, int level, 
 }
 static hipStream_t ensure_opt(sgv_engine* e) {
     // never on the main stream's queue: an AdamW launch that waits for a collective there would hold back every kernel behind it
-    if (!e->opt && make_aux_stream(&e->opt, "SGV_PRIO_OPT", SGV_PRIO_OPT_DEFAULT, {e->stream, e->side, e->lane2}) != hipSuccess) e->opt = nullptr;
+    if (!e->opt && make_aux_stream(&e->opt, "optimizer", {e->stream, e->side, e->lane2}) != hipSuccess) e->opt = nullptr;
     return e->opt;
 }
 // a communication stream for sgv_set_rccl that is guaranteed not to sit on the main stream's hardware queue (a collective there
 // would run strictly between the main stream's kernels instead of beside them)
 static hipStream_t ensure_comm_own(sgv_engine* e) {
-    if (!e->comm_own && make_aux_stream(&e->comm_own, "SGV_PRIO_COMM", 0, {e->stream, e->side, e->lane2}) != hipSuccess) e->comm_own = nullptr;
+    if (!e->comm_own && make_aux_stream(&e->comm_own, "communication", {e->stream, e->side, e->lane2}) != hipSuccess) e->comm_own = nullptr;
     return e->comm_own;
 }
 static hipStream_t ensure_wire(sgv_engine* e) {
-    if (!e->wire && make_aux_stream(&e->wire, "SGV_PRIO_WIRE", SGV_PRIO_OPT_DEFAULT, {e->stream, e->side}) != hipSuccess) e->wire = nullptr;
+    if (!e->wire && make_aux_stream(&e->wire, "wire", {e->stream, e->side}) != hipSuccess) e->wire = nullptr;
     return e->wire;
 }
 // ---- prefetched augmentation (see the members) ----
 static constexpr size_t AUG_CTL = 8192;
 static bool ensure_aug(sgv_engine* e) {
     if (e->aug_stream) return true;
-    if (make_aux_stream(&e->aug_stream, "SGV_PRIO_AUG", 0, {e->stream, e->side, e->lane2}) != hipSuccess) { e->aug_stream = nullptr; return false; }
+    if (make_aux_stream(&e->aug_stream, "augmentation", {e->stream, e->side, e->lane2}) != hipSuccess) { e->aug_stream = nullptr; return false; }
     bool ok = hipEventCreateWithFlags(&e->aug_done, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&e->aug_gate, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; i < 2 && ok; ++i) ok = hipEventCreateWithFlags(&e->x_free[i], hipEventDisableTiming) == hipSuccess;
@@ -1473,7 +1470,7 @@ static bool ensure_aug(sgv_engine* e) {
 // (fused Conv+GroupNorm stages, 128-row GEMMs) off the chip until it ends (AdamW slices).
 static int aug_fire(sgv_engine* e) {
     if (!e->aug_staged || e->aug_fired) return SGV_OK;
-    static const int per = getenv("SGV_AUG_SLICE") ? std::max(1, atoi(getenv("SGV_AUG_SLICE"))) : 2;
+    constexpr int per = 2;             // samples per launch
     const int nb = 1 - e->x_cur, batch = e->aug_next_batch;
     char* scratch = e->aug_ctl;
     int* d_idx = (int*)scratch; int* d_mix = d_idx + batch;
@@ -1500,13 +1497,6 @@ static int aug_join(sgv_engine* e) {
 static void x_release(sgv_engine* e) {
     if (!e->aug_stream) return;
     if (hipEventRecord(e->x_free[e->x_cur], e->stream) == hipSuccess) e->x_free_set[e->x_cur] = true;
-}
-static hipError_t make_stream(hipStream_t* s, const char* env, int level) {
-    if (getenv(env)) level = atoi(getenv(env));
-    if (level == 0) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    return hipStreamCreateWithPriority(s, hipStreamNonBlocking, level < 0 ? greatest : least);
 }
 int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     if (!cfg || !out) return fail(SGV_ERR_ARG, "null argument");
@@ -1578,7 +1568,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     e->gn_part_floats = 0;
     for (auto& l : e->layers) if (l.used && l.op != OP_LINEAR) e->gn_part_floats = std::max(e->gn_part_floats, gemm_nt256_part_floats((int)M, l.cout, 1));
     ALLOC(e->gn_part, e->gn_part_floats * 4);
-    if (e->use_lanes && make_aux_stream(&e->lane2, "SGV_PRIO_LANE", SGV_PRIO_LANE_DEFAULT, {e->stream}) == hipSuccess &&
+    if (e->use_lanes && make_aux_stream(&e->lane2, "lane", {e->stream}) == hipSuccess &&
         hipEventCreateWithFlags(&e->lane_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&e->lane_join, hipEventDisableTiming) == hipSuccess &&
         hipEventCreateWithFlags(&e->tail_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&e->tail_join, hipEventDisableTiming) == hipSuccess) {
         ALLOC(e->partial2, e->partial_floats * 4);
@@ -1594,7 +1584,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
         e->red_floats = nr;
     }
     ALLOC(e->red, e->red_floats * 4);
-    if (make_aux_stream(&e->side, "SGV_PRIO_SIDE", SGV_PRIO_SIDE_DEFAULT, {e->stream, e->lane2}) != hipSuccess) { e->side = nullptr; e->use_side = false; }
+    if (make_aux_stream(&e->side, "side", {e->stream, e->lane2}) != hipSuccess) { e->side = nullptr; e->use_side = false; }
     // the optimizer and wire streams of the data-parallel step are created on first use (ensure_opt / ensure_wire): every stream a
     // process creates shifts the runtime's stream -> hardware-queue assignment of the ones created after it
     if (getenv("SGV_DW_SIDE")) e->use_side = atoi(getenv("SGV_DW_SIDE")) != 0 && e->side != nullptr;
@@ -1919,7 +1909,6 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix) {
         ew_linear_expand_fwd(e->dt, e->zlat, e->params + l.w, e->params + l.b, e->sn_sigma + 2 * l.sn + 1, e->sbuf.p, B, l.cin, l.cout, e->stream);
     }
     CHK(block_fwd(e, e->decS, e->sbuf, B));
-    static const int hoist = getenv("SGV_LANE_HOIST") ? atoi(getenv("SGV_LANE_HOIST")) : 1;
     for (int i = 0; i < n_st; ++i) {
         const bool post = i < n_st - 1;
         auto xs_lift = [&]() -> int {       // xs lift of the posterior branch: depends on the encoder only
@@ -1928,7 +1917,7 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix) {
             ew_linear_expand_fwd(e->dt, e->xs_raw[lvl], e->params + l.w, e->params + l.b, e->sn_sigma + 2 * l.sn + 1, e->xl[i].p, B, l.cin, l.cout, e->stream);
             return block_fwd(e, e->decX[i], e->xl[i], B);
         };
-        if (post && hoist) {
+        if (post) {
             // hoisted onto the second lane beside this stage's up-sampling and residual blocks: the lane's chain (lift, condition_xz) was
             // twice as long as the prior branch it ran beside, and the main stream waited for it at the join
             Lane2 lane(e);
@@ -1940,7 +1929,6 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix) {
         const int C = e->dec[i + 1];
         {   // posterior branch (xs lift -> condition_xz) on the second lane, beside the prior branch below
             Lane2 lane(e);
-            if (!hoist) CHK(xs_lift());
             CHK(block_fwd(e, e->decQ1[i], e->cat[i], B));
             CHK(block_fwd(e, e->decQ2[i], e->decQ1[i].st.back().a, B));
         }
@@ -2328,8 +2316,7 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
     if (!e->have_fwd || !e->fwd_train) return fail(SGV_ERR_STATE, "sgv_backward needs a preceding sgv_forward(train=1)");
     e->lp_fp32 = false;                  // grad_bf16: this backward's gradients of the mirrored layers go to the mirror again
     const bool fuse = fuse_lr >= 0.f;
-    static const int early_on = getenv("SGV_EARLY_ADAM") ? atoi(getenv("SGV_EARLY_ADAM")) : 1;
-    const bool early = early_on && fuse && !e->cb && !e->comm && e->side && e->use_side && !e->timing;
+    const bool early = fuse && !e->cb && !e->comm && e->side && e->use_side && !e->timing;
     // engine-issued collectives with the learning rate in hand (sgv_backward_step on a registered communicator): every weight
     // bucket's <G,W> slots are averaged with the bucket and its conv-weight AdamW starts on the optimizer stream as soon as both
     // have landed, under the rest of backward -- the data-parallel mirror of `early`
@@ -2440,7 +2427,6 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
         fire();
     }
     // ---- decoder stages ----
-    static const int hoist_b = getenv("SGV_LANE_HOIST") ? atoi(getenv("SGV_LANE_HOIST")) : 1;
     for (int i = n_st - 1; i >= 0; --i) {
         const int C = e->dec[i + 1];
         if (i < n_st - 1) {
@@ -2462,14 +2448,13 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
                 bool q_ready = false;      // condition_xz: the output convolution's input gradient went straight into the residual block's GroupNorm backward
                 CHK(block_bwd(e, e->decQ2[i], e->decQ1[i].st.back().a, e->gq[i], &e->d_qres[i], B, nullptr, &e->decQ1[i].st.back(), &q_ready, false, 0.1f));
                 CHK(block_bwd(e, e->decQ1[i], e->cat[i], e->d_qres[i], &e->dcat[i], B, nullptr, nullptr, nullptr, q_ready));
-                if (!hoist_b) CHK(xs_lift_bwd());
             }
             bool p_ready = false;
             CHK(block_bwd(e, e->decP2[i], e->decP1[i].st.back().a, e->gp[i], &e->d_pres[i], B, nullptr, &e->decP1[i].st.back(), &p_ready, false, 0.1f));
             CHK(block_bwd(e, e->decP1[i], e->dec_out[i], e->d_pres[i], &e->d_outp[i], B, nullptr, nullptr, nullptr, p_ready));
             lane2_join(e);
             ew_add3(e->dt, e->d_outp[i].p, e->d_outp[i].ld, e->dzs[i + 1].p, e->dzs[i + 1].ld, d_oq.p, d_oq.ld, e->d_out[i].p, e->d_out[i].ld, (int)M, C, e->stream);
-            if (hoist_b) {
+            {
                 // the xs lift's backward needs d_xs only: deferred onto the lane beside the residual / up-sampling blocks' backward
                 // below (the mirror of the forward hoist); joined before the stage's bucket is released
                 Lane2 lane(e);
@@ -2478,7 +2463,7 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
         }
         CHK(block_bwd(e, e->decD[i], e->decU[i].st.back().a, e->d_out[i], &e->d_u[i], B));
         CHK(block_bwd(e, e->decU[i], e->zs[i], e->d_u[i], &e->dzs[i], B));
-        if (i < n_st - 1 && hoist_b) lane2_join(e);
+        if (i < n_st - 1) lane2_join(e);
         if (i == 0) {
             CHK(block_bwd(e, e->decS, e->sbuf, e->dzs[0], &e->d_sbuf, B));
             const Layer& l = e->layers[e->start_lin];
@@ -2545,8 +2530,7 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
                 for (int c = 0; c < n_c; ++c) {
                     const size_t off = L0.gw + (size_t)c * rows * L0.cin, cnt = (size_t)rows * L0.cin;
                     HIPCHK(hipStreamWaitEvent(e->stream, chunk_done[c], 0));
-                    if (lp && !e->lp_direct) ew_unpack_bf16((const char*)e->grads_lp + 2 * off, e->grads + off, (long)cnt, e->stream);
-                    CHK(adamw_tiles(e, fuse_lr, e->tile_off[last_b] + (c * rows / 64) * ct6, e->tile_off[last_b] + ((c + 1) * rows / 64) * ct6, e->stream, lp && e->lp_direct));
+                    CHK(adamw_tiles(e, fuse_lr, e->tile_off[last_b] + (c * rows / 64) * ct6, e->tile_off[last_b] + ((c + 1) * rows / 64) * ct6, e->stream, lp));
                 }
                 e->bucket_updated[last_b] = 1;
             }
@@ -2634,8 +2618,8 @@ static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, 
     // the main stream whose workgroup needs most of a CU's LDS (the 128-row GEMM tails, the fused Conv+GroupNorm stages) is not
     // placed until the launch ends -- a kernel trace showed a 60 us tail taking 816 us beside a 1.3 ms AdamW launch.  At a launch
     // boundary the chip drains, and the waiting workgroups get their CUs.
-    static const int slice_env = getenv("SGV_ADAM_SLICE") ? atoi(getenv("SGV_ADAM_SLICE")) : 3072;      // re-tuned on the final build: 2048 / 2560 / 3072 / 3584 = 11.16 / 11.11 / 11.10 / 11.11 ms
-    const int slice = (st != e->stream && slice_env > 0) ? slice_env : t1 - t0;
+    constexpr int ADAM_SLICE = 3072;    // re-tuned on the final build: 2048 / 2560 / 3072 / 3584 = 11.16 / 11.11 / 11.10 / 11.11 ms
+    const int slice = st != e->stream ? ADAM_SLICE : t1 - t0;
     for (int a = t0; a < t1; a += slice) {
         const int b = std::min(t1, a + slice);
         if (opt_adamw_sn(e->adam_dev, e->sn_dev, e->items_adam_2d + a, b - a, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + e->n_items_adam_flat + a, e->dt, st,
@@ -2643,10 +2627,6 @@ static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, 
             return fail(SGV_ERR_HIP, "adamw launch failed");
     }
     return 0;
-}
-static void unpack_bucket(sgv_engine* e, int b, hipStream_t st) {
-    ew_unpack_bf16((const char*)e->grads_lp + 2 * e->buckets[b].first, e->grads + e->buckets[b].first, (long)e->buckets[b].second, st);
-    e->bucket_packed[b] = 0;
 }
 // what the flat pass reads of a packed weight bucket (Linear heads)
 static void unpack_bucket_flat(sgv_engine* e, int b, hipStream_t st) {
@@ -2662,13 +2642,10 @@ static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, in
             HIPCHK(hipStreamWaitEvent(st, e->bucket_done[b], 0));
             e->bucket_pending[b] = 0;
         }
-    // the averaged bf16 wire copy: the tiled pass reads it in place (lp_direct), the flat pass gets its few weights unpacked
+    // the averaged bf16 wire copy: the tiled pass reads it in place, the flat pass gets its few weights unpacked
     const int np = (int)e->bucket_packed.size();
-    for (int b = bucket_lo; b < bucket_hi && b < np; ++b) {
-        if (!e->bucket_packed[b]) continue;
-        if (!e->lp_direct) unpack_bucket(e, b, st);
-        else if ((which & 2) && (e->bucket_packed[b] & 2)) unpack_bucket_flat(e, b, st);
-    }
+    for (int b = bucket_lo; b < bucket_hi && b < np; ++b)
+        if ((which & 2) && (e->bucket_packed[b] & 2)) unpack_bucket_flat(e, b, st);
     // biases, GroupNorm affine and the Linear heads: flat pass.  Conv weights: tiled pass that also writes both
     // compute copies and W_new^T u for the next forward's power iteration; buckets updated ahead (adamw_bucket_async) are skipped.
     const AdamCoef c = adam_coef(e);
@@ -2695,8 +2672,7 @@ static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, in
 static int adamw_bucket_async(sgv_engine* e, float lr, int b, hipStream_t st) {
     CHK(adamw_begin(e));
     const bool packed = b < (int)e->bucket_packed.size() && e->bucket_packed[b];
-    if (packed && !e->lp_direct) unpack_bucket(e, b, st);
-    const bool from_lp = packed && e->lp_direct && (e->bucket_packed[b] & 1);
+    const bool from_lp = packed && (e->bucket_packed[b] & 1);
     CHK(adamw_tiles(e, lr, e->tile_off[b], e->tile_off[b + 1], st, from_lp));
     if (from_lp) e->bucket_packed[b] &= ~1;
     e->bucket_updated[b] = 1;

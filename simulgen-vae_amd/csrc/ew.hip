@@ -1115,10 +1115,9 @@ int ew_gn_bwd_apply_act(int dtype, int act, GNParams p, hipStream_t s) {
     }
     return 0;
 }
-// one launch per direction for small slabs (SGV_GN_FUSED=0 restores the multi-kernel path for A/B runs)
+// one launch per direction for small slabs; the multi-kernel path takes the shapes the fused kernels refuse
 static bool gn_fused_ok(const GNParams& p) {
-    static const int on = getenv("SGV_GN_FUSED") ? atoi(getenv("SGV_GN_FUSED")) : 1;
-    if (!on || p.Cg % 8 || p.Cg / 8 > 256 || p.G > SGV_GN_MAX_GROUPS) return false;
+    if (p.Cg % 8 || p.Cg / 8 > 256 || p.G > SGV_GN_MAX_GROUPS) return false;
     int cv = 1;
     while (cv < p.Cg / 8) cv <<= 1;
     return (p.T + 256 / cv - 1) / (256 / cv) <= GN_FUSED_ITERS;      // rows per thread
@@ -1129,8 +1128,7 @@ static int gn_fused_cv(const GNParams& p) {
     return cv;
 }
 static bool gn_fused_bwd_ok(const GNParams& p) {
-    static const int on = getenv("SGV_GN_FUSED") ? atoi(getenv("SGV_GN_FUSED")) : 1;
-    if (!on || p.Cg % 8 || p.G > SGV_GN_MAX_GROUPS) return false;
+    if (p.Cg % 8 || p.G > SGV_GN_MAX_GROUPS) return false;
     const int cv = gn_fused_cv(p);
     return cv <= GN_BWD_MAX_CV && (p.T + GN_BWD_THREADS / cv - 1) / (GN_BWD_THREADS / cv) <= GN_BWD_ITERS;
 }

@@ -17,9 +17,7 @@
 
 // minimum waves per SIMD asked of the register allocator for the GEMM kernels: 3 (168 VGPRs; a dozen
 // prologue/epilogue spills) measured 3-6 % faster end-to-end than the uncapped 220-VGPR build
-#ifndef SGV_GEMM_MIN_WAVES
-#define SGV_GEMM_MIN_WAVES 3
-#endif
+constexpr int GEMM_MIN_WAVES = 3;
 
 // zero a 16-byte chunk with an integer mask (0 or ~0): a plain AND cannot be turned into a memory select
 // XCD-aware block -> work-item map.  Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an
@@ -62,7 +60,7 @@ __device__ __forceinline__ uint4 bload16(__amdgpu_buffer_rsrc_t r, uint32_t off)
 // NW: narrow form for N <= 64 (the conditioner's 16-64 channel layers on a million rows): 128 x 64 tile, the four waves stacked
 //     along M (32 rows x 64 columns each) -- half the MFMAs, weight-tile loads, fragment reads and epilogue work of the square tile
 template <typename T, int KCH, bool C2D = false, bool NW = false>
-__global__ __launch_bounds__(256, SGV_GEMM_MIN_WAVES) void gemm_nt_kernel(const GemmNT p) {
+__global__ __launch_bounds__(256, GEMM_MIN_WAVES) void gemm_nt_kernel(const GemmNT p) {
     constexpr int EPC = ElemTraits<T>::EPC;
     constexpr int BK = KCH * EPC;
     constexpr bool IS_BF16 = sizeof(T) == 2;
@@ -752,7 +750,7 @@ __global__ __launch_bounds__(256) void gemm_nt_reduce_kernel(const GemmNT p) {
 // C2D: the X operand is a virtual im2col matrix (GemmTN::cv_*): a thread's 16-byte column chunk belongs to one window
 // offset (kh, kw), its rows are output pixels whose (oh, ow) is carried from stage to stage
 template <typename T, bool USE_TR, bool C2D = false>
-__global__ __launch_bounds__(256, SGV_GEMM_MIN_WAVES) void gemm_tn_kernel(const GemmTN p) {
+__global__ __launch_bounds__(256, GEMM_MIN_WAVES) void gemm_tn_kernel(const GemmTN p) {
     constexpr int EPC = ElemTraits<T>::EPC;
     constexpr bool IS_BF16 = sizeof(T) == 2;
     constexpr int KR = IS_BF16 ? 32 : 16;      // reduction rows (m) per step
@@ -1304,12 +1302,11 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // The 128x256 LDS-DMA kernel is used for bf16 GEMMs with N >= 256 and >= 64 K-steps (short-K shapes are
 // faster on the 128x128 kernel: 3 blocks/CU hide the prologue/epilogue).  fp32 (validation mode) stays on
 // the 128x128 kernels: the fp32 build of the wide kernel showed an intermittent, unexplained corruption of a
-// few accumulator rows with 5-tap convs (tests/micro/nt_sweep.py), while the bf16 build is clean under
-// tests/test_kernels_gpu.py::test_gemm_nt_wide_stress.
+// few accumulator rows with 5-tap convs (a K-sweep micro-bench since removed; see git history), while the bf16 build is
+// clean under tests/test_kernels_gpu.py::test_gemm_nt_wide_stress.
+constexpr long WIDE_MIN_STEPS = 64;
 static bool gemm_nt_is_wide(int dtype, int N, long steps) {
-    static const int use_wide = getenv("SGV_GEMM_WIDE") ? atoi(getenv("SGV_GEMM_WIDE")) : 1;
-    static const int min_steps = getenv("SGV_WIDE_MIN_STEPS") ? atoi(getenv("SGV_WIDE_MIN_STEPS")) : 64;
-    return use_wide && dtype == 1 && N >= 256 && steps >= min_steps;
+    return dtype == 1 && N >= 256 && steps >= WIDE_MIN_STEPS;
 }
 static int pick_splitk(long tiles, long steps, double slab_bytes_per_slice, int min_steps, double slots = 768.0) {
     int best = 1;
@@ -1326,8 +1323,7 @@ static int pick_splitk(long tiles, long steps, double slab_bytes_per_slice, int 
 }
 
 bool gemm_nt_can_fuse_stats(int dtype, int M, int N, int K, int taps, int Tlen, int Cg) {
-    static const int on = getenv("SGV_GEMM_STATS") ? atoi(getenv("SGV_GEMM_STATS")) : 1;
-    return on && dtype == 1 && Tlen >= 128 && Cg >= 128 && !gemm_nt_is_wide(dtype, N, (long)taps * cdiv(K, 32)) &&
+    return dtype == 1 && Tlen >= 128 && Cg >= 128 && !gemm_nt_is_wide(dtype, N, (long)taps * cdiv(K, 32)) &&
            gemm_nt_pick_splitk(M, N, K, taps, dtype) == 1;
 }
 bool gemm_nt_uses_wide(int dtype, int N, int K, int taps) {
@@ -1342,14 +1338,9 @@ int gemm_nt_pick_splitk(int M, int N, int K, int taps, int dtype) {
     return pick_splitk(tiles, total, (double)M * N * 4.0, 8);
 }
 
-// 128x256 tiles, two blocks per CU (gemm_tn_w2_kernel): the default for bf16 weight gradients with N2 >= 256; SGV_TN_W2=0
-// falls back to the 128x128 register-staged kernel (A/B runs), GemmTN::force_w2 selects it regardless of the env.
-static bool gemm_tn_w2_eligible(int dtype, int M, int N1, int N2, int Tlen) {
-    return dtype == 1 && N2 >= 256 && N1 >= 64 && Tlen >= 32 && M >= 256;
-}
+// 128x256 tiles, two blocks per CU (gemm_tn_w2_kernel): the default for bf16 weight gradients with N2 >= 256.
 bool gemm_tn_uses_w2(int dtype, int M, int N1, int N2, int Tlen) {
-    static const int use_w2 = getenv("SGV_TN_W2") ? atoi(getenv("SGV_TN_W2")) : 1;
-    return use_w2 && gemm_tn_w2_eligible(dtype, M, N1, N2, Tlen);
+    return dtype == 1 && N2 >= 256 && N1 >= 64 && Tlen >= 32 && M >= 256;
 }
 int gemm_tn_pick_splitk(int M, int N1, int N2, int taps, int dtype, int Tlen) {
     {   // the 256 x 256 kernel takes the product whole (its items fill the chip without slices)
@@ -1402,8 +1393,7 @@ int launch_gemm_nt(int dtype, const GemmNT& p, hipStream_t s) {
                       p.gn_Cg < 128 || p.gn_G < 1))
         return -1;                                   // only the bf16 128x128 epilogue accumulates statistics
     // N <= 64 (bf16, no statistics epilogue): the 128 x 64 form of the kernel
-    static const int narrow_on = getenv("SGV_GEMM_NARROW") ? atoi(getenv("SGV_GEMM_NARROW")) : 1;
-    const bool narrow = narrow_on && dtype == 1 && p.N <= 64 && !p.gn_sums;
+    const bool narrow = dtype == 1 && p.N <= 64 && !p.gn_sums;
     if (narrow) {
         dim3 grid(cdiv(Mr, 128) * p.splitk);
         if (c2d) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 4, true, true>), grid, dim3(256), 0, s, q);
@@ -1441,30 +1431,25 @@ int launch_gemm_nt(int dtype, const GemmNT& p, hipStream_t s) {
 // Schedule of gemm_tn_w2_kernel (returns the grid).  Persistent form: 512 blocks = two per CU walk an XCD-chunked item list cut
 // into patches of pt1 x pt2 tiles x all taps.  The ~64 items an XCD has in flight then read pt1 dY panels (256-byte rows) and
 // pt2 X panels (512-byte rows): pick the patch that minimises (pt1 + 2 pt2) / (pt1 pt2) with pt1 pt2 taps <= 64.
-// Measured (round 3, tests/micro/order_ab.sh, FETCH_SIZE per launch / time): 5120 x 5120 x 5 taps 2.04 -> 1.15 GB, 829 -> 814 us;
-// 2560 x 2560 x 5 taps 0.44 -> 0.19 GB, 212 -> 217 us; the one-tap 95 008-wide gradients do NOT gain (recon head 2.52 -> 2.79 GB,
-// 652 -> 719 us; first encoder layer 1.33 -> 1.30 GB, 657 -> 668 us): there the fetches are the 6.5 MB operand falling out of
-// the 4 MiB L2 (Infinity-Cache hits), not missed panel sharing.  So: persistent for multi-tap launches with at least four rounds
-// of items (SGV_TN_PERSIST=0 / 1 forces one item per block / the persistent walk everywhere).
+// Measured (round 3, FETCH_SIZE per launch / time; the A/B script is removed, see git history): 5120 x 5120 x 5 taps 2.04 -> 1.15 GB,
+// 829 -> 814 us; 2560 x 2560 x 5 taps 0.44 -> 0.19 GB, 212 -> 217 us; the one-tap 95 008-wide gradients do NOT gain (recon head
+// 2.52 -> 2.79 GB, 652 -> 719 us; first encoder layer 1.33 -> 1.30 GB, 657 -> 668 us): there the fetches are the 6.5 MB operand
+// falling out of the 4 MiB L2 (Infinity-Cache hits), not missed panel sharing.  So: persistent for multi-tap launches with at
+// least four rounds of items.
+constexpr int TN_W2_SLOTS = 512;
 static int tn_w2_schedule(GemmTN& q, int tiles_1, int tiles_2, int taps) {
-    static const int persist_env = getenv("SGV_TN_PERSIST") ? atoi(getenv("SGV_TN_PERSIST")) : -1;
-    const bool persist = q.force_w2 == 2 || (persist_env >= 0 ? persist_env != 0 : (taps > 1 && (long)tiles_1 * tiles_2 * taps * q.splitk >= 2048));
-    static const int f1 = getenv("SGV_TN_PT1") ? atoi(getenv("SGV_TN_PT1")) : 0;
-    static const int f2 = getenv("SGV_TN_PT2") ? atoi(getenv("SGV_TN_PT2")) : 0;
-    static const int slots = getenv("SGV_TN_SLOTS") ? atoi(getenv("SGV_TN_SLOTS")) : 512;
+    const bool persist = q.force_w2 == 2 || (taps > 1 && (long)tiles_1 * tiles_2 * taps * q.splitk >= 2048);
     const int nitems = tiles_1 * tiles_2 * taps * q.splitk;
     q.order = persist ? 1 : 0; q.pt1 = 1; q.pt2 = 1;
     if (!persist) return nitems;
-    const int cap = slots / 8;
+    const int cap = TN_W2_SLOTS / 8;
     double best = 1e30;
     for (int a = 1; a <= tiles_1 && a <= cap; ++a)
         for (int b = 1; b <= tiles_2 && a * b * taps <= cap; ++b) {
             const double c = (double)(a + 2 * b) / ((double)a * b);
             if (c < best - 1e-9) { best = c; q.pt1 = a; q.pt2 = b; }
         }
-    if (f1 > 0) q.pt1 = f1 < tiles_1 ? f1 : tiles_1;
-    if (f2 > 0) q.pt2 = f2 < tiles_2 ? f2 : tiles_2;
-    return nitems < slots ? nitems : slots;
+    return nitems < TN_W2_SLOTS ? nitems : TN_W2_SLOTS;
 }
 
 int launch_gemm_tn(int dtype, const GemmTN& p, hipStream_t s) {
@@ -1491,7 +1476,7 @@ int launch_gemm_tn(int dtype, const GemmTN& p, hipStream_t s) {
     }
     // a bf16 output exists only in the 256 x 256 kernel: the kernels below would store fp32 over a region half that size
     if (p.out_bf16) return -1;
-    if (c2d && p.use_tr && (gemm_tn_uses_w2(dtype, p.M, p.N1, p.N2, p.M) || (p.force_w2 && gemm_tn_w2_eligible(dtype, p.M, p.N1, p.N2, p.M)))) {
+    if (c2d && p.use_tr && gemm_tn_uses_w2(dtype, p.M, p.N1, p.N2, p.M)) {
         dim3 gridw(tn_w2_schedule(q, cdiv(p.N1, 128), cdiv(p.N2, 256), 1));
         hipLaunchKernelGGL(gemm_tn_w2_kernel<true>, gridw, dim3(256), 0, s, q);
         return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -1502,7 +1487,7 @@ int launch_gemm_tn(int dtype, const GemmTN& p, hipStream_t s) {
         else hipLaunchKernelGGL((gemm_tn_kernel<float, false, true>), grid, dim3(256), 0, s, q);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
-    if (p.use_tr && (gemm_tn_uses_w2(dtype, p.M, p.N1, p.N2, p.Tlen) || (p.force_w2 && gemm_tn_w2_eligible(dtype, p.M, p.N1, p.N2, p.Tlen)))) {
+    if (p.use_tr && gemm_tn_uses_w2(dtype, p.M, p.N1, p.N2, p.Tlen)) {
         dim3 gridw(tn_w2_schedule(q, cdiv(p.N1, 128), cdiv(p.N2, 256), p.taps));
         hipLaunchKernelGGL(gemm_tn_w2_kernel<false>, gridw, dim3(256), 0, s, q);
         return hipGetLastError() == hipSuccess ? 0 : -2;

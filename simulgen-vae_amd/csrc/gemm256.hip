@@ -36,32 +36,6 @@ typedef uint32_t t256_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t t256_u2 __attribute__((ext_vector_type(2)));
 constexpr uint32_t T256_OOB = 0x7FFFFFF0u;
 
-#ifndef T256_STAGGER
-#define T256_STAGGER 1       // 1: the two row halves of a workgroup run half a section out of phase (see T256_KTILE)
-#endif
-#ifdef T256_ABL_NOBAR
-#define T256_ABL_NOBAR_ 1
-#else
-#define T256_ABL_NOBAR_ 0
-#endif
-#ifndef T256_FINEWAIT
-#define T256_FINEWAIT 1
-#endif
-#ifndef T256_DELAY
-#define T256_DELAY 0         // start skew: workgroup slot j of an XCD sleeps j * T256_DELAY * 64 cycles (de-phases the epilogue write bursts)
-#endif
-#ifdef T256_ABL_NOSTORE
-#define T256_ABL_NOSTORE_ 1
-#else
-#define T256_ABL_NOSTORE_ 0
-#endif
-#ifndef T256_SETPRIO
-#define T256_SETPRIO 1
-#endif
-#ifndef T256_STRM_DEFAULT
-#define T256_STRM_DEFAULT 0   // stream policy of the banded launches (see STRM): measured, not assumed
-#endif
-
 // one 16-byte bf16 chunk from two packed halves
 __device__ __forceinline__ uint32_t t256_pack2(float a, float b) {
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
@@ -110,7 +84,6 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
     const int it_hi = it_lo + (xcd < r8 ? q8 + 1 : q8);
     const int nbx = ((int)gridDim.x - xcd + 7) >> 3;          // workgroups carrying this XCD label
     if (it_lo + jb >= it_hi) return;                          // workgroup-uniform
-    if (T256_DELAY > 0 && q8 >= nbx) for (int d_ = 0; d_ < jb; ++d_) __builtin_amdgcn_s_sleep(T256_DELAY);
 
     const int lda_b = (int)(p.lda * ESZ), ldw_b = (int)(p.ldw * ESZ), wts_b = (int)(p.w_tap_stride * ESZ);
     const int kK_b = p.K * ESZ;
@@ -242,11 +215,7 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
 #define T256_VA(V, IM) (MT ? ((V) | ((uint32_t)__builtin_amdgcn_sbfe((int)(IM), (unsigned)ld_j, 1u) & 0x80000000u)) : (V))
     // K tail (last channel chunk of a K that is not a multiple of 64): chunks past K are zero-filled (general path only)
 #define T256_KT(V, DC) ((ld_kcb + (DC) * 16 < kK_b) ? (V) : 0x80000000u)
-#ifdef T256_ABL_NODMA
-#define T256_DMA(RS, VOFF, SOFF, DST) asm volatile("; no dma %0 %1" :: "v"(VOFF), "s"(SOFF));
-#else
 #define T256_DMA(RS, VOFF, SOFF, DST) __builtin_amdgcn_raw_ptr_buffer_load_lds(RS, (t256_lds_t*)(DST), 16, (VOFF), (SOFF), 0, 0);
-#endif
 #define T256_DMAW(VOFF, DST)                                                                                  \
     if constexpr ((STRM & 1) != 0) { __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (t256_lds_t*)(DST), 16, (VOFF), sW, 0, 2); } \
     else { T256_DMA(rsW, VOFF, sW, DST) }
@@ -327,34 +296,12 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
     bf16x8 fb00, fb01, fb10, fb11;                             // weight fragments, columns 0-31: [col tile][k sub-step]
     bf16x8 fc00, fc01, fc10, fc11;                             // weight fragments, columns 32-63
 
-#ifdef T256_ABL_NOREAD      // timing-only ablation builds (tests/micro): results are wrong by construction
-#define T256_DSR(DST, ADDR, IMM) asm volatile("; no read %0 %1" : "=v"(DST) : "v"(ADDR));
-#else
 #define T256_DSR(DST, ADDR, IMM) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(IMM));
-#endif
-#define T256_READ_A(A0_, A1_, BASE)                                                                           \
-    {                                                                                                         \
-        T256_DSR(fa00, A0_, (BASE) + 0) T256_DSR(fa01, A1_, (BASE) + 0)                                       \
-        T256_DSR(fa10, A0_, (BASE) + 2048) T256_DSR(fa11, A1_, (BASE) + 2048)                                 \
-        T256_DSR(fa20, A0_, (BASE) + 4096) T256_DSR(fa21, A1_, (BASE) + 4096)                                 \
-        T256_DSR(fa30, A0_, (BASE) + 6144) T256_DSR(fa31, A1_, (BASE) + 6144)                                 \
-    }
-#define T256_READ_B(X, B0_, B1_, BASE)                                                                        \
-    {                                                                                                         \
-        T256_DSR(X##00, B0_, (BASE) + 0) T256_DSR(X##01, B1_, (BASE) + 0)                                     \
-        T256_DSR(X##10, B0_, (BASE) + 2048) T256_DSR(X##11, B1_, (BASE) + 2048)                               \
-    }
-#define T256_WAIT_A() asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa00), "+v"(fa01), "+v"(fa10), "+v"(fa11), "+v"(fa20), "+v"(fa21), "+v"(fa30), "+v"(fa31));
-#define T256_WAIT_B(X) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(X##00), "+v"(X##01), "+v"(X##10), "+v"(X##11));
-#ifdef T256_ABL_NOMFMA
-#define T256_MMA(I, N, X, NI, FA, S) asm volatile("; no mfma" : "+v"(acc[I][N]) : "v"(X##NI##S), "v"(FA##S));
-#else
 #define T256_MMA(I, N, X, NI, FA, S) acc[I][N] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(X##NI##S, FA##S, acc[I][N], 0, 0, 0);
-#endif
     // 16 MFMAs: row tiles R0..R0+3 x column tiles C0, C0+1 (weights X) x 2 k sub-steps
 #define T256_MMA16(R0, C0, X)                                                                                 \
     {                                                                                                         \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                        \
         T256_MMA(R0 + 0, C0 + 0, X, 0, fa0, 0) T256_MMA(R0 + 0, C0 + 1, X, 1, fa0, 0)                         \
         T256_MMA(R0 + 1, C0 + 0, X, 0, fa1, 0) T256_MMA(R0 + 1, C0 + 1, X, 1, fa1, 0)                         \
         T256_MMA(R0 + 2, C0 + 0, X, 0, fa2, 0) T256_MMA(R0 + 2, C0 + 1, X, 1, fa2, 0)                         \
@@ -363,7 +310,7 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
         T256_MMA(R0 + 1, C0 + 0, X, 0, fa1, 1) T256_MMA(R0 + 1, C0 + 1, X, 1, fa1, 1)                         \
         T256_MMA(R0 + 2, C0 + 0, X, 0, fa2, 1) T256_MMA(R0 + 2, C0 + 1, X, 1, fa2, 1)                         \
         T256_MMA(R0 + 3, C0 + 0, X, 0, fa3, 1) T256_MMA(R0 + 3, C0 + 1, X, 1, fa3, 1)                         \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                      \
+        __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
     }
     // end of an L section: my DMAs older than the last four sections have landed; publish.
@@ -371,8 +318,7 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
     // 2: the DMA stream has ended (sections may have issued nothing: drain)
 #define T256_LEND(F)                                                                                          \
     {                                                                                                         \
-        if (T256_ABL_NOBAR_ && (F)) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VMW) : "memory");                \
-        else if ((F) || wmode == 0) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(VMW) : "memory");    \
+        if ((F) || wmode == 0) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(VMW) : "memory");       \
         else if (wmode == 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(VMW + NST) : "memory");   \
         else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
@@ -380,7 +326,6 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
     // one K-tile: parity buffer PB is consumed; quarters of the stream's next K-tiles are issued into PN (B1, A1: the K-tile
     // the cursor points at) and, after the cursor has moved, into PB (A0, B0).  A quarter is refilled two sections after the
     // section that read it, so the barrier of the section in between orders the reads before the DMA for every wave.
-#if T256_FINEWAIT
     // reads ordered by first use; every MFMA pair waits only for the fragments it consumes (LDS returns in order)
 #define T256_W3(N, X, Y, Z) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(X), "+v"(Y), "+v"(Z));
 #define T256_W1(N, X) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(X));
@@ -392,7 +337,7 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
         T256_DSR(fb01, B1P, 0) T256_DSR(fb11, B1P, 2048) T256_DSR(fa01, A1P, 0)                               \
         T256_DSR(fa11, A1P, 2048) T256_DSR(fa21, A1P, 4096) T256_DSR(fa31, A1P, 6144)
 #define T256_SEC1_MMA()                                                                                       \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                        \
         T256_W3(9, fb00, fb10, fa00) __builtin_amdgcn_sched_barrier(0); T256_MM2(0, 0, fb, fa0, 0)            \
         T256_W1(8, fa10) __builtin_amdgcn_sched_barrier(0); T256_MM2(1, 0, fb, fa1, 0)                        \
         T256_W1(7, fa20) __builtin_amdgcn_sched_barrier(0); T256_MM2(2, 0, fb, fa2, 0)                        \
@@ -401,23 +346,23 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
         T256_W1(2, fa11) __builtin_amdgcn_sched_barrier(0); T256_MM2(1, 0, fb, fa1, 1)                        \
         T256_W1(1, fa21) __builtin_amdgcn_sched_barrier(0); T256_MM2(2, 0, fb, fa2, 1)                        \
         T256_W1(0, fa31) __builtin_amdgcn_sched_barrier(0); T256_MM2(3, 0, fb, fa3, 1)                        \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                      \
+        __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);
 #define T256_SEC2_READ(B0P, B1P)                                                                              \
         T256_DSR(fc00, B0P, 4096) T256_DSR(fc10, B0P, 4096 + 2048) T256_DSR(fc01, B1P, 4096) T256_DSR(fc11, B1P, 4096 + 2048)
 #define T256_SEC2_MMA()                                                                                       \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                        \
         T256_W2(2, fc00, fc10) __builtin_amdgcn_sched_barrier(0);                                             \
         T256_MM2(0, 2, fc, fa0, 0) T256_MM2(1, 2, fc, fa1, 0) T256_MM2(2, 2, fc, fa2, 0) T256_MM2(3, 2, fc, fa3, 0) \
         T256_W2(0, fc01, fc11) __builtin_amdgcn_sched_barrier(0);                                             \
         T256_MM2(0, 2, fc, fa0, 1) T256_MM2(1, 2, fc, fa1, 1) T256_MM2(2, 2, fc, fa2, 1) T256_MM2(3, 2, fc, fa3, 1) \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                      \
+        __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);
 #define T256_SEC3_READ(A0P, A1P)                                                                              \
         T256_DSR(fa00, A0P, 8192) T256_DSR(fa10, A0P, 8192 + 2048) T256_DSR(fa20, A0P, 8192 + 4096) T256_DSR(fa30, A0P, 8192 + 6144) \
         T256_DSR(fa01, A1P, 8192) T256_DSR(fa11, A1P, 8192 + 2048) T256_DSR(fa21, A1P, 8192 + 4096) T256_DSR(fa31, A1P, 8192 + 6144)
 #define T256_SEC3_MMA()                                                                                       \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                      \
+        __builtin_amdgcn_s_setprio(1);                                                                        \
         T256_W1(7, fa00) __builtin_amdgcn_sched_barrier(0); T256_MM2(4, 2, fc, fa0, 0)                        \
         T256_W1(6, fa10) __builtin_amdgcn_sched_barrier(0); T256_MM2(5, 2, fc, fa1, 0)                        \
         T256_W1(5, fa20) __builtin_amdgcn_sched_barrier(0); T256_MM2(6, 2, fc, fa2, 0)                        \
@@ -426,16 +371,8 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
         T256_W1(2, fa11) __builtin_amdgcn_sched_barrier(0); T256_MM2(5, 2, fc, fa1, 1)                        \
         T256_W1(1, fa21) __builtin_amdgcn_sched_barrier(0); T256_MM2(6, 2, fc, fa2, 1)                        \
         T256_W1(0, fa31) __builtin_amdgcn_sched_barrier(0); T256_MM2(7, 2, fc, fa3, 1)                        \
-        if (T256_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                      \
+        __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);
-#else
-#define T256_SEC1_READ(A0P, A1P, B0P, B1P) T256_READ_A(A0P, A1P, 0) T256_READ_B(fb, B0P, B1P, 0)
-#define T256_SEC1_MMA() T256_WAIT_A() T256_WAIT_B(fb) __builtin_amdgcn_sched_barrier(0); T256_MMA16(0, 0, fb)
-#define T256_SEC2_READ(B0P, B1P) T256_READ_B(fc, B0P, B1P, 4096)
-#define T256_SEC2_MMA() T256_WAIT_B(fc) __builtin_amdgcn_sched_barrier(0); T256_MMA16(0, 2, fc)
-#define T256_SEC3_READ(A0P, A1P) T256_READ_A(A0P, A1P, 8192)
-#define T256_SEC3_MMA() T256_WAIT_A() __builtin_amdgcn_sched_barrier(0); T256_MMA16(4, 2, fc)
-#endif
 #define T256_KTILE(A0P, A1P, B0P, B1P, PB, PN, F)                                                             \
     {                                                                                                         \
         T256_SEC1_READ(A0P, A1P, B0P, B1P)                                                                    \
@@ -465,7 +402,7 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
     // waves 4-7 put it after their MFMAs (reads, wait, MFMAs inside one interval, beside the early half's MFMAs and reads).
     // Every wave still executes one barrier per section, each refill still comes two barriers after the reads it overwrites,
     // and each read still comes after the barrier that follows the counted wait of every wave that issued its DMA.
-    const bool early = !T256_STAGGER || g == 0;          // TS = 1: waves 0-3 / 4-7 (g is wave >> 2 there as well)
+    const bool early = g == 0;                          // TS = 1: waves 0-3 / 4-7 (g is wave >> 2 there as well)
 
     // ---------------- compute cursor ----------------
     int ci = it_lo + jb;
@@ -594,11 +531,7 @@ __global__ __launch_bounds__(512) void gemm_nt_t256_kernel(const GemmNT p) {
                                     ch[e] = t256_pack2(t256_lo(ch[e]) + t256_lo(ad[e]), t256_hi(ch[e]) + t256_hi(ad[e]));
                             }
                         }
-#ifdef T256_ABL_CONTIG      // timing only: every store instruction writes 1 KiB of consecutive bytes
-                        __builtin_amdgcn_raw_buffer_store_b128(ch, rsC, (uint32_t)((((long)mw * p.ldc + nw) * 2 & ~1023L) + ((i * 2 + pr) * 8 + wave) * 1024 + lane * 16), 0, 0);
-#else
-                        if (!T256_ABL_NOSTORE_) __builtin_amdgcn_raw_buffer_store_b128(ch, rsC, ok ? (uint32_t)(((long)row * p.ldc + col) * 2) : T256_OOB, 0, (STRM & 2) ? 16 : 0);
-#endif
+                        __builtin_amdgcn_raw_buffer_store_b128(ch, rsC, ok ? (uint32_t)(((long)row * p.ldc + col) * 2) : T256_OOB, 0, (STRM & 2) ? 16 : 0);
                         if (st) {
                             // the chunk's two 4-column halves may lie in different groups (Cg % 4 == 0)
                             const float l0 = t256_lo(ch[0]), h0 = t256_hi(ch[0]), l1 = t256_lo(ch[1]), h1 = t256_hi(ch[1]);
@@ -738,8 +671,7 @@ __global__ __launch_bounds__(256) void t256_reduce_kernel(const GemmNT p) {
 static inline int t256_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 bool gemm_nt256_eligible(int dtype, const GemmNT& p) {
-    static const int on = getenv("SGV_GEMM_T256") ? atoi(getenv("SGV_GEMM_T256")) : 1;
-    if (!on || dtype != 1) return false;
+    if (dtype != 1) return false;
     if (p.N < 256 || p.M < (p.ts > 0 ? 128 : 256)) return false;      // the 128 x 512 tile shape takes a single 128-row tile too
     if (p.K % 8 || p.N % 8 || p.lda % 8 || p.ldw % 8 || p.w_tap_stride % 8 || p.ldc % 8) return false;
     if (p.addend && p.ldadd % 8) return false;
@@ -789,9 +721,8 @@ int launch_gemm_nt256(const GemmNT& p, hipStream_t s) {
     // item order and stream policy (see T256_TILE_OF, STRM).  A one-tap product with a short K and many column panels (the recon
     // head: K = 1024, N = 95 008) streams every weight panel once per XCD and 608 MB of output through the XCD's 4 MiB L2; its
     // activation matrix (M x K, 6.5 MB) does not survive there, so the XCDs each take a band of row tiles (<= 3.5 MiB of
-    // activations).  SGV_T256_BAND / SGV_T256_STRM override (A/B runs); GemmNT::band / strm < 0 switch either off (tests).
-    static const int band_env = getenv("SGV_T256_BAND") ? atoi(getenv("SGV_T256_BAND")) : -1;
-    static const int strm_env = getenv("SGV_T256_STRM") ? atoi(getenv("SGV_T256_STRM")) : -1;
+    // activations).  The banded launches keep the default stream policy (strm 0): measured, not assumed.  GemmNT::band / strm
+    // > 0 choose either (tests), < 0 switch either off.
     {
         const int tm_all = t256_cdiv(p.M, TH), tn_all = t256_cdiv(p.N, TW);
         const long a_tile_bytes = (long)TH * p.K * 2 * p.taps;
@@ -801,10 +732,7 @@ int launch_gemm_nt256(const GemmNT& p, hipStream_t s) {
             if (band < 1) band = 1;
             const int nb = t256_cdiv(tm_all, band);
             band = t256_cdiv(tm_all, nb);                                // equal bands
-            strm = T256_STRM_DEFAULT;
         }
-        if (band_env >= 0 && p.band == 0) band = band_env;
-        if (strm_env >= 0 && p.strm == 0) strm = strm_env;
         if (band < 0 || band >= tm_all) band = 0;
         if (strm < 0) strm = 0;
         q.band = band; q.strm = (!ts && !p.cv_kw && p.taps == 1 && !(p.splitk > 1 || p.out_f32)) ? (strm & 3) : 0;
@@ -852,13 +780,13 @@ int launch_gemm_nt256(const GemmNT& p, hipStream_t s) {
 
 // ---- kernel choice -------------------------------------------------------------------------------------------------
 // costs in units of one K-tile of the 256 kernel (~1.7 us): measured on MI355X with tests/micro/g256_harness.hip
+// a K-tile of the 128 x 512 tile moves 80 KiB instead of 64 and issues 10 DMA pieces per wave instead of 8: measured 11-13 %
+// longer (5120 x 5120 x 5 taps: 630 us in one round of 250 items = the 256 x 256 kernel's 565 us + its 65 us tail)
+constexpr double T256_WIDE_KT = 1.13;
 static double t256_cost(int M, int N, long total_kt, int sk, int ts = 0) {
     const double items = (double)t256_cdiv(M, ts ? 128 : 256) * t256_cdiv(N, ts ? 512 : 256) * sk;
     const double rounds = ceil(items / 256.0);
-    // a K-tile of the 128 x 512 tile moves 80 KiB instead of 64 and issues 10 DMA pieces per wave instead of 8: measured 11-13 %
-    // longer (5120 x 5120 x 5 taps: 630 us in one round of 250 items = the 256 x 256 kernel's 565 us + its 65 us tail)
-    static const double wide_kt = getenv("SGV_T256_WIDE_KT") ? atof(getenv("SGV_T256_WIDE_KT")) : 1.13;
-    double c = rounds * (ceil((double)total_kt / sk) * (ts ? wide_kt : 1.0) + 2.5) + 3.0;
+    double c = rounds * (ceil((double)total_kt / sk) * (ts ? T256_WIDE_KT : 1.0) + 2.5) + 3.0;
     if (sk > 1) c += (2.0 * sk * (double)M * N * 4.0 / 3.5e12) / 1.7e-6 + 4.0;
     return c;
 }
@@ -872,13 +800,13 @@ static int t256_best_sk(int M, int N, long total_kt, size_t partial_floats, doub
     if (cost) *cost = bc;
     return best;
 }
+constexpr double T256_MIN_GF = 30.0;          // smaller products stay on the 128-row kernels
 GemmPlan gemm_nt_plan(int dtype, const GemmNT& p, size_t partial_floats, int want_stats) {
-    static const double min_gf = getenv("SGV_T256_MIN_GF") ? atof(getenv("SGV_T256_MIN_GF")) : 30.0;
     GemmPlan pl = {0, 1, 1, p.M, 0};
     const long total_kt = (long)p.taps * t256_cdiv(p.K, 64);
     const double gf = 2.0e-9 * p.M * p.N * p.K * p.taps;
     const long tiles256 = (long)t256_cdiv(p.M, 256) * t256_cdiv(p.N, 256);
-    const bool big = gemm_nt256_eligible(dtype, p) && (p.N >= 1024 || tiles256 >= 200) && gf >= min_gf && !p.out_f32 && total_kt >= 8 && p.add_W <= 0;
+    const bool big = gemm_nt256_eligible(dtype, p) && (p.N >= 1024 || tiles256 >= 200) && gf >= T256_MIN_GF && !p.out_f32 && total_kt >= 8 && p.add_W <= 0;
     if (!big) {
         pl.sk_main = gemm_nt_pick_splitk(p.M, p.N, p.K, p.taps, dtype);
         if ((size_t)pl.sk_main * p.M * p.N > partial_floats) pl.sk_main = 1;
@@ -886,17 +814,14 @@ GemmPlan gemm_nt_plan(int dtype, const GemmNT& p, size_t partial_floats, int wan
         return pl;
     }
     const bool stats_ok = want_stats && p.Tlen >= 128 && p.gn_Cg >= 64 && p.gn_Cg % 4 == 0;
-    // the 128 x 512 tile (kind 3): all rows in 128-row tiles, no tail launch.  SGV_T256_WIDE: 0 never, 1 where the cost model
-    // prefers it (default), 2 wherever it is eligible
-    static const int wide = getenv("SGV_T256_WIDE") ? atoi(getenv("SGV_T256_WIDE")) : 1;
-    // at least four column tiles (N >= 2048): with two (N = 1024: the K = 95 008 and 5120 -> 1024 layers) every workgroup re-reads
+    // the 128 x 512 tile (kind 3): all rows in 128-row tiles, no tail launch, where the cost model prefers it.
+    // At least four column tiles (N >= 2048): with two (N = 1024: the K = 95 008 and 5120 -> 1024 layers) every workgroup re-reads
     // half of the weight matrix for 128 rows of output and the tile measured slower than main + tail (70.6 vs 64.5 us, 613 vs 605 us)
-    const bool wide_ok = wide && !p.cv_kw && p.N >= (wide == 2 ? 512 : 2048) && p.ts >= 0;
+    const bool wide_ok = !p.cv_kw && p.N >= 2048 && p.ts >= 0;
     double c_all, c_main = 1e30, c_wide = 1e30;
     const int sk_all = stats_ok ? 1 : t256_best_sk(p.M, p.N, total_kt, partial_floats, &c_all);
-    if (stats_ok) {
+    if (stats_ok) {                                   // the recon head measured the same on either tile (592 vs 594 us): it keeps its banded 256 x 256 order
         pl.kind = 1; pl.sk_main = 1; pl.fuse_stats = 1;
-        if (wide_ok && wide == 2) pl.kind = 3;        // the recon head measured the same either way (592 vs 594 us): it keeps its banded 256 x 256 order
         return pl;
     }
     const int sk_wide = wide_ok ? t256_best_sk(p.M, p.N, total_kt, partial_floats, &c_wide, 1) : 1;
@@ -912,13 +837,12 @@ GemmPlan gemm_nt_plan(int dtype, const GemmNT& p, size_t partial_floats, int wan
     }
     if (c_main < c_all) { pl.kind = 2; pl.sk_main = sk_main; pl.sk_tail = sk_tail; pl.m_main = p.M - rem; }
     else { pl.kind = 1; pl.sk_main = sk_all; }
-    if (wide_ok && (wide == 2 || c_wide < (c_main < c_all ? c_main : c_all))) { pl.kind = 3; pl.sk_main = sk_wide; pl.sk_tail = 1; pl.m_main = p.M; }
+    if (wide_ok && c_wide < (c_main < c_all ? c_main : c_all)) { pl.kind = 3; pl.sk_main = sk_wide; pl.sk_tail = 1; pl.m_main = p.M; }
     return pl;
 }
 int gemm_nt_tail_split(int dtype, const GemmNT& p, const GemmPlan& pl, size_t tail_partial_floats) {
-    static const int on = getenv("SGV_TAIL_CONCURRENT") ? atoi(getenv("SGV_TAIL_CONCURRENT")) : 1;
     const int rem = p.M - pl.m_main;
-    if (!on || dtype != 1 || pl.kind != 2 || pl.fuse_stats || p.cv_kw || rem != 128 || p.N < 512 || p.row0 || p.out_f32 || p.add_W > 0 || p.trow0) return 0;
+    if (dtype != 1 || pl.kind != 2 || pl.fuse_stats || p.cv_kw || rem != 128 || p.N < 512 || p.row0 || p.out_f32 || p.add_W > 0 || p.trow0) return 0;
     if (pl.m_main < p.pad || p.taps > 24) return 0;
     const int ctiles = (p.N + 511) / 512;
     const long total_kt = (long)p.taps * ((p.K + 63) / 64);
@@ -926,8 +850,8 @@ int gemm_nt_tail_split(int dtype, const GemmNT& p, const GemmPlan& pl, size_t ta
     int sk_t = ctiles <= 16 ? 16 / ctiles : 0;
     while (sk_t > 1 && total_kt / sk_t < 24) --sk_t;
     if (sk_t < 1 || main_items + ctiles * sk_t > 256) return 0;
-    // a K-tile of the 128 x 512 tile costs 1.13 of the square tile's (t256_cost): the tail must be over before the main launch
-    if ((double)total_kt / sk_t * 1.13 > (double)total_kt / pl.sk_main * 1.05) return 0;
+    // a K-tile of the 128 x 512 tile costs T256_WIDE_KT of the square tile's: the tail must be over before the main launch
+    if ((double)total_kt / sk_t * T256_WIDE_KT > (double)total_kt / pl.sk_main * 1.05) return 0;
     if ((size_t)sk_t * rem * p.N > tail_partial_floats) return 0;
     return sk_t;
 }

@@ -237,22 +237,6 @@ __global__ __launch_bounds__(512) void gemm_tn_t256_kernel(const GemmTN p) {
         q256_l2 pr_; pr_[0] = lo_; pr_[1] = hi_;                                                              \
         DST = __builtin_bit_cast(bf16x8, pr_);                                                                \
     }
-    // dY row tiles R0..R0+3 of the wave's half (R0 = 0 or 4): slab 2g + (R0 >> 2), pairs 0..3; k sub-step = +4096
-#define Q256_READ_A(P0, P1, P2, P3, R0)                                                                       \
-    {                                                                                                         \
-        Q256_TR(fa00, P0, ((R0) >> 2) * 8192 + 0) Q256_TR(fa01, P0, ((R0) >> 2) * 8192 + 4096)                \
-        Q256_TR(fa10, P1, ((R0) >> 2) * 8192 + 0) Q256_TR(fa11, P1, ((R0) >> 2) * 8192 + 4096)                \
-        Q256_TR(fa20, P2, ((R0) >> 2) * 8192 + 0) Q256_TR(fa21, P2, ((R0) >> 2) * 8192 + 4096)                \
-        Q256_TR(fa30, P3, ((R0) >> 2) * 8192 + 0) Q256_TR(fa31, P3, ((R0) >> 2) * 8192 + 4096)                \
-    }
-    // X column tiles C0, C0+1 of the wave (C0 = 0 or 2): slab (C0 >> 1) * 2 + (wq >> 1)
-#define Q256_READ_B(X, Q0, Q1, C0)                                                                            \
-    {                                                                                                         \
-        Q256_TR(X##00, Q0, ((C0) >> 1) * 16384 + 0) Q256_TR(X##01, Q0, ((C0) >> 1) * 16384 + 4096)            \
-        Q256_TR(X##10, Q1, ((C0) >> 1) * 16384 + 0) Q256_TR(X##11, Q1, ((C0) >> 1) * 16384 + 4096)            \
-    }
-#define Q256_WAIT_A() asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa00), "+v"(fa01), "+v"(fa10), "+v"(fa11), "+v"(fa20), "+v"(fa21), "+v"(fa30), "+v"(fa31));
-#define Q256_WAIT_B(X) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(X##00), "+v"(X##01), "+v"(X##10), "+v"(X##11));
 #define Q256_MMA(I, N, X, NI, FA, S) acc[I][N] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(X##NI##S, FA##S, acc[I][N], 0, 0, 0);
     // 16 MFMAs: row tiles R0..R0+3 x column tiles C0, C0+1 (X fragments X) x 2 k sub-steps
 #define Q256_MMA16(R0, C0, X)                                                                                 \
@@ -279,14 +263,11 @@ __global__ __launch_bounds__(512) void gemm_tn_t256_kernel(const GemmTN p) {
     }
     // reads ordered by first use; every MFMA pair waits only for the fragments it consumes (LDS returns in order; lgkmcnt counts
     // at most 15, so the first wait of a section is looser than its operands need and still correct)
-#ifndef Q256_FINEWAIT
-#define Q256_FINEWAIT 1
-#endif
-#if Q256_FINEWAIT
 #define Q256_W3(N, X, Y, Z) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(X), "+v"(Y), "+v"(Z));
 #define Q256_W2(N, X, Y) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(X), "+v"(Y));
 #define Q256_W1(N, X) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(X));
 #define Q256_MM2(R, C0, X, FA, S) Q256_MMA(R, C0 + 0, X, 0, FA, S) Q256_MMA(R, C0 + 1, X, 1, FA, S)
+    // dY row tiles 0-3 / 4-7 of the wave's half at +0 / +8192 (k sub-step: +4096); X column tiles 0,1 / 2,3 at +0 / +16384
     // section 1: X tiles 0,1 + dY row tiles 0-3, k sub-step 0 first (24 reads)
 #define Q256_SEC1_READ(P0, P1, P2, P3, Q0, Q1)                                                                \
         Q256_TR(fb00, Q0, 0) Q256_TR(fb10, Q1, 0) Q256_TR(fa00, P0, 0) Q256_TR(fa10, P1, 0)                   \
@@ -332,14 +313,6 @@ __global__ __launch_bounds__(512) void gemm_tn_t256_kernel(const GemmTN p) {
         Q256_W1(0, fa31) __builtin_amdgcn_sched_barrier(0); Q256_MM2(7, 2, fc, fa3, 1)                        \
         __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);
-#else
-#define Q256_SEC1_READ(P0, P1, P2, P3, Q0, Q1) Q256_READ_A(P0, P1, P2, P3, 0) Q256_READ_B(fb, Q0, Q1, 0)
-#define Q256_SEC1_MMA() Q256_WAIT_A() Q256_WAIT_B(fb) __builtin_amdgcn_sched_barrier(0); Q256_MMA16(0, 0, fb)
-#define Q256_SEC2_READ(Q0, Q1) Q256_READ_B(fc, Q0, Q1, 2)
-#define Q256_SEC2_MMA() Q256_WAIT_B(fc) __builtin_amdgcn_sched_barrier(0); Q256_MMA16(0, 2, fc)
-#define Q256_SEC3_READ(P0, P1, P2, P3) Q256_READ_A(P0, P1, P2, P3, 4)
-#define Q256_SEC3_MMA() Q256_WAIT_A() __builtin_amdgcn_sched_barrier(0); Q256_MMA16(4, 2, fc)
-#endif
     // one K-tile (section structure and refill distances of gemm256.hip): parity buffer PB is consumed; quarters of the
     // stream's next K-tiles go into PN (B1, A1: the K-tile the cursor points at) and, after the cursor has moved, into PB (A0, B0)
 #define Q256_KTILE(P0, P1, P2, P3, Q0, Q1, PB, PN, F)                                                         \
@@ -478,8 +451,7 @@ static inline int q256_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // bf16, both widths >= 256, at least 16 K-tiles of 64 rows, sample length >= 64 (one conditional subtract keeps a lane's time index)
 bool gemm_tn256_eligible(int dtype, const GemmTN& p) {
-    static const int on = getenv("SGV_GEMM_TN256") ? atoi(getenv("SGV_GEMM_TN256")) : 1;
-    if (!on || dtype != 1 || p.cv_kw > 0) return false;
+    if (dtype != 1 || p.cv_kw > 0) return false;
     // M % 64 == 0: a K-tile never runs past the last row (the row advance is the DMA's SCALAR offset, which the buffer range check
     // does not see; every other out-of-window row is pushed out of range through the per-lane offset)
     if (p.N1 < 256 || p.N2 < 256 || p.M < 1024 || p.M % 64 || p.Tlen < 64 || p.taps > 15) return false;
@@ -488,11 +460,11 @@ bool gemm_tn256_eligible(int dtype, const GemmTN& p) {
 }
 // the planner's choice for a weight gradient: the 256 x 256 kernel when its items fill the chip (>= 200 per slice) and the
 // product is big enough to amortise the per-item epilogue (256 KiB of fp32 per 50 K-tiles at M = 3200)
+constexpr double TN256_MIN_GF = 150.0;
 bool gemm_tn_uses_t256(int dtype, const GemmTN& p) {
-    static const double min_gf = getenv("SGV_TN256_MIN_GF") ? atof(getenv("SGV_TN256_MIN_GF")) : 150.0;
     if (!gemm_tn256_eligible(dtype, p)) return false;
     const long items = (long)q256_cdiv(p.N1, 256) * q256_cdiv(p.N2, 256) * p.taps;
-    return items >= 200 && 2.0e-9 * p.M * p.N1 * p.N2 * p.taps >= min_gf;
+    return items >= 200 && 2.0e-9 * p.M * p.N1 * p.N2 * p.taps >= TN256_MIN_GF;
 }
 bool gemm_tn256_accepts(const GemmTN& p) {
     if (!gemm_tn256_eligible(1, p)) return false;
@@ -509,8 +481,7 @@ bool gemm_tn256_accepts(const GemmTN& p) {
 int launch_gemm_tn256(const GemmTN& p, hipStream_t s) {
     if (!gemm_tn256_accepts(p)) return -1;
     GemmTN q = p;
-    static const int order_env = getenv("SGV_TN256_ORDER") ? atoi(getenv("SGV_TN256_ORDER")) : -1;
-    q.order = order_env >= 0 ? order_env : 2;        // measured (one box, order 0 / 2): 665 / 650, 652 / 620, 837 / 826 us on the three big shapes
+    q.order = 2;                                     // measured (one box, order 0 / 2): 665 / 650, 652 / 620, 837 / 826 us on the three big shapes
     q.a_bytes = ((long)(p.M - 1) * p.lda + p.N1) * 2;
     q.b_bytes = ((long)(p.M - 1) * p.ldb + p.N2) * 2;
     const int nitems = q256_cdiv(p.N1, 256) * q256_cdiv(p.N2, 256) * p.taps * p.splitk;

@@ -419,22 +419,13 @@ __global__ __launch_bounds__(256) void adamw_sn_kernel(const AdamDesc* adam, con
 int opt_adamw_sn(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, float lr, float b1, float b2,
                  float eps, float wd, float bc1, float bc2sqrt, double* gnorm_sq, int compute_dtype, hipStream_t s, const float* g_base, const void* g_lp, int desc_lp) {
     if (n <= 0) return 0;
-    // default 9: the moments and the bf16 operand copies bypass the caches (measured, DESIGN.md section 13: moments 12.20 -> 12.05 ms
+    // NTM 9: the moments and the bf16 operand copies bypass the caches (measured, DESIGN.md section 13: moments 12.20 -> 12.05 ms
     // per step, the pass alone 2.90 -> 2.70 ms; the copies another 0.07 ms over eleven alternations)
-    static const int ntm = getenv("SGV_ADAM_NT") ? atoi(getenv("SGV_ADAM_NT")) : 9;
+    constexpr int NTM = 9;
     const uint16_t* lp = reinterpret_cast<const uint16_t*>(g_lp);
-#define SGV_ADAM_LAUNCH(TT, GLP, MODE) hipLaunchKernelGGL((adamw_sn_kernel<TT, GLP, MODE>), dim3(n), dim3(256), 0, s, adam_dev, sn_dev, items, lr, b1, b2, eps, wd, bc1, bc2sqrt, gnorm_sq, g_base, lp, desc_lp)
-#define SGV_ADAM_MODES(TT, GLP)                                   \
-    switch (ntm) {                                                \
-        case 0: SGV_ADAM_LAUNCH(TT, GLP, 0); break;               \
-        case 3: SGV_ADAM_LAUNCH(TT, GLP, 3); break;               \
-        case 5: SGV_ADAM_LAUNCH(TT, GLP, 5); break;               \
-        case 1: SGV_ADAM_LAUNCH(TT, GLP, 1); break;               \
-        default: SGV_ADAM_LAUNCH(TT, GLP, 9); break;              \
-    }
-    if (compute_dtype == 1) { if (lp) { SGV_ADAM_MODES(bf16_t, true) } else { SGV_ADAM_MODES(bf16_t, false) } }
-    else { if (lp) { SGV_ADAM_MODES(float, true) } else { SGV_ADAM_MODES(float, false) } }
-#undef SGV_ADAM_MODES
+#define SGV_ADAM_LAUNCH(TT, GLP) hipLaunchKernelGGL((adamw_sn_kernel<TT, GLP, NTM>), dim3(n), dim3(256), 0, s, adam_dev, sn_dev, items, lr, b1, b2, eps, wd, bc1, bc2sqrt, gnorm_sq, g_base, lp, desc_lp)
+    if (compute_dtype == 1) { if (lp) SGV_ADAM_LAUNCH(bf16_t, true); else SGV_ADAM_LAUNCH(bf16_t, false); }
+    else { if (lp) SGV_ADAM_LAUNCH(float, true); else SGV_ADAM_LAUNCH(float, false); }
 #undef SGV_ADAM_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

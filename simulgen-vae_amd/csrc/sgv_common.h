@@ -195,7 +195,7 @@ struct GemmTN {
     long out_tap_stride;
     long out_slab_stride;
     int M, N1, N2, taps, pad, Tlen, splitk, use_tr;
-    int force_w2;                   // tests: take gemm_tn_w2_kernel whenever the shape is eligible (ignores SGV_TN_W2); 2: and its persistent walk;
+    int force_w2;                   // tests: 1 = gemm_tn_w2_kernel whenever the shape is eligible (never the 256 x 256 kernel); 2: and its persistent walk;
                                     // 3: the 256 x 256 kernel (gemm256tn.hip) whenever eligible; -1: never the 256 x 256 kernel
     long a_bytes, b_bytes;          // filled by launch_gemm_tn
     // virtual im2col operand (cv_kw > 0; weight gradient of a 2-D convolution without the im2col matrix): B is a channels-

@@ -1,5 +1,5 @@
 // Standalone correctness + timing harness for the GEMM kernels (no Python, no torch: seconds of GPU-box time).
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DT256_PINGPONG=0 ...] tests/micro/g256_harness.hip -o tests/micro/_ab/g256
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 tests/micro/g256_harness.hip -o tests/micro/_ab/g256
 //   ./g256 [check=1] [reps=5] M N K taps splitk [M N K taps splitk ...]      (splitk 0: the launcher's own choice)
 // Per shape: the 256x256 persistent kernel (gemm256.hip) and the round-1 kernels (gemm.hip: 128x256 wide64p / 128x128) on the
 // same random bf16 operands, each checked against a plain one-thread-per-output fp32 reference kernel; with stats=1 the
@@ -11,9 +11,7 @@
 #include <algorithm>
 #include "../../simulgen-vae_amd/csrc/gemm.hip"
 #include "../../simulgen-vae_amd/csrc/gemm256.hip"
-
-bool gemm_nt_vendor_eligible(int, const GemmNT&) { return false; }
-int launch_gemm_nt_vendor(const GemmNT&, hipStream_t) { return 1; }
+#include "../../simulgen-vae_amd/csrc/gemm256tn.hip"      // the weight-gradient kernel that gemm.hip's launcher may pick
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(2); } } while (0)
 

@@ -267,7 +267,7 @@ def test_training_steps_match_reference(mode):
     bounds = STEP_BOUNDS["f32" if mode == "f32" else "bf16"]
     if mode == "bf16_grad_bf16":
         # the option engaged on exactly the four big layers: they took the bf16 epilogue, and their weights after one step differ
-        # from the plain bf16 engine's (a run where the 256 x 256 kernel is never picked -- SGV_TN256_MIN_GF=1e9 -- fails here)
+        # from the plain bf16 engine's (a build where the 256 x 256 kernel is never picked -- TN256_MIN_GF in gemm256tn.hip above every layer -- fails here)
         plain_dev, plain_info = _replay_steps("bf16")
         assert info["bf16_out_layers"] == sorted(k.rsplit(".", 1)[0] for k in BIG4), info["bf16_out_layers"]
         assert plain_info["bf16_out_layers"] == []

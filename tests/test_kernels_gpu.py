@@ -369,7 +369,7 @@ def test_gemm_tn_w2(case, persistent):
     scale = np.abs(ref).max()
     for rep in range(8):
         out = torch.full((taps, N1, N2), float("nan"), dtype=torch.float32, device="cuda")
-        # use_tr = 2: force the two-blocks-per-CU kernel for every eligible shape (whatever SGV_TN_W2 says); 3: and its persistent walk
+        # use_tr = 2: force the two-blocks-per-CU kernel for every eligible shape; 3: and its persistent walk
         rc = lib.sgv_test_gemm_tn(1, ddY.data_ptr(), dX.data_ptr(), out.data_ptr(), M, N1, N2, taps, Tlen, splitk, 2 + persistent, None)
         assert rc == 0, lib.sgv_last_error()
         got = out.cpu().numpy()

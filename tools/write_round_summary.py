@@ -110,7 +110,7 @@ divide sequence, 467 -> 252 µs, now HBM-bound at 5 TB/s); L2 prefetch touches i
 (1014 -> 1026-1210 µs: vector-memory returns are in order); one zeroing kernel per site instead of 14 memsets (no change); four
 rows per round in the bf16 `W v` pass (217 -> 243 µs); the library (hipBLASLt) on the K = 95 008 layers (1028 vs 832 µs) and on
 the conditioner's weight gradients (734 vs 1095 samples/s).  All removed.  Kept from the same series of per-kernel A/B runs
-(`tools/ab_kernel_stats.sh`): the library for plain one-tap GEMMs with K <= 8192 (+2.6 %), bf16 weight copy in the `W v` pass
+(a per-kernel A/B script, removed; see git history): the library for plain one-tap GEMMs with K <= 8192 (+2.6 %), bf16 weight copy in the `W v` pass
 (+1.1 %), GroupNorm statistics in the 128x128 GEMM epilogue (own-kernel path), the 16-byte split-K combine passes.
 
 ## Per-layer GEMM table (bench.py --layer-times, hipEvents, one step; top 40 by time)

@@ -363,6 +363,59 @@ int sgv_test_occupy(void* stream, int blocks, int threads, int lds_bytes, long l
  * one collective.  *calls / *elems return (and reset) the number of collectives and of elements since the last call. */
 int sgv_test_fake_collective(float k, long* calls, long* elems);
 
+/* Test hooks for the non-GEMM kernels of the step (csrc/ew.hip; tests/test_ew_kernels_gpu.py): caller-owned device buffers in, the
+ * launcher the engine calls, then a stream sync.  Maps are channels-last [B*T][ld] of `dtype` (ld >= C, ld % 8 == 0), C % 8 == 0,
+ * 1 <= G <= 32, C % G == 0; gamma / beta / dgamma / dbeta / dbias / cbias are [C] fp32, sums / sums2 [B*G][2] fp64.  `work` is a
+ * scratch array of work_floats >= sgv_test_gn_workspace_floats(B, T, C) floats.  Bad arguments return SGV_ERR_ARG before any
+ * launch.  Optional pointers may be NULL.  Nothing persistent is allocated. */
+size_t sgv_test_gn_workspace_floats(int B, int T, int C);
+/* out = [res + rscale *] act(GroupNorm(y)), act: 0 none, 1 GELU (erf), 2 tanh, 3 ReLU; sums (written) = (sum, sum of squares)
+ * per (sample, group).  *path: 1 = the one-launch slab kernel ran, 0 = statistics + apply. */
+int sgv_test_gn_fwd(int dtype, int act, const void* y, long ldy, const void* res, long ldres, float rscale, void* out, long ldout,
+                    const float* gamma, const float* beta, double* sums, float* work, size_t work_floats, int B, int T, int C, int G,
+                    int* path, void* stream);
+/* Backward of out = act(GroupNorm(y)), act in {0, 1, 3}, immediate mode.  With dz = dout * rscale * act'(z) (z the normalised
+ * and affine value, xhat the normalised one): dgamma (+)= sum dz xhat, dbeta (+)= sum dz, sums2 = (sum gamma dz, sum gamma dz xhat) per
+ * (sample, group), dy = gscale * dL/dy, dbias (+)= column sums of dy, cdot[0] = sum dy * (y - cbias).  accum_affine: += into
+ * dgamma / dbeta / dbias instead of =.  *path as above. */
+int sgv_test_gn_bwd(int dtype, int act, const void* y, long ldy, const void* dout, long lddout, float rscale, float gscale,
+                    const float* gamma, const float* beta, const double* sums, void* dy, long lddy, double* sums2, float* dgamma,
+                    float* dbeta, float* dbias, float* cdot, const float* cbias, int accum_affine, float* work, size_t work_floats,
+                    int B, int T, int C, int G, int* path, void* stream);
+/* Recon head as the engine runs it: statistics of y, then xhat = tanh(GroupNorm(y)) against the target x with loss kind
+ * SGV_LOSS_*: loss_sums[2] = (selected loss sum, squared-error sum), xhat optional.  train != 0 also: sums2, the unit-weight
+ * unit[3][C] = (dgamma, dbeta, dbias), and the second pass dy = gscale * dL/dy with cdot[0] = sum dy * (y - cbias). */
+int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long ldy, const void* x, long ldx, void* xhat, long ldxhat,
+                        const float* gamma, const float* beta, double* sums, double* loss_sums, double* sums2, float* unit, float gscale,
+                        void* dy, long lddy, float* cdot, const float* cbias, float* work, size_t work_floats, int B, int T, int C,
+                        int G, void* stream);
+/* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
+ * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
+ * (yf32 [B*T][ldyf] fp32; cdot needs it). */
+int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
+                 float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
+                 int T, int C, void* stream);
+/* Latent reparameterisation + KL: last [B][2Z] = [mu | logvar], eps / z / dz [B][Z], dlast [B][2Z], all fp32.  z and kl given:
+ * forward (kl[0] = batch mean).  dz and dlast given: backward of sum dz z + coef * B * kl. */
+int sgv_test_latent(const float* last, const float* eps, float* z, double* kl, const float* dz, float* dlast, float coef, int B, int Z,
+                    void* stream);
+/* Decoder stage: pz = [mu | lv], qz = [dmu | dlv] fp32 [M][2C], eps fp32 [M][C].  zs_next given: forward, zs_next = dec_out + z
+ * (dtype maps), zmap (fp32 [M][C], optional) = z, kl[0] = inv_b * sum of the KL terms; kl_part: scratch of 2048 doubles.
+ * dzs given: backward (std_scale 1) of sum dzs z + coef * (sum of the KL terms): g_p / g_q [M][2C] of dtype. */
+int sgv_test_stage(int dtype, const float* pz, const float* qz, const float* eps, const void* dec_out, long ldd, void* zs_next,
+                   long ldz, float* zmap, float std_scale, float inv_b, double* kl, double* kl_part, const void* dzs, long lddzs,
+                   void* g_p, void* g_q, float coef, int M, int C, void* stream);
+/* Linear "head" (K large, O small; K % 8 == 0): Y given: Y [B][O] fp32 = scale[0] * X W^T + bias, X [B][K] of xdtype, W [O][K]
+ * fp32, part: scratch of part_floats >= 128 * B * O floats.  dY given: dX (xdtype, optional) = scale[0] * dY W (+ addend),
+ * dW (optional) = dY^T X, db (optional, with dW) = column sums of dY. */
+int sgv_test_linear_head(int xdtype, const void* X, const float* W, const float* bias, const float* scale, float* Y, float* part,
+                         size_t part_floats, const float* dY, const void* addend, void* dX, float* dW, float* db, int B, int K, int O,
+                         void* stream);
+/* Linear "expand" (K small, O large): Y given: Y [B][O] of dtype = scale[0] * X W^T + bias (X [B][K], W [O][K], bias fp32).
+ * dY given (dtype): dW, db (both required), dX (optional) = scale[0] * dY W. */
+int sgv_test_linear_expand(int dtype, const float* X, const float* W, const float* bias, const float* scale, void* Y, const void* dY,
+                           float* dX, float* dW, float* db, int B, int K, int O, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

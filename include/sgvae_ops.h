@@ -64,8 +64,9 @@ int sgv_op_conv2d_tn(int dtype, const void* dy, const void* x, float* dW, int B,
                      int stride, int pad, float* slabs, int splitk, void* stream);
 int sgv_op_gemm_tn(int dtype, const void* A, const void* Bm, float* dW, int M, int N1, int N2, float* slabs, int splitk, void* stream);
 
-/* nn.GroupNorm + optional ReLU (model_cnn.py:94,98,104,187-188; act: 0 none, 3 relu) on [B][P][C], C % 8 == 0,
- * G <= 32.  sums: B*G*2 doubles written by the forward and read by the backward; sums2: same size scratch;
+/* nn.GroupNorm + optional activation (model_cnn.py:94,98,104,187-188 use act 0 none and 3 relu; the forward / apply also take
+ * 1 gelu (erf) and 2 tanh, the backward 1 gelu; any other value, tanh in the backward included, is an error) on [B][P][C],
+ * C % 8 == 0, G <= 32.  sums: B*G*2 doubles written by the forward and read by the backward; sums2: same size scratch;
  * part: sgv_op_gn_workspace_floats() floats scratch (forward and backward: per-block partial sums, combined in a fixed order --
  * no atomics, results are bitwise reproducible); dgamma/dbeta are ACCUMULATED into (+=). */
 int sgv_op_gn_fwd(int dtype, int act, const void* y, void* out, int B, int P, int C, int G, const float* gamma, const float* beta,

@@ -1157,12 +1157,13 @@ int sgv_op_chan_scale_bwd(int dtype, const void* x, const float* s, const void* 
     return OPLAUNCH_OK();
 }
 
-// GroupNorm (+ activation: 0 none, 3 relu) on [B][P][C]; sums: B*G*2 doubles (written); part: sgv_op_gn_workspace_floats floats of
+// GroupNorm (+ activation: 0 none, 1 gelu, 2 tanh, 3 relu) on [B][P][C]; sums: B*G*2 doubles (written); part: sgv_op_gn_workspace_floats floats of
 // scratch (per-block partial sums, combined in a fixed order: no atomics)
 int sgv_op_gn_fwd(int dtype, int act, const void* y, void* out, int B, int P, int C, int G, const float* gamma, const float* beta,
                   double* sums, float* part, void* stream) {
     OPCHK(y && out && gamma && beta && sums && part, "sgv_op_gn_fwd: null argument");
     OPCHK(C % 8 == 0 && G >= 1 && G <= SGV_GN_MAX_GROUPS && C % G == 0, "sgv_op_gn_fwd: C %% 8 == 0, 1 <= G <= %d, C %% G == 0 required", SGV_GN_MAX_GROUPS);
+    OPCHK(act >= 0 && act <= 3, "sgv_op_gn_fwd: act must be 0 none, 1 gelu, 2 tanh or 3 relu (got %d)", act);
     GNParams p = gn_params(y, B, P, C, G, gamma, beta, sums);
     p.out = out; p.ldout = C; p.part = part;
     if (ew_gn_fwd(dtype, act, p, ST(stream))) return sgv_set_error(-1, "sgv_op_gn_fwd: launch failed");
@@ -1186,6 +1187,7 @@ int sgv_op_gn_apply(int dtype, int act, const void* y, void* out, int B, int P, 
                     double* sums, void* stream) {
     OPCHK(y && out && gamma && beta && sums, "sgv_op_gn_apply: null argument");
     OPCHK(C % 8 == 0 && G >= 1 && G <= SGV_GN_MAX_GROUPS && C % G == 0, "sgv_op_gn_apply: C %% 8 == 0, 1 <= G <= %d, C %% G == 0 required", SGV_GN_MAX_GROUPS);
+    OPCHK(act >= 0 && act <= 3, "sgv_op_gn_apply: act must be 0 none, 1 gelu, 2 tanh or 3 relu (got %d)", act);
     GNParams p = gn_params(y, B, P, C, G, gamma, beta, sums);
     p.out = out; p.ldout = C;
     if (ew_gn_apply(dtype, act, p, ST(stream))) return sgv_set_error(-1, "sgv_op_gn_apply: launch failed");
@@ -1219,6 +1221,7 @@ static int gn_bwd_impl(int dtype, int act, const void* y, const void* dout, void
                        const float* beta, double* sums, double* sums2, float* part, float* dgamma, float* dbeta, int accumulate, void* stream) {
     OPCHK(y && dout && dy && gamma && beta && sums && sums2 && part && dgamma && dbeta, "sgv_op_gn_bwd: null argument");
     OPCHK(C % 8 == 0 && G >= 1 && G <= SGV_GN_MAX_GROUPS && C % G == 0, "sgv_op_gn_bwd: bad channel / group counts");
+    OPCHK(act == 0 || act == 1 || act == 3, "sgv_op_gn_bwd: act must be 0 none, 1 gelu or 3 relu (got %d; tanh has no backward here)", act);
     GNParams p = gn_params(y, B, P, C, G, gamma, beta, sums);
     p.sums2 = sums2; p.dout = dout; p.lddout = C; p.rscale = 1.f; p.dgamma = dgamma; p.dbeta = dbeta; p.part = part;
     p.out = dy; p.ldout = C; p.accum_affine = accumulate;

@@ -3111,4 +3111,148 @@ int sgv_test_gemm_tn(int dtype, const void* A, const void* Bm, float* dW, int M,
     return SGV_OK;
 }
 
+// ---- test hooks for the non-GEMM kernels (ew.hip): argument checks, the launcher the engine calls, sync ----
+static int ew_hook_done(int r, const char* what, void* stream) {
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
+    if (r) return fail(SGV_ERR_ARG, "%s: the launcher rejected the arguments (%d)", what, r);
+    if (le != hipSuccess) return fail(SGV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(le));
+    if (se != hipSuccess) return fail(SGV_ERR_HIP, "%s failed: %s", what, hipGetErrorString(se));
+    return SGV_OK;
+}
+static int gn_hook_shape(const char* what, int dtype, int B, int T, int C, int G, const float* work, size_t work_floats) {
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", what);
+    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", what, B, T, C);
+    if (G < 1 || G > SGV_GN_MAX_GROUPS || C % G) return fail(SGV_ERR_ARG, "%s: 1 <= G <= %d and C %% G == 0 required (C %d, G %d)", what, SGV_GN_MAX_GROUPS, C, G);
+    if (!work || work_floats < ew_gn_part_floats(B, T, C))
+        return fail(SGV_ERR_ARG, "%s: workspace of %zu floats given, %zu needed", what, work ? work_floats : (size_t)0, ew_gn_part_floats(B, T, C));
+    return SGV_OK;
+}
+static bool ld_ok(long ld, int C) { return ld >= C && ld % 8 == 0; }
+size_t sgv_test_gn_workspace_floats(int B, int T, int C) {
+    if (B < 1 || T < 1 || C < 8 || C % 8) return 0;
+    return ew_gn_part_floats(B, T, C);
+}
+int sgv_test_gn_fwd(int dtype, int act, const void* y, long ldy, const void* res, long ldres, float rscale, void* out, long ldout,
+                    const float* gamma, const float* beta, double* sums, float* work, size_t work_floats, int B, int T, int C, int G,
+                    int* path, void* stream) {
+    CHK(gn_hook_shape("sgv_test_gn_fwd", dtype, B, T, C, G, work, work_floats));
+    if (!y || !out || !gamma || !beta || !sums) return fail(SGV_ERR_ARG, "sgv_test_gn_fwd: null argument");
+    if (act < 0 || act > 3) return fail(SGV_ERR_ARG, "sgv_test_gn_fwd: act must be 0 none, 1 gelu, 2 tanh or 3 relu");
+    if (!ld_ok(ldy, C) || !ld_ok(ldout, C) || (res && !ld_ok(ldres, C))) return fail(SGV_ERR_ARG, "sgv_test_gn_fwd: row strides must be >= C and multiples of 8");
+    GNParams p;
+    p.y = y; p.ldy = ldy; p.res = res; p.ldres = ldres; p.rscale = rscale; p.out = out; p.ldout = ldout;
+    p.gamma = gamma; p.beta = beta; p.sums = sums; p.part = work; p.B = B; p.T = T; p.C = C; p.G = G; p.Cg = C / G;
+    if (path) *path = gn_fused_ok(p) ? 1 : 0;
+    return ew_hook_done(ew_gn_fwd(dtype, act, p, (hipStream_t)stream), "sgv_test_gn_fwd", stream);
+}
+int sgv_test_gn_bwd(int dtype, int act, const void* y, long ldy, const void* dout, long lddout, float rscale, float gscale,
+                    const float* gamma, const float* beta, const double* sums, void* dy, long lddy, double* sums2, float* dgamma,
+                    float* dbeta, float* dbias, float* cdot, const float* cbias, int accum_affine, float* work, size_t work_floats,
+                    int B, int T, int C, int G, int* path, void* stream) {
+    CHK(gn_hook_shape("sgv_test_gn_bwd", dtype, B, T, C, G, work, work_floats));
+    if (!y || !dout || !gamma || !beta || !sums || !dy || !sums2) return fail(SGV_ERR_ARG, "sgv_test_gn_bwd: null argument");
+    if (act != 0 && act != 1 && act != 3) return fail(SGV_ERR_ARG, "sgv_test_gn_bwd: act must be 0 none, 1 gelu or 3 relu");
+    if (!ld_ok(ldy, C) || !ld_ok(lddout, C) || !ld_ok(lddy, C)) return fail(SGV_ERR_ARG, "sgv_test_gn_bwd: row strides must be >= C and multiples of 8");
+    GNParams p;
+    p.y = y; p.ldy = ldy; p.dout = dout; p.lddout = lddout; p.rscale = rscale; p.gscale = gscale; p.out = dy; p.ldout = lddy;
+    p.gamma = gamma; p.beta = beta; p.sums = const_cast<double*>(sums); p.sums2 = sums2; p.dgamma = dgamma; p.dbeta = dbeta; p.dbias = dbias;
+    p.cdot = cdot; p.cbias = cbias; p.accum_affine = accum_affine ? 1 : 0; p.part = work;
+    p.B = B; p.T = T; p.C = C; p.G = G; p.Cg = C / G;
+    if (path) *path = gn_fused_bwd_ok(p) ? 1 : 0;
+    return ew_hook_done(ew_gn_bwd(dtype, act, p, (hipStream_t)stream), "sgv_test_gn_bwd", stream);
+}
+int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long ldy, const void* x, long ldx, void* xhat, long ldxhat,
+                        const float* gamma, const float* beta, double* sums, double* loss_sums, double* sums2, float* unit, float gscale,
+                        void* dy, long lddy, float* cdot, const float* cbias, float* work, size_t work_floats, int B, int T, int C,
+                        int G, void* stream) {
+    CHK(gn_hook_shape("sgv_test_recon_loss", dtype, B, T, C, G, work, work_floats));
+    if (!y || !x || !gamma || !beta || !sums || !loss_sums) return fail(SGV_ERR_ARG, "sgv_test_recon_loss: null argument");
+    if (loss_type < SGV_LOSS_MSE || loss_type > SGV_LOSS_HUBER) return fail(SGV_ERR_ARG, "sgv_test_recon_loss: unknown loss kind %d", loss_type);
+    if (train && (!sums2 || !unit || !dy)) return fail(SGV_ERR_ARG, "sgv_test_recon_loss: training needs sums2, unit and dy");
+    if (!ld_ok(ldy, C) || !ld_ok(ldx, C) || (xhat && !ld_ok(ldxhat, C)) || (train && !ld_ok(lddy, C)))
+        return fail(SGV_ERR_ARG, "sgv_test_recon_loss: row strides must be >= C and multiples of 8");
+    hipStream_t s = (hipStream_t)stream;
+    // forward half, as decoder_fwd: statistics, then tanh + loss (+ the backward reductions)
+    GNParams p;
+    p.B = B; p.T = T; p.C = C; p.G = G; p.Cg = C / G; p.gamma = gamma; p.beta = beta;
+    p.y = y; p.ldy = ldy; p.sums = sums; p.part = work;
+    int r = ew_gn_stats(dtype, p, s);
+    p.dout = x; p.lddout = ldx; p.loss_type = loss_type; p.loss_sums = loss_sums;
+    if (xhat) { p.out = xhat; p.ldout = ldxhat; }
+    if (train) { p.sums2 = sums2; p.dgamma = unit; p.dbeta = unit + C; p.dbias = unit + 2L * C; p.gscale = 1.0f; }
+    if (!r) r = ew_recon_loss(dtype, train ? 1 : 0, p, s);
+    if (!r && train) {
+        // backward half, as the recon-head block of the backward pass (immediate sum of the <G, W_eff> partials)
+        GNParams q;
+        q.B = B; q.T = T; q.C = C; q.G = G; q.Cg = C / G; q.gamma = gamma; q.beta = beta;
+        q.y = y; q.ldy = ldy; q.sums = sums; q.sums2 = sums2; q.dout = x; q.lddout = ldx; q.loss_type = loss_type; q.gscale = gscale;
+        q.out = dy; q.ldout = lddy; q.cdot = cdot; q.cbias = cbias; q.part = work;
+        r = ew_recon_bwd_apply(dtype, q, s);
+    }
+    return ew_hook_done(r, "sgv_test_recon_loss", stream);
+}
+int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
+                 float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
+                 int T, int C, void* stream) {
+    CHK(gn_hook_shape("sgv_test_act", dtype, B, T, C, 1, work, work_floats));
+    if (mode < 0 || mode > 2) return fail(SGV_ERR_ARG, "sgv_test_act: mode must be 0, 1 or 2");
+    if (!y || !ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "sgv_test_act: y missing or its row stride not >= C and a multiple of 8");
+    if (mode != 2 && (!out || !ld_ok(ldout, C))) return fail(SGV_ERR_ARG, "sgv_test_act: modes 0 and 1 need out (row stride >= C, multiple of 8)");
+    if (mode == 1 && (!dout || !ld_ok(lddout, C))) return fail(SGV_ERR_ARG, "sgv_test_act: mode 1 needs dout (row stride >= C, multiple of 8)");
+    if (mode == 2 && cdot && (!yf32 || !ld_ok(ldyf, C))) return fail(SGV_ERR_ARG, "sgv_test_act: mode 2 with cdot needs yf32 (row stride >= C, multiple of 8)");
+    GNParams p;
+    p.B = B; p.T = T; p.C = C; p.G = 1; p.Cg = C;
+    p.y = y; p.ldy = ldy; p.dout = dout; p.lddout = lddout; p.rscale = rscale; p.out = out; p.ldout = ldout;
+    p.dbias = dbias; p.cdot = cdot; p.cbias = cbias; p.yf32 = mode == 2 && cdot ? yf32 : nullptr; p.ldyf = ldyf; p.part = work;
+    return ew_hook_done(ew_act(dtype, mode, p, (hipStream_t)stream), "sgv_test_act", stream);
+}
+int sgv_test_latent(const float* last, const float* eps, float* z, double* kl, const float* dz, float* dlast, float coef, int B, int Z,
+                    void* stream) {
+    if (!last || !eps || B < 1 || Z < 1 || (long)B * Z > (1L << 24)) return fail(SGV_ERR_ARG, "sgv_test_latent: null argument or bad shape");
+    if (!z != !kl || !dz != !dlast || (!z && !dz)) return fail(SGV_ERR_ARG, "sgv_test_latent: give z and kl (forward) and / or dz and dlast (backward)");
+    int r = 0;
+    if (z) r = ew_latent_fwd(last, eps, z, B, Z, kl, (hipStream_t)stream);
+    if (!r && dz) r = ew_latent_bwd(last, eps, dz, dlast, B, Z, coef, (hipStream_t)stream);
+    return ew_hook_done(r, "sgv_test_latent", stream);
+}
+int sgv_test_stage(int dtype, const float* pz, const float* qz, const float* eps, const void* dec_out, long ldd, void* zs_next,
+                   long ldz, float* zmap, float std_scale, float inv_b, double* kl, double* kl_part, const void* dzs, long lddzs,
+                   void* g_p, void* g_q, float coef, int M, int C, void* stream) {
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "sgv_test_stage: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16");
+    if (!pz || !qz || !eps || M < 1 || C < 1) return fail(SGV_ERR_ARG, "sgv_test_stage: null argument or bad shape");
+    if (!zs_next && !dzs) return fail(SGV_ERR_ARG, "sgv_test_stage: give zs_next (forward) and / or dzs (backward)");
+    if (zs_next && (!dec_out || !kl || !kl_part || ldd < C || ldz < C)) return fail(SGV_ERR_ARG, "sgv_test_stage: forward needs dec_out, kl, kl_part and row strides >= C");
+    if (dzs && (!g_p || !g_q || lddzs < C)) return fail(SGV_ERR_ARG, "sgv_test_stage: backward needs g_p, g_q and a row stride >= C");
+    int r = 0;
+    if (zs_next) r = ew_stage_fwd(dtype, pz, qz, eps, dec_out, ldd, zs_next, ldz, zmap, M, C, std_scale, kl, inv_b, kl_part, (hipStream_t)stream);
+    if (!r && dzs) r = ew_stage_bwd(dtype, pz, qz, eps, dzs, lddzs, g_p, g_q, M, C, coef, (hipStream_t)stream);
+    return ew_hook_done(r, "sgv_test_stage", stream);
+}
+int sgv_test_linear_head(int xdtype, const void* X, const float* W, const float* bias, const float* scale, float* Y, float* part,
+                         size_t part_floats, const float* dY, const void* addend, void* dX, float* dW, float* db, int B, int K, int O,
+                         void* stream) {
+    if (xdtype != SGV_DTYPE_F32 && xdtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "sgv_test_linear_head: xdtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16");
+    if (!X || !W || B < 1 || O < 1 || K < 8 || K % 8) return fail(SGV_ERR_ARG, "sgv_test_linear_head: X, W, B, O >= 1 and K %% 8 == 0 required");
+    if (!Y && !dY) return fail(SGV_ERR_ARG, "sgv_test_linear_head: give Y (forward) and / or dY (backward)");
+    if (Y && (!part || part_floats < (size_t)128 * B * O)) return fail(SGV_ERR_ARG, "sgv_test_linear_head: forward needs a workspace of 128 * B * O floats");
+    if (dY && ((!dX && !dW) || (addend && !dX) || (db && !dW))) return fail(SGV_ERR_ARG, "sgv_test_linear_head: backward needs dX or dW (addend goes with dX, db with dW)");
+    int r = 0;
+    if (Y) r = ew_linear_head_fwd(xdtype, X, W, bias, scale, Y, B, K, O, part, (hipStream_t)stream);
+    if (!r && dY) r = ew_linear_head_bwd(xdtype, dY, X, W, scale, addend, dX, dW, db, B, K, O, (hipStream_t)stream);
+    return ew_hook_done(r, "sgv_test_linear_head", stream);
+}
+int sgv_test_linear_expand(int dtype, const float* X, const float* W, const float* bias, const float* scale, void* Y, const void* dY,
+                           float* dX, float* dW, float* db, int B, int K, int O, void* stream) {
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16");
+    if (!X || !W || B < 1 || O < 1 || K < 1) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: null argument or bad shape");
+    if (!Y && !dY) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: give Y (forward) and / or dY (backward)");
+    if (Y && !bias) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: forward needs bias");
+    if (dY && (!dW || !db)) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: backward needs dW and db");
+    int r = 0;
+    if (Y) r = ew_linear_expand_fwd(dtype, X, W, bias, scale, Y, B, K, O, (hipStream_t)stream);
+    if (!r && dY) r = ew_linear_expand_bwd(dtype, dY, X, W, scale, dX, dW, db, B, K, O, (hipStream_t)stream);
+    return ew_hook_done(r, "sgv_test_linear_expand", stream);
+}
+
 }  // extern "C"

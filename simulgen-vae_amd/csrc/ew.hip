@@ -1116,7 +1116,7 @@ int ew_gn_bwd_apply_act(int dtype, int act, GNParams p, hipStream_t s) {
     return 0;
 }
 // one launch per direction for small slabs; the multi-kernel path takes the shapes the fused kernels refuse
-static bool gn_fused_ok(const GNParams& p) {
+bool gn_fused_ok(const GNParams& p) {
     if (p.Cg % 8 || p.Cg / 8 > 256 || p.G > SGV_GN_MAX_GROUPS) return false;
     int cv = 1;
     while (cv < p.Cg / 8) cv <<= 1;
@@ -1127,7 +1127,7 @@ static int gn_fused_cv(const GNParams& p) {
     while (cv < p.Cg / 8) cv <<= 1;
     return cv;
 }
-static bool gn_fused_bwd_ok(const GNParams& p) {
+bool gn_fused_bwd_ok(const GNParams& p) {
     if (p.Cg % 8 || p.G > SGV_GN_MAX_GROUPS) return false;
     const int cv = gn_fused_cv(p);
     return cv <= GN_BWD_MAX_CV && (p.T + GN_BWD_THREADS / cv - 1) / (GN_BWD_THREADS / cv) <= GN_BWD_ITERS;

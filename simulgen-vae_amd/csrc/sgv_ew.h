@@ -96,8 +96,10 @@ int ew_rowsum(const float* part, int batches, int R, int n, float* out_f, double
 int ew_rowsum_d(const double* part, int R, int n, double* out_d, double scale, hipStream_t s);
 int ew_gn_stats(int dtype, GNParams p, hipStream_t s);
 // whole GroupNorm passes: one fused launch when a (sample, group) slab is small, else the multi-kernel path
-int ew_gn_fwd(int dtype, int act, GNParams p, hipStream_t s);   // stats (p.sums zeroed by the caller) + apply
+int ew_gn_fwd(int dtype, int act, GNParams p, hipStream_t s);   // stats (p.sums is written, not accumulated) + apply
 int ew_gn_bwd(int dtype, int act, GNParams p, hipStream_t s);   // reduce + finalize + dY; act in {0, 1 gelu, 3 relu}
+bool gn_fused_ok(const GNParams& p);       // ew_gn_fwd takes the one-launch slab kernel (B, T, C, G, Cg set)
+bool gn_fused_bwd_ok(const GNParams& p);   // ew_gn_bwd does
 int ew_gn_bwd_reduce_act(int dtype, int act, GNParams p, hipStream_t s);   // act: 0 none, 1 gelu, 3 relu
 int ew_gn_bwd_apply_act(int dtype, int act, GNParams p, hipStream_t s);
 int ew_gn_apply(int dtype, int act, GNParams p, hipStream_t s);

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "sgv_rccl_unique_id", "sgv_rccl_probe", "sgv_rccl_comm_count", "sgv_rccl_allreduce", "sgv_rccl_comm_init", "sgv_rccl_comm_destroy", "sgv_allreduce_grads", "sgv_set_rccl", "sgv_comm_stream",
     "sgv_augment_stage", "sgv_augment_advance",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
 ]
 
 
@@ -131,6 +132,19 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_occupy.argtypes = [vp, i32, i32, i32, C.c_longlong]
     lib.sgv_test_gemm_tn.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.sgv_test_conv_gn_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    lg, sz = C.c_long, C.c_size_t
+    lib.sgv_test_gn_workspace_floats.argtypes = [i32, i32, i32]
+    lib.sgv_test_gn_workspace_floats.restype = sz
+    lib.sgv_test_gn_fwd.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, sz, i32, i32, i32, i32, C.POINTER(i32), vp]
+    lib.sgv_test_gn_bwd.argtypes = [i32, i32, vp, lg, vp, lg, f32, f32, vp, vp, vp, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, sz,
+                                    i32, i32, i32, i32, C.POINTER(i32), vp]
+    lib.sgv_test_recon_loss.argtypes = [i32, i32, i32, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, vp, vp, f32, vp, lg, vp, vp, vp, sz,
+                                        i32, i32, i32, i32, vp]
+    lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
+    lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
+    lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
+    lib.sgv_test_linear_head.argtypes = [i32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.sgv_test_linear_expand.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.sgv_test_conv_gn_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     _lib = lib
     return lib

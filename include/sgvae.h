@@ -416,6 +416,49 @@ int sgv_test_linear_head(int xdtype, const void* X, const float* W, const float*
 int sgv_test_linear_expand(int dtype, const float* X, const float* W, const float* bias, const float* scale, void* Y, const void* dY,
                            float* dX, float* dW, float* db, int B, int K, int O, void* stream);
 
+/* Test hook for the multi-tensor optimizer / spectral-norm passes (csrc/optim.hip; tests/test_optim_kernels_gpu.py): an opaque
+ * object over a list of caller-owned device tensors.  Creation builds the descriptor and work-item tables with the same host
+ * helpers (csrc/sgv_ew.h) the engine and the parameter-set object size theirs with; every call runs the launcher the engine
+ * calls and synchronises `stream`.  Weights are fp32 [taps][rows][cols] (cols contiguous), u [rows], v_sn [taps*cols] in
+ * (tap, col) order, sigma [2] = (sigma, 1/sigma), dot [32] = the <G, W_eff> slots (the update adds them up).  rows = 0: a plain
+ * tensor of n elements (bias / affine), no spectral norm.  wc / wct: compute-dtype copies [taps][rows][cols] and the transposed,
+ * tap-flipped [taps][cols][rows], each optional; g_bf16: optional bf16 mirror of g.  tiled != 0: updated by the 64 x 64-tile
+ * pass (the engine's conv weights: that pass also writes wc / wct and the W^T u partials a following power iteration may
+ * reuse), otherwise by the flat pass.  active = 0: the power iteration leaves the entry alone.  Bias corrections follow from
+ * `step` (1-based); betas (0.9, 0.999) and eps 1e-8 are the engine's.  Scratch belongs to the object and starts as NaN.
+ * Creation rejects what the engine's layout never produces: n or cols not a multiple of 4, p / g / m / v not 16-byte aligned,
+ * tiled without spectral norm, taps * rows * cols != n. */
+typedef struct {
+    float* p; float* g; float* m; float* v;
+    long n;
+    int32_t taps, rows, cols;
+    float* u; float* v_sn; float* sigma; float* dot;
+    void* wc; void* wct;
+    const void* g_bf16;
+    int32_t tiled;
+    int32_t active;
+} sgv_optset_entry;
+typedef struct sgv_optset sgv_optset;
+int sgv_test_optset_create(int dtype, const sgv_optset_entry* entries, int n, sgv_optset** out);
+int sgv_test_optset_destroy(sgv_optset* os);
+/* train != 0: v <- norm(W^T u), u <- norm(W v), sigma = u.(W v); else sigma only.  The W v pass reads wc instead of W for bf16
+ * objects when wc is given and cols % 8 == 0.  reuse_tpart != 0 (training): the first pass skips the tiled entries, whose
+ * partials the last tiled update left behind. */
+int sgv_test_optset_power_iteration(sgv_optset* os, int train, int reuse_tpart, void* stream);
+/* dot[0] = <g, p> / sigma for the non-tiled spectrally-normalised entries (the conv kernels produce it for the tiled ones: the
+ * caller writes their slot itself); slots 1.. are left alone. */
+int sgv_test_optset_grad_dot(sgv_optset* os, void* stream);
+/* Sum of squares of the gradients wrt the original weights (chain rule applied), over all entries, from the fp32 gradients. */
+int sgv_test_optset_grad_norm(sgv_optset* os, double* gnorm_sq_out, void* stream);
+/* One AdamW step: flat pass over the non-tiled entries (gscale_dev: optional device scalar multiplied into the gradient after
+ * the norm is taken), tiled pass over the others.  grad_source selects what the tiled pass reads: 0 the fp32 g, 1 the entry's
+ * g_bf16 where given, 2 the bf16 wire copy g_wire of the fp32 arena starting at g_base (g_wire_elems elements: element k of
+ * g_wire mirrors g_base[k]).  gnorm_sq_out (optional): the squared gradient norm the two passes accumulated. */
+int sgv_test_optset_adamw(sgv_optset* os, float lr, float wd, int step, const float* gscale_dev, int grad_source, const float* g_base,
+                          const void* g_wire, size_t g_wire_elems, double* gnorm_sq_out, void* stream);
+/* wc / wct of every entry that has one, from the fp32 p. */
+int sgv_test_optset_make_copies(sgv_optset* os, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

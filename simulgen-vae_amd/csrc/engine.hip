@@ -200,9 +200,9 @@ struct sgv_engine {
     float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace
     SNDesc* sn_dev = nullptr; std::vector<SNDesc> sn_host;
     AdamDesc* adam_dev = nullptr; std::vector<AdamDesc> adam_host;
-    WorkItem *items_sn = nullptr, *items_dot = nullptr, *items_adam = nullptr, *items_copy = nullptr, *items_wct = nullptr;
+    WorkItem *items_sn = nullptr, *items_dot = nullptr, *items_adam = nullptr, *items_copy = nullptr;
     WorkItem *items_sn_unf = nullptr, *items_adam_flat = nullptr, *items_adam_2d = nullptr;
-    int n_items_sn = 0, n_items_dot = 0, n_items_adam = 0, n_items_copy = 0, n_items_wct = 0;
+    int n_items_sn = 0, n_items_dot = 0, n_items_adam = 0, n_items_copy = 0;
     int n_items_sn_unf = 0, n_items_adam_flat = 0, n_items_adam_2d = 0;
     std::vector<int> flat_off, tile_off;             // AdamW work items are sorted by gradient bucket: [bucket] -> first item
     // graph
@@ -697,9 +697,9 @@ static int build_tables(sgv_engine* e) {
     e->sn_tpart_off.clear(); e->sn_spart_off.clear();
     for (auto& l : e->layers) {
         e->sn_tpart_off.push_back(nt);
-        nt += align_up((size_t)((l.cout + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM) * l.k * l.cin, 4);
+        nt += align_up(sn_tpart_floats(l.k, l.cout, l.cin), 4);
         e->sn_spart_off.push_back(nt);
-        nt += align_up((size_t)l.k * ((l.cin + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM) * l.cout, 4);
+        nt += align_up(sn_spart_floats(l.k, l.cout, l.cin), 4);
     }
     e->n_sn_tmp = nt;
     return 0;
@@ -709,7 +709,7 @@ static int upload_tables(sgv_engine* e) {
     const int L = (int)e->layers.size();
     e->sn_host.resize(L);
     size_t to_f = 0, to_u = e->n_sn_tmp_fused, to_s = e->sn_tmp_s_off;
-    std::vector<WorkItem> i_sn, i_sn_unf, i_dot, i_adam, i_adam_flat, i_adam_2d, i_copy, i_wct, i_ts, i_ss;
+    std::vector<WorkItem> i_sn, i_sn_unf, i_dot, i_adam, i_adam_flat, i_adam_2d, i_copy, i_ts, i_ss;
     e->fin_lin_dots.clear();
     const int nbk = (int)e->buckets.size();
     std::vector<std::vector<WorkItem>> flat_b(nbk), tile_b(nbk), dot_b(nbk);
@@ -733,13 +733,12 @@ static int upload_tables(sgv_engine* e) {
         d.taps = l.k; d.rows = l.cout; d.cols = l.cin; d.active = l.used ? 1 : 0;
         e->sn_host[i] = d;
         if (l.used) {
-            const int rb = (l.cout + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM, cb = (l.cin + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM;
-            for (int c = 0; c < l.k * rb * cb; ++c) { i_sn.push_back({i, c}); if (!layer_fused_adam(l)) i_sn_unf.push_back({i, c}); }
-            for (int c = 0; c < (l.k * l.cin + 63) / 64; ++c) i_ts.push_back({i, c});
-            for (int c = 0; c < (l.cout + 63) / 64; ++c) i_ss.push_back({i, c});
+            for (int c = 0; c < sn_gemv_items(l.k, l.cout, l.cin); ++c) { i_sn.push_back({i, c}); if (!layer_fused_adam(l)) i_sn_unf.push_back({i, c}); }
+            for (int c = 0; c < sn_tsum_items(l.k, l.cin); ++c) i_ts.push_back({i, c});
+            for (int c = 0; c < sn_ssum_items(l.cout); ++c) i_ss.push_back({i, c});
         }
         if (l.has_grad && l.op == OP_LINEAR) {   // conv layers get <G,W_eff> from their dY kernels (ew.hip)
-            const long nch = (l.nw() + OPT_CHUNK - 1) / OPT_CHUNK;
+            const long nch = opt_flat_items(l.nw());
             const int bk = bucket_of(l.gw);
             fin_lin_b[bk].push_back({(const float*)(uintptr_t)dot_b[bk].size(), e->grads + l.gdot, (int)nch, 0});   // src = index inside the bucket for now, rebased below
             for (long c = 0; c < nch; ++c) dot_b[bk].push_back({i, (int)c});
@@ -763,13 +762,11 @@ static int upload_tables(sgv_engine* e) {
         a.glp = nullptr;                 // option grad_bf16 points it at the bf16 mirror arena
         const int id = (int)e->adam_host.size();
         e->adam_host.push_back(a);
-        const long nch = (n + OPT_CHUNK - 1) / OPT_CHUNK;
+        const long nch = opt_flat_items(n);
         const int bk = bucket_of(g);
         for (long c = 0; c < nch; ++c) { i_adam.push_back({id, (int)c}); if (!tiled) flat_b[bk].push_back({id, (int)c}); }
-        if (tiled) {
-            const int rt6 = (rows + 63) / 64, ct6 = (cols + 63) / 64;
-            for (int c = 0; c < taps * rt6 * ct6; ++c) tile_b[bk].push_back({id, c});
-        }
+        if (tiled)
+            for (int c = 0; c < opt_tile_items(taps, rows, cols); ++c) tile_b[bk].push_back({id, c});
         return id;
     };
     for (int i = 0; i < L; ++i) {
@@ -788,12 +785,7 @@ static int upload_tables(sgv_engine* e) {
                 id = (int)e->adam_host.size();
                 e->adam_host.push_back(a);
             }
-            const int rt = (l.cout + 31) / 32, ct = (l.cin + 31) / 32;
-            for (int c = 0; c < l.k * rt * ct; ++c) i_copy.push_back({id, c});
-            if (wct) {
-                const int rt6 = (l.cout + 63) / 64, ct6 = (l.cin + 63) / 64;
-                for (int c = 0; c < l.k * rt6 * ct6; ++c) i_wct.push_back({id, c});
-            }
+            for (int c = 0; c < opt_copy_items(l.k, l.cout, l.cin); ++c) i_copy.push_back({id, c});
         }
     }
     for (auto& g : e->gns) {
@@ -821,7 +813,6 @@ static int upload_tables(sgv_engine* e) {
     if (up(i_dot.data(), sizeof(WorkItem) * i_dot.size(), (void**)&e->items_dot)) return fail(SGV_ERR_HIP, "table upload failed");
     if (up(i_adam.data(), sizeof(WorkItem) * i_adam.size(), (void**)&e->items_adam)) return fail(SGV_ERR_HIP, "table upload failed");
     if (up(i_copy.data(), sizeof(WorkItem) * i_copy.size(), (void**)&e->items_copy)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_wct.data(), sizeof(WorkItem) * i_wct.size(), (void**)&e->items_wct)) return fail(SGV_ERR_HIP, "table upload failed");
     if (up(i_sn_unf.data(), sizeof(WorkItem) * i_sn_unf.size(), (void**)&e->items_sn_unf)) return fail(SGV_ERR_HIP, "table upload failed");
     if (up(i_adam_flat.data(), sizeof(WorkItem) * i_adam_flat.size(), (void**)&e->items_adam_flat)) return fail(SGV_ERR_HIP, "table upload failed");
     if (up(i_adam_2d.data(), sizeof(WorkItem) * i_adam_2d.size(), (void**)&e->items_adam_2d)) return fail(SGV_ERR_HIP, "table upload failed");
@@ -835,7 +826,7 @@ static int upload_tables(sgv_engine* e) {
     if (hipMemset(e->gnorm_part, 0, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "memset failed");
     e->n_items_sn_unf = (int)i_sn_unf.size(); e->n_items_adam_flat = (int)i_adam_flat.size(); e->n_items_adam_2d = (int)i_adam_2d.size();
     e->n_items_sn = (int)i_sn.size(); e->n_items_dot = (int)i_dot.size();
-    e->n_items_adam = (int)i_adam.size(); e->n_items_copy = (int)i_copy.size(); e->n_items_wct = (int)i_wct.size();
+    e->n_items_adam = (int)i_adam.size(); e->n_items_copy = (int)i_copy.size();
     return 0;
 }
 
@@ -1603,7 +1594,7 @@ int sgv_destroy(sgv_engine* e) {
     if (!e) return SGV_OK;
     hipStreamSynchronize(e->stream);
     void* ptrs[] = {e->params, e->grads, e->adam_m, e->adam_v, e->copies, e->act, e->stats, e->sn_tmp, e->sn_sigma, e->sn_dot_dummy,
-                    e->scal, e->partial, e->partial_tn, e->partial2, e->colpart2, e->gn_part2, e->gn_part, e->red, e->xpose_tmp, e->colpart, e->sn_dev, e->adam_dev, e->items_sn, e->items_dot, e->items_adam, e->items_copy, e->items_wct,
+                    e->scal, e->partial, e->partial_tn, e->partial2, e->colpart2, e->gn_part2, e->gn_part, e->red, e->xpose_tmp, e->colpart, e->sn_dev, e->adam_dev, e->items_sn, e->items_dot, e->items_adam, e->items_copy,
                     e->items_sn_unf, e->items_adam_flat, e->items_adam_2d, e->items_ts, e->items_ss, e->lin_dot_part, e->gnorm_part};
     for (void* p : ptrs) if (p) hipFree(p);
     if (e->side) { hipStreamSynchronize(e->side); hipStreamDestroy(e->side); }
@@ -1701,8 +1692,8 @@ static int refresh_copies(sgv_engine* e) {
 }
 
 static int run_sn(sgv_engine* e, int train) {
-    // tmp_t of the fused layers may already hold W^T u from the last AdamW pass (still valid: neither W nor u
-    // changed since); eval forwards never read or clobber it
+    // tpart of the fused layers may already hold the 64-row-block partials of W^T u from the last AdamW pass (still valid:
+    // neither W nor u changed since); eval forwards never read or clobber it
     const bool reuse = train && e->wtu_fresh;
     const WorkItem* it1 = reuse ? e->items_sn_unf : e->items_sn;
     const int n1 = reuse ? e->n_items_sn_unf : e->n_items_sn;
@@ -2605,14 +2596,9 @@ static int adamw_finish(sgv_engine* e) {
     ew_rowsum_d(e->gnorm_part, e->n_items_adam_flat + e->n_items_adam_2d, 1, e->scal + 15, 1.0, e->stream);
     return 0;
 }
-struct AdamCoef { float b1, b2, bc1, bc2s; };
-static AdamCoef adam_coef(const sgv_engine* e) {
-    const double b1 = 0.9, b2 = 0.999;
-    return {(float)b1, (float)b2, (float)(1.0 - pow(b1, (double)e->step)), (float)sqrt(1.0 - pow(b2, (double)e->step))};
-}
 static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, bool from_lp) {
     if (t1 <= t0) return 0;
-    const AdamCoef c = adam_coef(e);
+    const AdamCoef c = adam_coef(e->step);
     // Beside the backward pass (any stream but the main one) the pass goes out in slices of 3072 64 x 64 tiles: its
     // workgroups are small and short-lived, so while one launch lasts they refill every CU the moment a slot frees, and a kernel of
     // the main stream whose workgroup needs most of a CU's LDS (the 128-row GEMM tails, the fused Conv+GroupNorm stages) is not
@@ -2648,7 +2634,7 @@ static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, in
         if ((which & 2) && (e->bucket_packed[b] & 2)) unpack_bucket_flat(e, b, st);
     // biases, GroupNorm affine and the Linear heads: flat pass.  Conv weights: tiled pass that also writes both
     // compute copies and W_new^T u for the next forward's power iteration; buckets updated ahead (adamw_bucket_async) are skipped.
-    const AdamCoef c = adam_coef(e);
+    const AdamCoef c = adam_coef(e->step);
     const int f0 = e->flat_off[bucket_lo], f1 = e->flat_off[bucket_hi];
     if ((which & 2) && opt_adamw(e->adam_dev, e->sn_dev, e->items_adam_flat + f0, f1 - f0, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + f0, e->dt, st))
         return fail(SGV_ERR_HIP, "adamw launch failed");
@@ -3253,6 +3239,184 @@ int sgv_test_linear_expand(int dtype, const float* X, const float* W, const floa
     if (Y) r = ew_linear_expand_fwd(dtype, X, W, bias, scale, Y, B, K, O, (hipStream_t)stream);
     if (!r && dY) r = ew_linear_expand_bwd(dtype, dY, X, W, scale, dX, dW, db, B, K, O, (hipStream_t)stream);
     return ew_hook_done(r, "sgv_test_linear_expand", stream);
+}
+
+// ---- test hook for the multi-tensor optimizer / spectral-norm passes (optim.hip; tests/test_optim_kernels_gpu.py) ----
+// Descriptor and work-item tables over caller-owned device buffers, sized with the helpers of sgv_ew.h the engine and the
+// parameter-set object use; scratch (tmp_t, tmp_s, tpart, spart, the per-item partials) is the object's own and starts as NaN.
+struct sgv_optset {
+    int dt = 0;
+    std::vector<SNDesc> sn;
+    std::vector<AdamDesc> adam;
+    std::vector<int> tiled;                      // per AdamDesc
+    SNDesc* sn_dev = nullptr; AdamDesc* adam_dev = nullptr;
+    WorkItem *items_sn = nullptr, *items_sn_unf = nullptr, *items_ts = nullptr, *items_ss = nullptr, *items_dot = nullptr, *items_adam = nullptr,
+             *items_flat = nullptr, *items_tile = nullptr, *items_copy = nullptr;
+    int n_sn = 0, n_sn_unf = 0, n_ts = 0, n_ss = 0, n_dot = 0, n_adam = 0, n_flat = 0, n_tile = 0, n_copy = 0;
+    float *tmp = nullptr, *dot_part = nullptr;
+    double *gnorm_part = nullptr, *gnorm = nullptr;
+    std::vector<FinDot> fin_dots;
+};
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int optset_done(int r, const char* what, hipStream_t s) {
+    const hipError_t se = hipStreamSynchronize(s);
+    if (r) return fail(SGV_ERR_HIP, "%s: launch failed", what);
+    if (se != hipSuccess) return fail(SGV_ERR_HIP, "%s failed: %s", what, hipGetErrorString(se));
+    return SGV_OK;
+}
+static int optset_read(const double* dev, double* host, const char* what, hipStream_t s) {
+    if (hipMemcpyAsync(host, dev, sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) { hipStreamSynchronize(s); return fail(SGV_ERR_HIP, "%s: read-back failed", what); }
+    return SGV_OK;
+}
+int sgv_test_optset_destroy(sgv_optset* os) {
+    if (!os) return SGV_OK;
+    void* ptrs[] = {os->sn_dev, os->adam_dev, os->items_sn, os->items_sn_unf, os->items_ts, os->items_ss, os->items_dot, os->items_adam, os->items_flat,
+                    os->items_tile, os->items_copy, os->tmp, os->dot_part, os->gnorm_part, os->gnorm};
+    for (void* p : ptrs) if (p) hipFree(p);
+    delete os;
+    return SGV_OK;
+}
+int sgv_test_optset_create(int dtype, const sgv_optset_entry* entries, int n, sgv_optset** out) {
+    const char* me = "sgv_test_optset_create";
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
+    if (!entries || n < 1 || !out) return fail(SGV_ERR_ARG, "%s: null argument or no entries", me);
+    size_t n_tmp = 0;
+    for (int i = 0; i < n; ++i) {
+        const sgv_optset_entry& e = entries[i];
+        if (!e.p || !e.g || !e.m || !e.v) return fail(SGV_ERR_ARG, "%s: entry %d needs p, g, m and v", me, i);
+        if (!al16(e.p) || !al16(e.g) || !al16(e.m) || !al16(e.v)) return fail(SGV_ERR_ARG, "%s: entry %d: p, g, m and v must be 16-byte aligned", me, i);
+        if (e.n < 4 || e.n % 4) return fail(SGV_ERR_ARG, "%s: entry %d: n = %ld is not a positive multiple of 4", me, i, e.n);
+        if (e.rows < 0 || (e.rows == 0 && e.tiled)) return fail(SGV_ERR_ARG, "%s: entry %d: the tiled pass takes spectrally-normalised weights only (rows > 0)", me, i);
+        if (e.rows == 0 && (e.wct || e.g_bf16)) return fail(SGV_ERR_ARG, "%s: entry %d: wct and g_bf16 go with a spectrally-normalised weight", me, i);
+        if (e.wc && !al16(e.wc)) return fail(SGV_ERR_ARG, "%s: entry %d: wc must be 16-byte aligned", me, i);
+        if (e.rows > 0) {
+            if (e.taps < 1 || e.cols < 4 || e.cols % 4) return fail(SGV_ERR_ARG, "%s: entry %d: taps >= 1 and cols %% 4 == 0 required (taps %d, cols %d)", me, i, e.taps, e.cols);
+            if ((long)e.taps * e.rows * e.cols != e.n) return fail(SGV_ERR_ARG, "%s: entry %d: taps * rows * cols = %ld but n = %ld", me, i, (long)e.taps * e.rows * e.cols, e.n);
+            if (!e.u || !e.v_sn || !e.sigma || !e.dot || !al16(e.v_sn)) return fail(SGV_ERR_ARG, "%s: entry %d: a spectrally-normalised weight needs u, v_sn (16-byte aligned), sigma and dot", me, i);
+            if (e.g_bf16 && ((uintptr_t)e.g_bf16 & 7)) return fail(SGV_ERR_ARG, "%s: entry %d: g_bf16 must be 8-byte aligned", me, i);
+            n_tmp += align_up((size_t)e.taps * e.cols, 4) + align_up((size_t)e.rows, 4) + align_up(sn_tpart_floats(e.taps, e.rows, e.cols), 4) +
+                     align_up(sn_spart_floats(e.taps, e.rows, e.cols), 4);
+        }
+    }
+    sgv_optset* os = new sgv_optset();
+    os->dt = dtype;
+    auto bad = [&](const char* what) { sgv_test_optset_destroy(os); return fail(SGV_ERR_HIP, "%s: %s failed", me, what); };
+    auto nan_alloc = [&](void** dst, size_t bytes) {      // all-ones bytes are a NaN in float and in double
+        return hipMalloc(dst, bytes ? bytes : 256) == hipSuccess && hipMemset(*dst, 0xFF, bytes ? bytes : 256) == hipSuccess;
+    };
+    if (!nan_alloc((void**)&os->tmp, n_tmp * sizeof(float))) return bad("scratch allocation");
+    std::vector<WorkItem> i_sn, i_sn_unf, i_ts, i_ss, i_dot, i_adam, i_flat, i_tile, i_copy;
+    size_t toff = 0;
+    for (int i = 0; i < n; ++i) {
+        const sgv_optset_entry& e = entries[i];
+        AdamDesc a; memset(&a, 0, sizeof(a));
+        a.p = e.p; a.g = e.g; a.m = e.m; a.v = e.v; a.n = e.n; a.sn = -1; a.rows = 1; a.cols = (int)e.n; a.taps = 1;
+        a.wc = e.wc; a.wct = e.wct; a.glp = (const unsigned short*)e.g_bf16;
+        const int id = (int)os->adam.size();
+        if (e.rows > 0) {
+            SNDesc d; memset(&d, 0, sizeof(d));
+            const int si = (int)os->sn.size();
+            d.W = e.p; d.u = e.u; d.v = e.v_sn; d.sigma = e.sigma; d.dot = e.dot; d.G = e.g;
+            d.tmp_t = os->tmp + toff; toff += align_up((size_t)e.taps * e.cols, 4);
+            d.tmp_s = os->tmp + toff; toff += align_up((size_t)e.rows, 4);
+            d.tpart = os->tmp + toff; toff += align_up(sn_tpart_floats(e.taps, e.rows, e.cols), 4);
+            d.spart = os->tmp + toff; toff += align_up(sn_spart_floats(e.taps, e.rows, e.cols), 4);
+            d.wc = (dtype == SGV_DTYPE_BF16 && e.wc && e.cols % 8 == 0) ? (const void*)e.wc : nullptr;      // the engine's rule (upload_tables)
+            d.taps = e.taps; d.rows = e.rows; d.cols = e.cols; d.active = e.active ? 1 : 0;
+            os->sn.push_back(d);
+            a.sn = si; a.rows = e.rows; a.cols = e.cols; a.taps = e.taps;
+            if (e.active) {
+                for (int c = 0; c < sn_gemv_items(e.taps, e.rows, e.cols); ++c) { i_sn.push_back({si, c}); if (!e.tiled) i_sn_unf.push_back({si, c}); }
+                for (int c = 0; c < sn_tsum_items(e.taps, e.cols); ++c) i_ts.push_back({si, c});
+                for (int c = 0; c < sn_ssum_items(e.rows); ++c) i_ss.push_back({si, c});
+            }
+            if (!e.tiled) {
+                os->fin_dots.push_back({(const float*)(uintptr_t)i_dot.size(), d.dot, (int)opt_flat_items(e.n), 0});   // src = index for now, rebased below
+                for (long c = 0; c < opt_flat_items(e.n); ++c) i_dot.push_back({si, (int)c});
+            }
+            if (e.wc || e.wct)
+                for (int c = 0; c < opt_copy_items(e.taps, e.rows, e.cols); ++c) i_copy.push_back({id, c});
+        } else if (e.wc) {
+            for (int c = 0; c < opt_copy_items(1, 1, (int)e.n); ++c) i_copy.push_back({id, c});
+        }
+        os->adam.push_back(a);
+        os->tiled.push_back(e.tiled ? 1 : 0);
+        for (long c = 0; c < opt_flat_items(e.n); ++c) { i_adam.push_back({id, (int)c}); if (!e.tiled) i_flat.push_back({id, (int)c}); }
+        if (e.tiled)
+            for (int c = 0; c < opt_tile_items(e.taps, e.rows, e.cols); ++c) i_tile.push_back({id, c});
+    }
+    auto up = [&](const void* src, size_t bytes, void** dst) {
+        if (bytes == 0) { *dst = nullptr; return true; }
+        return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+#define OS_UP(vec, field, count) (up(vec.data(), sizeof(WorkItem) * vec.size(), (void**)&os->field) && ((os->count = (int)vec.size()), true))
+    if (!up(os->sn.data(), sizeof(SNDesc) * os->sn.size(), (void**)&os->sn_dev) || !up(os->adam.data(), sizeof(AdamDesc) * os->adam.size(), (void**)&os->adam_dev) ||
+        !OS_UP(i_sn, items_sn, n_sn) || !OS_UP(i_sn_unf, items_sn_unf, n_sn_unf) || !OS_UP(i_ts, items_ts, n_ts) || !OS_UP(i_ss, items_ss, n_ss) ||
+        !OS_UP(i_dot, items_dot, n_dot) || !OS_UP(i_adam, items_adam, n_adam) || !OS_UP(i_flat, items_flat, n_flat) || !OS_UP(i_tile, items_tile, n_tile) ||
+        !OS_UP(i_copy, items_copy, n_copy))
+        return bad("table upload");
+#undef OS_UP
+    if (!nan_alloc((void**)&os->dot_part, sizeof(float) * i_dot.size()) ||
+        !nan_alloc((void**)&os->gnorm_part, sizeof(double) * std::max(i_flat.size() + i_tile.size(), i_adam.size())) || !nan_alloc((void**)&os->gnorm, sizeof(double)))
+        return bad("workspace allocation");
+    for (auto& f : os->fin_dots) f.src = os->dot_part + (size_t)(uintptr_t)f.src;
+    *out = os;
+    return SGV_OK;
+}
+int sgv_test_optset_power_iteration(sgv_optset* os, int train, int reuse_tpart, void* stream) {
+    if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_power_iteration: null object");
+    if (os->sn.empty()) return SGV_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool reuse = train && reuse_tpart;         // run_sn with wtu_fresh: the tiled entries' tpart comes from the last AdamW pass
+    const int r = opt_sn_power_iteration(os->sn_dev, reuse ? os->items_sn_unf : os->items_sn, reuse ? os->n_sn_unf : os->n_sn, os->items_sn, os->n_sn, os->items_ts,
+                                         os->n_ts, os->items_ss, os->n_ss, (int)os->sn.size(), train, s);
+    return optset_done(r, "sgv_test_optset_power_iteration", s);
+}
+int sgv_test_optset_grad_dot(sgv_optset* os, void* stream) {
+    if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_grad_dot: null object");
+    hipStream_t s = (hipStream_t)stream;
+    int r = opt_sn_grad_dot(os->sn_dev, os->items_dot, os->n_dot, os->dot_part, s);
+    if (!r && !os->fin_dots.empty()) r = ew_fin_dots(os->fin_dots.data(), (int)os->fin_dots.size(), s);
+    return optset_done(r, "sgv_test_optset_grad_dot", s);
+}
+int sgv_test_optset_grad_norm(sgv_optset* os, double* gnorm_sq_out, void* stream) {
+    if (!os || !gnorm_sq_out) return fail(SGV_ERR_ARG, "sgv_test_optset_grad_norm: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    int r = opt_grad_norm(os->adam_dev, os->sn_dev, os->items_adam, os->n_adam, os->gnorm_part, s);
+    if (!r) r = ew_rowsum_d(os->gnorm_part, os->n_adam, 1, os->gnorm, 1.0, s);
+    if (!r) CHK(optset_read(os->gnorm, gnorm_sq_out, "sgv_test_optset_grad_norm", s));
+    return optset_done(r, "sgv_test_optset_grad_norm", s);
+}
+int sgv_test_optset_adamw(sgv_optset* os, float lr, float wd, int step, const float* gscale_dev, int grad_source, const float* g_base,
+                          const void* g_wire, size_t g_wire_elems, double* gnorm_sq_out, void* stream) {
+    const char* me = "sgv_test_optset_adamw";
+    if (!os) return fail(SGV_ERR_ARG, "%s: null object", me);
+    if (step < 1 || lr < 0.f) return fail(SGV_ERR_ARG, "%s: step >= 1 and lr >= 0 required", me);
+    if (grad_source < 0 || grad_source > 2) return fail(SGV_ERR_ARG, "%s: grad_source must be 0 (fp32), 1 (per-entry bf16 mirror) or 2 (bf16 wire copy)", me);
+    if (grad_source == 2) {
+        if (!g_base || !g_wire || ((uintptr_t)g_wire & 7)) return fail(SGV_ERR_ARG, "%s: the wire copy needs g_base and an 8-byte aligned g_wire", me);
+        for (size_t i = 0; i < os->adam.size(); ++i) {
+            if (!os->tiled[i]) continue;
+            const long off = os->adam[i].g - g_base;
+            if (off < 0 || off % 4 || (size_t)(off + os->adam[i].n) > g_wire_elems)
+                return fail(SGV_ERR_ARG, "%s: tiled entry %zu: its gradient must lie in [g_base, g_base + g_wire_elems) at a multiple of 4 elements", me, i);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const AdamCoef c = adam_coef(step);
+    int r = opt_adamw(os->adam_dev, os->sn_dev, os->items_flat, os->n_flat, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, os->gnorm_part, os->dt, s, gscale_dev);
+    if (!r) r = opt_adamw_sn(os->adam_dev, os->sn_dev, os->items_tile, os->n_tile, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, os->gnorm_part + os->n_flat, os->dt, s,
+                             g_base, grad_source == 2 ? g_wire : nullptr, grad_source == 1 ? 1 : 0);
+    if (!r && gnorm_sq_out) {
+        r = ew_rowsum_d(os->gnorm_part, os->n_flat + os->n_tile, 1, os->gnorm, 1.0, s);
+        if (!r) CHK(optset_read(os->gnorm, gnorm_sq_out, me, s));
+    }
+    return optset_done(r, me, s);
+}
+int sgv_test_optset_make_copies(sgv_optset* os, void* stream) {
+    if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_make_copies: null object");
+    hipStream_t s = (hipStream_t)stream;
+    return optset_done(opt_make_copies(os->adam_dev, os->items_copy, os->n_copy, os->dt, s), "sgv_test_optset_make_copies", s);
 }
 
 }  // extern "C"

@@ -473,36 +473,6 @@ __global__ __launch_bounds__(256) void make_copies_kernel(const AdamDesc* adam, 
         if (rr < a.rows && cc < a.cols) dst[(long)cc * a.rows + rr] = from_f32<T>(tile[tx][r]);
     }
 }
-// transposed copy only, sourced from the compute copy AdamW just wrote (bf16) or the master (fp32 mode):
-// wct[taps-1-tap][c][r] = w[tap][r][c]; 64x64 tiles
-template <typename T>
-__global__ __launch_bounds__(256) void make_wct_kernel(const AdamDesc* adam, const WorkItem* items) {
-    const WorkItem it = items[blockIdx.x];
-    const AdamDesc a = adam[it.desc];
-    const int ct = (a.cols + 63) >> 6, rt = (a.rows + 63) >> 6;
-    const int tap = it.chunk / (rt * ct);
-    const int rem = it.chunk - tap * rt * ct;
-    const int r0 = (rem / ct) << 6, c0 = (rem % ct) << 6;
-    __shared__ T tile[64][64 + 8];
-    const T* src = (a.wc ? reinterpret_cast<const T*>(a.wc) : reinterpret_cast<const T*>(a.p)) + (long)tap * a.rows * a.cols;
-    T* dst = reinterpret_cast<T*>(a.wct) + (long)(a.taps - 1 - tap) * a.rows * a.cols;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int r = ty; r < 64; r += 4) {
-        const int rr = r0 + r, cc = c0 + tx;
-        tile[r][tx] = (rr < a.rows && cc < a.cols) ? src[(long)rr * a.cols + cc] : (T)0.f;
-    }
-    __syncthreads();
-    for (int r = ty; r < 64; r += 4) {
-        const int cc = c0 + r, rr = r0 + tx;
-        if (rr < a.rows && cc < a.cols) dst[(long)cc * a.rows + rr] = tile[tx][r];
-    }
-}
-int opt_make_wct(const AdamDesc* adam_dev, const WorkItem* items, int n, int compute_dtype, hipStream_t s) {
-    if (n <= 0) return 0;
-    if (compute_dtype == 1) hipLaunchKernelGGL((make_wct_kernel<bf16_t>), dim3(n), dim3(256), 0, s, adam_dev, items);
-    else hipLaunchKernelGGL((make_wct_kernel<float>), dim3(n), dim3(256), 0, s, adam_dev, items);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
 int opt_make_copies(const AdamDesc* adam_dev, const WorkItem* items, int n, int compute_dtype, hipStream_t s) {
     if (n <= 0) return 0;
     if (compute_dtype == 1) hipLaunchKernelGGL((make_copies_kernel<bf16_t>), dim3(n), dim3(256), 0, s, adam_dev, items);

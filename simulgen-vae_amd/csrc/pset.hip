@@ -61,7 +61,7 @@ int sgv_pset_create(const sgv_pset_entry* entries, int n, sgv_pset** out) {
             }
             ++n_sn;
             n_tmp += al4(e.cols) + al4(e.rows);
-            n_tmp += al4((size_t)((e.rows + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM) * e.cols) + al4((size_t)((e.cols + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM) * e.rows);
+            n_tmp += al4(sn_tpart_floats(1, e.rows, e.cols)) + al4(sn_spart_floats(1, e.rows, e.cols));
         }
         total += al4(e.n);
     }
@@ -94,23 +94,22 @@ int sgv_pset_create(const sgv_pset_entry* entries, int n, sgv_pset** out) {
             d.W = e.p; d.u = e.u; d.v = e.v;
             d.tmp_t = ps->tmp + toff; toff += al4(e.cols);
             d.tmp_s = ps->tmp + toff; toff += al4(e.rows);
-            d.tpart = ps->tmp + toff; toff += al4((size_t)((e.rows + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM) * e.cols);
-            d.spart = ps->tmp + toff; toff += al4((size_t)((e.cols + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM) * e.rows);
+            d.tpart = ps->tmp + toff; toff += al4(sn_tpart_floats(1, e.rows, e.cols));
+            d.spart = ps->tmp + toff; toff += al4(sn_spart_floats(1, e.rows, e.cols));
             d.sigma = ps->sigma + 2 * si; d.dot = ps->dots + (size_t)si * SGV_DOT_SLOTS; d.G = e.g;
             d.taps = 1; d.rows = e.rows; d.cols = e.cols; d.active = 1;
             ps->sn.push_back(d);
             ps->sn_of_entry[i] = si;
             a.sn = si; a.rows = e.rows; a.cols = e.cols;
-            const int rb = (e.rows + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM, cb = (e.cols + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM;
-            for (int c = 0; c < rb * cb; ++c) i_sn.push_back({si, c});
-            for (int c = 0; c < (e.cols + 63) / 64; ++c) i_ts.push_back({si, c});
-            for (int c = 0; c < (e.rows + 63) / 64; ++c) i_ss.push_back({si, c});
-            ps->fin_dots.push_back({(const float*)(uintptr_t)i_dot.size(), d.dot, (int)((e.n + OPT_CHUNK - 1) / OPT_CHUNK), 0});
-            for (long c = 0; c < (e.n + OPT_CHUNK - 1) / OPT_CHUNK; ++c) i_dot.push_back({si, (int)c});
+            for (int c = 0; c < sn_gemv_items(1, e.rows, e.cols); ++c) i_sn.push_back({si, c});
+            for (int c = 0; c < sn_tsum_items(1, e.cols); ++c) i_ts.push_back({si, c});
+            for (int c = 0; c < sn_ssum_items(e.rows); ++c) i_ss.push_back({si, c});
+            ps->fin_dots.push_back({(const float*)(uintptr_t)i_dot.size(), d.dot, (int)opt_flat_items(e.n), 0});
+            for (long c = 0; c < opt_flat_items(e.n); ++c) i_dot.push_back({si, (int)c});
         }
         const int id = (int)ps->adam.size();
         ps->adam.push_back(a);
-        for (long c = 0; c < (e.n + OPT_CHUNK - 1) / OPT_CHUNK; ++c) i_adam.push_back({id, (int)c});
+        for (long c = 0; c < opt_flat_items(e.n); ++c) i_adam.push_back({id, (int)c});
     }
     auto up = [&](const void* src, size_t bytes, void** dst) -> bool {
         if (bytes == 0) { *dst = nullptr; return true; }
@@ -151,15 +150,14 @@ int sgv_pset_step(sgv_pset* ps, float lr, float weight_decay, float max_norm, fl
     if (!ps) return sgv_set_error(-1, "null parameter set");
     hipStream_t s = (hipStream_t)stream;
     ps->step += 1;
-    const double b1 = 0.9, b2 = 0.999;
-    const float bc1 = (float)(1.0 - pow(b1, (double)ps->step)), bc2s = (float)sqrt(1.0 - pow(b2, (double)ps->step));
+    const AdamCoef c = adam_coef(ps->step);
     // <G,W>/sigma per spectrally-normalised tensor and the gradient norm: per-work-item partials, summed in a fixed order
     if (opt_sn_grad_dot(ps->sn_dev, ps->items_dot, ps->n_items_dot, ps->dot_part, s)) return sgv_set_error(-2, "grad-dot launch failed");
     if (!ps->fin_dots.empty()) ew_fin_dots(ps->fin_dots.data(), (int)ps->fin_dots.size(), s);
     if (opt_grad_norm(ps->adam_dev, ps->sn_dev, ps->items_adam, ps->n_items_adam, ps->gnorm_part, s)) return sgv_set_error(-2, "grad-norm launch failed");
     ew_rowsum_d(ps->gnorm_part, ps->n_items_adam, 1, ps->gnorm, 1.0, s);
     hipLaunchKernelGGL(pset_clip_coef_kernel, dim3(1), dim3(1), 0, s, ps->gnorm, max_norm, ps->coef);
-    if (opt_adamw(ps->adam_dev, ps->sn_dev, ps->items_adam, ps->n_items_adam, lr, (float)b1, (float)b2, 1e-8f, weight_decay, bc1, bc2s, ps->gnorm_part, 0, s, ps->coef))
+    if (opt_adamw(ps->adam_dev, ps->sn_dev, ps->items_adam, ps->n_items_adam, lr, c.b1, c.b2, 1e-8f, weight_decay, c.bc1, c.bc2s, ps->gnorm_part, 0, s, ps->coef))
         return sgv_set_error(-2, "adamw launch failed");
     if (total_norm_host) {
         float h[2] = {0.f, 0.f};

@@ -178,7 +178,7 @@ struct WorkItem { int desc; int chunk; };
 // layout round 1's atomic accumulation chose, kept so that checkpoints and the all-reduced arena keep their offsets.
 constexpr int SGV_DOT_SLOTS = 32;
 
-// items_ts / items_ss: (desc, 64-element chunk of taps*cols / 1024-row chunk) for the fixed-order partial sums
+// items_ts / items_ss: (desc, 64-element chunk of taps*cols / 64-row chunk) for the fixed-order sums of tpart / spart
 int opt_sn_power_iteration(const SNDesc* descs_dev, const WorkItem* items1, int n1, const WorkItem* items3, int n3,
                            const WorkItem* items_ts, int n_ts, const WorkItem* items_ss, int n_ss, int ndesc, int train, hipStream_t s);
 // dot_part[i] = <G, W> / sigma of work item i (summed per layer by ew_fin_dots)
@@ -187,14 +187,34 @@ int opt_adamw(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* it
               float eps, float wd, float bc1, float bc2sqrt, double* gnorm_part, int compute_dtype, hipStream_t s, const float* gscale = nullptr);
 // gnorm_part: one double per work item (the block's sum of squared gradients), written at gnorm_part[blockIdx.x]: pass the
 // table base + the offset of `items` in the table; the caller sums the whole table in index order (ew_rowsum_d)
-// 64x64-tile AdamW for spectrally-normalised conv weights; also writes wc/wct and accumulates W_new^T u into tmp_t
+// 64x64-tile AdamW for spectrally-normalised conv weights; also writes wc/wct and the per-64-row-block partials of W_new^T u into tpart
 int opt_adamw_sn(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, float lr, float b1, float b2,
                  float eps, float wd, float bc1, float bc2sqrt, double* gnorm_sq, int compute_dtype, hipStream_t s,
                  const float* g_base = nullptr, const void* g_lp = nullptr, int desc_lp = 0);      // g_lp: gradients from the bf16 wire copy (offsets relative to g_base)
 int opt_grad_norm(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, double* gnorm_sq,
                   hipStream_t s);
 int opt_make_copies(const AdamDesc* adam_dev, const WorkItem* items, int n, int compute_dtype, hipStream_t s);
-int opt_make_wct(const AdamDesc* adam_dev, const WorkItem* items, int n, int compute_dtype, hipStream_t s);
 constexpr int OPT_CHUNK = 8192;      // elements per work item in the flat passes
 constexpr int SN_ROWS_PER_ITEM = 64; // rows per work item in the GEMV passes
 constexpr int SN_COLS_PER_ITEM = 1024;
+constexpr int SN_SUM_CHUNK = 64;     // elements of taps*cols (sn_tsum_kernel) / rows (sn_ssum_kernel) per work item of the partial sums
+constexpr int OPT_TILE = 64;         // tile edge of the tiled AdamW pass
+constexpr int COPY_TILE = 32;        // tile edge of opt_make_copies
+// Per-tensor geometry of the work-item tables and scratch buffers, [taps][rows][cols] weights.  Every host-side table builder
+// (engine.hip, pset.hip, the sgv_test_optset hook) sizes its tables with these; the kernels decode the same chunk numbering.
+inline int sn_row_blocks(int rows) { return (rows + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM; }
+inline int sn_col_blocks(int cols) { return (cols + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM; }
+inline int sn_gemv_items(int taps, int rows, int cols) { return taps * sn_row_blocks(rows) * sn_col_blocks(cols); }   // items1 / items3 of the power iteration
+inline int sn_tsum_items(int taps, int cols) { return (taps * cols + SN_SUM_CHUNK - 1) / SN_SUM_CHUNK; }               // items_ts
+inline int sn_ssum_items(int rows) { return (rows + SN_SUM_CHUNK - 1) / SN_SUM_CHUNK; }                                // items_ss
+inline long opt_flat_items(long n) { return (n + OPT_CHUNK - 1) / OPT_CHUNK; }                                         // <G,W>, flat AdamW, gradient norm
+inline int opt_tile_items(int taps, int rows, int cols) { return taps * ((rows + OPT_TILE - 1) / OPT_TILE) * ((cols + OPT_TILE - 1) / OPT_TILE); }
+inline int opt_copy_items(int taps, int rows, int cols) { return taps * ((rows + COPY_TILE - 1) / COPY_TILE) * ((cols + COPY_TILE - 1) / COPY_TILE); }
+inline size_t sn_tpart_floats(int taps, int rows, int cols) { return (size_t)sn_row_blocks(rows) * taps * cols; }
+inline size_t sn_spart_floats(int taps, int rows, int cols) { return (size_t)taps * sn_col_blocks(cols) * rows; }
+// torch.optim.AdamW defaults and the bias corrections of step `step` (1-based): bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step)
+struct AdamCoef { float b1, b2, bc1, bc2s; };
+inline AdamCoef adam_coef(long step) {
+    const double b1 = 0.9, b2 = 0.999;
+    return {(float)b1, (float)b2, (float)(1.0 - pow(b1, (double)step)), (float)sqrt(1.0 - pow(b2, (double)step))};
+}

@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
     "sgv_augment_stage", "sgv_augment_advance",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
     "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
+    "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
 
 
@@ -41,6 +43,14 @@ class SgvConfig(C.Structure):
                 ("num_filter_enc", C.c_int32 * MAX_LEVELS), ("num_node", C.c_int32), ("num_time", C.c_int32),
                 ("max_batch", C.c_int32), ("loss_type", C.c_int32), ("small", C.c_int32),
                 ("compute_dtype", C.c_int32), ("flags", C.c_int32)]
+
+
+class OptsetEntry(C.Structure):
+    """sgv_optset_entry (include/sgvae.h): one tensor of the optimizer test hook, device pointers"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_long),
+                ("taps", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("u", C.c_void_p), ("v_sn", C.c_void_p), ("sigma", C.c_void_p), ("dot", C.c_void_p),
+                ("wc", C.c_void_p), ("wct", C.c_void_p), ("g_bf16", C.c_void_p), ("tiled", C.c_int32), ("active", C.c_int32)]
 
 
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
@@ -146,6 +156,13 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_linear_head.argtypes = [i32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.sgv_test_linear_expand.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.sgv_test_conv_gn_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.sgv_test_optset_create.argtypes = [i32, C.POINTER(OptsetEntry), i32, C.POINTER(vp)]
+    lib.sgv_test_optset_destroy.argtypes = [vp]
+    lib.sgv_test_optset_power_iteration.argtypes = [vp, i32, i32, vp]
+    lib.sgv_test_optset_grad_dot.argtypes = [vp, vp]
+    lib.sgv_test_optset_grad_norm.argtypes = [vp, C.POINTER(C.c_double), vp]
+    lib.sgv_test_optset_adamw.argtypes = [vp, f32, f32, i32, vp, i32, vp, vp, sz, C.POINTER(C.c_double), vp]
+    lib.sgv_test_optset_make_copies.argtypes = [vp, vp]
     _lib = lib
     return lib
 

@@ -20,8 +20,6 @@
 #include <string.h>
 #include <math.h>
 
-int sgv_set_error(int code, const char* fmt, ...);   // engine.hip: fills sgv_last_error()
-
 static inline int cdivi(long a, long b) { return (int)((a + b - 1) / b); }
 #define OPCHK(cond, ...) do { if (!(cond)) return sgv_set_error(-1, __VA_ARGS__); } while (0)
 #define OPLAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : sgv_set_error(-2, "kernel launch failed in %s", __func__))

@@ -1,34 +1,16 @@
 // libsgvae engine: parameter/optimizer arenas, layer graph of the hierarchical VAE, forward /
-// backward orchestration on one HIP stream, and the C ABI of include/sgvae.h.
+// backward orchestration on one HIP stream, and the engine's part of the C ABI of include/sgvae.h.
+// Beside it, sharing engine_internal.h: engine_comm.hip (RCCL), engine_streams.hip (auxiliary streams), engine_input.hip, test_hooks.hip.
 //
 // Graph restated from the reference (channels-last, weights [tap][Cout][Cin]):
 //   VAE.forward modules/VAE_network.py:79-121 ; Encoder modules/encoder.py:96-167 ;
 //   Decoder modules/decoder.py:84-223 ; blocks modules/common.py:78-162 ; losses modules/losses.py:8-48 ;
 //   training step modules/train.py:139-168.
 // The backward pass is written out by hand (the reference uses autograd).
-#include <dlfcn.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
+#include "engine_internal.h"
 
-#include <functional>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../../include/sgvae.h"
-#include "sgv_ew.h"
-
+// ---- error state of the library: one thread-local message, written through sgv_set_error by every translation unit ----
 static thread_local char g_err[1024] = "";
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-// same, for the other translation units of the library (cnn.hip)
 int sgv_set_error(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -36,235 +18,9 @@ int sgv_set_error(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) return fail(SGV_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define CHK(x)                                  \
-    do {                                        \
-        int r_ = (x);                           \
-        if (r_ != 0) return r_ < 0 ? r_ : -r_;  \
-    } while (0)
-
-static const size_t NPOS = (size_t)-1;
-
-struct Tensor {
-    void* p = nullptr;
-    int C = 0;
-    long ld = 0;
-    bool f32 = false;
-};
-
-enum { OP_CONV = 0, OP_CONVT = 1, OP_LINEAR = 2 };
-enum { LIN_NONE = 0, LIN_HEAD = 1, LIN_EXPAND = 2 };
-
-struct Layer {
-    std::string prefix;
-    int op = OP_CONV, cin = 0, cout = 0, k = 1;
-    bool used = true, has_grad = true, need_wct = true;
-    int lin_kind = LIN_NONE, lin_C = 0;      // head: K = lin_C*T; expand: O = lin_C*T
-    size_t w = NPOS, b = NPOS, u = NPOS, v = NPOS;  // param arena (floats)
-    size_t gw = NPOS, gb = NPOS, gdot = NPOS;       // grad arena (floats); gdot: <G,W_eff> scalar (small zone)
-    size_t wc = NPOS, wct = NPOS;                   // compute-copy arena (elements)
-    int sn = -1;
-    int splitk_tn = 1;
-    size_t dot_part = NPOS;                         // per-block <G,W_eff> partials of the layer's dY kernel (e->red arena)
-    size_t col_part = NPOS;                         // per-block column sums of dY (bias gradient of a conv without GroupNorm), same arena
-    bool lp = false;                                // option grad_bf16: this layer's weight gradient lives in the bf16 mirror arena (fixed at creation:
-                                                    //   its weight-gradient GEMM takes the 256 x 256 kernel at the engine's full batch)
-    long nw() const { return (long)cout * cin * k; }
-};
-struct GNLayer {
-    std::string prefix;
-    int C = 0, G = 1;
-    bool used = true, has_grad = true;
-    size_t gamma = NPOS, beta = NPOS, ggamma = NPOS, gbeta = NPOS;
-    size_t ptot = NPOS;                             // [B][3][C] per-sample column totals of the backward pass (e->red arena)
-};
-struct Stage {
-    int layer = -1, gn = -1, act = 0;
-    bool pre_gelu = false, out_f32 = false;
-    Tensor pre, y, a, dy, da, dpre;
-    size_t sums = NPOS, sums2 = NPOS;   // stats arena (doubles)
-};
-struct Block {
-    std::vector<Stage> st;
-    bool residual = false;
-};
-struct StateEntry {
-    std::string name;
-    int kind;  // 0 bias,1 weight_orig,2 u,3 v,4 gn w,5 gn b
-    int layer = -1, gn = -1;
-    std::vector<int64_t> shape;
-    bool has_grad;
-    long count() const { long n = 1; for (auto s : shape) n *= s; return n; }
-};
-
-struct TimerRec { hipEvent_t a, b; int tag; };
-
-constexpr double DW_SIDE_MAX_GF = 250.0;   // weight-gradient GEMMs up to this size go to the side stream (sgv_engine::side)
-constexpr long CONVGN_MAXK = 4096;         // widest K * taps of a fused Conv -> GroupNorm -> GELU stage (sgv_engine::use_convgn)
-
-struct sgv_engine {
-    sgv_config cfg;
-    hipStream_t stream = nullptr;
-    int dt = 0;         // compute dtype
-    size_t esz = 4;     // bytes per compute element
-    int n = 0, n_st = 0, T = 0, N = 0, Z = 0, H = 0, maxB = 0;
-    std::vector<int> enc, dec;
-    std::vector<Layer> layers;
-    std::vector<GNLayer> gns;
-    std::vector<StateEntry> entries;
-    std::map<std::string, int> entry_index;
-    // arenas
-    float* params = nullptr; size_t n_params = 0;
-    float* grads = nullptr; size_t n_grads = 0, n_grads_w = 0;   // weights zone first, small zone after
-    float* adam_m = nullptr; float* adam_v = nullptr;
-    char* copies = nullptr; size_t n_copies = 0;
-    char* act = nullptr; size_t act_bytes = 0, act_used = 0;
-    double* stats = nullptr; size_t n_stats = 0, n_stats_fwd = 0;  // [fwd sums | bwd sums2]
-    float* sn_tmp = nullptr; size_t n_sn_tmp = 0;   // [tmp_t of fused layers][tmp_t of the others][tmp_s of all]
-    size_t n_sn_tmp_fused = 0, sn_tmp_s_off = 0;
-    bool wtu_fresh = false;                          // tpart of the fused layers holds the W^T u partials for the current weights
-    std::vector<size_t> sn_tpart_off, sn_spart_off;  // per layer: offsets of the power-iteration partials inside sn_tmp
-    WorkItem* items_ts = nullptr; WorkItem* items_ss = nullptr; int n_items_ts = 0, n_items_ss = 0;
-    float* lin_dot_part = nullptr;                   // per-work-item <G,W>/sigma partials of the Linear layers
-    std::vector<FinDot> fin_lin_dots;
-    std::vector<int> dot_off, fin_lin_off;           // [bucket] -> first Linear <G,W> work item / first fin_lin_dots entry (tables sorted by bucket)
-    double* gnorm_part = nullptr; int n_gnorm_part = 0;   // per-work-item sums of squared gradients of the AdamW passes
-    float* sn_sigma = nullptr;
-    float* sn_dot_dummy = nullptr;
-    double* scal = nullptr;        // device doubles: [0..1] loss sums, [2] kl, [3..] kl2, [15] grad norm^2
-    float* partial = nullptr; size_t partial_floats = 0;
-    // weight-gradient GEMMs are off the critical path of backward: the SMALL ones (<= 250 GFLOP, i.e. everything but
-    // the five largest layers) run on a second stream next to the dX GEMMs and normalisation passes of the following
-    // layers, which fills the CUs those 100-200-block launches leave idle (measured 16.14 -> 15.83 ms/step).  Putting
-    // the big ones there too loses 2.5 %: they fill every CU on their own and co-running kernels evict each other's
-    // L2 tiles.  Option "dw_side_stream" / SGV_DW_SIDE=0 turns it off; kernel-timing passes always run on one stream.
-    hipStream_t side = nullptr;
-    std::vector<char> aug_host[4]; int aug_turn = 0;                  // staging of sgv_augment_collate's control arrays
-    void* comm = nullptr; hipStream_t comm_stream = nullptr;          // native RCCL path (sgv_set_rccl)
-    std::vector<hipEvent_t> bucket_done; std::vector<char> bucket_pending;
-    // data-parallel wire format of the weight buckets: 0 = the fp32 arena itself, 1 = a bf16 copy (packed at the bucket's fire point,
-    // averaged by the collective, unpacked into the arena in front of the bucket's AdamW).  The small bucket always travels in fp32.
-    int payload_bf16 = 0; void* grads_lp = nullptr; std::vector<char> bucket_packed;
-    // option "grad_bf16" (bf16 engines, single-GPU path: no communicator, no bucket callback): the 256 x 256 weight-gradient kernel
-    // stores its result as bf16 into the mirror arena grads_lp and the AdamW pass reads it there (AdamDesc::glp) -- 4 B less
-    // written and read per parameter of the big layers.  The fp32 arena of those layers is refreshed on demand (lp_sync) for the
-    // calls that read it (sgv_export_grad, sgv_grad_norm).
-    // With the bf16 wire format of the data-parallel step the same kernel writes the wire copy directly (bit for bit what the pack
-    // pass produced from the fp32 result; that pass then skips those layers).
-    int grad_bf16 = 0;
-    bool lp_classified = false;
-    std::vector<char> lp_dirty;          // per layer: its gradient of the last backward was stored as bf16 into grads_lp (not into the fp32 arena)
-    // sgv_scale_grads / sgv_grad_buffer changed or exposed the fp32 arena after an lp_sync: until the next backward the AdamW pass
-    // reads the fp32 arena for every layer (the mirror no longer holds the gradient)
-    bool lp_fp32 = false;
-    std::vector<std::vector<int>> bucket_lp_layers;     // per weight bucket: its Layer::lp layers in arena order
-    bool dw_chunk_direct = false;        // chunked first-layer gradient (data-parallel): the chunk GEMMs write the wire copy themselves
-    // data-parallel optimizer overlap: the <G,W_eff> scalars of a weight bucket's layers sit together at the head of the small zone
-    // (bucket_dots[b] = their range), so they can be averaged WITH the bucket instead of with the small bucket at the end of backward;
-    // the bucket's conv-weight AdamW then runs on `opt` as soon as both collectives have landed, under the rest of backward
-    // (sgv_adamw_bucket_async; the engine's own RCCL path does it by itself in sgv_backward_step).  bucket_updated[b]: done this step.
-    std::vector<std::pair<size_t, size_t>> bucket_dots; size_t dots_total = 0;
-    hipStream_t opt = nullptr; bool opt_dirty = false, adam_open = false;
-    hipStream_t comm_own = nullptr;                   // sgv_comm_stream: a probed communication stream the engine owns
-    hipStream_t wire = nullptr; int use_wire = 0;     // callback path: buckets are complete (and packed) on this stream, not on the engine stream
-    std::vector<char> bucket_updated;
-    int ddp_early = getenv("SGV_DDP_EARLY") ? atoi(getenv("SGV_DDP_EARLY")) : 1;
-    // the last weight bucket (the first encoder layer: 97 M gradients that exist only when backward ends) is produced, exchanged and
-    // updated in row chunks of the weight-gradient GEMM: chunk c's pack / all-reduce / AdamW run under chunk c + 1's GEMM, so only
-    // the last chunk's exchange is exposed (engine-issued path; SGV_DDP_LAST_CHUNKS=1 turns it off).  Two chunks: 512 rows keep the
-    // GEMM's 128 x 256 tiles at whole rounds of the chip, four chunks of 256 rows cost 27 % of the GEMM
-    // BASELINE configs[3] "+ grad-checkpoint": what recomputing the GroupNorm + GELU outputs in backward would cost.  With the option on,
-    // block_bwd regenerates every stage's activation a = act(GN(y)) from the stored pre-normalisation map and statistics right before
-    // the stage's backward reads it (one extra streaming pass per stage).  The buffers themselves stay allocated -- this times the
-    // recompute, it does not free the memory (sgv_memory_info's "activations" minus what recompute_bytes reports is what a
-    // recompute build would keep); `use_checkpointing` stays forced off as in the reference
-    bool recompute_act = false;
-    size_t recompute_bytes = 0;
-    int ddp_last_chunks = getenv("SGV_DDP_LAST_CHUNKS") ? atoi(getenv("SGV_DDP_LAST_CHUNKS")) : 2;
-    double ddp_chunk_min_gf = getenv("SGV_DDP_CHUNK_MIN_GF") ? atof(getenv("SGV_DDP_CHUNK_MIN_GF")) : 250.0;   // tests lower it to chunk a small first layer
-    int dw_chunks = 1, dw_chunk_layer = -1;
-    std::function<int(int, int, int, int)> dw_chunk_hook;        // (chunk, chunks, first row, end row) after the chunk's GEMM is enqueued
-    // bf16 wire format: the conv-weight AdamW reads a packed bucket straight from the averaged bf16 copy (no unpack pass; the fp32
-    // arena keeps this rank's own gradients); only the few weights of a bucket that the flat pass updates (Linear heads:
-    // bucket_flat_w) are unpacked.  bucket_packed[b]: bit 0 = conv-weight part still packed, bit 1 = flat part still packed.
-    std::vector<std::vector<std::pair<size_t, size_t>>> bucket_flat_w;
-    float* partial_tn = nullptr; size_t partial_tn_floats = 0;
-    std::vector<hipEvent_t> ev_pool; size_t ev_next = 0;
-    bool use_side = true, side_dirty = false;
-    float* xpose_tmp = nullptr; size_t xpose_floats = 0;
-    float* recon_unit = nullptr;   // [3][N] unit-scale dgamma/dbeta/dbias of the recon head
-    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace
-    SNDesc* sn_dev = nullptr; std::vector<SNDesc> sn_host;
-    AdamDesc* adam_dev = nullptr; std::vector<AdamDesc> adam_host;
-    WorkItem *items_sn = nullptr, *items_dot = nullptr, *items_adam = nullptr, *items_copy = nullptr;
-    WorkItem *items_sn_unf = nullptr, *items_adam_flat = nullptr, *items_adam_2d = nullptr;
-    int n_items_sn = 0, n_items_dot = 0, n_items_adam = 0, n_items_copy = 0;
-    int n_items_sn_unf = 0, n_items_adam_flat = 0, n_items_adam_2d = 0;
-    std::vector<int> flat_off, tile_off;             // AdamW work items are sorted by gradient bucket: [bucket] -> first item
-    // graph
-    std::vector<Block> encA, encR, decU, decD, decP1, decP2, decX, decQ1, decQ2;
-    Block decS, recon;
-    std::vector<int> xs_lin, xs_exp;   // layer ids: encoder.xs_linear.i ; decoder.xs_sequence.i.0
-    int last_lin = -1, start_lin = -1;
-    // tensors
-    Tensor x_in, xhat, sbuf, d_sbuf, dy_recon;
-    // Prefetched augmentation (sgv_augment_stage / sgv_augment_advance): the NEXT batch is built in the spare input buffer on a
-    // stream of its own, in launches of a few samples, beside the short kernels that follow the first encoder layer's GEMM (the
-    // chip's HBM is idle there); the reference hides the same work in DataLoader worker processes.
-    Tensor x_bufs[2];
-    int x_cur = 0;
-    hipStream_t aug_stream = nullptr;
-    hipEvent_t aug_done = nullptr, aug_gate = nullptr, x_free[2] = {nullptr, nullptr};
-    bool x_free_set[2] = {false, false};
-    bool aug_staged = false, aug_fired = false, aug_pending = false;   // staged: control arrays on the device; fired: kernels enqueued; pending: the current batch's kernels may still run
-    const void* aug_data = nullptr;
-    int aug_next_batch = 0;
-    char* aug_ctl = nullptr;           // control arrays of the staged batch
-    std::vector<Tensor> enc_h, d_h, enc_a_dummy, zs, dzs, cat, dcat, dec_out, d_out, d_u, d_pres, d_qres, d_outp, gp, gq, xl, d_xl;
-    std::vector<float*> xs_raw, d_xs_raw, eps, zmap;
-    std::vector<int> eps_set;
-    float *last = nullptr, *d_last = nullptr, *zlat = nullptr, *d_z = nullptr;
-    int batch = 0;
-    bool have_fwd = false, fwd_train = false, write_xhat = true, copies_fresh = false;
-    int deterministic = 1;             // 1: no float-atomic accumulation anywhere in the step; option "deterministic"
-    float* gn_part = nullptr; size_t gn_part_floats = 0;   // per-(tile, wave) GroupNorm partial sums of the 256x256 GEMM epilogue
-    // deterministic reductions: block partials that nobody needs before the optimizer (GroupNorm affine / bias gradients,
-    // <G,W_eff>) stay in this arena until the bucket they belong to is released, then two table-driven passes sum them
-    // second compute lane: the posterior branch of a decoder stage (xs lift, condition_xz) is independent of the prior branch
-    // (condition_z) between the residual block and the KL / reparameterisation kernel, in forward and in backward; both are chains
-    // of small kernels that leave most of the chip idle, so they run side by side on two streams with workspaces of their own
-    hipStream_t lane2 = nullptr; float* partial2 = nullptr; float* colpart2 = nullptr; float* gn_part2 = nullptr;
-    hipEvent_t lane_fork = nullptr, lane_join = nullptr;
-    hipEvent_t tail_fork = nullptr, tail_join = nullptr;      // concurrent 128-row tail of a 256 x 256 launch (launch_nt)
-    bool coll_inflight = false;        // data-parallel backward, from the first released bucket on: a collective's channel workgroups may hold CUs
-    int* tn_sched = nullptr;           // 8 x 520 ints: work-stealing state of the 256 x 256 weight-gradient launches issued while coll_inflight
-    unsigned tn_sched_next = 0;
-    int use_lanes = getenv("SGV_LANES") ? atoi(getenv("SGV_LANES")) : 1;
-    // small Conv1d -> GroupNorm -> GELU stages in one launch (convgn.hip, K * taps <= CONVGN_MAXK); SGV_CONVGN=0 restores GEMM +
-    // combine + GroupNorm kernels
-    int use_convgn = getenv("SGV_CONVGN") ? atoi(getenv("SGV_CONVGN")) : 1;
-    float* red = nullptr; size_t red_floats = 0;
-    std::vector<FinDot> fin_dots; std::vector<FinAffine> fin_affine;
-    int dot_counts[512];
-    uint64_t seed = 0x5347564145ull, draw = 0;
-    int shard_rank = 0, shard_world = 1;        // sgv_set_shard: sample b of this engine's batch is sample b * world + rank of the global batch
-    long step = 0;
-    float scalars_host[SGV_MAX_SCALARS];
-    sgv_bucket_cb cb = nullptr; void* cb_user = nullptr;
-    std::vector<std::pair<size_t, size_t>> buckets;   // (offset, count) in grad arena, backward order
-    bool timing = false, timing_detail = false;
-    std::vector<TimerRec> timers;
-    std::map<std::string, int> tag_ids;
-    std::vector<std::string> tag_names;
-    int use_tr = 1;
-};
+extern "C" const char* sgv_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------------
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static int gn_groups(int c) { int g = c / 4; if (g < 1) g = 1; if (g > 8) g = 8; return g; }
 
 struct Builder {
@@ -866,6 +622,13 @@ struct ScopedTimer {
     }
     ~ScopedTimer() { if (on) { end_now(); e->timers.push_back(r); } }
 };
+// total time and number of the recorded launches that carry `tag` (none carries a negative one)
+static void tag_total(sgv_engine* e, int tag, float* total_ms, int* calls) {
+    float tot = 0.f; int n = 0;
+    for (auto& t : e->timers) if (t.tag == tag) { float ms = 0.f; hipEventElapsedTime(&ms, t.a, t.b); tot += ms; ++n; }
+    if (total_ms) *total_ms = tot;
+    if (calls) *calls = n;
+}
 
 // ------------------------------------------------------------------------------------------------
 // op wrappers
@@ -977,6 +740,11 @@ __global__ void sum_slabs_kernel(float* out, const float* partial, int splitk, l
         out[i] = v;
     }
 }
+// its one launcher (the weight-gradient path below, sgv_test_gemm_tn): four elements per thread (grid-stride either way)
+void sum_slabs(float* out, const float* partial, int splitk, long n, hipStream_t stream) {
+    int blocks = (int)((n / 4 + 255) / 256); if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks), dim3(256), 0, stream, out, partial, splitk, n);
+}
 static hipEvent_t next_event(sgv_engine* e) {
     if (e->ev_next == e->ev_pool.size()) {
         hipEvent_t ev = nullptr;
@@ -985,18 +753,22 @@ static hipEvent_t next_event(sgv_engine* e) {
     }
     return e->ev_pool[e->ev_next++];
 }
-// make the main stream wait for every weight-gradient GEMM issued so far on the side stream
-static int join_side(sgv_engine* e) {
-    if (!e->side_dirty) return 0;
+// `waiter` waits for everything enqueued on `of` so far
+int stream_wait(sgv_engine* e, hipStream_t waiter, hipStream_t of) {
     hipEvent_t ev = next_event(e);
     if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
-    HIPCHK(hipEventRecord(ev, e->side));
-    HIPCHK(hipStreamWaitEvent(e->stream, ev, 0));
+    HIPCHK(hipEventRecord(ev, of));
+    HIPCHK(hipStreamWaitEvent(waiter, ev, 0));
+    return 0;
+}
+// make the main stream wait for every weight-gradient GEMM issued so far on the side stream
+int join_side(sgv_engine* e) {
+    if (!e->side_dirty) return 0;
+    CHK(stream_wait(e, e->stream, e->side));
     e->side_dirty = false;
     return 0;
 }
 // ---- bf16 weight gradients straight from the 256 x 256 kernel (see the grad_bf16 member) ----
-static bool comm_is_single(void* comm);
 // which layers: those whose weight-gradient GEMM takes that kernel, unsplit, at the engine's full batch, and whose mirror range the
 // launcher accepts as its bf16 output (alignment, offset ranges: a refused launch must never be left to write the mirror) -- fixed
 // once: the AdamW table points the layer at the mirror arena
@@ -1078,10 +850,7 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
     hipStream_t st = e->stream;
     float* slabs = e->partial;
     if (side) {
-        hipEvent_t ev = next_event(e);
-        if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
-        HIPCHK(hipEventRecord(ev, e->stream));
-        HIPCHK(hipStreamWaitEvent(e->side, ev, 0));
+        CHK(stream_wait(e, e->side, e->stream));
         st = e->side; slabs = e->partial_tn; e->side_dirty = true;
     } else if ((size_t)sk * nw > e->partial_floats) sk = 1;
     if (e->dw_chunks > 1 && (int)(&l - e->layers.data()) == e->dw_chunk_layer && sk == 1 && !side && l.k == 1 && l.cout % (128 * e->dw_chunks) == 0) {
@@ -1125,8 +894,7 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
         p.splitk = sk; p.out = slabs; p.out_slab_stride = nw;
         if (launch_gemm_tn(e->dt, p, st)) return fail(SGV_ERR_ARG, "gemm_tn launch failed for %s", l.prefix.c_str());
         tm.end_now();
-        int blocks = (int)((nw / 4 + 255) / 256); if (blocks > 4096) blocks = 4096;     // four elements per thread (grid-stride either way)
-        hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks), dim3(256), 0, st, G, slabs, sk, nw);
+        sum_slabs(G, slabs, sk, nw, st);
         if (l.lp && grad_lp_active(e)) ew_pack_bf16(G, (char*)e->grads_lp + 2 * l.gw, nw, st);
         e->lp_dirty[li_] = 0;
     }
@@ -1348,147 +1116,6 @@ static int block_bwd(sgv_engine* e, Block& b, const Tensor& in, const Tensor& dO
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-const char* sgv_last_error(void) { return g_err; }
-
-// Auxiliary streams.  The HIP runtime maps streams onto a handful of hardware queues PER PRIORITY LEVEL (GPU_MAX_HW_QUEUES = 4),
-// round-robin in creation order, and two streams on one queue run their kernels strictly one after the other: a kernel trace showed
-// the second compute lane and the collective's stream sharing the main stream's queue (no overlap at all) depending on how many
-// streams the process had created before.  Every auxiliary stream has the main stream's (normal) priority and is probed instead:
-// streams of another priority level come from another queue pool, but measured no faster.
-// ---- which hardware queue did a new stream land on? ----
-// Not visible through the API, but observable: a kernel on stream b cannot finish while a kernel on stream a spins if both sit
-// on one queue.  probe_spin_kernel waits on the constant-rate clock for a bounded time (always exits), probe_nop_kernel is empty.
-__global__ void probe_spin_kernel(long long ticks) {
-    const long long t0 = (long long)wall_clock64();
-    while ((long long)wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
-}
-__global__ void probe_nop_kernel() {}
-// One probe: 1 = kernels of a and b run concurrently (different hardware queues), 0 = b's kernel finished only after a's, -1 = API
-// error.  Decided by the ORDER of two device-side timestamps (the event behind the spin on a, the event behind the empty kernel
-// on b), not by host wall time: if b's kernel ended while a was still spinning, the queues are different.
-static int streams_overlap_once(hipStream_t a, hipStream_t b, long long ticks) {
-    hipEvent_t e0 = nullptr, ea = nullptr, eb = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess) return -1;
-    if (hipEventCreate(&ea) != hipSuccess) { hipEventDestroy(e0); return -1; }
-    if (hipEventCreate(&eb) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(ea); return -1; }
-    int res = -1;
-    if (hipEventRecord(e0, a) == hipSuccess) {
-        hipLaunchKernelGGL(probe_spin_kernel, dim3(1), dim3(64), 0, a, ticks);
-        if (hipEventRecord(ea, a) == hipSuccess) {
-            hipLaunchKernelGGL(probe_nop_kernel, dim3(1), dim3(64), 0, b);
-            float ta = 0.f, tb = 0.f;       // both measured from e0, which precedes both kernels: never a negative interval
-            if (hipEventRecord(eb, b) == hipSuccess && hipStreamSynchronize(b) == hipSuccess && hipStreamSynchronize(a) == hipSuccess &&
-                hipEventElapsedTime(&ta, e0, ea) == hipSuccess && hipEventElapsedTime(&tb, e0, eb) == hipSuccess)
-                res = tb < ta - 0.02f ? 1 : 0;        // b's kernel was over >= 20 us before the spin ended
-        }
-    }
-    hipStreamSynchronize(a);
-    hipEventDestroy(e0); hipEventDestroy(ea); hipEventDestroy(eb);
-    (void)hipGetLastError();
-    return res;
-}
-// true: kernels of a and b run concurrently; on any API error: true (no reason to reject the stream).  The candidate gets an untimed
-// first launch (a new stream's first launch can take longer than the spin), and a "shares a queue" verdict is confirmed once with a
-// ten times longer spin: a host that needed more than 300 us to submit the empty kernel (loaded box, profiler attached) would
-// otherwise reject a good candidate.
-static bool streams_overlap(hipStream_t a, hipStream_t b) {
-    hipLaunchKernelGGL(probe_nop_kernel, dim3(1), dim3(64), 0, b);
-    if (hipStreamSynchronize(b) != hipSuccess) { (void)hipGetLastError(); return true; }
-    int r = streams_overlap_once(a, b, 30000LL);              // 300 us at the 100 MHz constant clock
-    if (r == 0) r = streams_overlap_once(a, b, 300000LL);     // 3 ms
-    return r != 0;
-}
-// A new auxiliary stream that shares its hardware queue with none of `avoid`.  The runtime gives a new stream the least-loaded
-// queue (round-robin in a fresh process; in a process that has created and destroyed many streams the main stream's queue can be the
-// emptiest for many creations in a row), so the rejected candidates stay alive until a keeper is found -- every reject loads the
-// queue it sits on and steers the next candidate elsewhere -- and up to 32 candidates are tried (0.3 ms each per stream to avoid).
-// If every candidate collides the last one is kept.
-static hipError_t make_aux_stream(hipStream_t* out, const char* label, std::initializer_list<hipStream_t> avoid) {
-    std::vector<hipStream_t> rejected;
-    hipStream_t s = nullptr;
-    hipError_t rc = hipSuccess;
-    constexpr int kAttempts = 32;
-    for (int attempt = 0; attempt < kAttempts; ++attempt) {
-        s = nullptr;
-        rc = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (rc != hipSuccess) break;
-        bool ok = true;
-        for (hipStream_t a : avoid) if (a != s && !streams_overlap(a, s)) { ok = false; break; }      // a == nullptr is the null stream: probed too
-        if (getenv("SGV_STREAM_LOG")) fprintf(stderr, "[sgvae] %s stream: candidate %d %s\n", label, attempt, ok ? "kept" : "shares a hardware queue with a stream it must not, rejected");
-        if (ok) break;
-        if (attempt == kAttempts - 1) {
-            // kept all the same: the engine stays correct, but this stream's kernels now run between the other stream's instead of
-            // beside them (no lane / optimizer / communication overlap) -- say so once, the bench line reports it as well
-            fprintf(stderr, "[sgvae] warning: %s stream: all %d candidate streams share a hardware queue with a stream they must avoid "
-                            "(GPU_MAX_HW_QUEUES too small for this process?); overlap on this stream is lost\n", label, kAttempts);
-            break;
-        }
-        rejected.push_back(s);
-    }
-    for (hipStream_t r : rejected) hipStreamDestroy(r);
-    *out = rc == hipSuccess ? s : nullptr;
-    return rc;
-}
-static hipStream_t ensure_opt(sgv_engine* e) {
-    // never on the main stream's queue: an AdamW launch that waits for a collective there would hold back every kernel behind it
-    if (!e->opt && make_aux_stream(&e->opt, "optimizer", {e->stream, e->side, e->lane2}) != hipSuccess) e->opt = nullptr;
-    return e->opt;
-}
-// a communication stream for sgv_set_rccl that is guaranteed not to sit on the main stream's hardware queue (a collective there
-// would run strictly between the main stream's kernels instead of beside them)
-static hipStream_t ensure_comm_own(sgv_engine* e) {
-    if (!e->comm_own && make_aux_stream(&e->comm_own, "communication", {e->stream, e->side, e->lane2}) != hipSuccess) e->comm_own = nullptr;
-    return e->comm_own;
-}
-static hipStream_t ensure_wire(sgv_engine* e) {
-    if (!e->wire && make_aux_stream(&e->wire, "wire", {e->stream, e->side}) != hipSuccess) e->wire = nullptr;
-    return e->wire;
-}
-// ---- prefetched augmentation (see the members) ----
-static constexpr size_t AUG_CTL = 8192;
-static bool ensure_aug(sgv_engine* e) {
-    if (e->aug_stream) return true;
-    if (make_aux_stream(&e->aug_stream, "augmentation", {e->stream, e->side, e->lane2}) != hipSuccess) { e->aug_stream = nullptr; return false; }
-    bool ok = hipEventCreateWithFlags(&e->aug_done, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&e->aug_gate, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 2 && ok; ++i) ok = hipEventCreateWithFlags(&e->x_free[i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc((void**)&e->aug_ctl, AUG_CTL) == hipSuccess;
-    if (!ok) { hipStreamDestroy(e->aug_stream); e->aug_stream = nullptr; }
-    return ok;
-}
-// Enqueue the staged batch's kernels, ordered after the current position of the stream the caller enqueues on.  A few samples per
-// launch: one launch of 8192 small workgroups would refill every CU as slots free and keep the forward pass's big-LDS workgroups
-// (fused Conv+GroupNorm stages, 128-row GEMMs) off the chip until it ends (AdamW slices).
-static int aug_fire(sgv_engine* e) {
-    if (!e->aug_staged || e->aug_fired) return SGV_OK;
-    constexpr int per = 2;             // samples per launch
-    const int nb = 1 - e->x_cur, batch = e->aug_next_batch;
-    char* scratch = e->aug_ctl;
-    int* d_idx = (int*)scratch; int* d_mix = d_idx + batch;
-    float* d_scale = (float*)(d_mix + batch); float* d_lam = d_scale + batch;
-    unsigned long long* d_seed = (unsigned long long*)(scratch + align_up((size_t)batch * 16, 8));
-    HIPCHK(hipEventRecord(e->aug_gate, e->stream));
-    HIPCHK(hipStreamWaitEvent(e->aug_stream, e->aug_gate, 0));
-    const long se = (long)e->N * e->T;
-    for (int b0 = 0; b0 < batch; b0 += per) {
-        const int nbt = std::min(per, batch - b0);
-        ew_augment(e->dt, e->aug_data, (char*)e->x_bufs[nb].p + (size_t)b0 * se * e->esz, se, nbt, d_idx + b0, d_seed + b0, d_scale + b0, d_mix + b0, d_lam + b0, e->aug_stream);
-    }
-    HIPCHK(hipEventRecord(e->aug_done, e->aug_stream));
-    if (e->timing) HIPCHK(hipStreamWaitEvent(e->stream, e->aug_done, 0));      // kernel-timing passes keep the step on one stream
-    e->aug_fired = true;
-    return SGV_OK;
-}
-// the main stream takes the batch whose prefetch kernels may still be running
-static int aug_join(sgv_engine* e) {
-    if (e->aug_pending) { HIPCHK(hipStreamWaitEvent(e->stream, e->aug_done, 0)); e->aug_pending = false; }
-    return SGV_OK;
-}
-// the main stream is done reading the current input buffer (end of a forward pass, end of backward)
-static void x_release(sgv_engine* e) {
-    if (!e->aug_stream) return;
-    if (hipEventRecord(e->x_free[e->x_cur], e->stream) == hipSuccess) e->x_free_set[e->x_cur] = true;
-}
 int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     if (!cfg || !out) return fail(SGV_ERR_ARG, "null argument");
     int ndev = 0;
@@ -2087,192 +1714,6 @@ int sgv_get_activation(sgv_engine* e, const char* name, float* host, size_t coun
     return fail(SGV_ERR_NAME, "unknown activation '%s'", name);
 }
 
-// ---- RCCL, resolved at run time --------------------------------------------------------------------------------
-namespace {
-struct RcclApi {
-    struct Id128 { char b[128]; };             // ncclUniqueId: 128 opaque bytes, passed by value
-    void* h = nullptr;
-    int (*GetUniqueId)(void*) = nullptr;
-    int (*CommInitRank)(void**, int, Id128, int) = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    int (*CommCount)(void*, int*) = nullptr;
-    int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-};
-RcclApi g_rccl;
-const int kNcclFloat32 = 7, kNcclBfloat16 = 9, kNcclAvg = 4;      // ncclDataType_t / ncclRedOp_t values of rccl.h (NCCL >= 2.10 ABI)
-int rccl_load() {
-    if (g_rccl.h) return 0;
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    void* h = nullptr;
-    for (const char* n : names) { h = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (h) break; }
-    if (!h) return fail(SGV_ERR_STATE, "RCCL not found (dlopen librccl.so.1): %s", dlerror());
-    g_rccl.GetUniqueId = (decltype(g_rccl.GetUniqueId))dlsym(h, "ncclGetUniqueId");
-    g_rccl.CommInitRank = (decltype(g_rccl.CommInitRank))dlsym(h, "ncclCommInitRank");
-    g_rccl.CommDestroy = (decltype(g_rccl.CommDestroy))dlsym(h, "ncclCommDestroy");
-    g_rccl.AllReduce = (decltype(g_rccl.AllReduce))dlsym(h, "ncclAllReduce");
-    g_rccl.GetErrorString = (decltype(g_rccl.GetErrorString))dlsym(h, "ncclGetErrorString");
-    g_rccl.CommCount = (decltype(g_rccl.CommCount))dlsym(h, "ncclCommCount");
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.CommDestroy || !g_rccl.AllReduce)
-        return fail(SGV_ERR_STATE, "librccl lacks ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllReduce");
-    g_rccl.h = h;
-    return 0;
-}
-// ---- test double for the collective (sgv_test_fake_collective): "all-reduce" = multiply the range in place by k on the given
-// stream.  With k a power of two every element the engine hands to a collective is scaled exactly, so a step through the fake must
-// leave bitwise the state of a plain step at (k alpha, k beta) -- if and only if every gradient element and every <G,W> slot went
-// through exactly one collective (backward is linear in (alpha, beta); tests/test_modules_gpu.py).
-float g_fake_k = 0.f;
-long g_fake_calls = 0, g_fake_elems = 0;
-__global__ void fake_scale_f32_kernel(float* p, size_t n, float k) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] *= k;
-}
-__global__ void fake_scale_bf16_kernel(bf16_t* p, size_t n, float k) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = (bf16_t)((float)p[i] * k);
-}
-int fake_allreduce(const void* in, void* out, size_t count, int dtype, int op, void* comm, hipStream_t st) {
-    (void)comm;
-    if (in != out || op != kNcclAvg || (dtype != kNcclFloat32 && dtype != kNcclBfloat16)) return 1;
-    ++g_fake_calls; g_fake_elems += (long)count;
-    if (!count) return 0;
-    const int blocks = (int)std::min<size_t>((count + 255) / 256, 4096);
-    if (dtype == kNcclFloat32) hipLaunchKernelGGL(fake_scale_f32_kernel, dim3(blocks), dim3(256), 0, st, (float*)out, count, g_fake_k);
-    else hipLaunchKernelGGL(fake_scale_bf16_kernel, dim3(blocks), dim3(256), 0, st, (bf16_t*)out, count, g_fake_k);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-int rccl_fail(const char* what, int rc) {
-    return fail(SGV_ERR_HIP, "%s failed: %s", what, g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error");
-}
-}  // namespace
-
-int sgv_rccl_probe(void) { return rccl_load(); }
-int sgv_rccl_comm_count(void* comm, int* nranks) {
-    if (!comm || !nranks) return fail(SGV_ERR_ARG, "null argument");
-    CHK(rccl_load());
-    if (g_fake_k != 0.f) { *nranks = 0; return SGV_OK; }                  // the test double has no ranks
-    if (!g_rccl.CommCount) return fail(SGV_ERR_STATE, "librccl lacks ncclCommCount");
-    const int rc = g_rccl.CommCount(comm, nranks);
-    return rc ? rccl_fail("ncclCommCount", rc) : SGV_OK;
-}
-int sgv_test_fake_collective(float k, long* calls, long* elems) {
-    if (calls) *calls = g_fake_calls;
-    if (elems) *elems = g_fake_elems;
-    g_fake_calls = 0; g_fake_elems = 0;
-    if (k != 0.f) {
-        g_fake_k = k;
-        g_rccl.AllReduce = fake_allreduce;
-        if (!g_rccl.h) g_rccl.h = (void*)&g_fake_k;                     // rccl_load: nothing to resolve while the double is installed
-    } else if (g_fake_k != 0.f) {
-        const bool own = g_rccl.h == (void*)&g_fake_k;
-        g_fake_k = 0.f;
-        if (own) g_rccl = RcclApi();                                    // the next rccl_load resolves the real library
-        else g_rccl.AllReduce = (decltype(g_rccl.AllReduce))dlsym(g_rccl.h, "ncclAllReduce");
-    }
-    return SGV_OK;
-}
-int sgv_rccl_unique_id(void* id128) {
-    if (!id128) return fail(SGV_ERR_ARG, "null argument");
-    CHK(rccl_load());
-    const int rc = g_rccl.GetUniqueId(id128);
-    return rc ? rccl_fail("ncclGetUniqueId", rc) : SGV_OK;
-}
-static std::map<void*, int> g_comm_ranks;      // communicator -> number of ranks (one rank: the mean is the identity, nothing is issued)
-// a one-rank communicator exchanges nothing: its all-reduces are skipped -- unless SGV_FORCE_COLLECTIVE=1 asks for the one-GPU
-// rehearsal of the N > 1 path (every bucket packed, handed to ncclAllReduce and unpacked as with more ranks)
-static bool comm_is_single(void* comm) {
-    const char* f = getenv("SGV_FORCE_COLLECTIVE");      // read per call: tests switch it inside one process
-    if (f && atoi(f) == 1) return false;
-    auto it = g_comm_ranks.find(comm);
-    return it != g_comm_ranks.end() && it->second == 1;
-}
-int sgv_rccl_comm_init(void** comm_out, int nranks, const void* id128, int rank) {
-    if (!comm_out || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(SGV_ERR_ARG, "bad argument");
-    CHK(rccl_load());
-    RcclApi::Id128 id;
-    memcpy(id.b, id128, 128);
-    const int rc = g_rccl.CommInitRank(comm_out, nranks, id, rank);
-    if (!rc) g_comm_ranks[*comm_out] = nranks;
-    return rc ? rccl_fail("ncclCommInitRank", rc) : SGV_OK;
-}
-int sgv_rccl_allreduce(void* comm, void* dev_buf, size_t count, int dtype, void* stream) {
-    if (!comm || !dev_buf) return fail(SGV_ERR_ARG, "null argument");
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "bad dtype");
-    CHK(rccl_load());
-    const int rc = g_rccl.AllReduce(dev_buf, dev_buf, count, dtype == SGV_DTYPE_BF16 ? kNcclBfloat16 : kNcclFloat32, kNcclAvg, comm, (hipStream_t)stream);
-    return rc ? rccl_fail("ncclAllReduce", rc) : SGV_OK;
-}
-int sgv_rccl_comm_destroy(void* comm) {
-    if (!comm) return SGV_OK;
-    CHK(rccl_load());
-    const int rc = g_rccl.CommDestroy(comm);
-    return rc ? rccl_fail("ncclCommDestroy", rc) : SGV_OK;
-}
-// bucket b: wait (on the communication stream) for what the engine stream holds so far, average it over the ranks.
-// split_dots: the <G,W_eff> slots of a weight bucket's conv layers travel with the bucket (a second, tiny fp32 all-reduce of
-// bucket_dots[b]) and the small bucket leaves them out -- the bucket's AdamW then needs nothing from the end of backward.
-static int rccl_bucket(sgv_engine* e, void* comm, hipStream_t cs, int b, hipEvent_t done, bool split_dots = false) {
-    hipEvent_t ev = next_event(e);
-    if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
-    HIPCHK(hipEventRecord(ev, e->stream));
-    HIPCHK(hipStreamWaitEvent(cs, ev, 0));
-    float* g = e->grads + e->buckets[b].first;
-    if (!comm_is_single(comm)) {
-        const bool small = b == (int)e->buckets.size() - 1;
-        const bool lp = b < (int)e->bucket_packed.size() && e->bucket_packed[b];
-        void* w = lp ? (void*)((char*)e->grads_lp + 2 * e->buckets[b].first) : (void*)g;
-        size_t cnt = e->buckets[b].second;
-        if (small && split_dots) { w = (void*)(g + e->dots_total); cnt -= e->dots_total; }
-        int rc = g_rccl.AllReduce(w, w, cnt, lp ? kNcclBfloat16 : kNcclFloat32, kNcclAvg, comm, cs);
-        if (rc) return rccl_fail("ncclAllReduce", rc);
-        if (!small && split_dots && e->bucket_dots[b].second) {
-            float* d = e->grads + e->bucket_dots[b].first;
-            rc = g_rccl.AllReduce(d, d, e->bucket_dots[b].second, kNcclFloat32, kNcclAvg, comm, cs);
-            if (rc) return rccl_fail("ncclAllReduce(<G,W> slots)", rc);
-        }
-    }
-    if (done) HIPCHK(hipEventRecord(done, cs));
-    return 0;
-}
-int sgv_allreduce_grads(sgv_engine* e, void* rccl_comm, void* comm_stream) {
-    if (!e || !rccl_comm) return fail(SGV_ERR_ARG, "null argument");
-    CHK(rccl_load());
-    CHK(join_side(e));
-    const hipStream_t cs = comm_stream ? (hipStream_t)comm_stream : e->stream;
-    for (int b = 0; b < (int)e->buckets.size(); ++b) CHK(rccl_bucket(e, rccl_comm, cs, b, nullptr));
-    if (cs != e->stream) {
-        hipEvent_t ev = next_event(e);
-        if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
-        HIPCHK(hipEventRecord(ev, cs));
-        HIPCHK(hipStreamWaitEvent(e->stream, ev, 0));
-    }
-    return SGV_OK;
-}
-int sgv_set_rccl(sgv_engine* e, void* rccl_comm, void* comm_stream) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    if (rccl_comm && e->cb) return fail(SGV_ERR_STATE, "a bucket callback is registered: use one of the two data-parallel paths");
-    if (rccl_comm) {
-        if (!comm_stream) return fail(SGV_ERR_ARG, "sgv_set_rccl needs a communication stream of its own");
-        CHK(rccl_load());
-        while (e->bucket_done.size() < e->buckets.size()) {
-            hipEvent_t ev = nullptr;
-            HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            e->bucket_done.push_back(ev);
-        }
-        e->bucket_pending.assign(e->buckets.size(), 0);
-        if (!e->tn_sched) HIPCHK(hipMalloc((void**)&e->tn_sched, 8 * 520 * sizeof(int)));
-    }
-    e->comm = rccl_comm;
-    e->comm_stream = (hipStream_t)comm_stream;
-    return SGV_OK;
-}
-
-int sgv_set_bucket_callback(sgv_engine* e, sgv_bucket_cb cb, void* user) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    if (cb && e->comm) return fail(SGV_ERR_STATE, "an RCCL communicator is registered: use one of the two data-parallel paths");
-    if (cb && !e->tn_sched) HIPCHK(hipMalloc((void**)&e->tn_sched, 8 * 520 * sizeof(int)));
-    e->cb = cb; e->cb_user = user;
-    return SGV_OK;
-}
 int sgv_grad_buffer(sgv_engine* e, float** dev_ptr, size_t* count_elems) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
     // grad_bf16: the caller may read or write the arena from here on -- it gets the gradients of the last backward, and what it
@@ -2584,10 +2025,7 @@ static int adamw_begin(sgv_engine* e) {
 // end of an optimisation step: whatever ran on the optimizer stream joins the engine stream, gradient norm^2 in a fixed order
 static int adamw_finish(sgv_engine* e) {
     if (e->opt_dirty) {
-        hipEvent_t ev = next_event(e);
-        if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
-        HIPCHK(hipEventRecord(ev, e->opt));
-        HIPCHK(hipStreamWaitEvent(e->stream, ev, 0));
+        CHK(stream_wait(e, e->stream, e->opt));
         e->opt_dirty = false;
     }
     e->copies_fresh = true;
@@ -2671,24 +2109,6 @@ int sgv_bucket_dots(const sgv_engine* e, int bucket, size_t* offset_elems, size_
     *offset_elems = e->bucket_dots[bucket].first; *count_elems = e->bucket_dots[bucket].second;
     return SGV_OK;
 }
-int sgv_comm_stream(sgv_engine* e, void** stream) {
-    if (!e || !stream) return fail(SGV_ERR_ARG, "null argument");
-    if (!ensure_comm_own(e)) return fail(SGV_ERR_HIP, "stream creation failed");
-    *stream = (void*)e->comm_own;
-    return SGV_OK;
-}
-int sgv_wire_stream(sgv_engine* e, void** stream) {
-    if (!e || !stream) return fail(SGV_ERR_ARG, "null argument");
-    if (!ensure_wire(e)) return fail(SGV_ERR_HIP, "the engine has no wire stream");
-    *stream = (void*)e->wire;
-    return SGV_OK;
-}
-int sgv_opt_stream(sgv_engine* e, void** stream) {
-    if (!e || !stream) return fail(SGV_ERR_ARG, "null argument");
-    if (!ensure_opt(e)) return fail(SGV_ERR_HIP, "the engine has no optimizer stream");
-    *stream = (void*)e->opt;
-    return SGV_OK;
-}
 int sgv_adamw_bucket_async(sgv_engine* e, float lr, int bucket) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
     if (lr < 0.f) return fail(SGV_ERR_ARG, "negative learning rate");
@@ -2766,7 +2186,6 @@ int sgv_last_grad_norm(sgv_engine* e, double* out) {
     *out = sqrt(h);
     return SGV_OK;
 }
-
 // ---- per-epoch statistics without a host sync per step (reference loop: modules/train.py:171-174 reads four scalars and
 // one gradient norm per parameter tensor with .item() after every step; here the step's scalars are added to a device-side
 // accumulator by a one-thread kernel and read once per epoch) ----
@@ -2794,101 +2213,6 @@ int sgv_scalars_read(sgv_engine* e, double* host16, int reset) {
     return SGV_OK;
 }
 
-// ---- input pipeline (stateless: no engine needed) ----------------------------------------------------
-int sgv_minmax_fit(const float* rows_dev, long n_rows, int n_node, float* min_dev, float* max_dev, int accumulate, void* stream) {
-    if (!rows_dev || !min_dev || !max_dev) return fail(SGV_ERR_ARG, "null argument");
-    if (n_rows <= 0 || n_node <= 0 || n_node % 4) return fail(SGV_ERR_ARG, "sgv_minmax_fit: n_rows > 0 and n_node %% 4 == 0 required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SGV_ERR_NOGPU, "no HIP device visible: libsgvae has no CPU fallback");
-    float* partial = nullptr;
-    HIPCHK(hipMalloc((void**)&partial, sizeof(float) * 2 * (size_t)n_node * SGV_MINMAX_ROWSPLIT));
-    int r = ew_minmax_fit(rows_dev, n_rows, n_node, min_dev, max_dev, partial, SGV_MINMAX_ROWSPLIT, accumulate, (hipStream_t)stream);
-    hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(partial);
-    if (r || se != hipSuccess) return fail(SGV_ERR_HIP, "minmax_fit failed");
-    return SGV_OK;
-}
-int sgv_minmax_coeffs(const float* min_dev, const float* max_dev, int n_node, float lo, float hi, float* scale_dev, float* offset_dev, void* stream) {
-    if (!min_dev || !max_dev || !scale_dev || !offset_dev || n_node <= 0) return fail(SGV_ERR_ARG, "bad argument");
-    if (ew_minmax_coeffs(min_dev, max_dev, n_node, lo, hi, scale_dev, offset_dev, (hipStream_t)stream)) return fail(SGV_ERR_HIP, "minmax_coeffs launch failed");
-    return SGV_OK;
-}
-int sgv_scale_convert(int dst_dtype, const float* src_dev, const float* scale_dev, const float* offset_dev, void* dst_dev, long n_rows, int n_node, void* stream) {
-    if (!src_dev || !scale_dev || !offset_dev || !dst_dev) return fail(SGV_ERR_ARG, "null argument");
-    if (n_node <= 0 || n_node % 8) return fail(SGV_ERR_ARG, "sgv_scale_convert: n_node %% 8 == 0 required");
-    if (dst_dtype != SGV_DTYPE_F32 && dst_dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "bad dtype");
-    if (ew_scale_convert(dst_dtype, src_dev, scale_dev, offset_dev, dst_dev, n_rows, n_node, (hipStream_t)stream)) return fail(SGV_ERR_HIP, "scale_convert launch failed");
-    return SGV_OK;
-}
-
-size_t sgv_dataset_sample_bytes(const sgv_engine* e) { return e ? (size_t)e->N * e->T * e->esz : 0; }
-
-int sgv_dataset_convert(sgv_engine* e, const float* src_dev, void* dst_dev, int count) {
-    if (!e || !src_dev || !dst_dev) return fail(SGV_ERR_ARG, "null argument");
-    ew_transpose(0, e->dt, src_dev, dst_dev, count, e->N, e->T, e->T, e->N, (long)e->N * e->T, (long)e->T * e->N, e->stream);
-    return SGV_OK;
-}
-
-int sgv_augment_collate(sgv_engine* e, const void* dataset_dev, int batch, const int32_t* idx, const uint64_t* noise_seed,
-                        const float* scale, const int32_t* mix_idx, const float* lam) {
-    if (!e || !dataset_dev || !idx || !noise_seed || !scale || !mix_idx || !lam) return fail(SGV_ERR_ARG, "null argument");
-    if (batch < 1 || batch > e->maxB) return fail(SGV_ERR_ARG, "batch %d outside [1,%d]", batch, e->maxB);
-    CHK(aug_join(e));
-    // small per-sample control arrays go through a device scratch at the head of xpose_tmp
-    char* scratch = (char*)e->xpose_tmp;
-    int* d_idx = (int*)scratch; int* d_mix = d_idx + batch;
-    float* d_scale = (float*)(d_mix + batch); float* d_lam = d_scale + batch;
-    unsigned long long* d_seed = (unsigned long long*)(scratch + align_up((size_t)batch * 16, 8));
-    // one host->device copy of the five arrays in the device layout (pageable source: staged before the call returns)
-    const size_t seed_off = align_up((size_t)batch * 16, 8), total = seed_off + (size_t)batch * 8;
-    std::vector<char>& hb = e->aug_host[e->aug_turn++ & 3];           // a buffer is reused four steps later
-    hb.resize(total);
-    char* h = hb.data();
-    memcpy(h, idx, batch * 4); memcpy(h + batch * 4, mix_idx, batch * 4);
-    memcpy(h + batch * 8, scale, batch * 4); memcpy(h + batch * 12, lam, batch * 4);
-    memcpy(h + seed_off, noise_seed, batch * 8);
-    HIPCHK(hipMemcpyAsync(scratch, h, total, hipMemcpyHostToDevice, e->stream));
-    ew_augment(e->dt, dataset_dev, e->x_in.p, (long)e->N * e->T, batch, d_idx, d_seed, d_scale, d_mix, d_lam, e->stream);
-    x_release(e);
-    e->batch = batch;
-    e->have_fwd = false;
-    return SGV_OK;
-}
-
-int sgv_augment_stage(sgv_engine* e, const void* dataset_dev, int batch, const int32_t* idx, const uint64_t* noise_seed,
-                      const float* scale, const int32_t* mix_idx, const float* lam) {
-    if (!e || !dataset_dev || !idx || !noise_seed || !scale || !mix_idx || !lam) return fail(SGV_ERR_ARG, "null argument");
-    if (batch < 1 || batch > e->maxB) return fail(SGV_ERR_ARG, "batch %d outside [1,%d]", batch, e->maxB);
-    const size_t seed_off = align_up((size_t)batch * 16, 8), total = seed_off + (size_t)batch * 8;
-    if (total > AUG_CTL) return fail(SGV_ERR_ARG, "batch %d: control arrays exceed the staging scratch", batch);
-    if (!ensure_aug(e)) return fail(SGV_ERR_HIP, "could not create the augmentation stream");
-    // the spare buffer's last reader (the backward pass two steps back, or a pass on a batch that was staged over) has ended;
-    // a batch staged before and never advanced to is replaced: same stream, so its kernels precede this copy
-    const int nb = 1 - e->x_cur;
-    if (e->x_free_set[nb]) HIPCHK(hipStreamWaitEvent(e->aug_stream, e->x_free[nb], 0));
-    std::vector<char>& hb = e->aug_host[e->aug_turn++ & 3];           // a buffer is reused four calls later
-    hb.resize(total);
-    char* h = hb.data();
-    memcpy(h, idx, batch * 4); memcpy(h + batch * 4, mix_idx, batch * 4);
-    memcpy(h + batch * 8, scale, batch * 4); memcpy(h + batch * 12, lam, batch * 4);
-    memcpy(h + seed_off, noise_seed, batch * 8);
-    HIPCHK(hipMemcpyAsync(e->aug_ctl, h, total, hipMemcpyHostToDevice, e->aug_stream));
-    e->aug_data = dataset_dev; e->aug_next_batch = batch;
-    e->aug_staged = true; e->aug_fired = false;
-    return SGV_OK;
-}
-int sgv_augment_advance(sgv_engine* e) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    if (!e->aug_staged) return fail(SGV_ERR_STATE, "sgv_augment_advance: no batch staged (sgv_augment_stage)");
-    CHK(aug_fire(e));                        // no training forward since the stage call: the kernels go out now
-    e->x_cur = 1 - e->x_cur; e->x_in = e->x_bufs[e->x_cur];
-    e->batch = e->aug_next_batch;
-    e->have_fwd = false;
-    e->aug_staged = false; e->aug_fired = false;
-    e->aug_pending = true;                   // the next reader of the batch waits for aug_done
-    return SGV_OK;
-}
-
 int sgv_kernel_time_reset(sgv_engine* e, int enable) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
     hipStreamSynchronize(e->stream);
@@ -2903,520 +2227,14 @@ int sgv_kernel_time_tag(sgv_engine* e, int index, char* name, size_t cap, float*
     if (index < 0 || index >= (int)e->tag_names.size()) return SGV_ERR_ARG;   // end of the list: not an error message
     HIPCHK(hipStreamSynchronize(e->stream));
     snprintf(name, cap, "%s", e->tag_names[index].c_str());
-    float tot = 0.f; int n = 0;
-    for (auto& t : e->timers) if (t.tag == index) { float ms = 0.f; hipEventElapsedTime(&ms, t.a, t.b); tot += ms; ++n; }
-    if (total_ms) *total_ms = tot;
-    if (calls) *calls = n;
+    tag_total(e, index, total_ms, calls);
     return SGV_OK;
 }
 int sgv_kernel_time(sgv_engine* e, const char* which, float* total_ms, int* calls) {
     if (!e || !which) return fail(SGV_ERR_ARG, "null argument");
     HIPCHK(hipStreamSynchronize(e->stream));
     auto it = e->tag_ids.find(which);
-    float tot = 0.f; int n = 0;
-    if (it != e->tag_ids.end()) {
-        for (auto& t : e->timers) if (t.tag == it->second) { float ms = 0.f; hipEventElapsedTime(&ms, t.a, t.b); tot += ms; ++n; }
-    }
-    if (total_ms) *total_ms = tot;
-    if (calls) *calls = n;
+    tag_total(e, it != e->tag_ids.end() ? it->second : -1, total_ms, calls);
     return SGV_OK;
 }
-
-int sgv_test_gemm_nt(int dtype, const void* A, const void* W, void* C, const float* bias, const float* scale, const void* addend,
-                     int M, int N, int K, int taps, int Tlen, int splitk, int out_f32, void* stream) {
-    GemmNT p; memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.w_tap_stride = (long)N * K; p.C = C; p.ldc = N;
-    p.addend = addend; p.ldadd = N; p.bias = bias; p.scale = scale;
-    p.M = M; p.N = N; p.K = K; p.taps = taps; p.pad = (taps - 1) / 2; p.Tlen = Tlen; p.splitk = splitk < 1 ? 1 : splitk; p.out_f32 = out_f32;
-    float* partial = nullptr;
-    if (p.splitk > 1) HIPCHK(hipMalloc((void**)&partial, sizeof(float) * (size_t)p.splitk * M * N));
-    p.partial = partial;
-    int r = launch_gemm_nt(dtype, p, (hipStream_t)stream);
-    hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    if (partial) hipFree(partial);
-    if (r) return fail(SGV_ERR_ARG, "launch_gemm_nt rejected the arguments (%d)", r);
-    if (se != hipSuccess) return fail(SGV_ERR_HIP, "gemm_nt failed: %s", hipGetErrorString(se));
-    return SGV_OK;
-}
-
-int sgv_test_gemm_nt_stats(const void* A, const void* W, void* C, const float* bias, const void* addend, int M, int N, int K,
-                           int taps, int Tlen, int Cg, double* sums, void* stream) {
-    if (Cg < 1 || N % Cg) return fail(SGV_ERR_ARG, "N must be a multiple of Cg");
-    GemmNT p; memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.w_tap_stride = (long)N * K; p.C = C; p.ldc = N;
-    p.addend = addend; p.ldadd = N; p.bias = bias;
-    p.M = M; p.N = N; p.K = K; p.taps = taps; p.pad = (taps - 1) / 2; p.Tlen = Tlen; p.splitk = 1;
-    p.gn_sums = sums; p.gn_Cg = Cg; p.gn_G = N / Cg;
-    int r = launch_gemm_nt(SGV_DTYPE_BF16, p, (hipStream_t)stream);
-    hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    if (r) return fail(SGV_ERR_ARG, "launch_gemm_nt rejected the arguments (%d)", r);
-    if (se != hipSuccess) return fail(SGV_ERR_HIP, "gemm_nt failed: %s", hipGetErrorString(se));
-    return SGV_OK;
-}
-
-// 256x256 persistent kernel (gemm256.hip), bf16.  mode 0: forced (launch_gemm_nt256, split-K as given), 1: the engine's plan
-// (gemm_nt_plan: kernel choice, split-K, main + tail rows).  sums != null: fused GroupNorm statistics (mode 0, split-K 1).
-int sgv_test_conv_gn_fwd(const void* A, const void* W, const float* bias, const float* scale, const void* res, const float* gamma,
-                         const float* beta, void* y, void* out, double* sums, int B, int T, int N, int K, int taps, int G, float rscale,
-                         void* stream) {
-    ConvGN q; memset(&q, 0, sizeof(q));
-    q.A = A; q.lda = K; q.W = W; q.ldw = K; q.w_tap_stride = (long)N * K; q.bias = bias; q.scale = scale;
-    q.y = y; q.ldy = N; q.out = out; q.ldout = N; q.res = res; q.ldres = N; q.rscale = rscale; q.gamma = gamma; q.beta = beta; q.sums = sums;
-    q.B = B; q.T = T; q.N = N; q.K = K; q.taps = taps; q.pad = (taps - 1) / 2; q.G = G; q.Cg = G > 0 ? N / G : 0;
-    if (!conv_gn_fused_eligible(SGV_DTYPE_BF16, q)) return fail(SGV_ERR_ARG, "shape not taken by the fused conv + GroupNorm kernel");
-    const int r = launch_conv_gn_fwd(q, (hipStream_t)stream);
-    const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    if (r || se != hipSuccess) return fail(SGV_ERR_HIP, "conv_gn launch failed (%d, %s)", r, hipGetErrorString(se));
-    return SGV_OK;
-}
-int sgv_test_conv_gn_bwd(const void* A, const void* W, const float* scale, const void* addend, const void* premul, void* da, const void* y,
-                         const double* sums, const float* gamma,
-                         const float* beta, const float* cbias, void* dy, double* sums2, float* ptot, float* cdot_part, int B, int T,
-                         int N, int K, int taps, int G, void* stream) {
-    ConvGNBwd q; memset(&q, 0, sizeof(q));
-    q.A = A; q.lda = K; q.W = W; q.ldw = K; q.w_tap_stride = (long)N * K; q.scale = scale; q.addend = addend; q.ldadd = N;
-    q.premul = premul; q.ldpre = N; q.da = da; q.ldda = N;
-    q.y = y; q.ldy = N; q.sums = sums; q.gamma = gamma; q.beta = beta; q.cbias = cbias; q.dy = dy; q.lddy = N;
-    q.sums2 = sums2; q.ptot = ptot; q.cdot_part = cdot_part; q.rscale = 1.f; q.gscale = 1.f;
-    q.B = B; q.T = T; q.N = N; q.K = K; q.taps = taps; q.pad = (taps - 1) / 2; q.G = G; q.Cg = G > 0 ? N / G : 0;
-    if (!conv_gn_bwd_eligible(SGV_DTYPE_BF16, q)) return fail(SGV_ERR_ARG, "shape not taken by the fused input-gradient + GroupNorm backward kernel");
-    const int r = launch_conv_gn_bwd(q, (hipStream_t)stream);
-    const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    if (r || se != hipSuccess) return fail(SGV_ERR_HIP, "conv_gn_bwd launch failed (%d, %s)", r, hipGetErrorString(se));
-    return SGV_OK;
-}
-int sgv_test_gemm_nt256(const void* A, const void* W, void* C, const float* bias, const float* scale, const void* addend, int M, int N,
-                        int K, int taps, int Tlen, int splitk, int out_f32, int mode, int Cg, double* sums, int* plan_kind, void* stream) {
-    GemmNT p; memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.w_tap_stride = (long)N * K; p.C = C; p.ldc = N;
-    p.addend = addend; p.ldadd = N; p.bias = bias; p.scale = scale;
-    p.M = M; p.N = N; p.K = K; p.taps = taps; p.pad = (taps - 1) / 2; p.Tlen = Tlen; p.splitk = splitk < 1 ? 1 : splitk; p.out_f32 = out_f32;
-    const size_t cap = (size_t)32 << 20;
-    float* partial = nullptr; float* part = nullptr;
-    HIPCHK(hipMalloc((void**)&partial, sizeof(float) * std::max(cap, (size_t)p.splitk * M * N)));
-    p.partial = partial;
-    if (sums) {
-        if (Cg < 1 || N % Cg) { hipFree(partial); return fail(SGV_ERR_ARG, "N must be a multiple of Cg"); }
-        HIPCHK(hipMalloc((void**)&part, sizeof(float) * gemm_nt256_part_floats(M, N, 1)));
-        p.gn_part = part; p.gn_sums = sums; p.gn_Cg = Cg; p.gn_G = N / Cg;
-    }
-    const int band_code = (mode >> 8) & 0xff, strm_code = (mode >> 16) & 7;
-    p.band = band_code == 255 ? -1 : band_code;
-    p.strm = strm_code == 7 ? -1 : strm_code;
-    const int ts_code = (mode >> 19) & 3;
-    p.ts = ts_code == 1 ? 1 : ts_code == 2 ? -1 : 0;
-    const bool split_tail = (mode >> 21) & 1;          // planned launch with the 128-row tail as its own 128 x 512 launch (the engine runs it beside the main one)
-    mode &= 0xff;
-    int r;
-    if (split_tail) {
-        // the split is forced here (the planner's cost comparison and the "tail shorter than the main launch" rule decide speed, not results)
-        GemmPlan pl = gemm_nt_plan(SGV_DTYPE_BF16, p, cap, 0);
-        if (M % 256 != 128 || M < 384) { hipFree(partial); return fail(SGV_ERR_ARG, "split-tail test mode needs M = 128 (mod 256)"); }
-        pl.kind = 2; pl.m_main = M - 128; pl.fuse_stats = 0;
-        pl.sk_main = std::max(1, std::min(p.splitk, 8));
-        if (plan_kind) *plan_kind = pl.kind;
-        float* tp = nullptr;
-        HIPCHK(hipMalloc((void**)&tp, sizeof(float) * cap));
-        int sk_t = gemm_nt_tail_split(SGV_DTYPE_BF16, p, pl, cap);
-        if (sk_t <= 0) {
-            const long tkt = (long)taps * ((K + 63) / 64);
-            sk_t = (int)std::max(1L, std::min((long)(16 / std::max(1, (N + 511) / 512)), tkt / 24));
-        }
-        if (N < 512) r = -4;
-        else {
-            r = launch_gemm_nt_main(p, pl, (hipStream_t)stream);
-            if (!r) r = launch_gemm_nt_tail(p, pl, sk_t, tp, (hipStream_t)stream);
-        }
-        hipStreamSynchronize((hipStream_t)stream);
-        hipFree(tp);
-    } else if (mode == 0) {
-        if (plan_kind) *plan_kind = p.ts == 1 ? 3 : 1;
-        if (p.ts < 0) p.ts = 0;
-        r = launch_gemm_nt256(p, (hipStream_t)stream);
-    } else {
-        const GemmPlan pl = gemm_nt_plan(SGV_DTYPE_BF16, p, cap, sums != nullptr);
-        if (plan_kind) *plan_kind = pl.kind;
-        if (sums && !pl.fuse_stats) r = -3;
-        else r = launch_gemm_nt_planned(SGV_DTYPE_BF16, p, pl, (hipStream_t)stream);
-    }
-    hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(partial); if (part) hipFree(part);
-    if (r) return fail(SGV_ERR_ARG, "the 256x256 GEMM path rejected the arguments (%d)", r);
-    if (se != hipSuccess) return fail(SGV_ERR_HIP, "gemm_nt256 failed: %s", hipGetErrorString(se));
-    return SGV_OK;
-}
-
-int sgv_test_stream_overlap(sgv_engine* e, int which, int* overlaps) {
-    if (!e || !overlaps) return fail(SGV_ERR_ARG, "null argument");
-    hipStream_t s = which == 0 ? e->lane2 : which == 1 ? e->side : which == 2 ? ensure_opt(e) : which == 3 ? ensure_comm_own(e) : nullptr;
-    if (which < 0 || which > 3) return fail(SGV_ERR_ARG, "which must be 0..3");
-    if (!s) { *overlaps = -1; return SGV_OK; }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    *overlaps = streams_overlap(e->stream, s) ? 1 : 0;
-    return SGV_OK;
-}
-// Test hook: occupy part of the chip for a bounded time (what a resident collective's channel workgroups do): `blocks` workgroups
-// of `threads` threads and `lds_bytes` of LDS each spin on the constant-rate clock for `ticks` (100 MHz) on `stream`; returns at once.
-__global__ void occupy_spin_kernel(long long ticks) {
-    extern __shared__ char occ_lds[];
-    if (threadIdx.x == 0xFFFFFF) occ_lds[0] = 1;
-    const long long t0 = (long long)wall_clock64();
-    while ((long long)wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
-}
-int sgv_test_occupy(void* stream, int blocks, int threads, int lds_bytes, long long ticks) {
-    if (blocks < 1 || blocks > 1024 || threads < 64 || threads > 1024 || lds_bytes < 0 || lds_bytes > 160 * 1024 || ticks < 0 || ticks > 1000000)
-        return fail(SGV_ERR_ARG, "sgv_test_occupy: argument out of range (at most 1024 workgroups, 10 ms)");
-    hipLaunchKernelGGL(occupy_spin_kernel, dim3(blocks), dim3(threads), (size_t)lds_bytes, (hipStream_t)stream, ticks);
-    return hipGetLastError() == hipSuccess ? SGV_OK : fail(SGV_ERR_HIP, "occupy launch failed");
-}
-int sgv_test_gemm_tn(int dtype, const void* A, const void* Bm, float* dW, int M, int N1, int N2, int taps, int Tlen, int splitk,
-                     int use_tr, void* stream) {
-    GemmTN p; memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = N1; p.B = Bm; p.ldb = N2; p.out = dW; p.ldo = N2; p.out_tap_stride = (long)N1 * N2;
-    p.M = M; p.N1 = N1; p.N2 = N2; p.taps = taps; p.pad = (taps - 1) / 2; p.Tlen = Tlen; p.splitk = splitk < 1 ? 1 : splitk; p.use_tr = use_tr != 0; p.force_w2 = use_tr == 2 ? 1 : use_tr == 3 ? 2 : (use_tr == 4 || use_tr == 6 || use_tr == 7) ? 3 : use_tr == 5 ? -1 : 0;
-    p.out_bf16 = use_tr == 6 ? 1 : 0;          // 6: the 256 x 256 kernel with bf16 output (dW is then a bf16 array; splitk 1)
-    // 7: the 256 x 256 kernel in its work-stealing form
-    static int* test_sched = nullptr;          // allocated once: an allocation per call would wait for whatever else runs on the device
-    if (use_tr == 7) { if (!test_sched) HIPCHK(hipMalloc((void**)&test_sched, 513 * sizeof(int))); p.sched = test_sched; }
-    if (p.out_bf16 && (splitk > 1 || !gemm_tn256_eligible(dtype, p))) return fail(SGV_ERR_ARG, "sgv_test_gemm_tn: bf16 output needs the 256 x 256 kernel and splitk 1");
-    float* partial = nullptr;
-    const long nw = (long)taps * N1 * N2;
-    if (p.splitk > 1) {
-        HIPCHK(hipMalloc((void**)&partial, sizeof(float) * (size_t)p.splitk * nw));
-        p.out = partial; p.out_slab_stride = nw;
-    }
-    int r = launch_gemm_tn(dtype, p, (hipStream_t)stream);
-    if (!r && p.splitk > 1) {
-        int blocks = (int)((nw + 255) / 256); if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dW, partial, p.splitk, nw);
-    }
-    hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    if (partial) hipFree(partial);
-    if (r) return fail(SGV_ERR_ARG, "launch_gemm_tn rejected the arguments (%d)", r);
-    if (se != hipSuccess) return fail(SGV_ERR_HIP, "gemm_tn failed: %s", hipGetErrorString(se));
-    return SGV_OK;
-}
-
-// ---- test hooks for the non-GEMM kernels (ew.hip): argument checks, the launcher the engine calls, sync ----
-static int ew_hook_done(int r, const char* what, void* stream) {
-    const hipError_t le = hipGetLastError();
-    const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
-    if (r) return fail(SGV_ERR_ARG, "%s: the launcher rejected the arguments (%d)", what, r);
-    if (le != hipSuccess) return fail(SGV_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(le));
-    if (se != hipSuccess) return fail(SGV_ERR_HIP, "%s failed: %s", what, hipGetErrorString(se));
-    return SGV_OK;
-}
-static int gn_hook_shape(const char* what, int dtype, int B, int T, int C, int G, const float* work, size_t work_floats) {
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", what);
-    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", what, B, T, C);
-    if (G < 1 || G > SGV_GN_MAX_GROUPS || C % G) return fail(SGV_ERR_ARG, "%s: 1 <= G <= %d and C %% G == 0 required (C %d, G %d)", what, SGV_GN_MAX_GROUPS, C, G);
-    if (!work || work_floats < ew_gn_part_floats(B, T, C))
-        return fail(SGV_ERR_ARG, "%s: workspace of %zu floats given, %zu needed", what, work ? work_floats : (size_t)0, ew_gn_part_floats(B, T, C));
-    return SGV_OK;
-}
-static bool ld_ok(long ld, int C) { return ld >= C && ld % 8 == 0; }
-size_t sgv_test_gn_workspace_floats(int B, int T, int C) {
-    if (B < 1 || T < 1 || C < 8 || C % 8) return 0;
-    return ew_gn_part_floats(B, T, C);
-}
-int sgv_test_gn_fwd(int dtype, int act, const void* y, long ldy, const void* res, long ldres, float rscale, void* out, long ldout,
-                    const float* gamma, const float* beta, double* sums, float* work, size_t work_floats, int B, int T, int C, int G,
-                    int* path, void* stream) {
-    CHK(gn_hook_shape("sgv_test_gn_fwd", dtype, B, T, C, G, work, work_floats));
-    if (!y || !out || !gamma || !beta || !sums) return fail(SGV_ERR_ARG, "sgv_test_gn_fwd: null argument");
-    if (act < 0 || act > 3) return fail(SGV_ERR_ARG, "sgv_test_gn_fwd: act must be 0 none, 1 gelu, 2 tanh or 3 relu");
-    if (!ld_ok(ldy, C) || !ld_ok(ldout, C) || (res && !ld_ok(ldres, C))) return fail(SGV_ERR_ARG, "sgv_test_gn_fwd: row strides must be >= C and multiples of 8");
-    GNParams p;
-    p.y = y; p.ldy = ldy; p.res = res; p.ldres = ldres; p.rscale = rscale; p.out = out; p.ldout = ldout;
-    p.gamma = gamma; p.beta = beta; p.sums = sums; p.part = work; p.B = B; p.T = T; p.C = C; p.G = G; p.Cg = C / G;
-    if (path) *path = gn_fused_ok(p) ? 1 : 0;
-    return ew_hook_done(ew_gn_fwd(dtype, act, p, (hipStream_t)stream), "sgv_test_gn_fwd", stream);
-}
-int sgv_test_gn_bwd(int dtype, int act, const void* y, long ldy, const void* dout, long lddout, float rscale, float gscale,
-                    const float* gamma, const float* beta, const double* sums, void* dy, long lddy, double* sums2, float* dgamma,
-                    float* dbeta, float* dbias, float* cdot, const float* cbias, int accum_affine, float* work, size_t work_floats,
-                    int B, int T, int C, int G, int* path, void* stream) {
-    CHK(gn_hook_shape("sgv_test_gn_bwd", dtype, B, T, C, G, work, work_floats));
-    if (!y || !dout || !gamma || !beta || !sums || !dy || !sums2) return fail(SGV_ERR_ARG, "sgv_test_gn_bwd: null argument");
-    if (act != 0 && act != 1 && act != 3) return fail(SGV_ERR_ARG, "sgv_test_gn_bwd: act must be 0 none, 1 gelu or 3 relu");
-    if (!ld_ok(ldy, C) || !ld_ok(lddout, C) || !ld_ok(lddy, C)) return fail(SGV_ERR_ARG, "sgv_test_gn_bwd: row strides must be >= C and multiples of 8");
-    GNParams p;
-    p.y = y; p.ldy = ldy; p.dout = dout; p.lddout = lddout; p.rscale = rscale; p.gscale = gscale; p.out = dy; p.ldout = lddy;
-    p.gamma = gamma; p.beta = beta; p.sums = const_cast<double*>(sums); p.sums2 = sums2; p.dgamma = dgamma; p.dbeta = dbeta; p.dbias = dbias;
-    p.cdot = cdot; p.cbias = cbias; p.accum_affine = accum_affine ? 1 : 0; p.part = work;
-    p.B = B; p.T = T; p.C = C; p.G = G; p.Cg = C / G;
-    if (path) *path = gn_fused_bwd_ok(p) ? 1 : 0;
-    return ew_hook_done(ew_gn_bwd(dtype, act, p, (hipStream_t)stream), "sgv_test_gn_bwd", stream);
-}
-int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long ldy, const void* x, long ldx, void* xhat, long ldxhat,
-                        const float* gamma, const float* beta, double* sums, double* loss_sums, double* sums2, float* unit, float gscale,
-                        void* dy, long lddy, float* cdot, const float* cbias, float* work, size_t work_floats, int B, int T, int C,
-                        int G, void* stream) {
-    CHK(gn_hook_shape("sgv_test_recon_loss", dtype, B, T, C, G, work, work_floats));
-    if (!y || !x || !gamma || !beta || !sums || !loss_sums) return fail(SGV_ERR_ARG, "sgv_test_recon_loss: null argument");
-    if (loss_type < SGV_LOSS_MSE || loss_type > SGV_LOSS_HUBER) return fail(SGV_ERR_ARG, "sgv_test_recon_loss: unknown loss kind %d", loss_type);
-    if (train && (!sums2 || !unit || !dy)) return fail(SGV_ERR_ARG, "sgv_test_recon_loss: training needs sums2, unit and dy");
-    if (!ld_ok(ldy, C) || !ld_ok(ldx, C) || (xhat && !ld_ok(ldxhat, C)) || (train && !ld_ok(lddy, C)))
-        return fail(SGV_ERR_ARG, "sgv_test_recon_loss: row strides must be >= C and multiples of 8");
-    hipStream_t s = (hipStream_t)stream;
-    // forward half, as decoder_fwd: statistics, then tanh + loss (+ the backward reductions)
-    GNParams p;
-    p.B = B; p.T = T; p.C = C; p.G = G; p.Cg = C / G; p.gamma = gamma; p.beta = beta;
-    p.y = y; p.ldy = ldy; p.sums = sums; p.part = work;
-    int r = ew_gn_stats(dtype, p, s);
-    p.dout = x; p.lddout = ldx; p.loss_type = loss_type; p.loss_sums = loss_sums;
-    if (xhat) { p.out = xhat; p.ldout = ldxhat; }
-    if (train) { p.sums2 = sums2; p.dgamma = unit; p.dbeta = unit + C; p.dbias = unit + 2L * C; p.gscale = 1.0f; }
-    if (!r) r = ew_recon_loss(dtype, train ? 1 : 0, p, s);
-    if (!r && train) {
-        // backward half, as the recon-head block of the backward pass (immediate sum of the <G, W_eff> partials)
-        GNParams q;
-        q.B = B; q.T = T; q.C = C; q.G = G; q.Cg = C / G; q.gamma = gamma; q.beta = beta;
-        q.y = y; q.ldy = ldy; q.sums = sums; q.sums2 = sums2; q.dout = x; q.lddout = ldx; q.loss_type = loss_type; q.gscale = gscale;
-        q.out = dy; q.ldout = lddy; q.cdot = cdot; q.cbias = cbias; q.part = work;
-        r = ew_recon_bwd_apply(dtype, q, s);
-    }
-    return ew_hook_done(r, "sgv_test_recon_loss", stream);
-}
-int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
-                 float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
-                 int T, int C, void* stream) {
-    CHK(gn_hook_shape("sgv_test_act", dtype, B, T, C, 1, work, work_floats));
-    if (mode < 0 || mode > 2) return fail(SGV_ERR_ARG, "sgv_test_act: mode must be 0, 1 or 2");
-    if (!y || !ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "sgv_test_act: y missing or its row stride not >= C and a multiple of 8");
-    if (mode != 2 && (!out || !ld_ok(ldout, C))) return fail(SGV_ERR_ARG, "sgv_test_act: modes 0 and 1 need out (row stride >= C, multiple of 8)");
-    if (mode == 1 && (!dout || !ld_ok(lddout, C))) return fail(SGV_ERR_ARG, "sgv_test_act: mode 1 needs dout (row stride >= C, multiple of 8)");
-    if (mode == 2 && cdot && (!yf32 || !ld_ok(ldyf, C))) return fail(SGV_ERR_ARG, "sgv_test_act: mode 2 with cdot needs yf32 (row stride >= C, multiple of 8)");
-    GNParams p;
-    p.B = B; p.T = T; p.C = C; p.G = 1; p.Cg = C;
-    p.y = y; p.ldy = ldy; p.dout = dout; p.lddout = lddout; p.rscale = rscale; p.out = out; p.ldout = ldout;
-    p.dbias = dbias; p.cdot = cdot; p.cbias = cbias; p.yf32 = mode == 2 && cdot ? yf32 : nullptr; p.ldyf = ldyf; p.part = work;
-    return ew_hook_done(ew_act(dtype, mode, p, (hipStream_t)stream), "sgv_test_act", stream);
-}
-int sgv_test_latent(const float* last, const float* eps, float* z, double* kl, const float* dz, float* dlast, float coef, int B, int Z,
-                    void* stream) {
-    if (!last || !eps || B < 1 || Z < 1 || (long)B * Z > (1L << 24)) return fail(SGV_ERR_ARG, "sgv_test_latent: null argument or bad shape");
-    if (!z != !kl || !dz != !dlast || (!z && !dz)) return fail(SGV_ERR_ARG, "sgv_test_latent: give z and kl (forward) and / or dz and dlast (backward)");
-    int r = 0;
-    if (z) r = ew_latent_fwd(last, eps, z, B, Z, kl, (hipStream_t)stream);
-    if (!r && dz) r = ew_latent_bwd(last, eps, dz, dlast, B, Z, coef, (hipStream_t)stream);
-    return ew_hook_done(r, "sgv_test_latent", stream);
-}
-int sgv_test_stage(int dtype, const float* pz, const float* qz, const float* eps, const void* dec_out, long ldd, void* zs_next,
-                   long ldz, float* zmap, float std_scale, float inv_b, double* kl, double* kl_part, const void* dzs, long lddzs,
-                   void* g_p, void* g_q, float coef, int M, int C, void* stream) {
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "sgv_test_stage: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16");
-    if (!pz || !qz || !eps || M < 1 || C < 1) return fail(SGV_ERR_ARG, "sgv_test_stage: null argument or bad shape");
-    if (!zs_next && !dzs) return fail(SGV_ERR_ARG, "sgv_test_stage: give zs_next (forward) and / or dzs (backward)");
-    if (zs_next && (!dec_out || !kl || !kl_part || ldd < C || ldz < C)) return fail(SGV_ERR_ARG, "sgv_test_stage: forward needs dec_out, kl, kl_part and row strides >= C");
-    if (dzs && (!g_p || !g_q || lddzs < C)) return fail(SGV_ERR_ARG, "sgv_test_stage: backward needs g_p, g_q and a row stride >= C");
-    int r = 0;
-    if (zs_next) r = ew_stage_fwd(dtype, pz, qz, eps, dec_out, ldd, zs_next, ldz, zmap, M, C, std_scale, kl, inv_b, kl_part, (hipStream_t)stream);
-    if (!r && dzs) r = ew_stage_bwd(dtype, pz, qz, eps, dzs, lddzs, g_p, g_q, M, C, coef, (hipStream_t)stream);
-    return ew_hook_done(r, "sgv_test_stage", stream);
-}
-int sgv_test_linear_head(int xdtype, const void* X, const float* W, const float* bias, const float* scale, float* Y, float* part,
-                         size_t part_floats, const float* dY, const void* addend, void* dX, float* dW, float* db, int B, int K, int O,
-                         void* stream) {
-    if (xdtype != SGV_DTYPE_F32 && xdtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "sgv_test_linear_head: xdtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16");
-    if (!X || !W || B < 1 || O < 1 || K < 8 || K % 8) return fail(SGV_ERR_ARG, "sgv_test_linear_head: X, W, B, O >= 1 and K %% 8 == 0 required");
-    if (!Y && !dY) return fail(SGV_ERR_ARG, "sgv_test_linear_head: give Y (forward) and / or dY (backward)");
-    if (Y && (!part || part_floats < (size_t)128 * B * O)) return fail(SGV_ERR_ARG, "sgv_test_linear_head: forward needs a workspace of 128 * B * O floats");
-    if (dY && ((!dX && !dW) || (addend && !dX) || (db && !dW))) return fail(SGV_ERR_ARG, "sgv_test_linear_head: backward needs dX or dW (addend goes with dX, db with dW)");
-    int r = 0;
-    if (Y) r = ew_linear_head_fwd(xdtype, X, W, bias, scale, Y, B, K, O, part, (hipStream_t)stream);
-    if (!r && dY) r = ew_linear_head_bwd(xdtype, dY, X, W, scale, addend, dX, dW, db, B, K, O, (hipStream_t)stream);
-    return ew_hook_done(r, "sgv_test_linear_head", stream);
-}
-int sgv_test_linear_expand(int dtype, const float* X, const float* W, const float* bias, const float* scale, void* Y, const void* dY,
-                           float* dX, float* dW, float* db, int B, int K, int O, void* stream) {
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16");
-    if (!X || !W || B < 1 || O < 1 || K < 1) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: null argument or bad shape");
-    if (!Y && !dY) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: give Y (forward) and / or dY (backward)");
-    if (Y && !bias) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: forward needs bias");
-    if (dY && (!dW || !db)) return fail(SGV_ERR_ARG, "sgv_test_linear_expand: backward needs dW and db");
-    int r = 0;
-    if (Y) r = ew_linear_expand_fwd(dtype, X, W, bias, scale, Y, B, K, O, (hipStream_t)stream);
-    if (!r && dY) r = ew_linear_expand_bwd(dtype, dY, X, W, scale, dX, dW, db, B, K, O, (hipStream_t)stream);
-    return ew_hook_done(r, "sgv_test_linear_expand", stream);
-}
-
-// ---- test hook for the multi-tensor optimizer / spectral-norm passes (optim.hip; tests/test_optim_kernels_gpu.py) ----
-// Descriptor and work-item tables over caller-owned device buffers, sized with the helpers of sgv_ew.h the engine and the
-// parameter-set object use; scratch (tmp_t, tmp_s, tpart, spart, the per-item partials) is the object's own and starts as NaN.
-struct sgv_optset {
-    int dt = 0;
-    std::vector<SNDesc> sn;
-    std::vector<AdamDesc> adam;
-    std::vector<int> tiled;                      // per AdamDesc
-    SNDesc* sn_dev = nullptr; AdamDesc* adam_dev = nullptr;
-    WorkItem *items_sn = nullptr, *items_sn_unf = nullptr, *items_ts = nullptr, *items_ss = nullptr, *items_dot = nullptr, *items_adam = nullptr,
-             *items_flat = nullptr, *items_tile = nullptr, *items_copy = nullptr;
-    int n_sn = 0, n_sn_unf = 0, n_ts = 0, n_ss = 0, n_dot = 0, n_adam = 0, n_flat = 0, n_tile = 0, n_copy = 0;
-    float *tmp = nullptr, *dot_part = nullptr;
-    double *gnorm_part = nullptr, *gnorm = nullptr;
-    std::vector<FinDot> fin_dots;
-};
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static int optset_done(int r, const char* what, hipStream_t s) {
-    const hipError_t se = hipStreamSynchronize(s);
-    if (r) return fail(SGV_ERR_HIP, "%s: launch failed", what);
-    if (se != hipSuccess) return fail(SGV_ERR_HIP, "%s failed: %s", what, hipGetErrorString(se));
-    return SGV_OK;
-}
-static int optset_read(const double* dev, double* host, const char* what, hipStream_t s) {
-    if (hipMemcpyAsync(host, dev, sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) { hipStreamSynchronize(s); return fail(SGV_ERR_HIP, "%s: read-back failed", what); }
-    return SGV_OK;
-}
-int sgv_test_optset_destroy(sgv_optset* os) {
-    if (!os) return SGV_OK;
-    void* ptrs[] = {os->sn_dev, os->adam_dev, os->items_sn, os->items_sn_unf, os->items_ts, os->items_ss, os->items_dot, os->items_adam, os->items_flat,
-                    os->items_tile, os->items_copy, os->tmp, os->dot_part, os->gnorm_part, os->gnorm};
-    for (void* p : ptrs) if (p) hipFree(p);
-    delete os;
-    return SGV_OK;
-}
-int sgv_test_optset_create(int dtype, const sgv_optset_entry* entries, int n, sgv_optset** out) {
-    const char* me = "sgv_test_optset_create";
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
-    if (!entries || n < 1 || !out) return fail(SGV_ERR_ARG, "%s: null argument or no entries", me);
-    size_t n_tmp = 0;
-    for (int i = 0; i < n; ++i) {
-        const sgv_optset_entry& e = entries[i];
-        if (!e.p || !e.g || !e.m || !e.v) return fail(SGV_ERR_ARG, "%s: entry %d needs p, g, m and v", me, i);
-        if (!al16(e.p) || !al16(e.g) || !al16(e.m) || !al16(e.v)) return fail(SGV_ERR_ARG, "%s: entry %d: p, g, m and v must be 16-byte aligned", me, i);
-        if (e.n < 4 || e.n % 4) return fail(SGV_ERR_ARG, "%s: entry %d: n = %ld is not a positive multiple of 4", me, i, e.n);
-        if (e.rows < 0 || (e.rows == 0 && e.tiled)) return fail(SGV_ERR_ARG, "%s: entry %d: the tiled pass takes spectrally-normalised weights only (rows > 0)", me, i);
-        if (e.rows == 0 && (e.wct || e.g_bf16)) return fail(SGV_ERR_ARG, "%s: entry %d: wct and g_bf16 go with a spectrally-normalised weight", me, i);
-        if (e.wc && !al16(e.wc)) return fail(SGV_ERR_ARG, "%s: entry %d: wc must be 16-byte aligned", me, i);
-        if (e.rows > 0) {
-            if (e.taps < 1 || e.cols < 4 || e.cols % 4) return fail(SGV_ERR_ARG, "%s: entry %d: taps >= 1 and cols %% 4 == 0 required (taps %d, cols %d)", me, i, e.taps, e.cols);
-            if ((long)e.taps * e.rows * e.cols != e.n) return fail(SGV_ERR_ARG, "%s: entry %d: taps * rows * cols = %ld but n = %ld", me, i, (long)e.taps * e.rows * e.cols, e.n);
-            if (!e.u || !e.v_sn || !e.sigma || !e.dot || !al16(e.v_sn)) return fail(SGV_ERR_ARG, "%s: entry %d: a spectrally-normalised weight needs u, v_sn (16-byte aligned), sigma and dot", me, i);
-            if (e.g_bf16 && ((uintptr_t)e.g_bf16 & 7)) return fail(SGV_ERR_ARG, "%s: entry %d: g_bf16 must be 8-byte aligned", me, i);
-            n_tmp += align_up((size_t)e.taps * e.cols, 4) + align_up((size_t)e.rows, 4) + align_up(sn_tpart_floats(e.taps, e.rows, e.cols), 4) +
-                     align_up(sn_spart_floats(e.taps, e.rows, e.cols), 4);
-        }
-    }
-    sgv_optset* os = new sgv_optset();
-    os->dt = dtype;
-    auto bad = [&](const char* what) { sgv_test_optset_destroy(os); return fail(SGV_ERR_HIP, "%s: %s failed", me, what); };
-    auto nan_alloc = [&](void** dst, size_t bytes) {      // all-ones bytes are a NaN in float and in double
-        return hipMalloc(dst, bytes ? bytes : 256) == hipSuccess && hipMemset(*dst, 0xFF, bytes ? bytes : 256) == hipSuccess;
-    };
-    if (!nan_alloc((void**)&os->tmp, n_tmp * sizeof(float))) return bad("scratch allocation");
-    std::vector<WorkItem> i_sn, i_sn_unf, i_ts, i_ss, i_dot, i_adam, i_flat, i_tile, i_copy;
-    size_t toff = 0;
-    for (int i = 0; i < n; ++i) {
-        const sgv_optset_entry& e = entries[i];
-        AdamDesc a; memset(&a, 0, sizeof(a));
-        a.p = e.p; a.g = e.g; a.m = e.m; a.v = e.v; a.n = e.n; a.sn = -1; a.rows = 1; a.cols = (int)e.n; a.taps = 1;
-        a.wc = e.wc; a.wct = e.wct; a.glp = (const unsigned short*)e.g_bf16;
-        const int id = (int)os->adam.size();
-        if (e.rows > 0) {
-            SNDesc d; memset(&d, 0, sizeof(d));
-            const int si = (int)os->sn.size();
-            d.W = e.p; d.u = e.u; d.v = e.v_sn; d.sigma = e.sigma; d.dot = e.dot; d.G = e.g;
-            d.tmp_t = os->tmp + toff; toff += align_up((size_t)e.taps * e.cols, 4);
-            d.tmp_s = os->tmp + toff; toff += align_up((size_t)e.rows, 4);
-            d.tpart = os->tmp + toff; toff += align_up(sn_tpart_floats(e.taps, e.rows, e.cols), 4);
-            d.spart = os->tmp + toff; toff += align_up(sn_spart_floats(e.taps, e.rows, e.cols), 4);
-            d.wc = (dtype == SGV_DTYPE_BF16 && e.wc && e.cols % 8 == 0) ? (const void*)e.wc : nullptr;      // the engine's rule (upload_tables)
-            d.taps = e.taps; d.rows = e.rows; d.cols = e.cols; d.active = e.active ? 1 : 0;
-            os->sn.push_back(d);
-            a.sn = si; a.rows = e.rows; a.cols = e.cols; a.taps = e.taps;
-            if (e.active) {
-                for (int c = 0; c < sn_gemv_items(e.taps, e.rows, e.cols); ++c) { i_sn.push_back({si, c}); if (!e.tiled) i_sn_unf.push_back({si, c}); }
-                for (int c = 0; c < sn_tsum_items(e.taps, e.cols); ++c) i_ts.push_back({si, c});
-                for (int c = 0; c < sn_ssum_items(e.rows); ++c) i_ss.push_back({si, c});
-            }
-            if (!e.tiled) {
-                os->fin_dots.push_back({(const float*)(uintptr_t)i_dot.size(), d.dot, (int)opt_flat_items(e.n), 0});   // src = index for now, rebased below
-                for (long c = 0; c < opt_flat_items(e.n); ++c) i_dot.push_back({si, (int)c});
-            }
-            if (e.wc || e.wct)
-                for (int c = 0; c < opt_copy_items(e.taps, e.rows, e.cols); ++c) i_copy.push_back({id, c});
-        } else if (e.wc) {
-            for (int c = 0; c < opt_copy_items(1, 1, (int)e.n); ++c) i_copy.push_back({id, c});
-        }
-        os->adam.push_back(a);
-        os->tiled.push_back(e.tiled ? 1 : 0);
-        for (long c = 0; c < opt_flat_items(e.n); ++c) { i_adam.push_back({id, (int)c}); if (!e.tiled) i_flat.push_back({id, (int)c}); }
-        if (e.tiled)
-            for (int c = 0; c < opt_tile_items(e.taps, e.rows, e.cols); ++c) i_tile.push_back({id, c});
-    }
-    auto up = [&](const void* src, size_t bytes, void** dst) {
-        if (bytes == 0) { *dst = nullptr; return true; }
-        return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-#define OS_UP(vec, field, count) (up(vec.data(), sizeof(WorkItem) * vec.size(), (void**)&os->field) && ((os->count = (int)vec.size()), true))
-    if (!up(os->sn.data(), sizeof(SNDesc) * os->sn.size(), (void**)&os->sn_dev) || !up(os->adam.data(), sizeof(AdamDesc) * os->adam.size(), (void**)&os->adam_dev) ||
-        !OS_UP(i_sn, items_sn, n_sn) || !OS_UP(i_sn_unf, items_sn_unf, n_sn_unf) || !OS_UP(i_ts, items_ts, n_ts) || !OS_UP(i_ss, items_ss, n_ss) ||
-        !OS_UP(i_dot, items_dot, n_dot) || !OS_UP(i_adam, items_adam, n_adam) || !OS_UP(i_flat, items_flat, n_flat) || !OS_UP(i_tile, items_tile, n_tile) ||
-        !OS_UP(i_copy, items_copy, n_copy))
-        return bad("table upload");
-#undef OS_UP
-    if (!nan_alloc((void**)&os->dot_part, sizeof(float) * i_dot.size()) ||
-        !nan_alloc((void**)&os->gnorm_part, sizeof(double) * std::max(i_flat.size() + i_tile.size(), i_adam.size())) || !nan_alloc((void**)&os->gnorm, sizeof(double)))
-        return bad("workspace allocation");
-    for (auto& f : os->fin_dots) f.src = os->dot_part + (size_t)(uintptr_t)f.src;
-    *out = os;
-    return SGV_OK;
-}
-int sgv_test_optset_power_iteration(sgv_optset* os, int train, int reuse_tpart, void* stream) {
-    if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_power_iteration: null object");
-    if (os->sn.empty()) return SGV_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool reuse = train && reuse_tpart;         // run_sn with wtu_fresh: the tiled entries' tpart comes from the last AdamW pass
-    const int r = opt_sn_power_iteration(os->sn_dev, reuse ? os->items_sn_unf : os->items_sn, reuse ? os->n_sn_unf : os->n_sn, os->items_sn, os->n_sn, os->items_ts,
-                                         os->n_ts, os->items_ss, os->n_ss, (int)os->sn.size(), train, s);
-    return optset_done(r, "sgv_test_optset_power_iteration", s);
-}
-int sgv_test_optset_grad_dot(sgv_optset* os, void* stream) {
-    if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_grad_dot: null object");
-    hipStream_t s = (hipStream_t)stream;
-    int r = opt_sn_grad_dot(os->sn_dev, os->items_dot, os->n_dot, os->dot_part, s);
-    if (!r && !os->fin_dots.empty()) r = ew_fin_dots(os->fin_dots.data(), (int)os->fin_dots.size(), s);
-    return optset_done(r, "sgv_test_optset_grad_dot", s);
-}
-int sgv_test_optset_grad_norm(sgv_optset* os, double* gnorm_sq_out, void* stream) {
-    if (!os || !gnorm_sq_out) return fail(SGV_ERR_ARG, "sgv_test_optset_grad_norm: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    int r = opt_grad_norm(os->adam_dev, os->sn_dev, os->items_adam, os->n_adam, os->gnorm_part, s);
-    if (!r) r = ew_rowsum_d(os->gnorm_part, os->n_adam, 1, os->gnorm, 1.0, s);
-    if (!r) CHK(optset_read(os->gnorm, gnorm_sq_out, "sgv_test_optset_grad_norm", s));
-    return optset_done(r, "sgv_test_optset_grad_norm", s);
-}
-int sgv_test_optset_adamw(sgv_optset* os, float lr, float wd, int step, const float* gscale_dev, int grad_source, const float* g_base,
-                          const void* g_wire, size_t g_wire_elems, double* gnorm_sq_out, void* stream) {
-    const char* me = "sgv_test_optset_adamw";
-    if (!os) return fail(SGV_ERR_ARG, "%s: null object", me);
-    if (step < 1 || lr < 0.f) return fail(SGV_ERR_ARG, "%s: step >= 1 and lr >= 0 required", me);
-    if (grad_source < 0 || grad_source > 2) return fail(SGV_ERR_ARG, "%s: grad_source must be 0 (fp32), 1 (per-entry bf16 mirror) or 2 (bf16 wire copy)", me);
-    if (grad_source == 2) {
-        if (!g_base || !g_wire || ((uintptr_t)g_wire & 7)) return fail(SGV_ERR_ARG, "%s: the wire copy needs g_base and an 8-byte aligned g_wire", me);
-        for (size_t i = 0; i < os->adam.size(); ++i) {
-            if (!os->tiled[i]) continue;
-            const long off = os->adam[i].g - g_base;
-            if (off < 0 || off % 4 || (size_t)(off + os->adam[i].n) > g_wire_elems)
-                return fail(SGV_ERR_ARG, "%s: tiled entry %zu: its gradient must lie in [g_base, g_base + g_wire_elems) at a multiple of 4 elements", me, i);
-        }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const AdamCoef c = adam_coef(step);
-    int r = opt_adamw(os->adam_dev, os->sn_dev, os->items_flat, os->n_flat, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, os->gnorm_part, os->dt, s, gscale_dev);
-    if (!r) r = opt_adamw_sn(os->adam_dev, os->sn_dev, os->items_tile, os->n_tile, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, os->gnorm_part + os->n_flat, os->dt, s,
-                             g_base, grad_source == 2 ? g_wire : nullptr, grad_source == 1 ? 1 : 0);
-    if (!r && gnorm_sq_out) {
-        r = ew_rowsum_d(os->gnorm_part, os->n_flat + os->n_tile, 1, os->gnorm, 1.0, s);
-        if (!r) CHK(optset_read(os->gnorm, gnorm_sq_out, me, s));
-    }
-    return optset_done(r, me, s);
-}
-int sgv_test_optset_make_copies(sgv_optset* os, void* stream) {
-    if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_make_copies: null object");
-    hipStream_t s = (hipStream_t)stream;
-    return optset_done(opt_make_copies(os->adam_dev, os->items_copy, os->n_copy, os->dt, s), "sgv_test_optset_make_copies", s);
-}
-
 }  // extern "C"

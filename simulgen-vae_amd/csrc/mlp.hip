@@ -16,8 +16,6 @@
 
 #include <math.h>
 
-int sgv_set_error(int code, const char* fmt, ...);   // engine.hip
-
 #define MLP_THREADS 256
 #define MLP_MAX_PROBS 2
 #define MLP_MAX_SUMS 12

@@ -10,8 +10,6 @@
 #include <string.h>
 #include <vector>
 
-int sgv_set_error(int code, const char* fmt, ...);   // engine.hip
-
 struct sgv_pset {
     std::vector<SNDesc> sn;
     std::vector<AdamDesc> adam;

@@ -12,6 +12,8 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 #define SGV_WAVE 64
 
+int sgv_set_error(int code, const char* fmt, ...);   // fills sgv_last_error() (printf-style) and returns `code`; defined next to the error state (engine.hip)
+
 template <typename T> struct ElemTraits;
 template <> struct ElemTraits<float>  { static constexpr int EPC = 4; };   // elements per 16-byte chunk
 template <> struct ElemTraits<bf16_t> { static constexpr int EPC = 8; };

@@ -201,7 +201,7 @@ constexpr int SN_SUM_CHUNK = 64;     // elements of taps*cols (sn_tsum_kernel) /
 constexpr int OPT_TILE = 64;         // tile edge of the tiled AdamW pass
 constexpr int COPY_TILE = 32;        // tile edge of opt_make_copies
 // Per-tensor geometry of the work-item tables and scratch buffers, [taps][rows][cols] weights.  Every host-side table builder
-// (engine.hip, pset.hip, the sgv_test_optset hook) sizes its tables with these; the kernels decode the same chunk numbering.
+// (engine.hip, pset.hip, the sgv_test_optset hook of test_hooks.hip) sizes its tables with these; the kernels decode the same chunk numbering.
 inline int sn_row_blocks(int rows) { return (rows + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM; }
 inline int sn_col_blocks(int cols) { return (cols + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM; }
 inline int sn_gemv_items(int taps, int rows, int cols) { return taps * sn_row_blocks(rows) * sn_col_blocks(cols); }   // items1 / items3 of the power iteration

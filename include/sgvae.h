@@ -91,6 +91,41 @@ int sgv_export_state(sgv_engine* e, const char* name, float* host, size_t count)
 int sgv_export_grad(sgv_engine* e, const char* name, float* host, size_t count, int* is_none);
 /* Adam exp_avg / exp_avg_sq of a parameter (torch.optim.AdamW state), reference layout. [sync] */
 int sgv_export_adam(sgv_engine* e, const char* name, float* host_m, float* host_v, size_t count);
+/* torch.optim.AdamW.load_state_dict for one parameter: the inverse of sgv_export_adam (reference layout in; either pointer may be
+ * NULL).  SGV_ERR_NAME for an unknown key, SGV_ERR_ARG for a size mismatch or a parameter without optimizer state -- all three
+ * before anything is launched or copied.  [sync] */
+int sgv_load_adam(sgv_engine* e, const char* name, const float* host_m, const float* host_v, size_t count);
+/* What a training run carries besides its tensors: state[0] = AdamW steps taken (torch's state["step"]; fixes the bias corrections
+ * of the next step), state[1] = the noise seed (sgv_seed), state[2] = noise draws consumed (the Philox position of the engine's
+ * own reparameterisation noise: every noise tensor the engine drew advanced it by one), state[3] = reserved, 0.  sgv_set_train_state puts all three back and,
+ * unlike sgv_seed, keeps the draw position it is given; SGV_ERR_STATE while an AdamW step is open (after sgv_adamw_step_range
+ * first=1 / sgv_adamw_bucket_async and before last=1), SGV_ERR_ARG if the reserved slot is not 0. */
+int sgv_get_train_state(const sgv_engine* e, uint64_t state[4]);
+int sgv_set_train_state(sgv_engine* e, const uint64_t state[4]);
+
+/* Whole-state snapshot / restore for exact resume (the reference saves model.state_dict() once, after the last epoch,
+ * modules/train.py:254; its optimizer state is never saved).  ONE flat fp32 buffer in reference layout holds, for every
+ * sgv_param_info index in order, the value and then -- where the entry has a gradient -- exp_avg and exp_avg_sq.
+ *  - sgv_snapshot_floats: the buffer's size; sgv_snapshot_slice: offset and count (floats) of (index, which), which = 0 value,
+ *    1 exp_avg, 2 exp_avg_sq; count 0 for the moments of an entry without optimizer state.  The slice of a key holds exactly what
+ *    sgv_export_state / sgv_export_adam return for it.
+ *  - sgv_snapshot_begin: on the engine stream, table-driven permute kernels (csrc/engine_ckpt.hip) write the whole state in
+ *    reference layout into a device staging buffer (allocated on first use, freed by sgv_destroy, not part of sgv_memory_info);
+ *    one device-to-host copy into host_pinned follows on a copy stream the engine owns and has placed on another hardware queue
+ *    than the engine stream.  Returns without synchronising: the engine stream may run the next step at once, the staging buffer
+ *    holds the state as of this call.  host_pinned must be page-locked (hipHostMalloc / torch pin_memory) and must not be read
+ *    before sgv_snapshot_wait.  SGV_ERR_ARG: wrong size or pageable memory; SGV_ERR_STATE: a snapshot is still in flight, or an
+ *    AdamW step is open.
+ *  - sgv_snapshot_wait: blocks until the copy stream is idle (the engine stream is not waited for).  No snapshot in flight: no-op.
+ *  - sgv_restore: host buffer (pinned or not) -> staging -> inverse permute into the parameters and both moment arenas, then the
+ *    compute-dtype copies are refreshed and the W^T u partials of the conv weights are rebuilt in the summation order of the tiled
+ *    AdamW pass, so that the next training forward computes bit for bit what it computes after an optimizer step.  Pair it with
+ *    sgv_set_train_state.  A backward needs a new forward afterwards.  SGV_ERR_STATE as above.  [sync] */
+int sgv_snapshot_floats(sgv_engine* e, size_t* total_floats);
+int sgv_snapshot_slice(sgv_engine* e, int index, int which, size_t* offset_floats, size_t* count_floats);
+int sgv_snapshot_begin(sgv_engine* e, float* host_pinned, size_t floats);
+int sgv_snapshot_wait(sgv_engine* e);
+int sgv_restore(sgv_engine* e, const float* host, size_t floats);
 
 /* Refresh the compute-dtype weight copies from the fp32 masters after sgv_load_state. */
 int sgv_prepare(sgv_engine* e);

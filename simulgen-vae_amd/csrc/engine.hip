@@ -1241,6 +1241,7 @@ int sgv_destroy(sgv_engine* e) {
     for (auto& t : e->timers) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
     if (e->grads_lp) hipFree(e->grads_lp);
     if (e->tn_sched) hipFree(e->tn_sched);
+    ckpt_release(e);
     delete e;
     return SGV_OK;
 }
@@ -1294,12 +1295,12 @@ static void permute_entry(const sgv_engine* e, const StateEntry& s, const float*
         else memcpy(dst, src, cnt * 4);
     }
 }
-static size_t entry_param_offset(const sgv_engine* e, const StateEntry& s) {
+size_t entry_param_offset(const sgv_engine* e, const StateEntry& s) {
     if (s.gn >= 0) return s.kind == 4 ? e->gns[s.gn].gamma : e->gns[s.gn].beta;
     const Layer& l = e->layers[s.layer];
     switch (s.kind) { case 0: return l.b; case 1: return l.w; case 2: return l.u; default: return l.v; }
 }
-static size_t entry_grad_offset(const sgv_engine* e, const StateEntry& s) {
+size_t entry_grad_offset(const sgv_engine* e, const StateEntry& s) {
     if (!s.has_grad) return NPOS;
     if (s.gn >= 0) return s.kind == 4 ? e->gns[s.gn].ggamma : e->gns[s.gn].gbeta;
     const Layer& l = e->layers[s.layer];
@@ -1412,6 +1413,34 @@ int sgv_export_adam(sgv_engine* e, const char* name, float* host_m, float* host_
     HIPCHK(hipStreamSynchronize(e->stream));
     if (host_m) { HIPCHK(hipMemcpy(t.data(), e->adam_m + go, count * 4, hipMemcpyDeviceToHost)); permute_entry(e, *s, t.data(), host_m, -1); }
     if (host_v) { HIPCHK(hipMemcpy(t.data(), e->adam_v + go, count * 4, hipMemcpyDeviceToHost)); permute_entry(e, *s, t.data(), host_v, -1); }
+    return SGV_OK;
+}
+
+int sgv_load_adam(sgv_engine* e, const char* name, const float* host_m, const float* host_v, size_t count) {
+    if (!e || !name) return fail(SGV_ERR_ARG, "null argument");
+    const StateEntry* s = find_entry(e, name);
+    if (!s) return fail(SGV_ERR_NAME, "unknown state key '%s'", name);
+    const size_t go = entry_grad_offset(e, *s);
+    if (go == NPOS) return fail(SGV_ERR_ARG, "'%s' has no optimizer state", name);
+    if ((long)count != s->count()) return fail(SGV_ERR_ARG, "size mismatch for '%s': got %zu expected %ld", name, count, s->count());
+    std::vector<float> t(count);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (host_m) { permute_entry(e, *s, host_m, t.data(), +1); HIPCHK(hipMemcpy(e->adam_m + go, t.data(), count * 4, hipMemcpyHostToDevice)); }
+    if (host_v) { permute_entry(e, *s, host_v, t.data(), +1); HIPCHK(hipMemcpy(e->adam_v + go, t.data(), count * 4, hipMemcpyHostToDevice)); }
+    return SGV_OK;
+}
+
+int sgv_get_train_state(const sgv_engine* e, uint64_t state[4]) {
+    if (!e || !state) return fail(SGV_ERR_ARG, "null argument");
+    state[0] = (uint64_t)e->step; state[1] = e->seed; state[2] = e->draw; state[3] = 0;
+    return SGV_OK;
+}
+int sgv_set_train_state(sgv_engine* e, const uint64_t state[4]) {
+    if (!e || !state) return fail(SGV_ERR_ARG, "null argument");
+    if (e->adam_open) return fail(SGV_ERR_STATE, "sgv_set_train_state: an AdamW step is open");
+    if (state[3] != 0) return fail(SGV_ERR_ARG, "sgv_set_train_state: the reserved slot must be 0");
+    if (state[0] > (uint64_t)1 << 62) return fail(SGV_ERR_ARG, "sgv_set_train_state: step count out of range");
+    e->step = (long)state[0]; e->seed = state[1]; e->draw = state[2];     // unlike sgv_seed, the draw position is kept
     return SGV_OK;
 }
 

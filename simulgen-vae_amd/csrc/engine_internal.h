@@ -240,6 +240,10 @@ struct sgv_engine {
     std::map<std::string, int> tag_ids;
     std::vector<std::string> tag_names;
     int use_tr = 1;
+    // whole-state snapshot / restore (engine_ckpt.hip): one flat fp32 buffer in reference layout, filled by table-driven permute
+    // kernels into a device staging buffer (allocated on first use, not counted by sgv_memory_info) and copied to the caller's
+    // pinned host buffer on a stream of the engine's own, so the main stream can go on with the next step at once
+    struct CkptState* ckpt = nullptr;
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -248,6 +252,10 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 void sum_slabs(float* out, const float* partial, int splitk, long n, hipStream_t stream);   // out = sum of split-K slabs, fixed order
 int stream_wait(sgv_engine* e, hipStream_t waiter, hipStream_t of);                         // waiter waits for what `of` holds so far
 int join_side(sgv_engine* e);
+size_t entry_param_offset(const sgv_engine* e, const StateEntry& s);                         // float offset of a state entry in the parameter arena
+size_t entry_grad_offset(const sgv_engine* e, const StateEntry& s);                          // ... in the gradient / Adam-moment arenas, NPOS if it gets no gradient
+// engine_ckpt.hip
+void ckpt_release(sgv_engine* e);                                                           // sgv_destroy: staging buffer, tables, copy stream
 // engine_streams.hip
 bool streams_overlap(hipStream_t a, hipStream_t b);
 hipError_t make_aux_stream(hipStream_t* out, const char* label, std::initializer_list<hipStream_t> avoid);

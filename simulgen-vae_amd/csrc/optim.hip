@@ -429,6 +429,47 @@ int opt_adamw_sn(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem*
 #undef SGV_ADAM_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+// tpart of the tiled entries from the weights as they stand (after a whole-state restore): the W^T u partials exactly as
+// adamw_sn_kernel leaves them behind -- the same 64 x 64 tiles, the same four rows per thread added up in the same order, the same
+// fixed-order sum of the sixteen row groups -- so that a power iteration that reuses them (opt_sn_power_iteration with the
+// item list that skips the tiled entries) computes bit for bit what it computes after an AdamW pass.  sn_wt_u_kernel's
+// 64-row blocks are the same partition but add the rows up one after the other, which rounds differently.
+__global__ __launch_bounds__(256) void sn_tpart_tiles_kernel(const AdamDesc* adam, const SNDesc* sn, const WorkItem* items) {
+    __shared__ float tus[16][64];
+    const WorkItem it = items[blockIdx.x];
+    const AdamDesc a = adam[it.desc];
+    const SNDesc d = sn[a.sn];
+    const int ct = (a.cols + 63) >> 6, rt = (a.rows + 63) >> 6;
+    const int tap = it.chunk / (rt * ct);
+    const int rem = it.chunk - tap * rt * ct;
+    const int r0 = (rem / ct) << 6, c0 = (rem % ct) << 6;
+    const int cq = threadIdx.x & 15, rr = threadIdx.x >> 4;
+    const int col = c0 + cq * 4;
+    const bool cok = col < a.cols;          // cols % 4 == 0 (checked on the host)
+    const long base = (long)tap * a.rows * a.cols;
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int rl = k * 16 + rr, row = r0 + rl;
+        if (cok && row < a.rows) {
+            const float4 p = *reinterpret_cast<const float4*>(a.p + base + (long)row * a.cols + col);
+            const float u_r = d.u[row];
+            t0 += p.x * u_r; t1 += p.y * u_r; t2 += p.z * u_r; t3 += p.w * u_r;
+        }
+    }
+    tus[rr][cq * 4 + 0] = t0; tus[rr][cq * 4 + 1] = t1; tus[rr][cq * 4 + 2] = t2; tus[rr][cq * 4 + 3] = t3;
+    __syncthreads();
+    if (threadIdx.x < 64 && c0 + (int)threadIdx.x < a.cols) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += tus[k][threadIdx.x];
+        d.tpart[((long)(r0 >> 6) * a.taps + tap) * a.cols + c0 + threadIdx.x] = t;
+    }
+}
+int opt_sn_tpart_tiles(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(sn_tpart_tiles_kernel, dim3(n), dim3(256), 0, s, adam_dev, sn_dev, items);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 int opt_adamw(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, float lr, float b1, float b2,
               float eps, float wd, float bc1, float bc2sqrt, double* gnorm_sq, int compute_dtype, hipStream_t s, const float* gscale) {
     if (n > 0 && compute_dtype == 1) hipLaunchKernelGGL((adamw_kernel<true, true>), dim3(n), dim3(256), 0, s, adam_dev, sn_dev, items, lr, b1, b2, eps, wd, bc1, bc2sqrt, gnorm_sq, gscale);

@@ -191,6 +191,8 @@ int opt_adamw(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* it
 int opt_adamw_sn(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, float lr, float b1, float b2,
                  float eps, float wd, float bc1, float bc2sqrt, double* gnorm_sq, int compute_dtype, hipStream_t s,
                  const float* g_base = nullptr, const void* g_lp = nullptr, int desc_lp = 0);      // g_lp: gradients from the bf16 wire copy (offsets relative to g_base)
+// tpart of the tiled entries rebuilt from the current weights and u, bit for bit what opt_adamw_sn leaves behind (same items table)
+int opt_sn_tpart_tiles(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, hipStream_t s);
 int opt_grad_norm(const AdamDesc* adam_dev, const SNDesc* sn_dev, const WorkItem* items, int n, double* gnorm_sq,
                   hipStream_t s);
 int opt_make_copies(const AdamDesc* adam_dev, const WorkItem* items, int n, int compute_dtype, hipStream_t s);

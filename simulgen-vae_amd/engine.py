@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
     "sgv_minmax_fit", "sgv_minmax_coeffs", "sgv_scale_convert",
     "sgv_rccl_unique_id", "sgv_rccl_probe", "sgv_rccl_comm_count", "sgv_rccl_allreduce", "sgv_rccl_comm_init", "sgv_rccl_comm_destroy", "sgv_allreduce_grads", "sgv_set_rccl", "sgv_comm_stream",
     "sgv_augment_stage", "sgv_augment_advance",
+    "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
+    "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
     "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
@@ -53,6 +55,7 @@ class OptsetEntry(C.Structure):
                 ("wc", C.c_void_p), ("wct", C.c_void_p), ("g_bf16", C.c_void_p), ("tiled", C.c_int32), ("active", C.c_int32)]
 
 
+SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")      # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
 
@@ -81,6 +84,14 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_export_state.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
     lib.sgv_export_grad.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(i32)]
     lib.sgv_export_adam.argtypes = [vp, C.c_char_p, vp, vp, C.c_size_t]
+    lib.sgv_load_adam.argtypes = [vp, C.c_char_p, vp, vp, C.c_size_t]
+    lib.sgv_get_train_state.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.sgv_set_train_state.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.sgv_snapshot_floats.argtypes = [vp, C.POINTER(C.c_size_t)]
+    lib.sgv_snapshot_slice.argtypes = [vp, i32, i32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.sgv_snapshot_begin.argtypes = [vp, vp, C.c_size_t]
+    lib.sgv_snapshot_wait.argtypes = [vp]
+    lib.sgv_restore.argtypes = [vp, vp, C.c_size_t]
     lib.sgv_prepare.argtypes = [vp]
     lib.sgv_set_input.argtypes = [vp, vp, i32]
     lib.sgv_set_eps.argtypes = [vp, i32, vp, i32]
@@ -265,6 +276,80 @@ class Engine:
         _check(self.lib, self.lib.sgv_export_adam(self.h, name.encode(), m.ctypes.data_as(C.c_void_p),
                                                   v.ctypes.data_as(C.c_void_p), m.size), "sgv_export_adam")
         return m, v
+
+    def load_adam(self, name: str, exp_avg=None, exp_avg_sq=None):
+        """torch.optim.AdamW state of one parameter back into the engine (reference layout; None leaves a moment alone)."""
+        e = next((x for x in self.spec if x.name == name), None)
+        arrs = []
+        for a in (exp_avg, exp_avg_sq):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if e is not None and a.shape != tuple(e.shape):
+                    a = a.reshape(-1)            # the library reports the size mismatch
+            arrs.append(a)
+        n = next((a.size for a in arrs if a is not None), 0)
+        if all(a is not None for a in arrs) and arrs[0].size != arrs[1].size:
+            raise ValueError(f"load_adam({name}): exp_avg has {arrs[0].size} elements, exp_avg_sq {arrs[1].size}")
+        ptr = [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in arrs]
+        _check(self.lib, self.lib.sgv_load_adam(self.h, name.encode(), ptr[0], ptr[1], n), f"sgv_load_adam({name})")
+
+    def train_state(self):
+        """dict(step, seed, draw): AdamW steps taken, the noise seed and the noise draws consumed (include/sgvae.h)."""
+        st = (C.c_uint64 * 4)()
+        _check(self.lib, self.lib.sgv_get_train_state(self.h, st), "sgv_get_train_state")
+        return dict(step=int(st[0]), seed=int(st[1]), draw=int(st[2]))
+
+    def set_train_state(self, step: int, seed: int, draw: int):
+        """Put the three values of train_state() back; unlike seed() the draw position is kept."""
+        st = (C.c_uint64 * 4)(int(step), int(seed), int(draw), 0)
+        _check(self.lib, self.lib.sgv_set_train_state(self.h, st), "sgv_set_train_state")
+
+    def snapshot_layout(self):
+        """(total floats, [(key, which, offset, count)]) of the flat snapshot buffer: which = "value", "exp_avg" or "exp_avg_sq";
+        entries without optimizer state have a "value" row only."""
+        total = C.c_size_t()
+        _check(self.lib, self.lib.sgv_snapshot_floats(self.h, C.byref(total)), "sgv_snapshot_floats")
+        rows = []
+        for i, (name, _shape, _kind, _hg) in enumerate(self.param_info()):
+            for w, label in enumerate(SNAPSHOT_PARTS):
+                off, cnt = C.c_size_t(), C.c_size_t()
+                _check(self.lib, self.lib.sgv_snapshot_slice(self.h, i, w, C.byref(off), C.byref(cnt)), "sgv_snapshot_slice")
+                if cnt.value:
+                    rows.append((name, label, int(off.value), int(cnt.value)))
+        return int(total.value), rows
+
+    def snapshot_floats(self) -> int:
+        total = C.c_size_t()
+        _check(self.lib, self.lib.sgv_snapshot_floats(self.h, C.byref(total)), "sgv_snapshot_floats")
+        return int(total.value)
+
+    def _snapshot_buffer(self, buf, what, pinned):
+        t = self.torch
+        n = self.snapshot_floats()
+        if not t.is_tensor(buf) or buf.device.type != "cpu" or buf.dtype != t.float32 or not buf.is_contiguous():
+            raise ValueError(f"{what}: the buffer must be a contiguous torch.float32 CPU tensor")
+        if buf.numel() != n:
+            raise ValueError(f"{what}: the buffer holds {buf.numel()} floats, the engine's state has {n}")
+        if pinned and not buf.is_pinned():
+            raise ValueError(f"{what}: the buffer must be pinned (torch.empty(n, dtype=torch.float32, pin_memory=True))")
+        return n
+
+    def snapshot_begin(self, buf):
+        """Enqueue a snapshot of the whole state (parameters, u / v, both Adam moments) into the pinned float32 CPU tensor `buf`
+        (snapshot_floats() elements) and return at once; the next step may be enqueued right away.  Read `buf` only after
+        snapshot_wait()."""
+        n = self._snapshot_buffer(buf, "snapshot_begin", True)
+        _check(self.lib, self.lib.sgv_snapshot_begin(self.h, C.c_void_p(buf.data_ptr()), n), "sgv_snapshot_begin")
+        self._snap_buf = buf                       # the copy writes into it until snapshot_wait()
+
+    def snapshot_wait(self):
+        _check(self.lib, self.lib.sgv_snapshot_wait(self.h), "sgv_snapshot_wait")
+        self._snap_buf = None
+
+    def restore(self, buf):
+        """The inverse of a snapshot: `buf` (float32 CPU tensor, pinned or not) replaces parameters, u / v and both moments."""
+        n = self._snapshot_buffer(buf, "restore", False)
+        _check(self.lib, self.lib.sgv_restore(self.h, C.c_void_p(buf.data_ptr()), n), "sgv_restore")
 
     # ---- step ----
     def set_option(self, key: str, value: int):

@@ -6,6 +6,7 @@
   .forward(x) / __call__(x) -> (x_hat, recon_loss, [kl, kl2_0, ...], recon_loss_MSE)
   .encoder(x) -> (mu, log_var, xs) ; .decoder(z, xs, mode="random"|"fix", freeze_level=-1) -> (x_hat, kl_list)
   .state_dict() / .load_state_dict() with the reference's key names, .train()/.eval(), .to(),
+  .optimizer_state_dict() / .load_optimizer_state_dict() in the format of torch.optim.AdamW.state_dict(),
   .compile_model(mode) (no-op: there is no tracing compiler here), picklable.
 Differences a caller can observe: tensors returned are detached (gradients live inside the engine and
 are applied by `modules.train.train` / `VAE.training_step`), and the model only runs on a GPU.
@@ -101,6 +102,58 @@ class VAE:
             self._engine.load_state(st)
         else:
             self._pending_state = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in st.items()}
+        return self
+
+    # ---- optimizer state (torch.optim.AdamW.state_dict() format) ----
+    def _param_keys(self):
+        """[(state_dict key, trainable)] of the parameters in the reference module's parameters() order: the bias, weight_orig and
+        GroupNorm weight / bias entries of the state_dict, in its order (weight_u / weight_v are buffers)."""
+        return [(e.name, e.trainable) for e in self._eng().spec if e.kind in ("bias", "weight_orig", "gn_weight", "gn_bias")]
+
+    def optimizer_state_dict(self, lr=1e-3):
+        """What torch.optim.AdamW(model.parameters(), lr).state_dict() holds after the steps taken so far: state[i] =
+        {"step", "exp_avg", "exp_avg_sq"} for parameter i of parameters() (the parameters that never get a gradient have no entry,
+        as in torch; no entry at all before the first step) and one param_groups entry with torch's default keys."""
+        eng = self._eng()
+        keys = self._param_keys()
+        step = eng.train_state()["step"]
+        state = {}
+        if step > 0:
+            for i, (name, trainable) in enumerate(keys):
+                if not trainable:
+                    continue
+                m, v = eng.adam_state(name)
+                state[i] = {"step": torch.tensor(float(step)), "exp_avg": torch.from_numpy(m), "exp_avg_sq": torch.from_numpy(v)}
+        group = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr).state_dict()["param_groups"][0])
+        group["params"] = list(range(len(keys)))
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, sd):
+        """The inverse: moments and step count of an AdamW state dict in the format above go into the engine."""
+        eng = self._eng()
+        keys = self._param_keys()
+        groups = sd.get("param_groups", [])
+        if len(groups) != 1 or list(groups[0].get("params", [])) != list(range(len(keys))):
+            raise ValueError(f"optimizer state dict: expected one parameter group over {len(keys)} parameters")
+        steps = set()
+        for i, st in sd["state"].items():
+            i = int(i)
+            if not 0 <= i < len(keys):
+                raise ValueError(f"optimizer state dict: parameter index {i} outside [0, {len(keys)})")
+            name, trainable = keys[i]
+            if not trainable:
+                raise ValueError(f"optimizer state dict: parameter {i} ({name}) never gets a gradient and has no optimizer state")
+            shape = tuple(next(e.shape for e in eng.spec if e.name == name))
+            for part in ("exp_avg", "exp_avg_sq"):
+                if tuple(st[part].shape) != shape:
+                    raise ValueError(f"optimizer state dict: {part} of parameter {i} ({name}) has shape {tuple(st[part].shape)}, "
+                                     f"expected {shape}")
+            eng.load_adam(name, st["exp_avg"].detach().cpu().numpy(), st["exp_avg_sq"].detach().cpu().numpy())
+            steps.add(int(float(st["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"optimizer state dict: parameters disagree on the step count ({sorted(steps)}); the engine keeps one")
+        ts = eng.train_state()
+        eng.set_train_state(step=steps.pop() if steps else 0, seed=ts["seed"], draw=ts["draw"])
         return self
 
     def __getstate__(self):

@@ -4,7 +4,8 @@ modules.train.train (modules/train.py:50-256); the step itself runs in libsgvae.
 Deviations, on purpose: scalar losses are accumulated per step but read back without forcing a
 device sync per parameter tensor (the reference does ~200 `.item()` per step, train.py:156-174);
 under torch.distributed the gradients are averaged with an overlapped RCCL all-reduce (the
-reference's --use_ddp never synchronises gradients)."""
+reference's --use_ddp never synchronises gradients); `checkpoint_every` / `resume_from` (keyword-only, off by
+default) write and continue from exact training checkpoints, which the reference does not have."""
 from __future__ import annotations
 
 import logging
@@ -401,6 +402,118 @@ def make_allreduce(engine, group=None):
     return GradAllReduce(engine, group)
 
 
+RESUME_PATH = "checkpoints/SimulGen-VAE_resume.pt"
+RESUME_FORMAT = 1
+# the hyper-parameters that shape the schedules (epochs, LR: cosine restarts and KL warm-up are functions of both) and the model
+HYPER_KEYS = ("epochs", "batch_size", "LR", "alpha", "num_filter_enc", "num_filter_dec", "num_node", "latent_dim", "hierarchical_dim",
+              "num_time", "lossfun", "small", "compute_dtype")
+
+
+def write_checkpoint(path, payload):
+    """torch.save to a temporary file next to `path`, then os.replace: a run killed (or a writer that raises) midway leaves the
+    previous checkpoint as it was."""
+    tmp = f"{path}.tmp"
+    try:
+        torch.save(payload, tmp)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def read_checkpoint(path):
+    """The payload of write_checkpoint: tensors and plain Python containers only, so torch's restricted unpickler loads it."""
+    ck = torch.load(path, map_location="cpu", weights_only=True, mmap=True)      # the buffer's pages are read when restore copies them
+    if not isinstance(ck, dict) or ck.get("format") != RESUME_FORMAT:
+        raise ValueError(f"{path} is not a resume checkpoint of format {RESUME_FORMAT}")
+    return ck
+
+
+def _plain(v):
+    return list(v) if isinstance(v, (list, tuple)) else v
+
+
+def resume_hyper(**kw):
+    """The hyper-parameter record of a checkpoint, in the plain types the file stores."""
+    out = {}
+    for k in HYPER_KEYS:
+        v = kw[k]
+        if isinstance(v, (list, tuple)):
+            v = [int(x) for x in v]
+        elif isinstance(v, (bool, np.bool_)):
+            v = bool(v)
+        elif isinstance(v, (int, np.integer)):
+            v = int(v)
+        elif isinstance(v, (float, np.floating)):
+            v = float(v)
+        out[k] = v
+    return out
+
+
+def check_resume_hyper(ck, hyper):
+    """ValueError naming the first hyper-parameter of the checkpoint that differs from this run's."""
+    for k in HYPER_KEYS:
+        if k not in ck["hyper"] or _plain(ck["hyper"][k]) != _plain(hyper[k]):
+            raise ValueError(f"resume: hyper-parameter '{k}' differs: the checkpoint has {ck['hyper'].get(k)!r}, this run {hyper[k]!r}")
+
+
+def check_resume_layout(ck, total, rows):
+    """ValueError naming the first entry of the checkpoint's layout table that differs from the engine's."""
+    have = [tuple(r) for r in ck["layout"]]
+    want = [tuple(r) for r in rows]
+    for i in range(max(len(have), len(want))):
+        a = have[i] if i < len(have) else None
+        b = want[i] if i < len(want) else None
+        if a != b:
+            raise ValueError(f"resume: layout entry {i} differs: the checkpoint has {a}, the engine {b}")
+    if int(ck["total"]) != int(total) or ck["buffer"].numel() != int(total):
+        raise ValueError(f"resume: layout field 'total' differs: the checkpoint has {int(ck['total'])} floats "
+                         f"(buffer {ck['buffer'].numel()}), the engine {int(total)}")
+
+
+def rng_state():
+    """Python `random`, numpy and torch CPU generator states as tensors and plain containers."""
+    import random
+    version, internal, gauss = random.getstate()
+    name, keys, pos, has_gauss, cached = np.random.get_state()
+    return {"python": [int(version), [int(x) for x in internal], gauss],
+            "numpy": [str(name), torch.from_numpy(keys.astype(np.int64)), int(pos), int(has_gauss), float(cached)],
+            "torch": torch.get_rng_state().clone()}
+
+
+def set_rng_state(st):
+    import random
+    version, internal, gauss = st["python"]
+    random.setstate((int(version), tuple(int(x) for x in internal), gauss))
+    name, keys, pos, has_gauss, cached = st["numpy"]
+    np.random.set_state((str(name), keys.numpy().astype(np.uint32), int(pos), int(has_gauss), float(cached)))
+    torch.set_rng_state(st["torch"].to(torch.uint8))
+
+
+def loader_state(ld):
+    """What an exact resume needs of a loader: ResidentLoader's epoch counter, split (index list) and shuffle seed; None for the
+    fields a plain iterable does not have."""
+    idx = getattr(ld, "indices", None)
+    return {"epoch": getattr(ld, "epoch", None), "indices": [int(i) for i in idx] if idx is not None else None,
+            "shuffle_seed": getattr(ld, "shuffle_seed", None)}
+
+
+def set_loader_state(ld, st, which):
+    for k in ("epoch", "indices", "shuffle_seed"):
+        if (st[k] is None) != (getattr(ld, k, None) is None) and k != "shuffle_seed":
+            raise ValueError(f"resume: {which} loader field '{k}' differs: the checkpoint has {st[k]!r}, this run {getattr(ld, k, None)!r}")
+    if st["indices"] is not None:
+        if len(st["indices"]) != len(ld.indices):
+            raise ValueError(f"resume: {which} loader field 'indices' differs: the checkpoint's split has {len(st['indices'])} samples, "
+                             f"this run's {len(ld.indices)}")
+        ld.indices = list(st["indices"])
+    if st["epoch"] is not None:
+        ld.epoch = int(st["epoch"])
+    if hasattr(ld, "shuffle_seed"):
+        ld.shuffle_seed = st["shuffle_seed"]
+
+
 def _lookahead(it, first):
     """(current, next) pairs over `first` followed by the items of `it`; next is None for the last one."""
     cur = first
@@ -411,10 +524,27 @@ def _lookahead(it, first):
 
 
 def train(epochs, batch_size, train_dataloader, val_dataloader, LR, num_filter_enc, num_filter_dec, num_node, latent_dim,
-          hierarchical_dim, num_time, alpha, lossfun, small, load_all, debug_mode=0, compute_dtype="bf16"):
+          hierarchical_dim, num_time, alpha, lossfun, small, load_all, debug_mode=0, compute_dtype="bf16", *,
+          checkpoint_every=0, resume_from=None):
+    """checkpoint_every = k > 0: after every k-th epoch the whole training state goes to checkpoints/SimulGen-VAE_resume.pt (the
+    snapshot is taken behind the epoch's last step, the file is written while the next epoch's steps run on the GPU);
+    resume_from = such a file: the run continues behind the stored epoch, bit for bit as if it had never stopped."""
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    checkpoint_every = int(checkpoint_every or 0)
+    if checkpoint_every < 0:
+        raise ValueError(f"checkpoint_every must be >= 0, got {checkpoint_every}")
+    if world > 1 and (checkpoint_every > 0 or resume_from is not None):
+        raise NotImplementedError("data-parallel resume is not built: checkpoint_every / resume_from need world size 1 "
+                                  f"(this job has {world} ranks); the replica set-up protocol would have to carry the restored state")
+    hyper = resume_hyper(epochs=epochs, batch_size=batch_size, LR=LR, alpha=alpha, num_filter_enc=num_filter_enc,
+                         num_filter_dec=num_filter_dec, num_node=num_node, latent_dim=latent_dim, hierarchical_dim=hierarchical_dim,
+                         num_time=num_time, lossfun=lossfun, small=small, compute_dtype=compute_dtype)
+    ck = None
+    if resume_from is not None:
+        ck = read_checkpoint(resume_from)
+        check_resume_hyper(ck, hyper)           # before anything is built
     if rank == 0:
         os.makedirs("checkpoints", exist_ok=True)
         os.makedirs("output", exist_ok=True)
@@ -444,13 +574,45 @@ def train(epochs, batch_size, train_dataloader, val_dataloader, LR, num_filter_e
     recon_print = np.zeros(epochs)
     kl_print = np.zeros(epochs)
     recon_loss_val_print = np.zeros(epochs)
+    arrays = {"loss": loss_print, "loss_val": loss_val_print, "recon": recon_print, "kl": kl_print, "recon_val": recon_loss_val_print}
+    start_epoch = 0
+    if ck is not None:
+        total, rows = eng.snapshot_layout()
+        check_resume_layout(ck, total, rows)
+        eng.restore(ck["buffer"])
+        eng.set_train_state(**{k: int(v) for k, v in ck["train_state"].items()})
+        for k, a in arrays.items():
+            a[:] = ck["arrays"][k].numpy()
+        set_loader_state(train_dataloader, ck["loaders"]["train"], "train")
+        set_loader_state(val_dataloader, ck["loaders"]["val"], "val")
+        set_rng_state(ck["rng"])
+        start_epoch = int(ck["epoch"]) + 1
+        ck = None                               # the buffer is as large as the model's whole state
+    snap_buf = None
+    snap_meta = None                            # the payload of a snapshot whose copy is in flight
+
+    def snapshot_begin(epoch):
+        nonlocal snap_buf
+        total, rows = eng.snapshot_layout()
+        if snap_buf is None:
+            snap_buf = torch.empty(total, dtype=torch.float32).pin_memory()
+        eng.snapshot_begin(snap_buf)            # returns at once: the copy runs beside the next epoch's steps
+        return {"format": RESUME_FORMAT, "total": total, "layout": [list(r) for r in rows], "train_state": eng.train_state(),
+                "epoch": int(epoch), "arrays": {k: torch.from_numpy(a.copy()) for k, a in arrays.items()},
+                "loaders": {"train": loader_state(train_dataloader), "val": loader_state(val_dataloader)},
+                "rng": rng_state(), "hyper": hyper}
+
+    def snapshot_finish(meta):
+        eng.snapshot_wait()
+        meta["buffer"] = snap_buf
+        write_checkpoint(RESUME_PATH, meta)
 
     def run_forward_losses(sc, beta):
         kl = float(sum(sc["kls"]))
         recon = sc["recon"] * alpha
         return recon + kl * beta, recon, kl * beta
 
-    for epoch in range(epochs):
+    for epoch in range(start_epoch, epochs):
         t_start = time.time()
         model.train(True)
         beta, _ = warmup_kl.get_loss(epoch, [])
@@ -477,6 +639,9 @@ def train(epochs, batch_size, train_dataloader, val_dataloader, LR, num_filter_e
             else:
                 eng.backward_step(alpha, beta, lr)
             eng.accumulate_scalars()
+        if snap_meta is not None:                        # the last epoch's snapshot: this epoch's steps are enqueued, now wait and write
+            snapshot_finish(snap_meta)
+            snap_meta = None
         acc = eng.read_accumulated(reset=True)           # one read-back per epoch
         nb = acc["steps"]
         if nb == 0:
@@ -518,6 +683,11 @@ def train(epochs, batch_size, train_dataloader, val_dataloader, LR, num_filter_e
                              epoch + 1, epochs, loss_print[epoch], loss_val_print[epoch], recon_print[epoch],
                              recon_loss_val_print[epoch], kl_print[epoch], beta, grad_sum / nb, dur,
                              (epochs - epoch) * dur / 3600, lr))
+        if checkpoint_every > 0 and (epoch + 1) % checkpoint_every == 0 and rank == 0:
+            snap_meta = snapshot_begin(epoch)
+    if snap_meta is not None:
+        snapshot_finish(snap_meta)
+        snap_meta = None
     if allreduce is not None and hasattr(allreduce, "close"):
         torch.cuda.synchronize()
         allreduce.close()                 # the engine's own communicator (NativeAllReduce): unregister and destroy it

@@ -46,6 +46,7 @@ typedef enum {
 enum { SGV_DTYPE_F32 = 0, SGV_DTYPE_BF16 = 1 };
 enum { SGV_LOSS_MSE = 0, SGV_LOSS_MAE = 1, SGV_LOSS_SMOOTHL1 = 2, SGV_LOSS_HUBER = 3 };
 enum { SGV_MAX_LEVELS = 8 };
+enum { SGV_LAYOUT_TN = 0, SGV_LAYOUT_NT = 1 };   /* sgv_generate output: [B][T][N] (the data set's own order) or [B][N][T] (the reference's tensors) */
 
 /* Mirrors the constructor arguments of modules.VAE_network.VAE (modules/VAE_network.py:60):
  * VAE(latent_dim, hierarchical_dim, num_filter_enc, num_filter_dec, num_node, num_time,
@@ -126,6 +127,11 @@ int sgv_snapshot_slice(sgv_engine* e, int index, int which, size_t* offset_float
 int sgv_snapshot_begin(sgv_engine* e, float* host_pinned, size_t floats);
 int sgv_snapshot_wait(sgv_engine* e);
 int sgv_restore(sgv_engine* e, const float* host, size_t floats);
+/* The copy stream of the snapshots (created on first use, never on the engine stream's hardware queue), for a caller that moves
+ * results of its own to the host beside the engine's work: order it behind the engine stream with an event, as sgv_snapshot_begin
+ * does, and wait for its copies itself (an event or a stream
+ * synchronise): sgv_snapshot_wait only waits when a snapshot is in flight.  sgv_destroy drains and destroys the stream. */
+int sgv_copy_stream(sgv_engine* e, void** hip_stream);
 
 /* Refresh the compute-dtype weight copies from the fp32 masters after sgv_load_state. */
 int sgv_prepare(sgv_engine* e);
@@ -167,8 +173,19 @@ int sgv_forward(sgv_engine* e, int train, int mode_fix, float* scalars_host);
 /* Decoder.forward(z, xs, mode) from caller-supplied latents (utils.py:499, latent_conditioner_e2e.py:371,
  * reconstruction_evaluator.py:174): z_dev fp32 [B,latent], xs_dev fp32 [n_levels-1][B,hier] in the list
  * order Encoder.forward returns; eval-mode spectral norm.  Scalars as sgv_forward (the loss entries compare
- * against whatever input is current and are meaningless without one).  Result via sgv_get_xhat. */
+ * against whatever input is current and are meaningless without one).  Result via sgv_get_xhat.  xs_dev == NULL is SGV_ERR_ARG
+ * before anything is enqueued. */
 int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, float* scalars_host);
+/* Decoder.forward(z, xs, mode) as sgv_decode, but the reconstruction leaves the engine as a physical-unit field:
+ * out_dev fp32, layout SGV_LAYOUT_TN [B][T][N] or SGV_LAYOUT_NT [B][N][T]; scale_dev / min_dev fp32 [N] on the device
+ * (MinMaxScaler.scale_ / .min_ of data_scaler).  No loss is computed, x_in is not read, x_hat is not stored.
+ * One streaming kernel behind the recon head's convolution and statistics computes
+ * (tanh(GroupNorm(y)) - min_n) / scale_n in fp32 and stores it straight into out_dev (16-byte aligned): no compute-dtype
+ * rounding of the prediction on a bf16 engine.  Argument checks of sgv_decode, plus SGV_ERR_ARG for a NULL pointer or an unknown
+ * layout, before anything is enqueued.  Synchronises nothing.  Afterwards there is no forward pass to read from:
+ * sgv_get_xhat / sgv_get_activation / sgv_backward answer SGV_ERR_STATE until the next sgv_forward / sgv_decode. */
+int sgv_generate(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix,
+                 const float* scale_dev, const float* min_dev, int layout, float* out_dev);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -424,6 +441,11 @@ int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long
                         const float* gamma, const float* beta, double* sums, double* loss_sums, double* sums2, float* unit, float gscale,
                         void* dy, long lddy, float* cdot, const float* cbias, float* work, size_t work_floats, int B, int T, int C,
                         int G, void* stream);
+/* The kernel of sgv_generate on caller-owned buffers: statistics of y (ew_gn_stats, groups by the model's rule
+ * G = min(8, max(1, C / 4))), then out = (tanh(GroupNorm(y)) - min) / scale as fp32, layout SGV_LAYOUT_TN [B][T][C] or
+ * SGV_LAYOUT_NT [B][C][T], dense and 16-byte aligned; sums [B*G][2] fp64 (written), scale / min [C] fp32. */
+int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, int layout, float* out, int B, int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

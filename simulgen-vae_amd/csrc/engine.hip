@@ -1544,8 +1544,10 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
     return 0;
 }
 
-// Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass.
-static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix) {
+// Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen` (sgv_generate),
+// the recon head's convolution and statistics followed by the physical-field pass instead of the loss tail.
+struct GenOut { const float* scale; const float* mn; int layout; float* out; };
+static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
     for (int s = 1; s < n_st; ++s) {
@@ -1597,6 +1599,10 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix) {
         CHK(conv_fwd(e, L, e->dec_out[n_st - 1], S.y, M));
         ew_gn_stats(e->dt, p, e->stream);
     }
+    if (gen) {          // no loss, no read of x_in, no x_hat: the fp32 physical field goes straight to the caller's buffer
+        const int r = ew_recon_physical(e->dt, p, gen->scale, gen->mn, gen->layout, gen->out, e->stream);
+        return r ? fail(SGV_ERR_ARG, "sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)", r) : 0;
+    }
     p.dout = e->x_in.p; p.lddout = e->x_in.ld; p.loss_type = e->cfg.loss_type;
     p.loss_sums = e->scal;
     if (e->write_xhat || !train) { p.out = e->xhat.p; p.ldout = e->xhat.ld; }
@@ -1642,9 +1648,13 @@ int sgv_forward(sgv_engine* e, int train, int mode_fix, float* scalars_host) {
     return SGV_OK;
 }
 
-int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, float* scalars_host) {
+// what sgv_decode and sgv_generate share in front of decoder_fwd: argument checks, fresh weight copies, eval-mode spectral norm,
+// the caller's latents into e->zlat / e->xs_raw
+static int decode_begin(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, const char* who) {
     if (!e || !z_dev) return fail(SGV_ERR_ARG, "null argument");
     if (batch < 1 || batch > e->maxB) return fail(SGV_ERR_ARG, "batch %d outside [1,%d]", batch, e->maxB);
+    if (!xs_dev)
+        return fail(SGV_ERR_ARG, "%s needs xs (Decoder.forward with xs=None leaves z unchanged between stages in the reference; not supported)", who);
     if (!e->copies_fresh) CHK(refresh_copies(e));
     const int B = batch;
     e->batch = B;
@@ -1652,18 +1662,34 @@ int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch
     HIPCHK(hipMemsetAsync(e->scal, 0, 16 * 8, e->stream));
     CHK(run_sn(e, 0));
     HIPCHK(hipMemcpyAsync(e->zlat, z_dev, (size_t)B * e->Z * 4, hipMemcpyDeviceToDevice, e->stream));
-    if (xs_dev) {
-        // list order of Encoder.forward's return: [xs_{n-2}, ..., xs_0]
-        for (int j = 0; j < e->n - 1; ++j)
-            HIPCHK(hipMemcpyAsync(e->xs_raw[e->n - 2 - j], xs_dev + (size_t)j * B * e->H, (size_t)B * e->H * 4, hipMemcpyDeviceToDevice, e->stream));
-    } else {
-        return fail(SGV_ERR_ARG, "sgv_decode needs xs (Decoder.forward with xs=None leaves z unchanged between stages in the reference; not supported)");
-    }
-    CHK(decoder_fwd(e, B, 0, mode_fix));
+    // list order of Encoder.forward's return: [xs_{n-2}, ..., xs_0]
+    for (int j = 0; j < e->n - 1; ++j)
+        HIPCHK(hipMemcpyAsync(e->xs_raw[e->n - 2 - j], xs_dev + (size_t)j * B * e->H, (size_t)B * e->H * 4, hipMemcpyDeviceToDevice, e->stream));
+    return 0;
+}
+
+int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, float* scalars_host) {
+    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_decode"));
+    CHK(decoder_fwd(e, batch, 0, mode_fix));
     e->have_fwd = true;
     e->fwd_train = false;
     for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
-    if (scalars_host) CHK(read_scalars(e, B, scalars_host));
+    if (scalars_host) CHK(read_scalars(e, batch, scalars_host));
+    return SGV_OK;
+}
+
+int sgv_generate(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                 const float* min_dev, int layout, float* out_dev) {
+    if (!e || !z_dev || !scale_dev || !min_dev || !out_dev) return fail(SGV_ERR_ARG, "sgv_generate: null argument");
+    if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "sgv_generate: unknown layout %d", layout);
+    if ((uintptr_t)out_dev & 15) return fail(SGV_ERR_ARG, "sgv_generate: out_dev must be 16-byte aligned");
+    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_generate"));
+    // the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
+    e->have_fwd = false;
+    e->fwd_train = false;
+    const GenOut gen = {scale_dev, min_dev, layout, out_dev};
+    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
+    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
     return SGV_OK;
 }
 

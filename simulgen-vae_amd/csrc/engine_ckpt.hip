@@ -164,6 +164,14 @@ static bool ckpt_geometry(const sgv_engine* e, const StateEntry& s, CkptTile& t,
     return plain();
 }
 
+// the copy stream, made on first use: never on the main stream's hardware queue (nor on the side / second-lane streams'), so that a
+// copy runs beside the next step
+static hipStream_t ckpt_copy_stream(sgv_engine* e) {
+    CkptState* c = ckpt_layout(e);
+    if (!c->stream) make_aux_stream(&c->stream, "snapshot copy", {e->stream, e->side, e->lane2});
+    return c->stream;
+}
+
 static int ckpt_prepare(sgv_engine* e) {
     CkptState* c = ckpt_layout(e);
     if (c->staging) return 0;
@@ -205,8 +213,7 @@ static int ckpt_prepare(sgv_engine* e) {
         return fail(SGV_ERR_HIP, "snapshot table upload failed");
     c->n_items_tile = (int)it_tile.size(); c->n_items_copy = (int)it_copy.size();
     HIPCHK(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
-    // never on the main stream's hardware queue (nor on the side / second-lane streams'): the copy must run beside the next step
-    if (make_aux_stream(&c->stream, "snapshot copy", {e->stream, e->side, e->lane2}) != hipSuccess || !c->stream) return fail(SGV_ERR_HIP, "snapshot copy stream creation failed");
+    if (!ckpt_copy_stream(e)) return fail(SGV_ERR_HIP, "snapshot copy stream creation failed");
     HIPCHK(hipMalloc((void**)&c->staging, std::max<size_t>(c->total, 1) * sizeof(float)));
     return 0;
 }
@@ -272,6 +279,14 @@ int sgv_snapshot_wait(sgv_engine* e) {
     if (!c || !c->pending) return SGV_OK;
     c->pending = false;
     HIPCHK(hipStreamSynchronize(c->stream));
+    return SGV_OK;
+}
+
+int sgv_copy_stream(sgv_engine* e, void** hip_stream) {
+    if (!e || !hip_stream) return fail(SGV_ERR_ARG, "null argument");
+    hipStream_t s = ckpt_copy_stream(e);
+    if (!s) return fail(SGV_ERR_HIP, "copy stream creation failed");
+    *hip_stream = (void*)s;
     return SGV_OK;
 }
 

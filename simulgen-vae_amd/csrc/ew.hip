@@ -56,6 +56,18 @@ __device__ __forceinline__ GNCtx gn_ctx(const GNParams& p) {
     return c;
 }
 
+// mean and 1 / sqrt(var + eps) of group g of sample b from the fp64 (sum, sum of squares) in p.sums: the one place they are derived
+__device__ __forceinline__ void gn_mean_rstd(const GNParams& p, int b, int g, float& mean, float& rstd) {
+    const double n = (double)p.Cg * (double)p.T;
+    const double s = p.sums[((long)b * p.G + g) * 2 + 0];
+    const double ss = p.sums[((long)b * p.G + g) * 2 + 1];
+    const double m = s / n;
+    double var = ss / n - m * m;
+    if (var < 0.0) var = 0.0;
+    mean = (float)m;
+    rstd = (float)(1.0 / sqrt(var + 1e-5));
+}
+
 // per-element mean / rstd (and, WITH_M, the backward means m1 = s1/n, m2 = s2/n) of the element's group.
 // The fp64 divide/sqrt chain runs once per block on G threads and is broadcast through LDS: done per
 // thread it cost more than the streaming work of the small layers.  Must be called by all 256 threads.
@@ -65,15 +77,9 @@ __device__ __forceinline__ void gn_consts(const GNParams& p, const GNCtx& c, flo
     __shared__ float gc[SGV_GN_MAX_GROUPS][4];
     if ((int)threadIdx.x < p.G) {
         const int g = threadIdx.x;
-        const double n = (double)p.Cg * (double)p.T;
-        const double s = p.sums[((long)c.b * p.G + g) * 2 + 0];
-        const double ss = p.sums[((long)c.b * p.G + g) * 2 + 1];
-        const double m = s / n;
-        double var = ss / n - m * m;
-        if (var < 0.0) var = 0.0;
-        gc[g][0] = (float)m;
-        gc[g][1] = (float)(1.0 / sqrt(var + 1e-5));
+        gn_mean_rstd(p, c.b, g, gc[g][0], gc[g][1]);
         if constexpr (WITH_M) {
+            const double n = (double)p.Cg * (double)p.T;
             gc[g][2] = (float)(p.sums2[((long)c.b * p.G + g) * 2 + 0] / n);
             gc[g][3] = (float)(p.sums2[((long)c.b * p.G + g) * 2 + 1] / n);
         }
@@ -1228,6 +1234,104 @@ int ew_recon_bwd_apply(int dtype, GNParams p, hipStream_t s) {
     gn_fin_immediate(p, false, own_dots, grid_total(gn_geom(p.B, p.T, p.C).grid), s);
     return 0;
 }
+// ------------------------------------------------------------------------------------------
+// Surrogate prediction: recon head -> physical-unit field in one pass (sgv_generate).
+//   out = (tanh(gamma * (y - mean) * rstd + beta) - min_n) / scale_n      (MinMaxScaler.inverse_transform per node)
+// fp32 from the load of y to the fp32 store: no loss, no target read, no compute-dtype x_hat in between.  mean / rstd come from
+// p.sums exactly as in the eval loss pass (gn_consts; the normalised value is formed as (y - mean) * rstd first, as there).
+// ------------------------------------------------------------------------------------------
+struct ReconPhys { const float* scale; const float* mn; float* out; };
+
+// [B][T][N]: the geometry of gn_apply_kernel, 16-byte loads of y and two 16-byte stores per thread and row
+template <typename T>
+__global__ __launch_bounds__(256) void recon_phys_tn_kernel(const GNParams p, const ReconPhys q) {
+    const GNCtx c = gn_ctx(p);
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);
+    if (!c.col_ok) return;
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        gam[e] = p.gamma[c.c0 + e]; bet[e] = p.beta[c.c0 + e];
+        mn[e] = q.mn[c.c0 + e]; inv[e] = 1.0f / q.scale[c.c0 + e];      // correctly rounded reciprocal, once per thread
+    }
+    const T* y = reinterpret_cast<const T*>(p.y);
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += 2 * c.RL) {      // two rows per round, loads first
+        const bool two = t + c.RL < c.t_hi;
+        const long m0 = (long)c.b * p.T + t, m1 = two ? m0 + c.RL : m0;
+        Raw8<T> r0, r1;
+        raw_load(y + m0 * p.ldy + c.c0, r0);
+        raw_load(y + m1 * p.ldy + c.c0, r1);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (u == 1 && !two) break;
+            float v[8];
+            raw_unpack(u ? r1 : r0, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float xh = (v[e] - mean[e]) * rstd[e];
+                v[e] = (tanh_f(xh * gam[e] + bet[e]) - mn[e]) * inv[e];
+            }
+            store8(q.out + (u ? m1 : m0) * p.C + c.c0, v);
+        }
+    }
+}
+
+// [B][N][T] (the reference's tensor layout): a tile of 32 rows (t) x 64 channels goes through LDS transposed; every thread loads
+// 8 channels of one row (16 / 32 bytes), the stores run along T.  blockIdx = (channel tile, row tile, sample).
+constexpr int RP_TT = 32, RP_TN = 64;
+template <typename T>
+__global__ __launch_bounds__(256) void recon_phys_nt_kernel(const GNParams p, const ReconPhys q) {
+    __shared__ float tile[RP_TN][RP_TT + 1];
+    __shared__ float cst[6][RP_TN];          // per channel of the tile: mean, rstd, gamma, beta, min, 1 / scale
+    const int b = blockIdx.z, n0 = blockIdx.x * RP_TN, t0 = blockIdx.y * RP_TT;
+    const int tid = threadIdx.x;
+    if (tid < RP_TN && n0 + tid < p.C) {
+        const int ch = n0 + tid, g = min(ch / p.Cg, p.G - 1);
+        gn_mean_rstd(p, b, g, cst[0][tid], cst[1][tid]);
+        cst[2][tid] = p.gamma[ch]; cst[3][tid] = p.beta[ch]; cst[4][tid] = q.mn[ch]; cst[5][tid] = 1.0f / q.scale[ch];
+    }
+    __syncthreads();
+    const int r = tid >> 3, cx = (tid & 7) * 8;          // row of the tile, first of this thread's 8 channels
+    const int t = t0 + r;
+    if (t < p.T && n0 + cx < p.C) {
+        float v[8];
+        load8(reinterpret_cast<const T*>(p.y) + ((long)b * p.T + t) * p.ldy + n0 + cx, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int j = cx + e;
+            const float xh = (v[e] - cst[0][j]) * cst[1][j];
+            tile[j][r] = (tanh_f(xh * cst[2][j] + cst[3][j]) - cst[4][j]) * cst[5][j];
+        }
+    }
+    __syncthreads();
+    const int tx = tid & 31;
+    if (t0 + tx < p.T) {
+        for (int j = tid >> 5; j < RP_TN; j += 8) {
+            if (n0 + j >= p.C) break;
+            q.out[((long)b * p.C + n0 + j) * p.T + t0 + tx] = tile[j][tx];
+        }
+    }
+}
+// p: y / ldy / gamma / beta / sums (given) / B, T, C, G, Cg; scale, mn [C] fp32; out fp32, dense: layout 0 [B][T][C], 1 [B][C][T]
+int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn, int layout, float* out, hipStream_t s) {
+    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn || !out) return -1;
+    if (layout != 0 && layout != 1) return -2;
+    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)out) & 15) return -4;          // 16-byte vector accesses
+    p.Cg = p.C / p.G;
+    const ReconPhys q = {scale, mn, out};
+    if (layout == 0) {
+        if (dtype == 1) GN_LAUNCH((recon_phys_tn_kernel<bf16_t>), p, s, q);
+        else GN_LAUNCH((recon_phys_tn_kernel<float>), p, s, q);
+    } else {
+        const dim3 grid(cdiv_i(p.C, RP_TN), cdiv_i(p.T, RP_TT), p.B);
+        if (dtype == 1) hipLaunchKernelGGL((recon_phys_nt_kernel<bf16_t>), grid, dim3(256), 0, s, p, q);
+        else hipLaunchKernelGGL((recon_phys_nt_kernel<float>), grid, dim3(256), 0, s, p, q);
+    }
+    return 0;
+}
+
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s) {
     float* const ws = p.part;
     const bool own_dots = mode != 0 && p.cdot && !p.cdot_part;

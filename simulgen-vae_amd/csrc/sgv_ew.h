@@ -109,6 +109,9 @@ int ew_gn_max_blocks(int B, int T, int C);
 int ew_act_part_rows(int B, int T, int C);         // rows of per-block column sums an ew_act launch with dbias writes          // upper bound of the per-block <G,W_eff> partials one launch writes
 int ew_recon_loss(int dtype, int train, GNParams p, hipStream_t s);
 int ew_recon_bwd_apply(int dtype, GNParams p, hipStream_t s);
+// recon head -> physical-unit fp32 field: out = (tanh(GroupNorm(y)) - mn) / scale per channel; layout 0 [B][T][C], 1 [B][C][T] (dense).
+// Non-zero (nothing launched): -1 null pointer, -2 unknown layout, -3 bad shape, -4 y or out not 16-byte aligned
+int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn, int layout, float* out, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

@@ -245,6 +245,29 @@ int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long
     }
     return ew_hook_done(r, "sgv_test_recon_loss", stream);
 }
+int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, int layout, float* out, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_physical";
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
+    if (!y || !sums || !gamma || !beta || !scale || !min || !out) return fail(SGV_ERR_ARG, "%s: null argument", me);
+    if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "%s: unknown layout %d", me, layout);
+    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
+    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
+    if (((uintptr_t)y | (uintptr_t)out) & 15) return fail(SGV_ERR_ARG, "%s: y and out must be 16-byte aligned", me);
+    GNParams p;
+    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
+    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
+    p.y = y; p.ldy = ldy; p.sums = sums;
+    float* work = nullptr;
+    HIPCHK(hipMalloc((void**)&work, sizeof(float) * ew_gn_part_floats(B, T, C)));
+    p.part = work;
+    hipStream_t s = (hipStream_t)stream;
+    int r = ew_gn_stats(dtype, p, s);
+    if (!r) r = ew_recon_physical(dtype, p, scale, min, layout, out, s);
+    const int rc = ew_hook_done(r, me, stream);
+    hipFree(work);
+    return rc;
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

@@ -19,12 +19,13 @@ LIB_PATH = os.environ.get("SGV_LIB") or os.path.join(_HERE, "csrc", "libsgvae.so
 MAX_LEVELS = 8
 MAX_SCALARS = 12
 DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
+LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T, N] or [B, N, T]
 
 # every symbol include/sgvae.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -32,9 +33,9 @@ ABI_SYMBOLS = [
     "sgv_rccl_unique_id", "sgv_rccl_probe", "sgv_rccl_comm_count", "sgv_rccl_allreduce", "sgv_rccl_comm_init", "sgv_rccl_comm_destroy", "sgv_allreduce_grads", "sgv_set_rccl", "sgv_comm_stream",
     "sgv_augment_stage", "sgv_augment_advance",
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
-    "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore",
+    "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -101,6 +102,8 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_forward.argtypes = [vp, i32, i32, vp]
     lib.sgv_encode.argtypes = [vp, vp, vp, vp]
     lib.sgv_decode.argtypes = [vp, vp, vp, i32, i32, vp]
+    lib.sgv_generate.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
     lib.sgv_backward.argtypes = [vp, f32, f32]
@@ -161,6 +164,7 @@ def load_library(path: str = LIB_PATH):
                                     i32, i32, i32, i32, C.POINTER(i32), vp]
     lib.sgv_test_recon_loss.argtypes = [i32, i32, i32, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, vp, vp, f32, vp, lg, vp, vp, vp, sz,
                                         i32, i32, i32, i32, vp]
+    lib.sgv_test_recon_physical.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -396,6 +400,39 @@ class Engine:
                "sgv_decode")
         self.batch = B
         return [buf[2 + i] for i in range(self.n_kl - 1)]
+
+    def generate(self, z, xs, scale, min, out=None, layout="TN", fix=True):
+        """Decoder.forward(z, xs, mode) delivered as a physical-unit field: (x_hat - min) / scale per node (MinMaxScaler.inverse_transform
+        of data_scaler), fp32, written by the recon head's output pass straight into `out` -- [B, T, N] for layout "TN", [B, N, T] for
+        "NT"; allocated when None.  z [B, latent], xs a list of [B, hier] in Encoder order (or one [n_levels - 1, B, hier] tensor),
+        scale / min fp32 CUDA [num_node].  Nothing synchronises; afterwards there is no forward pass to read (xhat() raises)."""
+        t = self.torch
+        if layout not in LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, not {layout!r}")
+        B, N, T = z.shape[0], self.cfg.num_node, self.cfg.num_time
+        z = z.to(device="cuda", dtype=t.float32).contiguous()
+        xs_t = (xs if t.is_tensor(xs) else t.stack([x.to(device="cuda", dtype=t.float32) for x in xs])).to(device="cuda", dtype=t.float32).contiguous()
+        if tuple(xs_t.shape) != (self.n_kl, B, self.cfg.hierarchical_dim):
+            raise ValueError(f"xs of shape {tuple(xs_t.shape)}, expected {(self.n_kl, B, self.cfg.hierarchical_dim)}")
+        for name, v in (("scale", scale), ("min", min)):
+            if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == N):
+                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
+        shape = (B, T, N) if layout == "TN" else (B, N, T)
+        if out is None:
+            out = t.empty(shape, dtype=t.float32, device="cuda")
+        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
+        _check(self.lib, self.lib.sgv_generate(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
+                                               C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), LAYOUTS[layout],
+                                               C.c_void_p(out.data_ptr())), "sgv_generate")
+        self.batch = B
+        return out
+
+    def copy_stream(self) -> int:
+        """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""
+        p = C.c_void_p()
+        _check(self.lib, self.lib.sgv_copy_stream(self.h, C.byref(p)), "sgv_copy_stream")
+        return p.value
 
     def encode(self):
         B, Z, Hd = self.batch, self.cfg.latent_dim, self.cfg.hierarchical_dim

@@ -495,15 +495,17 @@ class LatentConditionerImg:
         return out, bwd
 
     # ---- forward / backward -----------------------------------------------------------------------------------------
-    def forward(self, x, dropout_masks=None):
-        """x: [B, H*W] (or anything reshapeable to it) -> (latent_main [B, latent_dim_end], xs [B, size2, latent_dim])."""
+    def forward(self, x, dropout_masks=None, remap=None):
+        """x: [B, H*W] (or anything reshapeable to it) -> (latent_main [B, latent_dim_end], xs [B, size2, latent_dim]).
+        remap: None tests the batch's minimum as the reference's forward does (a device-to-host read: the host waits for the
+        stream); True / False: the caller has decided whether the inputs are in [-1, 1], and nothing is read back."""
         if not torch.is_tensor(x):
             x = torch.as_tensor(np.asarray(x))
         x = x.to(device="cuda", dtype=torch.float32)
         B = x.shape[0]
         side = int(math.sqrt(x.shape[-1]))
         x = x.reshape(B, side, side)
-        if float(x.min()) < -0.1:          # reference forward: inputs in [-1, 1] are mapped to [0, 1]
+        if (float(x.min()) < -0.1) if remap is None else remap:          # reference forward: inputs in [-1, 1] are mapped to [0, 1]
             x = (x + 1) / 2
         masks = list(dropout_masks) if dropout_masks is not None else None
         self.grads = {}

@@ -1,6 +1,7 @@
 // libsgvae engine: parameter/optimizer arenas, layer graph of the hierarchical VAE, forward /
 // backward orchestration on one HIP stream, and the engine's part of the C ABI of include/sgvae.h.
-// Beside it, sharing engine_internal.h: engine_comm.hip (RCCL), engine_streams.hip (auxiliary streams), engine_input.hip, test_hooks.hip.
+// Beside it, sharing engine_internal.h: engine_build.hip (what runs once at creation), engine_optim.hip (gradient buckets, AdamW), engine_comm.hip (RCCL),
+// engine_streams.hip (auxiliary streams), engine_input.hip, engine_ckpt.hip, test_hooks.hip.
 //
 // Graph restated from the reference (channels-last, weights [tap][Cout][Cin]):
 //   VAE.forward modules/VAE_network.py:79-121 ; Encoder modules/encoder.py:96-167 ;
@@ -19,572 +20,6 @@ int sgv_set_error(int code, const char* fmt, ...) {
     return code;
 }
 extern "C" const char* sgv_last_error(void) { return g_err; }
-
-// ------------------------------------------------------------------------------------------
-static int gn_groups(int c) { int g = c / 4; if (g < 1) g = 1; if (g > 8) g = 8; return g; }
-
-struct Builder {
-    sgv_engine* e;
-    size_t np = 0, ngw = 0, ngs = 0, ncp = 0;
-    std::vector<size_t*> small_grad_slots;   // gb / ggamma / gbeta offsets get rebased after the weight zone
-    int add_layer(const std::string& prefix, int op, int cin, int cout, int k, bool used, bool has_grad, bool need_wct,
-                  int lin_kind = LIN_NONE, int lin_C = 0) {
-        Layer l;
-        l.prefix = prefix; l.op = op; l.cin = cin; l.cout = cout; l.k = k;
-        l.used = used; l.has_grad = has_grad; l.need_wct = need_wct && used && op != OP_LINEAR;
-        l.lin_kind = lin_kind; l.lin_C = lin_C;
-        e->layers.push_back(l);
-        return (int)e->layers.size() - 1;
-    }
-    int add_gn(const std::string& prefix, int C, bool used, bool has_grad) {
-        GNLayer g;
-        g.prefix = prefix; g.C = C; g.G = gn_groups(C); g.used = used; g.has_grad = has_grad;
-        e->gns.push_back(g);
-        return (int)e->gns.size() - 1;
-    }
-};
-
-static Tensor alloc_act(sgv_engine* e, long rows, int C, bool f32 = false) {
-    Tensor t;
-    t.C = C; t.ld = C; t.f32 = f32;
-    size_t bytes = (size_t)rows * C * (f32 ? 4 : e->esz);
-    e->act_used = align_up(e->act_used, 256);
-    t.p = (void*)(e->act_used);   // offset for now; rebased after allocation
-    e->act_used += bytes;
-    return t;
-}
-static Tensor view_cols(const Tensor& t, int c0, int C, sgv_engine* e) {
-    Tensor v = t;
-    v.p = (char*)t.p + (size_t)c0 * (t.f32 ? 4 : e->esz);
-    v.C = C;
-    return v;
-}
-
-// ---- state-entry list in reference order (mirrors simulgen-vae_amd/spec.py) --------------------
-static void add_entries_for_layer(sgv_engine* e, int li) {
-    const Layer& l = e->layers[li];
-    auto push = [&](const char* suffix, int kind, std::vector<int64_t> shape, bool hg) {
-        StateEntry s;
-        s.name = l.prefix + suffix; s.kind = kind; s.layer = li; s.shape = shape; s.has_grad = hg;
-        e->entry_index[s.name] = (int)e->entries.size();
-        e->entries.push_back(s);
-    };
-    push(".bias", 0, {l.cout}, l.has_grad);
-    if (l.op == OP_CONV) push(".weight_orig", 1, {l.cout, l.cin, l.k}, l.has_grad);
-    else if (l.op == OP_CONVT) push(".weight_orig", 1, {l.cin, l.cout, l.k}, l.has_grad);
-    else push(".weight_orig", 1, {l.cout, l.cin}, l.has_grad);
-    push(".weight_u", 2, {l.cout}, false);
-    push(".weight_v", 3, {(int64_t)l.cin * l.k}, false);
-}
-static void add_entries_for_gn(sgv_engine* e, int gi) {
-    const GNLayer& g = e->gns[gi];
-    StateEntry s;
-    s.name = g.prefix + ".weight"; s.kind = 4; s.gn = gi; s.shape = {g.C}; s.has_grad = g.has_grad;
-    e->entry_index[s.name] = (int)e->entries.size(); e->entries.push_back(s);
-    s.name = g.prefix + ".bias"; s.kind = 5;
-    e->entry_index[s.name] = (int)e->entries.size(); e->entries.push_back(s);
-}
-
-static Stage mk_stage(int layer, int gn, int act, bool pre_gelu = false, bool out_f32 = false) {
-    Stage s;
-    s.layer = layer; s.gn = gn; s.act = act; s.pre_gelu = pre_gelu; s.out_f32 = out_f32;
-    return s;
-}
-
-// Build layers + blocks in the reference's module registration order so that `entries` comes out in
-// state_dict order (encoder: blocks, residual blocks, xs_linear, last; decoder: blocks, residual blocks,
-// recon, sequence_start, xs_sequence, condition_z, condition_xz).
-static int build_graph(sgv_engine* e) {
-    Builder B{e};
-    const bool small = e->cfg.small != 0;
-    const int n = e->n, T = e->T;
-    char buf[256];
-    auto P = [&](const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap); return std::string(buf); };
-    std::vector<std::function<void()>> entry_order;
-
-    e->encA.resize(n); e->encR.resize(n);
-    for (int i = 0; i < n; ++i) {
-        const int cin = i == 0 ? e->N : e->enc[i - 1], C = e->enc[i];
-        std::string p = P("encoder.encoder_blocks.%d.module_list.0._seq", i);
-        int l0 = B.add_layer(p + ".0", OP_CONV, cin, C, 1, true, true, i > 0);
-        int g0 = B.add_gn(p + ".1", C, true, true);
-        add_entries_for_layer(e, l0); add_entries_for_gn(e, g0);
-        e->encA[i].st.push_back(mk_stage(l0, g0, 1));
-        if (!small) {
-            int l1 = B.add_layer(p + ".3", OP_CONV, C, C, 3, true, true, true);
-            int g1 = B.add_gn(p + ".4", C, true, true);
-            add_entries_for_layer(e, l1); add_entries_for_gn(e, g1);
-            e->encA[i].st.push_back(mk_stage(l1, g1, 1));
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        const int C = e->enc[i];
-        std::string p = P("encoder.encoder_residual_blocks.%d.seq", i);
-        e->encR[i].residual = true;
-        for (int r = 0; r < (small ? 1 : 2); ++r) {
-            int l = B.add_layer(p + P(".%d", r * 3), OP_CONV, C, C, 3, true, true, true);
-            int g = B.add_gn(p + P(".%d", r * 3 + 1), C, true, true);
-            add_entries_for_layer(e, l); add_entries_for_gn(e, g);
-            e->encR[i].st.push_back(mk_stage(l, g, 1));
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        const bool dead = (i == 0) || (i == n - 1);
-        int l = B.add_layer(P("encoder.xs_linear.%d", i), OP_LINEAR, e->enc[i] * T, e->H, 1, true, !dead, false, LIN_HEAD, e->enc[i]);
-        add_entries_for_layer(e, l);
-        e->xs_lin.push_back(l);
-    }
-    e->last_lin = B.add_layer("encoder.last_x_linear", OP_LINEAR, e->enc[n - 1] * T, 2 * e->Z, 1, true, true, false, LIN_HEAD, e->enc[n - 1]);
-    add_entries_for_layer(e, e->last_lin);
-
-    const int n_st = e->n_st;
-    e->decU.resize(n_st); e->decD.resize(n_st);
-    e->decP1.resize(n_st); e->decP2.resize(n_st); e->decX.resize(n_st); e->decQ1.resize(n_st); e->decQ2.resize(n_st);
-    for (int i = 0; i < n_st; ++i) {
-        int l = B.add_layer(P("decoder.decoder_blocks.%d.module_list.0._seq.0", i), OP_CONVT, e->dec[i], e->dec[i + 1], 3, true, true, true);
-        add_entries_for_layer(e, l);
-        e->decU[i].st.push_back(mk_stage(l, -1, 1));
-    }
-    for (int i = 0; i < n_st; ++i) {
-        const int C = e->dec[i + 1];
-        std::string p = P("decoder.decoder_residual_blocks.%d.seq", i);
-        e->decD[i].residual = true;
-        struct CS { int cin, cout, k; };
-        std::vector<CS> cs;
-        if (small) cs = {{C, 5 * C, 1}, {5 * C, 5 * C, 5}, {5 * C, C, 1}};
-        else cs = {{C, C, 1}, {C, 5 * C, 5}, {5 * C, 5 * C, 5}, {5 * C, C, 1}};
-        for (size_t r = 0; r < cs.size(); ++r) {
-            int l = B.add_layer(p + P(".%d", (int)r * 3), OP_CONV, cs[r].cin, cs[r].cout, cs[r].k, true, true, true);
-            int g = B.add_gn(p + P(".%d", (int)r * 3 + 1), cs[r].cout, true, true);
-            add_entries_for_layer(e, l); add_entries_for_gn(e, g);
-            e->decD[i].st.push_back(mk_stage(l, g, 1));
-        }
-    }
-    {
-        int l = B.add_layer("decoder.recon.0", OP_CONV, e->dec[n_st], e->N, 1, true, true, true);
-        int g = B.add_gn("decoder.recon.1", e->N, true, true);
-        add_entries_for_layer(e, l); add_entries_for_gn(e, g);
-        e->recon.st.push_back(mk_stage(l, g, 2));
-    }
-    {
-        e->start_lin = B.add_layer("decoder.sequence_start.0.0", OP_LINEAR, e->Z, e->Z * T, 1, true, true, false, LIN_EXPAND, e->Z);
-        int l = B.add_layer("decoder.sequence_start.0.2", OP_CONV, e->Z, e->dec[0], 5, true, true, true);
-        int g = B.add_gn("decoder.sequence_start.0.3", e->dec[0], true, true);
-        add_entries_for_layer(e, e->start_lin); add_entries_for_layer(e, l); add_entries_for_gn(e, g);
-        e->decS.st.push_back(mk_stage(l, g, 1));
-    }
-    for (int i = 0; i < n_st; ++i) {
-        const bool live = i < n_st - 1;
-        std::string p = P("decoder.xs_sequence.%d", i);
-        int ll = B.add_layer(p + ".0", OP_LINEAR, e->H, e->H * T, 1, live, live, false, LIN_EXPAND, e->H);
-        int l = B.add_layer(p + ".2", OP_CONV, e->H, e->dec[i + 1], 5, live, live, true);
-        int g = B.add_gn(p + ".3", e->dec[i + 1], live, live);
-        add_entries_for_layer(e, ll); add_entries_for_layer(e, l); add_entries_for_gn(e, g);
-        e->xs_exp.push_back(ll);
-        e->decX[i].st.push_back(mk_stage(l, g, 1));
-    }
-    for (int which = 0; which < 2; ++which) {
-        for (int i = 0; i < n_st; ++i) {
-            const bool live = i < n_st - 1;
-            const int C = (which + 1) * e->dec[i + 1];
-            std::string p = P("decoder.%s.%d", which ? "condition_xz" : "condition_z", i);
-            Block& b1 = which ? e->decQ1[i] : e->decP1[i];
-            Block& b2 = which ? e->decQ2[i] : e->decP2[i];
-            b1.residual = true;
-            for (int r = 0; r < (small ? 1 : 2); ++r) {
-                int l = B.add_layer(p + P(".0._seq.%d", r * 3), OP_CONV, C, C, 3, live, live, true);
-                int g = B.add_gn(p + P(".0._seq.%d", r * 3 + 1), C, live, live);
-                add_entries_for_layer(e, l); add_entries_for_gn(e, g);
-                b1.st.push_back(mk_stage(l, g, 1));
-            }
-            int l2 = B.add_layer(p + ".2", OP_CONV, C, 2 * e->dec[i + 1], 3, live, live, true);
-            add_entries_for_layer(e, l2);
-            b2.st.push_back(mk_stage(l2, -1, 0, true, true));
-        }
-    }
-    return 0;
-}
-
-// ---- arena layout ---------------------------------------------------------------------------
-static int layout_arenas(sgv_engine* e) {
-    size_t np = 0;
-    auto take = [&](size_t& cur, size_t n) { size_t o = cur; cur = align_up(cur + n, 4); return o; };
-    for (auto& l : e->layers) {
-        l.w = take(np, (size_t)l.nw());
-        l.b = take(np, l.cout);
-        l.u = take(np, l.cout);
-        l.v = take(np, (size_t)l.cin * l.k);
-    }
-    for (auto& g : e->gns) { g.gamma = take(np, g.C); g.beta = take(np, g.C); }
-    e->n_params = np;
-    return 0;
-}
-
-// order in which weight gradients become available during backward (for bucketed all-reduce)
-static void backward_layer_order(sgv_engine* e, std::vector<std::vector<int>>& sections) {
-    auto add_block = [&](std::vector<int>& v, const Block& b) {
-        for (int s = (int)b.st.size() - 1; s >= 0; --s) v.push_back(b.st[s].layer);
-    };
-    const int n = e->n, n_st = e->n_st;
-    std::vector<int> sec;
-    add_block(sec, e->recon);
-    sections.push_back(sec);
-    for (int i = n_st - 1; i >= 0; --i) {
-        sec.clear();
-        if (i < n_st - 1) {
-            add_block(sec, e->decQ2[i]); add_block(sec, e->decQ1[i]); add_block(sec, e->decX[i]);
-            sec.push_back(e->xs_exp[i]);
-            add_block(sec, e->decP2[i]); add_block(sec, e->decP1[i]);
-        }
-        add_block(sec, e->decD[i]); add_block(sec, e->decU[i]);
-        if (i == 0) { add_block(sec, e->decS); sec.push_back(e->start_lin); }
-        sections.push_back(sec);
-    }
-    sec.clear();
-    sec.push_back(e->last_lin);
-    for (int i = n - 1; i >= 1; --i) {
-        if (e->layers[e->xs_lin[i]].has_grad) sec.push_back(e->xs_lin[i]);
-        add_block(sec, e->encR[i]); add_block(sec, e->encA[i]);
-    }
-    add_block(sec, e->encR[0]);
-    sections.push_back(sec);
-    sec.clear();
-    add_block(sec, e->encA[0]);
-    sections.push_back(sec);
-}
-
-static int layout_grads(sgv_engine* e) {
-    std::vector<std::vector<int>> sections;
-    backward_layer_order(e, sections);
-    size_t ng = 0;
-    auto take = [&](size_t n) { size_t o = ng; ng = align_up(ng + n, 4); return o; };
-    e->buckets.clear();
-    std::vector<int> placed;          // sections that became buckets
-    for (size_t si = 0; si < sections.size(); ++si) {
-        size_t start = ng;
-        for (int li : sections[si]) {
-            Layer& l = e->layers[li];
-            if (!l.has_grad) continue;
-            l.gw = take((size_t)l.nw());
-        }
-        if (ng > start) { e->buckets.push_back({start, ng - start}); placed.push_back((int)si); }
-    }
-    e->n_grads_w = ng;
-    size_t small_start = ng;
-    // head of the small zone: the <G,W_eff> slots of the CONV layers, bucket by bucket (bucket_dots: final once the bucket's dY
-    // kernels are enqueued); then the Linear layers' slots (computed from G itself at the end of backward, they travel with the
-    // small bucket), biases and GroupNorm affine
-    e->bucket_dots.clear();
-    for (int si : placed) {
-        const size_t d0 = ng;
-        for (int li : sections[si]) { Layer& l = e->layers[li]; if (l.has_grad && l.op != OP_LINEAR && l.gdot == NPOS) l.gdot = take(SGV_DOT_SLOTS); }
-        e->bucket_dots.push_back({d0, ng - d0});
-    }
-    e->dots_total = ng - small_start;
-    for (auto& l : e->layers) if (l.has_grad) { if (l.gdot == NPOS) l.gdot = take(SGV_DOT_SLOTS); l.gb = take(l.cout); }
-    for (auto& g : e->gns) if (g.has_grad) { g.ggamma = take(g.C); g.gbeta = take(g.C); }
-    e->buckets.push_back({small_start, ng - small_start});
-    e->n_grads = ng;
-    // every trainable layer must have been placed
-    for (auto& l : e->layers) if (l.has_grad && l.gw == NPOS) return fail(SGV_ERR_STATE, "layer %s missing from backward order", l.prefix.c_str());
-    return 0;
-}
-
-// ---- activations ------------------------------------------------------------------------------
-static void alloc_block(sgv_engine* e, Block& b, long M, int cin, bool need_din) {
-    int c_in = cin;
-    for (size_t s = 0; s < b.st.size(); ++s) {
-        Stage& S = b.st[s];
-        const Layer& L = e->layers[S.layer];
-        if (S.pre_gelu) { S.pre = alloc_act(e, M, c_in); S.dpre = alloc_act(e, M, c_in); }
-        S.y = alloc_act(e, M, L.cout, S.out_f32);
-        if (S.gn >= 0 || S.act) { if (!S.a.p) S.a = alloc_act(e, M, L.cout); }
-        else S.a = S.y;
-        S.dy = (S.gn >= 0 || S.act) ? alloc_act(e, M, L.cout) : Tensor();
-        if (s + 1 < b.st.size()) S.da = alloc_act(e, M, L.cout);
-        if (S.gn >= 0) {
-            const GNLayer& g = e->gns[S.gn];
-            S.sums = e->n_stats_fwd; e->n_stats_fwd += (size_t)e->maxB * g.G * 2;
-        }
-        c_in = L.cout;
-    }
-    (void)need_din;
-}
-// Tensor.p holds arena offsets until rebase; mark "preset" views via a flag value
-static void rebase(sgv_engine* e, Tensor& t) { if (t.p || t.C) t.p = e->act + (size_t)t.p; }
-
-static int alloc_activations(sgv_engine* e) {
-    const long M = (long)e->maxB * e->T;
-    const int n = e->n, n_st = e->n_st;
-    e->act_used = 256;   // offset 0 is reserved so that "p == 0" means unallocated
-    e->x_bufs[0] = alloc_act(e, M, e->N);
-    e->x_bufs[1] = alloc_act(e, M, e->N);
-    e->xhat = alloc_act(e, M, e->N);
-    e->dy_recon = alloc_act(e, M, e->N);
-    e->enc_h.resize(n); e->d_h.resize(n);
-    for (int i = 0; i < n; ++i) {
-        alloc_block(e, e->encA[i], M, i == 0 ? e->N : e->enc[i - 1], i > 0);
-        alloc_block(e, e->encR[i], M, e->enc[i], true);
-        e->enc_h[i] = e->encR[i].st.back().a;
-        e->d_h[i] = alloc_act(e, M, e->enc[i]);
-    }
-    e->enc_a_dummy.resize(n);
-    for (int i = 0; i < n; ++i) e->enc_a_dummy[i] = alloc_act(e, M, e->enc[i]);   // d(a_i): grad wrt ConvBlock output
-    e->sbuf = alloc_act(e, M, e->Z);
-    e->d_sbuf = alloc_act(e, M, e->Z);
-    alloc_block(e, e->decS, M, e->Z, true);
-    e->zs.resize(n_st); e->dzs.resize(n_st); e->cat.resize(n_st); e->dcat.resize(n_st); e->dec_out.resize(n_st);
-    e->d_out.resize(n_st); e->d_u.resize(n_st); e->d_pres.resize(n_st); e->d_qres.resize(n_st); e->d_outp.resize(n_st);
-    e->gp.resize(n_st); e->gq.resize(n_st); e->xl.resize(n_st); e->d_xl.resize(n_st);
-    e->zs[0] = e->decS.st.back().a;
-    for (int i = 0; i < n_st; ++i) {
-        const int C = e->dec[i + 1];
-        const bool live = i < n_st - 1;
-        if (i > 0) e->zs[i] = alloc_act(e, M, e->dec[i]);
-        e->dzs[i] = alloc_act(e, M, e->dec[i]);
-        alloc_block(e, e->decU[i], M, e->dec[i], true);
-        if (live) {
-            e->cat[i] = alloc_act(e, M, 2 * C);
-            e->dcat[i] = alloc_act(e, M, 2 * C);
-            // DecoderResidualBlock output and xs_sequence output are written straight into the concat buffer
-            Tensor v = e->cat[i]; v.C = C; v.p = (void*)((size_t)v.p + (size_t)C * e->esz);
-            e->decD[i].st.back().a = v;
-            Tensor vx = e->cat[i]; vx.C = C;
-            e->decX[i].st.back().a = vx;
-        }
-        alloc_block(e, e->decD[i], M, C, true);
-        e->dec_out[i] = e->decD[i].st.back().a;
-        e->d_out[i] = alloc_act(e, M, C);
-        e->d_u[i] = alloc_act(e, M, C);
-        if (live) {
-            alloc_block(e, e->decP1[i], M, C, true);
-            alloc_block(e, e->decP2[i], M, C, true);
-            e->xl[i] = alloc_act(e, M, e->H);
-            e->d_xl[i] = alloc_act(e, M, e->H);
-            alloc_block(e, e->decX[i], M, e->H, true);
-            alloc_block(e, e->decQ1[i], M, 2 * C, true);
-            alloc_block(e, e->decQ2[i], M, 2 * C, true);
-            e->d_pres[i] = alloc_act(e, M, C);
-            e->d_qres[i] = alloc_act(e, M, 2 * C);
-            e->d_outp[i] = alloc_act(e, M, C);
-            e->gp[i] = alloc_act(e, M, 2 * C);
-            e->gq[i] = alloc_act(e, M, 2 * C);
-        }
-    }
-    alloc_block(e, e->recon, M, e->dec[n_st], true);
-    // fp32 side buffers
-    auto f32buf = [&](long count) { e->act_used = align_up(e->act_used, 256); size_t o = e->act_used; e->act_used += (size_t)count * 4; return (float*)o; };
-    e->xs_raw.resize(n); e->d_xs_raw.resize(n);
-    for (int i = 0; i < n; ++i) { e->xs_raw[i] = f32buf((long)e->maxB * e->H); e->d_xs_raw[i] = f32buf((long)e->maxB * e->H); }
-    e->last = f32buf((long)e->maxB * 2 * e->Z); e->d_last = f32buf((long)e->maxB * 2 * e->Z);
-    e->zlat = f32buf((long)e->maxB * e->Z); e->d_z = f32buf((long)e->maxB * e->Z);
-    e->eps.resize(n_st); e->zmap.resize(n_st); e->eps_set.assign(n_st, 0);
-    e->eps[0] = f32buf((long)e->maxB * e->Z);
-    e->zmap[0] = nullptr;
-    for (int i = 0; i + 1 < n_st; ++i) {
-        e->eps[i + 1] = f32buf(M * e->dec[i + 1]);
-        e->zmap[i] = f32buf(M * e->dec[i + 1]);
-    }
-    e->recon_unit = f32buf(3L * e->N);
-    // backward group sums mirror the forward slots
-    e->n_stats = e->n_stats_fwd * 2;
-    e->act_bytes = align_up(e->act_used, 256);
-    return 0;
-}
-
-static void rebase_block(sgv_engine* e, Block& b) {
-    for (auto& S : b.st) {
-        const bool alias = (S.gn < 0 && !S.act);
-        rebase(e, S.pre); rebase(e, S.dpre); rebase(e, S.y); rebase(e, S.dy); rebase(e, S.da);
-        if (alias) S.a = S.y; else rebase(e, S.a);
-        if (S.sums != NPOS) S.sums2 = S.sums + e->n_stats_fwd;
-    }
-}
-static void rebase_all(sgv_engine* e) {
-    auto R = [&](Tensor& t) { rebase(e, t); };
-    auto RF = [&](float*& p) { if (p) p = (float*)(e->act + (size_t)p); };
-    R(e->x_bufs[0]); R(e->x_bufs[1]); e->x_cur = 0; e->x_in = e->x_bufs[0];
-    R(e->xhat); R(e->dy_recon); R(e->sbuf); R(e->d_sbuf);
-    for (auto& b : e->encA) rebase_block(e, b);
-    for (auto& b : e->encR) rebase_block(e, b);
-    for (auto& b : e->decU) rebase_block(e, b);
-    for (auto& b : e->decD) rebase_block(e, b);
-    for (int i = 0; i + 1 < e->n_st; ++i) { rebase_block(e, e->decP1[i]); rebase_block(e, e->decP2[i]); rebase_block(e, e->decX[i]); rebase_block(e, e->decQ1[i]); rebase_block(e, e->decQ2[i]); }
-    rebase_block(e, e->decS); rebase_block(e, e->recon);
-    for (auto& t : e->d_h) R(t);
-    for (auto& t : e->enc_a_dummy) R(t);
-    for (int i = 0; i < e->n; ++i) e->enc_h[i] = e->encR[i].st.back().a;
-    for (int i = 0; i < e->n_st; ++i) {
-        if (i > 0) R(e->zs[i]);
-        R(e->dzs[i]); R(e->d_out[i]); R(e->d_u[i]);
-        if (i + 1 < e->n_st) { R(e->cat[i]); R(e->dcat[i]); R(e->xl[i]); R(e->d_xl[i]); R(e->d_pres[i]); R(e->d_qres[i]); R(e->d_outp[i]); R(e->gp[i]); R(e->gq[i]); }
-        e->dec_out[i] = e->decD[i].st.back().a;
-    }
-    e->zs[0] = e->decS.st.back().a;
-    for (auto& p : e->xs_raw) RF(p);
-    for (auto& p : e->d_xs_raw) RF(p);
-    RF(e->last); RF(e->d_last); RF(e->zlat); RF(e->d_z);
-    for (auto& p : e->eps) RF(p);
-    for (auto& p : e->zmap) RF(p);
-    RF(e->recon_unit);
-}
-
-// ---- descriptor tables --------------------------------------------------------------------------
-// conv weights that train go through the tiled AdamW (optim.hip adamw_sn_kernel), which also leaves W_new^T u
-// behind for the next forward's power iteration
-static bool layer_fused_adam(const Layer& l) { return l.used && l.has_grad && l.op != OP_LINEAR && l.cin % 4 == 0; }
-static int build_tables(sgv_engine* e) {
-    // compute copies
-    size_t nc = 0;
-    for (auto& l : e->layers) {
-        if (!l.used || l.op == OP_LINEAR) continue;
-        if (e->dt == SGV_DTYPE_BF16) { l.wc = nc; nc = align_up(nc + (size_t)l.nw(), 8); }
-        if (l.need_wct) { l.wct = nc; nc = align_up(nc + (size_t)l.nw(), 8); }
-    }
-    e->n_copies = nc;
-    // SN scratch
-    size_t nt = 0;
-    int si = 0;
-    for (auto& l : e->layers) { l.sn = si++; if (layer_fused_adam(l)) nt += align_up((size_t)l.cin * l.k, 4); }
-    e->n_sn_tmp_fused = nt;
-    for (auto& l : e->layers) if (!layer_fused_adam(l)) nt += align_up((size_t)l.cin * l.k, 4);
-    e->sn_tmp_s_off = nt;
-    for (auto& l : e->layers) nt += align_up((size_t)l.cout, 4);
-    e->sn_tpart_off.clear(); e->sn_spart_off.clear();
-    for (auto& l : e->layers) {
-        e->sn_tpart_off.push_back(nt);
-        nt += align_up(sn_tpart_floats(l.k, l.cout, l.cin), 4);
-        e->sn_spart_off.push_back(nt);
-        nt += align_up(sn_spart_floats(l.k, l.cout, l.cin), 4);
-    }
-    e->n_sn_tmp = nt;
-    return 0;
-}
-
-static int upload_tables(sgv_engine* e) {
-    const int L = (int)e->layers.size();
-    e->sn_host.resize(L);
-    size_t to_f = 0, to_u = e->n_sn_tmp_fused, to_s = e->sn_tmp_s_off;
-    std::vector<WorkItem> i_sn, i_sn_unf, i_dot, i_adam, i_adam_flat, i_adam_2d, i_copy, i_ts, i_ss;
-    e->fin_lin_dots.clear();
-    const int nbk = (int)e->buckets.size();
-    std::vector<std::vector<WorkItem>> flat_b(nbk), tile_b(nbk), dot_b(nbk);
-    std::vector<std::vector<FinDot>> fin_lin_b(nbk);
-    auto bucket_of = [&](size_t goff) {
-        for (int b = 0; b < nbk; ++b) if (goff >= e->buckets[b].first && goff < e->buckets[b].first + e->buckets[b].second) return b;
-        return nbk - 1;
-    };
-    for (int i = 0; i < L; ++i) {
-        Layer& l = e->layers[i];
-        SNDesc d;
-        d.W = e->params + l.w; d.u = e->params + l.u; d.v = e->params + l.v;
-        size_t& to_t = layer_fused_adam(l) ? to_f : to_u;
-        d.tmp_t = e->sn_tmp + to_t; to_t += align_up((size_t)l.cin * l.k, 4);
-        d.tmp_s = e->sn_tmp + to_s; to_s += align_up((size_t)l.cout, 4);
-        d.tpart = e->sn_tmp + e->sn_tpart_off[i]; d.spart = e->sn_tmp + e->sn_spart_off[i];
-        d.sigma = e->sn_sigma + 2 * i;
-        d.dot = l.has_grad ? e->grads + l.gdot : e->sn_dot_dummy;
-        d.G = l.has_grad ? e->grads + l.gw : nullptr;
-        d.wc = (e->dt == SGV_DTYPE_BF16 && l.wc != NPOS && l.cin % 8 == 0) ? (const void*)(e->copies + l.wc * e->esz) : nullptr;
-        d.taps = l.k; d.rows = l.cout; d.cols = l.cin; d.active = l.used ? 1 : 0;
-        e->sn_host[i] = d;
-        if (l.used) {
-            for (int c = 0; c < sn_gemv_items(l.k, l.cout, l.cin); ++c) { i_sn.push_back({i, c}); if (!layer_fused_adam(l)) i_sn_unf.push_back({i, c}); }
-            for (int c = 0; c < sn_tsum_items(l.k, l.cin); ++c) i_ts.push_back({i, c});
-            for (int c = 0; c < sn_ssum_items(l.cout); ++c) i_ss.push_back({i, c});
-        }
-        if (l.has_grad && l.op == OP_LINEAR) {   // conv layers get <G,W_eff> from their dY kernels (ew.hip)
-            const long nch = opt_flat_items(l.nw());
-            const int bk = bucket_of(l.gw);
-            fin_lin_b[bk].push_back({(const float*)(uintptr_t)dot_b[bk].size(), e->grads + l.gdot, (int)nch, 0});   // src = index inside the bucket for now, rebased below
-            for (long c = 0; c < nch; ++c) dot_b[bk].push_back({i, (int)c});
-        }
-    }
-    // Linear <G,W> items sorted by gradient bucket: a data-parallel backward computes a bucket's share before the bucket is
-    // released (the collective may reduce the bucket's gradients in place while backward goes on)
-    e->dot_off.assign(nbk + 1, 0); e->fin_lin_off.assign(nbk + 1, 0);
-    for (int b = 0; b < nbk; ++b) {
-        for (auto f : fin_lin_b[b]) { f.src = (const float*)((uintptr_t)f.src + i_dot.size()); e->fin_lin_dots.push_back(f); }
-        i_dot.insert(i_dot.end(), dot_b[b].begin(), dot_b[b].end());
-        e->dot_off[b + 1] = (int)i_dot.size(); e->fin_lin_off[b + 1] = (int)e->fin_lin_dots.size();
-    }
-    // the small bucket (which carries these scalars) is released before the last weight bucket: that one must hold no Linear layer
-    if (nbk >= 2 && e->dot_off[nbk] != e->dot_off[nbk - 2]) return fail(SGV_ERR_STATE, "a Linear layer sits in the last weight bucket");
-    e->adam_host.clear();
-    auto add_adam = [&](size_t p, size_t g, long n, int sn, int rows, int cols, int taps, void* wc, void* wct, bool tiled = false) {
-        AdamDesc a;
-        a.p = e->params + p; a.g = e->grads + g; a.m = e->adam_m + g; a.v = e->adam_v + g;
-        a.n = n; a.sn = sn; a.rows = rows; a.cols = cols; a.taps = taps; a.wc = wc; a.wct = wct;
-        a.glp = nullptr;                 // option grad_bf16 points it at the bf16 mirror arena
-        const int id = (int)e->adam_host.size();
-        e->adam_host.push_back(a);
-        const long nch = opt_flat_items(n);
-        const int bk = bucket_of(g);
-        for (long c = 0; c < nch; ++c) { i_adam.push_back({id, (int)c}); if (!tiled) flat_b[bk].push_back({id, (int)c}); }
-        if (tiled)
-            for (int c = 0; c < opt_tile_items(taps, rows, cols); ++c) tile_b[bk].push_back({id, c});
-        return id;
-    };
-    for (int i = 0; i < L; ++i) {
-        Layer& l = e->layers[i];
-        void* wc = l.wc != NPOS ? (void*)(e->copies + l.wc * e->esz) : nullptr;
-        void* wct = l.wct != NPOS ? (void*)(e->copies + l.wct * e->esz) : nullptr;
-        int id = -1;
-        if (l.has_grad) {
-            id = add_adam(l.w, l.gw, l.nw(), i, l.cout, l.cin, l.k, wc, wct, layer_fused_adam(l));
-            add_adam(l.b, l.gb, l.cout, -1, 1, l.cout, 1, nullptr, nullptr);
-        }
-        if (wc || wct) {
-            if (id < 0) {   // used-in-forward but frozen layers never occur for convs; keep general
-                AdamDesc a; memset(&a, 0, sizeof(a));
-                a.p = e->params + l.w; a.n = l.nw(); a.sn = -1; a.rows = l.cout; a.cols = l.cin; a.taps = l.k; a.wc = wc; a.wct = wct;
-                id = (int)e->adam_host.size();
-                e->adam_host.push_back(a);
-            }
-            for (int c = 0; c < opt_copy_items(l.k, l.cout, l.cin); ++c) i_copy.push_back({id, c});
-        }
-    }
-    for (auto& g : e->gns) {
-        if (!g.has_grad) continue;
-        add_adam(g.gamma, g.ggamma, g.C, -1, 1, g.C, 1, nullptr, nullptr);
-        add_adam(g.beta, g.gbeta, g.C, -1, 1, g.C, 1, nullptr, nullptr);
-    }
-    e->bucket_flat_w.assign(nbk, {});
-    for (auto& l : e->layers) if (l.has_grad && !layer_fused_adam(l)) e->bucket_flat_w[bucket_of(l.gw)].push_back({l.gw, (size_t)l.nw()});
-    e->flat_off.assign(nbk + 1, 0); e->tile_off.assign(nbk + 1, 0);
-    for (int b = 0; b < nbk; ++b) {
-        i_adam_flat.insert(i_adam_flat.end(), flat_b[b].begin(), flat_b[b].end());
-        i_adam_2d.insert(i_adam_2d.end(), tile_b[b].begin(), tile_b[b].end());
-        e->flat_off[b + 1] = (int)i_adam_flat.size(); e->tile_off[b + 1] = (int)i_adam_2d.size();
-    }
-    auto up = [&](const void* src, size_t bytes, void** dst) -> int {
-        if (bytes == 0) { *dst = nullptr; return 0; }
-        if (hipMalloc(dst, bytes) != hipSuccess) return -1;
-        if (hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
-        return 0;
-    };
-    if (up(e->sn_host.data(), sizeof(SNDesc) * L, (void**)&e->sn_dev)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(e->adam_host.data(), sizeof(AdamDesc) * e->adam_host.size(), (void**)&e->adam_dev)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_sn.data(), sizeof(WorkItem) * i_sn.size(), (void**)&e->items_sn)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_dot.data(), sizeof(WorkItem) * i_dot.size(), (void**)&e->items_dot)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_adam.data(), sizeof(WorkItem) * i_adam.size(), (void**)&e->items_adam)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_copy.data(), sizeof(WorkItem) * i_copy.size(), (void**)&e->items_copy)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_sn_unf.data(), sizeof(WorkItem) * i_sn_unf.size(), (void**)&e->items_sn_unf)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_adam_flat.data(), sizeof(WorkItem) * i_adam_flat.size(), (void**)&e->items_adam_flat)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_adam_2d.data(), sizeof(WorkItem) * i_adam_2d.size(), (void**)&e->items_adam_2d)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_ts.data(), sizeof(WorkItem) * i_ts.size(), (void**)&e->items_ts)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_ss.data(), sizeof(WorkItem) * i_ss.size(), (void**)&e->items_ss)) return fail(SGV_ERR_HIP, "table upload failed");
-    e->n_items_ts = (int)i_ts.size(); e->n_items_ss = (int)i_ss.size();
-    if (hipMalloc((void**)&e->lin_dot_part, sizeof(float) * std::max<size_t>(i_dot.size(), 1)) != hipSuccess) return fail(SGV_ERR_HIP, "hipMalloc failed");
-    for (auto& f : e->fin_lin_dots) f.src = e->lin_dot_part + (size_t)(uintptr_t)f.src;
-    e->n_gnorm_part = (int)std::max(i_adam_flat.size() + i_adam_2d.size(), i_adam.size());
-    if (hipMalloc((void**)&e->gnorm_part, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "hipMalloc failed");
-    if (hipMemset(e->gnorm_part, 0, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "memset failed");
-    e->n_items_sn_unf = (int)i_sn_unf.size(); e->n_items_adam_flat = (int)i_adam_flat.size(); e->n_items_adam_2d = (int)i_adam_2d.size();
-    e->n_items_sn = (int)i_sn.size(); e->n_items_dot = (int)i_dot.size();
-    e->n_items_adam = (int)i_adam.size(); e->n_items_copy = (int)i_copy.size();
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------------------
 // timing helpers
@@ -745,93 +180,6 @@ void sum_slabs(float* out, const float* partial, int splitk, long n, hipStream_t
     int blocks = (int)((n / 4 + 255) / 256); if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sum_slabs_kernel, dim3(blocks), dim3(256), 0, stream, out, partial, splitk, n);
 }
-static hipEvent_t next_event(sgv_engine* e) {
-    if (e->ev_next == e->ev_pool.size()) {
-        hipEvent_t ev = nullptr;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr;
-        e->ev_pool.push_back(ev);
-    }
-    return e->ev_pool[e->ev_next++];
-}
-// `waiter` waits for everything enqueued on `of` so far
-int stream_wait(sgv_engine* e, hipStream_t waiter, hipStream_t of) {
-    hipEvent_t ev = next_event(e);
-    if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
-    HIPCHK(hipEventRecord(ev, of));
-    HIPCHK(hipStreamWaitEvent(waiter, ev, 0));
-    return 0;
-}
-// make the main stream wait for every weight-gradient GEMM issued so far on the side stream
-int join_side(sgv_engine* e) {
-    if (!e->side_dirty) return 0;
-    CHK(stream_wait(e, e->stream, e->side));
-    e->side_dirty = false;
-    return 0;
-}
-// ---- bf16 weight gradients straight from the 256 x 256 kernel (see the grad_bf16 member) ----
-// which layers: those whose weight-gradient GEMM takes that kernel, unsplit, at the engine's full batch, and whose mirror range the
-// launcher accepts as its bf16 output (alignment, offset ranges: a refused launch must never be left to write the mirror) -- fixed
-// once: the AdamW table points the layer at the mirror arena
-static void classify_lp(sgv_engine* e) {
-    if (e->lp_classified) return;
-    const long M = (long)e->maxB * e->T;
-    for (auto& l : e->layers) {
-        l.lp = false;
-        if (!(l.used && l.has_grad && l.op != OP_LINEAR && l.cin % 4 == 0) || e->dt != SGV_DTYPE_BF16 || !e->use_tr) continue;
-        GemmTN q; memset(&q, 0, sizeof(q));
-        q.M = (int)M; q.N1 = l.cout; q.N2 = l.cin; q.taps = l.k; q.pad = (l.k - 1) / 2; q.Tlen = e->T; q.lda = l.cout; q.ldb = l.cin; q.ldo = l.cin; q.use_tr = 1; q.splitk = 1;
-        q.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw); q.out_bf16 = 1;
-        l.lp = gemm_tn_uses_t256(e->dt, q) && gemm_tn256_accepts(q) && gemm_tn_pick_splitk(q.M, q.N1, q.N2, q.taps, e->dt, e->T) == 1;
-    }
-    e->bucket_lp_layers.assign(e->buckets.size(), {});
-    for (size_t b = 0; b + 1 < e->buckets.size(); ++b) {
-        std::vector<std::pair<size_t, int>> v;
-        for (size_t i = 0; i < e->layers.size(); ++i) {
-            const Layer& l = e->layers[i];
-            if (l.lp && l.gw >= e->buckets[b].first && l.gw < e->buckets[b].first + e->buckets[b].second) v.push_back({l.gw, (int)i});
-        }
-        std::sort(v.begin(), v.end());
-        for (auto& x : v) e->bucket_lp_layers[b].push_back(x.second);
-    }
-    e->lp_classified = true;
-}
-static int ensure_lp_mirror(sgv_engine* e) {
-    if (!e->grads_lp) HIPCHK(hipMalloc(&e->grads_lp, e->n_grads * 2));
-    classify_lp(e);
-    return 0;
-}
-// single-GPU option: no communicator, no bucket callback
-static inline bool grad_lp_active(const sgv_engine* e) { return e->grad_bf16 && e->grads_lp && !e->comm && !e->cb; }
-// data-parallel step with the bf16 wire format (the condition under which fire_at packs a bucket)
-static inline bool wire_lp_active(sgv_engine* e) {
-    const char* off = getenv("SGV_WIRE_DIRECT");           // read per call: a test compares both forms in one process
-    if (off && atoi(off) == 0) return false;
-    return e->payload_bf16 && e->grads_lp && e->lp_classified && (e->comm ? !comm_is_single(e->comm) : e->cb != nullptr);
-}
-// the fp32 arena of the layers whose last gradient was stored as bf16: refreshed for the calls that read it.  (After a
-// data-parallel step the mirror holds the averaged gradient of those layers.)
-static int lp_sync(sgv_engine* e) {
-    for (size_t i = 0; i < e->layers.size(); ++i) {
-        if (!e->lp_dirty[i]) continue;
-        const Layer& l = e->layers[i];
-        ew_unpack_bf16((const char*)e->grads_lp + 2 * l.gw, e->grads + l.gw, l.nw(), e->stream);
-        e->lp_dirty[i] = 0;
-    }
-    return 0;
-}
-// a bucket's fp32 gradients -> the bf16 wire copy, except the layers whose GEMM wrote the copy itself
-static void pack_bucket(sgv_engine* e, int b, hipStream_t st) {
-    size_t cur = e->buckets[b].first;
-    const size_t end = cur + e->buckets[b].second;
-    if (e->lp_classified && b < (int)e->bucket_lp_layers.size())
-        for (int li : e->bucket_lp_layers[b]) {
-            const Layer& l = e->layers[li];
-            if (!e->lp_dirty[li]) continue;
-            if (l.gw > cur) ew_pack_bf16(e->grads + cur, (char*)e->grads_lp + 2 * cur, (long)(l.gw - cur), st);
-            cur = l.gw + align_up((size_t)l.nw(), 4);
-        }
-    if (end > cur) ew_pack_bf16(e->grads + cur, (char*)e->grads_lp + 2 * cur, (long)(end - cur), st);
-}
 // dW[tap][co][ci] = sum_m dY[m][co] X[m+tap-pad][ci]
 static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Tensor& x, long M) {
     GemmTN p; memset(&p, 0, sizeof(p));
@@ -868,7 +216,7 @@ static int conv_bwd_dw(sgv_engine* e, const Layer& l, const Tensor& dy, const Te
             if (direct) { q.out = reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(e->grads_lp) + l.gw + (size_t)c * rows * l.cin); q.out_bf16 = 1; }
             if (e->coll_inflight && e->tn_sched) q.sched = e->tn_sched + 520 * (e->tn_sched_next++ & 7);
             if (launch_gemm_tn(e->dt, q, st)) return fail(SGV_ERR_ARG, "gemm_tn launch failed for %s (rows %d..%d)", l.prefix.c_str(), c * rows, (c + 1) * rows);
-            if (e->dw_chunk_hook && e->dw_chunk_hook(c, e->dw_chunks, c * rows, (c + 1) * rows)) return fail(SGV_ERR_HIP, "weight-gradient chunk exchange failed for %s", l.prefix.c_str());
+            if (e->release && e->release->after_chunk(c, e->dw_chunks, c * rows, (c + 1) * rows)) return fail(SGV_ERR_HIP, "weight-gradient chunk exchange failed for %s", l.prefix.c_str());
         }
         return 0;
     }
@@ -976,7 +324,7 @@ static int block_fwd(sgv_engine* e, Block& b, const Tensor& in, int B) {
 }
 
 // dOut: gradient wrt the block output; dIn (nullable): gradient wrt the block input (overwritten).
-// before_first_dw (optional) runs after the last dY of the block exists, right before the weight-gradient GEMM of
+// before_first_dw (optional): its release_small() runs after the last dY of the block exists, right before the weight-gradient GEMM of
 // the block's first conv (sgv_backward uses it to release the small-gradient bucket early).
 // Input gradient of convolution L (its dY given) + GroupNorm / GELU backward of stage P below it in one launch (convgn.hip);
 // `addend` (residual path) is added to the input gradient before it is rounded; `premul` = x when L reads GELU(x) (the gradient
@@ -1013,7 +361,7 @@ static int fused_dx_gn_bwd(sgv_engine* e, const Layer& L, const Tensor& dY, cons
 // can take (this block's first convolution, that stage) together, it writes dIn AND that stage's dY, *below_done is set and the
 // caller passes last_dy_ready = true to that block's block_bwd (below_rscale: that block's residual scale).
 static int block_bwd(sgv_engine* e, Block& b, const Tensor& in, const Tensor& dOut, const Tensor* dIn, int B,
-                     const std::function<void()>* before_first_dw = nullptr, Stage* below = nullptr, bool* below_done = nullptr,
+                     GradRelease* before_first_dw = nullptr, Stage* below = nullptr, bool* below_done = nullptr,
                      bool last_dy_ready = false, float below_rscale = 1.f) {
     const long M = (long)B * e->T;
     Tensor dA = dOut;
@@ -1026,7 +374,7 @@ static int block_bwd(sgv_engine* e, Block& b, const Tensor& in, const Tensor& dO
         const Tensor x_conv = S.pre_gelu ? S.pre : x_raw;
         Tensor dY;
         // <G,W_eff> and the GroupNorm affine / bias gradients leave these kernels as block / per-sample partials in e->red; the
-        // fixed-order sums run once per bucket (flush_fin in backward_impl)
+        // fixed-order sums run once per bucket (GradRelease::flush_fin)
         int* cnt = &e->dot_counts[e->fin_dots.size() % 512];
         if (e->recompute_act && S.gn >= 0 && !S.y.f32) {
             // regenerate this stage's output map exactly as block_fwd's unfused path writes it (the fused forward kernel normalises the
@@ -1079,7 +427,7 @@ static int block_bwd(sgv_engine* e, Block& b, const Tensor& in, const Tensor& dO
             dY = dA;
         }
         sc = 1.0f;
-        if (s == 0 && before_first_dw) (*before_first_dw)();
+        if (s == 0 && before_first_dw) before_first_dw->release_small();
         CHK(conv_bwd_dw(e, L, dY, x_conv, M));
         const bool need = (s > 0) || (dIn != nullptr);
         if (need && (s > 0 ? !S.pre_gelu : (below && below_done))) {
@@ -1111,6 +459,16 @@ static int block_bwd(sgv_engine* e, Block& b, const Tensor& in, const Tensor& dO
     return 0;
 }
 
+// the environment's switches (A/B runs and tests), read once per engine, in front of everything sgv_create builds
+static void env_switches(sgv_engine* e) {
+    if (const char* v = getenv("SGV_DDP_EARLY")) e->ddp_early = atoi(v);
+    if (const char* v = getenv("SGV_DDP_LAST_CHUNKS")) e->ddp_last_chunks = atoi(v);
+    if (const char* v = getenv("SGV_DDP_CHUNK_MIN_GF")) e->ddp_chunk_min_gf = atof(v);
+    if (const char* v = getenv("SGV_LANES")) e->use_lanes = atoi(v);
+    if (const char* v = getenv("SGV_CONVGN")) e->use_convgn = atoi(v);
+    if (const char* v = getenv("SGV_DW_SIDE")) e->use_side = atoi(v) != 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
@@ -1131,6 +489,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     if (cfg->max_batch < 1 || cfg->num_time < 1) return fail(SGV_ERR_ARG, "bad batch/time");
     if (cfg->loss_type < 0 || cfg->loss_type > 3) return fail(SGV_ERR_ARG, "bad loss_type");
     sgv_engine* e = new sgv_engine();
+    env_switches(e);
     e->cfg = *cfg;
     e->stream = (hipStream_t)hip_stream;
     e->dt = cfg->compute_dtype; e->esz = e->dt == SGV_DTYPE_BF16 ? 2 : 4;
@@ -1140,7 +499,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     for (int i = 0; i < e->n; ++i) e->enc.push_back(cfg->num_filter_enc[i]);
     e->dec.assign(e->enc.rbegin(), e->enc.rend());
     int r;
-    if ((r = build_graph(e)) || (r = layout_arenas(e)) || (r = layout_grads(e)) || (r = alloc_activations(e)) || (r = build_tables(e))) { delete e; return r; }
+    if ((r = build_layout(e))) { delete e; return r; }
     // workspace for split-K slabs: enough for the largest split GEMM
     const long M = (long)e->maxB * e->T;
     size_t pf = 0, pf_tn = 0;
@@ -1202,16 +561,15 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
         e->red_floats = nr;
     }
     ALLOC(e->red, e->red_floats * 4);
-    if (make_aux_stream(&e->side, "side", {e->stream, e->lane2}) != hipSuccess) { e->side = nullptr; e->use_side = false; }
+    if (make_aux_stream(&e->side, "side", {e->stream, e->lane2}) != hipSuccess) e->side = nullptr;
+    e->use_side = e->use_side && e->side != nullptr;          // SGV_DW_SIDE applies once the side stream exists
     // the optimizer and wire streams of the data-parallel step are created on first use (ensure_opt / ensure_wire): every stream a
     // process creates shifts the runtime's stream -> hardware-queue assignment of the ones created after it
-    if (getenv("SGV_DW_SIDE")) e->use_side = atoi(getenv("SGV_DW_SIDE")) != 0 && e->side != nullptr;
     ALLOC(e->xpose_tmp, e->xpose_floats * 4);
     ALLOC(e->colpart, e->colpart_floats * 4);
     if (e->use_lanes) ALLOC(e->colpart2, e->colpart_floats * 4);
 #undef ALLOC
-    rebase_all(e);
-    if ((r = upload_tables(e))) { sgv_destroy(e); return r; }
+    if ((r = build_bind(e))) { sgv_destroy(e); return r; }
     if (hipStreamSynchronize(e->stream) != hipSuccess) { sgv_destroy(e); return fail(SGV_ERR_HIP, "stream sync failed in create"); }
     *out = e;
     return SGV_OK;
@@ -1497,24 +855,7 @@ int sgv_set_option(sgv_engine* e, const char* key, int value) {
     else if (!strcmp(key, "vendor_gemm")) { if (value) return fail(SGV_ERR_ARG, "vendor_gemm: the library GEMM back end was removed from libsgvae.so (comparator: tests/micro/vendor)"); }
     else if (!strcmp(key, "deterministic")) e->deterministic = value != 0;
     else if (!strcmp(key, "lanes")) e->use_lanes = value != 0 && e->lane2 != nullptr;          // second compute lane (schedule only: results are bitwise the same)
-    else if (!strcmp(key, "grad_bf16")) {                                                           // see the member
-        if (value && (e->dt != SGV_DTYPE_BF16)) return fail(SGV_ERR_ARG, "grad_bf16 needs a bf16 engine");
-        CHK(lp_sync(e));
-        if (value) {
-            CHK(ensure_lp_mirror(e));
-            // point the optimizer's table at the mirror for the classified layers (the kernel follows the pointer only when the launch
-            // says so: adamw_tiles)
-            bool changed = false;
-            for (auto& a : e->adam_host) {
-                if (a.sn < 0 || a.sn >= (int)e->layers.size()) continue;
-                const Layer& l = e->layers[a.sn];
-                if (!l.lp || a.g != e->grads + l.gw || a.glp) continue;
-                a.glp = reinterpret_cast<const unsigned short*>(e->grads_lp) + l.gw; changed = true;
-            }
-            if (changed) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipMemcpy(e->adam_dev, e->adam_host.data(), sizeof(AdamDesc) * e->adam_host.size(), hipMemcpyHostToDevice)); }
-        }
-        e->grad_bf16 = value != 0;
-    }
+    else if (!strcmp(key, "grad_bf16")) CHK(set_grad_bf16(e, value));                            // see the member
     else if (!strcmp(key, "recompute_activations")) e->recompute_act = value != 0;               // measurement only, see block_bwd
     else if (!strcmp(key, "fused_stages")) e->use_convgn = value != 0;                          // csrc/convgn.hip kernels for the small Conv -> GroupNorm -> GELU stages
     else return fail(SGV_ERR_ARG, "unknown option '%s'", key);
@@ -1769,129 +1110,21 @@ int sgv_get_activation(sgv_engine* e, const char* name, float* host, size_t coun
     return fail(SGV_ERR_NAME, "unknown activation '%s'", name);
 }
 
-int sgv_grad_buffer(sgv_engine* e, float** dev_ptr, size_t* count_elems) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    // grad_bf16: the caller may read or write the arena from here on -- it gets the gradients of the last backward, and what it
-    // leaves there is what the next AdamW reads (the refresh is finished before the pointer is handed out)
-    if (std::find(e->lp_dirty.begin(), e->lp_dirty.end(), 1) != e->lp_dirty.end()) {
-        CHK(lp_sync(e));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    e->lp_fp32 = true;
-    if (dev_ptr) *dev_ptr = e->grads;
-    if (count_elems) *count_elems = e->n_grads;
-    return SGV_OK;
-}
-int sgv_scale_grads(sgv_engine* e, float factor) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    CHK(lp_sync(e));                     // grad_bf16: the gradient of the mirrored layers into the fp32 arena, scaled there with the rest
-    e->lp_fp32 = true;
-    ew_scale(e->grads, factor, (long)e->n_grads, e->stream);
-    return SGV_OK;
-}
-
-static int adamw_begin(sgv_engine* e);
-static int adamw_finish(sgv_engine* e);
-static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, int which, hipStream_t st);
-static int adamw_bucket_async(sgv_engine* e, float lr, int b, hipStream_t st);
-static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, bool from_lp);
-int sgv_adamw_step(sgv_engine* e, float lr);
-// fuse_lr >= 0: also run the optimizer, and start the AdamW of every conv-weight bucket on the side stream as soon as
-// that bucket's gradients are final, under the rest of backward (single-GPU path: no bucket callback registered)
+// The backward traversal of the model: recon head, decoder stages, latent, encoder.  When a gradient bucket is complete and what
+// happens to it then (transport, wire format, where its AdamW runs; fuse_lr >= 0: the optimizer step too) is GradRelease's
+// business (engine_optim.hip): the traversal only says where a bucket's last gradient has been enqueued.
 static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
     if (!e->have_fwd || !e->fwd_train) return fail(SGV_ERR_STATE, "sgv_backward needs a preceding sgv_forward(train=1)");
     e->lp_fp32 = false;                  // grad_bf16: this backward's gradients of the mirrored layers go to the mirror again
-    const bool fuse = fuse_lr >= 0.f;
-    const bool early = fuse && !e->cb && !e->comm && e->side && e->use_side && !e->timing;
-    // engine-issued collectives with the learning rate in hand (sgv_backward_step on a registered communicator): every weight
-    // bucket's <G,W> slots are averaged with the bucket and its conv-weight AdamW starts on the optimizer stream as soon as both
-    // have landed, under the rest of backward -- the data-parallel mirror of `early`
-    const bool dearly = e->ddp_early && fuse && e->comm && !comm_is_single(e->comm) && !e->timing && ensure_opt(e);
-    if (early || dearly) CHK(adamw_begin(e));
-    // chunked exchange of the last weight bucket: it must be exactly the first encoder layer's tiled weight
-    const int last_b = (int)e->buckets.size() - 2;
-    const int L0i = e->encA[0].st[0].layer;
-    bool last_chunked = false;
-    std::vector<hipEvent_t> chunk_done;
-    if (dearly && e->ddp_last_chunks > 1 && last_b >= 0) {
-        const Layer& L0 = e->layers[L0i];
-        const int rt6 = (L0.cout + 63) / 64, ct6 = (L0.cin + 63) / 64;
-        last_chunked = e->encA[0].st.size() == 1 && L0.k == 1 && L0.has_grad && layer_fused_adam(L0) && L0.cout % (128 * e->ddp_last_chunks) == 0 &&
-                       e->buckets[last_b].first == L0.gw && e->buckets[last_b].second == align_up((size_t)L0.nw(), 4) &&
-                       e->tile_off[last_b + 1] - e->tile_off[last_b] == rt6 * ct6 && e->flat_off[last_b + 1] == e->flat_off[last_b] &&
-                       2.0e-9 * (double)((long)e->batch * e->T) * L0.cout * L0.cin > e->ddp_chunk_min_gf;      // the big-GEMM regime: main stream, split-K 1
-    }
+    GradRelease rel(e, fuse_lr);
+    CHK(rel.begin());
     const int B = e->batch, n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
     const float coefB = beta / (float)B;
-    int bucket = 0;
     e->ev_next = 0;
     e->recompute_bytes = 0;
-    int early_err = 0;
-    // the inputs of a bucket's collective are what the main stream and the side stream hold so far.  They are gathered on the
-    // stream the collective is issued from (the communicator's stream; with a callback the wire stream, option "wire_stream"), and
-    // the bf16 wire copy is packed THERE: the main stream neither waits for the side stream's weight-gradient GEMMs nor runs the
-    // pack pass (0.45 ms per step at preset 1).  Without a wire stream (a caller that orders itself after the engine stream) the
-    // main stream joins the side stream and packs, as before.
-    auto gather_on = [&](hipStream_t t) -> int {
-        hipEvent_t ev = next_event(e);
-        if (!ev || hipEventRecord(ev, e->stream) != hipSuccess || hipStreamWaitEvent(t, ev, 0) != hipSuccess) return 1;
-        if (e->side_dirty) {
-            hipEvent_t ev2 = next_event(e);
-            if (!ev2 || hipEventRecord(ev2, e->side) != hipSuccess || hipStreamWaitEvent(t, ev2, 0) != hipSuccess) return 1;
-        }
-        return 0;
-    };
-    auto fire_at = [&](int b) {
-        if (b < 0 || b >= (int)e->buckets.size()) return;
-        if (e->cb || (e->comm && !comm_is_single(e->comm))) e->coll_inflight = true;
-        if (e->comm || e->cb) {
-            const hipStream_t ws = e->comm ? e->comm_stream : (e->use_wire ? e->wire : nullptr);
-            if (ws ? gather_on(ws) : join_side(e)) { early_err = 1; return; }
-            if (e->payload_bf16 && b != (int)e->buckets.size() - 1 && !(e->comm && comm_is_single(e->comm))) {
-                pack_bucket(e, b, ws ? ws : e->stream);
-                e->bucket_packed[b] = 3;
-            }
-        }
-        if (e->comm) {
-            if (rccl_bucket(e, e->comm, e->comm_stream, b, e->bucket_done[b], dearly)) { early_err = 1; return; }
-            e->bucket_pending[b] = 1;
-            if (dearly && b < (int)e->buckets.size() - 2) {
-                if (hipStreamWaitEvent(e->opt, e->bucket_done[b], 0) != hipSuccess) { early_err = 1; return; }
-                e->bucket_pending[b] = 0;
-                if (adamw_bucket_async(e, fuse_lr, b, e->opt)) early_err = 1;
-            }
-        } else if (e->cb) {
-            e->cb(e->cb_user, b, e->buckets[b].first, e->buckets[b].second);
-        } else if (early && b < (int)e->buckets.size() - 2) {
-            // the bucket's weight gradients (and the <G,W> slots of its conv layers) are final once everything enqueued
-            // so far has run: AdamW of its conv weights goes to the side stream, under the remaining backward
-            hipEvent_t ev = next_event(e);
-            if (!ev || hipEventRecord(ev, e->stream) != hipSuccess || hipStreamWaitEvent(e->side, ev, 0) != hipSuccess) { early_err = 1; return; }
-            if (adamw_range(e, fuse_lr, b, b + 1, 1, e->side)) early_err = 1;
-            e->side_dirty = true;
-        }
-    };
-    // fixed-order sums of the partials collected so far: the <G,W_eff> scalars of the layers whose dY kernels have been enqueued
-    // (every fire point: the bucket's AdamW / all-reduce reads them), the GroupNorm affine and bias gradients (small bucket)
-    auto flush_fin = [&](bool affine) {
-        if (!e->fin_dots.empty()) { ew_fin_dots(e->fin_dots.data(), (int)e->fin_dots.size(), e->stream); e->fin_dots.clear(); }
-        if (affine && !e->fin_affine.empty()) { ew_fin_affine(e->fin_affine.data(), (int)e->fin_affine.size(), e->stream); e->fin_affine.clear(); }
-    };
     e->fin_dots.clear(); e->fin_affine.clear();
-    // <G,W_eff> of the Linear layers is computed from G itself: in one launch at the end of backward -- unless a collective may
-    // already be reducing a released bucket's gradients in place by then (fp32 wire format): with a callback or a communicator
-    // every bucket's Linear layers get theirs at the bucket's fire point.  Same per-item partials, same fixed-order sums.
-    const bool dots_per_bucket = e->cb || e->comm;
-    int lin_err = 0;
-    auto lin_dots = [&](int b0, int b1) {
-        const int d0 = e->dot_off[b0], d1 = e->dot_off[b1];
-        if (d1 > d0 && opt_sn_grad_dot(e->sn_dev, e->items_dot + d0, d1 - d0, e->lin_dot_part + d0, e->stream)) lin_err = 1;
-        e->fin_dots.insert(e->fin_dots.end(), e->fin_lin_dots.begin() + e->fin_lin_off[b0], e->fin_lin_dots.begin() + e->fin_lin_off[b1]);
-    };
-    auto fire = [&]() { if (dots_per_bucket) lin_dots(bucket, bucket + 1); flush_fin(false); fire_at(bucket); ++bucket; };
-    const int small_bucket = (int)e->buckets.size() - 1;
     // no zero-fills: every gradient of the small zone (biases, GroupNorm affine, <G,W_eff> slot 0) and every backward group sum
     // is written, not accumulated, by its fixed-order reduction; tensors that get no gradient stay at their initial zero
     // ---- recon head ----
@@ -1911,7 +1144,7 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
         ew_scale3(e->grads + g.ggamma, e->grads + g.gbeta, e->grads + L.gb, e->recon_unit, gs, e->N, e->stream);
         CHK(conv_bwd_dw(e, L, e->dy_recon, e->dec_out[n_st - 1], M));
         CHK(conv_bwd_dx(e, L, e->dy_recon, e->d_out[n_st - 1], nullptr, M));
-        fire();
+        rel.fire();
     }
     // ---- decoder stages ----
     for (int i = n_st - 1; i >= 0; --i) {
@@ -1921,15 +1154,6 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
                          e->gp[i].p, e->gq[i].p, (int)M, C, coefB, e->stream);
             Tensor d_xs = e->dcat[i]; d_xs.C = C;
             Tensor d_oq = e->dcat[i]; d_oq.C = C; d_oq.p = (char*)d_oq.p + (size_t)C * e->esz;
-            auto xs_lift_bwd = [&]() -> int {
-                const int r = block_bwd(e, e->decX[i], e->xl[i], d_xs, &e->d_xl[i], B);
-                if (r) return r;
-                const Layer& l = e->layers[e->xs_exp[i]];
-                const int lvl = n - 2 - i;
-                ew_linear_expand_bwd(e->dt, e->d_xl[i].p, e->xs_raw[lvl], e->params + l.w, e->sn_sigma + 2 * l.sn + 1, e->d_xs_raw[lvl],
-                                     e->grads + l.gw, e->grads + l.gb, B, l.cin, l.cout, e->stream);
-                return 0;
-            };
             {   // posterior branch on the second lane, beside the prior branch below (they meet in the add3 after the join)
                 Lane2 lane(e);
                 bool q_ready = false;      // condition_xz: the output convolution's input gradient went straight into the residual block's GroupNorm backward
@@ -1945,7 +1169,11 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
                 // the xs lift's backward needs d_xs only: deferred onto the lane beside the residual / up-sampling blocks' backward
                 // below (the mirror of the forward hoist); joined before the stage's bucket is released
                 Lane2 lane(e);
-                CHK(xs_lift_bwd());
+                CHK(block_bwd(e, e->decX[i], e->xl[i], d_xs, &e->d_xl[i], B));
+                const Layer& l = e->layers[e->xs_exp[i]];
+                const int lvl = n - 2 - i;
+                ew_linear_expand_bwd(e->dt, e->d_xl[i].p, e->xs_raw[lvl], e->params + l.w, e->sn_sigma + 2 * l.sn + 1, e->d_xs_raw[lvl],
+                                     e->grads + l.gw, e->grads + l.gb, B, l.cin, l.cout, e->stream);
             }
         }
         CHK(block_bwd(e, e->decD[i], e->decU[i].st.back().a, e->d_out[i], &e->d_u[i], B));
@@ -1957,7 +1185,7 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
             ew_linear_expand_bwd(e->dt, e->d_sbuf.p, e->zlat, e->params + l.w, e->sn_sigma + 2 * l.sn + 1, e->d_z, e->grads + l.gw, e->grads + l.gb,
                                  B, l.cin, l.cout, e->stream);
         }
-        fire();
+        rel.fire();
     }
     // ---- latent + encoder ----
     ew_latent_bwd(e->last, e->eps[0], e->d_z, e->d_last, B, e->Z, coefB, e->stream);
@@ -1976,75 +1204,14 @@ static int backward_impl(sgv_engine* e, float alpha, float beta, float fuse_lr) 
         CHK(block_bwd(e, e->encR[i], e->encA[i].st.back().a, e->d_h[i], &e->enc_a_dummy[i], B, nullptr, &e->encA[i].st.back(), &a_ready));
         const Tensor x_prev = i == 0 ? e->x_in : e->enc_h[i - 1];
         if (i == 0) {
-            fire();   // everything but the first block's weight gradients is now enqueued
-            // <G,W_eff> of the (small) Linear layers from their weights; conv layers accumulated theirs in the dY kernels
-            if (!dots_per_bucket) lin_dots(0, (int)e->buckets.size());
-            if (lin_err) return fail(SGV_ERR_HIP, "grad-dot launch failed");
-            // the small zone (biases, GroupNorm affine, <G,W_eff> scalars) is complete once the first conv's dY exists:
-            // release it BEFORE the first-layer weight-gradient GEMM so that its all-reduce (and, with it, the AdamW
-            // of every other layer) does not queue behind the 390 MB first-layer bucket
-            const std::function<void()> early = [&]() { flush_fin(true); fire_at(small_bucket); };
-            if (last_chunked) {
-                e->dw_chunks = e->ddp_last_chunks; e->dw_chunk_layer = L0i;
-                e->dw_chunk_hook = [&](int c, int n_c, int co0, int co1) -> int {
-                    const Layer& L0 = e->layers[L0i];
-                    const size_t off = L0.gw + (size_t)co0 * L0.cin, cnt = (size_t)(co1 - co0) * L0.cin;
-                    const hipStream_t cs = e->comm_stream;
-                    if (gather_on(cs)) return 1;                                  // the chunk's GEMM (main stream)
-                    const bool lp = e->payload_bf16 != 0;
-                    void* w = lp ? (void*)((char*)e->grads_lp + 2 * off) : (void*)(e->grads + off);
-                    if (lp && !e->dw_chunk_direct) ew_pack_bf16(e->grads + off, w, (long)cnt, cs);
-                    if (g_rccl.AllReduce(w, w, cnt, lp ? kNcclBfloat16 : kNcclFloat32, kNcclAvg, e->comm, cs)) return 1;
-                    if (c == 0 && e->bucket_dots[last_b].second) {
-                        float* d = e->grads + e->bucket_dots[last_b].first;
-                        if (g_rccl.AllReduce(d, d, e->bucket_dots[last_b].second, kNcclFloat32, kNcclAvg, e->comm, cs)) return 1;
-                    }
-                    hipEvent_t ev = c == n_c - 1 ? e->bucket_done[last_b] : next_event(e);
-                    if (!ev || hipEventRecord(ev, cs) != hipSuccess) return 1;
-                    chunk_done.push_back(ev);
-                    return 0;
-                };
-            }
-            const int br = block_bwd(e, e->encA[0], x_prev, e->enc_a_dummy[0], nullptr, B, &early, nullptr, nullptr, a_ready);
-            e->dw_chunks = 1; e->dw_chunk_layer = -1; e->dw_chunk_hook = nullptr;
-            CHK(br);
-            if (last_chunked && (int)chunk_done.size() == e->ddp_last_chunks) {
-                // the chunks' updates go to the MAIN stream, behind the last GEMM chunk: it has nothing else left to do, and chunk c's
-                // AdamW then runs beside chunk c + 1's exchange instead of in front of it on the communication stream's queue
-                const Layer& L0 = e->layers[L0i];
-                const int n_c = e->ddp_last_chunks, rows = L0.cout / n_c, ct6 = (L0.cin + 63) / 64;
-                const bool lp = e->payload_bf16 != 0;
-                for (int c = 0; c < n_c; ++c) {
-                    const size_t off = L0.gw + (size_t)c * rows * L0.cin, cnt = (size_t)rows * L0.cin;
-                    HIPCHK(hipStreamWaitEvent(e->stream, chunk_done[c], 0));
-                    CHK(adamw_tiles(e, fuse_lr, e->tile_off[last_b] + (c * rows / 64) * ct6, e->tile_off[last_b] + ((c + 1) * rows / 64) * ct6, e->stream, lp));
-                }
-                e->bucket_updated[last_b] = 1;
-            }
+            // the small bucket is released from inside the block, in front of its first layer's weight-gradient GEMM (release_small)
+            CHK(rel.before_first_block());
+            CHK(rel.after_first_block(block_bwd(e, e->encA[0], x_prev, e->enc_a_dummy[0], nullptr, B, &rel, nullptr, nullptr, a_ready)));
         } else {
             CHK(block_bwd(e, e->encA[i], x_prev, e->enc_a_dummy[i], &e->d_h[i - 1], B, nullptr, nullptr, nullptr, a_ready));
         }
     }
-    if (last_chunked && e->bucket_updated[last_b]) ++bucket;      // exchanged and updated chunk by chunk above
-    else fire();                                                   // first encoder block's weights
-    if (early_err) return fail(SGV_ERR_HIP, "early AdamW launch failed");
-    if (fuse) {
-        const int nbk = (int)e->buckets.size();
-        if (early) {
-            CHK(join_side(e));                                            // side-stream dW GEMMs of the last bucket
-            CHK(adamw_range(e, fuse_lr, nbk - 2, nbk - 1, 1, e->stream)); // first encoder block's conv weights
-            CHK(adamw_range(e, fuse_lr, 0, nbk, 2, e->stream));           // every flat item
-            e->side_dirty = true;                                          // AdamW launches may still run on the side stream
-            CHK(join_side(e));
-            CHK(adamw_finish(e));
-        } else {
-            CHK(join_side(e));
-            if (!e->cb) CHK(sgv_adamw_step(e, fuse_lr));
-        }
-        return SGV_OK;
-    }
-    CHK(join_side(e));
-    return SGV_OK;
+    return rel.finish();
 }
 // every path out of backward_impl has joined the side stream: the main stream's position is past the last reader of the batch
 static int backward_done(sgv_engine* e, int rc) { e->coll_inflight = false; if (rc == SGV_OK) x_release(e); return rc; }
@@ -2055,171 +1222,6 @@ int sgv_backward_step(sgv_engine* e, float alpha, float beta, float lr) {
     return backward_done(e, backward_impl(e, alpha, beta, lr));
 }
 
-int sgv_grad_norm(sgv_engine* e, double* out) {
-    if (!e || !out) return fail(SGV_ERR_ARG, "null argument");
-    CHK(lp_sync(e));
-    if (opt_grad_norm(e->adam_dev, e->sn_dev, e->items_adam, e->n_items_adam, e->gnorm_part, e->stream)) return fail(SGV_ERR_HIP, "grad-norm launch failed");
-    ew_rowsum_d(e->gnorm_part, e->n_items_adam, 1, e->scal + 15, 1.0, e->stream);
-    double h = 0.0;
-    HIPCHK(hipMemcpyAsync(&h, e->scal + 15, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    *out = sqrt(h);
-    return SGV_OK;
-}
-
-// which: 1 = conv-weight tiles, 2 = flat items (biases, GroupNorm affine, Linear heads), 3 = both
-static int adamw_begin(sgv_engine* e) {
-    if (e->adam_open) return 0;          // a bucket of this step was updated ahead of the caller's first=1 call
-    e->step += 1;
-    e->copies_fresh = false;
-    e->wtu_fresh = false;
-    e->adam_open = true;
-    e->bucket_updated.assign(e->buckets.size(), 0);
-    return 0;
-}
-// end of an optimisation step: whatever ran on the optimizer stream joins the engine stream, gradient norm^2 in a fixed order
-static int adamw_finish(sgv_engine* e) {
-    if (e->opt_dirty) {
-        CHK(stream_wait(e, e->stream, e->opt));
-        e->opt_dirty = false;
-    }
-    e->copies_fresh = true;
-    e->wtu_fresh = true;
-    e->adam_open = false;
-    ew_rowsum_d(e->gnorm_part, e->n_items_adam_flat + e->n_items_adam_2d, 1, e->scal + 15, 1.0, e->stream);
-    return 0;
-}
-static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, bool from_lp) {
-    if (t1 <= t0) return 0;
-    const AdamCoef c = adam_coef(e->step);
-    // Beside the backward pass (any stream but the main one) the pass goes out in slices of 3072 64 x 64 tiles: its
-    // workgroups are small and short-lived, so while one launch lasts they refill every CU the moment a slot frees, and a kernel of
-    // the main stream whose workgroup needs most of a CU's LDS (the 128-row GEMM tails, the fused Conv+GroupNorm stages) is not
-    // placed until the launch ends -- a kernel trace showed a 60 us tail taking 816 us beside a 1.3 ms AdamW launch.  At a launch
-    // boundary the chip drains, and the waiting workgroups get their CUs.
-    constexpr int ADAM_SLICE = 3072;    // re-tuned on the final build: 2048 / 2560 / 3072 / 3584 = 11.16 / 11.11 / 11.10 / 11.11 ms
-    const int slice = st != e->stream ? ADAM_SLICE : t1 - t0;
-    for (int a = t0; a < t1; a += slice) {
-        const int b = std::min(t1, a + slice);
-        if (opt_adamw_sn(e->adam_dev, e->sn_dev, e->items_adam_2d + a, b - a, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + e->n_items_adam_flat + a, e->dt, st,
-                         e->grads, from_lp ? e->grads_lp : nullptr, (!from_lp && grad_lp_active(e) && !e->lp_fp32) ? 1 : 0))
-            return fail(SGV_ERR_HIP, "adamw launch failed");
-    }
-    return 0;
-}
-// what the flat pass reads of a packed weight bucket (Linear heads)
-static void unpack_bucket_flat(sgv_engine* e, int b, hipStream_t st) {
-    for (auto& r : e->bucket_flat_w[b]) ew_unpack_bf16((const char*)e->grads_lp + 2 * r.first, e->grads + r.first, (long)r.second, st);
-    e->bucket_packed[b] &= ~2;
-}
-static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, int which, hipStream_t st) {
-    // native RCCL path: the all-reduce of every bucket touched here must have landed, and so must the small bucket's
-    // (last index): it carries the <G,W> scalars every conv weight's update reads
-    const int n_pend = (int)e->bucket_pending.size();
-    for (int b = bucket_lo; b < n_pend; b = (b + 1 < bucket_hi ? b + 1 : (b < n_pend - 1 ? n_pend - 1 : n_pend)))
-        if (e->bucket_pending[b]) {
-            HIPCHK(hipStreamWaitEvent(st, e->bucket_done[b], 0));
-            e->bucket_pending[b] = 0;
-        }
-    // the averaged bf16 wire copy: the tiled pass reads it in place, the flat pass gets its few weights unpacked
-    const int np = (int)e->bucket_packed.size();
-    for (int b = bucket_lo; b < bucket_hi && b < np; ++b)
-        if ((which & 2) && (e->bucket_packed[b] & 2)) unpack_bucket_flat(e, b, st);
-    // biases, GroupNorm affine and the Linear heads: flat pass.  Conv weights: tiled pass that also writes both
-    // compute copies and W_new^T u for the next forward's power iteration; buckets updated ahead (adamw_bucket_async) are skipped.
-    const AdamCoef c = adam_coef(e->step);
-    const int f0 = e->flat_off[bucket_lo], f1 = e->flat_off[bucket_hi];
-    if ((which & 2) && opt_adamw(e->adam_dev, e->sn_dev, e->items_adam_flat + f0, f1 - f0, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + f0, e->dt, st))
-        return fail(SGV_ERR_HIP, "adamw launch failed");
-    if (which & 1) {
-        const int nu = (int)e->bucket_updated.size();
-        auto skip = [&](int b) { return b < nu && e->bucket_updated[b]; };
-        auto lp = [&](int b) { return b < np && (e->bucket_packed[b] & 1); };
-        for (int b = bucket_lo; b < bucket_hi;) {
-            if (skip(b)) { ++b; continue; }
-            int h = b + 1;
-            while (h < bucket_hi && !skip(h) && lp(h) == lp(b)) ++h;          // runs of buckets read from the same place
-            CHK(adamw_tiles(e, lr, e->tile_off[b], e->tile_off[h], st, lp(b)));
-            for (int k = b; k < h; ++k) if (k < np) e->bucket_packed[k] &= ~1;
-            b = h;
-        }
-    }
-    return 0;
-}
-// conv-weight AdamW of ONE weight bucket on `st`, ahead of the rest of the step: the caller has made `st` wait for the bucket's
-// gradients (and their all-reduce) and for the <G,W> slots of its layers (bucket_dots)
-static int adamw_bucket_async(sgv_engine* e, float lr, int b, hipStream_t st) {
-    CHK(adamw_begin(e));
-    const bool packed = b < (int)e->bucket_packed.size() && e->bucket_packed[b];
-    const bool from_lp = packed && (e->bucket_packed[b] & 1);
-    CHK(adamw_tiles(e, lr, e->tile_off[b], e->tile_off[b + 1], st, from_lp));
-    if (from_lp) e->bucket_packed[b] &= ~1;
-    e->bucket_updated[b] = 1;
-    if (st != e->stream) e->opt_dirty = e->opt_dirty || st == e->opt;
-    return 0;
-}
-int sgv_bucket_dots(const sgv_engine* e, int bucket, size_t* offset_elems, size_t* count_elems) {
-    if (!e || !offset_elems || !count_elems) return fail(SGV_ERR_ARG, "null argument");
-    if (bucket < 0 || bucket >= (int)e->bucket_dots.size()) return fail(SGV_ERR_ARG, "bucket %d is not a weight bucket [0,%d)", bucket, (int)e->bucket_dots.size());
-    *offset_elems = e->bucket_dots[bucket].first; *count_elems = e->bucket_dots[bucket].second;
-    return SGV_OK;
-}
-int sgv_adamw_bucket_async(sgv_engine* e, float lr, int bucket) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    if (lr < 0.f) return fail(SGV_ERR_ARG, "negative learning rate");
-    if (!ensure_opt(e)) return fail(SGV_ERR_HIP, "the engine has no optimizer stream");
-    if (bucket < 0 || bucket >= (int)e->buckets.size() - 1) return fail(SGV_ERR_ARG, "bucket %d is not a weight bucket [0,%d)", bucket, (int)e->buckets.size() - 1);
-    if (e->adam_open && e->bucket_updated[bucket]) return fail(SGV_ERR_STATE, "bucket %d was already updated in this step", bucket);
-    return adamw_bucket_async(e, lr, bucket, e->opt);
-}
-int sgv_adamw_step_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, int first, int last) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    const int nbk = (int)e->buckets.size();
-    if (bucket_lo < 0 || bucket_hi > nbk || bucket_lo > bucket_hi) return fail(SGV_ERR_ARG, "bucket range [%d,%d) outside [0,%d)", bucket_lo, bucket_hi, nbk);
-    if (first) CHK(adamw_begin(e));
-    if (e->step < 1 || !e->adam_open) return fail(SGV_ERR_STATE, "sgv_adamw_step_range: the first call of a step must pass first=1");
-    CHK(adamw_range(e, lr, bucket_lo, bucket_hi, 3, e->stream));
-    if (last) CHK(adamw_finish(e));
-    return SGV_OK;
-}
-int sgv_adamw_step(sgv_engine* e, float lr) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    const int nbk = (int)e->buckets.size();
-    if (e->comm && nbk >= 3) {
-        // every layer whose bucket has arrived, then the small bucket's tensors, while the last weight bucket (first
-        // encoder layer, index nbk - 2) is still in flight; that layer last
-        CHK(sgv_adamw_step_range(e, lr, 0, nbk - 2, 1, 0));
-        CHK(sgv_adamw_step_range(e, lr, nbk - 1, nbk, 0, 0));
-        return sgv_adamw_step_range(e, lr, nbk - 2, nbk - 1, 0, 1);
-    }
-    return sgv_adamw_step_range(e, lr, 0, nbk, 1, 1);
-}
-int sgv_bucket_count(const sgv_engine* e) { return e ? (int)e->buckets.size() : 0; }
-int sgv_set_grad_payload(sgv_engine* e, int dtype) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "gradient payload must be f32 or bf16");
-    for (char c : e->bucket_packed) if (c) return fail(SGV_ERR_STATE, "a packed bucket is in flight: change the payload between steps");
-    if (dtype == SGV_DTYPE_BF16) CHK(ensure_lp_mirror(e));
-    e->payload_bf16 = dtype == SGV_DTYPE_BF16;
-    e->bucket_packed.assign(e->buckets.size(), 0);
-    return SGV_OK;
-}
-int sgv_grad_payload_buffer(sgv_engine* e, void** ptr, size_t* count) {
-    if (!e || !ptr || !count) return fail(SGV_ERR_ARG, "null argument");
-    if (!e->payload_bf16) return fail(SGV_ERR_STATE, "the gradient payload is the fp32 arena (sgv_grad_buffer)");
-    *ptr = e->grads_lp; *count = e->n_grads;
-    return SGV_OK;
-}
-int sgv_grad_payload_unpack(sgv_engine* e) {
-    if (!e) return fail(SGV_ERR_ARG, "null engine");
-    for (int b = 0; b < (int)e->bucket_packed.size(); ++b)
-        if (e->bucket_packed[b]) {
-            if (b < (int)e->bucket_pending.size() && e->bucket_pending[b]) { HIPCHK(hipStreamWaitEvent(e->stream, e->bucket_done[b], 0)); e->bucket_pending[b] = 0; }
-            ew_unpack_bf16((const char*)e->grads_lp + 2 * e->buckets[b].first, e->grads + e->buckets[b].first, (long)e->buckets[b].second, e->stream);
-            e->bucket_packed[b] = 0;
-        }
-    return SGV_OK;
-}
 // device memory held by the engine, bytes: [0] fp32 master parameters, [1] gradient arena, [2] Adam m + v, [3] compute-dtype weight
 // copies, [4] activations (every map of forward and backward at max_batch: nothing is recomputed), [5] split-K / reduction workspaces
 int sgv_memory_info(const sgv_engine* e, size_t out[6]) {
@@ -2231,14 +1233,6 @@ int sgv_memory_info(const sgv_engine* e, size_t out[6]) {
 int sgv_recompute_bytes(const sgv_engine* e, size_t* bytes) {
     if (!e || !bytes) return fail(SGV_ERR_ARG, "null argument");
     *bytes = e->recompute_bytes;
-    return SGV_OK;
-}
-int sgv_last_grad_norm(sgv_engine* e, double* out) {
-    if (!e || !out) return fail(SGV_ERR_ARG, "null argument");
-    double h = 0.0;
-    HIPCHK(hipMemcpyAsync(&h, e->scal + 15, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    *out = sqrt(h);
     return SGV_OK;
 }
 // ---- per-epoch statistics without a host sync per step (reference loop: modules/train.py:171-174 reads four scalars and

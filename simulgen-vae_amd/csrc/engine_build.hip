@@ -1,0 +1,574 @@
+// What runs once in sgv_create: the layer graph in the reference's registration order, the layout of the parameter, gradient and
+// activation arenas, and the descriptor / work-item tables of the table-driven kernels.
+#include "engine_internal.h"
+
+static int gn_groups(int c) { int g = c / 4; if (g < 1) g = 1; if (g > 8) g = 8; return g; }
+
+struct Builder {
+    sgv_engine* e;
+    size_t np = 0, ngw = 0, ngs = 0, ncp = 0;
+    std::vector<size_t*> small_grad_slots;   // gb / ggamma / gbeta offsets get rebased after the weight zone
+    int add_layer(const std::string& prefix, int op, int cin, int cout, int k, bool used, bool has_grad, bool need_wct,
+                  int lin_kind = LIN_NONE, int lin_C = 0) {
+        Layer l;
+        l.prefix = prefix; l.op = op; l.cin = cin; l.cout = cout; l.k = k;
+        l.used = used; l.has_grad = has_grad; l.need_wct = need_wct && used && op != OP_LINEAR;
+        l.lin_kind = lin_kind; l.lin_C = lin_C;
+        e->layers.push_back(l);
+        return (int)e->layers.size() - 1;
+    }
+    int add_gn(const std::string& prefix, int C, bool used, bool has_grad) {
+        GNLayer g;
+        g.prefix = prefix; g.C = C; g.G = gn_groups(C); g.used = used; g.has_grad = has_grad;
+        e->gns.push_back(g);
+        return (int)e->gns.size() - 1;
+    }
+};
+
+static Tensor alloc_act(sgv_engine* e, long rows, int C, bool f32 = false) {
+    Tensor t;
+    t.C = C; t.ld = C; t.f32 = f32;
+    size_t bytes = (size_t)rows * C * (f32 ? 4 : e->esz);
+    e->act_used = align_up(e->act_used, 256);
+    t.p = (void*)(e->act_used);   // offset for now; rebased after allocation
+    e->act_used += bytes;
+    return t;
+}
+static Tensor view_cols(const Tensor& t, int c0, int C, sgv_engine* e) {
+    Tensor v = t;
+    v.p = (char*)t.p + (size_t)c0 * (t.f32 ? 4 : e->esz);
+    v.C = C;
+    return v;
+}
+
+// ---- state-entry list in reference order (mirrors simulgen-vae_amd/spec.py) --------------------
+static void add_entries_for_layer(sgv_engine* e, int li) {
+    const Layer& l = e->layers[li];
+    auto push = [&](const char* suffix, int kind, std::vector<int64_t> shape, bool hg) {
+        StateEntry s;
+        s.name = l.prefix + suffix; s.kind = kind; s.layer = li; s.shape = shape; s.has_grad = hg;
+        e->entry_index[s.name] = (int)e->entries.size();
+        e->entries.push_back(s);
+    };
+    push(".bias", 0, {l.cout}, l.has_grad);
+    if (l.op == OP_CONV) push(".weight_orig", 1, {l.cout, l.cin, l.k}, l.has_grad);
+    else if (l.op == OP_CONVT) push(".weight_orig", 1, {l.cin, l.cout, l.k}, l.has_grad);
+    else push(".weight_orig", 1, {l.cout, l.cin}, l.has_grad);
+    push(".weight_u", 2, {l.cout}, false);
+    push(".weight_v", 3, {(int64_t)l.cin * l.k}, false);
+}
+static void add_entries_for_gn(sgv_engine* e, int gi) {
+    const GNLayer& g = e->gns[gi];
+    StateEntry s;
+    s.name = g.prefix + ".weight"; s.kind = 4; s.gn = gi; s.shape = {g.C}; s.has_grad = g.has_grad;
+    e->entry_index[s.name] = (int)e->entries.size(); e->entries.push_back(s);
+    s.name = g.prefix + ".bias"; s.kind = 5;
+    e->entry_index[s.name] = (int)e->entries.size(); e->entries.push_back(s);
+}
+
+static Stage mk_stage(int layer, int gn, int act, bool pre_gelu = false, bool out_f32 = false) {
+    Stage s;
+    s.layer = layer; s.gn = gn; s.act = act; s.pre_gelu = pre_gelu; s.out_f32 = out_f32;
+    return s;
+}
+
+// Build layers + blocks in the reference's module registration order so that `entries` comes out in
+// state_dict order (encoder: blocks, residual blocks, xs_linear, last; decoder: blocks, residual blocks,
+// recon, sequence_start, xs_sequence, condition_z, condition_xz).
+static int build_graph(sgv_engine* e) {
+    Builder B{e};
+    const bool small = e->cfg.small != 0;
+    const int n = e->n, T = e->T;
+    char buf[256];
+    auto P = [&](const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap); return std::string(buf); };
+
+    e->encA.resize(n); e->encR.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const int cin = i == 0 ? e->N : e->enc[i - 1], C = e->enc[i];
+        std::string p = P("encoder.encoder_blocks.%d.module_list.0._seq", i);
+        int l0 = B.add_layer(p + ".0", OP_CONV, cin, C, 1, true, true, i > 0);
+        int g0 = B.add_gn(p + ".1", C, true, true);
+        add_entries_for_layer(e, l0); add_entries_for_gn(e, g0);
+        e->encA[i].st.push_back(mk_stage(l0, g0, 1));
+        if (!small) {
+            int l1 = B.add_layer(p + ".3", OP_CONV, C, C, 3, true, true, true);
+            int g1 = B.add_gn(p + ".4", C, true, true);
+            add_entries_for_layer(e, l1); add_entries_for_gn(e, g1);
+            e->encA[i].st.push_back(mk_stage(l1, g1, 1));
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const int C = e->enc[i];
+        std::string p = P("encoder.encoder_residual_blocks.%d.seq", i);
+        e->encR[i].residual = true;
+        for (int r = 0; r < (small ? 1 : 2); ++r) {
+            int l = B.add_layer(p + P(".%d", r * 3), OP_CONV, C, C, 3, true, true, true);
+            int g = B.add_gn(p + P(".%d", r * 3 + 1), C, true, true);
+            add_entries_for_layer(e, l); add_entries_for_gn(e, g);
+            e->encR[i].st.push_back(mk_stage(l, g, 1));
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const bool dead = (i == 0) || (i == n - 1);
+        int l = B.add_layer(P("encoder.xs_linear.%d", i), OP_LINEAR, e->enc[i] * T, e->H, 1, true, !dead, false, LIN_HEAD, e->enc[i]);
+        add_entries_for_layer(e, l);
+        e->xs_lin.push_back(l);
+    }
+    e->last_lin = B.add_layer("encoder.last_x_linear", OP_LINEAR, e->enc[n - 1] * T, 2 * e->Z, 1, true, true, false, LIN_HEAD, e->enc[n - 1]);
+    add_entries_for_layer(e, e->last_lin);
+
+    const int n_st = e->n_st;
+    e->decU.resize(n_st); e->decD.resize(n_st);
+    e->decP1.resize(n_st); e->decP2.resize(n_st); e->decX.resize(n_st); e->decQ1.resize(n_st); e->decQ2.resize(n_st);
+    for (int i = 0; i < n_st; ++i) {
+        int l = B.add_layer(P("decoder.decoder_blocks.%d.module_list.0._seq.0", i), OP_CONVT, e->dec[i], e->dec[i + 1], 3, true, true, true);
+        add_entries_for_layer(e, l);
+        e->decU[i].st.push_back(mk_stage(l, -1, 1));
+    }
+    for (int i = 0; i < n_st; ++i) {
+        const int C = e->dec[i + 1];
+        std::string p = P("decoder.decoder_residual_blocks.%d.seq", i);
+        e->decD[i].residual = true;
+        struct CS { int cin, cout, k; };
+        std::vector<CS> cs;
+        if (small) cs = {{C, 5 * C, 1}, {5 * C, 5 * C, 5}, {5 * C, C, 1}};
+        else cs = {{C, C, 1}, {C, 5 * C, 5}, {5 * C, 5 * C, 5}, {5 * C, C, 1}};
+        for (size_t r = 0; r < cs.size(); ++r) {
+            int l = B.add_layer(p + P(".%d", (int)r * 3), OP_CONV, cs[r].cin, cs[r].cout, cs[r].k, true, true, true);
+            int g = B.add_gn(p + P(".%d", (int)r * 3 + 1), cs[r].cout, true, true);
+            add_entries_for_layer(e, l); add_entries_for_gn(e, g);
+            e->decD[i].st.push_back(mk_stage(l, g, 1));
+        }
+    }
+    {
+        int l = B.add_layer("decoder.recon.0", OP_CONV, e->dec[n_st], e->N, 1, true, true, true);
+        int g = B.add_gn("decoder.recon.1", e->N, true, true);
+        add_entries_for_layer(e, l); add_entries_for_gn(e, g);
+        e->recon.st.push_back(mk_stage(l, g, 2));
+    }
+    {
+        e->start_lin = B.add_layer("decoder.sequence_start.0.0", OP_LINEAR, e->Z, e->Z * T, 1, true, true, false, LIN_EXPAND, e->Z);
+        int l = B.add_layer("decoder.sequence_start.0.2", OP_CONV, e->Z, e->dec[0], 5, true, true, true);
+        int g = B.add_gn("decoder.sequence_start.0.3", e->dec[0], true, true);
+        add_entries_for_layer(e, e->start_lin); add_entries_for_layer(e, l); add_entries_for_gn(e, g);
+        e->decS.st.push_back(mk_stage(l, g, 1));
+    }
+    for (int i = 0; i < n_st; ++i) {
+        const bool live = i < n_st - 1;
+        std::string p = P("decoder.xs_sequence.%d", i);
+        int ll = B.add_layer(p + ".0", OP_LINEAR, e->H, e->H * T, 1, live, live, false, LIN_EXPAND, e->H);
+        int l = B.add_layer(p + ".2", OP_CONV, e->H, e->dec[i + 1], 5, live, live, true);
+        int g = B.add_gn(p + ".3", e->dec[i + 1], live, live);
+        add_entries_for_layer(e, ll); add_entries_for_layer(e, l); add_entries_for_gn(e, g);
+        e->xs_exp.push_back(ll);
+        e->decX[i].st.push_back(mk_stage(l, g, 1));
+    }
+    for (int which = 0; which < 2; ++which) {
+        for (int i = 0; i < n_st; ++i) {
+            const bool live = i < n_st - 1;
+            const int C = (which + 1) * e->dec[i + 1];
+            std::string p = P("decoder.%s.%d", which ? "condition_xz" : "condition_z", i);
+            Block& b1 = which ? e->decQ1[i] : e->decP1[i];
+            Block& b2 = which ? e->decQ2[i] : e->decP2[i];
+            b1.residual = true;
+            for (int r = 0; r < (small ? 1 : 2); ++r) {
+                int l = B.add_layer(p + P(".0._seq.%d", r * 3), OP_CONV, C, C, 3, live, live, true);
+                int g = B.add_gn(p + P(".0._seq.%d", r * 3 + 1), C, live, live);
+                add_entries_for_layer(e, l); add_entries_for_gn(e, g);
+                b1.st.push_back(mk_stage(l, g, 1));
+            }
+            int l2 = B.add_layer(p + ".2", OP_CONV, C, 2 * e->dec[i + 1], 3, live, live, true);
+            add_entries_for_layer(e, l2);
+            b2.st.push_back(mk_stage(l2, -1, 0, true, true));
+        }
+    }
+    return 0;
+}
+
+// ---- arena layout ---------------------------------------------------------------------------
+static int layout_arenas(sgv_engine* e) {
+    size_t np = 0;
+    auto take = [&](size_t& cur, size_t n) { size_t o = cur; cur = align_up(cur + n, 4); return o; };
+    for (auto& l : e->layers) {
+        l.w = take(np, (size_t)l.nw());
+        l.b = take(np, l.cout);
+        l.u = take(np, l.cout);
+        l.v = take(np, (size_t)l.cin * l.k);
+    }
+    for (auto& g : e->gns) { g.gamma = take(np, g.C); g.beta = take(np, g.C); }
+    e->n_params = np;
+    return 0;
+}
+
+// order in which weight gradients become available during backward (for bucketed all-reduce)
+static void backward_layer_order(sgv_engine* e, std::vector<std::vector<int>>& sections) {
+    auto add_block = [&](std::vector<int>& v, const Block& b) {
+        for (int s = (int)b.st.size() - 1; s >= 0; --s) v.push_back(b.st[s].layer);
+    };
+    const int n = e->n, n_st = e->n_st;
+    std::vector<int> sec;
+    add_block(sec, e->recon);
+    sections.push_back(sec);
+    for (int i = n_st - 1; i >= 0; --i) {
+        sec.clear();
+        if (i < n_st - 1) {
+            add_block(sec, e->decQ2[i]); add_block(sec, e->decQ1[i]); add_block(sec, e->decX[i]);
+            sec.push_back(e->xs_exp[i]);
+            add_block(sec, e->decP2[i]); add_block(sec, e->decP1[i]);
+        }
+        add_block(sec, e->decD[i]); add_block(sec, e->decU[i]);
+        if (i == 0) { add_block(sec, e->decS); sec.push_back(e->start_lin); }
+        sections.push_back(sec);
+    }
+    sec.clear();
+    sec.push_back(e->last_lin);
+    for (int i = n - 1; i >= 1; --i) {
+        if (e->layers[e->xs_lin[i]].has_grad) sec.push_back(e->xs_lin[i]);
+        add_block(sec, e->encR[i]); add_block(sec, e->encA[i]);
+    }
+    add_block(sec, e->encR[0]);
+    sections.push_back(sec);
+    sec.clear();
+    add_block(sec, e->encA[0]);
+    sections.push_back(sec);
+}
+
+static int layout_grads(sgv_engine* e) {
+    std::vector<std::vector<int>> sections;
+    backward_layer_order(e, sections);
+    size_t ng = 0;
+    auto take = [&](size_t n) { size_t o = ng; ng = align_up(ng + n, 4); return o; };
+    e->buckets.clear();
+    std::vector<int> placed;          // sections that became buckets
+    for (size_t si = 0; si < sections.size(); ++si) {
+        size_t start = ng;
+        for (int li : sections[si]) {
+            Layer& l = e->layers[li];
+            if (!l.has_grad) continue;
+            l.gw = take((size_t)l.nw());
+        }
+        if (ng > start) { e->buckets.push_back({start, ng - start}); placed.push_back((int)si); }
+    }
+    e->n_grads_w = ng;
+    size_t small_start = ng;
+    // head of the small zone: the <G,W_eff> slots of the CONV layers, bucket by bucket (bucket_dots: final once the bucket's dY
+    // kernels are enqueued); then the Linear layers' slots (computed from G itself at the end of backward, they travel with the
+    // small bucket), biases and GroupNorm affine
+    e->bucket_dots.clear();
+    for (int si : placed) {
+        const size_t d0 = ng;
+        for (int li : sections[si]) { Layer& l = e->layers[li]; if (l.has_grad && l.op != OP_LINEAR && l.gdot == NPOS) l.gdot = take(SGV_DOT_SLOTS); }
+        e->bucket_dots.push_back({d0, ng - d0});
+    }
+    e->dots_total = ng - small_start;
+    for (auto& l : e->layers) if (l.has_grad) { if (l.gdot == NPOS) l.gdot = take(SGV_DOT_SLOTS); l.gb = take(l.cout); }
+    for (auto& g : e->gns) if (g.has_grad) { g.ggamma = take(g.C); g.gbeta = take(g.C); }
+    e->buckets.push_back({small_start, ng - small_start});
+    e->n_grads = ng;
+    // every trainable layer must have been placed
+    for (auto& l : e->layers) if (l.has_grad && l.gw == NPOS) return fail(SGV_ERR_STATE, "layer %s missing from backward order", l.prefix.c_str());
+    return 0;
+}
+
+// ---- activations ------------------------------------------------------------------------------
+static void alloc_block(sgv_engine* e, Block& b, long M, int cin, bool need_din) {
+    int c_in = cin;
+    for (size_t s = 0; s < b.st.size(); ++s) {
+        Stage& S = b.st[s];
+        const Layer& L = e->layers[S.layer];
+        if (S.pre_gelu) { S.pre = alloc_act(e, M, c_in); S.dpre = alloc_act(e, M, c_in); }
+        S.y = alloc_act(e, M, L.cout, S.out_f32);
+        if (S.gn >= 0 || S.act) { if (!S.a.p) S.a = alloc_act(e, M, L.cout); }
+        else S.a = S.y;
+        S.dy = (S.gn >= 0 || S.act) ? alloc_act(e, M, L.cout) : Tensor();
+        if (s + 1 < b.st.size()) S.da = alloc_act(e, M, L.cout);
+        if (S.gn >= 0) {
+            const GNLayer& g = e->gns[S.gn];
+            S.sums = e->n_stats_fwd; e->n_stats_fwd += (size_t)e->maxB * g.G * 2;
+        }
+        c_in = L.cout;
+    }
+    (void)need_din;
+}
+// Tensor.p holds arena offsets until rebase; mark "preset" views via a flag value
+static void rebase(sgv_engine* e, Tensor& t) { if (t.p || t.C) t.p = e->act + (size_t)t.p; }
+
+static int alloc_activations(sgv_engine* e) {
+    const long M = (long)e->maxB * e->T;
+    const int n = e->n, n_st = e->n_st;
+    e->act_used = 256;   // offset 0 is reserved so that "p == 0" means unallocated
+    e->x_bufs[0] = alloc_act(e, M, e->N);
+    e->x_bufs[1] = alloc_act(e, M, e->N);
+    e->xhat = alloc_act(e, M, e->N);
+    e->dy_recon = alloc_act(e, M, e->N);
+    e->enc_h.resize(n); e->d_h.resize(n);
+    for (int i = 0; i < n; ++i) {
+        alloc_block(e, e->encA[i], M, i == 0 ? e->N : e->enc[i - 1], i > 0);
+        alloc_block(e, e->encR[i], M, e->enc[i], true);
+        e->enc_h[i] = e->encR[i].st.back().a;
+        e->d_h[i] = alloc_act(e, M, e->enc[i]);
+    }
+    e->enc_a_dummy.resize(n);
+    for (int i = 0; i < n; ++i) e->enc_a_dummy[i] = alloc_act(e, M, e->enc[i]);   // d(a_i): grad wrt ConvBlock output
+    e->sbuf = alloc_act(e, M, e->Z);
+    e->d_sbuf = alloc_act(e, M, e->Z);
+    alloc_block(e, e->decS, M, e->Z, true);
+    e->zs.resize(n_st); e->dzs.resize(n_st); e->cat.resize(n_st); e->dcat.resize(n_st); e->dec_out.resize(n_st);
+    e->d_out.resize(n_st); e->d_u.resize(n_st); e->d_pres.resize(n_st); e->d_qres.resize(n_st); e->d_outp.resize(n_st);
+    e->gp.resize(n_st); e->gq.resize(n_st); e->xl.resize(n_st); e->d_xl.resize(n_st);
+    e->zs[0] = e->decS.st.back().a;
+    for (int i = 0; i < n_st; ++i) {
+        const int C = e->dec[i + 1];
+        const bool live = i < n_st - 1;
+        if (i > 0) e->zs[i] = alloc_act(e, M, e->dec[i]);
+        e->dzs[i] = alloc_act(e, M, e->dec[i]);
+        alloc_block(e, e->decU[i], M, e->dec[i], true);
+        if (live) {
+            e->cat[i] = alloc_act(e, M, 2 * C);
+            e->dcat[i] = alloc_act(e, M, 2 * C);
+            // DecoderResidualBlock output and xs_sequence output are written straight into the concat buffer
+            Tensor v = e->cat[i]; v.C = C; v.p = (void*)((size_t)v.p + (size_t)C * e->esz);
+            e->decD[i].st.back().a = v;
+            Tensor vx = e->cat[i]; vx.C = C;
+            e->decX[i].st.back().a = vx;
+        }
+        alloc_block(e, e->decD[i], M, C, true);
+        e->dec_out[i] = e->decD[i].st.back().a;
+        e->d_out[i] = alloc_act(e, M, C);
+        e->d_u[i] = alloc_act(e, M, C);
+        if (live) {
+            alloc_block(e, e->decP1[i], M, C, true);
+            alloc_block(e, e->decP2[i], M, C, true);
+            e->xl[i] = alloc_act(e, M, e->H);
+            e->d_xl[i] = alloc_act(e, M, e->H);
+            alloc_block(e, e->decX[i], M, e->H, true);
+            alloc_block(e, e->decQ1[i], M, 2 * C, true);
+            alloc_block(e, e->decQ2[i], M, 2 * C, true);
+            e->d_pres[i] = alloc_act(e, M, C);
+            e->d_qres[i] = alloc_act(e, M, 2 * C);
+            e->d_outp[i] = alloc_act(e, M, C);
+            e->gp[i] = alloc_act(e, M, 2 * C);
+            e->gq[i] = alloc_act(e, M, 2 * C);
+        }
+    }
+    alloc_block(e, e->recon, M, e->dec[n_st], true);
+    // fp32 side buffers
+    auto f32buf = [&](long count) { e->act_used = align_up(e->act_used, 256); size_t o = e->act_used; e->act_used += (size_t)count * 4; return (float*)o; };
+    e->xs_raw.resize(n); e->d_xs_raw.resize(n);
+    for (int i = 0; i < n; ++i) { e->xs_raw[i] = f32buf((long)e->maxB * e->H); e->d_xs_raw[i] = f32buf((long)e->maxB * e->H); }
+    e->last = f32buf((long)e->maxB * 2 * e->Z); e->d_last = f32buf((long)e->maxB * 2 * e->Z);
+    e->zlat = f32buf((long)e->maxB * e->Z); e->d_z = f32buf((long)e->maxB * e->Z);
+    e->eps.resize(n_st); e->zmap.resize(n_st); e->eps_set.assign(n_st, 0);
+    e->eps[0] = f32buf((long)e->maxB * e->Z);
+    e->zmap[0] = nullptr;
+    for (int i = 0; i + 1 < n_st; ++i) {
+        e->eps[i + 1] = f32buf(M * e->dec[i + 1]);
+        e->zmap[i] = f32buf(M * e->dec[i + 1]);
+    }
+    e->recon_unit = f32buf(3L * e->N);
+    // backward group sums mirror the forward slots
+    e->n_stats = e->n_stats_fwd * 2;
+    e->act_bytes = align_up(e->act_used, 256);
+    return 0;
+}
+
+static void rebase_block(sgv_engine* e, Block& b) {
+    for (auto& S : b.st) {
+        const bool alias = (S.gn < 0 && !S.act);
+        rebase(e, S.pre); rebase(e, S.dpre); rebase(e, S.y); rebase(e, S.dy); rebase(e, S.da);
+        if (alias) S.a = S.y; else rebase(e, S.a);
+        if (S.sums != NPOS) S.sums2 = S.sums + e->n_stats_fwd;
+    }
+}
+static void rebase_all(sgv_engine* e) {
+    auto R = [&](Tensor& t) { rebase(e, t); };
+    auto RF = [&](float*& p) { if (p) p = (float*)(e->act + (size_t)p); };
+    R(e->x_bufs[0]); R(e->x_bufs[1]); e->x_cur = 0; e->x_in = e->x_bufs[0];
+    R(e->xhat); R(e->dy_recon); R(e->sbuf); R(e->d_sbuf);
+    for (auto& b : e->encA) rebase_block(e, b);
+    for (auto& b : e->encR) rebase_block(e, b);
+    for (auto& b : e->decU) rebase_block(e, b);
+    for (auto& b : e->decD) rebase_block(e, b);
+    for (int i = 0; i + 1 < e->n_st; ++i) { rebase_block(e, e->decP1[i]); rebase_block(e, e->decP2[i]); rebase_block(e, e->decX[i]); rebase_block(e, e->decQ1[i]); rebase_block(e, e->decQ2[i]); }
+    rebase_block(e, e->decS); rebase_block(e, e->recon);
+    for (auto& t : e->d_h) R(t);
+    for (auto& t : e->enc_a_dummy) R(t);
+    for (int i = 0; i < e->n; ++i) e->enc_h[i] = e->encR[i].st.back().a;
+    for (int i = 0; i < e->n_st; ++i) {
+        if (i > 0) R(e->zs[i]);
+        R(e->dzs[i]); R(e->d_out[i]); R(e->d_u[i]);
+        if (i + 1 < e->n_st) { R(e->cat[i]); R(e->dcat[i]); R(e->xl[i]); R(e->d_xl[i]); R(e->d_pres[i]); R(e->d_qres[i]); R(e->d_outp[i]); R(e->gp[i]); R(e->gq[i]); }
+        e->dec_out[i] = e->decD[i].st.back().a;
+    }
+    e->zs[0] = e->decS.st.back().a;
+    for (auto& p : e->xs_raw) RF(p);
+    for (auto& p : e->d_xs_raw) RF(p);
+    RF(e->last); RF(e->d_last); RF(e->zlat); RF(e->d_z);
+    for (auto& p : e->eps) RF(p);
+    for (auto& p : e->zmap) RF(p);
+    RF(e->recon_unit);
+}
+
+// ---- descriptor tables --------------------------------------------------------------------------
+// conv weights that train go through the tiled AdamW (optim.hip adamw_sn_kernel), which also leaves W_new^T u
+// behind for the next forward's power iteration
+bool layer_fused_adam(const Layer& l) { return l.used && l.has_grad && l.op != OP_LINEAR && l.cin % 4 == 0; }
+static int build_tables(sgv_engine* e) {
+    // compute copies
+    size_t nc = 0;
+    for (auto& l : e->layers) {
+        if (!l.used || l.op == OP_LINEAR) continue;
+        if (e->dt == SGV_DTYPE_BF16) { l.wc = nc; nc = align_up(nc + (size_t)l.nw(), 8); }
+        if (l.need_wct) { l.wct = nc; nc = align_up(nc + (size_t)l.nw(), 8); }
+    }
+    e->n_copies = nc;
+    // SN scratch
+    size_t nt = 0;
+    int si = 0;
+    for (auto& l : e->layers) { l.sn = si++; if (layer_fused_adam(l)) nt += align_up((size_t)l.cin * l.k, 4); }
+    e->n_sn_tmp_fused = nt;
+    for (auto& l : e->layers) if (!layer_fused_adam(l)) nt += align_up((size_t)l.cin * l.k, 4);
+    e->sn_tmp_s_off = nt;
+    for (auto& l : e->layers) nt += align_up((size_t)l.cout, 4);
+    e->sn_tpart_off.clear(); e->sn_spart_off.clear();
+    for (auto& l : e->layers) {
+        e->sn_tpart_off.push_back(nt);
+        nt += align_up(sn_tpart_floats(l.k, l.cout, l.cin), 4);
+        e->sn_spart_off.push_back(nt);
+        nt += align_up(sn_spart_floats(l.k, l.cout, l.cin), 4);
+    }
+    e->n_sn_tmp = nt;
+    return 0;
+}
+
+static int upload_tables(sgv_engine* e) {
+    const int L = (int)e->layers.size();
+    e->sn_host.resize(L);
+    size_t to_f = 0, to_u = e->n_sn_tmp_fused, to_s = e->sn_tmp_s_off;
+    std::vector<WorkItem> i_sn, i_sn_unf, i_dot, i_adam, i_adam_flat, i_adam_2d, i_copy, i_ts, i_ss;
+    e->fin_lin_dots.clear();
+    const int nbk = (int)e->buckets.size();
+    std::vector<std::vector<WorkItem>> flat_b(nbk), tile_b(nbk), dot_b(nbk);
+    std::vector<std::vector<FinDot>> fin_lin_b(nbk);
+    auto bucket_of = [&](size_t goff) {
+        for (int b = 0; b < nbk; ++b) if (goff >= e->buckets[b].first && goff < e->buckets[b].first + e->buckets[b].second) return b;
+        return nbk - 1;
+    };
+    for (int i = 0; i < L; ++i) {
+        Layer& l = e->layers[i];
+        SNDesc d;
+        d.W = e->params + l.w; d.u = e->params + l.u; d.v = e->params + l.v;
+        size_t& to_t = layer_fused_adam(l) ? to_f : to_u;
+        d.tmp_t = e->sn_tmp + to_t; to_t += align_up((size_t)l.cin * l.k, 4);
+        d.tmp_s = e->sn_tmp + to_s; to_s += align_up((size_t)l.cout, 4);
+        d.tpart = e->sn_tmp + e->sn_tpart_off[i]; d.spart = e->sn_tmp + e->sn_spart_off[i];
+        d.sigma = e->sn_sigma + 2 * i;
+        d.dot = l.has_grad ? e->grads + l.gdot : e->sn_dot_dummy;
+        d.G = l.has_grad ? e->grads + l.gw : nullptr;
+        d.wc = (e->dt == SGV_DTYPE_BF16 && l.wc != NPOS && l.cin % 8 == 0) ? (const void*)(e->copies + l.wc * e->esz) : nullptr;
+        d.taps = l.k; d.rows = l.cout; d.cols = l.cin; d.active = l.used ? 1 : 0;
+        e->sn_host[i] = d;
+        if (l.used) {
+            for (int c = 0; c < sn_gemv_items(l.k, l.cout, l.cin); ++c) { i_sn.push_back({i, c}); if (!layer_fused_adam(l)) i_sn_unf.push_back({i, c}); }
+            for (int c = 0; c < sn_tsum_items(l.k, l.cin); ++c) i_ts.push_back({i, c});
+            for (int c = 0; c < sn_ssum_items(l.cout); ++c) i_ss.push_back({i, c});
+        }
+        if (l.has_grad && l.op == OP_LINEAR) {   // conv layers get <G,W_eff> from their dY kernels (ew.hip)
+            const long nch = opt_flat_items(l.nw());
+            const int bk = bucket_of(l.gw);
+            fin_lin_b[bk].push_back({(const float*)(uintptr_t)dot_b[bk].size(), e->grads + l.gdot, (int)nch, 0});   // src = index inside the bucket for now, rebased below
+            for (long c = 0; c < nch; ++c) dot_b[bk].push_back({i, (int)c});
+        }
+    }
+    // Linear <G,W> items sorted by gradient bucket: a data-parallel backward computes a bucket's share before the bucket is
+    // released (the collective may reduce the bucket's gradients in place while backward goes on)
+    e->dot_off.assign(nbk + 1, 0); e->fin_lin_off.assign(nbk + 1, 0);
+    for (int b = 0; b < nbk; ++b) {
+        for (auto f : fin_lin_b[b]) { f.src = (const float*)((uintptr_t)f.src + i_dot.size()); e->fin_lin_dots.push_back(f); }
+        i_dot.insert(i_dot.end(), dot_b[b].begin(), dot_b[b].end());
+        e->dot_off[b + 1] = (int)i_dot.size(); e->fin_lin_off[b + 1] = (int)e->fin_lin_dots.size();
+    }
+    // the small bucket (which carries these scalars) is released before the last weight bucket: that one must hold no Linear layer
+    if (nbk >= 2 && e->dot_off[nbk] != e->dot_off[nbk - 2]) return fail(SGV_ERR_STATE, "a Linear layer sits in the last weight bucket");
+    e->adam_host.clear();
+    auto add_adam = [&](size_t p, size_t g, long n, int sn, int rows, int cols, int taps, void* wc, void* wct, bool tiled = false) {
+        AdamDesc a;
+        a.p = e->params + p; a.g = e->grads + g; a.m = e->adam_m + g; a.v = e->adam_v + g;
+        a.n = n; a.sn = sn; a.rows = rows; a.cols = cols; a.taps = taps; a.wc = wc; a.wct = wct;
+        a.glp = nullptr;                 // option grad_bf16 points it at the bf16 mirror arena
+        const int id = (int)e->adam_host.size();
+        e->adam_host.push_back(a);
+        const long nch = opt_flat_items(n);
+        const int bk = bucket_of(g);
+        for (long c = 0; c < nch; ++c) { i_adam.push_back({id, (int)c}); if (!tiled) flat_b[bk].push_back({id, (int)c}); }
+        if (tiled)
+            for (int c = 0; c < opt_tile_items(taps, rows, cols); ++c) tile_b[bk].push_back({id, c});
+        return id;
+    };
+    for (int i = 0; i < L; ++i) {
+        Layer& l = e->layers[i];
+        void* wc = l.wc != NPOS ? (void*)(e->copies + l.wc * e->esz) : nullptr;
+        void* wct = l.wct != NPOS ? (void*)(e->copies + l.wct * e->esz) : nullptr;
+        int id = -1;
+        if (l.has_grad) {
+            id = add_adam(l.w, l.gw, l.nw(), i, l.cout, l.cin, l.k, wc, wct, layer_fused_adam(l));
+            add_adam(l.b, l.gb, l.cout, -1, 1, l.cout, 1, nullptr, nullptr);
+        }
+        if (wc || wct) {
+            if (id < 0) {   // used-in-forward but frozen layers never occur for convs; keep general
+                AdamDesc a; memset(&a, 0, sizeof(a));
+                a.p = e->params + l.w; a.n = l.nw(); a.sn = -1; a.rows = l.cout; a.cols = l.cin; a.taps = l.k; a.wc = wc; a.wct = wct;
+                id = (int)e->adam_host.size();
+                e->adam_host.push_back(a);
+            }
+            for (int c = 0; c < opt_copy_items(l.k, l.cout, l.cin); ++c) i_copy.push_back({id, c});
+        }
+    }
+    for (auto& g : e->gns) {
+        if (!g.has_grad) continue;
+        add_adam(g.gamma, g.ggamma, g.C, -1, 1, g.C, 1, nullptr, nullptr);
+        add_adam(g.beta, g.gbeta, g.C, -1, 1, g.C, 1, nullptr, nullptr);
+    }
+    e->bucket_flat_w.assign(nbk, {});
+    for (auto& l : e->layers) if (l.has_grad && !layer_fused_adam(l)) e->bucket_flat_w[bucket_of(l.gw)].push_back({l.gw, (size_t)l.nw()});
+    e->flat_off.assign(nbk + 1, 0); e->tile_off.assign(nbk + 1, 0);
+    for (int b = 0; b < nbk; ++b) {
+        i_adam_flat.insert(i_adam_flat.end(), flat_b[b].begin(), flat_b[b].end());
+        i_adam_2d.insert(i_adam_2d.end(), tile_b[b].begin(), tile_b[b].end());
+        e->flat_off[b + 1] = (int)i_adam_flat.size(); e->tile_off[b + 1] = (int)i_adam_2d.size();
+    }
+    auto up = [&](const void* src, size_t bytes, void** dst) -> int {
+        if (bytes == 0) { *dst = nullptr; return 0; }
+        if (hipMalloc(dst, bytes) != hipSuccess) return -1;
+        if (hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
+        return 0;
+    };
+    if (up(e->sn_host.data(), sizeof(SNDesc) * L, (void**)&e->sn_dev)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(e->adam_host.data(), sizeof(AdamDesc) * e->adam_host.size(), (void**)&e->adam_dev)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_sn.data(), sizeof(WorkItem) * i_sn.size(), (void**)&e->items_sn)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_dot.data(), sizeof(WorkItem) * i_dot.size(), (void**)&e->items_dot)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_adam.data(), sizeof(WorkItem) * i_adam.size(), (void**)&e->items_adam)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_copy.data(), sizeof(WorkItem) * i_copy.size(), (void**)&e->items_copy)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_sn_unf.data(), sizeof(WorkItem) * i_sn_unf.size(), (void**)&e->items_sn_unf)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_adam_flat.data(), sizeof(WorkItem) * i_adam_flat.size(), (void**)&e->items_adam_flat)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_adam_2d.data(), sizeof(WorkItem) * i_adam_2d.size(), (void**)&e->items_adam_2d)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_ts.data(), sizeof(WorkItem) * i_ts.size(), (void**)&e->items_ts)) return fail(SGV_ERR_HIP, "table upload failed");
+    if (up(i_ss.data(), sizeof(WorkItem) * i_ss.size(), (void**)&e->items_ss)) return fail(SGV_ERR_HIP, "table upload failed");
+    e->n_items_ts = (int)i_ts.size(); e->n_items_ss = (int)i_ss.size();
+    if (hipMalloc((void**)&e->lin_dot_part, sizeof(float) * std::max<size_t>(i_dot.size(), 1)) != hipSuccess) return fail(SGV_ERR_HIP, "hipMalloc failed");
+    for (auto& f : e->fin_lin_dots) f.src = e->lin_dot_part + (size_t)(uintptr_t)f.src;
+    e->n_gnorm_part = (int)std::max(i_adam_flat.size() + i_adam_2d.size(), i_adam.size());
+    if (hipMalloc((void**)&e->gnorm_part, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "hipMalloc failed");
+    if (hipMemset(e->gnorm_part, 0, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "memset failed");
+    e->n_items_sn_unf = (int)i_sn_unf.size(); e->n_items_adam_flat = (int)i_adam_flat.size(); e->n_items_adam_2d = (int)i_adam_2d.size();
+    e->n_items_sn = (int)i_sn.size(); e->n_items_dot = (int)i_dot.size();
+    e->n_items_adam = (int)i_adam.size(); e->n_items_copy = (int)i_copy.size();
+    return 0;
+}
+
+// sgv_create's two calls: what only counts and places (no device memory yet); then, the arenas allocated, pointers and device tables
+int build_layout(sgv_engine* e) {
+    CHK(build_graph(e)); CHK(layout_arenas(e)); CHK(layout_grads(e)); CHK(alloc_activations(e)); CHK(build_tables(e));
+    return 0;
+}
+int build_bind(sgv_engine* e) { rebase_all(e); return upload_tables(e); }

@@ -5,7 +5,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <functional>
 #include <initializer_list>
 #include <map>
 #include <string>
@@ -151,11 +150,7 @@ struct sgv_engine {
     hipStream_t comm_own = nullptr;                   // sgv_comm_stream: a probed communication stream the engine owns
     hipStream_t wire = nullptr; int use_wire = 0;     // callback path: buckets are complete (and packed) on this stream, not on the engine stream
     std::vector<char> bucket_updated;
-    int ddp_early = getenv("SGV_DDP_EARLY") ? atoi(getenv("SGV_DDP_EARLY")) : 1;
-    // the last weight bucket (the first encoder layer: 97 M gradients that exist only when backward ends) is produced, exchanged and
-    // updated in row chunks of the weight-gradient GEMM: chunk c's pack / all-reduce / AdamW run under chunk c + 1's GEMM, so only
-    // the last chunk's exchange is exposed (engine-issued path; SGV_DDP_LAST_CHUNKS=1 turns it off).  Two chunks: 512 rows keep the
-    // GEMM's 128 x 256 tiles at whole rounds of the chip, four chunks of 256 rows cost 27 % of the GEMM
+    int ddp_early = 1;                                // SGV_DDP_EARLY; this and the other environment switches: env_switches (engine.hip)
     // BASELINE configs[3] "+ grad-checkpoint": what recomputing the GroupNorm + GELU outputs in backward would cost.  With the option on,
     // block_bwd regenerates every stage's activation a = act(GN(y)) from the stored pre-normalisation map and statistics right before
     // the stage's backward reads it (one extra streaming pass per stage).  The buffers themselves stay allocated -- this times the
@@ -163,10 +158,14 @@ struct sgv_engine {
     // recompute build would keep); `use_checkpointing` stays forced off as in the reference
     bool recompute_act = false;
     size_t recompute_bytes = 0;
-    int ddp_last_chunks = getenv("SGV_DDP_LAST_CHUNKS") ? atoi(getenv("SGV_DDP_LAST_CHUNKS")) : 2;
-    double ddp_chunk_min_gf = getenv("SGV_DDP_CHUNK_MIN_GF") ? atof(getenv("SGV_DDP_CHUNK_MIN_GF")) : 250.0;   // tests lower it to chunk a small first layer
+    // the last weight bucket (the first encoder layer: 97 M gradients that exist only when backward ends) is produced, exchanged and
+    // updated in row chunks of the weight-gradient GEMM: chunk c's pack / all-reduce / AdamW run under chunk c + 1's GEMM, so only
+    // the last chunk's exchange is exposed (engine-issued path; SGV_DDP_LAST_CHUNKS=1 turns it off).  Two chunks: 512 rows keep the
+    // GEMM's 128 x 256 tiles at whole rounds of the chip, four chunks of 256 rows would cost 27 % of the GEMM
+    int ddp_last_chunks = 2;
+    double ddp_chunk_min_gf = 250.0;                  // SGV_DDP_CHUNK_MIN_GF: tests lower it to chunk a small first layer
     int dw_chunks = 1, dw_chunk_layer = -1;
-    std::function<int(int, int, int, int)> dw_chunk_hook;        // (chunk, chunks, first row, end row) after the chunk's GEMM is enqueued
+    struct GradRelease* release = nullptr;            // non-null only while backward_impl runs: conv_bwd_dw reports each chunk's GEMM to it (after_chunk)
     // bf16 wire format: the conv-weight AdamW reads a packed bucket straight from the averaged bf16 copy (no unpack pass; the fp32
     // arena keeps this rank's own gradients); only the few weights of a bucket that the flat pass updates (Linear heads:
     // bucket_flat_w) are unpacked.  bucket_packed[b]: bit 0 = conv-weight part still packed, bit 1 = flat part still packed.
@@ -222,10 +221,10 @@ struct sgv_engine {
     bool coll_inflight = false;        // data-parallel backward, from the first released bucket on: a collective's channel workgroups may hold CUs
     int* tn_sched = nullptr;           // 8 x 520 ints: work-stealing state of the 256 x 256 weight-gradient launches issued while coll_inflight
     unsigned tn_sched_next = 0;
-    int use_lanes = getenv("SGV_LANES") ? atoi(getenv("SGV_LANES")) : 1;
+    int use_lanes = 1;                 // SGV_LANES
     // small Conv1d -> GroupNorm -> GELU stages in one launch (convgn.hip, K * taps <= CONVGN_MAXK); SGV_CONVGN=0 restores GEMM +
     // combine + GroupNorm kernels
-    int use_convgn = getenv("SGV_CONVGN") ? atoi(getenv("SGV_CONVGN")) : 1;
+    int use_convgn = 1;
     float* red = nullptr; size_t red_floats = 0;
     std::vector<FinDot> fin_dots; std::vector<FinAffine> fin_affine;
     int dot_counts[512];
@@ -248,15 +247,47 @@ struct sgv_engine {
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+#pragma GCC visibility push(hidden)       // shared among the engine's files only: kept out of the library's dynamic symbols
+// The release policy of the gradient buckets, on backward_impl's stack for one backward pass (engine_optim.hip): the transport (none,
+// bucket callback, engine-issued RCCL), the wire format, where a bucket's AdamW runs (`early`: side stream, `dearly`: optimizer
+// stream, or after backward), per-bucket or final Linear <G,W> dots, the early small bucket, the chunked last weight bucket.
+struct GradRelease {
+    sgv_engine* e; float fuse_lr;
+    bool fuse = false, early = false, dearly = false, dots_per_bucket = false, last_chunked = false, lin_err = false;
+    int last_b = -1, L0i = -1, bucket = 0;     // last weight bucket, the first encoder layer, the next weight bucket to release
+    std::vector<hipEvent_t> chunk_done;
+    const char* err = nullptr;                 // the first policy call that failed; a failure ends the work on its bucket, finish() reports it
+    GradRelease(sgv_engine* e_, float lr) : e(e_), fuse_lr(lr) { e->release = this; }  ~GradRelease() { e->release = nullptr; }
+    void failed(const char* what) { if (!err) err = what; }
+    int begin(), gather_on(hipStream_t t);
+    void fire(), fire_at(int b);               // release the next weight bucket / bucket b
+    void flush_fin(bool affine), lin_dots(int b0, int b1);  // fixed-order partial sums; the Linear <G,W> dots of buckets [b0, b1)
+    void release_small();                      // block_bwd: in front of the first encoder layer's weight-gradient GEMM
+    int after_chunk(int c, int n_c, int co0, int co1);      // conv_bwd_dw: (chunk, chunks, first row, end row) after the chunk's GEMM is enqueued
+    int before_first_block(), after_first_block(int br);    // around the first encoder block's backward: chunking on; off, the chunks' updates
+    int finish();                              // the last weight bucket and the tail of the step; backward_impl returns it
+};
+// engine_build.hip
+bool layer_fused_adam(const Layer& l);                                                       // conv weights that train: tiled AdamW
+int build_layout(sgv_engine* e);                                                            // graph, arena layouts, table sizes
+int build_bind(sgv_engine* e);                                                              // arenas allocated: pointers rebased, tables uploaded
+// engine_optim.hip
+bool grad_lp_active(const sgv_engine* e);
+bool wire_lp_active(sgv_engine* e);
+int lp_sync(sgv_engine* e);
+int set_grad_bf16(sgv_engine* e, int value);
+hipEvent_t next_event(sgv_engine* e);                                                       // engine_streams.hip: from the engine's pool (rewound by every backward)
+#pragma GCC visibility pop
+
 // ---- helpers that more than one translation unit calls, under the file that defines them: engine.hip ----
 void sum_slabs(float* out, const float* partial, int splitk, long n, hipStream_t stream);   // out = sum of split-K slabs, fixed order
-int stream_wait(sgv_engine* e, hipStream_t waiter, hipStream_t of);                         // waiter waits for what `of` holds so far
-int join_side(sgv_engine* e);
 size_t entry_param_offset(const sgv_engine* e, const StateEntry& s);                         // float offset of a state entry in the parameter arena
 size_t entry_grad_offset(const sgv_engine* e, const StateEntry& s);                          // ... in the gradient / Adam-moment arenas, NPOS if it gets no gradient
 // engine_ckpt.hip
 void ckpt_release(sgv_engine* e);                                                           // sgv_destroy: staging buffer, tables, copy stream
 // engine_streams.hip
+int stream_wait(sgv_engine* e, hipStream_t waiter, hipStream_t of);                         // waiter waits for what `of` holds so far
+int join_side(sgv_engine* e);
 bool streams_overlap(hipStream_t a, hipStream_t b);
 hipError_t make_aux_stream(hipStream_t* out, const char* label, std::initializer_list<hipStream_t> avoid);
 hipStream_t ensure_opt(sgv_engine* e);

@@ -1,4 +1,5 @@
-// The engine's auxiliary streams: the probe that tells which hardware queue a new stream landed on, and the streams created on first use.
+// The engine's auxiliary streams: the probe that tells which hardware queue a new stream landed on, the streams created on first use,
+// and the event waits that order one stream behind another.
 #include "engine_internal.h"
 
 // Auxiliary streams.  The HIP runtime maps streams onto a handful of hardware queues PER PRIORITY LEVEL (GPU_MAX_HW_QUEUES = 4),
@@ -93,6 +94,29 @@ hipStream_t ensure_opt(sgv_engine* e) { return ensure(&e->opt, "optimizer", {e->
 // would run strictly between the main stream's kernels instead of beside them)
 hipStream_t ensure_comm_own(sgv_engine* e) { return ensure(&e->comm_own, "communication", {e->stream, e->side, e->lane2}); }
 hipStream_t ensure_wire(sgv_engine* e) { return ensure(&e->wire, "wire", {e->stream, e->side}); }
+hipEvent_t next_event(sgv_engine* e) {
+    if (e->ev_next == e->ev_pool.size()) {
+        hipEvent_t ev = nullptr;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr;
+        e->ev_pool.push_back(ev);
+    }
+    return e->ev_pool[e->ev_next++];
+}
+// `waiter` waits for everything enqueued on `of` so far
+int stream_wait(sgv_engine* e, hipStream_t waiter, hipStream_t of) {
+    hipEvent_t ev = next_event(e);
+    if (!ev) return fail(SGV_ERR_HIP, "event creation failed");
+    HIPCHK(hipEventRecord(ev, of));
+    HIPCHK(hipStreamWaitEvent(waiter, ev, 0));
+    return 0;
+}
+// make the main stream wait for every weight-gradient GEMM issued so far on the side stream
+int join_side(sgv_engine* e) {
+    if (!e->side_dirty) return 0;
+    CHK(stream_wait(e, e->stream, e->side));
+    e->side_dirty = false;
+    return 0;
+}
 
 // the three getters of the C ABI: the stream `get` makes or finds goes to *stream; `err` if there is none
 static int stream_out(sgv_engine* e, void** stream, hipStream_t (*get)(sgv_engine*), const char* err) {

@@ -186,6 +186,33 @@ int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch
  * sgv_get_xhat / sgv_get_activation / sgv_backward answer SGV_ERR_STATE until the next sgv_forward / sgv_decode. */
 int sgv_generate(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix,
                  const float* scale_dev, const float* min_dev, int layout, float* out_dev);
+/* Summaries of the field sgv_generate would write, without writing it.  Device pointers, each optional (NULL = not computed),
+ * at least one required; node_* 16-byte aligned, frame_* 8-byte, probes 4-byte:
+ *   node_stats  fp32  [B][3][N]  per sample and node: max over t, min over t, mean over t (fp32 sum, one division by T)
+ *   node_when   int32 [B][2][N]  t of the max, t of the min; the smallest t on a tie
+ *   frame_stats fp32  [B][T][2]  per sample and time step: max over the nodes, min over the nodes
+ *   frame_where int32 [B][T][2]  node of the max, of the min; the smallest node on a tie
+ *   probes      fp32  [B][T][K]  the field at the K nodes of sgv_set_probes
+ * Every value compared is the descaled one, (tanh(GroupNorm(y)) - min_n) / scale_n, bit for bit what sgv_generate stores. */
+typedef struct {
+    float* node_stats;
+    int32_t* node_when;
+    float* frame_stats;
+    int32_t* frame_where;
+    float* probes;
+} sgv_summary_out;
+/* The probe nodes of sgv_summarize: count indices in [0, num_node) on the host, 0 <= count <= 4096 (0 clears the list;
+ * duplicates allowed, order kept).  Checked here, SGV_ERR_ARG names the first offending position; the copy into the engine's
+ * device buffer is enqueued on the engine stream from a copy of the list the engine keeps (nodes_host may be reused on return;
+ * replacing an earlier list waits for the engine stream once, so that its upload has left that copy). */
+int sgv_set_probes(sgv_engine* e, const int32_t* nodes_host, int count);
+/* Decoder.forward(z, xs, mode) as sgv_generate (same arguments, same checks), followed by the summary pass in place of the
+ * field: no atomics, every reduction in a fixed order, two calls on the same inputs are bitwise equal; the frame partials live
+ * in the engine's workspace, nothing is allocated.  SGV_ERR_ARG before anything is enqueued: out NULL, all five outputs NULL,
+ * probes asked for with no probe list set, a misaligned pointer.  Synchronises nothing.  Afterwards there is no forward pass to
+ * read from, as after sgv_generate. */
+int sgv_summarize(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix,
+                  const float* scale_dev, const float* min_dev, const sgv_summary_out* out);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -446,6 +473,13 @@ int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long
  * SGV_LAYOUT_NT [B][C][T], dense and 16-byte aligned; sums [B*G][2] fp64 (written), scale / min [C] fp32. */
 int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, int layout, float* out, int B, int T, int C, void* stream);
+/* The kernels of sgv_summarize on caller-owned buffers: inputs as sgv_test_recon_physical, then the statistics of y and the summary
+ * pass into the outputs of `out` (shapes of sgv_summary_out with N = C).  probes_host: n_probes node indices on the host, checked
+ * as sgv_set_probes checks them (needed when out->probes is given).  SGV_ERR_ARG, nothing launched: a NULL input, out NULL or
+ * all of its outputs NULL, probes without a list, an index outside [0, C), a misaligned pointer. */
+int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                           const float* scale, const float* min, const sgv_summary_out* out, const int32_t* probes_host,
+                           int n_probes, int B, int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

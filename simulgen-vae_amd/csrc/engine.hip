@@ -519,6 +519,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     e->colpart_floats = 0;
     for (auto& g : e->gns) e->colpart_floats = std::max(e->colpart_floats, ew_gn_part_floats(e->maxB, e->T, g.C));
     for (auto& l : e->layers) if (l.op != OP_LINEAR) e->colpart_floats = std::max(e->colpart_floats, ew_gn_part_floats(e->maxB, e->T, l.cout));
+    e->colpart_floats = std::max(e->colpart_floats, ew_recon_summary_work_floats(e->maxB, e->T, e->N));   // sgv_summarize's frame partials (smaller up to T of several hundred)
     e->xpose_floats = (size_t)M * std::max(e->N, 8);
     for (int i = 0; i < e->n; ++i) e->xpose_floats = std::max(e->xpose_floats, (size_t)M * e->enc[i] * 2);
 #define ALLOC(ptr, bytes)                                                                                      \
@@ -599,6 +600,7 @@ int sgv_destroy(sgv_engine* e) {
     for (auto& t : e->timers) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
     if (e->grads_lp) hipFree(e->grads_lp);
     if (e->tn_sched) hipFree(e->tn_sched);
+    if (e->probes_dev) hipFree(e->probes_dev);
     ckpt_release(e);
     delete e;
     return SGV_OK;
@@ -886,8 +888,9 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 }
 
 // Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen` (sgv_generate),
-// the recon head's convolution and statistics followed by the physical-field pass instead of the loss tail.
-struct GenOut { const float* scale; const float* mn; int layout; float* out; };
+// the recon head's convolution and statistics followed by the physical-field pass instead of the loss tail -- or, with gen->sum
+// (sgv_summarize), by the summary pass: its frame partials go to e->colpart, which nothing uses once the statistics are done.
+struct GenOut { const float* scale; const float* mn; int layout; float* out; const ReconSummary* sum = nullptr; };
 static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
@@ -940,7 +943,15 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenO
         CHK(conv_fwd(e, L, e->dec_out[n_st - 1], S.y, M));
         ew_gn_stats(e->dt, p, e->stream);
     }
+    if (gen && gen->sum) {
+        ReconSummary o = *gen->sum;
+        o.work = e->colpart;
+        ScopedTimer tm(e, "recon_summary", nullptr);
+        const int r = ew_recon_summary(e->dt, p, gen->scale, gen->mn, o, e->stream);
+        return r ? fail(SGV_ERR_ARG, "sgv_summarize: the summary pass rejected its arguments (%d)", r) : 0;
+    }
     if (gen) {          // no loss, no read of x_in, no x_hat: the fp32 physical field goes straight to the caller's buffer
+        ScopedTimer tm(e, "recon_phys", nullptr);
         const int r = ew_recon_physical(e->dt, p, gen->scale, gen->mn, gen->layout, gen->out, e->stream);
         return r ? fail(SGV_ERR_ARG, "sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)", r) : 0;
     }
@@ -1029,6 +1040,45 @@ int sgv_generate(sgv_engine* e, const float* z_dev, const float* xs_dev, int bat
     e->have_fwd = false;
     e->fwd_train = false;
     const GenOut gen = {scale_dev, min_dev, layout, out_dev};
+    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
+    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
+    return SGV_OK;
+}
+
+int sgv_set_probes(sgv_engine* e, const int32_t* nodes_host, int count) {
+    if (!e) return fail(SGV_ERR_ARG, "sgv_set_probes: null engine");
+    if (count < 0 || count > SGV_MAX_PROBES) return fail(SGV_ERR_ARG, "sgv_set_probes: count %d outside [0, %d]", count, SGV_MAX_PROBES);
+    if (count > 0 && !nodes_host) return fail(SGV_ERR_ARG, "sgv_set_probes: null node list");
+    const int bad = first_bad_probe(nodes_host, count, e->N);
+    if (bad >= 0) return fail(SGV_ERR_ARG, "sgv_set_probes: nodes[%d] = %d is outside [0, %d)", bad, (int)nodes_host[bad], e->N);
+    if (count > 0) {
+        if (!e->probes_dev) HIPCHK(hipMalloc((void**)&e->probes_dev, sizeof(int32_t) * SGV_MAX_PROBES));
+        // an upload still in flight reads the old vector: let it finish before the storage changes
+        if (!e->probes_host.empty()) HIPCHK(hipStreamSynchronize(e->stream));
+        e->probes_host.assign(nodes_host, nodes_host + count);
+        HIPCHK(hipMemcpyAsync(e->probes_dev, e->probes_host.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, e->stream));
+    }
+    e->n_probes = count;
+    return SGV_OK;
+}
+
+int sgv_summarize(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                  const float* min_dev, const sgv_summary_out* out) {
+    if (!e || !z_dev || !scale_dev || !min_dev || !out) return fail(SGV_ERR_ARG, "sgv_summarize: null argument");
+    if (!out->node_stats && !out->node_when && !out->frame_stats && !out->frame_where && !out->probes)
+        return fail(SGV_ERR_ARG, "sgv_summarize: all five outputs are NULL");
+    if (out->probes && e->n_probes < 1) return fail(SGV_ERR_ARG, "sgv_summarize: probes asked for, but no probe nodes are set (sgv_set_probes)");
+    if ((((uintptr_t)out->node_stats | (uintptr_t)out->node_when) & 15) || (((uintptr_t)out->frame_stats | (uintptr_t)out->frame_where) & 7) ||
+        ((uintptr_t)out->probes & 3))
+        return fail(SGV_ERR_ARG, "sgv_summarize: misaligned output (node_stats / node_when 16 bytes, frame_stats / frame_where 8, probes 4)");
+    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_summarize"));
+    // as sgv_generate: the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
+    e->have_fwd = false;
+    e->fwd_train = false;
+    ReconSummary o;
+    o.node_stats = out->node_stats; o.node_when = out->node_when; o.frame_stats = out->frame_stats; o.frame_where = out->frame_where;
+    o.probes = out->probes; o.probe_nodes = e->probes_dev; o.n_probes = e->n_probes;
+    const GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr, &o};
     CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
     for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
     return SGV_OK;

@@ -175,7 +175,9 @@ struct sgv_engine {
     bool use_side = true, side_dirty = false;
     float* xpose_tmp = nullptr; size_t xpose_floats = 0;
     float* recon_unit = nullptr;   // [3][N] unit-scale dgamma/dbeta/dbias of the recon head
-    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace
+    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace (also the frame partials of sgv_summarize)
+    int* probes_dev = nullptr; int n_probes = 0;           // sgv_set_probes: SGV_MAX_PROBES checked node indices (allocated on first use)
+    std::vector<int32_t> probes_host;                      // the source of the last upload stays alive until the next one
     SNDesc* sn_dev = nullptr; std::vector<SNDesc> sn_host;
     AdamDesc* adam_dev = nullptr; std::vector<AdamDesc> adam_host;
     WorkItem *items_sn = nullptr, *items_dot = nullptr, *items_adam = nullptr, *items_copy = nullptr;
@@ -246,6 +248,12 @@ struct sgv_engine {
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr int SGV_MAX_PROBES = 4096;
+// position of the first probe node outside [0, N), -1 if none (sgv_set_probes, sgv_test_recon_summary)
+static inline int first_bad_probe(const int32_t* nodes, int count, int N) {
+    for (int i = 0; i < count; ++i) if (nodes[i] < 0 || nodes[i] >= N) return i;
+    return -1;
+}
 
 #pragma GCC visibility push(hidden)       // shared among the engine's files only: kept out of the library's dynamic symbols
 // The release policy of the gradient buckets, on backward_impl's stack for one backward pass (engine_optim.hip): the transport (none,

@@ -1241,6 +1241,13 @@ int ew_recon_bwd_apply(int dtype, GNParams p, hipStream_t s) {
 // p.sums exactly as in the eval loss pass (gn_consts; the normalised value is formed as (y - mean) * rstd first, as there).
 // ------------------------------------------------------------------------------------------
 struct ReconPhys { const float* scale; const float* mn; float* out; };
+// One element of the physical field and the reciprocal of its scale: the only place either is written down.  recon_phys_* and
+// recon_summary_* all call these, so a summary is a reduction of bit-identical values.
+__device__ __forceinline__ float recon_phys_val(float y, float mean, float rstd, float gam, float bet, float mn, float inv) {
+    const float xh = (y - mean) * rstd;
+    return (tanh_f(xh * gam + bet) - mn) * inv;
+}
+__device__ __forceinline__ float recon_phys_inv(float scale) { return 1.0f / scale; }      // correctly rounded reciprocal, once per thread
 
 // [B][T][N]: the geometry of gn_apply_kernel, 16-byte loads of y and two 16-byte stores per thread and row
 template <typename T>
@@ -1253,7 +1260,7 @@ __global__ __launch_bounds__(256) void recon_phys_tn_kernel(const GNParams p, co
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         gam[e] = p.gamma[c.c0 + e]; bet[e] = p.beta[c.c0 + e];
-        mn[e] = q.mn[c.c0 + e]; inv[e] = 1.0f / q.scale[c.c0 + e];      // correctly rounded reciprocal, once per thread
+        mn[e] = q.mn[c.c0 + e]; inv[e] = recon_phys_inv(q.scale[c.c0 + e]);
     }
     const T* y = reinterpret_cast<const T*>(p.y);
     for (int t = c.t_lo + c.ty; t < c.t_hi; t += 2 * c.RL) {      // two rows per round, loads first
@@ -1268,10 +1275,7 @@ __global__ __launch_bounds__(256) void recon_phys_tn_kernel(const GNParams p, co
             float v[8];
             raw_unpack(u ? r1 : r0, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xh = (v[e] - mean[e]) * rstd[e];
-                v[e] = (tanh_f(xh * gam[e] + bet[e]) - mn[e]) * inv[e];
-            }
+            for (int e = 0; e < 8; ++e) v[e] = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
             store8(q.out + (u ? m1 : m0) * p.C + c.c0, v);
         }
     }
@@ -1289,7 +1293,7 @@ __global__ __launch_bounds__(256) void recon_phys_nt_kernel(const GNParams p, co
     if (tid < RP_TN && n0 + tid < p.C) {
         const int ch = n0 + tid, g = min(ch / p.Cg, p.G - 1);
         gn_mean_rstd(p, b, g, cst[0][tid], cst[1][tid]);
-        cst[2][tid] = p.gamma[ch]; cst[3][tid] = p.beta[ch]; cst[4][tid] = q.mn[ch]; cst[5][tid] = 1.0f / q.scale[ch];
+        cst[2][tid] = p.gamma[ch]; cst[3][tid] = p.beta[ch]; cst[4][tid] = q.mn[ch]; cst[5][tid] = recon_phys_inv(q.scale[ch]);
     }
     __syncthreads();
     const int r = tid >> 3, cx = (tid & 7) * 8;          // row of the tile, first of this thread's 8 channels
@@ -1300,8 +1304,7 @@ __global__ __launch_bounds__(256) void recon_phys_nt_kernel(const GNParams p, co
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int j = cx + e;
-            const float xh = (v[e] - cst[0][j]) * cst[1][j];
-            tile[j][r] = (tanh_f(xh * cst[2][j] + cst[3][j]) - cst[4][j]) * cst[5][j];
+            tile[j][r] = recon_phys_val(v[e], cst[0][j], cst[1][j], cst[2][j], cst[3][j], cst[4][j], cst[5][j]);
         }
     }
     __syncthreads();
@@ -1328,6 +1331,251 @@ int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn
         const dim3 grid(cdiv_i(p.C, RP_TN), cdiv_i(p.T, RP_TT), p.B);
         if (dtype == 1) hipLaunchKernelGGL((recon_phys_nt_kernel<bf16_t>), grid, dim3(256), 0, s, p, q);
         else hipLaunchKernelGGL((recon_phys_nt_kernel<float>), grid, dim3(256), 0, s, p, q);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate field summaries (sgv_summarize): the same pass as recon_phys_tn_kernel with the stores replaced by reductions of the
+// values it would have stored -- per (sample, node) max / min / mean over t and the t of both extrema, per (sample, t) max / min
+// over the nodes and the node of both, and the time histories at a list of probe nodes.  Every comparison is made on the descaled
+// value (scale_n may be negative).  No atomics: a block owns 8 * CV channels of one sample for ALL rows (no row split), so a
+// node's time axis lies in one block -- its RL row lanes are combined through LDS in lane order; a row's extrema over the block's
+// channels come from an in-wave reduction over the CV lanes of that row and go to a partials workspace [B*T][column blocks], which
+// recon_summary_frames_kernel combines.  (value, index) pairs are ordered by value, then by the smaller index, so the result does
+// not depend on the shape of any tree: ties go to the smallest t / n and two launches are bitwise equal.
+// Geometry: CV = 64 column lanes (one wave per row; fewer for C < 512), RL = 256 / CV row lanes, grid (ceil(C / (8 CV)), 1, B).
+// ------------------------------------------------------------------------------------------
+constexpr int RS_MAX_CV = 64;
+struct RSGeom { int CV, colblocks; };
+static RSGeom rs_geom(int C) {
+    const int nv = C / 8;
+    int cv = 1;
+    while (cv < nv && cv < RS_MAX_CV) cv <<= 1;
+    return {cv, cdiv_i(nv, cv)};
+}
+size_t ew_recon_summary_work_floats(int B, int T, int C) { return (size_t)B * T * rs_geom(C).colblocks * 4; }
+
+// b replaces a when it is the larger (MAX) / smaller value, or the same value at a smaller index
+template <bool MAX>
+__device__ __forceinline__ void ext_take(float& av, int& ai, float bv, int bi) {
+    const bool better = MAX ? bv > av : bv < av;
+    if (better || (bv == av && bi < ai)) { av = bv; ai = bi; }
+}
+constexpr int RS_NO_INDEX = 0x7fffffff;       // index of the neutral element: loses every tie
+// In-wave reduction over the CV lanes of a row (neighbours inside a wave, aligned to CV) with DPP operands -- VALU instructions,
+// no trip through the LDS crossbar: pairs within quads, quads within 8 and 8s within 16 lanes by mirrored exchanges (every lane
+// of a DPP row of 16 then holds that row's result), then lane 15 of each DPP row into the next row and lane 31 into the upper
+// half.  Lanes of DPP rows outside the row mask get their own value back.  The LAST lane of the CV ends up with the result.
+// The pass is VALU-bound, not HBM-bound: reducing (value, index) pairs this way, 4 moves + 12 compare /
+// select per step, cost more than the element arithmetic; so the values are reduced alone, the winner is handed back to the
+// row's lanes, and the smallest index among the lanes that hold it is reduced as an integer minimum.
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v);
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL, ROW_MASK>(__float_as_int(v))); }
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v) {
+    // every lane has a source in the unmasked exchanges: with bound_ctrl set the compiler may fold the move into the instruction that uses it
+    if constexpr (ROW_MASK == 0xF) return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+    else return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xF, false);
+}
+#define RS_LANE_REDUCE(NAME, TYPE, OP, DPP)                                                      \
+    __device__ __forceinline__ TYPE NAME(TYPE v, int cv) {                                       \
+        if (cv > 1) v = OP(v, DPP<0xB1, 0xF>(v));  /* quad_perm [1, 0, 3, 2] */                  \
+        if (cv > 2) v = OP(v, DPP<0x4E, 0xF>(v));  /* quad_perm [2, 3, 0, 1] */                  \
+        if (cv > 4) v = OP(v, DPP<0x141, 0xF>(v)); /* row_half_mirror */                         \
+        if (cv > 8) v = OP(v, DPP<0x140, 0xF>(v)); /* row_mirror */                              \
+        if (cv > 16) v = OP(v, DPP<0x142, 0xA>(v)); /* row_bcast:15 into rows 1 and 3 */         \
+        if (cv > 32) v = OP(v, DPP<0x143, 0xC>(v)); /* row_bcast:31 into rows 2 and 3 */         \
+        return v;                                                                                \
+    }
+RS_LANE_REDUCE(lane_max_f, float, fmaxf, dpp_f)
+RS_LANE_REDUCE(lane_min_f, float, fminf, dpp_f)
+RS_LANE_REDUCE(lane_min_i, int, min, dpp_i)
+#undef RS_LANE_REDUCE
+
+// 4 waves / SIMD asked for: with every output the bf16 kernel sits at 128 VGPRs without scratch (131 and 3 waves unasked; the fp32 one
+// then keeps a few dwords in scratch)
+template <typename T, bool NODE, bool FRAME>
+__global__ __launch_bounds__(256, 4) void recon_summary_kernel(const GNParams p, const ReconPhys q, const ReconSummary o) {
+    const GNCtx c = gn_ctx(p);          // gridDim.y == 1: t_lo = 0, t_hi = T
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);
+    // no early return for the lanes past C: the shuffles and barriers below need every thread; such lanes load nothing and
+    // carry the neutral element
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        gam[e] = c.col_ok ? p.gamma[c.c0 + e] : 0.f; bet[e] = c.col_ok ? p.beta[c.c0 + e] : 0.f;
+        mn[e] = c.col_ok ? q.mn[c.c0 + e] : 0.f; inv[e] = c.col_ok ? recon_phys_inv(q.scale[c.c0 + e]) : 0.f;
+    }
+    float vmax[8], vmin[8], vsum[8];
+    int tmax[8], tmin[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { vmax[e] = -INFINITY; vmin[e] = INFINITY; vsum[e] = 0.f; tmax[e] = RS_NO_INDEX; tmin[e] = RS_NO_INDEX; }
+    const T* y = reinterpret_cast<const T*>(p.y);
+    float4* const fpart = reinterpret_cast<float4*>(o.work);
+    for (int t0 = 0; t0 < p.T; t0 += 2 * c.RL) {          // block-uniform trip count; two rows per round, loads first
+        const int ta = t0 + c.ty, tb = ta + c.RL;
+        const bool oka = c.col_ok && ta < p.T, okb = c.col_ok && tb < p.T;
+        const long m0 = (long)c.b * p.T + ta, m1 = m0 + c.RL;
+        Raw8<T> r0, r1;
+        raw_zero(r0); raw_zero(r1);
+        if (oka) raw_load(y + m0 * p.ldy + c.c0, r0);
+        if (okb) raw_load(y + m1 * p.ldy + c.c0, r1);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool ok = u ? okb : oka;
+            const int t = u ? tb : ta;
+            float fmx = -INFINITY, fmn = INFINITY;
+            int imx = RS_NO_INDEX, imn = RS_NO_INDEX;
+            if (ok) {
+                float v[8];
+                raw_unpack(u ? r1 : r0, v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float x = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+                    if constexpr (NODE) {          // this thread's rows come in ascending t: a strict comparison keeps the first
+                        if (x > vmax[e]) { vmax[e] = x; tmax[e] = t; }
+                        if (x < vmin[e]) { vmin[e] = x; tmin[e] = t; }
+                        vsum[e] += x;
+                    }
+                    if constexpr (FRAME) {         // ascending n
+                        if (x > fmx) { fmx = x; imx = c.c0 + e; }
+                        if (x < fmn) { fmn = x; imn = c.c0 + e; }
+                    }
+                }
+            }
+            if constexpr (FRAME) {
+                // the row's extrema (in the last lane of the CV) back to all of its lanes; a lane that holds one offers its index,
+                // which is the smallest of its 8 channels with that value, and the smallest offer wins
+                const int last = ((int)threadIdx.x & 63) | (p.CV - 1);
+                const float rmx = __shfl(lane_max_f(fmx, p.CV), last, 64), rmn = __shfl(lane_min_f(fmn, p.CV), last, 64);
+                const int rimx = lane_min_i(fmx == rmx ? imx : RS_NO_INDEX, p.CV), rimn = lane_min_i(fmn == rmn ? imn : RS_NO_INDEX, p.CV);
+                if (c.tx == p.CV - 1 && t < p.T)
+                    fpart[((long)c.b * p.T + t) * gridDim.x + blockIdx.x] = make_float4(rmx, __int_as_float(rimx), rmn, __int_as_float(rimn));
+            }
+        }
+    }
+    if constexpr (NODE) {
+        // across the block's row lanes, in lane order; row lane 0 ends up with the result and stores it
+        __shared__ float smv[2048];
+        __shared__ int smi[2048];
+        const int slot = (c.ty * p.CV + c.tx) * 8;
+        const bool owner = c.ty == 0 && c.col_ok;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {          // 0: max, 1: min
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { smv[slot + e] = k ? vmin[e] : vmax[e]; smi[slot + e] = k ? tmin[e] : tmax[e]; }
+            __syncthreads();
+            if (owner) {
+                for (int r = 1; r < c.RL; ++r)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int j = (r * p.CV + c.tx) * 8 + e;
+                        if (k) ext_take<false>(vmin[e], tmin[e], smv[j], smi[j]);
+                        else ext_take<true>(vmax[e], tmax[e], smv[j], smi[j]);
+                    }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) smv[slot + e] = vsum[e];
+        __syncthreads();
+        if (owner) {
+            for (int r = 1; r < c.RL; ++r)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vsum[e] += smv[(r * p.CV + c.tx) * 8 + e];
+            const float ft = (float)p.T;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vsum[e] = vsum[e] / ft;          // the one division of the mean
+            if (o.node_stats) {
+                float* d = o.node_stats + (long)c.b * 3 * p.C + c.c0;
+                store8(d, vmax); store8(d + p.C, vmin); store8(d + 2L * p.C, vsum);
+            }
+            if (o.node_when) {
+                int* d = o.node_when + (long)c.b * 2 * p.C + c.c0;
+                *reinterpret_cast<int4*>(d) = make_int4(tmax[0], tmax[1], tmax[2], tmax[3]);
+                *reinterpret_cast<int4*>(d + 4) = make_int4(tmax[4], tmax[5], tmax[6], tmax[7]);
+                *reinterpret_cast<int4*>(d + p.C) = make_int4(tmin[0], tmin[1], tmin[2], tmin[3]);
+                *reinterpret_cast<int4*>(d + p.C + 4) = make_int4(tmin[4], tmin[5], tmin[6], tmin[7]);
+            }
+        }
+    }
+}
+
+// frame partials [rows = B*T][nblk] of (max, node, min, node) -> frame_stats [rows][2], frame_where [rows][2]; one wave per row
+__global__ __launch_bounds__(256) void recon_summary_frames_kernel(const float4* part, int rows, int nblk, float* frame_stats, int* frame_where) {
+    const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float fmx = -INFINITY, fmn = INFINITY;
+    int imx = RS_NO_INDEX, imn = RS_NO_INDEX;
+    if (row < rows) {          // wave-uniform
+        for (int j = lane; j < nblk; j += 64) {
+            const float4 v = part[(long)row * nblk + j];
+            ext_take<true>(fmx, imx, v.x, __float_as_int(v.y));
+            ext_take<false>(fmn, imn, v.z, __float_as_int(v.w));
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float omx = __shfl_xor(fmx, off, 64), omn = __shfl_xor(fmn, off, 64);
+        const int oimx = __shfl_xor(imx, off, 64), oimn = __shfl_xor(imn, off, 64);
+        ext_take<true>(fmx, imx, omx, oimx);
+        ext_take<false>(fmn, imn, omn, oimn);
+    }
+    if (row < rows && lane == 0) {
+        if (frame_stats) { frame_stats[2L * row] = fmx; frame_stats[2L * row + 1] = fmn; }
+        if (frame_where) { frame_where[2L * row] = imx; frame_where[2L * row + 1] = imn; }
+    }
+}
+
+// probes[b][t][k] = the field at node nodes[k] (checked on the host: 0 <= node < C): 64 probes x 4 rows per block, the
+// per-probe constants once per thread.  mean / rstd go through gn_mean_rstd as in gn_consts, so the values are those of the
+// full pass bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void recon_probe_kernel(const GNParams p, const ReconPhys q, const int* nodes, int K, float* out) {
+    const int k = blockIdx.x * 64 + ((int)threadIdx.x & 63), ty = (int)threadIdx.x >> 6, b = blockIdx.z;
+    if (k >= K) return;
+    const int n = nodes[k];
+    float mean, rstd;
+    gn_mean_rstd(p, b, min(n / p.Cg, p.G - 1), mean, rstd);
+    const float gam = p.gamma[n], bet = p.beta[n], mn = q.mn[n], inv = recon_phys_inv(q.scale[n]);
+    const T* y = reinterpret_cast<const T*>(p.y);
+    for (int t = blockIdx.y * 4 + ty; t < p.T; t += gridDim.y * 4) {
+        const long m = (long)b * p.T + t;
+        out[m * K + k] = recon_phys_val(to_f32(y[m * p.ldy + n]), mean, rstd, gam, bet, mn, inv);
+    }
+}
+
+// p as for ew_recon_physical; o: any subset of the five outputs (ReconSummary, sgv_ew.h), o.work = ew_recon_summary_work_floats
+// floats when a frame output is asked for.  Non-zero (nothing launched): -1 null input, -2 no output, -3 bad shape, -4 a pointer
+// not 16-byte aligned (probes, frame outputs: 4 / 8 bytes), -5 probes without a node list, -6 frame output without workspace
+int ew_recon_summary(int dtype, GNParams p, const float* scale, const float* mn, const ReconSummary& o, hipStream_t s) {
+    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn) return -1;
+    const bool node = o.node_stats || o.node_when, frame = o.frame_stats || o.frame_where;
+    if (!node && !frame && !o.probes) return -2;
+    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.node_stats | (uintptr_t)o.node_when | (uintptr_t)o.work) & 15) return -4;
+    if (((uintptr_t)o.frame_stats | (uintptr_t)o.frame_where) & 7) return -4;
+    if ((uintptr_t)o.probes & 3) return -4;
+    if (o.probes && (!o.probe_nodes || o.n_probes < 1)) return -5;
+    if (frame && !o.work) return -6;
+    p.Cg = p.C / p.G;
+    const ReconPhys q = {scale, mn, nullptr};
+    if (node || frame) {
+        const RSGeom g = rs_geom(p.C);
+        p.CV = g.CV;
+        const dim3 grid(g.colblocks, 1, p.B);
+#define RS_LAUNCH(TT, NODE, FRAME) hipLaunchKernelGGL((recon_summary_kernel<TT, NODE, FRAME>), grid, dim3(256), 0, s, p, q, o)
+        if (dtype == 1) { if (node && frame) RS_LAUNCH(bf16_t, true, true); else if (node) RS_LAUNCH(bf16_t, true, false); else RS_LAUNCH(bf16_t, false, true); }
+        else { if (node && frame) RS_LAUNCH(float, true, true); else if (node) RS_LAUNCH(float, true, false); else RS_LAUNCH(float, false, true); }
+#undef RS_LAUNCH
+        if (frame)
+            hipLaunchKernelGGL(recon_summary_frames_kernel, dim3(cdiv_i((long)p.B * p.T, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(o.work),
+                               p.B * p.T, g.colblocks, o.frame_stats, o.frame_where);
+    }
+    if (o.probes) {
+        const dim3 grid(cdiv_i(o.n_probes, 64), std::min(cdiv_i(p.T, 4), 64), p.B);
+        if (dtype == 1) hipLaunchKernelGGL((recon_probe_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
+        else hipLaunchKernelGGL((recon_probe_kernel<float>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
     }
     return 0;
 }

@@ -112,6 +112,18 @@ int ew_recon_bwd_apply(int dtype, GNParams p, hipStream_t s);
 // recon head -> physical-unit fp32 field: out = (tanh(GroupNorm(y)) - mn) / scale per channel; layout 0 [B][T][C], 1 [B][C][T] (dense).
 // Non-zero (nothing launched): -1 null pointer, -2 unknown layout, -3 bad shape, -4 y or out not 16-byte aligned
 int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn, int layout, float* out, hipStream_t s);
+// recon head -> summaries of the physical field, the field itself never stored (same p, scale, mn as ew_recon_physical).  Any subset of
+// the outputs, null = not computed: node_stats fp32 [B][3][C] (max, min, mean over t), node_when int32 [B][2][C] (t of max, of
+// min; smallest t on a tie), frame_stats fp32 [B][T][2] (max, min over the channels), frame_where int32 [B][T][2] (their
+// channel; smallest on a tie), probes fp32 [B][T][n_probes] (the field at probe_nodes[k], device int32, each in [0, C): the
+// caller has checked them).  work: ew_recon_summary_work_floats floats, 16-byte aligned, needed for a frame output.
+struct ReconSummary {
+    float* node_stats = nullptr; int* node_when = nullptr; float* frame_stats = nullptr; int* frame_where = nullptr; float* probes = nullptr;
+    const int* probe_nodes = nullptr; int n_probes = 0;
+    float* work = nullptr;
+};
+size_t ew_recon_summary_work_floats(int B, int T, int C);
+int ew_recon_summary(int dtype, GNParams p, const float* scale, const float* mn, const ReconSummary& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

@@ -268,6 +268,50 @@ int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, co
     hipFree(work);
     return rc;
 }
+int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                           const float* scale, const float* min, const sgv_summary_out* out, const int32_t* probes_host,
+                           int n_probes, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_summary";
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
+    if (!y || !sums || !gamma || !beta || !scale || !min || !out) return fail(SGV_ERR_ARG, "%s: null argument", me);
+    if (!out->node_stats && !out->node_when && !out->frame_stats && !out->frame_where && !out->probes)
+        return fail(SGV_ERR_ARG, "%s: all five outputs are NULL", me);
+    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
+    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
+    if (out->probes && (!probes_host || n_probes < 1)) return fail(SGV_ERR_ARG, "%s: probes asked for, but no probe nodes are given", me);
+    if (!out->probes) n_probes = 0;
+    if (n_probes > SGV_MAX_PROBES) return fail(SGV_ERR_ARG, "%s: %d probe nodes, at most %d", me, n_probes, SGV_MAX_PROBES);
+    const int bad = first_bad_probe(probes_host, n_probes, C);
+    if (bad >= 0) return fail(SGV_ERR_ARG, "%s: probe nodes[%d] = %d is outside [0, %d)", me, bad, (int)probes_host[bad], C);
+    if (((uintptr_t)y & 15) || (((uintptr_t)out->node_stats | (uintptr_t)out->node_when) & 15) ||
+        (((uintptr_t)out->frame_stats | (uintptr_t)out->frame_where) & 7) || ((uintptr_t)out->probes & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (y, node_stats / node_when 16 bytes, frame_stats / frame_where 8, probes 4)", me);
+    GNParams p;
+    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
+    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
+    p.y = y; p.ldy = ldy; p.sums = sums;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t stat_floats = align_up(ew_gn_part_floats(B, T, C), 4);          // [statistics workspace | frame partials | probe nodes]
+    const size_t frame_floats = ew_recon_summary_work_floats(B, T, C);
+    float* work = nullptr;
+    HIPCHK(hipMalloc((void**)&work, sizeof(float) * (stat_floats + frame_floats + (size_t)n_probes)));
+    p.part = work;
+    ReconSummary o;
+    o.node_stats = out->node_stats; o.node_when = out->node_when; o.frame_stats = out->frame_stats; o.frame_where = out->frame_where;
+    o.probes = out->probes; o.work = work + stat_floats;
+    if (n_probes) {
+        o.probe_nodes = reinterpret_cast<const int*>(work + stat_floats + frame_floats); o.n_probes = n_probes;
+        if (hipMemcpy(work + stat_floats + frame_floats, probes_host, sizeof(int32_t) * n_probes, hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(work);
+            return fail(SGV_ERR_HIP, "%s: the probe nodes could not be copied to the device", me);
+        }
+    }
+    int r = ew_gn_stats(dtype, p, s);
+    if (!r) r = ew_recon_summary(dtype, p, scale, min, o, s);
+    const int rc = ew_hook_done(r, me, stream);
+    hipFree(work);
+    return rc;
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

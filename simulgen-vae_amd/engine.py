@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -56,6 +56,14 @@ class OptsetEntry(C.Structure):
                 ("wc", C.c_void_p), ("wct", C.c_void_p), ("g_bf16", C.c_void_p), ("tiled", C.c_int32), ("active", C.c_int32)]
 
 
+class SummaryOut(C.Structure):
+    """sgv_summary_out (include/sgvae.h): the five optional outputs of sgv_summarize, device pointers"""
+    _fields_ = [("node_stats", C.c_void_p), ("node_when", C.c_void_p), ("frame_stats", C.c_void_p), ("frame_where", C.c_void_p),
+                ("probes", C.c_void_p)]
+
+
+MAX_PROBES = 4096
+SUMMARY_PARTS = ("node", "frame", "probes")      # `want` of Engine.summarize
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")      # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -103,6 +111,8 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_encode.argtypes = [vp, vp, vp, vp]
     lib.sgv_decode.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.sgv_generate.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.sgv_set_probes.argtypes = [vp, vp, i32]
+    lib.sgv_summarize.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.POINTER(SummaryOut)]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -165,6 +175,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_loss.argtypes = [i32, i32, i32, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, vp, vp, f32, vp, lg, vp, vp, vp, sz,
                                         i32, i32, i32, i32, vp]
     lib.sgv_test_recon_physical.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
+    lib.sgv_test_recon_summary.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, C.POINTER(SummaryOut), vp, i32, i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -219,6 +230,7 @@ class Engine:
         self.n_kl = len(cfg.num_filter_enc) - 1
         self.batch = 0
         self._cb = None
+        self.n_probes = 0
 
     def close(self):
         if getattr(self, "h", None):
@@ -409,14 +421,9 @@ class Engine:
         t = self.torch
         if layout not in LAYOUTS:
             raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, not {layout!r}")
-        B, N, T = z.shape[0], self.cfg.num_node, self.cfg.num_time
-        z = z.to(device="cuda", dtype=t.float32).contiguous()
-        xs_t = (xs if t.is_tensor(xs) else t.stack([x.to(device="cuda", dtype=t.float32) for x in xs])).to(device="cuda", dtype=t.float32).contiguous()
-        if tuple(xs_t.shape) != (self.n_kl, B, self.cfg.hierarchical_dim):
-            raise ValueError(f"xs of shape {tuple(xs_t.shape)}, expected {(self.n_kl, B, self.cfg.hierarchical_dim)}")
-        for name, v in (("scale", scale), ("min", min)):
-            if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == N):
-                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
+        N, T = self.cfg.num_node, self.cfg.num_time
+        B, z, xs_t = self._latents(z, xs)
+        self._scaler(scale, min)
         shape = (B, T, N) if layout == "TN" else (B, N, T)
         if out is None:
             out = t.empty(shape, dtype=t.float32, device="cuda")
@@ -427,6 +434,73 @@ class Engine:
                                                C.c_void_p(out.data_ptr())), "sgv_generate")
         self.batch = B
         return out
+
+    def _latents(self, z, xs):
+        """the checks generate and summarize share: z [B, latent] and xs as fp32 CUDA tensors"""
+        t = self.torch
+        B = z.shape[0]
+        z = z.to(device="cuda", dtype=t.float32).contiguous()
+        xs_t = (xs if t.is_tensor(xs) else t.stack([x.to(device="cuda", dtype=t.float32) for x in xs])).to(device="cuda", dtype=t.float32).contiguous()
+        if tuple(xs_t.shape) != (self.n_kl, B, self.cfg.hierarchical_dim):
+            raise ValueError(f"xs of shape {tuple(xs_t.shape)}, expected {(self.n_kl, B, self.cfg.hierarchical_dim)}")
+        return B, z, xs_t
+
+    def _scaler(self, scale, min):
+        t, N = self.torch, self.cfg.num_node
+        for name, v in (("scale", scale), ("min", min)):
+            if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == N):
+                raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
+
+    def set_probes(self, nodes):
+        """The probe nodes of summarize(): a 1-D integer sequence of at most MAX_PROBES node indices in [0, num_node); an empty
+        one clears the list.  Duplicates are allowed and the order is kept (include/sgvae.h: sgv_set_probes)."""
+        a = np.asarray(nodes)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"probe nodes must be integers, not {a.dtype}")
+        if a.ndim != 1:
+            raise ValueError(f"probe nodes must be 1-D, got shape {a.shape}")
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError("probe nodes do not fit int32")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        _check(self.lib, self.lib.sgv_set_probes(self.h, a.ctypes.data_as(C.c_void_p), int(a.size)), "sgv_set_probes")
+        self.n_probes = int(a.size)
+
+    def summarize(self, z, xs, scale, min, fix=True, want=SUMMARY_PARTS, out=None):
+        """Summaries of the field generate() would write, computed by the recon head's last pass itself; the field is never stored.
+        Same inputs and checks as generate().  want: any of "node", "frame", "probes".  Returns a dict of CUDA tensors:
+        node_stats fp32 [B, 3, N] (max, min, mean over t) and node_when int32 [B, 2, N] (t of max, of min);
+        frame_stats fp32 [B, T, 2] (max, min over the nodes) and frame_where int32 [B, T, 2] (their node);
+        probes fp32 [B, T, K] at the nodes of set_probes().  Ties go to the smallest index.  out: a dict of such tensors to
+        write into (those present are reused).  Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        want = tuple(want)
+        if not want or any(w not in SUMMARY_PARTS for w in want):
+            raise ValueError(f"want must name at least one of {SUMMARY_PARTS}, not {want!r}")
+        if "probes" in want and self.n_probes < 1:
+            raise ValueError("want includes 'probes', but no probe nodes are set (set_probes)")
+        B, z, xs_t = self._latents(z, xs)
+        self._scaler(scale, min)
+        N, T = self.cfg.num_node, self.cfg.num_time
+        shapes = {}
+        if "node" in want:
+            shapes.update(node_stats=((B, 3, N), t.float32), node_when=((B, 2, N), t.int32))
+        if "frame" in want:
+            shapes.update(frame_stats=((B, T, 2), t.float32), frame_where=((B, T, 2), t.int32))
+        if "probes" in want:
+            shapes.update(probes=((B, T, self.n_probes), t.float32))
+        res = {}
+        for name, (shape, dt) in shapes.items():
+            v = None if out is None else out.get(name)
+            if v is None:
+                v = t.empty(shape, dtype=dt, device="cuda")
+            elif not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
+                raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
+            res[name] = v
+        so = SummaryOut(**{name: v.data_ptr() for name, v in res.items()})
+        _check(self.lib, self.lib.sgv_summarize(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
+                                                C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), C.byref(so)), "sgv_summarize")
+        self.batch = B
+        return res
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

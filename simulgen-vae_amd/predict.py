@@ -15,6 +15,8 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     s = Surrogate.from_files("model_save", batch=16)
     fields = s.predict(conditions)                 # [P, T, N] fp32 on the device, physical units
     fields = s.predict_to_host(conditions)         # the same in pinned host memory, for P too large for the device
+    summary = s.sweep(conditions, probes=[17, 4711])   # extrema per node / per time step, their indices, means, probe histories
+                                                   # (DESIGN.md section 17): the fields are reduced by the pass that would store them
 """
 from __future__ import annotations
 
@@ -47,6 +49,36 @@ def scaler_vectors(scaler, name, length, what):
     if bad.size:
         raise ValueError(f"{name}: min_[{int(bad[0])}] = {mn[bad[0]]!r} is not finite")
     return s32, mn.astype(np.float32)
+
+
+MAX_PROBES = 4096          # SGV_MAX_PROBES of the engine
+
+
+def probe_nodes(nodes, num_node):
+    """The probe list of Surrogate.sweep as an int32 vector: a 1-D array of integer dtype with 1 to MAX_PROBES entries, each in
+    [0, num_node).  Duplicates are allowed and the order is kept.  ValueError naming the first bad position otherwise.  numpy only."""
+    a = np.asarray(nodes)
+    if a.ndim != 1:
+        raise ValueError(f"probes: a 1-D array of node indices is required, got shape {a.shape}")
+    if a.size < 1 or a.size > MAX_PROBES:
+        raise ValueError(f"probes: {a.size} entries, between 1 and {MAX_PROBES} are required")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"probes: an integer dtype is required, not {a.dtype}")
+    bad = np.flatnonzero((a < 0) | (a >= num_node))
+    if bad.size:
+        raise ValueError(f"probes[{int(bad[0])}] = {int(a[bad[0]])} is outside [0, {int(num_node)})")
+    return a.astype(np.int32)
+
+
+class SweepResult:
+    """Surrogate.sweep's result for P conditions, device tensors: node_max / node_min / node_mean [P, N] fp32 and t_max / t_min
+    [P, N] int32 (extrema over time per node, the time step of each, the mean over time); frame_max / frame_min [P, T] fp32 and
+    n_max / n_min [P, T] int32 (extrema over the mesh per time step and their node); probes [P, T, K] fp32 or None."""
+    FIELDS = ("node_max", "node_min", "node_mean", "t_max", "t_min", "frame_max", "frame_min", "n_max", "n_min", "probes")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
 
 
 class Surrogate:
@@ -112,8 +144,8 @@ class Surrogate:
                 loaded[k] = pickle.load(f)
         return cls(vae, loaded["conditioner"], loaded["latent_scaler"], loaded["xs_scaler"], loaded["data_scaler"], **kw)
 
-    # ---- one batch: conditions [b, F] -> the field, written into `dst` ([b, T, N] or [b, N, T]) on the engine stream ----
-    def _generate(self, cond, dst, layout, fix, remap):
+    # ---- one batch: conditions [b, F] -> the decoder's latents (z [b, latent], xs [n_levels - 1, b, hier]) on the engine stream ----
+    def _latents(self, cond, remap):
         from . import ops
         y = self.conditioner(cond, remap=remap) if self._takes_remap else self.conditioner(cond)
         y1, y2 = (y["latent_main"], y["xs"]) if isinstance(y, dict) else y          # a conditioner built with return_dict=True
@@ -121,7 +153,11 @@ class Surrogate:
         lat = ops.cols_sub_div(y1.contiguous(), self.lat_min, self.lat_scale)
         xs = ops.cols_sub_div(y2.reshape(b, -1).contiguous(), self.xs_min, self.xs_scale)
         # list order of ReconstructionEvaluator._reconstruct_from_latents: xs_list[k] = columns k*d .. (k+1)*d
-        xs = xs.view(b, self.size2, self.hier).transpose(0, 1).contiguous()
+        return lat, xs.view(b, self.size2, self.hier).transpose(0, 1).contiguous()
+
+    # ... -> the field, written into `dst` ([b, T, N] or [b, N, T])
+    def _generate(self, cond, dst, layout, fix, remap):
+        lat, xs = self._latents(cond, remap)
         self.eng.generate(lat, xs, self.data_scale, self.data_min, out=dst, layout=layout, fix=fix)
 
     def _args(self, conditions, layout, mode):
@@ -168,6 +204,45 @@ class Surrogate:
         if t.cuda.current_stream() != self._stream:
             t.cuda.current_stream().wait_stream(self._stream)
         return out
+
+    def sweep(self, conditions, probes=None, mode="fix"):
+        """What a design study keeps of predict(conditions), without the fields: a SweepResult of device tensors -- per condition
+        and node the extrema over time, when they happen and the mean; per condition and time step the extrema over the mesh and
+        where they are; with `probes` (node indices, see probe_nodes) the time histories there.  The recon head's last pass reduces
+        the values predict() would store (bit for bit the same, ties to the smallest index), so 20 N + 16 T bytes per condition
+        leave the decoder instead of 4 T N.  Batching, streams, the single input-range decision and `mode` are predict()'s: no
+        host wait between batches; the engine writes per-batch buffers and the copies into the [P, ...] results run on its stream."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        want = ("node", "frame") + (("probes",) if probes is not None else ())
+        if probes is not None:
+            self.eng.set_probes(probe_nodes(probes, self.N))
+        K = self.eng.n_probes if probes is not None else 0
+        f32 = dict(dtype=t.float32, device="cuda")
+        i32 = dict(dtype=t.int32, device="cuda")
+        node, when = t.empty((3, P, self.N), **f32), t.empty((2, P, self.N), **i32)          # the results: the caller's stream owns them
+        frame, where = t.empty((2, P, self.T), **f32), t.empty((2, P, self.T), **i32)
+        hist = t.empty((P, self.T, K), **f32) if probes is not None else None
+        self._stream.wait_stream(t.cuda.current_stream())
+        with t.cuda.stream(self._stream):
+            b0 = min(self.batch, max(P, 1))
+            buf = dict(node_stats=t.empty((b0, 3, self.N), **f32), node_when=t.empty((b0, 2, self.N), **i32),
+                       frame_stats=t.empty((b0, self.T, 2), **f32), frame_where=t.empty((b0, self.T, 2), **i32))
+            for lo in range(0, P, self.batch):
+                hi = min(P, lo + self.batch)
+                lat, xs = self._latents(self._batch(conditions, lo, hi), remap)
+                out = {k: v[:hi - lo] for k, v in buf.items()}
+                if hist is not None:
+                    out["probes"] = hist[lo:hi]                  # [b, T, K] is the result's own layout: written in place
+                self.eng.summarize(lat, xs, self.data_scale, self.data_min, fix=mode == "fix", want=want, out=out)
+                node[:, lo:hi].copy_(out["node_stats"].transpose(0, 1))
+                when[:, lo:hi].copy_(out["node_when"].transpose(0, 1))
+                frame[:, lo:hi].copy_(out["frame_stats"].permute(2, 0, 1))
+                where[:, lo:hi].copy_(out["frame_where"].permute(2, 0, 1))
+        if t.cuda.current_stream() != self._stream:
+            t.cuda.current_stream().wait_stream(self._stream)
+        return SweepResult(node_max=node[0], node_min=node[1], node_mean=node[2], t_max=when[0], t_min=when[1],
+                           frame_max=frame[0], frame_min=frame[1], n_max=where[0], n_min=where[1], probes=hist)
 
     def predict_to_host(self, conditions, out=None, layout="TN", mode="fix"):
         """The same result in pinned host memory: two device batch buffers alternate, each batch's device-to-host copy runs on the

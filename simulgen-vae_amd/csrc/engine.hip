@@ -580,9 +580,9 @@ int sgv_destroy(sgv_engine* e) {
     if (!e) return SGV_OK;
     hipStreamSynchronize(e->stream);
     void* ptrs[] = {e->params, e->grads, e->adam_m, e->adam_v, e->copies, e->act, e->stats, e->sn_tmp, e->sn_sigma, e->sn_dot_dummy,
-                    e->scal, e->partial, e->partial_tn, e->partial2, e->colpart2, e->gn_part2, e->gn_part, e->red, e->xpose_tmp, e->colpart, e->sn_dev, e->adam_dev, e->items_sn, e->items_dot, e->items_adam, e->items_copy,
-                    e->items_sn_unf, e->items_adam_flat, e->items_adam_2d, e->items_ts, e->items_ss, e->lin_dot_part, e->gnorm_part};
+                    e->scal, e->partial, e->partial_tn, e->partial2, e->colpart2, e->gn_part2, e->gn_part, e->red, e->xpose_tmp, e->colpart};
     for (void* p : ptrs) if (p) hipFree(p);
+    e->tab.release();
     if (e->side) { hipStreamSynchronize(e->side); hipStreamDestroy(e->side); }
     if (e->opt) { hipStreamSynchronize(e->opt); hipStreamDestroy(e->opt); }
     if (e->wire) { hipStreamSynchronize(e->wire); hipStreamDestroy(e->wire); }
@@ -673,7 +673,7 @@ static const StateEntry* find_entry(sgv_engine* e, const char* name) {
 }
 
 static int refresh_copies(sgv_engine* e) {
-    int r = opt_make_copies(e->adam_dev, e->items_copy, e->n_items_copy, e->dt, e->stream);
+    int r = opt_make_copies(e->tab.adam_dev, e->tab.dev[OptTables::COPY], e->tab.n(OptTables::COPY), e->dt, e->stream);
     if (r) return fail(SGV_ERR_HIP, "make_copies launch failed");
     e->copies_fresh = true;
     return 0;
@@ -683,10 +683,10 @@ static int run_sn(sgv_engine* e, int train) {
     // tpart of the fused layers may already hold the 64-row-block partials of W^T u from the last AdamW pass (still valid:
     // neither W nor u changed since); eval forwards never read or clobber it
     const bool reuse = train && e->wtu_fresh;
-    const WorkItem* it1 = reuse ? e->items_sn_unf : e->items_sn;
-    const int n1 = reuse ? e->n_items_sn_unf : e->n_items_sn;
-    if (opt_sn_power_iteration(e->sn_dev, it1, n1, e->items_sn, e->n_items_sn, e->items_ts, e->n_items_ts, e->items_ss, e->n_items_ss,
-                               (int)e->layers.size(), train, e->stream))
+    const OptTables& t = e->tab;
+    const OptTables::List l1 = reuse ? OptTables::SN_UNF : OptTables::SN;
+    if (opt_sn_power_iteration(t.sn_dev, t.dev[l1], t.n(l1), t.dev[OptTables::SN], t.n(OptTables::SN), t.dev[OptTables::TSUM], t.n(OptTables::TSUM),
+                               t.dev[OptTables::SSUM], t.n(OptTables::SSUM), (int)e->layers.size(), train, e->stream))
         return fail(SGV_ERR_HIP, "spectral-norm launch failed");
     if (train) e->wtu_fresh = false;     // u moved
     return 0;

@@ -422,88 +422,44 @@ static int build_tables(sgv_engine* e) {
         if (l.need_wct) { l.wct = nc; nc = align_up(nc + (size_t)l.nw(), 8); }
     }
     e->n_copies = nc;
-    // SN scratch
-    size_t nt = 0;
+    // SN scratch: four blocks per layer (sn_scratch_carve)
+    e->n_sn_tmp = 0;
     int si = 0;
-    for (auto& l : e->layers) { l.sn = si++; if (layer_fused_adam(l)) nt += align_up((size_t)l.cin * l.k, 4); }
-    e->n_sn_tmp_fused = nt;
-    for (auto& l : e->layers) if (!layer_fused_adam(l)) nt += align_up((size_t)l.cin * l.k, 4);
-    e->sn_tmp_s_off = nt;
-    for (auto& l : e->layers) nt += align_up((size_t)l.cout, 4);
-    e->sn_tpart_off.clear(); e->sn_spart_off.clear();
-    for (auto& l : e->layers) {
-        e->sn_tpart_off.push_back(nt);
-        nt += align_up(sn_tpart_floats(l.k, l.cout, l.cin), 4);
-        e->sn_spart_off.push_back(nt);
-        nt += align_up(sn_spart_floats(l.k, l.cout, l.cin), 4);
-    }
-    e->n_sn_tmp = nt;
+    for (auto& l : e->layers) { l.sn = si++; e->n_sn_tmp += sn_scratch_floats(l.k, l.cout, l.cin); }
     return 0;
 }
 
 static int upload_tables(sgv_engine* e) {
+    OptTables& t = e->tab;
     const int L = (int)e->layers.size();
-    e->sn_host.resize(L);
-    size_t to_f = 0, to_u = e->n_sn_tmp_fused, to_s = e->sn_tmp_s_off;
-    std::vector<WorkItem> i_sn, i_sn_unf, i_dot, i_adam, i_adam_flat, i_adam_2d, i_copy, i_ts, i_ss;
-    e->fin_lin_dots.clear();
     const int nbk = (int)e->buckets.size();
-    std::vector<std::vector<WorkItem>> flat_b(nbk), tile_b(nbk), dot_b(nbk);
-    std::vector<std::vector<FinDot>> fin_lin_b(nbk);
     auto bucket_of = [&](size_t goff) {
         for (int b = 0; b < nbk; ++b) if (goff >= e->buckets[b].first && goff < e->buckets[b].first + e->buckets[b].second) return b;
         return nbk - 1;
     };
+    float* scratch = e->sn_tmp;
     for (int i = 0; i < L; ++i) {
         Layer& l = e->layers[i];
         SNDesc d;
         d.W = e->params + l.w; d.u = e->params + l.u; d.v = e->params + l.v;
-        size_t& to_t = layer_fused_adam(l) ? to_f : to_u;
-        d.tmp_t = e->sn_tmp + to_t; to_t += align_up((size_t)l.cin * l.k, 4);
-        d.tmp_s = e->sn_tmp + to_s; to_s += align_up((size_t)l.cout, 4);
-        d.tpart = e->sn_tmp + e->sn_tpart_off[i]; d.spart = e->sn_tmp + e->sn_spart_off[i];
+        d.taps = l.k; d.rows = l.cout; d.cols = l.cin; d.active = l.used ? 1 : 0;
+        sn_scratch_carve(d, scratch);
         d.sigma = e->sn_sigma + 2 * i;
         d.dot = l.has_grad ? e->grads + l.gdot : e->sn_dot_dummy;
         d.G = l.has_grad ? e->grads + l.gw : nullptr;
-        d.wc = (e->dt == SGV_DTYPE_BF16 && l.wc != NPOS && l.cin % 8 == 0) ? (const void*)(e->copies + l.wc * e->esz) : nullptr;
-        d.taps = l.k; d.rows = l.cout; d.cols = l.cin; d.active = l.used ? 1 : 0;
-        e->sn_host[i] = d;
-        if (l.used) {
-            for (int c = 0; c < sn_gemv_items(l.k, l.cout, l.cin); ++c) { i_sn.push_back({i, c}); if (!layer_fused_adam(l)) i_sn_unf.push_back({i, c}); }
-            for (int c = 0; c < sn_tsum_items(l.k, l.cin); ++c) i_ts.push_back({i, c});
-            for (int c = 0; c < sn_ssum_items(l.cout); ++c) i_ss.push_back({i, c});
-        }
-        if (l.has_grad && l.op == OP_LINEAR) {   // conv layers get <G,W_eff> from their dY kernels (ew.hip)
-            const long nch = opt_flat_items(l.nw());
-            const int bk = bucket_of(l.gw);
-            fin_lin_b[bk].push_back({(const float*)(uintptr_t)dot_b[bk].size(), e->grads + l.gdot, (int)nch, 0});   // src = index inside the bucket for now, rebased below
-            for (long c = 0; c < nch; ++c) dot_b[bk].push_back({i, (int)c});
-        }
+        d.wc = sn_compute_copy(e->dt == SGV_DTYPE_BF16, l.wc != NPOS ? e->copies + l.wc * e->esz : nullptr, l.cin);
+        // conv layers get <G,W_eff> from their dY kernels (ew.hip).  The Linear layers' <G,W> items go by gradient bucket: a data-parallel
+        // backward computes a bucket's share before the bucket is released (the collective may reduce the bucket's gradients in place
+        // while backward goes on)
+        const bool lin = l.has_grad && l.op == OP_LINEAR;
+        t.add_sn(d, layer_fused_adam(l), lin, lin ? bucket_of(l.gw) : 0);
     }
-    // Linear <G,W> items sorted by gradient bucket: a data-parallel backward computes a bucket's share before the bucket is
-    // released (the collective may reduce the bucket's gradients in place while backward goes on)
-    e->dot_off.assign(nbk + 1, 0); e->fin_lin_off.assign(nbk + 1, 0);
-    for (int b = 0; b < nbk; ++b) {
-        for (auto f : fin_lin_b[b]) { f.src = (const float*)((uintptr_t)f.src + i_dot.size()); e->fin_lin_dots.push_back(f); }
-        i_dot.insert(i_dot.end(), dot_b[b].begin(), dot_b[b].end());
-        e->dot_off[b + 1] = (int)i_dot.size(); e->fin_lin_off[b + 1] = (int)e->fin_lin_dots.size();
-    }
-    // the small bucket (which carries these scalars) is released before the last weight bucket: that one must hold no Linear layer
-    if (nbk >= 2 && e->dot_off[nbk] != e->dot_off[nbk - 2]) return fail(SGV_ERR_STATE, "a Linear layer sits in the last weight bucket");
-    e->adam_host.clear();
     auto add_adam = [&](size_t p, size_t g, long n, int sn, int rows, int cols, int taps, void* wc, void* wct, bool tiled = false) {
         AdamDesc a;
         a.p = e->params + p; a.g = e->grads + g; a.m = e->adam_m + g; a.v = e->adam_v + g;
         a.n = n; a.sn = sn; a.rows = rows; a.cols = cols; a.taps = taps; a.wc = wc; a.wct = wct;
         a.glp = nullptr;                 // option grad_bf16 points it at the bf16 mirror arena
-        const int id = (int)e->adam_host.size();
-        e->adam_host.push_back(a);
-        const long nch = opt_flat_items(n);
-        const int bk = bucket_of(g);
-        for (long c = 0; c < nch; ++c) { i_adam.push_back({id, (int)c}); if (!tiled) flat_b[bk].push_back({id, (int)c}); }
-        if (tiled)
-            for (int c = 0; c < opt_tile_items(taps, rows, cols); ++c) tile_b[bk].push_back({id, c});
-        return id;
+        return t.add_adam(a, tiled, bucket_of(g));
     };
     for (int i = 0; i < L; ++i) {
         Layer& l = e->layers[i];
@@ -518,10 +474,9 @@ static int upload_tables(sgv_engine* e) {
             if (id < 0) {   // used-in-forward but frozen layers never occur for convs; keep general
                 AdamDesc a; memset(&a, 0, sizeof(a));
                 a.p = e->params + l.w; a.n = l.nw(); a.sn = -1; a.rows = l.cout; a.cols = l.cin; a.taps = l.k; a.wc = wc; a.wct = wct;
-                id = (int)e->adam_host.size();
-                e->adam_host.push_back(a);
+                id = t.add_adam(a, false);      // no gradient: the descriptor gets no optimizer items
             }
-            for (int c = 0; c < opt_copy_items(l.k, l.cout, l.cin); ++c) i_copy.push_back({id, c});
+            t.add_copy(id);
         }
     }
     for (auto& g : e->gns) {
@@ -529,40 +484,12 @@ static int upload_tables(sgv_engine* e) {
         add_adam(g.gamma, g.ggamma, g.C, -1, 1, g.C, 1, nullptr, nullptr);
         add_adam(g.beta, g.gbeta, g.C, -1, 1, g.C, 1, nullptr, nullptr);
     }
+    t.finish(nbk);
+    // the small bucket (which carries the <G,W> scalars) is released before the last weight bucket: that one must hold no Linear layer
+    if (nbk >= 2 && t.dot_off[nbk] != t.dot_off[nbk - 2]) return fail(SGV_ERR_STATE, "a Linear layer sits in the last weight bucket");
     e->bucket_flat_w.assign(nbk, {});
     for (auto& l : e->layers) if (l.has_grad && !layer_fused_adam(l)) e->bucket_flat_w[bucket_of(l.gw)].push_back({l.gw, (size_t)l.nw()});
-    e->flat_off.assign(nbk + 1, 0); e->tile_off.assign(nbk + 1, 0);
-    for (int b = 0; b < nbk; ++b) {
-        i_adam_flat.insert(i_adam_flat.end(), flat_b[b].begin(), flat_b[b].end());
-        i_adam_2d.insert(i_adam_2d.end(), tile_b[b].begin(), tile_b[b].end());
-        e->flat_off[b + 1] = (int)i_adam_flat.size(); e->tile_off[b + 1] = (int)i_adam_2d.size();
-    }
-    auto up = [&](const void* src, size_t bytes, void** dst) -> int {
-        if (bytes == 0) { *dst = nullptr; return 0; }
-        if (hipMalloc(dst, bytes) != hipSuccess) return -1;
-        if (hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
-        return 0;
-    };
-    if (up(e->sn_host.data(), sizeof(SNDesc) * L, (void**)&e->sn_dev)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(e->adam_host.data(), sizeof(AdamDesc) * e->adam_host.size(), (void**)&e->adam_dev)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_sn.data(), sizeof(WorkItem) * i_sn.size(), (void**)&e->items_sn)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_dot.data(), sizeof(WorkItem) * i_dot.size(), (void**)&e->items_dot)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_adam.data(), sizeof(WorkItem) * i_adam.size(), (void**)&e->items_adam)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_copy.data(), sizeof(WorkItem) * i_copy.size(), (void**)&e->items_copy)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_sn_unf.data(), sizeof(WorkItem) * i_sn_unf.size(), (void**)&e->items_sn_unf)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_adam_flat.data(), sizeof(WorkItem) * i_adam_flat.size(), (void**)&e->items_adam_flat)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_adam_2d.data(), sizeof(WorkItem) * i_adam_2d.size(), (void**)&e->items_adam_2d)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_ts.data(), sizeof(WorkItem) * i_ts.size(), (void**)&e->items_ts)) return fail(SGV_ERR_HIP, "table upload failed");
-    if (up(i_ss.data(), sizeof(WorkItem) * i_ss.size(), (void**)&e->items_ss)) return fail(SGV_ERR_HIP, "table upload failed");
-    e->n_items_ts = (int)i_ts.size(); e->n_items_ss = (int)i_ss.size();
-    if (hipMalloc((void**)&e->lin_dot_part, sizeof(float) * std::max<size_t>(i_dot.size(), 1)) != hipSuccess) return fail(SGV_ERR_HIP, "hipMalloc failed");
-    for (auto& f : e->fin_lin_dots) f.src = e->lin_dot_part + (size_t)(uintptr_t)f.src;
-    e->n_gnorm_part = (int)std::max(i_adam_flat.size() + i_adam_2d.size(), i_adam.size());
-    if (hipMalloc((void**)&e->gnorm_part, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "hipMalloc failed");
-    if (hipMemset(e->gnorm_part, 0, sizeof(double) * std::max(e->n_gnorm_part, 1)) != hipSuccess) return fail(SGV_ERR_HIP, "memset failed");
-    e->n_items_sn_unf = (int)i_sn_unf.size(); e->n_items_adam_flat = (int)i_adam_flat.size(); e->n_items_adam_2d = (int)i_adam_2d.size();
-    e->n_items_sn = (int)i_sn.size(); e->n_items_dot = (int)i_dot.size();
-    e->n_items_adam = (int)i_adam.size(); e->n_items_copy = (int)i_copy.size();
+    if (!t.upload(0)) return fail(SGV_ERR_HIP, "table upload failed");
     return 0;
 }
 

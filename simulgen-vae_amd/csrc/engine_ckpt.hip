@@ -204,12 +204,7 @@ static int ckpt_prepare(sgv_engine* e) {
             }
         }
     }
-    auto up = [&](const void* src, size_t bytes, void** dst) -> bool {
-        if (bytes == 0) { *dst = nullptr; return true; }
-        return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(tiles.data(), sizeof(CkptTile) * tiles.size(), (void**)&c->tiles_dev) || !up(copies.data(), sizeof(CkptCopy) * copies.size(), (void**)&c->copies_dev) ||
-        !up(it_tile.data(), sizeof(WorkItem) * it_tile.size(), (void**)&c->items_tile) || !up(it_copy.data(), sizeof(WorkItem) * it_copy.size(), (void**)&c->items_copy))
+    if (!upload_vec(tiles, &c->tiles_dev) || !upload_vec(copies, &c->copies_dev) || !upload_vec(it_tile, &c->items_tile) || !upload_vec(it_copy, &c->items_copy))
         return fail(SGV_ERR_HIP, "snapshot table upload failed");
     c->n_items_tile = (int)it_tile.size(); c->n_items_copy = (int)it_copy.size();
     HIPCHK(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
@@ -308,7 +303,7 @@ int sgv_restore(sgv_engine* e, const float* host, size_t floats) {
     CHK(sgv_prepare(e));
     // an uninterrupted run enters its next training forward with the W^T u partials of the last tiled AdamW pass; the full
     // power-iteration pass sums the same 64-row blocks in another order, so those partials are rebuilt here in the tiled pass's order
-    if (opt_sn_tpart_tiles(e->adam_dev, e->sn_dev, e->items_adam_2d, e->n_items_adam_2d, e->stream)) return fail(SGV_ERR_HIP, "W^T u partial launch failed");
+    if (opt_sn_tpart_tiles(e->tab.adam_dev, e->tab.sn_dev, e->tab.dev[OptTables::TILE], e->tab.n(OptTables::TILE), e->stream)) return fail(SGV_ERR_HIP, "W^T u partial launch failed");
     e->wtu_fresh = true;
     HIPCHK(hipStreamSynchronize(e->stream));
     return SGV_OK;

@@ -102,15 +102,11 @@ struct sgv_engine {
     char* copies = nullptr; size_t n_copies = 0;
     char* act = nullptr; size_t act_bytes = 0, act_used = 0;
     double* stats = nullptr; size_t n_stats = 0, n_stats_fwd = 0;  // [fwd sums | bwd sums2]
-    float* sn_tmp = nullptr; size_t n_sn_tmp = 0;   // [tmp_t of fused layers][tmp_t of the others][tmp_s of all]
-    size_t n_sn_tmp_fused = 0, sn_tmp_s_off = 0;
+    float* sn_tmp = nullptr; size_t n_sn_tmp = 0;   // power-iteration scratch, four blocks per layer (sn_scratch_carve)
     bool wtu_fresh = false;                          // tpart of the fused layers holds the W^T u partials for the current weights
-    std::vector<size_t> sn_tpart_off, sn_spart_off;  // per layer: offsets of the power-iteration partials inside sn_tmp
-    WorkItem* items_ts = nullptr; WorkItem* items_ss = nullptr; int n_items_ts = 0, n_items_ss = 0;
-    float* lin_dot_part = nullptr;                   // per-work-item <G,W>/sigma partials of the Linear layers
-    std::vector<FinDot> fin_lin_dots;
-    std::vector<int> dot_off, fin_lin_off;           // [bucket] -> first Linear <G,W> work item / first fin_lin_dots entry (tables sorted by bucket)
-    double* gnorm_part = nullptr; int n_gnorm_part = 0;   // per-work-item sums of squared gradients of the AdamW passes
+    // descriptor and work-item tables of the optimizer / spectral-norm kernels, groups = gradient buckets.  DOT / fin hold the Linear
+    // layers' <G,W> (per-item partials in tab.dot_part), tab.gnorm_part the per-item sums of squared gradients of the AdamW passes
+    OptTables tab;
     float* sn_sigma = nullptr;
     float* sn_dot_dummy = nullptr;
     double* scal = nullptr;        // device doubles: [0..1] loss sums, [2] kl, [3..] kl2, [15] grad norm^2
@@ -178,13 +174,6 @@ struct sgv_engine {
     float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace (also the frame partials of sgv_summarize)
     int* probes_dev = nullptr; int n_probes = 0;           // sgv_set_probes: SGV_MAX_PROBES checked node indices (allocated on first use)
     std::vector<int32_t> probes_host;                      // the source of the last upload stays alive until the next one
-    SNDesc* sn_dev = nullptr; std::vector<SNDesc> sn_host;
-    AdamDesc* adam_dev = nullptr; std::vector<AdamDesc> adam_host;
-    WorkItem *items_sn = nullptr, *items_dot = nullptr, *items_adam = nullptr, *items_copy = nullptr;
-    WorkItem *items_sn_unf = nullptr, *items_adam_flat = nullptr, *items_adam_2d = nullptr;
-    int n_items_sn = 0, n_items_dot = 0, n_items_adam = 0, n_items_copy = 0;
-    int n_items_sn_unf = 0, n_items_adam_flat = 0, n_items_adam_2d = 0;
-    std::vector<int> flat_off, tile_off;             // AdamW work items are sorted by gradient bucket: [bucket] -> first item
     // graph
     std::vector<Block> encA, encR, decU, decD, decP1, decP2, decX, decQ1, decQ2;
     Block decS, recon;
@@ -247,7 +236,6 @@ struct sgv_engine {
     struct CkptState* ckpt = nullptr;
 };
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr int SGV_MAX_PROBES = 4096;
 // position of the first probe node outside [0, N), -1 if none (sgv_set_probes, sgv_test_recon_summary)
 static inline int first_bad_probe(const int32_t* nodes, int count, int N) {

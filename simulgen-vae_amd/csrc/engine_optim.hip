@@ -75,13 +75,13 @@ int set_grad_bf16(sgv_engine* e, int value) {
         // point the optimizer's table at the mirror for the classified layers (the kernel follows the pointer only when the launch
         // says so: adamw_tiles)
         bool changed = false;
-        for (auto& a : e->adam_host) {
+        for (auto& a : e->tab.adam) {
             if (a.sn < 0 || a.sn >= (int)e->layers.size()) continue;
             const Layer& l = e->layers[a.sn];
             if (!l.lp || a.g != e->grads + l.gw || a.glp) continue;
             a.glp = reinterpret_cast<const unsigned short*>(e->grads_lp) + l.gw; changed = true;
         }
-        if (changed) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipMemcpy(e->adam_dev, e->adam_host.data(), sizeof(AdamDesc) * e->adam_host.size(), hipMemcpyHostToDevice)); }
+        if (changed) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipMemcpy(e->tab.adam_dev, e->tab.adam.data(), sizeof(AdamDesc) * e->tab.adam.size(), hipMemcpyHostToDevice)); }
     }
     e->grad_bf16 = value != 0;
     return 0;
@@ -106,7 +106,7 @@ static int adamw_finish(sgv_engine* e) {
     e->copies_fresh = true;
     e->wtu_fresh = true;
     e->adam_open = false;
-    ew_rowsum_d(e->gnorm_part, e->n_items_adam_flat + e->n_items_adam_2d, 1, e->scal + 15, 1.0, e->stream);
+    ew_rowsum_d(e->tab.gnorm_part, e->tab.n(OptTables::FLAT) + e->tab.n(OptTables::TILE), 1, e->scal + 15, 1.0, e->stream);
     return 0;
 }
 static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, bool from_lp) {
@@ -121,7 +121,7 @@ static int adamw_tiles(sgv_engine* e, float lr, int t0, int t1, hipStream_t st, 
     const int slice = st != e->stream ? ADAM_SLICE : t1 - t0;
     for (int a = t0; a < t1; a += slice) {
         const int b = std::min(t1, a + slice);
-        if (opt_adamw_sn(e->adam_dev, e->sn_dev, e->items_adam_2d + a, b - a, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + e->n_items_adam_flat + a, e->dt, st,
+        if (opt_adamw_sn(e->tab.adam_dev, e->tab.sn_dev, e->tab.dev[OptTables::TILE] + a, b - a, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->tab.gnorm_part + e->tab.n(OptTables::FLAT) + a, e->dt, st,
                          e->grads, from_lp ? e->grads_lp : nullptr, (!from_lp && grad_lp_active(e) && !e->lp_fp32) ? 1 : 0))
             return fail(SGV_ERR_HIP, "adamw launch failed");
     }
@@ -148,8 +148,8 @@ static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, in
     // biases, GroupNorm affine and the Linear heads: flat pass.  Conv weights: tiled pass that also writes both
     // compute copies and W_new^T u for the next forward's power iteration; buckets updated ahead (adamw_bucket_async) are skipped.
     const AdamCoef c = adam_coef(e->step);
-    const int f0 = e->flat_off[bucket_lo], f1 = e->flat_off[bucket_hi];
-    if ((which & 2) && opt_adamw(e->adam_dev, e->sn_dev, e->items_adam_flat + f0, f1 - f0, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->gnorm_part + f0, e->dt, st))
+    const int f0 = e->tab.flat_off[bucket_lo], f1 = e->tab.flat_off[bucket_hi];
+    if ((which & 2) && opt_adamw(e->tab.adam_dev, e->tab.sn_dev, e->tab.dev[OptTables::FLAT] + f0, f1 - f0, lr, c.b1, c.b2, 1e-8f, 0.01f, c.bc1, c.bc2s, e->tab.gnorm_part + f0, e->dt, st))
         return fail(SGV_ERR_HIP, "adamw launch failed");
     if (which & 1) {
         const int nu = (int)e->bucket_updated.size();
@@ -159,7 +159,7 @@ static int adamw_range(sgv_engine* e, float lr, int bucket_lo, int bucket_hi, in
             if (skip(b)) { ++b; continue; }
             int h = b + 1;
             while (h < bucket_hi && !skip(h) && lp(h) == lp(b)) ++h;          // runs of buckets read from the same place
-            CHK(adamw_tiles(e, lr, e->tile_off[b], e->tile_off[h], st, lp(b)));
+            CHK(adamw_tiles(e, lr, e->tab.tile_off[b], e->tab.tile_off[h], st, lp(b)));
             for (int k = b; k < h; ++k) if (k < np) e->bucket_packed[k] &= ~1;
             b = h;
         }
@@ -172,7 +172,7 @@ static int adamw_bucket_async(sgv_engine* e, float lr, int b, hipStream_t st) {
     CHK(adamw_begin(e));
     const bool packed = b < (int)e->bucket_packed.size() && e->bucket_packed[b];
     const bool from_lp = packed && (e->bucket_packed[b] & 1);
-    CHK(adamw_tiles(e, lr, e->tile_off[b], e->tile_off[b + 1], st, from_lp));
+    CHK(adamw_tiles(e, lr, e->tab.tile_off[b], e->tab.tile_off[b + 1], st, from_lp));
     if (from_lp) e->bucket_packed[b] &= ~1;
     e->bucket_updated[b] = 1;
     if (st != e->stream) e->opt_dirty = e->opt_dirty || st == e->opt;
@@ -198,7 +198,7 @@ int GradRelease::begin() {
         const int rt6 = (L0.cout + 63) / 64, ct6 = (L0.cin + 63) / 64;
         last_chunked = e->encA[0].st.size() == 1 && L0.k == 1 && L0.has_grad && layer_fused_adam(L0) && L0.cout % (128 * e->ddp_last_chunks) == 0 &&
                        e->buckets[last_b].first == L0.gw && e->buckets[last_b].second == align_up((size_t)L0.nw(), 4) &&
-                       e->tile_off[last_b + 1] - e->tile_off[last_b] == rt6 * ct6 && e->flat_off[last_b + 1] == e->flat_off[last_b] &&
+                       e->tab.tile_off[last_b + 1] - e->tab.tile_off[last_b] == rt6 * ct6 && e->tab.flat_off[last_b + 1] == e->tab.flat_off[last_b] &&
                        2.0e-9 * (double)((long)e->batch * e->T) * L0.cout * L0.cin > e->ddp_chunk_min_gf;      // the big-GEMM regime: main stream, split-K 1
     }
     // <G,W_eff> of the Linear layers is computed from G itself: in one launch at the end of backward -- unless a collective may
@@ -253,9 +253,9 @@ void GradRelease::flush_fin(bool affine) {
     if (affine && !e->fin_affine.empty()) { ew_fin_affine(e->fin_affine.data(), (int)e->fin_affine.size(), e->stream); e->fin_affine.clear(); }
 }
 void GradRelease::lin_dots(int b0, int b1) {
-    const int d0 = e->dot_off[b0], d1 = e->dot_off[b1];
-    if (d1 > d0 && opt_sn_grad_dot(e->sn_dev, e->items_dot + d0, d1 - d0, e->lin_dot_part + d0, e->stream)) lin_err = true;
-    e->fin_dots.insert(e->fin_dots.end(), e->fin_lin_dots.begin() + e->fin_lin_off[b0], e->fin_lin_dots.begin() + e->fin_lin_off[b1]);
+    const int d0 = e->tab.dot_off[b0], d1 = e->tab.dot_off[b1];
+    if (d1 > d0 && opt_sn_grad_dot(e->tab.sn_dev, e->tab.dev[OptTables::DOT] + d0, d1 - d0, e->tab.dot_part + d0, e->stream)) lin_err = true;
+    e->fin_dots.insert(e->fin_dots.end(), e->tab.fin.begin() + e->tab.fin_off[b0], e->tab.fin.begin() + e->tab.fin_off[b1]);
 }
 void GradRelease::fire() { if (dots_per_bucket) lin_dots(bucket, bucket + 1); flush_fin(false); fire_at(bucket); ++bucket; }
 // the small zone (biases, GroupNorm affine, <G,W_eff> scalars) is complete once the first conv's dY exists:
@@ -301,7 +301,7 @@ int GradRelease::after_first_block(int br) {
         const bool lp = e->payload_bf16 != 0;
         for (int c = 0; c < n_c; ++c) {
             HIPCHK(hipStreamWaitEvent(e->stream, chunk_done[c], 0));
-            CHK(adamw_tiles(e, fuse_lr, e->tile_off[last_b] + (c * rows / 64) * ct6, e->tile_off[last_b] + ((c + 1) * rows / 64) * ct6, e->stream, lp));
+            CHK(adamw_tiles(e, fuse_lr, e->tab.tile_off[last_b] + (c * rows / 64) * ct6, e->tab.tile_off[last_b] + ((c + 1) * rows / 64) * ct6, e->stream, lp));
         }
         e->bucket_updated[last_b] = 1;
     }
@@ -350,8 +350,8 @@ int sgv_scale_grads(sgv_engine* e, float factor) {
 int sgv_grad_norm(sgv_engine* e, double* out) {
     if (!e || !out) return fail(SGV_ERR_ARG, "null argument");
     CHK(lp_sync(e));
-    if (opt_grad_norm(e->adam_dev, e->sn_dev, e->items_adam, e->n_items_adam, e->gnorm_part, e->stream)) return fail(SGV_ERR_HIP, "grad-norm launch failed");
-    ew_rowsum_d(e->gnorm_part, e->n_items_adam, 1, e->scal + 15, 1.0, e->stream);
+    if (opt_grad_norm(e->tab.adam_dev, e->tab.sn_dev, e->tab.dev[OptTables::ADAM], e->tab.n(OptTables::ADAM), e->tab.gnorm_part, e->stream)) return fail(SGV_ERR_HIP, "grad-norm launch failed");
+    ew_rowsum_d(e->tab.gnorm_part, e->tab.n(OptTables::ADAM), 1, e->scal + 15, 1.0, e->stream);
     double h = 0.0;
     HIPCHK(hipMemcpyAsync(&h, e->scal + 15, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -11,15 +11,10 @@
 #include <vector>
 
 struct sgv_pset {
-    std::vector<SNDesc> sn;
-    std::vector<AdamDesc> adam;
-    std::vector<int> sn_of_entry;                 // entry -> index into sn, or -1
-    SNDesc* sn_dev = nullptr; AdamDesc* adam_dev = nullptr;
-    WorkItem *items_sn = nullptr, *items_dot = nullptr, *items_adam = nullptr, *items_ts = nullptr, *items_ss = nullptr;
-    int n_items_sn = 0, n_items_dot = 0, n_items_adam = 0, n_items_ts = 0, n_items_ss = 0;
-    float *mv = nullptr, *sigma = nullptr, *dots = nullptr, *tmp = nullptr, *coef = nullptr, *dot_part = nullptr;
-    double *gnorm = nullptr, *gnorm_part = nullptr;      // gnorm_part: one partial per AdamW work item, summed in index order (no atomics)
-    std::vector<FinDot> fin_dots;
+    OptTables tab;                                // one group, nothing tiled: every spectral-norm entry gets its <G,W> from the flat pass
+    std::vector<int> sn_of_entry;                 // entry -> index into tab.sn, or -1
+    float *mv = nullptr, *sigma = nullptr, *dots = nullptr, *tmp = nullptr, *coef = nullptr;
+    double* gnorm = nullptr;
     size_t n_tmp = 0, n_dots = 0;
     int step = 0;
 };
@@ -30,14 +25,13 @@ __global__ void pset_clip_coef_kernel(const double* sumsq, float max_norm, float
     out[1] = tn;
 }
 
-static size_t al4(size_t n) { return (n + 3) / 4 * 4; }
-
 extern "C" {
 
 int sgv_pset_destroy(sgv_pset* ps) {
     if (!ps) return 0;
-    void* ptrs[] = {ps->sn_dev, ps->adam_dev, ps->items_sn, ps->items_dot, ps->items_adam, ps->items_ts, ps->items_ss, ps->mv, ps->sigma, ps->dots, ps->tmp, ps->coef, ps->gnorm, ps->dot_part, ps->gnorm_part};
+    void* ptrs[] = {ps->mv, ps->sigma, ps->dots, ps->tmp, ps->coef, ps->gnorm};
     for (void* p : ptrs) if (p) hipFree(p);
+    ps->tab.release();
     delete ps;
     return 0;
 }
@@ -58,10 +52,9 @@ int sgv_pset_create(const sgv_pset_entry* entries, int n, sgv_pset** out) {
                 return sgv_set_error(-1, "sgv_pset_create: spectral-norm entry %d needs rows*cols == n, cols %% 4 == 0 and u, v", i);
             }
             ++n_sn;
-            n_tmp += al4(e.cols) + al4(e.rows);
-            n_tmp += al4(sn_tpart_floats(1, e.rows, e.cols)) + al4(sn_spart_floats(1, e.rows, e.cols));
+            n_tmp += sn_scratch_floats(1, e.rows, e.cols);
         }
-        total += al4(e.n);
+        total += align_up((size_t)e.n, 4);
     }
 #define PS_ALLOC(ptr, bytes)                                                                   \
     do {                                                                                       \
@@ -78,63 +71,43 @@ int sgv_pset_create(const sgv_pset_entry* entries, int n, sgv_pset** out) {
     PS_ALLOC(ps->tmp, n_tmp * sizeof(float));
     PS_ALLOC(ps->coef, 2 * sizeof(float));
     PS_ALLOC(ps->gnorm, sizeof(double));
-    std::vector<WorkItem> i_sn, i_dot, i_adam, i_ts, i_ss;
-    size_t off = 0, toff = 0;
+    OptTables& t = ps->tab;
+    size_t off = 0;
+    float* scratch = ps->tmp;
     ps->sn_of_entry.assign(n, -1);
     for (int i = 0; i < n; ++i) {
         const sgv_pset_entry& e = entries[i];
         AdamDesc a; memset(&a, 0, sizeof(a));
         a.p = e.p; a.g = e.g; a.m = ps->mv + off; a.v = ps->mv + total + off; a.n = e.n; a.sn = -1; a.rows = 1; a.cols = (int)e.n; a.taps = 1;
-        off += al4(e.n);
+        off += align_up((size_t)e.n, 4);
         if (e.rows > 0) {
             SNDesc d; memset(&d, 0, sizeof(d));
-            const int si = (int)ps->sn.size();
+            const int si = (int)t.sn.size();
             d.W = e.p; d.u = e.u; d.v = e.v;
-            d.tmp_t = ps->tmp + toff; toff += al4(e.cols);
-            d.tmp_s = ps->tmp + toff; toff += al4(e.rows);
-            d.tpart = ps->tmp + toff; toff += al4(sn_tpart_floats(1, e.rows, e.cols));
-            d.spart = ps->tmp + toff; toff += al4(sn_spart_floats(1, e.rows, e.cols));
-            d.sigma = ps->sigma + 2 * si; d.dot = ps->dots + (size_t)si * SGV_DOT_SLOTS; d.G = e.g;
             d.taps = 1; d.rows = e.rows; d.cols = e.cols; d.active = 1;
-            ps->sn.push_back(d);
-            ps->sn_of_entry[i] = si;
+            sn_scratch_carve(d, scratch);
+            d.sigma = ps->sigma + 2 * si; d.dot = ps->dots + (size_t)si * SGV_DOT_SLOTS; d.G = e.g;
+            ps->sn_of_entry[i] = t.add_sn(d, false, true);
             a.sn = si; a.rows = e.rows; a.cols = e.cols;
-            for (int c = 0; c < sn_gemv_items(1, e.rows, e.cols); ++c) i_sn.push_back({si, c});
-            for (int c = 0; c < sn_tsum_items(1, e.cols); ++c) i_ts.push_back({si, c});
-            for (int c = 0; c < sn_ssum_items(e.rows); ++c) i_ss.push_back({si, c});
-            ps->fin_dots.push_back({(const float*)(uintptr_t)i_dot.size(), d.dot, (int)opt_flat_items(e.n), 0});
-            for (long c = 0; c < opt_flat_items(e.n); ++c) i_dot.push_back({si, (int)c});
         }
-        const int id = (int)ps->adam.size();
-        ps->adam.push_back(a);
-        for (long c = 0; c < opt_flat_items(e.n); ++c) i_adam.push_back({id, (int)c});
+        t.add_adam(a, false);
     }
-    auto up = [&](const void* src, size_t bytes, void** dst) -> bool {
-        if (bytes == 0) { *dst = nullptr; return true; }
-        return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(ps->sn.data(), sizeof(SNDesc) * ps->sn.size(), (void**)&ps->sn_dev) || !up(ps->adam.data(), sizeof(AdamDesc) * ps->adam.size(), (void**)&ps->adam_dev) ||
-        !up(i_sn.data(), sizeof(WorkItem) * i_sn.size(), (void**)&ps->items_sn) || !up(i_dot.data(), sizeof(WorkItem) * i_dot.size(), (void**)&ps->items_dot) ||
-        !up(i_adam.data(), sizeof(WorkItem) * i_adam.size(), (void**)&ps->items_adam) ||
-        !up(i_ts.data(), sizeof(WorkItem) * i_ts.size(), (void**)&ps->items_ts) || !up(i_ss.data(), sizeof(WorkItem) * i_ss.size(), (void**)&ps->items_ss)) {
+    t.finish();
+    if (!t.upload(0)) {
         sgv_pset_destroy(ps);
         return sgv_set_error(-2, "sgv_pset_create: table upload failed");
     }
-    ps->n_items_sn = (int)i_sn.size(); ps->n_items_dot = (int)i_dot.size(); ps->n_items_adam = (int)i_adam.size();
-    ps->n_items_ts = (int)i_ts.size(); ps->n_items_ss = (int)i_ss.size();
-    PS_ALLOC(ps->dot_part, (i_dot.size() ? i_dot.size() : 1) * sizeof(float));
-    PS_ALLOC(ps->gnorm_part, (i_adam.size() ? i_adam.size() : 1) * sizeof(double));
-    for (auto& f : ps->fin_dots) f.src = ps->dot_part + (size_t)(uintptr_t)f.src;
     *out = ps;
     return 0;
 }
 
 int sgv_pset_power_iteration(sgv_pset* ps, int train, void* stream) {
     if (!ps) return sgv_set_error(-1, "null parameter set");
-    if (ps->sn.empty()) return 0;
+    const OptTables& t = ps->tab;
+    if (t.sn.empty()) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (opt_sn_power_iteration(ps->sn_dev, ps->items_sn, ps->n_items_sn, ps->items_sn, ps->n_items_sn, ps->items_ts, ps->n_items_ts,
-                               ps->items_ss, ps->n_items_ss, (int)ps->sn.size(), train, s))
+    if (opt_sn_power_iteration(t.sn_dev, t.dev[OptTables::SN], t.n(OptTables::SN), t.dev[OptTables::SN], t.n(OptTables::SN), t.dev[OptTables::TSUM],
+                               t.n(OptTables::TSUM), t.dev[OptTables::SSUM], t.n(OptTables::SSUM), (int)t.sn.size(), train, s))
         return sgv_set_error(-2, "power-iteration launch failed");
     return 0;
 }
@@ -150,12 +123,15 @@ int sgv_pset_step(sgv_pset* ps, float lr, float weight_decay, float max_norm, fl
     ps->step += 1;
     const AdamCoef c = adam_coef(ps->step);
     // <G,W>/sigma per spectrally-normalised tensor and the gradient norm: per-work-item partials, summed in a fixed order
-    if (opt_sn_grad_dot(ps->sn_dev, ps->items_dot, ps->n_items_dot, ps->dot_part, s)) return sgv_set_error(-2, "grad-dot launch failed");
-    if (!ps->fin_dots.empty()) ew_fin_dots(ps->fin_dots.data(), (int)ps->fin_dots.size(), s);
-    if (opt_grad_norm(ps->adam_dev, ps->sn_dev, ps->items_adam, ps->n_items_adam, ps->gnorm_part, s)) return sgv_set_error(-2, "grad-norm launch failed");
-    ew_rowsum_d(ps->gnorm_part, ps->n_items_adam, 1, ps->gnorm, 1.0, s);
+    const OptTables& t = ps->tab;
+    const WorkItem* items_adam = t.dev[OptTables::ADAM];
+    const int n_adam = t.n(OptTables::ADAM);
+    if (opt_sn_grad_dot(t.sn_dev, t.dev[OptTables::DOT], t.n(OptTables::DOT), t.dot_part, s)) return sgv_set_error(-2, "grad-dot launch failed");
+    if (!t.fin.empty() && ew_fin_dots(t.fin.data(), (int)t.fin.size(), s)) return sgv_set_error(-2, "grad-dot sum launch failed");
+    if (opt_grad_norm(t.adam_dev, t.sn_dev, items_adam, n_adam, t.gnorm_part, s)) return sgv_set_error(-2, "grad-norm launch failed");
+    if (ew_rowsum_d(t.gnorm_part, n_adam, 1, ps->gnorm, 1.0, s)) return sgv_set_error(-2, "grad-norm sum launch failed");
     hipLaunchKernelGGL(pset_clip_coef_kernel, dim3(1), dim3(1), 0, s, ps->gnorm, max_norm, ps->coef);
-    if (opt_adamw(ps->adam_dev, ps->sn_dev, ps->items_adam, ps->n_items_adam, lr, c.b1, c.b2, 1e-8f, weight_decay, c.bc1, c.bc2s, ps->gnorm_part, 0, s, ps->coef))
+    if (opt_adamw(t.adam_dev, t.sn_dev, items_adam, n_adam, lr, c.b1, c.b2, 1e-8f, weight_decay, c.bc1, c.bc2s, t.gnorm_part, 0, s, ps->coef))
         return sgv_set_error(-2, "adamw launch failed");
     if (total_norm_host) {
         float h[2] = {0.f, 0.f};

@@ -1,6 +1,7 @@
 // Host-callable launchers of the elementwise / normalisation / optimizer kernels (ew.hip, optim.hip).
 #pragma once
 #include "sgv_common.h"
+#include <vector>
 
 struct GNParams {
     const void* y = nullptr;    long ldy = 0;      // conv output (pre-norm) [B*T][C]
@@ -217,8 +218,9 @@ constexpr int SN_COLS_PER_ITEM = 1024;
 constexpr int SN_SUM_CHUNK = 64;     // elements of taps*cols (sn_tsum_kernel) / rows (sn_ssum_kernel) per work item of the partial sums
 constexpr int OPT_TILE = 64;         // tile edge of the tiled AdamW pass
 constexpr int COPY_TILE = 32;        // tile edge of opt_make_copies
-// Per-tensor geometry of the work-item tables and scratch buffers, [taps][rows][cols] weights.  Every host-side table builder
-// (engine.hip, pset.hip, the sgv_test_optset hook of test_hooks.hip) sizes its tables with these; the kernels decode the same chunk numbering.
+// Per-tensor geometry of the work-item tables and scratch buffers, [taps][rows][cols] weights.  OptTables (below) is the one host-side
+// builder of those tables: the engine, the parameter set (pset.hip) and the sgv_test_optset hook all go through it; the kernels decode
+// the same chunk numbering.
 inline int sn_row_blocks(int rows) { return (rows + SN_ROWS_PER_ITEM - 1) / SN_ROWS_PER_ITEM; }
 inline int sn_col_blocks(int cols) { return (cols + SN_COLS_PER_ITEM - 1) / SN_COLS_PER_ITEM; }
 inline int sn_gemv_items(int taps, int rows, int cols) { return taps * sn_row_blocks(rows) * sn_col_blocks(cols); }   // items1 / items3 of the power iteration
@@ -229,6 +231,54 @@ inline int opt_tile_items(int taps, int rows, int cols) { return taps * ((rows +
 inline int opt_copy_items(int taps, int rows, int cols) { return taps * ((rows + COPY_TILE - 1) / COPY_TILE) * ((cols + COPY_TILE - 1) / COPY_TILE); }
 inline size_t sn_tpart_floats(int taps, int rows, int cols) { return (size_t)sn_row_blocks(rows) * taps * cols; }
 inline size_t sn_spart_floats(int taps, int rows, int cols) { return (size_t)taps * sn_col_blocks(cols) * rows; }
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+#pragma GCC visibility push(hidden)      // host-side table building, shared among the library's files only: kept out of its dynamic symbols
+// Scratch of one spectrally-normalised weight: four consecutive 16-byte aligned blocks (tmp_t, tmp_s, tpart, spart)
+inline size_t sn_scratch_floats(int taps, int rows, int cols) {
+    return align_up((size_t)taps * cols, 4) + align_up((size_t)rows, 4) + align_up(sn_tpart_floats(taps, rows, cols), 4) + align_up(sn_spart_floats(taps, rows, cols), 4);
+}
+inline void sn_scratch_carve(SNDesc& d, float*& cursor) {      // d.taps / rows / cols set; cursor moves on by sn_scratch_floats
+    d.tmp_t = cursor; cursor += align_up((size_t)d.taps * d.cols, 4);
+    d.tmp_s = cursor; cursor += align_up((size_t)d.rows, 4);
+    d.tpart = cursor; cursor += align_up(sn_tpart_floats(d.taps, d.rows, d.cols), 4);
+    d.spart = cursor; cursor += align_up(sn_spart_floats(d.taps, d.rows, d.cols), 4);
+}
+// SNDesc::wc: W v reads the bf16 copy instead of the master weight where its 16-byte loads fit (bf16 engine, copy present, cols % 8 == 0)
+inline const void* sn_compute_copy(bool bf16, const void* copy, int cols) { return bf16 && copy && cols % 8 == 0 ? copy : nullptr; }
+// `v` in a fresh device allocation (*dst = null for an empty vector); false: hipMalloc or the copy failed
+bool upload_bytes(const void* src, size_t bytes, void** dst);
+template <typename T> bool upload_vec(const std::vector<T>& v, T** dst) { return upload_bytes(v.data(), sizeof(T) * v.size(), (void**)dst); }
+// The descriptor and work-item tables of the kernels above (opt_tables.hip).  Construction is plain host code: add_sn / add_adam /
+// add_copy in any order, then finish(); upload() makes the device copies and the per-item partial buffers, release() frees them.
+// Items keep insertion order, except that finish() stable-sorts the DOT, FLAT and TILE lists and the FinDot entries by `group` (the
+// engine's gradient buckets: a bucket's share of a pass is one range of its list).  dot_part / gnorm_part are summed in index order, so
+// the order of the lists is visible bit for bit in <G,W> and in the gradient norm.
+struct OptTables {
+    enum List { SN, SN_UNF, TSUM, SSUM, DOT, ADAM, FLAT, TILE, COPY, N_LISTS };
+    std::vector<SNDesc> sn;                  // host copies: callers may edit them and copy them to sn_dev / adam_dev again
+    std::vector<AdamDesc> adam;
+    std::vector<WorkItem> items[N_LISTS];    // SN: power iteration, SN_UNF: without the entries the reuse pass skips; TSUM / SSUM: its partial sums;
+                                             // DOT: <G,W>; ADAM: every trainable tensor (gradient norm, untiled AdamW); FLAT / TILE: the two AdamW passes; COPY
+    std::vector<FinDot> fin;                 // one per add_sn(.., flat_dot): its DOT items' partials -> SNDesc::dot; src is an index into dot_part until upload()
+    std::vector<int> dot_off, fin_off, flat_off, tile_off;   // after finish(): [group] -> first DOT item / fin entry / FLAT item / TILE item, [n_groups] = size
+    SNDesc* sn_dev = nullptr; AdamDesc* adam_dev = nullptr;
+    WorkItem* dev[N_LISTS] = {};
+    float* dot_part = nullptr;               // one float per DOT item
+    double* gnorm_part = nullptr;            // one double per AdamW item of a pass: max(FLAT + TILE, ADAM), the tiles' share after the flat items'
+    int n(List l) const { return (int)items[l].size(); }
+    // d complete (pointers, geometry, active).  Inactive: no SN / TSUM / SSUM items.  skip_in_reuse: its tpart comes from the tiled AdamW, so
+    // it stays out of SN_UNF.  flat_dot: <G,W> by the flat pass (DOT items + a FinDot).  Returns the descriptor's index.
+    int add_sn(const SNDesc& d, bool skip_in_reuse, bool flat_dot, int group = 0);
+    // ADAM items and, by `tiled`, FLAT or TILE items; none for a descriptor without gradient (a.g null: it only carries copies).  Returns its id.
+    int add_adam(const AdamDesc& a, bool tiled, int group = 0);
+    void add_copy(int adam_id);
+    void finish(int n_groups = 1);
+    bool upload(int part_fill_byte);         // false: an allocation or copy failed (release() what was made)
+    void release();
+private:
+    std::vector<int> dot_group, fin_group, flat_group, tile_group;     // per element, until finish()
+};
+#pragma GCC visibility pop
 // torch.optim.AdamW defaults and the bias corrections of step `step` (1-based): bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step)
 struct AdamCoef { float b1, b2, bc1, bc2s; };
 inline AdamCoef adam_coef(long step) {

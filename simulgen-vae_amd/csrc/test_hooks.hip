@@ -376,20 +376,14 @@ int sgv_test_linear_expand(int dtype, const float* X, const float* W, const floa
 }
 
 // ---- test hook for the multi-tensor optimizer / spectral-norm passes (optim.hip; tests/test_optim_kernels_gpu.py) ----
-// Descriptor and work-item tables over caller-owned device buffers, sized with the helpers of sgv_ew.h the engine and the
-// parameter-set object use; scratch (tmp_t, tmp_s, tpart, spart, the per-item partials) is the object's own and starts as NaN.
+// Descriptor and work-item tables over caller-owned device buffers, built by the OptTables of sgv_ew.h like the engine's and the
+// parameter-set object's; scratch (tmp_t, tmp_s, tpart, spart, the per-item partials) is the object's own and starts as NaN.
 struct sgv_optset {
     int dt = 0;
-    std::vector<SNDesc> sn;
-    std::vector<AdamDesc> adam;
+    OptTables tab;                               // one group
     std::vector<int> tiled;                      // per AdamDesc
-    SNDesc* sn_dev = nullptr; AdamDesc* adam_dev = nullptr;
-    WorkItem *items_sn = nullptr, *items_sn_unf = nullptr, *items_ts = nullptr, *items_ss = nullptr, *items_dot = nullptr, *items_adam = nullptr,
-             *items_flat = nullptr, *items_tile = nullptr, *items_copy = nullptr;
-    int n_sn = 0, n_sn_unf = 0, n_ts = 0, n_ss = 0, n_dot = 0, n_adam = 0, n_flat = 0, n_tile = 0, n_copy = 0;
-    float *tmp = nullptr, *dot_part = nullptr;
-    double *gnorm_part = nullptr, *gnorm = nullptr;
-    std::vector<FinDot> fin_dots;
+    float* tmp = nullptr;
+    double* gnorm = nullptr;
 };
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static int optset_done(int r, const char* what, hipStream_t s) {
@@ -404,9 +398,9 @@ static int optset_read(const double* dev, double* host, const char* what, hipStr
 }
 int sgv_test_optset_destroy(sgv_optset* os) {
     if (!os) return SGV_OK;
-    void* ptrs[] = {os->sn_dev, os->adam_dev, os->items_sn, os->items_sn_unf, os->items_ts, os->items_ss, os->items_dot, os->items_adam, os->items_flat,
-                    os->items_tile, os->items_copy, os->tmp, os->dot_part, os->gnorm_part, os->gnorm};
-    for (void* p : ptrs) if (p) hipFree(p);
+    if (os->tmp) hipFree(os->tmp);
+    if (os->gnorm) hipFree(os->gnorm);
+    os->tab.release();
     delete os;
     return SGV_OK;
 }
@@ -428,8 +422,7 @@ int sgv_test_optset_create(int dtype, const sgv_optset_entry* entries, int n, sg
             if ((long)e.taps * e.rows * e.cols != e.n) return fail(SGV_ERR_ARG, "%s: entry %d: taps * rows * cols = %ld but n = %ld", me, i, (long)e.taps * e.rows * e.cols, e.n);
             if (!e.u || !e.v_sn || !e.sigma || !e.dot || !al16(e.v_sn)) return fail(SGV_ERR_ARG, "%s: entry %d: a spectrally-normalised weight needs u, v_sn (16-byte aligned), sigma and dot", me, i);
             if (e.g_bf16 && ((uintptr_t)e.g_bf16 & 7)) return fail(SGV_ERR_ARG, "%s: entry %d: g_bf16 must be 8-byte aligned", me, i);
-            n_tmp += align_up((size_t)e.taps * e.cols, 4) + align_up((size_t)e.rows, 4) + align_up(sn_tpart_floats(e.taps, e.rows, e.cols), 4) +
-                     align_up(sn_spart_floats(e.taps, e.rows, e.cols), 4);
+            n_tmp += sn_scratch_floats(e.taps, e.rows, e.cols);
         }
     }
     sgv_optset* os = new sgv_optset();
@@ -439,85 +432,57 @@ int sgv_test_optset_create(int dtype, const sgv_optset_entry* entries, int n, sg
         return hipMalloc(dst, bytes ? bytes : 256) == hipSuccess && hipMemset(*dst, 0xFF, bytes ? bytes : 256) == hipSuccess;
     };
     if (!nan_alloc((void**)&os->tmp, n_tmp * sizeof(float))) return bad("scratch allocation");
-    std::vector<WorkItem> i_sn, i_sn_unf, i_ts, i_ss, i_dot, i_adam, i_flat, i_tile, i_copy;
-    size_t toff = 0;
+    OptTables& t = os->tab;
+    float* scratch = os->tmp;
     for (int i = 0; i < n; ++i) {
         const sgv_optset_entry& e = entries[i];
         AdamDesc a; memset(&a, 0, sizeof(a));
         a.p = e.p; a.g = e.g; a.m = e.m; a.v = e.v; a.n = e.n; a.sn = -1; a.rows = 1; a.cols = (int)e.n; a.taps = 1;
         a.wc = e.wc; a.wct = e.wct; a.glp = (const unsigned short*)e.g_bf16;
-        const int id = (int)os->adam.size();
         if (e.rows > 0) {
             SNDesc d; memset(&d, 0, sizeof(d));
-            const int si = (int)os->sn.size();
             d.W = e.p; d.u = e.u; d.v = e.v_sn; d.sigma = e.sigma; d.dot = e.dot; d.G = e.g;
-            d.tmp_t = os->tmp + toff; toff += align_up((size_t)e.taps * e.cols, 4);
-            d.tmp_s = os->tmp + toff; toff += align_up((size_t)e.rows, 4);
-            d.tpart = os->tmp + toff; toff += align_up(sn_tpart_floats(e.taps, e.rows, e.cols), 4);
-            d.spart = os->tmp + toff; toff += align_up(sn_spart_floats(e.taps, e.rows, e.cols), 4);
-            d.wc = (dtype == SGV_DTYPE_BF16 && e.wc && e.cols % 8 == 0) ? (const void*)e.wc : nullptr;      // the engine's rule (upload_tables)
             d.taps = e.taps; d.rows = e.rows; d.cols = e.cols; d.active = e.active ? 1 : 0;
-            os->sn.push_back(d);
-            a.sn = si; a.rows = e.rows; a.cols = e.cols; a.taps = e.taps;
-            if (e.active) {
-                for (int c = 0; c < sn_gemv_items(e.taps, e.rows, e.cols); ++c) { i_sn.push_back({si, c}); if (!e.tiled) i_sn_unf.push_back({si, c}); }
-                for (int c = 0; c < sn_tsum_items(e.taps, e.cols); ++c) i_ts.push_back({si, c});
-                for (int c = 0; c < sn_ssum_items(e.rows); ++c) i_ss.push_back({si, c});
-            }
-            if (!e.tiled) {
-                os->fin_dots.push_back({(const float*)(uintptr_t)i_dot.size(), d.dot, (int)opt_flat_items(e.n), 0});   // src = index for now, rebased below
-                for (long c = 0; c < opt_flat_items(e.n); ++c) i_dot.push_back({si, (int)c});
-            }
-            if (e.wc || e.wct)
-                for (int c = 0; c < opt_copy_items(e.taps, e.rows, e.cols); ++c) i_copy.push_back({id, c});
-        } else if (e.wc) {
-            for (int c = 0; c < opt_copy_items(1, 1, (int)e.n); ++c) i_copy.push_back({id, c});
+            sn_scratch_carve(d, scratch);
+            d.wc = sn_compute_copy(dtype == SGV_DTYPE_BF16, e.wc, e.cols);
+            a.sn = t.add_sn(d, e.tiled != 0, !e.tiled);
+            a.rows = e.rows; a.cols = e.cols; a.taps = e.taps;
         }
-        os->adam.push_back(a);
+        const int id = t.add_adam(a, e.tiled != 0);
         os->tiled.push_back(e.tiled ? 1 : 0);
-        for (long c = 0; c < opt_flat_items(e.n); ++c) { i_adam.push_back({id, (int)c}); if (!e.tiled) i_flat.push_back({id, (int)c}); }
-        if (e.tiled)
-            for (int c = 0; c < opt_tile_items(e.taps, e.rows, e.cols); ++c) i_tile.push_back({id, c});
+        if (e.wc || e.wct) t.add_copy(id);
     }
-    auto up = [&](const void* src, size_t bytes, void** dst) {
-        if (bytes == 0) { *dst = nullptr; return true; }
-        return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-#define OS_UP(vec, field, count) (up(vec.data(), sizeof(WorkItem) * vec.size(), (void**)&os->field) && ((os->count = (int)vec.size()), true))
-    if (!up(os->sn.data(), sizeof(SNDesc) * os->sn.size(), (void**)&os->sn_dev) || !up(os->adam.data(), sizeof(AdamDesc) * os->adam.size(), (void**)&os->adam_dev) ||
-        !OS_UP(i_sn, items_sn, n_sn) || !OS_UP(i_sn_unf, items_sn_unf, n_sn_unf) || !OS_UP(i_ts, items_ts, n_ts) || !OS_UP(i_ss, items_ss, n_ss) ||
-        !OS_UP(i_dot, items_dot, n_dot) || !OS_UP(i_adam, items_adam, n_adam) || !OS_UP(i_flat, items_flat, n_flat) || !OS_UP(i_tile, items_tile, n_tile) ||
-        !OS_UP(i_copy, items_copy, n_copy))
-        return bad("table upload");
-#undef OS_UP
-    if (!nan_alloc((void**)&os->dot_part, sizeof(float) * i_dot.size()) ||
-        !nan_alloc((void**)&os->gnorm_part, sizeof(double) * std::max(i_flat.size() + i_tile.size(), i_adam.size())) || !nan_alloc((void**)&os->gnorm, sizeof(double)))
-        return bad("workspace allocation");
-    for (auto& f : os->fin_dots) f.src = os->dot_part + (size_t)(uintptr_t)f.src;
+    t.finish();
+    if (!t.upload(0xFF)) return bad("table upload");
+    if (!nan_alloc((void**)&os->gnorm, sizeof(double))) return bad("workspace allocation");
     *out = os;
     return SGV_OK;
 }
 int sgv_test_optset_power_iteration(sgv_optset* os, int train, int reuse_tpart, void* stream) {
     if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_power_iteration: null object");
-    if (os->sn.empty()) return SGV_OK;
+    const OptTables& t = os->tab;
+    if (t.sn.empty()) return SGV_OK;
     hipStream_t s = (hipStream_t)stream;
     const bool reuse = train && reuse_tpart;         // run_sn with wtu_fresh: the tiled entries' tpart comes from the last AdamW pass
-    const int r = opt_sn_power_iteration(os->sn_dev, reuse ? os->items_sn_unf : os->items_sn, reuse ? os->n_sn_unf : os->n_sn, os->items_sn, os->n_sn, os->items_ts,
-                                         os->n_ts, os->items_ss, os->n_ss, (int)os->sn.size(), train, s);
+    const OptTables::List l1 = reuse ? OptTables::SN_UNF : OptTables::SN;
+    const int r = opt_sn_power_iteration(t.sn_dev, t.dev[l1], t.n(l1), t.dev[OptTables::SN], t.n(OptTables::SN), t.dev[OptTables::TSUM], t.n(OptTables::TSUM),
+                                         t.dev[OptTables::SSUM], t.n(OptTables::SSUM), (int)t.sn.size(), train, s);
     return optset_done(r, "sgv_test_optset_power_iteration", s);
 }
 int sgv_test_optset_grad_dot(sgv_optset* os, void* stream) {
     if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_grad_dot: null object");
     hipStream_t s = (hipStream_t)stream;
-    int r = opt_sn_grad_dot(os->sn_dev, os->items_dot, os->n_dot, os->dot_part, s);
-    if (!r && !os->fin_dots.empty()) r = ew_fin_dots(os->fin_dots.data(), (int)os->fin_dots.size(), s);
+    const OptTables& t = os->tab;
+    int r = opt_sn_grad_dot(t.sn_dev, t.dev[OptTables::DOT], t.n(OptTables::DOT), t.dot_part, s);
+    if (!r && !t.fin.empty()) r = ew_fin_dots(t.fin.data(), (int)t.fin.size(), s);
     return optset_done(r, "sgv_test_optset_grad_dot", s);
 }
 int sgv_test_optset_grad_norm(sgv_optset* os, double* gnorm_sq_out, void* stream) {
     if (!os || !gnorm_sq_out) return fail(SGV_ERR_ARG, "sgv_test_optset_grad_norm: null argument");
     hipStream_t s = (hipStream_t)stream;
-    int r = opt_grad_norm(os->adam_dev, os->sn_dev, os->items_adam, os->n_adam, os->gnorm_part, s);
-    if (!r) r = ew_rowsum_d(os->gnorm_part, os->n_adam, 1, os->gnorm, 1.0, s);
+    const OptTables& t = os->tab;
+    int r = opt_grad_norm(t.adam_dev, t.sn_dev, t.dev[OptTables::ADAM], t.n(OptTables::ADAM), t.gnorm_part, s);
+    if (!r) r = ew_rowsum_d(t.gnorm_part, t.n(OptTables::ADAM), 1, os->gnorm, 1.0, s);
     if (!r) CHK(optset_read(os->gnorm, gnorm_sq_out, "sgv_test_optset_grad_norm", s));
     return optset_done(r, "sgv_test_optset_grad_norm", s);
 }
@@ -529,20 +494,22 @@ int sgv_test_optset_adamw(sgv_optset* os, float lr, float wd, int step, const fl
     if (grad_source < 0 || grad_source > 2) return fail(SGV_ERR_ARG, "%s: grad_source must be 0 (fp32), 1 (per-entry bf16 mirror) or 2 (bf16 wire copy)", me);
     if (grad_source == 2) {
         if (!g_base || !g_wire || ((uintptr_t)g_wire & 7)) return fail(SGV_ERR_ARG, "%s: the wire copy needs g_base and an 8-byte aligned g_wire", me);
-        for (size_t i = 0; i < os->adam.size(); ++i) {
+        for (size_t i = 0; i < os->tab.adam.size(); ++i) {
             if (!os->tiled[i]) continue;
-            const long off = os->adam[i].g - g_base;
-            if (off < 0 || off % 4 || (size_t)(off + os->adam[i].n) > g_wire_elems)
+            const long off = os->tab.adam[i].g - g_base;
+            if (off < 0 || off % 4 || (size_t)(off + os->tab.adam[i].n) > g_wire_elems)
                 return fail(SGV_ERR_ARG, "%s: tiled entry %zu: its gradient must lie in [g_base, g_base + g_wire_elems) at a multiple of 4 elements", me, i);
         }
     }
     hipStream_t s = (hipStream_t)stream;
     const AdamCoef c = adam_coef(step);
-    int r = opt_adamw(os->adam_dev, os->sn_dev, os->items_flat, os->n_flat, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, os->gnorm_part, os->dt, s, gscale_dev);
-    if (!r) r = opt_adamw_sn(os->adam_dev, os->sn_dev, os->items_tile, os->n_tile, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, os->gnorm_part + os->n_flat, os->dt, s,
+    const OptTables& t = os->tab;
+    const int n_flat = t.n(OptTables::FLAT), n_tile = t.n(OptTables::TILE);
+    int r = opt_adamw(t.adam_dev, t.sn_dev, t.dev[OptTables::FLAT], n_flat, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, t.gnorm_part, os->dt, s, gscale_dev);
+    if (!r) r = opt_adamw_sn(t.adam_dev, t.sn_dev, t.dev[OptTables::TILE], n_tile, lr, c.b1, c.b2, 1e-8f, wd, c.bc1, c.bc2s, t.gnorm_part + n_flat, os->dt, s,
                              g_base, grad_source == 2 ? g_wire : nullptr, grad_source == 1 ? 1 : 0);
     if (!r && gnorm_sq_out) {
-        r = ew_rowsum_d(os->gnorm_part, os->n_flat + os->n_tile, 1, os->gnorm, 1.0, s);
+        r = ew_rowsum_d(t.gnorm_part, n_flat + n_tile, 1, os->gnorm, 1.0, s);
         if (!r) CHK(optset_read(os->gnorm, gnorm_sq_out, me, s));
     }
     return optset_done(r, me, s);
@@ -550,6 +517,6 @@ int sgv_test_optset_adamw(sgv_optset* os, float lr, float wd, int step, const fl
 int sgv_test_optset_make_copies(sgv_optset* os, void* stream) {
     if (!os) return fail(SGV_ERR_ARG, "sgv_test_optset_make_copies: null object");
     hipStream_t s = (hipStream_t)stream;
-    return optset_done(opt_make_copies(os->adam_dev, os->items_copy, os->n_copy, os->dt, s), "sgv_test_optset_make_copies", s);
+    return optset_done(opt_make_copies(os->tab.adam_dev, os->tab.dev[OptTables::COPY], os->tab.n(OptTables::COPY), os->dt, s), "sgv_test_optset_make_copies", s);
 }
 }  // extern "C"

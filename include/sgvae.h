@@ -213,6 +213,32 @@ int sgv_set_probes(sgv_engine* e, const int32_t* nodes_host, int count);
  * read from, as after sgv_generate. */
 int sgv_summarize(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix,
                   const float* scale_dev, const float* min_dev, const sgv_summary_out* out);
+/* The error of the field sgv_generate would write against held-out fields, e[b][t][n] = field - truth, reduced by the pass that
+ * would store the field; neither the field nor e is stored.  Device pointers, each optional (NULL = not computed), at least one
+ * required; node_* 16-byte aligned, frame_* 4-byte:
+ *   node_err    fp32  [B][3][N]  per sample and node: max over t of |e|, mean over t of e (the bias), mean over t of e^2
+ *                                (fp32 sums, one division by T each)
+ *   node_when   int32 [B][N]     t of the largest |e|; the smallest t on a tie
+ *   frame_err   fp32  [B][T][3]  per sample and time step: max over the nodes of |e|, mean over the nodes of e^2, mean over the
+ *                                nodes of truth^2 (fp32 sums inside a block of 512 nodes, combined in fp64, one division by N):
+ *                                sqrt(sum_t [1] / sum_t [2]) is the relative L2 error, without reading the truth again
+ *   frame_where int32 [B][T]     node of the largest |e|; the smallest node on a tie
+ * e is one fp32 subtraction of the value sgv_generate stores: on the same inputs, the field minus the truth bit for bit. */
+typedef struct {
+    float* node_err;
+    int32_t* node_when;
+    float* frame_err;
+    int32_t* frame_where;
+} sgv_score_out;
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the error pass against truth_dev:
+ * fp32 [B][T][N], dense, in physical units (the data set's own order, SGV_LAYOUT_TN of sgv_generate), 16-byte aligned.  truth
+ * must be finite; it is not checked: a NaN poisons the sums it enters and loses every comparison, so a maximum may then be one
+ * of the other elements.  No atomics, every reduction in a fixed order, two calls on the same inputs are bitwise equal; the
+ * frame partials live in the engine's workspace, nothing is allocated.  SGV_ERR_ARG before anything is enqueued: e, z_dev,
+ * scale_dev, min_dev, truth_dev or out NULL, all four outputs NULL, a misaligned pointer, the checks of sgv_decode.
+ * Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
+int sgv_score(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+              const float* min_dev, const float* truth_dev, const sgv_score_out* out);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -480,6 +506,13 @@ int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, co
 int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                            const float* scale, const float* min, const sgv_summary_out* out, const int32_t* probes_host,
                            int n_probes, int B, int T, int C, void* stream);
+/* The kernels of sgv_score on caller-owned buffers: inputs as sgv_test_recon_physical plus truth fp32 [B][T][C] (dense, 16-byte
+ * aligned), then the statistics of y and the error pass into the outputs of `out` (shapes of sgv_score_out with N = C); the frame
+ * workspace is allocated and freed here.  SGV_ERR_ARG, nothing launched: a NULL input (truth included), out NULL or all of its
+ * outputs NULL, B or T < 1, C < 8 or C % 8 != 0, a bad row stride, a misaligned pointer (y, truth, node_* 16 bytes; frame_* 4). */
+int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                         const float* scale, const float* min, const float* truth, const sgv_score_out* out, int B, int T, int C,
+                         void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

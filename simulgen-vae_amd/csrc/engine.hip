@@ -889,8 +889,9 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 
 // Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen` (sgv_generate),
 // the recon head's convolution and statistics followed by the physical-field pass instead of the loss tail -- or, with gen->sum
-// (sgv_summarize), by the summary pass: its frame partials go to e->colpart, which nothing uses once the statistics are done.
-struct GenOut { const float* scale; const float* mn; int layout; float* out; const ReconSummary* sum = nullptr; };
+// (sgv_summarize), by the summary pass: its frame partials go to e->colpart, which nothing uses once the statistics are done -- or,
+// with gen->score and gen->truth (sgv_score), by the error pass against the truth, with the same workspace.
+struct GenOut { const float* scale; const float* mn; int layout; float* out; const ReconSummary* sum = nullptr; const ReconScore* score = nullptr; const float* truth = nullptr; };
 static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
@@ -949,6 +950,13 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenO
         ScopedTimer tm(e, "recon_summary", nullptr);
         const int r = ew_recon_summary(e->dt, p, gen->scale, gen->mn, o, e->stream);
         return r ? fail(SGV_ERR_ARG, "sgv_summarize: the summary pass rejected its arguments (%d)", r) : 0;
+    }
+    if (gen && gen->score) {
+        ReconScore o = *gen->score;
+        o.work = e->colpart;
+        ScopedTimer tm(e, "recon_score", nullptr);
+        const int r = ew_recon_score(e->dt, p, gen->scale, gen->mn, gen->truth, o, e->stream);
+        return r ? fail(SGV_ERR_ARG, "sgv_score: the error pass rejected its arguments (%d)", r) : 0;
     }
     if (gen) {          // no loss, no read of x_in, no x_hat: the fp32 physical field goes straight to the caller's buffer
         ScopedTimer tm(e, "recon_phys", nullptr);
@@ -1079,6 +1087,25 @@ int sgv_summarize(sgv_engine* e, const float* z_dev, const float* xs_dev, int ba
     o.node_stats = out->node_stats; o.node_when = out->node_when; o.frame_stats = out->frame_stats; o.frame_where = out->frame_where;
     o.probes = out->probes; o.probe_nodes = e->probes_dev; o.n_probes = e->n_probes;
     const GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr, &o};
+    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
+    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
+    return SGV_OK;
+}
+
+int sgv_score(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+              const float* min_dev, const float* truth_dev, const sgv_score_out* out) {
+    if (!e || !z_dev || !scale_dev || !min_dev || !truth_dev || !out) return fail(SGV_ERR_ARG, "sgv_score: null argument");
+    if (!out->node_err && !out->node_when && !out->frame_err && !out->frame_where) return fail(SGV_ERR_ARG, "sgv_score: all four outputs are NULL");
+    if ((((uintptr_t)truth_dev | (uintptr_t)out->node_err | (uintptr_t)out->node_when) & 15) || (((uintptr_t)out->frame_err | (uintptr_t)out->frame_where) & 3))
+        return fail(SGV_ERR_ARG, "sgv_score: misaligned pointer (truth_dev, node_err / node_when 16 bytes, frame_err / frame_where 4)");
+    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_score"));
+    // as sgv_generate: the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
+    e->have_fwd = false;
+    e->fwd_train = false;
+    ReconScore o;
+    o.node_err = out->node_err; o.node_when = out->node_when; o.frame_err = out->frame_err; o.frame_where = out->frame_where;
+    GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr};
+    gen.score = &o; gen.truth = truth_dev;
     CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
     for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
     return SGV_OK;

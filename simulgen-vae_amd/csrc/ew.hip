@@ -1390,6 +1390,10 @@ template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v) {
 RS_LANE_REDUCE(lane_max_f, float, fmaxf, dpp_f)
 RS_LANE_REDUCE(lane_min_f, float, fminf, dpp_f)
 RS_LANE_REDUCE(lane_min_i, int, min, dpp_i)
+// the sum over a row's lanes in the same fixed tree (the score pass); lanes of DPP rows outside a row mask end up with twice their
+// value, which nobody reads: as above, only the LAST lane of the CV holds the result
+__device__ __forceinline__ float rs_add_f(float a, float b) { return a + b; }
+RS_LANE_REDUCE(lane_sum_f, float, rs_add_f, dpp_f)
 #undef RS_LANE_REDUCE
 
 // 4 waves / SIMD asked for: with every output the bf16 kernel sits at 128 VGPRs without scratch (131 and 3 waves unasked; the fp32 one
@@ -1577,6 +1581,197 @@ int ew_recon_summary(int dtype, GNParams p, const float* scale, const float* mn,
         if (dtype == 1) hipLaunchKernelGGL((recon_probe_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
         else hipLaunchKernelGGL((recon_probe_kernel<float>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate scoring (sgv_score): the summary pass with one more input stream.  e[b, t, n] = val[b, t, n] - truth[b, t, n], val the
+// value recon_phys_tn_kernel would store, truth fp32 dense [B][T][C] in physical units; reduced to, per (sample, node), max_t |e|,
+// the t of it, mean_t e and mean_t e^2, and per (sample, t), max_n |e|, its node, mean_n e^2 and mean_n truth^2 (what a relative
+// L2 error needs, so the truth is read once).  Geometry, tie rule and workspace are recon_summary_kernel's: no row split, the row
+// lanes combined through LDS in lane order, a row's channels reduced inside the wave (the maximum value first, then the smallest
+// index among its holders; the two sums in the same fixed DPP tree) into one float4 (max |e|, node, sum e^2, sum truth^2) per
+// (row, column block), which recon_score_frames_kernel combines -- the sums in fp64.  No atomics: two launches are bitwise equal.
+// ------------------------------------------------------------------------------------------
+// the error of one element: exactly one fp32 subtraction of the stored value (never contracted with the multiplication by
+// 1 / scale inside recon_phys_val: F - truth formed from the stored field F has the same bits)
+__device__ __forceinline__ float recon_score_err(float val, float truth) {
+#pragma clang fp contract(off)
+    return val - truth;
+}
+
+// No occupancy asked for, unlike recon_summary_kernel: 8 x (max, t, sum e, sum e^2) per thread plus the truth of two rows in flight take
+// 138 VGPRs (bf16; fp32 143) with all outputs, 3 waves / SIMD, no scratch; held to 128 the kernel spilled 44 bytes per lane and was
+// slower (0.537 against 0.464 ms).  Node or frame outputs alone stay under 128 and run at 4 waves.
+template <typename T, bool NODE, bool FRAME>
+__global__ __launch_bounds__(256) void recon_score_kernel(const GNParams p, const ReconPhys q, const float* __restrict__ truth, const ReconScore o) {
+    const GNCtx c = gn_ctx(p);          // gridDim.y == 1: t_lo = 0, t_hi = T
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);
+    // no early return for the lanes past C (see recon_summary_kernel): they load neither y nor truth and carry the neutral element
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        gam[e] = c.col_ok ? p.gamma[c.c0 + e] : 0.f; bet[e] = c.col_ok ? p.beta[c.c0 + e] : 0.f;
+        mn[e] = c.col_ok ? q.mn[c.c0 + e] : 0.f; inv[e] = c.col_ok ? recon_phys_inv(q.scale[c.c0 + e]) : 0.f;
+    }
+    float vmax[8], vsum[8], vsq[8];
+    int tmax[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { vmax[e] = -INFINITY; tmax[e] = RS_NO_INDEX; vsum[e] = 0.f; vsq[e] = 0.f; }
+    const T* y = reinterpret_cast<const T*>(p.y);
+    float4* const fpart = reinterpret_cast<float4*>(o.work);
+    for (int t0 = 0; t0 < p.T; t0 += 2 * c.RL) {          // block-uniform trip count; two rows per round, loads first
+        const int ta = t0 + c.ty, tb = ta + c.RL;
+        const bool oka = c.col_ok && ta < p.T, okb = c.col_ok && tb < p.T;
+        const long m0 = (long)c.b * p.T + ta, m1 = m0 + c.RL;
+        Raw8<T> r0, r1;
+        Raw8<float> w0, w1;
+        raw_zero(r0); raw_zero(r1); raw_zero(w0); raw_zero(w1);
+        if (oka) { raw_load(y + m0 * p.ldy + c.c0, r0); raw_load(truth + m0 * p.C + c.c0, w0); }
+        if (okb) { raw_load(y + m1 * p.ldy + c.c0, r1); raw_load(truth + m1 * p.C + c.c0, w1); }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool ok = u ? okb : oka;
+            const int t = u ? tb : ta;
+            float fmx = -INFINITY, fse = 0.f, fst = 0.f;
+            int imx = RS_NO_INDEX;
+            if (ok) {
+                float v[8], w[8];
+                raw_unpack(u ? r1 : r0, v);
+                raw_unpack(u ? w1 : w0, w);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // squares rounded once and then added (no fused multiply-add, which the compiler would form in some instantiations
+                    // and not in others): every subset of the outputs gives the same bits
+#pragma clang fp contract(off)
+                    const float d = recon_score_err(recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]), w[e]);
+                    const float a = fabsf(d);
+                    if constexpr (NODE) {          // this thread's rows come in ascending t: a strict comparison keeps the first
+                        if (a > vmax[e]) { vmax[e] = a; tmax[e] = t; }
+                        vsum[e] += d;
+                        vsq[e] += d * d;
+                    }
+                    if constexpr (FRAME) {         // ascending n
+                        if (a > fmx) { fmx = a; imx = c.c0 + e; }
+                        fse += d * d;
+                        fst += w[e] * w[e];
+                    }
+                }
+            }
+            if constexpr (FRAME) {
+                // the row's maximum (in the last lane of the CV) back to all of its lanes; the smallest index among the lanes that hold it wins
+                const int last = ((int)threadIdx.x & 63) | (p.CV - 1);
+                const float rmx = __shfl(lane_max_f(fmx, p.CV), last, 64);
+                const int rimx = lane_min_i(fmx == rmx ? imx : RS_NO_INDEX, p.CV);
+                const float rse = lane_sum_f(fse, p.CV), rst = lane_sum_f(fst, p.CV);
+                if (c.tx == p.CV - 1 && t < p.T)
+                    fpart[((long)c.b * p.T + t) * gridDim.x + blockIdx.x] = make_float4(rmx, __int_as_float(rimx), rse, rst);
+            }
+        }
+    }
+    if constexpr (NODE) {
+        // across the block's row lanes, in lane order; row lane 0 ends up with the result and stores it
+        __shared__ float smv[2048];
+        __shared__ int smi[2048];
+        const int slot = (c.ty * p.CV + c.tx) * 8;
+        const bool owner = c.ty == 0 && c.col_ok;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { smv[slot + e] = vmax[e]; smi[slot + e] = tmax[e]; }
+        __syncthreads();
+        if (owner) {
+            for (int r = 1; r < c.RL; ++r)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int j = (r * p.CV + c.tx) * 8 + e;
+                    ext_take<true>(vmax[e], tmax[e], smv[j], smi[j]);
+                }
+        }
+        __syncthreads();
+        float* const sms = reinterpret_cast<float*>(smi);          // the two sums side by side
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { smv[slot + e] = vsum[e]; sms[slot + e] = vsq[e]; }
+        __syncthreads();
+        if (owner) {
+            for (int r = 1; r < c.RL; ++r)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int j = (r * p.CV + c.tx) * 8 + e;
+                    vsum[e] += smv[j];
+                    vsq[e] += sms[j];
+                }
+            const float ft = (float)p.T;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { vsum[e] = vsum[e] / ft; vsq[e] = vsq[e] / ft; }          // the one division of each mean
+            if (o.node_err) {
+                float* d = o.node_err + (long)c.b * 3 * p.C + c.c0;
+                store8(d, vmax); store8(d + p.C, vsum); store8(d + 2L * p.C, vsq);
+            }
+            if (o.node_when) {
+                int* d = o.node_when + (long)c.b * p.C + c.c0;
+                *reinterpret_cast<int4*>(d) = make_int4(tmax[0], tmax[1], tmax[2], tmax[3]);
+                *reinterpret_cast<int4*>(d + 4) = make_int4(tmax[4], tmax[5], tmax[6], tmax[7]);
+            }
+        }
+    }
+}
+
+// frame partials [rows = B*T][nblk] of (max |e|, node, sum e^2, sum truth^2) -> frame_err [rows][3] (max |e|, mean e^2, mean truth^2),
+// frame_where [rows]; one wave per row.  The sums: each lane adds its partials in ascending block order in fp64, then the lanes in
+// a fixed xor tree (a + b is commutative: every lane holds the same bits), one division by C, rounded to fp32 once.
+__global__ __launch_bounds__(256) void recon_score_frames_kernel(const float4* part, int rows, int nblk, int C, float* frame_err, int* frame_where) {
+    const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float fmx = -INFINITY;
+    int imx = RS_NO_INDEX;
+    double se = 0.0, st = 0.0;
+    if (row < rows) {          // wave-uniform
+        for (int j = lane; j < nblk; j += 64) {
+            const float4 v = part[(long)row * nblk + j];
+            ext_take<true>(fmx, imx, v.x, __float_as_int(v.y));
+            se += (double)v.z;
+            st += (double)v.w;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float omx = __shfl_xor(fmx, off, 64);
+        const int oimx = __shfl_xor(imx, off, 64);
+        ext_take<true>(fmx, imx, omx, oimx);
+        se += __shfl_xor(se, off, 64);
+        st += __shfl_xor(st, off, 64);
+    }
+    if (row < rows && lane == 0) {
+        if (frame_err) {
+            frame_err[3L * row] = fmx; frame_err[3L * row + 1] = (float)(se / (double)C); frame_err[3L * row + 2] = (float)(st / (double)C);
+        }
+        if (frame_where) frame_where[row] = imx;
+    }
+}
+
+// p as for ew_recon_physical; truth fp32 dense [B][T][C]; o: any subset of the four outputs (ReconScore, sgv_ew.h), o.work =
+// ew_recon_summary_work_floats floats when a frame output is asked for.  Non-zero (nothing launched): -1 null input, -2 no output,
+// -3 bad shape, -4 y / truth / a node output / work not 16-byte aligned or a frame output not 4-byte aligned, -5 frame output
+// without workspace
+int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, const float* truth, const ReconScore& o, hipStream_t s) {
+    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn || !truth) return -1;
+    const bool node = o.node_err || o.node_when, frame = o.frame_err || o.frame_where;
+    if (!node && !frame) return -2;
+    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)truth | (uintptr_t)o.node_err | (uintptr_t)o.node_when | (uintptr_t)o.work) & 15) return -4;
+    if (((uintptr_t)o.frame_err | (uintptr_t)o.frame_where) & 3) return -4;
+    if (frame && !o.work) return -5;
+    p.Cg = p.C / p.G;
+    const ReconPhys q = {scale, mn, nullptr};
+    const RSGeom g = rs_geom(p.C);
+    p.CV = g.CV;
+    const dim3 grid(g.colblocks, 1, p.B);
+#define RS_LAUNCH(TT, NODE, FRAME) hipLaunchKernelGGL((recon_score_kernel<TT, NODE, FRAME>), grid, dim3(256), 0, s, p, q, truth, o)
+    if (dtype == 1) { if (node && frame) RS_LAUNCH(bf16_t, true, true); else if (node) RS_LAUNCH(bf16_t, true, false); else RS_LAUNCH(bf16_t, false, true); }
+    else { if (node && frame) RS_LAUNCH(float, true, true); else if (node) RS_LAUNCH(float, true, false); else RS_LAUNCH(float, false, true); }
+#undef RS_LAUNCH
+    if (frame)
+        hipLaunchKernelGGL(recon_score_frames_kernel, dim3(cdiv_i((long)p.B * p.T, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(o.work),
+                           p.B * p.T, g.colblocks, p.C, o.frame_err, o.frame_where);
     return 0;
 }
 

@@ -125,6 +125,16 @@ struct ReconSummary {
 };
 size_t ew_recon_summary_work_floats(int B, int T, int C);
 int ew_recon_summary(int dtype, GNParams p, const float* scale, const float* mn, const ReconSummary& o, hipStream_t s);
+// recon head -> the error of the physical field against truth (fp32 dense [B][T][C], physical units, 16-byte aligned, finite: not
+// checked), neither stored: e = val - truth, val as ew_recon_physical stores it.  Any subset of the outputs, null = not computed:
+// node_err fp32 [B][3][C] (max_t |e|, mean_t e, mean_t e^2), node_when int32 [B][C] (t of max |e|; smallest t on a tie), frame_err
+// fp32 [B][T][3] (max_n |e|, mean_n e^2, mean_n truth^2), frame_where int32 [B][T] (node of max |e|; smallest on a tie).
+// work: ew_recon_summary_work_floats floats, 16-byte aligned, needed for a frame output.
+struct ReconScore {
+    float* node_err = nullptr; int* node_when = nullptr; float* frame_err = nullptr; int* frame_where = nullptr;
+    float* work = nullptr;
+};
+int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, const float* truth, const ReconScore& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

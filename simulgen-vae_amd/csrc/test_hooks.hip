@@ -312,6 +312,36 @@ int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, con
     hipFree(work);
     return rc;
 }
+int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                         const float* scale, const float* min, const float* truth, const sgv_score_out* out, int B, int T, int C,
+                         void* stream) {
+    const char* me = "sgv_test_recon_score";
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
+    if (!y || !sums || !gamma || !beta || !scale || !min || !truth || !out) return fail(SGV_ERR_ARG, "%s: null argument", me);
+    if (!out->node_err && !out->node_when && !out->frame_err && !out->frame_where) return fail(SGV_ERR_ARG, "%s: all four outputs are NULL", me);
+    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
+    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
+    if ((((uintptr_t)y | (uintptr_t)truth | (uintptr_t)out->node_err | (uintptr_t)out->node_when) & 15) ||
+        (((uintptr_t)out->frame_err | (uintptr_t)out->frame_where) & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (y, truth, node_err / node_when 16 bytes, frame_err / frame_where 4)", me);
+    GNParams p;
+    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
+    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
+    p.y = y; p.ldy = ldy; p.sums = sums;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t stat_floats = align_up(ew_gn_part_floats(B, T, C), 4);          // [statistics workspace | frame partials]
+    float* work = nullptr;
+    HIPCHK(hipMalloc((void**)&work, sizeof(float) * (stat_floats + ew_recon_summary_work_floats(B, T, C))));
+    p.part = work;
+    ReconScore o;
+    o.node_err = out->node_err; o.node_when = out->node_when; o.frame_err = out->frame_err; o.frame_where = out->frame_where;
+    o.work = work + stat_floats;
+    int r = ew_gn_stats(dtype, p, s);
+    if (!r) r = ew_recon_score(dtype, p, scale, min, truth, o, s);
+    const int rc = ew_hook_done(r, me, stream);
+    hipFree(work);
+    return rc;
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

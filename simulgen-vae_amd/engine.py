@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -62,8 +62,14 @@ class SummaryOut(C.Structure):
                 ("probes", C.c_void_p)]
 
 
+class ScoreOut(C.Structure):
+    """sgv_score_out (include/sgvae.h): the four optional outputs of sgv_score, device pointers"""
+    _fields_ = [("node_err", C.c_void_p), ("node_when", C.c_void_p), ("frame_err", C.c_void_p), ("frame_where", C.c_void_p)]
+
+
 MAX_PROBES = 4096
 SUMMARY_PARTS = ("node", "frame", "probes")      # `want` of Engine.summarize
+SCORE_PARTS = ("node", "frame")                  # `want` of Engine.score
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")      # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -113,6 +119,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_generate.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
     lib.sgv_set_probes.argtypes = [vp, vp, i32]
     lib.sgv_summarize.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.POINTER(SummaryOut)]
+    lib.sgv_score.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, C.POINTER(ScoreOut)]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -176,6 +183,7 @@ def load_library(path: str = LIB_PATH):
                                         i32, i32, i32, i32, vp]
     lib.sgv_test_recon_physical.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_summary.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, C.POINTER(SummaryOut), vp, i32, i32, i32, i32, vp]
+    lib.sgv_test_recon_score.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, C.POINTER(ScoreOut), i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -499,6 +507,43 @@ class Engine:
         so = SummaryOut(**{name: v.data_ptr() for name, v in res.items()})
         _check(self.lib, self.lib.sgv_summarize(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
                                                 C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), C.byref(so)), "sgv_summarize")
+        self.batch = B
+        return res
+
+    def score(self, z, xs, scale, min, truth, fix=True, want=SCORE_PARTS, out=None):
+        """The error of the field generate() would write against `truth` (contiguous fp32 CUDA [B, T, N], physical units), reduced by
+        the recon head's last pass itself: e = field - truth, one fp32 subtraction; neither is stored.  Same inputs and checks as
+        summarize().  want: any of "node", "frame".  Returns a dict of CUDA tensors:
+        node_err fp32 [B, 3, N] (max_t |e|, mean_t e, mean_t e^2) and node_when int32 [B, N] (t of the largest |e|);
+        frame_err fp32 [B, T, 3] (max_n |e|, mean_n e^2, mean_n truth^2) and frame_where int32 [B, T] (its node).  Ties go to the
+        smallest index.  truth must be finite (not checked).  out: a dict of such tensors to write into (those present are reused).
+        Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        want = tuple(want)
+        if not want or any(w not in SCORE_PARTS for w in want):
+            raise ValueError(f"want must name at least one of {SCORE_PARTS}, not {want!r}")
+        B, z, xs_t = self._latents(z, xs)
+        self._scaler(scale, min)
+        N, T = self.cfg.num_node, self.cfg.num_time
+        if not (t.is_tensor(truth) and truth.is_cuda and truth.dtype == t.float32 and truth.is_contiguous() and tuple(truth.shape) == (B, T, N)):
+            raise ValueError(f"truth must be a contiguous float32 CUDA tensor of shape {(B, T, N)}")
+        shapes = {}
+        if "node" in want:
+            shapes.update(node_err=((B, 3, N), t.float32), node_when=((B, N), t.int32))
+        if "frame" in want:
+            shapes.update(frame_err=((B, T, 3), t.float32), frame_where=((B, T), t.int32))
+        res = {}
+        for name, (shape, dt) in shapes.items():
+            v = None if out is None else out.get(name)
+            if v is None:
+                v = t.empty(shape, dtype=dt, device="cuda")
+            elif not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
+                raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
+            res[name] = v
+        so = ScoreOut(**{name: v.data_ptr() for name, v in res.items()})
+        _check(self.lib, self.lib.sgv_score(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
+                                            C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), C.c_void_p(truth.data_ptr()),
+                                            C.byref(so)), "sgv_score")
         self.batch = B
         return res
 

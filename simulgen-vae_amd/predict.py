@@ -17,6 +17,8 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     fields = s.predict_to_host(conditions)         # the same in pinned host memory, for P too large for the device
     summary = s.sweep(conditions, probes=[17, 4711])   # extrema per node / per time step, their indices, means, probe histories
                                                    # (DESIGN.md section 17): the fields are reduced by the pass that would store them
+    score = s.score(conditions, truth)             # error against held-out fields [P, T, N]: per node / per time step max |e|, bias, MSE,
+                                                   # per condition rmse / rel_l2 / max_abs, same fused pass
 """
 from __future__ import annotations
 
@@ -68,6 +70,37 @@ def probe_nodes(nodes, num_node):
     if bad.size:
         raise ValueError(f"probes[{int(bad[0])}] = {int(a[bad[0]])} is outside [0, {int(num_node)})")
     return a.astype(np.int32)
+
+
+def truth_fields(truth, P, T, N):
+    """The held-out fields of Surrogate.score: `truth` as given if it is a float32 array or tensor (host or device) of shape
+    [P, T, N]; anything else array-like is looked at through np.asarray.  ValueError naming the offending dimension or the dtype
+    otherwise.  numpy only: a tensor is judged by its shape and dtype attributes and not converted."""
+    a = truth if hasattr(truth, "shape") and hasattr(truth, "dtype") else np.asarray(truth)
+    shape = tuple(int(d) for d in a.shape)
+    if len(shape) != 3:
+        raise ValueError(f"truth: a [P, T, N] array is required, got shape {shape}")
+    for name, got, want in (("P", shape[0], P), ("T", shape[1], T), ("N", shape[2], N)):
+        if got != int(want):
+            raise ValueError(f"truth: dimension {name} is {got}, expected {name} = {int(want)} (shape {shape}, wanted [P, T, N] = {[int(P), int(T), int(N)]})")
+    if str(a.dtype).replace("torch.", "") != "float32":
+        raise ValueError(f"truth: dtype float32 is required, not {a.dtype}")
+    return a
+
+
+class ScoreResult:
+    """Surrogate.score's result for P conditions, device tensors; e = predicted field - truth.  node_max_abs / node_bias / node_mse
+    [P, N] fp32 (max over time of |e|, mean of e, mean of e^2 per node) and t_worst [P, N] int32 (the time step of the largest |e|);
+    frame_max_abs / frame_mse / frame_truth_ms [P, T] fp32 (max over the mesh of |e|, mean of e^2, mean of truth^2 per time step)
+    and n_worst [P, T] int32 (the node of the largest |e|); per condition rmse = sqrt(mean_t frame_mse) and
+    rel_l2 = sqrt(sum_t frame_mse / sum_t frame_truth_ms) [P] fp64 (inf / nan for a zero truth, as the division says) and
+    max_abs = max_t frame_max_abs [P] fp32."""
+    FIELDS = ("node_max_abs", "node_bias", "node_mse", "t_worst", "frame_max_abs", "frame_mse", "frame_truth_ms", "n_worst",
+              "rmse", "rel_l2", "max_abs")
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
 
 
 class SweepResult:
@@ -243,6 +276,43 @@ class Surrogate:
             t.cuda.current_stream().wait_stream(self._stream)
         return SweepResult(node_max=node[0], node_min=node[1], node_mean=node[2], t_max=when[0], t_min=when[1],
                            frame_max=frame[0], frame_min=frame[1], n_max=where[0], n_min=where[1], probes=hist)
+
+    def score(self, conditions, truth, mode="fix"):
+        """How wrong predict(conditions) is against held-out fields, without the fields: truth [P, T, N] fp32 in physical units (the
+        data set's own order; a CUDA tensor, or a host array / CPU tensor that is moved batch by batch on the engine stream as the
+        conditions are) -> a ScoreResult of device tensors.  The recon head's last pass subtracts the truth from the values
+        predict() would store (one fp32 subtraction each) and reduces the error in a fixed order: bitwise reproducible, ties to the
+        smallest index.  truth must be finite (not checked).  Batching, streams, the single input-range decision and `mode` are
+        sweep()'s: no host wait between batches."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        truth = truth_fields(truth, P, self.T, self.N)
+        if not t.is_tensor(truth):
+            truth = t.from_numpy(np.ascontiguousarray(truth))
+        f32 = dict(dtype=t.float32, device="cuda")
+        i32 = dict(dtype=t.int32, device="cuda")
+        node, when = t.empty((3, P, self.N), **f32), t.empty((P, self.N), **i32)          # the results: the caller's stream owns them
+        frame, where = t.empty((3, P, self.T), **f32), t.empty((P, self.T), **i32)
+        self._stream.wait_stream(t.cuda.current_stream())
+        with t.cuda.stream(self._stream):
+            b0 = min(self.batch, max(P, 1))
+            buf = dict(node_err=t.empty((b0, 3, self.N), **f32), frame_err=t.empty((b0, self.T, 3), **f32))
+            for lo in range(0, P, self.batch):
+                hi = min(P, lo + self.batch)
+                lat, xs = self._latents(self._batch(conditions, lo, hi), remap)
+                out = {k: v[:hi - lo] for k, v in buf.items()}
+                out.update(node_when=when[lo:hi], frame_where=where[lo:hi])          # the results' own layout: written in place
+                self.eng.score(lat, xs, self.data_scale, self.data_min, self._batch(truth, lo, hi).contiguous(), fix=mode == "fix", out=out)
+                node[:, lo:hi].copy_(out["node_err"].transpose(0, 1))
+                frame[:, lo:hi].copy_(out["frame_err"].permute(2, 0, 1))
+            mse64, tms64 = frame[1].double(), frame[2].double()
+            rmse = mse64.mean(dim=1).sqrt()
+            rel_l2 = (mse64.sum(dim=1) / tms64.sum(dim=1)).sqrt()
+            max_abs = frame[0].max(dim=1).values
+        if t.cuda.current_stream() != self._stream:
+            t.cuda.current_stream().wait_stream(self._stream)
+        return ScoreResult(node_max_abs=node[0], node_bias=node[1], node_mse=node[2], t_worst=when, frame_max_abs=frame[0],
+                           frame_mse=frame[1], frame_truth_ms=frame[2], n_worst=where, rmse=rmse, rel_l2=rel_l2, max_abs=max_abs)
 
     def predict_to_host(self, conditions, out=None, layout="TN", mode="fix"):
         """The same result in pinned host memory: two device batch buffers alternate, each batch's device-to-host copy runs on the

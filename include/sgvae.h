@@ -239,6 +239,36 @@ typedef struct {
  * Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
 int sgv_score(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
               const float* min_dev, const float* truth_dev, const sgv_score_out* out);
+/* Running statistics over many generated fields per (time step, node), the reduction along the batch axis: what a Monte-Carlo or
+ * design-space study keeps of thousands of draws.  Device pointers, every array dense [T][N] and 16-byte aligned (limit: [N],
+ * 4-byte aligned); three groups, each given completely or not at all (all NULL), at least one required:
+ *   moments  mean, m2  fp32   Welford's running mean and sum of squared deviations: variance = m2 / count
+ *   extrema  max, min  fp32   the envelope;  arg_max, arg_min int32: the index of the member that produced it, the earliest on a tie
+ *   exceed   limit     fp32 [N] (input, physical units);  exceed int32: the number of members with field > limit[n] (strict)
+ * The state belongs to the caller and persists across calls: the kernel reads, updates and writes it in place. */
+typedef struct {
+    float* mean;
+    float* m2;
+    float* max;
+    float* min;
+    int32_t* arg_max;
+    int32_t* arg_min;
+    const float* limit;
+    int32_t* exceed;
+} sgv_ensemble_state;
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the ensemble pass: sample b of the
+ * batch is member count_before + b, and the value sgv_generate would store for it (SGV_LAYOUT_TN) is merged into *st, members in
+ * ascending order, all in fp32 with every operation rounded on its own (k = index + 1, r = 1.0f / k, d = x - mean,
+ * mean += d * r, m2 += d * (x - mean); strict comparisons for the extrema and the limit).  With count_before == 0 the state is
+ * not read: it starts empty.  The result does not depend on where batch boundaries fall: any cut of the same members into calls
+ * gives the same bits.  That holds for the noise too: where the caller has not set it (sgv_set_eps), the decoder's noise of a
+ * member is a function of (seed, member index, site) alone -- the rows count_before + b of the streams the first call after
+ * sgv_seed draws from, so a single call with count_before == 0 right after sgv_seed sees the noise sgv_generate would -- and the
+ * engine's draw position is left where it is.  No atomics, no workspace, nothing allocated.  SGV_ERR_ARG before anything is enqueued: e, z_dev,
+ * scale_dev, min_dev or st NULL, no group or half a group, a misaligned pointer, count_before < 0 or count_before + batch > 2^24,
+ * the checks of sgv_decode.  Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
+int sgv_ensemble(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                 const float* min_dev, long count_before, const sgv_ensemble_state* st);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -513,6 +543,13 @@ int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, con
 int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                          const float* scale, const float* min, const float* truth, const sgv_score_out* out, int B, int T, int C,
                          void* stream);
+/* The kernel of sgv_ensemble on caller-owned buffers: inputs as sgv_test_recon_physical, then the statistics of y and the ensemble
+ * pass into *st (shapes of sgv_ensemble_state with N = C).  SGV_ERR_ARG, nothing launched: a NULL input, st NULL, no group or half
+ * a group, B or T < 1, C < 8 or C % 8 != 0, a bad row stride, a misaligned pointer (y and the state arrays 16 bytes; limit 4),
+ * count_before < 0 or count_before + B > 2^24. */
+int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, long count_before, const sgv_ensemble_state* st, int B, int T,
+                            int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

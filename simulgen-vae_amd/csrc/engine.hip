@@ -890,13 +890,23 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 // Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen` (sgv_generate),
 // the recon head's convolution and statistics followed by the physical-field pass instead of the loss tail -- or, with gen->sum
 // (sgv_summarize), by the summary pass: its frame partials go to e->colpart, which nothing uses once the statistics are done -- or,
-// with gen->score and gen->truth (sgv_score), by the error pass against the truth, with the same workspace.
-struct GenOut { const float* scale; const float* mn; int layout; float* out; const ReconSummary* sum = nullptr; const ReconScore* score = nullptr; const float* truth = nullptr; };
+// with gen->score and gen->truth (sgv_score), by the error pass against the truth, with the same workspace -- or, with gen->ens
+// (sgv_ensemble), by the ensemble pass, which merges the batch into the caller's running state and needs no workspace.
+struct GenOut {
+    const float* scale; const float* mn; int layout; float* out;
+    const ReconSummary* sum = nullptr; const ReconScore* score = nullptr; const float* truth = nullptr;
+    const ReconEnsemble* ens = nullptr; long ens_count = 0;
+};
 static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
+    // sgv_ensemble: the noise of member m is a function of (seed, m, site) alone -- the rows count_before + b of the streams the first
+    // call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size
+    const bool ens = gen && gen->ens;
+    uint64_t ens_draw = 0;
     for (int s = 1; s < n_st; ++s) {
-        if (!e->eps_set[s]) ew_randn(e->eps[s], M * e->dec[s], e->seed, (e->draw++) * 8 + s, e->stream, (long)e->T * e->dec[s], e->shard_world, e->shard_rank);
+        if (!e->eps_set[s]) ew_randn(e->eps[s], M * e->dec[s], e->seed, (ens ? ens_draw++ : e->draw++) * 8 + s, e->stream, (long)e->T * e->dec[s], e->shard_world, e->shard_rank,
+                                     ens ? gen->ens_count : 0);
     }
     {
         const Layer& l = e->layers[e->start_lin];
@@ -957,6 +967,11 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenO
         ScopedTimer tm(e, "recon_score", nullptr);
         const int r = ew_recon_score(e->dt, p, gen->scale, gen->mn, gen->truth, o, e->stream);
         return r ? fail(SGV_ERR_ARG, "sgv_score: the error pass rejected its arguments (%d)", r) : 0;
+    }
+    if (gen && gen->ens) {
+        ScopedTimer tm(e, "recon_ensemble", nullptr);
+        const int r = ew_recon_ensemble(e->dt, p, gen->scale, gen->mn, gen->ens_count, *gen->ens, e->stream);
+        return r ? fail(SGV_ERR_ARG, "sgv_ensemble: the ensemble pass rejected its arguments (%d)", r) : 0;
     }
     if (gen) {          // no loss, no read of x_in, no x_hat: the fp32 physical field goes straight to the caller's buffer
         ScopedTimer tm(e, "recon_phys", nullptr);
@@ -1106,6 +1121,32 @@ int sgv_score(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch,
     o.node_err = out->node_err; o.node_when = out->node_when; o.frame_err = out->frame_err; o.frame_where = out->frame_where;
     GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr};
     gen.score = &o; gen.truth = truth_dev;
+    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
+    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
+    return SGV_OK;
+}
+
+int sgv_ensemble(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                 const float* min_dev, long count_before, const sgv_ensemble_state* st) {
+    if (!e || !z_dev || !scale_dev || !min_dev || !st) return fail(SGV_ERR_ARG, "sgv_ensemble: null argument");
+    const bool mo = st->mean || st->m2, ex = st->max || st->min || st->arg_max || st->arg_min, ec = st->exceed || st->limit;
+    if (!mo && !ex && !ec) return fail(SGV_ERR_ARG, "sgv_ensemble: no group of the state is given");
+    if ((mo && !(st->mean && st->m2)) || (ex && !(st->max && st->min && st->arg_max && st->arg_min)) || (ec && !(st->exceed && st->limit)))
+        return fail(SGV_ERR_ARG, "sgv_ensemble: half a group (mean + m2, max + min + arg_max + arg_min, limit + exceed go together)");
+    if ((((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->max | (uintptr_t)st->min | (uintptr_t)st->arg_max | (uintptr_t)st->arg_min |
+          (uintptr_t)st->exceed) & 15) || ((uintptr_t)st->limit & 3))
+        return fail(SGV_ERR_ARG, "sgv_ensemble: misaligned pointer (the state arrays 16 bytes, limit 4)");
+    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
+        return fail(SGV_ERR_ARG, "sgv_ensemble: count_before = %ld with batch = %d is outside [0, 2^24]", count_before, batch);
+    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_ensemble"));
+    // as sgv_generate: the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
+    e->have_fwd = false;
+    e->fwd_train = false;
+    ReconEnsemble o;
+    o.mean = st->mean; o.m2 = st->m2; o.vmax = st->max; o.vmin = st->min; o.imax = st->arg_max; o.imin = st->arg_min;
+    o.limit = st->limit; o.exceed = st->exceed;
+    GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr};
+    gen.ens = &o; gen.ens_count = count_before;
     CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
     for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
     return SGV_OK;

@@ -1775,6 +1775,176 @@ int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, c
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Surrogate ensemble statistics (sgv_ensemble): the reduction along the batch axis.  For every (t, n) the values the members of
+// a launch would store are merged, one member after the other in ascending order, into a running state [T][C] that outlives the
+// launch: Welford mean / M2, maximum / minimum with the index of the member that produced each, and the count of members above a
+// per-node limit.  Member b of a launch has index m = count_before + b; every update is sequential in m and the state is stored
+// in the types it is held in, so any cut of the same members into launches gives the same bits.
+// Geometry: the columns of rs_geom (CV = 64 column lanes x 4 row lanes for C >= 512, 8 channels per thread), grid (column blocks,
+// row chunks over T).  A thread owns its (t, octet) for all members: no reduction across threads, no LDS traffic besides the
+// block's table of (mean, rstd) per (member, group) -- members have different GroupNorm statistics -- which is filled once per
+// block through gn_mean_rstd, and 1 / k per member.  With count_before == 0 the state is not read.
+// ------------------------------------------------------------------------------------------
+constexpr int EN_MAX_B = 32;          // members per launch (the table); ew_recon_ensemble cuts a larger batch into several launches
+constexpr int EN_FLIGHT = 4;          // members whose y loads are issued before the first is used
+
+// 3 waves / SIMD asked for: unasked, the kernel with all groups takes 176 VGPRs (bf16; fp32 192) and runs at 2 waves;
+// held to 168 it keeps 12 bytes per lane in scratch (fp32 68) and is faster, 0.339 against 0.365 ms in one job -- the pass is bound by memory
+// and the third wave hides more latency than the three spilled dwords cost.  Every other instantiation is below 168 anyway.
+template <typename T, bool MOMENTS, bool EXTREMA, bool EXCEED>
+__global__ __launch_bounds__(256, 3) void recon_ensemble_kernel(const GNParams p, const ReconPhys q, const ReconEnsemble o, const int count_before) {
+    __shared__ float2 tab[EN_MAX_B][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of member b
+    __shared__ float rk[EN_MAX_B];                               // 1 / k, k = count_before + b + 1: one correctly rounded division per member
+    for (int i = threadIdx.x; i < p.B * p.G; i += 256) {
+        float m, r;
+        gn_mean_rstd(p, i / p.G, i % p.G, m, r);
+        tab[i / p.G][i % p.G] = make_float2(m, r);
+    }
+    if ((int)threadIdx.x < p.B) rk[threadIdx.x] = 1.0f / (float)(count_before + (int)threadIdx.x + 1);
+    __syncthreads();
+    const GNCtx c = gn_ctx(p);          // blockIdx.z == 0; c.b is not a member here
+    if (!c.col_ok) return;              // no barrier below: lanes past C touch nothing
+    float gam[8], bet[8], mn[8], inv[8], lim[8];
+    unsigned long long gidx = 0;        // the group of each of the 8 channels, one byte each
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        gam[e] = p.gamma[c.c0 + e]; bet[e] = p.beta[c.c0 + e];
+        mn[e] = q.mn[c.c0 + e]; inv[e] = recon_phys_inv(q.scale[c.c0 + e]);
+        lim[e] = EXCEED ? o.limit[c.c0 + e] : 0.f;
+        gidx |= (unsigned long long)min((c.c0 + e) / p.Cg, p.G - 1) << (8 * e);
+    }
+    const int g_lo = (int)(gidx & 0xff), g_hi = (int)(gidx >> 56);
+    const bool two = p.Cg >= 8;          // block-uniform: the octet lies in at most two groups, g_lo and g_hi
+    const T* y = reinterpret_cast<const T*>(p.y);
+    const bool fresh = count_before == 0;
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += c.RL) {
+        const long at = (long)t * p.C + c.c0;
+        float mean[8], m2[8], vmax[8], vmin[8];
+        int imax[8], imin[8], exc[8];
+        if (fresh) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { mean[e] = 0.f; m2[e] = 0.f; vmax[e] = -INFINITY; vmin[e] = INFINITY; imax[e] = 0; imin[e] = 0; exc[e] = 0; }
+        } else {
+            if constexpr (MOMENTS) { load8(o.mean + at, mean); load8(o.m2 + at, m2); }
+            if constexpr (EXTREMA) {
+                load8(o.vmax + at, vmax); load8(o.vmin + at, vmin);
+                const int4 a0 = *reinterpret_cast<const int4*>(o.imax + at), a1 = *reinterpret_cast<const int4*>(o.imax + at + 4);
+                const int4 b0 = *reinterpret_cast<const int4*>(o.imin + at), b1 = *reinterpret_cast<const int4*>(o.imin + at + 4);
+                imax[0] = a0.x; imax[1] = a0.y; imax[2] = a0.z; imax[3] = a0.w; imax[4] = a1.x; imax[5] = a1.y; imax[6] = a1.z; imax[7] = a1.w;
+                imin[0] = b0.x; imin[1] = b0.y; imin[2] = b0.z; imin[3] = b0.w; imin[4] = b1.x; imin[5] = b1.y; imin[6] = b1.z; imin[7] = b1.w;
+            }
+            if constexpr (EXCEED) {
+                const int4 a0 = *reinterpret_cast<const int4*>(o.exceed + at), a1 = *reinterpret_cast<const int4*>(o.exceed + at + 4);
+                exc[0] = a0.x; exc[1] = a0.y; exc[2] = a0.z; exc[3] = a0.w; exc[4] = a1.x; exc[5] = a1.y; exc[6] = a1.z; exc[7] = a1.w;
+            }
+        }
+        for (int b0 = 0; b0 < p.B; b0 += EN_FLIGHT) {          // EN_FLIGHT members per round, loads first
+            Raw8<T> r[EN_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < EN_FLIGHT; ++u)                  // past the last member: its row again, loaded and not used
+                raw_load(y + ((long)min(b0 + u, p.B - 1) * p.T + t) * p.ldy + c.c0, r[u]);
+#pragma unroll
+            for (int u = 0; u < EN_FLIGHT; ++u) {
+                const int b = b0 + u;
+                if (b >= p.B) break;
+                const int m = count_before + b;
+                const float rkb = rk[b];
+                float v[8], gm[8], gr[8];
+                raw_unpack(r[u], v);
+                if (two) {
+                    const float2 lo = tab[b][g_lo], hi = tab[b][g_hi];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const bool up = (int)((gidx >> (8 * e)) & 0xff) != g_lo;
+                        gm[e] = up ? hi.x : lo.x; gr[e] = up ? hi.y : lo.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float2 w = tab[b][(int)((gidx >> (8 * e)) & 0xff)];
+                        gm[e] = w.x; gr[e] = w.y;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // every product and sum below rounds on its own (no fused multiply-add, which the compiler would form in some
+                    // instantiations and not in others), and x is the stored value before it meets the state
+#pragma clang fp contract(off)
+                    const float x = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
+                    if constexpr (MOMENTS) {          // Welford, one member at a time
+                        const float d = x - mean[e];
+                        mean[e] = mean[e] + d * rkb;
+                        m2[e] = m2[e] + d * (x - mean[e]);
+                    }
+                    if constexpr (EXTREMA) {          // ascending m: a strict comparison keeps the earliest member
+                        if (x > vmax[e]) { vmax[e] = x; imax[e] = m; }
+                        if (x < vmin[e]) { vmin[e] = x; imin[e] = m; }
+                    }
+                    if constexpr (EXCEED) exc[e] += x > lim[e] ? 1 : 0;
+                }
+            }
+        }
+        if constexpr (MOMENTS) { store8(o.mean + at, mean); store8(o.m2 + at, m2); }
+        if constexpr (EXTREMA) {
+            store8(o.vmax + at, vmax); store8(o.vmin + at, vmin);
+            *reinterpret_cast<int4*>(o.imax + at) = make_int4(imax[0], imax[1], imax[2], imax[3]);
+            *reinterpret_cast<int4*>(o.imax + at + 4) = make_int4(imax[4], imax[5], imax[6], imax[7]);
+            *reinterpret_cast<int4*>(o.imin + at) = make_int4(imin[0], imin[1], imin[2], imin[3]);
+            *reinterpret_cast<int4*>(o.imin + at + 4) = make_int4(imin[4], imin[5], imin[6], imin[7]);
+        }
+        if constexpr (EXCEED) {
+            *reinterpret_cast<int4*>(o.exceed + at) = make_int4(exc[0], exc[1], exc[2], exc[3]);
+            *reinterpret_cast<int4*>(o.exceed + at + 4) = make_int4(exc[4], exc[5], exc[6], exc[7]);
+        }
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: any of the three groups of ReconEnsemble (sgv_ew.h), each complete;
+// count_before members are already in the state (0: the state is not read).  A batch of more than EN_MAX_B members goes out as
+// several launches with count_before advanced, which is bitwise the same.  Non-zero (nothing launched): -1 null input, -2 no
+// group or half a group, -3 bad shape, -4 y or a state array not 16-byte aligned (limit 4), -5 count_before < 0 or
+// count_before + B > 2^24 (beyond that (float)k is not exact)
+int ew_recon_ensemble(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconEnsemble& o, hipStream_t s) {
+    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn) return -1;
+    const bool mo = o.mean || o.m2, ex = o.vmax || o.vmin || o.imax || o.imin, ec = o.exceed || o.limit;
+    if (!mo && !ex && !ec) return -2;
+    if ((mo && !(o.mean && o.m2)) || (ex && !(o.vmax && o.vmin && o.imax && o.imin)) || (ec && !(o.exceed && o.limit))) return -2;
+    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.mean | (uintptr_t)o.m2 | (uintptr_t)o.vmax | (uintptr_t)o.vmin | (uintptr_t)o.imax | (uintptr_t)o.imin |
+         (uintptr_t)o.exceed) & 15) return -4;
+    if ((uintptr_t)o.limit & 3) return -4;
+    if (count_before < 0 || count_before + p.B > (1L << 24)) return -5;
+    p.Cg = p.C / p.G;
+    const ReconPhys q = {scale, mn, nullptr};
+    const RSGeom g = rs_geom(p.C);
+    p.CV = g.CV;
+    const int RL = 256 / g.CV;
+    const int rowchunks = std::max(1, std::min(cdiv_i(p.T, RL), cdiv_i(2048, g.colblocks)));      // >= ~2048 blocks, at least one row per row lane
+    const dim3 grid(g.colblocks, rowchunks, 1);
+    const int B = p.B;
+    const size_t esz = dtype == 1 ? 2 : 4;
+    for (int b0 = 0; b0 < B; b0 += EN_MAX_B) {
+        GNParams ps = p;
+        ps.B = std::min(EN_MAX_B, B - b0);
+        ps.y = (const char*)p.y + (size_t)b0 * p.T * p.ldy * esz;
+        ps.sums = p.sums + (size_t)b0 * p.G * 2;
+        const int cb = (int)count_before + b0;
+#define EN_LAUNCH(TT, MO, EX, EC) hipLaunchKernelGGL((recon_ensemble_kernel<TT, MO, EX, EC>), grid, dim3(256), 0, s, ps, q, o, cb)
+#define EN_PICK(TT)                                                                                                   \
+        do {                                                                                                          \
+            if (mo && ex && ec) EN_LAUNCH(TT, true, true, true); else if (mo && ex) EN_LAUNCH(TT, true, true, false); \
+            else if (mo && ec) EN_LAUNCH(TT, true, false, true); else if (ex && ec) EN_LAUNCH(TT, false, true, true); \
+            else if (mo) EN_LAUNCH(TT, true, false, false); else if (ex) EN_LAUNCH(TT, false, true, false);           \
+            else EN_LAUNCH(TT, false, false, true);                                                                   \
+        } while (0)
+        if (dtype == 1) EN_PICK(bf16_t); else EN_PICK(float);
+#undef EN_PICK
+#undef EN_LAUNCH
+    }
+    return 0;
+}
+
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s) {
     float* const ws = p.part;
     const bool own_dots = mode != 0 && p.cdot && !p.cdot_part;
@@ -1875,25 +2045,26 @@ int ew_transpose(int src_dtype, int dst_dtype, const void* src, void* dst, int B
 // standard normals into an fp32 buffer [rows][per_row] (Philox keyed by seed/stream).  Row b is sample b of this rank's batch =
 // sample b * world + rank of the GLOBAL batch (shards are r::world), and its elements take the counters
 // (global row) * per_row + j: a world of N ranks with B / N samples each draws exactly the noise one rank draws for B samples.
-// per_row % 4 == 0 (one Philox block makes 4 normals); world = 1, rank = 0: element i <- block i / 4 as before.
-__global__ __launch_bounds__(256) void randn_kernel(float* out, long n, long per_row, int world, int rank, uint64_t seed, uint64_t stream) {
+// per_row % 4 == 0 (one Philox block makes 4 normals); world = 1, rank = 0: element i <- block i / 4 as before.  row0: row b of
+// the buffer is sample row0 + b of this rank (sgv_ensemble: a member's noise follows its index, not its place in a batch).
+__global__ __launch_bounds__(256) void randn_kernel(float* out, long n, long per_row, int world, int rank, uint64_t seed, uint64_t stream, long row0) {
     const long n4 = (n + 3) / 4;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const long e0 = i * 4;
         const long b = e0 / per_row, j = e0 - b * per_row;
         float r[4];
-        philox_normal4(seed, stream, (uint64_t)(((b * world + rank) * per_row + j) >> 2), r);
+        philox_normal4(seed, stream, (uint64_t)((((b + row0) * world + rank) * per_row + j) >> 2), r);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (e0 + e < n) out[e0 + e] = r[e];
     }
 }
-int ew_randn(float* out, long n, uint64_t seed, uint64_t stream, hipStream_t s, long per_row, int world, int rank) {
+int ew_randn(float* out, long n, uint64_t seed, uint64_t stream, hipStream_t s, long per_row, int world, int rank, long row0) {
     if (per_row <= 0 || per_row % 4 || world < 1) { per_row = n > 0 ? ((n + 3) / 4) * 4 : 4; world = 1; rank = 0; }
     int blocks = cdiv_i((n + 3) / 4, 256);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(randn_kernel, dim3(blocks), dim3(256), 0, s, out, n, per_row, world, rank, seed, stream);
+    hipLaunchKernelGGL(randn_kernel, dim3(blocks), dim3(256), 0, s, out, n, per_row, world, rank, seed, stream, row0);
     return 0;
 }
 

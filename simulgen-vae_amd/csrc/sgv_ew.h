@@ -135,12 +135,26 @@ struct ReconScore {
     float* work = nullptr;
 };
 int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, const float* truth, const ReconScore& o, hipStream_t s);
+// recon head -> running statistics over the members of a batch (and of the batches before it) per (t, channel), the field never
+// stored: the values ew_recon_physical would store (layout [B][T][C]) are merged member after member, in fp32, into a state that
+// persists across launches.  Three groups, any subset, each complete; every array dense [T][C], 16-byte aligned:
+//   moments  mean, m2 fp32: Welford, k = index + 1, r = 1.0f / k, d = x - mean, mean += d * r, m2 += d * (x - mean), each rounded
+//   extrema  vmax, vmin fp32 and imax, imin int32: strict comparisons, so the earliest member keeps a tie; the index of the member
+//   exceed   limit fp32 [C] (input) and exceed int32: the count of members with x > limit[channel]
+// Member b has index count_before + b.  With count_before == 0 the state is not read (mean = m2 = 0, extrema -inf / +inf, indices
+// and counts 0).  Any cut of the same members into launches gives the same bits.
+struct ReconEnsemble {
+    float* mean = nullptr; float* m2 = nullptr;
+    float* vmax = nullptr; float* vmin = nullptr; int* imax = nullptr; int* imin = nullptr;
+    const float* limit = nullptr; int* exceed = nullptr;
+};
+int ew_recon_ensemble(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconEnsemble& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);
 int ew_transpose(int src_dtype, int dst_dtype, const void* src, void* dst, int Bn, int I, int J, long lds_, long ldd,
                  long sbatch, long dbatch, hipStream_t s);
-int ew_randn(float* out, long n, uint64_t seed, uint64_t stream, hipStream_t s, long per_row = 0, int world = 1, int rank = 0);
+int ew_randn(float* out, long n, uint64_t seed, uint64_t stream, hipStream_t s, long per_row = 0, int world = 1, int rank = 0, long row0 = 0);
 int ew_latent_fwd(const float* last, const float* eps, float* z, int B, int Z, double* kl_sum, hipStream_t s);
 int ew_latent_bwd(const float* last, const float* eps, const float* dz, float* dlast, int B, int Z, float coef, hipStream_t s);
 int ew_stage_fwd(int dtype, const float* pz, const float* qz, const float* eps, const void* dec_out, long ldd,

@@ -342,6 +342,40 @@ int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const
     hipFree(work);
     return rc;
 }
+int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, long count_before, const sgv_ensemble_state* st, int B, int T,
+                            int C, void* stream) {
+    const char* me = "sgv_test_recon_ensemble";
+    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
+    if (!y || !sums || !gamma || !beta || !scale || !min || !st) return fail(SGV_ERR_ARG, "%s: null argument", me);
+    const bool mo = st->mean || st->m2, ex = st->max || st->min || st->arg_max || st->arg_min, ec = st->exceed || st->limit;
+    if (!mo && !ex && !ec) return fail(SGV_ERR_ARG, "%s: no group of the state is given", me);
+    if ((mo && !(st->mean && st->m2)) || (ex && !(st->max && st->min && st->arg_max && st->arg_min)) || (ec && !(st->exceed && st->limit)))
+        return fail(SGV_ERR_ARG, "%s: half a group (mean + m2, max + min + arg_max + arg_min, limit + exceed go together)", me);
+    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
+    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
+    if ((((uintptr_t)y | (uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->max | (uintptr_t)st->min | (uintptr_t)st->arg_max |
+          (uintptr_t)st->arg_min | (uintptr_t)st->exceed) & 15) || ((uintptr_t)st->limit & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (y and the state arrays 16 bytes, limit 4)", me);
+    if (count_before < 0 || count_before + B > (1L << 24))
+        return fail(SGV_ERR_ARG, "%s: count_before = %ld with B = %d is outside [0, 2^24]", me, count_before, B);
+    GNParams p;
+    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
+    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
+    p.y = y; p.ldy = ldy; p.sums = sums;
+    hipStream_t s = (hipStream_t)stream;
+    float* work = nullptr;
+    HIPCHK(hipMalloc((void**)&work, sizeof(float) * ew_gn_part_floats(B, T, C)));          // statistics workspace
+    p.part = work;
+    ReconEnsemble o;
+    o.mean = st->mean; o.m2 = st->m2; o.vmax = st->max; o.vmin = st->min; o.imax = st->arg_max; o.imin = st->arg_min;
+    o.limit = st->limit; o.exceed = st->exceed;
+    int r = ew_gn_stats(dtype, p, s);
+    if (!r) r = ew_recon_ensemble(dtype, p, scale, min, count_before, o, s);
+    const int rc = ew_hook_done(r, me, stream);
+    hipFree(work);
+    return rc;
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

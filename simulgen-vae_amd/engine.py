@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -67,9 +67,17 @@ class ScoreOut(C.Structure):
     _fields_ = [("node_err", C.c_void_p), ("node_when", C.c_void_p), ("frame_err", C.c_void_p), ("frame_where", C.c_void_p)]
 
 
+class EnsembleState(C.Structure):
+    """sgv_ensemble_state (include/sgvae.h): the running state of sgv_ensemble, device pointers; a group is given whole or not at all"""
+    _fields_ = [("mean", C.c_void_p), ("m2", C.c_void_p), ("max", C.c_void_p), ("min", C.c_void_p), ("arg_max", C.c_void_p),
+                ("arg_min", C.c_void_p), ("limit", C.c_void_p), ("exceed", C.c_void_p)]
+
+
 MAX_PROBES = 4096
 SUMMARY_PARTS = ("node", "frame", "probes")      # `want` of Engine.summarize
 SCORE_PARTS = ("node", "frame")                  # `want` of Engine.score
+ENSEMBLE_GROUPS = {"moments": ("mean", "m2"), "extrema": ("max", "min", "arg_max", "arg_min"), "exceed": ("limit", "exceed")}      # the state of Engine.ensemble
+ENSEMBLE_MAX_COUNT = 1 << 24                     # members of one ensemble: beyond that float(k) is not exact
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")      # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -120,6 +128,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_set_probes.argtypes = [vp, vp, i32]
     lib.sgv_summarize.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.POINTER(SummaryOut)]
     lib.sgv_score.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, C.POINTER(ScoreOut)]
+    lib.sgv_ensemble.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.c_long, C.POINTER(EnsembleState)]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -184,6 +193,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_physical.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_summary.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, C.POINTER(SummaryOut), vp, i32, i32, i32, i32, vp]
     lib.sgv_test_recon_score.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, C.POINTER(ScoreOut), i32, i32, i32, vp]
+    lib.sgv_test_recon_ensemble.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, lg, C.POINTER(EnsembleState), i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -546,6 +556,47 @@ class Engine:
                                             C.byref(so)), "sgv_score")
         self.batch = B
         return res
+
+    def ensemble(self, z, xs, scale, min, state, count_before, fix=True):
+        """Merges the fields generate() would write for this batch into the running statistics `state`, per (time step, node), by
+        the recon head's last pass itself; the fields are never stored.  Same inputs and checks as summarize().  state: a dict of
+        contiguous CUDA tensors [T, N], whole groups only (ENSEMBLE_GROUPS): "mean", "m2" fp32 (Welford: variance = m2 / count);
+        "max", "min" fp32 with "arg_max", "arg_min" int32 (the index of the member that produced the extremum, the earliest on a
+        tie); "limit" fp32 [N] (input) with "exceed" int32 (members with field > limit, strict).  Sample b of the batch is member
+        count_before + b; with count_before == 0 the state is not read.  The tensors are updated in place and `state` is returned.
+        Any cut of the same members into calls gives the same bits, the decoder's noise included: unless set with set_eps() it
+        follows the member's index (the rows count_before + b of the streams the first call after seed() draws from) and the
+        draw position does not move.  Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        if not isinstance(state, dict) or not state:
+            raise ValueError(f"state must be a dict with the tensors of at least one of the groups {ENSEMBLE_GROUPS}")
+        known = {k: g for g, names in ENSEMBLE_GROUPS.items() for k in names}
+        for k in state:
+            if k not in known:
+                raise ValueError(f"state[{k!r}] is not a tensor of the ensemble state ({sorted(known)})")
+        for g, names in ENSEMBLE_GROUPS.items():
+            have = [k for k in names if state.get(k) is not None]
+            if have and len(have) != len(names):
+                raise ValueError(f"state: group {g!r} needs all of {names}, got only {have}")
+        for k, v in state.items():
+            if v is None:
+                continue
+            dt = t.int32 if k in ("arg_max", "arg_min", "exceed") else t.float32
+            shape = (N,) if k == "limit" else (T, N)
+            if not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
+                raise ValueError(f"state[{k!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
+        B, z, xs_t = self._latents(z, xs)
+        self._scaler(scale, min)
+        count_before = int(count_before)
+        if count_before < 0 or count_before + B > ENSEMBLE_MAX_COUNT:
+            raise ValueError(f"count_before = {count_before} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
+        st = EnsembleState(**{k: v.data_ptr() for k, v in state.items() if v is not None})
+        _check(self.lib, self.lib.sgv_ensemble(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
+                                               C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), count_before, C.byref(st)),
+               "sgv_ensemble")
+        self.batch = B
+        return state
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -19,6 +19,9 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
                                                    # (DESIGN.md section 17): the fields are reduced by the pass that would store them
     score = s.score(conditions, truth)             # error against held-out fields [P, T, N]: per node / per time step max |e|, bias, MSE,
                                                    # per condition rmse / rel_l2 / max_abs, same fused pass
+    ens = s.ensemble(conditions.repeat(1000, 1), limit=250.0, mode="random")   # statistics ACROSS draws per (time step, node): mean,
+                                                   # ens.std(), envelope, which draw was worst, how often the limit is exceeded
+                                                   # (DESIGN.md section 19); [T, N] running state instead of 1000 fields
 """
 from __future__ import annotations
 
@@ -101,6 +104,83 @@ class ScoreResult:
     def __init__(self, **kw):
         for k in self.FIELDS:
             setattr(self, k, kw[k])
+
+
+def exceed_limit(limit, N):
+    """The limit of Surrogate.ensemble as a float32 vector of N entries in physical units: a scalar is broadcast to every node, a
+    1-D array of N entries is taken node by node.  ValueError naming the problem otherwise: a rank above 1, a length other than N,
+    or an entry that is not finite (the first one is named).  numpy only."""
+    a = np.asarray(limit, dtype=np.float64)
+    if a.ndim > 1:
+        raise ValueError(f"limit: a scalar or a 1-D array of N = {int(N)} entries is required, got shape {a.shape}")
+    if a.ndim == 1 and a.size != int(N):
+        raise ValueError(f"limit: {a.size} entries, expected N = {int(N)} (or a scalar)")
+    with np.errstate(over="ignore"):          # a value beyond float32 becomes inf and is reported below
+        v = np.broadcast_to(a.astype(np.float32), (int(N),))
+    bad = np.flatnonzero(~np.isfinite(v))
+    if bad.size:
+        where = f"limit[{int(bad[0])}]" if a.ndim == 1 else "limit"
+        raise ValueError(f"{where} = {float(a.reshape(-1)[bad[0] if a.ndim == 1 else 0])!r} is not finite as float32")
+    return np.array(v)          # a copy: the broadcast view is read-only
+
+
+class EnsembleResult:
+    """Surrogate.ensemble's result: statistics over `count` members per (time step, node), device tensors [T, N] that ARE the running
+    state (pass the result back as `into=` to go on accumulating).  mean, m2 fp32 (Welford: m2 is the sum of squared deviations
+    from the mean); max, min fp32 with arg_max, arg_min int32 (the index, in call order, of the condition that produced the
+    extremum; the earliest on a tie); exceed int32 (members with field > limit, strict) with limit fp32 [N].  Groups not asked for
+    are None."""
+    FIELDS = ("count", "mean", "m2", "max", "min", "arg_max", "arg_min", "exceed", "limit")
+    GROUPS = {"moments": ("mean", "m2"), "extrema": ("max", "min", "arg_max", "arg_min"), "exceed": ("limit", "exceed")}
+
+    def __init__(self, stream=None, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+        self._stream = stream          # the engine stream (a torch stream): var / std / exceed_fraction run there
+
+    def groups(self):
+        """the groups this result holds, in the order of GROUPS"""
+        return tuple(g for g, names in self.GROUPS.items() if getattr(self, names[0]) is not None)
+
+    def state(self):
+        """the tensors of the running state by their names in Engine.ensemble"""
+        return {k: getattr(self, k) for names in self.GROUPS.values() for k in names if getattr(self, k) is not None}
+
+    def _on_stream(self, fn):
+        if self._stream is None:
+            return fn()
+        import torch
+        cur = torch.cuda.current_stream()
+        self._stream.wait_stream(cur)
+        with torch.cuda.stream(self._stream):
+            r = fn()
+        if cur != self._stream:
+            cur.wait_stream(self._stream)
+        return r
+
+    def var(self, ddof=0):
+        """m2 / (count - ddof) [T, N] fp32"""
+        if self.m2 is None:
+            raise ValueError("var: the moments were not asked for")
+        if self.count - ddof <= 0:
+            raise ValueError(f"var: count - ddof = {self.count} - {ddof} is not positive")
+        return self._on_stream(lambda: self.m2 / float(self.count - ddof))
+
+    def std(self, ddof=0):
+        """sqrt(var(ddof))"""
+        if self.m2 is None:
+            raise ValueError("std: the moments were not asked for")
+        if self.count - ddof <= 0:
+            raise ValueError(f"std: count - ddof = {self.count} - {ddof} is not positive")
+        return self._on_stream(lambda: (self.m2 / float(self.count - ddof)).sqrt())
+
+    def exceed_fraction(self):
+        """exceed / count [T, N] fp32: how often the limit is exceeded"""
+        if self.exceed is None:
+            raise ValueError("exceed_fraction: no limit was given")
+        if self.count < 1:
+            raise ValueError("exceed_fraction: the ensemble is empty")
+        return self._on_stream(lambda: self.exceed.float() / float(self.count))
 
 
 class SweepResult:
@@ -313,6 +393,77 @@ class Surrogate:
             t.cuda.current_stream().wait_stream(self._stream)
         return ScoreResult(node_max_abs=node[0], node_bias=node[1], node_mse=node[2], t_worst=when, frame_max_abs=frame[0],
                            frame_mse=frame[1], frame_truth_ms=frame[2], n_worst=where, rmse=rmse, rel_l2=rel_l2, max_abs=max_abs)
+
+    def ensemble(self, conditions, limit=None, want=("moments", "extrema"), mode="fix", into=None):
+        """Statistics over the fields of all `conditions` per (time step, node), without the fields: what a Monte-Carlo or
+        design-space study asks of thousands of draws -> an EnsembleResult of device tensors [T, N].  want: "moments" (mean and m2,
+        Welford's running update; result.var() / std()), "extrema" (the envelope max / min and arg_max / arg_min, the index into
+        `conditions` in call order of the draw that produced each); with `limit` (a scalar or N values in physical units, see
+        exceed_limit) also "exceed", the number of draws above the limit, which is in the result exactly when a limit is given.
+        The recon head's last pass merges the values predict() would store into the result tensors themselves, member after member
+        in fp32: they are the running state, updated in place batch after batch; there are no per-batch buffers and no copies, and
+        the result does not depend on the batch size, bit for bit.  into: an earlier result to go on accumulating into (same groups,
+        same limit; its tensors are updated and returned in a new result with the larger count): equal to one call on the
+        concatenated conditions, bit for bit, wherever the cut falls.  Draws of ONE design are conditions.repeat(K, 1) with
+        mode="random": the decoder's latents are then sampled per draw.  The decoder's noise of a draw follows its index in the
+        ensemble, not its place in a batch (predict() draws per call): the same seed gives the same ensemble at any batch size, two
+        studies on one seed share their random numbers, and predict() sees the same draws only while it makes a single call.
+        Batching, streams, the single input-range decision and `mode` are sweep()'s: no host wait between batches, the last
+        batch may be ragged."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        want = tuple(want)
+        groups = EnsembleResult.GROUPS
+        if any(w not in groups for w in want):
+            raise ValueError(f"want must name groups of {tuple(groups)}, not {want!r}")
+        if limit is None and "exceed" in want:
+            raise ValueError("want names 'exceed' but no limit is given")
+        if limit is not None and "exceed" not in want:
+            want += ("exceed",)
+        want = tuple(g for g in groups if g in want)
+        if not want:
+            raise ValueError(f"want must name at least one of {tuple(groups)}")
+        lim = None if limit is None else exceed_limit(limit, self.N)
+        f32 = dict(dtype=t.float32, device="cuda")
+        i32 = dict(dtype=t.int32, device="cuda")
+        dtypes = dict(mean=t.float32, m2=t.float32, max=t.float32, min=t.float32, arg_max=t.int32, arg_min=t.int32, exceed=t.int32, limit=t.float32)
+        if into is not None:
+            if not isinstance(into, EnsembleResult):
+                raise ValueError(f"into must be an EnsembleResult, not {type(into).__name__}")
+            if into.groups() != want:
+                raise ValueError(f"into holds the groups {into.groups()}, this call asks for {want}")
+            state = into.state()
+            for k, v in state.items():
+                shape = (self.N,) if k == "limit" else (self.T, self.N)
+                if not (t.is_tensor(v) and v.is_cuda and v.dtype == dtypes[k] and v.is_contiguous() and tuple(v.shape) == shape):
+                    raise ValueError(f"into.{k} must be a contiguous {dtypes[k]} CUDA tensor of shape {shape}")
+            if lim is not None and not np.array_equal(state["limit"].cpu().numpy(), lim):
+                raise ValueError("into was accumulated against another limit")
+            count = int(into.count)
+            if count < 0:
+                raise ValueError(f"into.count = {count} is negative")
+        else:
+            state, count = {}, 0
+        if count + P > (1 << 24):
+            raise ValueError(f"{count} + {P} members: an ensemble holds at most 2^24")
+        self._stream.wait_stream(t.cuda.current_stream())
+        with t.cuda.stream(self._stream):
+            if into is None:
+                for g in want:
+                    for k in groups[g]:
+                        state[k] = (t.from_numpy(lim).cuda() if k == "limit"
+                                    else t.empty((self.T, self.N), **(i32 if dtypes[k] == t.int32 else f32)))
+                if P == 0:          # the empty ensemble, as the first batch would have found it
+                    for k, v in state.items():
+                        if k != "limit":
+                            v.fill_({"max": float("-inf"), "min": float("inf")}.get(k, 0))
+            for lo in range(0, P, self.batch):
+                hi = min(P, lo + self.batch)
+                lat, xs = self._latents(self._batch(conditions, lo, hi), remap)
+                self.eng.ensemble(lat, xs, self.data_scale, self.data_min, state, count + lo, fix=mode == "fix")
+        if t.cuda.current_stream() != self._stream:
+            t.cuda.current_stream().wait_stream(self._stream)
+        return EnsembleResult(stream=self._stream, count=count + P, **{k: state.get(k) for k in EnsembleResult.FIELDS if k != "count"})
 
     def predict_to_host(self, conditions, out=None, layout="TN", mode="fix"):
         """The same result in pinned host memory: two device batch buffers alternate, each batch's device-to-host copy runs on the

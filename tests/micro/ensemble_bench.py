@@ -1,0 +1,138 @@
+"""What the ensemble pass costs at preset-1 `small` (N = 95 008, T = 200), batch 16, bf16, random weights and latents, P = 64
+members in four batches.  Recorded, not asserted.
+
+  kernel times: the engine's own timers (sgv_kernel_time) around the output pass of sgv_generate ("recon_phys":
+      recon_phys_tn_kernel) and around the ensemble pass of sgv_ensemble ("recon_ensemble": recon_ensemble_kernel) for every
+      subset of the three groups, on a continuing batch (count_before = 16: the state is read and written) and, for all groups,
+      on the first batch (count_before = 0: written only), mean over --batches calls, with the bytes each must move and the
+      rate that comes to;
+  whole studies: hipEvents on the engine stream, the variants alternating: P / batch calls of Engine.ensemble with all groups,
+      against as many calls of Engine.generate into a [P, T, N] buffer followed by torch max / min (values and indices), mean,
+      var and (F > limit).sum over dim 0.
+
+Prints one JSON line.  Usage: python tests/micro/ensemble_bench.py [--batches 10] [--blocks 3] [--members 64] [--small-net]"""
+import argparse
+import itertools
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import simulgen_vae_amd  # noqa: E402,F401
+from simulgen_vae_amd.engine import ENSEMBLE_GROUPS  # noqa: E402
+from simulgen_vae_amd.modules.VAE_network import VAE  # noqa: E402
+
+ENC = [1024, 512, 256, 128]
+STATE_ARRAYS = {"moments": 2, "extrema": 4, "exceed": 1}          # [T, N] arrays of 4 bytes a group reads and writes
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=10, help="calls per timed block of the kernel timers")
+    ap.add_argument("--blocks", type=int, default=3, help="alternations of the variants")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--members", type=int, default=64, help="P: members of one study")
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--small-net", action="store_true", help="N = 4096, T = 32: a quick functional run of this script")
+    args = ap.parse_args()
+    N, T = (4096, 32) if args.small_net else (95008, 200)
+    B, nb, P = args.batch, args.batches, args.members
+    assert P % B == 0
+    vae = VAE(32, 8, ENC, ENC[::-1], N, T, lossfun="MSE", batch_size=B, small=True, compute_dtype=args.dtype).eval()
+    eng = vae._eng(B)
+    stream = torch.cuda.ExternalStream(eng.stream) if eng.stream else torch.cuda.current_stream()
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    z = torch.randn((P, 32), generator=gen, device="cuda")
+    xs = torch.randn((3, P, 8), generator=gen, device="cuda") * 0.5
+    rng = np.random.default_rng(2)
+    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), N)).astype(np.float32)
+    scale = torch.from_numpy(np.where(rng.random(N) < 0.25, -scale, scale).astype(np.float32)).cuda()
+    mn = torch.from_numpy(rng.standard_normal(N).astype(np.float32)).cuda()
+    fields = torch.empty((P, T, N), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+
+    with torch.cuda.stream(stream):
+        eng.generate(z[:B], xs[:, :B].contiguous(), scale, mn, out=fields[:B])
+        limit = fields[:B].reshape(B * T, N).median(dim=0).values.contiguous()
+        state = {}
+        for g, names in ENSEMBLE_GROUPS.items():
+            for k in names:
+                state[k] = limit if k == "limit" else torch.zeros((T, N), dtype=torch.int32 if k in ("arg_max", "arg_min", "exceed") else torch.float32, device="cuda")
+        zb = [z[lo:lo + B].contiguous() for lo in range(0, P, B)]
+        xb = [xs[:, lo:lo + B].contiguous() for lo in range(0, P, B)]
+
+        def one(groups, count_before):
+            eng.ensemble(zb[0], xb[0], scale, mn, {k: state[k] for g in groups for k in ENSEMBLE_GROUPS[g]}, count_before)
+
+        def study():
+            for i in range(P // B):
+                eng.ensemble(zb[i], xb[i], scale, mn, state, i * B)
+
+        def generate_then_reduce():
+            for i in range(P // B):
+                eng.generate(zb[i], xb[i], scale, mn, out=fields[i * B:(i + 1) * B])
+            return fields.max(dim=0), fields.min(dim=0), fields.mean(dim=0), fields.var(dim=0, unbiased=False), (fields > limit).sum(dim=0)
+
+        el = 2 if args.dtype == "bf16" else 4
+        subsets = [s for r in (1, 2, 3) for s in itertools.combinations(ENSEMBLE_GROUPS, r)]
+        bytes_ = {"recon_phys": B * T * N * el + B * T * N * 4}
+        for s in subsets:
+            bytes_["+".join(s)] = B * T * N * el + 2 * 4 * T * N * sum(STATE_ARRAYS[g] for g in s)
+        bytes_["first:" + "+".join(ENSEMBLE_GROUPS)] = B * T * N * el + 4 * T * N * sum(STATE_ARRAYS.values())
+        out = {"config": f"preset-1 small, N={N}, T={T}, batch {B}, {args.dtype}, P={P}, {nb} calls per block", "bytes": bytes_}
+
+        # ---- kernel times from the engine's timers ----
+        passes = {"recon_phys": lambda: eng.generate(zb[0], xb[0], scale, mn, out=fields[:B])}
+        for s in subsets:
+            passes["+".join(s)] = lambda s=s: one(s, B)
+        passes["first:" + "+".join(ENSEMBLE_GROUPS)] = lambda: one(tuple(ENSEMBLE_GROUPS), 0)
+        for fn in passes.values():
+            fn()
+        torch.cuda.synchronize()
+        kern = {k: [] for k in passes}
+        for _ in range(args.blocks):
+            for k, fn in passes.items():
+                eng.kernel_time_reset(True)
+                for _ in range(nb):
+                    fn()
+                ms, n = eng.kernel_time("recon_phys" if k == "recon_phys" else "recon_ensemble")
+                assert n == nb, (k, n)
+                kern[k].append(ms / n)
+        eng.kernel_time_reset(False)
+        for k, v in kern.items():
+            out[k + "_kernel_ms_blocks"] = [round(t, 4) for t in v]
+            out[k + "_kernel_ms"] = round(statistics.mean(v), 4)
+            out[k + "_tb_per_s"] = round(bytes_[k] / (statistics.mean(v) * 1e-3) / 1e12, 3)
+
+        # ---- whole studies of P members ----
+        def timed(fn, n):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record(stream)
+            for _ in range(n):
+                fn()
+            b.record(stream)
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / n
+
+        calls = {"generate_only": lambda: [eng.generate(zb[i], xb[i], scale, mn, out=fields[i * B:(i + 1) * B]) for i in range(P // B)],
+                 "generate_then_torch_reduce": generate_then_reduce, "ensemble": study}
+        for fn in calls.values():
+            timed(fn, 1)
+        res = {k: [] for k in calls}
+        reps = max(1, nb // 3)
+        for _ in range(args.blocks):
+            for k, fn in calls.items():
+                res[k].append(timed(fn, reps))
+        for k, v in res.items():
+            out[k + "_study_ms_blocks"] = [round(t, 3) for t in v]
+            out[k + "_study_ms"] = round(statistics.mean(v), 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

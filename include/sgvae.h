@@ -498,7 +498,7 @@ int sgv_test_occupy(void* stream, int blocks, int threads, int lds_bytes, long l
  * one collective.  *calls / *elems return (and reset) the number of collectives and of elements since the last call. */
 int sgv_test_fake_collective(float k, long* calls, long* elems);
 
-/* Test hooks for the non-GEMM kernels of the step (csrc/ew.hip; tests/test_ew_kernels_gpu.py): caller-owned device buffers in, the
+/* Test hooks for the non-GEMM kernels of the step (csrc/ew.hip, csrc/recon_out.hip; tests/test_ew_kernels_gpu.py): caller-owned device buffers in, the
  * launcher the engine calls, then a stream sync.  Maps are channels-last [B*T][ld] of `dtype` (ld >= C, ld % 8 == 0), C % 8 == 0,
  * 1 <= G <= 32, C % G == 0; gamma / beta / dgamma / dbeta / dbias / cbias are [C] fp32, sums / sums2 [B*G][2] fp64.  `work` is a
  * scratch array of work_floats >= sgv_test_gn_workspace_floats(B, T, C) floats.  Bad arguments return SGV_ERR_ARG before any

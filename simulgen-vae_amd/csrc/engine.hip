@@ -887,22 +887,42 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
     return 0;
 }
 
-// Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen` (sgv_generate),
-// the recon head's convolution and statistics followed by the physical-field pass instead of the loss tail -- or, with gen->sum
-// (sgv_summarize), by the summary pass: its frame partials go to e->colpart, which nothing uses once the statistics are done -- or,
-// with gen->score and gen->truth (sgv_score), by the error pass against the truth, with the same workspace -- or, with gen->ens
-// (sgv_ensemble), by the ensemble pass, which merges the batch into the caller's running state and needs no workspace.
+// What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
+// (sgv_summarize), its error against the truth (sgv_score) or the ensemble statistics (sgv_ensemble); only the members of `kind` are read.
 struct GenOut {
-    const float* scale; const float* mn; int layout; float* out;
-    const ReconSummary* sum = nullptr; const ReconScore* score = nullptr; const float* truth = nullptr;
-    const ReconEnsemble* ens = nullptr; long ens_count = 0;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE } kind;
+    const float* scale; const float* mn;
+    int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
+    ReconSummary sum;                                          // SUMMARY
+    ReconScore score; const float* truth = nullptr;            // SCORE
+    ReconEnsemble ens; long ens_count = 0;                     // ENSEMBLE
 };
+// The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass go
+// to e->colpart, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
+// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace.
+static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble"};
+    static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
+                                           "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
+                                           "sgv_ensemble: the ensemble pass rejected its arguments (%d)"};
+    ScopedTimer tm(e, tag[g.kind], nullptr);
+    int r = 0;
+    switch (g.kind) {
+    case GenOut::FIELD: r = ew_recon_physical(e->dt, p, g.scale, g.mn, g.layout, g.out, e->stream); break;
+    case GenOut::SUMMARY: { ReconSummary o = g.sum; o.work = e->colpart; r = ew_recon_summary(e->dt, p, g.scale, g.mn, o, e->stream); break; }
+    case GenOut::SCORE: { ReconScore o = g.score; o.work = e->colpart; r = ew_recon_score(e->dt, p, g.scale, g.mn, g.truth, o, e->stream); break; }
+    case GenOut::ENSEMBLE: r = ew_recon_ensemble(e->dt, p, g.scale, g.mn, g.ens_count, g.ens, e->stream); break;
+    }
+    return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
+}
+// Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen`, the recon head's
+// convolution and statistics followed by recon_tail instead of the loss tail.
 static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
     // sgv_ensemble: the noise of member m is a function of (seed, m, site) alone -- the rows count_before + b of the streams the first
     // call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size
-    const bool ens = gen && gen->ens;
+    const bool ens = gen && gen->kind == GenOut::ENSEMBLE;
     uint64_t ens_draw = 0;
     for (int s = 1; s < n_st; ++s) {
         if (!e->eps_set[s]) ew_randn(e->eps[s], M * e->dec[s], e->seed, (ens ? ens_draw++ : e->draw++) * 8 + s, e->stream, (long)e->T * e->dec[s], e->shard_world, e->shard_rank,
@@ -954,30 +974,7 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenO
         CHK(conv_fwd(e, L, e->dec_out[n_st - 1], S.y, M));
         ew_gn_stats(e->dt, p, e->stream);
     }
-    if (gen && gen->sum) {
-        ReconSummary o = *gen->sum;
-        o.work = e->colpart;
-        ScopedTimer tm(e, "recon_summary", nullptr);
-        const int r = ew_recon_summary(e->dt, p, gen->scale, gen->mn, o, e->stream);
-        return r ? fail(SGV_ERR_ARG, "sgv_summarize: the summary pass rejected its arguments (%d)", r) : 0;
-    }
-    if (gen && gen->score) {
-        ReconScore o = *gen->score;
-        o.work = e->colpart;
-        ScopedTimer tm(e, "recon_score", nullptr);
-        const int r = ew_recon_score(e->dt, p, gen->scale, gen->mn, gen->truth, o, e->stream);
-        return r ? fail(SGV_ERR_ARG, "sgv_score: the error pass rejected its arguments (%d)", r) : 0;
-    }
-    if (gen && gen->ens) {
-        ScopedTimer tm(e, "recon_ensemble", nullptr);
-        const int r = ew_recon_ensemble(e->dt, p, gen->scale, gen->mn, gen->ens_count, *gen->ens, e->stream);
-        return r ? fail(SGV_ERR_ARG, "sgv_ensemble: the ensemble pass rejected its arguments (%d)", r) : 0;
-    }
-    if (gen) {          // no loss, no read of x_in, no x_hat: the fp32 physical field goes straight to the caller's buffer
-        ScopedTimer tm(e, "recon_phys", nullptr);
-        const int r = ew_recon_physical(e->dt, p, gen->scale, gen->mn, gen->layout, gen->out, e->stream);
-        return r ? fail(SGV_ERR_ARG, "sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)", r) : 0;
-    }
+    if (gen) return recon_tail(e, p, *gen);
     p.dout = e->x_in.p; p.lddout = e->x_in.ld; p.loss_type = e->cfg.loss_type;
     p.loss_sums = e->scal;
     if (e->write_xhat || !train) { p.out = e->xhat.p; p.ldout = e->xhat.ld; }
@@ -1053,19 +1050,25 @@ int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch
     return SGV_OK;
 }
 
+// what the four surrogate entry points share behind their own argument checks: decode_begin, no forward left to read (the maps of an
+// earlier forward are overwritten from here on, and these passes leave no x_hat behind), the decoder with `gen` as its tail
+static int surrogate_pass(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const char* who, const GenOut& gen) {
+    CHK(decode_begin(e, z_dev, xs_dev, batch, who));
+    e->have_fwd = false;
+    e->fwd_train = false;
+    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
+    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
+    return SGV_OK;
+}
+
 int sgv_generate(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                  const float* min_dev, int layout, float* out_dev) {
     if (!e || !z_dev || !scale_dev || !min_dev || !out_dev) return fail(SGV_ERR_ARG, "sgv_generate: null argument");
     if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "sgv_generate: unknown layout %d", layout);
     if ((uintptr_t)out_dev & 15) return fail(SGV_ERR_ARG, "sgv_generate: out_dev must be 16-byte aligned");
-    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_generate"));
-    // the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
-    e->have_fwd = false;
-    e->fwd_train = false;
-    const GenOut gen = {scale_dev, min_dev, layout, out_dev};
-    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
-    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
-    return SGV_OK;
+    GenOut gen = {GenOut::FIELD, scale_dev, min_dev};
+    gen.layout = layout; gen.out = out_dev;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_generate", gen);
 }
 
 int sgv_set_probes(sgv_engine* e, const int32_t* nodes_host, int count) {
@@ -1087,69 +1090,30 @@ int sgv_set_probes(sgv_engine* e, const int32_t* nodes_host, int count) {
 
 int sgv_summarize(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                   const float* min_dev, const sgv_summary_out* out) {
-    if (!e || !z_dev || !scale_dev || !min_dev || !out) return fail(SGV_ERR_ARG, "sgv_summarize: null argument");
-    if (!out->node_stats && !out->node_when && !out->frame_stats && !out->frame_where && !out->probes)
-        return fail(SGV_ERR_ARG, "sgv_summarize: all five outputs are NULL");
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_summarize: null argument");
+    CHK(summary_out_ok("sgv_summarize", "output", out));
     if (out->probes && e->n_probes < 1) return fail(SGV_ERR_ARG, "sgv_summarize: probes asked for, but no probe nodes are set (sgv_set_probes)");
-    if ((((uintptr_t)out->node_stats | (uintptr_t)out->node_when) & 15) || (((uintptr_t)out->frame_stats | (uintptr_t)out->frame_where) & 7) ||
-        ((uintptr_t)out->probes & 3))
-        return fail(SGV_ERR_ARG, "sgv_summarize: misaligned output (node_stats / node_when 16 bytes, frame_stats / frame_where 8, probes 4)");
-    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_summarize"));
-    // as sgv_generate: the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
-    e->have_fwd = false;
-    e->fwd_train = false;
-    ReconSummary o;
-    o.node_stats = out->node_stats; o.node_when = out->node_when; o.frame_stats = out->frame_stats; o.frame_where = out->frame_where;
-    o.probes = out->probes; o.probe_nodes = e->probes_dev; o.n_probes = e->n_probes;
-    const GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr, &o};
-    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
-    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
-    return SGV_OK;
+    GenOut gen = {GenOut::SUMMARY, scale_dev, min_dev};
+    gen.sum = recon_summary_of(*out, e->probes_dev, e->n_probes, nullptr);
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_summarize", gen);
 }
 
 int sgv_score(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
               const float* min_dev, const float* truth_dev, const sgv_score_out* out) {
-    if (!e || !z_dev || !scale_dev || !min_dev || !truth_dev || !out) return fail(SGV_ERR_ARG, "sgv_score: null argument");
-    if (!out->node_err && !out->node_when && !out->frame_err && !out->frame_where) return fail(SGV_ERR_ARG, "sgv_score: all four outputs are NULL");
-    if ((((uintptr_t)truth_dev | (uintptr_t)out->node_err | (uintptr_t)out->node_when) & 15) || (((uintptr_t)out->frame_err | (uintptr_t)out->frame_where) & 3))
-        return fail(SGV_ERR_ARG, "sgv_score: misaligned pointer (truth_dev, node_err / node_when 16 bytes, frame_err / frame_where 4)");
-    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_score"));
-    // as sgv_generate: the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
-    e->have_fwd = false;
-    e->fwd_train = false;
-    ReconScore o;
-    o.node_err = out->node_err; o.node_when = out->node_when; o.frame_err = out->frame_err; o.frame_where = out->frame_where;
-    GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr};
-    gen.score = &o; gen.truth = truth_dev;
-    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
-    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
-    return SGV_OK;
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_score: null argument");
+    CHK(score_out_ok("sgv_score", "truth_dev", truth_dev, out));
+    GenOut gen = {GenOut::SCORE, scale_dev, min_dev};
+    gen.score = recon_score_of(*out, nullptr); gen.truth = truth_dev;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_score", gen);
 }
 
 int sgv_ensemble(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                  const float* min_dev, long count_before, const sgv_ensemble_state* st) {
-    if (!e || !z_dev || !scale_dev || !min_dev || !st) return fail(SGV_ERR_ARG, "sgv_ensemble: null argument");
-    const bool mo = st->mean || st->m2, ex = st->max || st->min || st->arg_max || st->arg_min, ec = st->exceed || st->limit;
-    if (!mo && !ex && !ec) return fail(SGV_ERR_ARG, "sgv_ensemble: no group of the state is given");
-    if ((mo && !(st->mean && st->m2)) || (ex && !(st->max && st->min && st->arg_max && st->arg_min)) || (ec && !(st->exceed && st->limit)))
-        return fail(SGV_ERR_ARG, "sgv_ensemble: half a group (mean + m2, max + min + arg_max + arg_min, limit + exceed go together)");
-    if ((((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->max | (uintptr_t)st->min | (uintptr_t)st->arg_max | (uintptr_t)st->arg_min |
-          (uintptr_t)st->exceed) & 15) || ((uintptr_t)st->limit & 3))
-        return fail(SGV_ERR_ARG, "sgv_ensemble: misaligned pointer (the state arrays 16 bytes, limit 4)");
-    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
-        return fail(SGV_ERR_ARG, "sgv_ensemble: count_before = %ld with batch = %d is outside [0, 2^24]", count_before, batch);
-    CHK(decode_begin(e, z_dev, xs_dev, batch, "sgv_ensemble"));
-    // as sgv_generate: the maps of an earlier forward are overwritten from here on, and this pass leaves no x_hat behind
-    e->have_fwd = false;
-    e->fwd_train = false;
-    ReconEnsemble o;
-    o.mean = st->mean; o.m2 = st->m2; o.vmax = st->max; o.vmin = st->min; o.imax = st->arg_max; o.imin = st->arg_min;
-    o.limit = st->limit; o.exceed = st->exceed;
-    GenOut gen = {scale_dev, min_dev, SGV_LAYOUT_TN, nullptr};
-    gen.ens = &o; gen.ens_count = count_before;
-    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
-    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
-    return SGV_OK;
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_ensemble: null argument");
+    CHK(ensemble_state_ok("sgv_ensemble", "batch", st, count_before, batch));
+    GenOut gen = {GenOut::ENSEMBLE, scale_dev, min_dev};
+    gen.ens = recon_ensemble_of(*st); gen.ens_count = count_before;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_ensemble", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

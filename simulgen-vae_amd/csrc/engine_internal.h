@@ -242,6 +242,53 @@ static inline int first_bad_probe(const int32_t* nodes, int count, int N) {
     for (int i = 0; i < count; ++i) if (nodes[i] < 0 || nodes[i] >= N) return i;
     return -1;
 }
+// The output structs of the surrogate passes, checked and converted in one place for the entry points (engine.hip) and the kernel
+// hooks (test_hooks.hip).  *_ok: 0, or SGV_ERR_ARG with the message set; `who` is the caller's name, the prefix of the message, and the
+// second string the one word in which the texts of an entry point and of its hook differ.
+static inline int summary_out_ok(const char* who, const char* noun, const sgv_summary_out* o) {
+    if (!o) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (!o->node_stats && !o->node_when && !o->frame_stats && !o->frame_where && !o->probes) return fail(SGV_ERR_ARG, "%s: all five outputs are NULL", who);
+    if ((((uintptr_t)o->node_stats | (uintptr_t)o->node_when) & 15) || (((uintptr_t)o->frame_stats | (uintptr_t)o->frame_where) & 7) || ((uintptr_t)o->probes & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned %s (node_stats / node_when 16 bytes, frame_stats / frame_where 8, probes 4)", who, noun);
+    return 0;
+}
+static inline ReconSummary recon_summary_of(const sgv_summary_out& o, const int* probe_nodes, int n_probes, float* work) {
+    ReconSummary r;
+    r.node_stats = o.node_stats; r.node_when = o.node_when; r.frame_stats = o.frame_stats; r.frame_where = o.frame_where;
+    r.probes = o.probes; r.probe_nodes = probe_nodes; r.n_probes = n_probes; r.work = work;
+    return r;
+}
+static inline int score_out_ok(const char* who, const char* truth_name, const float* truth, const sgv_score_out* o) {
+    if (!truth || !o) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (!o->node_err && !o->node_when && !o->frame_err && !o->frame_where) return fail(SGV_ERR_ARG, "%s: all four outputs are NULL", who);
+    if ((((uintptr_t)truth | (uintptr_t)o->node_err | (uintptr_t)o->node_when) & 15) || (((uintptr_t)o->frame_err | (uintptr_t)o->frame_where) & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (%s, node_err / node_when 16 bytes, frame_err / frame_where 4)", who, truth_name);
+    return 0;
+}
+static inline ReconScore recon_score_of(const sgv_score_out& o, float* work) {
+    ReconScore r;
+    r.node_err = o.node_err; r.node_when = o.node_when; r.frame_err = o.frame_err; r.frame_where = o.frame_where; r.work = work;
+    return r;
+}
+static inline int ensemble_state_ok(const char* who, const char* batch_name, const sgv_ensemble_state* st, long count_before, int batch) {
+    if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    const bool mo = st->mean || st->m2, ex = st->max || st->min || st->arg_max || st->arg_min, ec = st->exceed || st->limit;
+    if (!mo && !ex && !ec) return fail(SGV_ERR_ARG, "%s: no group of the state is given", who);
+    if ((mo && !(st->mean && st->m2)) || (ex && !(st->max && st->min && st->arg_max && st->arg_min)) || (ec && !(st->exceed && st->limit)))
+        return fail(SGV_ERR_ARG, "%s: half a group (mean + m2, max + min + arg_max + arg_min, limit + exceed go together)", who);
+    if ((((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->max | (uintptr_t)st->min | (uintptr_t)st->arg_max | (uintptr_t)st->arg_min |
+          (uintptr_t)st->exceed) & 15) || ((uintptr_t)st->limit & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (the state arrays 16 bytes, limit 4)", who);
+    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
+        return fail(SGV_ERR_ARG, "%s: count_before = %ld with %s = %d is outside [0, 2^24]", who, count_before, batch_name, batch);
+    return 0;
+}
+static inline ReconEnsemble recon_ensemble_of(const sgv_ensemble_state& st) {
+    ReconEnsemble r;
+    r.mean = st.mean; r.m2 = st.m2; r.vmax = st.max; r.vmin = st.min; r.imax = st.arg_max; r.imin = st.arg_min;
+    r.limit = st.limit; r.exceed = st.exceed;
+    return r;
+}
 
 #pragma GCC visibility push(hidden)       // shared among the engine's files only: kept out of the library's dynamic symbols
 // The release policy of the gradient buckets, on backward_impl's stack for one backward pass (engine_optim.hip): the transport (none,

@@ -7,92 +7,10 @@
 // modules/decoder.py:133,143), layout conversion and augmentation (modules/augmentation.py:86-124).
 // All arithmetic in fp32 (group sums in fp64); every thread owns 8 consecutive channels (16/32-byte
 // vector accesses) and walks rows, so per-channel constants stay in registers.
+// The passes that replace the loss tail of the recon head in surrogate use (field, summaries, score, ensemble) live in recon_out.hip;
+// the geometry and device helpers both files use are in sgv_gn_dev.h.
 #include <algorithm>
-#include "sgv_ew.h"
-
-static inline int cdiv_i(long a, long b) { return (int)((a + b - 1) / b); }
-
-// ------------------------------------------------------------------------------------------
-// geometry shared by the GroupNorm-family kernels
-// ------------------------------------------------------------------------------------------
-struct GNGeom {
-    int CV, RL, rowsplit;
-    dim3 grid;
-};
-static GNGeom gn_geom(int B, int T, int C, int target = 2048) {
-    GNGeom g;
-    const int nv = C / 8;
-    int cv = 1;
-    while (cv < nv && cv < 256) cv <<= 1;
-    g.CV = cv;
-    g.RL = 256 / cv;
-    const int colblocks = cdiv_i(nv, cv);
-    // aim for >= ~target blocks, at least RL rows per block
-    int rs = cdiv_i(target, (long)colblocks * B);
-    int maxrs = cdiv_i(T, g.RL);
-    if (rs > maxrs) rs = maxrs;
-    if (rs < 1) rs = 1;
-    g.rowsplit = rs;
-    g.grid = dim3(colblocks, rs, B);
-    return g;
-}
-
-struct GNCtx {
-    int tx, ty, c0, b, t_lo, t_hi, RL;
-    bool col_ok;
-};
-__device__ __forceinline__ GNCtx gn_ctx(const GNParams& p) {
-    GNCtx c;
-    const int tid = threadIdx.x;
-    c.tx = tid % p.CV;
-    c.ty = tid / p.CV;
-    c.RL = 256 / p.CV;
-    c.c0 = (blockIdx.x * p.CV + c.tx) * 8;
-    c.col_ok = c.c0 < p.C;
-    c.b = blockIdx.z;
-    const int rps = (p.T + gridDim.y - 1) / gridDim.y;
-    c.t_lo = blockIdx.y * rps;
-    c.t_hi = min(p.T, c.t_lo + rps);
-    return c;
-}
-
-// mean and 1 / sqrt(var + eps) of group g of sample b from the fp64 (sum, sum of squares) in p.sums: the one place they are derived
-__device__ __forceinline__ void gn_mean_rstd(const GNParams& p, int b, int g, float& mean, float& rstd) {
-    const double n = (double)p.Cg * (double)p.T;
-    const double s = p.sums[((long)b * p.G + g) * 2 + 0];
-    const double ss = p.sums[((long)b * p.G + g) * 2 + 1];
-    const double m = s / n;
-    double var = ss / n - m * m;
-    if (var < 0.0) var = 0.0;
-    mean = (float)m;
-    rstd = (float)(1.0 / sqrt(var + 1e-5));
-}
-
-// per-element mean / rstd (and, WITH_M, the backward means m1 = s1/n, m2 = s2/n) of the element's group.
-// The fp64 divide/sqrt chain runs once per block on G threads and is broadcast through LDS: done per
-// thread it cost more than the streaming work of the small layers.  Must be called by all 256 threads.
-template <bool WITH_M = false>
-__device__ __forceinline__ void gn_consts(const GNParams& p, const GNCtx& c, float mean[8], float rstd[8],
-                                          float* m1 = nullptr, float* m2 = nullptr) {
-    __shared__ float gc[SGV_GN_MAX_GROUPS][4];
-    if ((int)threadIdx.x < p.G) {
-        const int g = threadIdx.x;
-        gn_mean_rstd(p, c.b, g, gc[g][0], gc[g][1]);
-        if constexpr (WITH_M) {
-            const double n = (double)p.Cg * (double)p.T;
-            gc[g][2] = (float)(p.sums2[((long)c.b * p.G + g) * 2 + 0] / n);
-            gc[g][3] = (float)(p.sums2[((long)c.b * p.G + g) * 2 + 1] / n);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int g = min((c.c0 + e) / p.Cg, p.G - 1);
-        mean[e] = gc[g][0];
-        rstd[e] = gc[g][1];
-        if constexpr (WITH_M) { m1[e] = gc[g][2]; m2[e] = gc[g][3]; }
-    }
-}
+#include "sgv_gn_dev.h"
 
 // sum of one float per thread over the block in a fixed order (shuffle tree per wave, then the waves in index order);
 // the result is returned to every thread.  All blockDim.x (<= 1024, multiple of 64) threads must call.
@@ -1015,12 +933,6 @@ __global__ __launch_bounds__(256) void act_kernel(const GNParams p) {
     }
 }
 
-#define GN_LAUNCH(KERN, P, S, ...)                                         \
-    do {                                                                   \
-        GNGeom g_ = gn_geom((P).B, (P).T, (P).C);                          \
-        (P).CV = g_.CV;                                                    \
-        hipLaunchKernelGGL(KERN, g_.grid, dim3(256), 0, S, P, ##__VA_ARGS__); \
-    } while (0)
 // reduce-type kernels write per-block column sums: coarser row split keeps that workspace traffic small
 constexpr int GN_REDUCE_TARGET = 768;
 #define GN_LAUNCH_R(KERN, P, S)                                            \
@@ -1234,717 +1146,6 @@ int ew_recon_bwd_apply(int dtype, GNParams p, hipStream_t s) {
     gn_fin_immediate(p, false, own_dots, grid_total(gn_geom(p.B, p.T, p.C).grid), s);
     return 0;
 }
-// ------------------------------------------------------------------------------------------
-// Surrogate prediction: recon head -> physical-unit field in one pass (sgv_generate).
-//   out = (tanh(gamma * (y - mean) * rstd + beta) - min_n) / scale_n      (MinMaxScaler.inverse_transform per node)
-// fp32 from the load of y to the fp32 store: no loss, no target read, no compute-dtype x_hat in between.  mean / rstd come from
-// p.sums exactly as in the eval loss pass (gn_consts; the normalised value is formed as (y - mean) * rstd first, as there).
-// ------------------------------------------------------------------------------------------
-struct ReconPhys { const float* scale; const float* mn; float* out; };
-// One element of the physical field and the reciprocal of its scale: the only place either is written down.  recon_phys_* and
-// recon_summary_* all call these, so a summary is a reduction of bit-identical values.
-__device__ __forceinline__ float recon_phys_val(float y, float mean, float rstd, float gam, float bet, float mn, float inv) {
-    const float xh = (y - mean) * rstd;
-    return (tanh_f(xh * gam + bet) - mn) * inv;
-}
-__device__ __forceinline__ float recon_phys_inv(float scale) { return 1.0f / scale; }      // correctly rounded reciprocal, once per thread
-
-// [B][T][N]: the geometry of gn_apply_kernel, 16-byte loads of y and two 16-byte stores per thread and row
-template <typename T>
-__global__ __launch_bounds__(256) void recon_phys_tn_kernel(const GNParams p, const ReconPhys q) {
-    const GNCtx c = gn_ctx(p);
-    float mean[8], rstd[8];
-    gn_consts(p, c, mean, rstd);
-    if (!c.col_ok) return;
-    float gam[8], bet[8], mn[8], inv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        gam[e] = p.gamma[c.c0 + e]; bet[e] = p.beta[c.c0 + e];
-        mn[e] = q.mn[c.c0 + e]; inv[e] = recon_phys_inv(q.scale[c.c0 + e]);
-    }
-    const T* y = reinterpret_cast<const T*>(p.y);
-    for (int t = c.t_lo + c.ty; t < c.t_hi; t += 2 * c.RL) {      // two rows per round, loads first
-        const bool two = t + c.RL < c.t_hi;
-        const long m0 = (long)c.b * p.T + t, m1 = two ? m0 + c.RL : m0;
-        Raw8<T> r0, r1;
-        raw_load(y + m0 * p.ldy + c.c0, r0);
-        raw_load(y + m1 * p.ldy + c.c0, r1);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (u == 1 && !two) break;
-            float v[8];
-            raw_unpack(u ? r1 : r0, v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
-            store8(q.out + (u ? m1 : m0) * p.C + c.c0, v);
-        }
-    }
-}
-
-// [B][N][T] (the reference's tensor layout): a tile of 32 rows (t) x 64 channels goes through LDS transposed; every thread loads
-// 8 channels of one row (16 / 32 bytes), the stores run along T.  blockIdx = (channel tile, row tile, sample).
-constexpr int RP_TT = 32, RP_TN = 64;
-template <typename T>
-__global__ __launch_bounds__(256) void recon_phys_nt_kernel(const GNParams p, const ReconPhys q) {
-    __shared__ float tile[RP_TN][RP_TT + 1];
-    __shared__ float cst[6][RP_TN];          // per channel of the tile: mean, rstd, gamma, beta, min, 1 / scale
-    const int b = blockIdx.z, n0 = blockIdx.x * RP_TN, t0 = blockIdx.y * RP_TT;
-    const int tid = threadIdx.x;
-    if (tid < RP_TN && n0 + tid < p.C) {
-        const int ch = n0 + tid, g = min(ch / p.Cg, p.G - 1);
-        gn_mean_rstd(p, b, g, cst[0][tid], cst[1][tid]);
-        cst[2][tid] = p.gamma[ch]; cst[3][tid] = p.beta[ch]; cst[4][tid] = q.mn[ch]; cst[5][tid] = recon_phys_inv(q.scale[ch]);
-    }
-    __syncthreads();
-    const int r = tid >> 3, cx = (tid & 7) * 8;          // row of the tile, first of this thread's 8 channels
-    const int t = t0 + r;
-    if (t < p.T && n0 + cx < p.C) {
-        float v[8];
-        load8(reinterpret_cast<const T*>(p.y) + ((long)b * p.T + t) * p.ldy + n0 + cx, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int j = cx + e;
-            tile[j][r] = recon_phys_val(v[e], cst[0][j], cst[1][j], cst[2][j], cst[3][j], cst[4][j], cst[5][j]);
-        }
-    }
-    __syncthreads();
-    const int tx = tid & 31;
-    if (t0 + tx < p.T) {
-        for (int j = tid >> 5; j < RP_TN; j += 8) {
-            if (n0 + j >= p.C) break;
-            q.out[((long)b * p.C + n0 + j) * p.T + t0 + tx] = tile[j][tx];
-        }
-    }
-}
-// p: y / ldy / gamma / beta / sums (given) / B, T, C, G, Cg; scale, mn [C] fp32; out fp32, dense: layout 0 [B][T][C], 1 [B][C][T]
-int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn, int layout, float* out, hipStream_t s) {
-    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn || !out) return -1;
-    if (layout != 0 && layout != 1) return -2;
-    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
-    if (((uintptr_t)p.y | (uintptr_t)out) & 15) return -4;          // 16-byte vector accesses
-    p.Cg = p.C / p.G;
-    const ReconPhys q = {scale, mn, out};
-    if (layout == 0) {
-        if (dtype == 1) GN_LAUNCH((recon_phys_tn_kernel<bf16_t>), p, s, q);
-        else GN_LAUNCH((recon_phys_tn_kernel<float>), p, s, q);
-    } else {
-        const dim3 grid(cdiv_i(p.C, RP_TN), cdiv_i(p.T, RP_TT), p.B);
-        if (dtype == 1) hipLaunchKernelGGL((recon_phys_nt_kernel<bf16_t>), grid, dim3(256), 0, s, p, q);
-        else hipLaunchKernelGGL((recon_phys_nt_kernel<float>), grid, dim3(256), 0, s, p, q);
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Surrogate field summaries (sgv_summarize): the same pass as recon_phys_tn_kernel with the stores replaced by reductions of the
-// values it would have stored -- per (sample, node) max / min / mean over t and the t of both extrema, per (sample, t) max / min
-// over the nodes and the node of both, and the time histories at a list of probe nodes.  Every comparison is made on the descaled
-// value (scale_n may be negative).  No atomics: a block owns 8 * CV channels of one sample for ALL rows (no row split), so a
-// node's time axis lies in one block -- its RL row lanes are combined through LDS in lane order; a row's extrema over the block's
-// channels come from an in-wave reduction over the CV lanes of that row and go to a partials workspace [B*T][column blocks], which
-// recon_summary_frames_kernel combines.  (value, index) pairs are ordered by value, then by the smaller index, so the result does
-// not depend on the shape of any tree: ties go to the smallest t / n and two launches are bitwise equal.
-// Geometry: CV = 64 column lanes (one wave per row; fewer for C < 512), RL = 256 / CV row lanes, grid (ceil(C / (8 CV)), 1, B).
-// ------------------------------------------------------------------------------------------
-constexpr int RS_MAX_CV = 64;
-struct RSGeom { int CV, colblocks; };
-static RSGeom rs_geom(int C) {
-    const int nv = C / 8;
-    int cv = 1;
-    while (cv < nv && cv < RS_MAX_CV) cv <<= 1;
-    return {cv, cdiv_i(nv, cv)};
-}
-size_t ew_recon_summary_work_floats(int B, int T, int C) { return (size_t)B * T * rs_geom(C).colblocks * 4; }
-
-// b replaces a when it is the larger (MAX) / smaller value, or the same value at a smaller index
-template <bool MAX>
-__device__ __forceinline__ void ext_take(float& av, int& ai, float bv, int bi) {
-    const bool better = MAX ? bv > av : bv < av;
-    if (better || (bv == av && bi < ai)) { av = bv; ai = bi; }
-}
-constexpr int RS_NO_INDEX = 0x7fffffff;       // index of the neutral element: loses every tie
-// In-wave reduction over the CV lanes of a row (neighbours inside a wave, aligned to CV) with DPP operands -- VALU instructions,
-// no trip through the LDS crossbar: pairs within quads, quads within 8 and 8s within 16 lanes by mirrored exchanges (every lane
-// of a DPP row of 16 then holds that row's result), then lane 15 of each DPP row into the next row and lane 31 into the upper
-// half.  Lanes of DPP rows outside the row mask get their own value back.  The LAST lane of the CV ends up with the result.
-// The pass is VALU-bound, not HBM-bound: reducing (value, index) pairs this way, 4 moves + 12 compare /
-// select per step, cost more than the element arithmetic; so the values are reduced alone, the winner is handed back to the
-// row's lanes, and the smallest index among the lanes that hold it is reduced as an integer minimum.
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v);
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL, ROW_MASK>(__float_as_int(v))); }
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v) {
-    // every lane has a source in the unmasked exchanges: with bound_ctrl set the compiler may fold the move into the instruction that uses it
-    if constexpr (ROW_MASK == 0xF) return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-    else return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xF, false);
-}
-#define RS_LANE_REDUCE(NAME, TYPE, OP, DPP)                                                      \
-    __device__ __forceinline__ TYPE NAME(TYPE v, int cv) {                                       \
-        if (cv > 1) v = OP(v, DPP<0xB1, 0xF>(v));  /* quad_perm [1, 0, 3, 2] */                  \
-        if (cv > 2) v = OP(v, DPP<0x4E, 0xF>(v));  /* quad_perm [2, 3, 0, 1] */                  \
-        if (cv > 4) v = OP(v, DPP<0x141, 0xF>(v)); /* row_half_mirror */                         \
-        if (cv > 8) v = OP(v, DPP<0x140, 0xF>(v)); /* row_mirror */                              \
-        if (cv > 16) v = OP(v, DPP<0x142, 0xA>(v)); /* row_bcast:15 into rows 1 and 3 */         \
-        if (cv > 32) v = OP(v, DPP<0x143, 0xC>(v)); /* row_bcast:31 into rows 2 and 3 */         \
-        return v;                                                                                \
-    }
-RS_LANE_REDUCE(lane_max_f, float, fmaxf, dpp_f)
-RS_LANE_REDUCE(lane_min_f, float, fminf, dpp_f)
-RS_LANE_REDUCE(lane_min_i, int, min, dpp_i)
-// the sum over a row's lanes in the same fixed tree (the score pass); lanes of DPP rows outside a row mask end up with twice their
-// value, which nobody reads: as above, only the LAST lane of the CV holds the result
-__device__ __forceinline__ float rs_add_f(float a, float b) { return a + b; }
-RS_LANE_REDUCE(lane_sum_f, float, rs_add_f, dpp_f)
-#undef RS_LANE_REDUCE
-
-// 4 waves / SIMD asked for: with every output the bf16 kernel sits at 128 VGPRs without scratch (131 and 3 waves unasked; the fp32 one
-// then keeps a few dwords in scratch)
-template <typename T, bool NODE, bool FRAME>
-__global__ __launch_bounds__(256, 4) void recon_summary_kernel(const GNParams p, const ReconPhys q, const ReconSummary o) {
-    const GNCtx c = gn_ctx(p);          // gridDim.y == 1: t_lo = 0, t_hi = T
-    float mean[8], rstd[8];
-    gn_consts(p, c, mean, rstd);
-    // no early return for the lanes past C: the shuffles and barriers below need every thread; such lanes load nothing and
-    // carry the neutral element
-    float gam[8], bet[8], mn[8], inv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        gam[e] = c.col_ok ? p.gamma[c.c0 + e] : 0.f; bet[e] = c.col_ok ? p.beta[c.c0 + e] : 0.f;
-        mn[e] = c.col_ok ? q.mn[c.c0 + e] : 0.f; inv[e] = c.col_ok ? recon_phys_inv(q.scale[c.c0 + e]) : 0.f;
-    }
-    float vmax[8], vmin[8], vsum[8];
-    int tmax[8], tmin[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { vmax[e] = -INFINITY; vmin[e] = INFINITY; vsum[e] = 0.f; tmax[e] = RS_NO_INDEX; tmin[e] = RS_NO_INDEX; }
-    const T* y = reinterpret_cast<const T*>(p.y);
-    float4* const fpart = reinterpret_cast<float4*>(o.work);
-    for (int t0 = 0; t0 < p.T; t0 += 2 * c.RL) {          // block-uniform trip count; two rows per round, loads first
-        const int ta = t0 + c.ty, tb = ta + c.RL;
-        const bool oka = c.col_ok && ta < p.T, okb = c.col_ok && tb < p.T;
-        const long m0 = (long)c.b * p.T + ta, m1 = m0 + c.RL;
-        Raw8<T> r0, r1;
-        raw_zero(r0); raw_zero(r1);
-        if (oka) raw_load(y + m0 * p.ldy + c.c0, r0);
-        if (okb) raw_load(y + m1 * p.ldy + c.c0, r1);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bool ok = u ? okb : oka;
-            const int t = u ? tb : ta;
-            float fmx = -INFINITY, fmn = INFINITY;
-            int imx = RS_NO_INDEX, imn = RS_NO_INDEX;
-            if (ok) {
-                float v[8];
-                raw_unpack(u ? r1 : r0, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float x = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
-                    if constexpr (NODE) {          // this thread's rows come in ascending t: a strict comparison keeps the first
-                        if (x > vmax[e]) { vmax[e] = x; tmax[e] = t; }
-                        if (x < vmin[e]) { vmin[e] = x; tmin[e] = t; }
-                        vsum[e] += x;
-                    }
-                    if constexpr (FRAME) {         // ascending n
-                        if (x > fmx) { fmx = x; imx = c.c0 + e; }
-                        if (x < fmn) { fmn = x; imn = c.c0 + e; }
-                    }
-                }
-            }
-            if constexpr (FRAME) {
-                // the row's extrema (in the last lane of the CV) back to all of its lanes; a lane that holds one offers its index,
-                // which is the smallest of its 8 channels with that value, and the smallest offer wins
-                const int last = ((int)threadIdx.x & 63) | (p.CV - 1);
-                const float rmx = __shfl(lane_max_f(fmx, p.CV), last, 64), rmn = __shfl(lane_min_f(fmn, p.CV), last, 64);
-                const int rimx = lane_min_i(fmx == rmx ? imx : RS_NO_INDEX, p.CV), rimn = lane_min_i(fmn == rmn ? imn : RS_NO_INDEX, p.CV);
-                if (c.tx == p.CV - 1 && t < p.T)
-                    fpart[((long)c.b * p.T + t) * gridDim.x + blockIdx.x] = make_float4(rmx, __int_as_float(rimx), rmn, __int_as_float(rimn));
-            }
-        }
-    }
-    if constexpr (NODE) {
-        // across the block's row lanes, in lane order; row lane 0 ends up with the result and stores it
-        __shared__ float smv[2048];
-        __shared__ int smi[2048];
-        const int slot = (c.ty * p.CV + c.tx) * 8;
-        const bool owner = c.ty == 0 && c.col_ok;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {          // 0: max, 1: min
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { smv[slot + e] = k ? vmin[e] : vmax[e]; smi[slot + e] = k ? tmin[e] : tmax[e]; }
-            __syncthreads();
-            if (owner) {
-                for (int r = 1; r < c.RL; ++r)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const int j = (r * p.CV + c.tx) * 8 + e;
-                        if (k) ext_take<false>(vmin[e], tmin[e], smv[j], smi[j]);
-                        else ext_take<true>(vmax[e], tmax[e], smv[j], smi[j]);
-                    }
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) smv[slot + e] = vsum[e];
-        __syncthreads();
-        if (owner) {
-            for (int r = 1; r < c.RL; ++r)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) vsum[e] += smv[(r * p.CV + c.tx) * 8 + e];
-            const float ft = (float)p.T;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vsum[e] = vsum[e] / ft;          // the one division of the mean
-            if (o.node_stats) {
-                float* d = o.node_stats + (long)c.b * 3 * p.C + c.c0;
-                store8(d, vmax); store8(d + p.C, vmin); store8(d + 2L * p.C, vsum);
-            }
-            if (o.node_when) {
-                int* d = o.node_when + (long)c.b * 2 * p.C + c.c0;
-                *reinterpret_cast<int4*>(d) = make_int4(tmax[0], tmax[1], tmax[2], tmax[3]);
-                *reinterpret_cast<int4*>(d + 4) = make_int4(tmax[4], tmax[5], tmax[6], tmax[7]);
-                *reinterpret_cast<int4*>(d + p.C) = make_int4(tmin[0], tmin[1], tmin[2], tmin[3]);
-                *reinterpret_cast<int4*>(d + p.C + 4) = make_int4(tmin[4], tmin[5], tmin[6], tmin[7]);
-            }
-        }
-    }
-}
-
-// frame partials [rows = B*T][nblk] of (max, node, min, node) -> frame_stats [rows][2], frame_where [rows][2]; one wave per row
-__global__ __launch_bounds__(256) void recon_summary_frames_kernel(const float4* part, int rows, int nblk, float* frame_stats, int* frame_where) {
-    const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    float fmx = -INFINITY, fmn = INFINITY;
-    int imx = RS_NO_INDEX, imn = RS_NO_INDEX;
-    if (row < rows) {          // wave-uniform
-        for (int j = lane; j < nblk; j += 64) {
-            const float4 v = part[(long)row * nblk + j];
-            ext_take<true>(fmx, imx, v.x, __float_as_int(v.y));
-            ext_take<false>(fmn, imn, v.z, __float_as_int(v.w));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float omx = __shfl_xor(fmx, off, 64), omn = __shfl_xor(fmn, off, 64);
-        const int oimx = __shfl_xor(imx, off, 64), oimn = __shfl_xor(imn, off, 64);
-        ext_take<true>(fmx, imx, omx, oimx);
-        ext_take<false>(fmn, imn, omn, oimn);
-    }
-    if (row < rows && lane == 0) {
-        if (frame_stats) { frame_stats[2L * row] = fmx; frame_stats[2L * row + 1] = fmn; }
-        if (frame_where) { frame_where[2L * row] = imx; frame_where[2L * row + 1] = imn; }
-    }
-}
-
-// probes[b][t][k] = the field at node nodes[k] (checked on the host: 0 <= node < C): 64 probes x 4 rows per block, the
-// per-probe constants once per thread.  mean / rstd go through gn_mean_rstd as in gn_consts, so the values are those of the
-// full pass bit for bit.
-template <typename T>
-__global__ __launch_bounds__(256) void recon_probe_kernel(const GNParams p, const ReconPhys q, const int* nodes, int K, float* out) {
-    const int k = blockIdx.x * 64 + ((int)threadIdx.x & 63), ty = (int)threadIdx.x >> 6, b = blockIdx.z;
-    if (k >= K) return;
-    const int n = nodes[k];
-    float mean, rstd;
-    gn_mean_rstd(p, b, min(n / p.Cg, p.G - 1), mean, rstd);
-    const float gam = p.gamma[n], bet = p.beta[n], mn = q.mn[n], inv = recon_phys_inv(q.scale[n]);
-    const T* y = reinterpret_cast<const T*>(p.y);
-    for (int t = blockIdx.y * 4 + ty; t < p.T; t += gridDim.y * 4) {
-        const long m = (long)b * p.T + t;
-        out[m * K + k] = recon_phys_val(to_f32(y[m * p.ldy + n]), mean, rstd, gam, bet, mn, inv);
-    }
-}
-
-// p as for ew_recon_physical; o: any subset of the five outputs (ReconSummary, sgv_ew.h), o.work = ew_recon_summary_work_floats
-// floats when a frame output is asked for.  Non-zero (nothing launched): -1 null input, -2 no output, -3 bad shape, -4 a pointer
-// not 16-byte aligned (probes, frame outputs: 4 / 8 bytes), -5 probes without a node list, -6 frame output without workspace
-int ew_recon_summary(int dtype, GNParams p, const float* scale, const float* mn, const ReconSummary& o, hipStream_t s) {
-    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn) return -1;
-    const bool node = o.node_stats || o.node_when, frame = o.frame_stats || o.frame_where;
-    if (!node && !frame && !o.probes) return -2;
-    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
-    if (((uintptr_t)p.y | (uintptr_t)o.node_stats | (uintptr_t)o.node_when | (uintptr_t)o.work) & 15) return -4;
-    if (((uintptr_t)o.frame_stats | (uintptr_t)o.frame_where) & 7) return -4;
-    if ((uintptr_t)o.probes & 3) return -4;
-    if (o.probes && (!o.probe_nodes || o.n_probes < 1)) return -5;
-    if (frame && !o.work) return -6;
-    p.Cg = p.C / p.G;
-    const ReconPhys q = {scale, mn, nullptr};
-    if (node || frame) {
-        const RSGeom g = rs_geom(p.C);
-        p.CV = g.CV;
-        const dim3 grid(g.colblocks, 1, p.B);
-#define RS_LAUNCH(TT, NODE, FRAME) hipLaunchKernelGGL((recon_summary_kernel<TT, NODE, FRAME>), grid, dim3(256), 0, s, p, q, o)
-        if (dtype == 1) { if (node && frame) RS_LAUNCH(bf16_t, true, true); else if (node) RS_LAUNCH(bf16_t, true, false); else RS_LAUNCH(bf16_t, false, true); }
-        else { if (node && frame) RS_LAUNCH(float, true, true); else if (node) RS_LAUNCH(float, true, false); else RS_LAUNCH(float, false, true); }
-#undef RS_LAUNCH
-        if (frame)
-            hipLaunchKernelGGL(recon_summary_frames_kernel, dim3(cdiv_i((long)p.B * p.T, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(o.work),
-                               p.B * p.T, g.colblocks, o.frame_stats, o.frame_where);
-    }
-    if (o.probes) {
-        const dim3 grid(cdiv_i(o.n_probes, 64), std::min(cdiv_i(p.T, 4), 64), p.B);
-        if (dtype == 1) hipLaunchKernelGGL((recon_probe_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
-        else hipLaunchKernelGGL((recon_probe_kernel<float>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Surrogate scoring (sgv_score): the summary pass with one more input stream.  e[b, t, n] = val[b, t, n] - truth[b, t, n], val the
-// value recon_phys_tn_kernel would store, truth fp32 dense [B][T][C] in physical units; reduced to, per (sample, node), max_t |e|,
-// the t of it, mean_t e and mean_t e^2, and per (sample, t), max_n |e|, its node, mean_n e^2 and mean_n truth^2 (what a relative
-// L2 error needs, so the truth is read once).  Geometry, tie rule and workspace are recon_summary_kernel's: no row split, the row
-// lanes combined through LDS in lane order, a row's channels reduced inside the wave (the maximum value first, then the smallest
-// index among its holders; the two sums in the same fixed DPP tree) into one float4 (max |e|, node, sum e^2, sum truth^2) per
-// (row, column block), which recon_score_frames_kernel combines -- the sums in fp64.  No atomics: two launches are bitwise equal.
-// ------------------------------------------------------------------------------------------
-// the error of one element: exactly one fp32 subtraction of the stored value (never contracted with the multiplication by
-// 1 / scale inside recon_phys_val: F - truth formed from the stored field F has the same bits)
-__device__ __forceinline__ float recon_score_err(float val, float truth) {
-#pragma clang fp contract(off)
-    return val - truth;
-}
-
-// No occupancy asked for, unlike recon_summary_kernel: 8 x (max, t, sum e, sum e^2) per thread plus the truth of two rows in flight take
-// 138 VGPRs (bf16; fp32 143) with all outputs, 3 waves / SIMD, no scratch; held to 128 the kernel spilled 44 bytes per lane and was
-// slower (0.537 against 0.464 ms).  Node or frame outputs alone stay under 128 and run at 4 waves.
-template <typename T, bool NODE, bool FRAME>
-__global__ __launch_bounds__(256) void recon_score_kernel(const GNParams p, const ReconPhys q, const float* __restrict__ truth, const ReconScore o) {
-    const GNCtx c = gn_ctx(p);          // gridDim.y == 1: t_lo = 0, t_hi = T
-    float mean[8], rstd[8];
-    gn_consts(p, c, mean, rstd);
-    // no early return for the lanes past C (see recon_summary_kernel): they load neither y nor truth and carry the neutral element
-    float gam[8], bet[8], mn[8], inv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        gam[e] = c.col_ok ? p.gamma[c.c0 + e] : 0.f; bet[e] = c.col_ok ? p.beta[c.c0 + e] : 0.f;
-        mn[e] = c.col_ok ? q.mn[c.c0 + e] : 0.f; inv[e] = c.col_ok ? recon_phys_inv(q.scale[c.c0 + e]) : 0.f;
-    }
-    float vmax[8], vsum[8], vsq[8];
-    int tmax[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { vmax[e] = -INFINITY; tmax[e] = RS_NO_INDEX; vsum[e] = 0.f; vsq[e] = 0.f; }
-    const T* y = reinterpret_cast<const T*>(p.y);
-    float4* const fpart = reinterpret_cast<float4*>(o.work);
-    for (int t0 = 0; t0 < p.T; t0 += 2 * c.RL) {          // block-uniform trip count; two rows per round, loads first
-        const int ta = t0 + c.ty, tb = ta + c.RL;
-        const bool oka = c.col_ok && ta < p.T, okb = c.col_ok && tb < p.T;
-        const long m0 = (long)c.b * p.T + ta, m1 = m0 + c.RL;
-        Raw8<T> r0, r1;
-        Raw8<float> w0, w1;
-        raw_zero(r0); raw_zero(r1); raw_zero(w0); raw_zero(w1);
-        if (oka) { raw_load(y + m0 * p.ldy + c.c0, r0); raw_load(truth + m0 * p.C + c.c0, w0); }
-        if (okb) { raw_load(y + m1 * p.ldy + c.c0, r1); raw_load(truth + m1 * p.C + c.c0, w1); }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const bool ok = u ? okb : oka;
-            const int t = u ? tb : ta;
-            float fmx = -INFINITY, fse = 0.f, fst = 0.f;
-            int imx = RS_NO_INDEX;
-            if (ok) {
-                float v[8], w[8];
-                raw_unpack(u ? r1 : r0, v);
-                raw_unpack(u ? w1 : w0, w);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    // squares rounded once and then added (no fused multiply-add, which the compiler would form in some instantiations
-                    // and not in others): every subset of the outputs gives the same bits
-#pragma clang fp contract(off)
-                    const float d = recon_score_err(recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]), w[e]);
-                    const float a = fabsf(d);
-                    if constexpr (NODE) {          // this thread's rows come in ascending t: a strict comparison keeps the first
-                        if (a > vmax[e]) { vmax[e] = a; tmax[e] = t; }
-                        vsum[e] += d;
-                        vsq[e] += d * d;
-                    }
-                    if constexpr (FRAME) {         // ascending n
-                        if (a > fmx) { fmx = a; imx = c.c0 + e; }
-                        fse += d * d;
-                        fst += w[e] * w[e];
-                    }
-                }
-            }
-            if constexpr (FRAME) {
-                // the row's maximum (in the last lane of the CV) back to all of its lanes; the smallest index among the lanes that hold it wins
-                const int last = ((int)threadIdx.x & 63) | (p.CV - 1);
-                const float rmx = __shfl(lane_max_f(fmx, p.CV), last, 64);
-                const int rimx = lane_min_i(fmx == rmx ? imx : RS_NO_INDEX, p.CV);
-                const float rse = lane_sum_f(fse, p.CV), rst = lane_sum_f(fst, p.CV);
-                if (c.tx == p.CV - 1 && t < p.T)
-                    fpart[((long)c.b * p.T + t) * gridDim.x + blockIdx.x] = make_float4(rmx, __int_as_float(rimx), rse, rst);
-            }
-        }
-    }
-    if constexpr (NODE) {
-        // across the block's row lanes, in lane order; row lane 0 ends up with the result and stores it
-        __shared__ float smv[2048];
-        __shared__ int smi[2048];
-        const int slot = (c.ty * p.CV + c.tx) * 8;
-        const bool owner = c.ty == 0 && c.col_ok;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { smv[slot + e] = vmax[e]; smi[slot + e] = tmax[e]; }
-        __syncthreads();
-        if (owner) {
-            for (int r = 1; r < c.RL; ++r)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int j = (r * p.CV + c.tx) * 8 + e;
-                    ext_take<true>(vmax[e], tmax[e], smv[j], smi[j]);
-                }
-        }
-        __syncthreads();
-        float* const sms = reinterpret_cast<float*>(smi);          // the two sums side by side
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { smv[slot + e] = vsum[e]; sms[slot + e] = vsq[e]; }
-        __syncthreads();
-        if (owner) {
-            for (int r = 1; r < c.RL; ++r)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int j = (r * p.CV + c.tx) * 8 + e;
-                    vsum[e] += smv[j];
-                    vsq[e] += sms[j];
-                }
-            const float ft = (float)p.T;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { vsum[e] = vsum[e] / ft; vsq[e] = vsq[e] / ft; }          // the one division of each mean
-            if (o.node_err) {
-                float* d = o.node_err + (long)c.b * 3 * p.C + c.c0;
-                store8(d, vmax); store8(d + p.C, vsum); store8(d + 2L * p.C, vsq);
-            }
-            if (o.node_when) {
-                int* d = o.node_when + (long)c.b * p.C + c.c0;
-                *reinterpret_cast<int4*>(d) = make_int4(tmax[0], tmax[1], tmax[2], tmax[3]);
-                *reinterpret_cast<int4*>(d + 4) = make_int4(tmax[4], tmax[5], tmax[6], tmax[7]);
-            }
-        }
-    }
-}
-
-// frame partials [rows = B*T][nblk] of (max |e|, node, sum e^2, sum truth^2) -> frame_err [rows][3] (max |e|, mean e^2, mean truth^2),
-// frame_where [rows]; one wave per row.  The sums: each lane adds its partials in ascending block order in fp64, then the lanes in
-// a fixed xor tree (a + b is commutative: every lane holds the same bits), one division by C, rounded to fp32 once.
-__global__ __launch_bounds__(256) void recon_score_frames_kernel(const float4* part, int rows, int nblk, int C, float* frame_err, int* frame_where) {
-    const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    float fmx = -INFINITY;
-    int imx = RS_NO_INDEX;
-    double se = 0.0, st = 0.0;
-    if (row < rows) {          // wave-uniform
-        for (int j = lane; j < nblk; j += 64) {
-            const float4 v = part[(long)row * nblk + j];
-            ext_take<true>(fmx, imx, v.x, __float_as_int(v.y));
-            se += (double)v.z;
-            st += (double)v.w;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float omx = __shfl_xor(fmx, off, 64);
-        const int oimx = __shfl_xor(imx, off, 64);
-        ext_take<true>(fmx, imx, omx, oimx);
-        se += __shfl_xor(se, off, 64);
-        st += __shfl_xor(st, off, 64);
-    }
-    if (row < rows && lane == 0) {
-        if (frame_err) {
-            frame_err[3L * row] = fmx; frame_err[3L * row + 1] = (float)(se / (double)C); frame_err[3L * row + 2] = (float)(st / (double)C);
-        }
-        if (frame_where) frame_where[row] = imx;
-    }
-}
-
-// p as for ew_recon_physical; truth fp32 dense [B][T][C]; o: any subset of the four outputs (ReconScore, sgv_ew.h), o.work =
-// ew_recon_summary_work_floats floats when a frame output is asked for.  Non-zero (nothing launched): -1 null input, -2 no output,
-// -3 bad shape, -4 y / truth / a node output / work not 16-byte aligned or a frame output not 4-byte aligned, -5 frame output
-// without workspace
-int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, const float* truth, const ReconScore& o, hipStream_t s) {
-    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn || !truth) return -1;
-    const bool node = o.node_err || o.node_when, frame = o.frame_err || o.frame_where;
-    if (!node && !frame) return -2;
-    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
-    if (((uintptr_t)p.y | (uintptr_t)truth | (uintptr_t)o.node_err | (uintptr_t)o.node_when | (uintptr_t)o.work) & 15) return -4;
-    if (((uintptr_t)o.frame_err | (uintptr_t)o.frame_where) & 3) return -4;
-    if (frame && !o.work) return -5;
-    p.Cg = p.C / p.G;
-    const ReconPhys q = {scale, mn, nullptr};
-    const RSGeom g = rs_geom(p.C);
-    p.CV = g.CV;
-    const dim3 grid(g.colblocks, 1, p.B);
-#define RS_LAUNCH(TT, NODE, FRAME) hipLaunchKernelGGL((recon_score_kernel<TT, NODE, FRAME>), grid, dim3(256), 0, s, p, q, truth, o)
-    if (dtype == 1) { if (node && frame) RS_LAUNCH(bf16_t, true, true); else if (node) RS_LAUNCH(bf16_t, true, false); else RS_LAUNCH(bf16_t, false, true); }
-    else { if (node && frame) RS_LAUNCH(float, true, true); else if (node) RS_LAUNCH(float, true, false); else RS_LAUNCH(float, false, true); }
-#undef RS_LAUNCH
-    if (frame)
-        hipLaunchKernelGGL(recon_score_frames_kernel, dim3(cdiv_i((long)p.B * p.T, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(o.work),
-                           p.B * p.T, g.colblocks, p.C, o.frame_err, o.frame_where);
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Surrogate ensemble statistics (sgv_ensemble): the reduction along the batch axis.  For every (t, n) the values the members of
-// a launch would store are merged, one member after the other in ascending order, into a running state [T][C] that outlives the
-// launch: Welford mean / M2, maximum / minimum with the index of the member that produced each, and the count of members above a
-// per-node limit.  Member b of a launch has index m = count_before + b; every update is sequential in m and the state is stored
-// in the types it is held in, so any cut of the same members into launches gives the same bits.
-// Geometry: the columns of rs_geom (CV = 64 column lanes x 4 row lanes for C >= 512, 8 channels per thread), grid (column blocks,
-// row chunks over T).  A thread owns its (t, octet) for all members: no reduction across threads, no LDS traffic besides the
-// block's table of (mean, rstd) per (member, group) -- members have different GroupNorm statistics -- which is filled once per
-// block through gn_mean_rstd, and 1 / k per member.  With count_before == 0 the state is not read.
-// ------------------------------------------------------------------------------------------
-constexpr int EN_MAX_B = 32;          // members per launch (the table); ew_recon_ensemble cuts a larger batch into several launches
-constexpr int EN_FLIGHT = 4;          // members whose y loads are issued before the first is used
-
-// 3 waves / SIMD asked for: unasked, the kernel with all groups takes 176 VGPRs (bf16; fp32 192) and runs at 2 waves;
-// held to 168 it keeps 12 bytes per lane in scratch (fp32 68) and is faster, 0.339 against 0.365 ms in one job -- the pass is bound by memory
-// and the third wave hides more latency than the three spilled dwords cost.  Every other instantiation is below 168 anyway.
-template <typename T, bool MOMENTS, bool EXTREMA, bool EXCEED>
-__global__ __launch_bounds__(256, 3) void recon_ensemble_kernel(const GNParams p, const ReconPhys q, const ReconEnsemble o, const int count_before) {
-    __shared__ float2 tab[EN_MAX_B][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of member b
-    __shared__ float rk[EN_MAX_B];                               // 1 / k, k = count_before + b + 1: one correctly rounded division per member
-    for (int i = threadIdx.x; i < p.B * p.G; i += 256) {
-        float m, r;
-        gn_mean_rstd(p, i / p.G, i % p.G, m, r);
-        tab[i / p.G][i % p.G] = make_float2(m, r);
-    }
-    if ((int)threadIdx.x < p.B) rk[threadIdx.x] = 1.0f / (float)(count_before + (int)threadIdx.x + 1);
-    __syncthreads();
-    const GNCtx c = gn_ctx(p);          // blockIdx.z == 0; c.b is not a member here
-    if (!c.col_ok) return;              // no barrier below: lanes past C touch nothing
-    float gam[8], bet[8], mn[8], inv[8], lim[8];
-    unsigned long long gidx = 0;        // the group of each of the 8 channels, one byte each
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        gam[e] = p.gamma[c.c0 + e]; bet[e] = p.beta[c.c0 + e];
-        mn[e] = q.mn[c.c0 + e]; inv[e] = recon_phys_inv(q.scale[c.c0 + e]);
-        lim[e] = EXCEED ? o.limit[c.c0 + e] : 0.f;
-        gidx |= (unsigned long long)min((c.c0 + e) / p.Cg, p.G - 1) << (8 * e);
-    }
-    const int g_lo = (int)(gidx & 0xff), g_hi = (int)(gidx >> 56);
-    const bool two = p.Cg >= 8;          // block-uniform: the octet lies in at most two groups, g_lo and g_hi
-    const T* y = reinterpret_cast<const T*>(p.y);
-    const bool fresh = count_before == 0;
-    for (int t = c.t_lo + c.ty; t < c.t_hi; t += c.RL) {
-        const long at = (long)t * p.C + c.c0;
-        float mean[8], m2[8], vmax[8], vmin[8];
-        int imax[8], imin[8], exc[8];
-        if (fresh) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { mean[e] = 0.f; m2[e] = 0.f; vmax[e] = -INFINITY; vmin[e] = INFINITY; imax[e] = 0; imin[e] = 0; exc[e] = 0; }
-        } else {
-            if constexpr (MOMENTS) { load8(o.mean + at, mean); load8(o.m2 + at, m2); }
-            if constexpr (EXTREMA) {
-                load8(o.vmax + at, vmax); load8(o.vmin + at, vmin);
-                const int4 a0 = *reinterpret_cast<const int4*>(o.imax + at), a1 = *reinterpret_cast<const int4*>(o.imax + at + 4);
-                const int4 b0 = *reinterpret_cast<const int4*>(o.imin + at), b1 = *reinterpret_cast<const int4*>(o.imin + at + 4);
-                imax[0] = a0.x; imax[1] = a0.y; imax[2] = a0.z; imax[3] = a0.w; imax[4] = a1.x; imax[5] = a1.y; imax[6] = a1.z; imax[7] = a1.w;
-                imin[0] = b0.x; imin[1] = b0.y; imin[2] = b0.z; imin[3] = b0.w; imin[4] = b1.x; imin[5] = b1.y; imin[6] = b1.z; imin[7] = b1.w;
-            }
-            if constexpr (EXCEED) {
-                const int4 a0 = *reinterpret_cast<const int4*>(o.exceed + at), a1 = *reinterpret_cast<const int4*>(o.exceed + at + 4);
-                exc[0] = a0.x; exc[1] = a0.y; exc[2] = a0.z; exc[3] = a0.w; exc[4] = a1.x; exc[5] = a1.y; exc[6] = a1.z; exc[7] = a1.w;
-            }
-        }
-        for (int b0 = 0; b0 < p.B; b0 += EN_FLIGHT) {          // EN_FLIGHT members per round, loads first
-            Raw8<T> r[EN_FLIGHT];
-#pragma unroll
-            for (int u = 0; u < EN_FLIGHT; ++u)                  // past the last member: its row again, loaded and not used
-                raw_load(y + ((long)min(b0 + u, p.B - 1) * p.T + t) * p.ldy + c.c0, r[u]);
-#pragma unroll
-            for (int u = 0; u < EN_FLIGHT; ++u) {
-                const int b = b0 + u;
-                if (b >= p.B) break;
-                const int m = count_before + b;
-                const float rkb = rk[b];
-                float v[8], gm[8], gr[8];
-                raw_unpack(r[u], v);
-                if (two) {
-                    const float2 lo = tab[b][g_lo], hi = tab[b][g_hi];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const bool up = (int)((gidx >> (8 * e)) & 0xff) != g_lo;
-                        gm[e] = up ? hi.x : lo.x; gr[e] = up ? hi.y : lo.y;
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float2 w = tab[b][(int)((gidx >> (8 * e)) & 0xff)];
-                        gm[e] = w.x; gr[e] = w.y;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    // every product and sum below rounds on its own (no fused multiply-add, which the compiler would form in some
-                    // instantiations and not in others), and x is the stored value before it meets the state
-#pragma clang fp contract(off)
-                    const float x = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
-                    if constexpr (MOMENTS) {          // Welford, one member at a time
-                        const float d = x - mean[e];
-                        mean[e] = mean[e] + d * rkb;
-                        m2[e] = m2[e] + d * (x - mean[e]);
-                    }
-                    if constexpr (EXTREMA) {          // ascending m: a strict comparison keeps the earliest member
-                        if (x > vmax[e]) { vmax[e] = x; imax[e] = m; }
-                        if (x < vmin[e]) { vmin[e] = x; imin[e] = m; }
-                    }
-                    if constexpr (EXCEED) exc[e] += x > lim[e] ? 1 : 0;
-                }
-            }
-        }
-        if constexpr (MOMENTS) { store8(o.mean + at, mean); store8(o.m2 + at, m2); }
-        if constexpr (EXTREMA) {
-            store8(o.vmax + at, vmax); store8(o.vmin + at, vmin);
-            *reinterpret_cast<int4*>(o.imax + at) = make_int4(imax[0], imax[1], imax[2], imax[3]);
-            *reinterpret_cast<int4*>(o.imax + at + 4) = make_int4(imax[4], imax[5], imax[6], imax[7]);
-            *reinterpret_cast<int4*>(o.imin + at) = make_int4(imin[0], imin[1], imin[2], imin[3]);
-            *reinterpret_cast<int4*>(o.imin + at + 4) = make_int4(imin[4], imin[5], imin[6], imin[7]);
-        }
-        if constexpr (EXCEED) {
-            *reinterpret_cast<int4*>(o.exceed + at) = make_int4(exc[0], exc[1], exc[2], exc[3]);
-            *reinterpret_cast<int4*>(o.exceed + at + 4) = make_int4(exc[4], exc[5], exc[6], exc[7]);
-        }
-    }
-}
-
-// p as for ew_recon_physical (layout [B][T][C] only); o: any of the three groups of ReconEnsemble (sgv_ew.h), each complete;
-// count_before members are already in the state (0: the state is not read).  A batch of more than EN_MAX_B members goes out as
-// several launches with count_before advanced, which is bitwise the same.  Non-zero (nothing launched): -1 null input, -2 no
-// group or half a group, -3 bad shape, -4 y or a state array not 16-byte aligned (limit 4), -5 count_before < 0 or
-// count_before + B > 2^24 (beyond that (float)k is not exact)
-int ew_recon_ensemble(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconEnsemble& o, hipStream_t s) {
-    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn) return -1;
-    const bool mo = o.mean || o.m2, ex = o.vmax || o.vmin || o.imax || o.imin, ec = o.exceed || o.limit;
-    if (!mo && !ex && !ec) return -2;
-    if ((mo && !(o.mean && o.m2)) || (ex && !(o.vmax && o.vmin && o.imax && o.imin)) || (ec && !(o.exceed && o.limit))) return -2;
-    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
-    if (((uintptr_t)p.y | (uintptr_t)o.mean | (uintptr_t)o.m2 | (uintptr_t)o.vmax | (uintptr_t)o.vmin | (uintptr_t)o.imax | (uintptr_t)o.imin |
-         (uintptr_t)o.exceed) & 15) return -4;
-    if ((uintptr_t)o.limit & 3) return -4;
-    if (count_before < 0 || count_before + p.B > (1L << 24)) return -5;
-    p.Cg = p.C / p.G;
-    const ReconPhys q = {scale, mn, nullptr};
-    const RSGeom g = rs_geom(p.C);
-    p.CV = g.CV;
-    const int RL = 256 / g.CV;
-    const int rowchunks = std::max(1, std::min(cdiv_i(p.T, RL), cdiv_i(2048, g.colblocks)));      // >= ~2048 blocks, at least one row per row lane
-    const dim3 grid(g.colblocks, rowchunks, 1);
-    const int B = p.B;
-    const size_t esz = dtype == 1 ? 2 : 4;
-    for (int b0 = 0; b0 < B; b0 += EN_MAX_B) {
-        GNParams ps = p;
-        ps.B = std::min(EN_MAX_B, B - b0);
-        ps.y = (const char*)p.y + (size_t)b0 * p.T * p.ldy * esz;
-        ps.sums = p.sums + (size_t)b0 * p.G * 2;
-        const int cb = (int)count_before + b0;
-#define EN_LAUNCH(TT, MO, EX, EC) hipLaunchKernelGGL((recon_ensemble_kernel<TT, MO, EX, EC>), grid, dim3(256), 0, s, ps, q, o, cb)
-#define EN_PICK(TT)                                                                                                   \
-        do {                                                                                                          \
-            if (mo && ex && ec) EN_LAUNCH(TT, true, true, true); else if (mo && ex) EN_LAUNCH(TT, true, true, false); \
-            else if (mo && ec) EN_LAUNCH(TT, true, false, true); else if (ex && ec) EN_LAUNCH(TT, false, true, true); \
-            else if (mo) EN_LAUNCH(TT, true, false, false); else if (ex) EN_LAUNCH(TT, false, true, false);           \
-            else EN_LAUNCH(TT, false, false, true);                                                                   \
-        } while (0)
-        if (dtype == 1) EN_PICK(bf16_t); else EN_PICK(float);
-#undef EN_PICK
-#undef EN_LAUNCH
-    }
-    return 0;
-}
-
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s) {
     float* const ws = p.part;
     const bool own_dots = mode != 0 && p.cdot && !p.cdot_part;

@@ -1,0 +1,693 @@
+// The recon tails (gfx950): passes that replace the loss tail of the recon head in surrogate use -- the physical-unit field
+// (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score) and the running statistics over the
+// members of an ensemble (sgv_ensemble).  All of them stream y = the recon head's convolution output once, form the same value per
+// element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
+#include <algorithm>
+#include <type_traits>
+#include "sgv_gn_dev.h"
+
+// ------------------------------------------------------------------------------------------
+// Surrogate prediction: recon head -> physical-unit field in one pass (sgv_generate).
+//   out = (tanh(gamma * (y - mean) * rstd + beta) - min_n) / scale_n      (MinMaxScaler.inverse_transform per node)
+// fp32 from the load of y to the fp32 store: no loss, no target read, no compute-dtype x_hat in between.  mean / rstd come from
+// p.sums exactly as in the eval loss pass (gn_consts; the normalised value is formed as (y - mean) * rstd first, as there).
+// ------------------------------------------------------------------------------------------
+struct ReconPhys { const float* scale; const float* mn; float* out; };
+// One element of the physical field and the reciprocal of its scale: the only place either is written down.  Every kernel of this
+// file calls these, so a summary, a score or an ensemble state is a reduction of bit-identical values.
+__device__ __forceinline__ float recon_phys_val(float y, float mean, float rstd, float gam, float bet, float mn, float inv) {
+    const float xh = (y - mean) * rstd;
+    return (tanh_f(xh * gam + bet) - mn) * inv;
+}
+__device__ __forceinline__ float recon_phys_inv(float scale) { return 1.0f / scale; }      // correctly rounded reciprocal, once per thread
+// the constants of channel ch, (gamma, beta, min, 1 / scale); !ok (a thread past C in the kernels whose shuffles and barriers need every
+// thread) loads nothing and gets 0.  By value, and the 8-wide loop that fills gam / bet / mn / inv stays in the kernels: handing their
+// arrays to a helper cost registers ("the recon tails").
+__device__ __forceinline__ float4 recon_channel(const GNParams& p, const ReconPhys& q, int ch, bool ok) {
+    return ok ? make_float4(p.gamma[ch], p.beta[ch], q.mn[ch], recon_phys_inv(q.scale[ch])) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// [B][T][N]: the geometry of gn_apply_kernel, 16-byte loads of y and two 16-byte stores per thread and row
+template <typename T>
+__global__ __launch_bounds__(256) void recon_phys_tn_kernel(const GNParams p, const ReconPhys q) {
+    const GNCtx c = gn_ctx(p);
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);
+    if (!c.col_ok) return;
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const T* y = reinterpret_cast<const T*>(p.y);
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += 2 * c.RL) {      // two rows per round, loads first
+        const bool two = t + c.RL < c.t_hi;
+        const long m0 = (long)c.b * p.T + t, m1 = two ? m0 + c.RL : m0;
+        Raw8<T> r0, r1;
+        raw_load(y + m0 * p.ldy + c.c0, r0);
+        raw_load(y + m1 * p.ldy + c.c0, r1);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (u == 1 && !two) break;
+            float v[8];
+            raw_unpack(u ? r1 : r0, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+            store8(q.out + (u ? m1 : m0) * p.C + c.c0, v);
+        }
+    }
+}
+
+// [B][N][T] (the reference's tensor layout): a tile of 32 rows (t) x 64 channels goes through LDS transposed; every thread loads
+// 8 channels of one row (16 / 32 bytes), the stores run along T.  blockIdx = (channel tile, row tile, sample).
+constexpr int RP_TT = 32, RP_TN = 64;
+template <typename T>
+__global__ __launch_bounds__(256) void recon_phys_nt_kernel(const GNParams p, const ReconPhys q) {
+    __shared__ float tile[RP_TN][RP_TT + 1];
+    __shared__ float cst[6][RP_TN];          // per channel of the tile: mean, rstd, gamma, beta, min, 1 / scale
+    const int b = blockIdx.z, n0 = blockIdx.x * RP_TN, t0 = blockIdx.y * RP_TT;
+    const int tid = threadIdx.x;
+    if (tid < RP_TN && n0 + tid < p.C) {
+        const int ch = n0 + tid, g = min(ch / p.Cg, p.G - 1);
+        gn_mean_rstd(p, b, g, cst[0][tid], cst[1][tid]);
+        cst[2][tid] = p.gamma[ch]; cst[3][tid] = p.beta[ch]; cst[4][tid] = q.mn[ch]; cst[5][tid] = recon_phys_inv(q.scale[ch]);
+    }
+    __syncthreads();
+    const int r = tid >> 3, cx = (tid & 7) * 8;          // row of the tile, first of this thread's 8 channels
+    const int t = t0 + r;
+    if (t < p.T && n0 + cx < p.C) {
+        float v[8];
+        load8(reinterpret_cast<const T*>(p.y) + ((long)b * p.T + t) * p.ldy + n0 + cx, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int j = cx + e;
+            tile[j][r] = recon_phys_val(v[e], cst[0][j], cst[1][j], cst[2][j], cst[3][j], cst[4][j], cst[5][j]);
+        }
+    }
+    __syncthreads();
+    const int tx = tid & 31;
+    if (t0 + tx < p.T) {
+        for (int j = tid >> 5; j < RP_TN; j += 8) {
+            if (n0 + j >= p.C) break;
+            q.out[((long)b * p.C + n0 + j) * p.T + t0 + tx] = tile[j][tx];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// What the launchers share: the checks on p, the setup of the kernels' arguments, the choice of an instantiation.
+// ------------------------------------------------------------------------------------------
+constexpr int RS_MAX_CV = 64;
+struct RSGeom { int CV, colblocks; };
+static RSGeom rs_geom(int C) {
+    const int nv = C / 8;
+    int cv = 1;
+    while (cv < nv && cv < RS_MAX_CV) cv <<= 1;
+    return {cv, cdiv_i(nv, cv)};
+}
+size_t ew_recon_summary_work_floats(int B, int T, int C) { return (size_t)B * T * rs_geom(C).colblocks * 4; }
+
+// the inputs every tail has: -1 a null pointer, -3 a bad shape, 0 fine
+static int recon_args_ok(const GNParams& p, const float* scale, const float* mn) {
+    if (!p.y || !p.sums || !p.gamma || !p.beta || !scale || !mn) return -1;
+    if (p.B < 1 || p.T < 1 || p.C < 8 || p.C % 8 || p.ldy < p.C || p.ldy % 8 || p.G < 1 || p.G > SGV_GN_MAX_GROUPS || p.C % p.G) return -3;
+    return 0;
+}
+// Cg and the column geometry of the summary / score / ensemble kernels (CV = 64 column lanes, fewer for C < 512; GN_LAUNCH sets its own)
+static ReconPhys recon_setup(GNParams& p, const float* scale, const float* mn, float* out = nullptr) {
+    p.Cg = p.C / p.G;
+    p.CV = rs_geom(p.C).CV;
+    return {scale, mn, out};
+}
+// f(Elem<T>, std::bool_constant<flag>...) for the element type of `dtype` and up to three run-time flags; the combination with every
+// flag false is never called, so a kernel template is instantiated for exactly the combinations its launcher can ask for
+template <typename T> struct Elem { using type = T; };
+template <bool... Bs, typename F>
+static void recon_dispatch(F& f, int dtype) {
+    if constexpr ((Bs || ...)) {
+        if (dtype == 1) f(Elem<bf16_t>{}, std::bool_constant<Bs>{}...);
+        else f(Elem<float>{}, std::bool_constant<Bs>{}...);
+    }
+}
+template <bool... Bs, typename F, typename... Rest>
+static void recon_dispatch(F& f, int dtype, bool b, Rest... rest) {
+    if (b) recon_dispatch<Bs..., true>(f, dtype, rest...);
+    else recon_dispatch<Bs..., false>(f, dtype, rest...);
+}
+
+// p: y / ldy / gamma / beta / sums (given) / B, T, C, G, Cg; scale, mn [C] fp32; out fp32, dense: layout 0 [B][T][C], 1 [B][C][T]
+int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn, int layout, float* out, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!out) return -1;
+    if (layout != 0 && layout != 1) return -2;
+    if (((uintptr_t)p.y | (uintptr_t)out) & 15) return -4;          // 16-byte vector accesses
+    const ReconPhys q = recon_setup(p, scale, mn, out);
+    if (layout == 0) {
+        if (dtype == 1) GN_LAUNCH((recon_phys_tn_kernel<bf16_t>), p, s, q);
+        else GN_LAUNCH((recon_phys_tn_kernel<float>), p, s, q);
+    } else {
+        const dim3 grid(cdiv_i(p.C, RP_TN), cdiv_i(p.T, RP_TT), p.B);
+        if (dtype == 1) hipLaunchKernelGGL((recon_phys_nt_kernel<bf16_t>), grid, dim3(256), 0, s, p, q);
+        else hipLaunchKernelGGL((recon_phys_nt_kernel<float>), grid, dim3(256), 0, s, p, q);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The pieces the summary and the score pass are built from.  No atomics: a block owns 8 * CV channels of one sample for ALL rows (no
+// row split), so a node's time axis lies in one block -- its RL row lanes are combined through LDS in lane order; a row's reduction
+// over the block's channels happens inside the wave, over the CV lanes of that row, and goes to a partials workspace
+// [B*T][column blocks] of float4, which recon_frames_kernel combines.  (value, index) pairs are ordered by value, then by the
+// smaller index, so the result does not depend on the shape of any tree: ties go to the smallest t / n and two launches are bitwise
+// equal.  Geometry: CV = 64 column lanes (one wave per row; fewer for C < 512), RL = 256 / CV row lanes, grid (ceil(C / (8 CV)), 1, B).
+// ------------------------------------------------------------------------------------------
+// b replaces a when it is the larger (MAX) / smaller value, or the same value at a smaller index
+template <bool MAX>
+__device__ __forceinline__ void ext_take(float& av, int& ai, float bv, int bi) {
+    const bool better = MAX ? bv > av : bv < av;
+    if (better || (bv == av && bi < ai)) { av = bv; ai = bi; }
+}
+constexpr int RS_NO_INDEX = 0x7fffffff;       // index of the neutral element: loses every tie
+// In-wave reduction over the CV lanes of a row (neighbours inside a wave, aligned to CV) with DPP operands -- VALU instructions,
+// no trip through the LDS crossbar: pairs within quads, quads within 8 and 8s within 16 lanes by mirrored exchanges (every lane
+// of a DPP row of 16 then holds that row's result), then lane 15 of each DPP row into the next row and lane 31 into the upper
+// half.  Lanes of DPP rows outside the row mask get their own value back.  The LAST lane of the CV ends up with the result.
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v);
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL, ROW_MASK>(__float_as_int(v))); }
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_i(int v) {
+    // every lane has a source in the unmasked exchanges: with bound_ctrl set the compiler may fold the move into the instruction that uses it
+    if constexpr (ROW_MASK == 0xF) return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
+    else return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xF, false);
+}
+#define RS_LANE_REDUCE(NAME, TYPE, OP, DPP)                                                      \
+    __device__ __forceinline__ TYPE NAME(TYPE v, int cv) {                                       \
+        if (cv > 1) v = OP(v, DPP<0xB1, 0xF>(v));  /* quad_perm [1, 0, 3, 2] */                  \
+        if (cv > 2) v = OP(v, DPP<0x4E, 0xF>(v));  /* quad_perm [2, 3, 0, 1] */                  \
+        if (cv > 4) v = OP(v, DPP<0x141, 0xF>(v)); /* row_half_mirror */                         \
+        if (cv > 8) v = OP(v, DPP<0x140, 0xF>(v)); /* row_mirror */                              \
+        if (cv > 16) v = OP(v, DPP<0x142, 0xA>(v)); /* row_bcast:15 into rows 1 and 3 */         \
+        if (cv > 32) v = OP(v, DPP<0x143, 0xC>(v)); /* row_bcast:31 into rows 2 and 3 */         \
+        return v;                                                                                \
+    }
+RS_LANE_REDUCE(lane_max_f, float, fmaxf, dpp_f)
+RS_LANE_REDUCE(lane_min_f, float, fminf, dpp_f)
+RS_LANE_REDUCE(lane_min_i, int, min, dpp_i)
+// the sum over a row's lanes in the same fixed tree (the score pass); lanes of DPP rows outside a row mask end up with twice their
+// value, which nobody reads: as above, only the LAST lane of the CV holds the result
+__device__ __forceinline__ float rs_add_f(float a, float b) { return a + b; }
+RS_LANE_REDUCE(lane_sum_f, float, rs_add_f, dpp_f)
+#undef RS_LANE_REDUCE
+
+// The frame reduction: the maximum (MAX) or minimum of v over the CV lanes of this thread's row and the smallest index among the lanes
+// that hold it -- i is the smallest index at which this lane saw v.  The passes are VALU-bound, not HBM-bound:
+// reducing (value, index) pairs through the DPP tree, 4 moves + 12 compare / select per step, cost more than the element arithmetic;
+// so the values are reduced alone, the winner is handed back from the last lane to the row's lanes, and the index is reduced as an
+// integer minimum.  The pair is complete in the LAST lane of the CV.
+struct ValIdx { float v; int i; };
+template <bool MAX>
+__device__ __forceinline__ ValIdx row_extremum(float v, int i, int cv) {
+    const int last = ((int)threadIdx.x & 63) | (cv - 1);
+    const float r = __shfl(MAX ? lane_max_f(v, cv) : lane_min_f(v, cv), last, 64);
+    return {r, lane_min_i(v == r ? i : RS_NO_INDEX, cv)};
+}
+
+// The row-lane combines: the RL row lanes of a block hold partial results for the same 8 channels; they meet through LDS (2048
+// entries per array: 256 threads x 8) and row lane 0 (`owner`) takes the others in lane order, so it ends up with the result.
+// All 256 threads call; a barrier separates the owner's reads from whatever is written to the arrays next.
+__device__ __forceinline__ int rowlane_slot(const GNParams& p, int ty, int tx) { return (ty * p.CV + tx) * 8; }
+template <bool MAX>
+__device__ __forceinline__ void rowlane_extremum(const GNParams& p, const GNCtx& c, bool owner, float* smv, int* smi, float v[8], int i[8]) {
+    const int slot = rowlane_slot(p, c.ty, c.tx);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { smv[slot + e] = v[e]; smi[slot + e] = i[e]; }
+    __syncthreads();
+    if (owner) {
+        for (int r = 1; r < c.RL; ++r)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int j = rowlane_slot(p, r, c.tx) + e;
+                ext_take<MAX>(v[e], i[e], smv[j], smi[j]);
+            }
+    }
+    __syncthreads();
+}
+// plain sums of one array, or of two side by side (smb / b given); the last use of the arrays: no barrier behind the owner's reads
+__device__ __forceinline__ void rowlane_sum(const GNParams& p, const GNCtx& c, bool owner, float* sma, float a[8], float* smb = nullptr,
+                                            float* b = nullptr) {
+    const int slot = rowlane_slot(p, c.ty, c.tx);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { sma[slot + e] = a[e]; if (smb) smb[slot + e] = b[e]; }
+    __syncthreads();
+    if (owner) {
+        for (int r = 1; r < c.RL; ++r)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int j = rowlane_slot(p, r, c.tx) + e;
+                a[e] += sma[j];
+                if (smb) b[e] += smb[j];
+            }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate field summaries (sgv_summarize): the same pass as recon_phys_tn_kernel with the stores replaced by reductions of the
+// values it would have stored -- per (sample, node) max / min / mean over t and the t of both extrema, per (sample, t) max / min
+// over the nodes and the node of both, and the time histories at a list of probe nodes.  Every comparison is made on the descaled
+// value (scale_n may be negative).  Frame partial: (max, node, min, node).
+// ------------------------------------------------------------------------------------------
+// 4 waves / SIMD asked for: with every output the bf16 kernel sits at 128 VGPRs without scratch (131 and 3 waves unasked; the fp32 one
+// then keeps a few dwords in scratch)
+template <typename T, bool NODE, bool FRAME>
+__global__ __launch_bounds__(256, 4) void recon_summary_kernel(const GNParams p, const ReconPhys q, const ReconSummary o) {
+    const GNCtx c = gn_ctx(p);          // gridDim.y == 1: t_lo = 0, t_hi = T
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);
+    // no early return for the lanes past C: the shuffles and barriers below need every thread; such lanes load nothing and
+    // carry the neutral element
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    float vmax[8], vmin[8], vsum[8];
+    int tmax[8], tmin[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { vmax[e] = -INFINITY; vmin[e] = INFINITY; vsum[e] = 0.f; tmax[e] = RS_NO_INDEX; tmin[e] = RS_NO_INDEX; }
+    const T* y = reinterpret_cast<const T*>(p.y);
+    float4* const fpart = reinterpret_cast<float4*>(o.work);
+    for (int t0 = 0; t0 < p.T; t0 += 2 * c.RL) {          // block-uniform trip count; two rows per round, loads first
+        const int ta = t0 + c.ty, tb = ta + c.RL;
+        const bool oka = c.col_ok && ta < p.T, okb = c.col_ok && tb < p.T;
+        const long m0 = (long)c.b * p.T + ta, m1 = m0 + c.RL;
+        Raw8<T> r0, r1;
+        raw_zero(r0); raw_zero(r1);
+        if (oka) raw_load(y + m0 * p.ldy + c.c0, r0);
+        if (okb) raw_load(y + m1 * p.ldy + c.c0, r1);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool ok = u ? okb : oka;
+            const int t = u ? tb : ta;
+            float fmx = -INFINITY, fmn = INFINITY;
+            int imx = RS_NO_INDEX, imn = RS_NO_INDEX;
+            if (ok) {
+                float v[8];
+                raw_unpack(u ? r1 : r0, v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float x = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+                    if constexpr (NODE) {          // this thread's rows come in ascending t: a strict comparison keeps the first
+                        if (x > vmax[e]) { vmax[e] = x; tmax[e] = t; }
+                        if (x < vmin[e]) { vmin[e] = x; tmin[e] = t; }
+                        vsum[e] += x;
+                    }
+                    if constexpr (FRAME) {         // ascending n
+                        if (x > fmx) { fmx = x; imx = c.c0 + e; }
+                        if (x < fmn) { fmn = x; imn = c.c0 + e; }
+                    }
+                }
+            }
+            if constexpr (FRAME) {
+                const ValIdx rmx = row_extremum<true>(fmx, imx, p.CV), rmn = row_extremum<false>(fmn, imn, p.CV);
+                if (c.tx == p.CV - 1 && t < p.T)
+                    fpart[((long)c.b * p.T + t) * gridDim.x + blockIdx.x] = make_float4(rmx.v, __int_as_float(rmx.i), rmn.v, __int_as_float(rmn.i));
+            }
+        }
+    }
+    if constexpr (NODE) {
+        __shared__ float smv[2048];
+        __shared__ int smi[2048];
+        const bool owner = c.ty == 0 && c.col_ok;
+        rowlane_extremum<true>(p, c, owner, smv, smi, vmax, tmax);
+        rowlane_extremum<false>(p, c, owner, smv, smi, vmin, tmin);
+        rowlane_sum(p, c, owner, smv, vsum);
+        if (owner) {
+            const float ft = (float)p.T;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vsum[e] = vsum[e] / ft;          // the one division of the mean
+            if (o.node_stats) {
+                float* d = o.node_stats + (long)c.b * 3 * p.C + c.c0;
+                store8(d, vmax); store8(d + p.C, vmin); store8(d + 2L * p.C, vsum);
+            }
+            if (o.node_when) {
+                int* d = o.node_when + (long)c.b * 2 * p.C + c.c0;
+                store8(d, tmax); store8(d + p.C, tmin);
+            }
+        }
+    }
+}
+
+// Frame partials [rows = B*T][nblk] -> the frame outputs; one wave per row, every lane takes its partials in ascending block order
+// and the lanes meet in a fixed xor tree.  Summary (!SCORE): (max, node, min, node) -> stats [rows][2], where [rows][2].  Score:
+// (max |e|, node, sum e^2, sum truth^2) -> stats [rows][3] (max |e|, mean e^2, mean truth^2), where [rows]; the sums in fp64 (a + b
+// is commutative: every lane of the tree holds the same bits), one division by C, rounded to fp32 once.
+template <bool MAX>
+__device__ __forceinline__ void wave_extremum(float& v, int& i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(i, off, 64);
+        ext_take<MAX>(v, i, ov, oi);
+    }
+}
+template <bool SCORE>
+__global__ __launch_bounds__(256) void recon_frames_kernel(const float4* part, int rows, int nblk, int C, float* stats, int* where) {
+    const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float fmx = -INFINITY, fmn = INFINITY;
+    int imx = RS_NO_INDEX, imn = RS_NO_INDEX;
+    double se = 0.0, st = 0.0;
+    if (row < rows) {          // wave-uniform
+        for (int j = lane; j < nblk; j += 64) {
+            const float4 v = part[(long)row * nblk + j];
+            ext_take<true>(fmx, imx, v.x, __float_as_int(v.y));
+            if constexpr (SCORE) { se += (double)v.z; st += (double)v.w; }
+            else ext_take<false>(fmn, imn, v.z, __float_as_int(v.w));
+        }
+    }
+    wave_extremum<true>(fmx, imx);
+    if constexpr (SCORE) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { se += __shfl_xor(se, off, 64); st += __shfl_xor(st, off, 64); }
+    } else wave_extremum<false>(fmn, imn);
+    if (row < rows && lane == 0) {
+        if constexpr (SCORE) {
+            if (stats) { stats[3L * row] = fmx; stats[3L * row + 1] = (float)(se / (double)C); stats[3L * row + 2] = (float)(st / (double)C); }
+            if (where) where[row] = imx;
+        } else {
+            if (stats) { stats[2L * row] = fmx; stats[2L * row + 1] = fmn; }
+            if (where) { where[2L * row] = imx; where[2L * row + 1] = imn; }
+        }
+    }
+}
+template <bool SCORE>
+static void recon_frames(const GNParams& p, const float* work, float* stats, int* where, hipStream_t s) {
+    hipLaunchKernelGGL(recon_frames_kernel<SCORE>, dim3(cdiv_i((long)p.B * p.T, 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(work),
+                       p.B * p.T, rs_geom(p.C).colblocks, p.C, stats, where);
+}
+
+// probes[b][t][k] = the field at node nodes[k] (checked on the host: 0 <= node < C): 64 probes x 4 rows per block, the
+// per-probe constants once per thread.  mean / rstd go through gn_mean_rstd as in gn_consts, so the values are those of the
+// full pass bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void recon_probe_kernel(const GNParams p, const ReconPhys q, const int* nodes, int K, float* out) {
+    const int k = blockIdx.x * 64 + ((int)threadIdx.x & 63), ty = (int)threadIdx.x >> 6, b = blockIdx.z;
+    if (k >= K) return;
+    const int n = nodes[k];
+    float mean, rstd;
+    gn_mean_rstd(p, b, min(n / p.Cg, p.G - 1), mean, rstd);
+    const float4 ch = recon_channel(p, q, n, true);
+    const T* y = reinterpret_cast<const T*>(p.y);
+    for (int t = blockIdx.y * 4 + ty; t < p.T; t += gridDim.y * 4) {
+        const long m = (long)b * p.T + t;
+        out[m * K + k] = recon_phys_val(to_f32(y[m * p.ldy + n]), mean, rstd, ch.x, ch.y, ch.z, ch.w);
+    }
+}
+
+// p as for ew_recon_physical; o: any subset of the five outputs (ReconSummary, sgv_ew.h), o.work = ew_recon_summary_work_floats
+// floats when a frame output is asked for.  Non-zero (nothing launched): -1 null input, -2 no output, -3 bad shape, -4 a pointer
+// not 16-byte aligned (probes, frame outputs: 4 / 8 bytes), -5 probes without a node list, -6 frame output without workspace
+int ew_recon_summary(int dtype, GNParams p, const float* scale, const float* mn, const ReconSummary& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    const bool node = o.node_stats || o.node_when, frame = o.frame_stats || o.frame_where;
+    if (!node && !frame && !o.probes) return -2;
+    if (((uintptr_t)p.y | (uintptr_t)o.node_stats | (uintptr_t)o.node_when | (uintptr_t)o.work) & 15) return -4;
+    if (((uintptr_t)o.frame_stats | (uintptr_t)o.frame_where) & 7) return -4;
+    if ((uintptr_t)o.probes & 3) return -4;
+    if (o.probes && (!o.probe_nodes || o.n_probes < 1)) return -5;
+    if (frame && !o.work) return -6;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    if (node || frame) {
+        const dim3 grid(rs_geom(p.C).colblocks, 1, p.B);
+        auto launch = [&](auto el, auto node_c, auto frame_c) {
+            hipLaunchKernelGGL((recon_summary_kernel<typename decltype(el)::type, decltype(node_c)::value, decltype(frame_c)::value>), grid, dim3(256), 0, s,
+                               p, q, o);
+        };
+        recon_dispatch(launch, dtype, node, frame);
+        if (frame) recon_frames<false>(p, o.work, o.frame_stats, o.frame_where, s);
+    }
+    if (o.probes) {
+        const dim3 grid(cdiv_i(o.n_probes, 64), std::min(cdiv_i(p.T, 4), 64), p.B);
+        if (dtype == 1) hipLaunchKernelGGL((recon_probe_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
+        else hipLaunchKernelGGL((recon_probe_kernel<float>), grid, dim3(256), 0, s, p, q, o.probe_nodes, o.n_probes, o.probes);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate scoring (sgv_score): the summary pass with one more input stream.  e[b, t, n] = val[b, t, n] - truth[b, t, n], val the
+// value recon_phys_tn_kernel would store, truth fp32 dense [B][T][C] in physical units; reduced to, per (sample, node), max_t |e|,
+// the t of it, mean_t e and mean_t e^2, and per (sample, t), max_n |e|, its node, mean_n e^2 and mean_n truth^2 (what a relative
+// L2 error needs, so the truth is read once).  The two frame sums go through the same fixed DPP tree as the maximum.
+// Frame partial: (max |e|, node, sum e^2, sum truth^2).
+// ------------------------------------------------------------------------------------------
+// the error of one element: exactly one fp32 subtraction of the stored value (never contracted with the multiplication by
+// 1 / scale inside recon_phys_val: F - truth formed from the stored field F has the same bits)
+__device__ __forceinline__ float recon_score_err(float val, float truth) {
+#pragma clang fp contract(off)
+    return val - truth;
+}
+
+// No occupancy asked for, unlike recon_summary_kernel: 8 x (max, t, sum e, sum e^2) per thread plus the truth of two rows in flight take
+// 138 VGPRs (bf16; fp32 143) with all outputs, 3 waves / SIMD, no scratch; held to 128 the kernel spilled 44 bytes per lane and was
+// slower (0.537 against 0.464 ms).  Node or frame outputs alone stay under 128 and run at 4 waves.
+template <typename T, bool NODE, bool FRAME>
+__global__ __launch_bounds__(256) void recon_score_kernel(const GNParams p, const ReconPhys q, const float* __restrict__ truth, const ReconScore o) {
+    const GNCtx c = gn_ctx(p);          // gridDim.y == 1: t_lo = 0, t_hi = T
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);
+    // no early return for the lanes past C (see recon_summary_kernel): they load neither y nor truth and carry the neutral element
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    float vmax[8], vsum[8], vsq[8];
+    int tmax[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { vmax[e] = -INFINITY; tmax[e] = RS_NO_INDEX; vsum[e] = 0.f; vsq[e] = 0.f; }
+    const T* y = reinterpret_cast<const T*>(p.y);
+    float4* const fpart = reinterpret_cast<float4*>(o.work);
+    for (int t0 = 0; t0 < p.T; t0 += 2 * c.RL) {          // block-uniform trip count; two rows per round, loads first
+        const int ta = t0 + c.ty, tb = ta + c.RL;
+        const bool oka = c.col_ok && ta < p.T, okb = c.col_ok && tb < p.T;
+        const long m0 = (long)c.b * p.T + ta, m1 = m0 + c.RL;
+        Raw8<T> r0, r1;
+        Raw8<float> w0, w1;
+        raw_zero(r0); raw_zero(r1); raw_zero(w0); raw_zero(w1);
+        if (oka) { raw_load(y + m0 * p.ldy + c.c0, r0); raw_load(truth + m0 * p.C + c.c0, w0); }
+        if (okb) { raw_load(y + m1 * p.ldy + c.c0, r1); raw_load(truth + m1 * p.C + c.c0, w1); }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool ok = u ? okb : oka;
+            const int t = u ? tb : ta;
+            float fmx = -INFINITY, fse = 0.f, fst = 0.f;
+            int imx = RS_NO_INDEX;
+            if (ok) {
+                float v[8], w[8];
+                raw_unpack(u ? r1 : r0, v);
+                raw_unpack(u ? w1 : w0, w);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // squares rounded once and then added (no fused multiply-add, which the compiler would form in some instantiations
+                    // and not in others): every subset of the outputs gives the same bits
+#pragma clang fp contract(off)
+                    const float d = recon_score_err(recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]), w[e]);
+                    const float a = fabsf(d);
+                    if constexpr (NODE) {          // this thread's rows come in ascending t: a strict comparison keeps the first
+                        if (a > vmax[e]) { vmax[e] = a; tmax[e] = t; }
+                        vsum[e] += d;
+                        vsq[e] += d * d;
+                    }
+                    if constexpr (FRAME) {         // ascending n
+                        if (a > fmx) { fmx = a; imx = c.c0 + e; }
+                        fse += d * d;
+                        fst += w[e] * w[e];
+                    }
+                }
+            }
+            if constexpr (FRAME) {
+                const ValIdx rmx = row_extremum<true>(fmx, imx, p.CV);
+                const float rse = lane_sum_f(fse, p.CV), rst = lane_sum_f(fst, p.CV);
+                if (c.tx == p.CV - 1 && t < p.T)
+                    fpart[((long)c.b * p.T + t) * gridDim.x + blockIdx.x] = make_float4(rmx.v, __int_as_float(rmx.i), rse, rst);
+            }
+        }
+    }
+    if constexpr (NODE) {
+        __shared__ float smv[2048];
+        __shared__ int smi[2048];
+        const bool owner = c.ty == 0 && c.col_ok;
+        rowlane_extremum<true>(p, c, owner, smv, smi, vmax, tmax);
+        rowlane_sum(p, c, owner, smv, vsum, reinterpret_cast<float*>(smi), vsq);          // the two sums side by side
+        if (owner) {
+            const float ft = (float)p.T;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { vsum[e] = vsum[e] / ft; vsq[e] = vsq[e] / ft; }          // the one division of each mean
+            if (o.node_err) {
+                float* d = o.node_err + (long)c.b * 3 * p.C + c.c0;
+                store8(d, vmax); store8(d + p.C, vsum); store8(d + 2L * p.C, vsq);
+            }
+            if (o.node_when) store8(o.node_when + (long)c.b * p.C + c.c0, tmax);
+        }
+    }
+}
+
+// p as for ew_recon_physical; truth fp32 dense [B][T][C]; o: any subset of the four outputs (ReconScore, sgv_ew.h), o.work =
+// ew_recon_summary_work_floats floats when a frame output is asked for.  Non-zero (nothing launched): -1 null input, -2 no output,
+// -3 bad shape, -4 y / truth / a node output / work not 16-byte aligned or a frame output not 4-byte aligned, -5 frame output
+// without workspace
+int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, const float* truth, const ReconScore& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!truth) return -1;
+    const bool node = o.node_err || o.node_when, frame = o.frame_err || o.frame_where;
+    if (!node && !frame) return -2;
+    if (((uintptr_t)p.y | (uintptr_t)truth | (uintptr_t)o.node_err | (uintptr_t)o.node_when | (uintptr_t)o.work) & 15) return -4;
+    if (((uintptr_t)o.frame_err | (uintptr_t)o.frame_where) & 3) return -4;
+    if (frame && !o.work) return -5;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const dim3 grid(rs_geom(p.C).colblocks, 1, p.B);
+    auto launch = [&](auto el, auto node_c, auto frame_c) {
+        hipLaunchKernelGGL((recon_score_kernel<typename decltype(el)::type, decltype(node_c)::value, decltype(frame_c)::value>), grid, dim3(256), 0, s,
+                           p, q, truth, o);
+    };
+    recon_dispatch(launch, dtype, node, frame);
+    if (frame) recon_frames<true>(p, o.work, o.frame_err, o.frame_where, s);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate ensemble statistics (sgv_ensemble): the reduction along the batch axis.  For every (t, n) the values the members of
+// a launch would store are merged, one member after the other in ascending order, into a running state [T][C] that outlives the
+// launch: Welford mean / M2, maximum / minimum with the index of the member that produced each, and the count of members above a
+// per-node limit.  Member b of a launch has index m = count_before + b; every update is sequential in m and the state is stored
+// in the types it is held in, so any cut of the same members into launches gives the same bits.
+// Geometry: the columns of rs_geom (CV = 64 column lanes x 4 row lanes for C >= 512, 8 channels per thread), grid (column blocks,
+// row chunks over T).  A thread owns its (t, octet) for all members: no reduction across threads, no LDS traffic besides the
+// block's table of (mean, rstd) per (member, group) -- members have different GroupNorm statistics -- which is filled once per
+// block through gn_mean_rstd, and 1 / k per member.  With count_before == 0 the state is not read.
+// ------------------------------------------------------------------------------------------
+constexpr int EN_MAX_B = 32;          // members per launch (the table); ew_recon_ensemble cuts a larger batch into several launches
+constexpr int EN_FLIGHT = 4;          // members whose y loads are issued before the first is used
+
+// 3 waves / SIMD asked for: unasked, the kernel with all groups takes 176 VGPRs (bf16; fp32 192) and runs at 2 waves;
+// held to 168 it keeps 12 bytes per lane in scratch (fp32 68) and is faster, 0.339 against 0.365 ms in one job -- the pass is bound by memory
+// and the third wave hides more latency than the three spilled dwords cost.  Every other instantiation is below 168 anyway.
+template <typename T, bool MOMENTS, bool EXTREMA, bool EXCEED>
+__global__ __launch_bounds__(256, 3) void recon_ensemble_kernel(const GNParams p, const ReconPhys q, const ReconEnsemble o, const int count_before) {
+    __shared__ float2 tab[EN_MAX_B][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of member b
+    __shared__ float rk[EN_MAX_B];                               // 1 / k, k = count_before + b + 1: one correctly rounded division per member
+    for (int i = threadIdx.x; i < p.B * p.G; i += 256) {
+        float m, r;
+        gn_mean_rstd(p, i / p.G, i % p.G, m, r);
+        tab[i / p.G][i % p.G] = make_float2(m, r);
+    }
+    if ((int)threadIdx.x < p.B) rk[threadIdx.x] = 1.0f / (float)(count_before + (int)threadIdx.x + 1);
+    __syncthreads();
+    const GNCtx c = gn_ctx(p);          // blockIdx.z == 0; c.b is not a member here
+    if (!c.col_ok) return;              // no barrier below: lanes past C touch nothing
+    float lim[8];
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    unsigned long long gidx = 0;        // the group of each of the 8 channels, one byte each
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        lim[e] = EXCEED ? o.limit[c.c0 + e] : 0.f;
+        gidx |= (unsigned long long)min((c.c0 + e) / p.Cg, p.G - 1) << (8 * e);
+    }
+    const int g_lo = (int)(gidx & 0xff), g_hi = (int)(gidx >> 56);
+    const bool two = p.Cg >= 8;          // block-uniform: the octet lies in at most two groups, g_lo and g_hi
+    const T* y = reinterpret_cast<const T*>(p.y);
+    const bool fresh = count_before == 0;
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += c.RL) {
+        const long at = (long)t * p.C + c.c0;
+        float mean[8], m2[8], vmax[8], vmin[8];
+        int imax[8], imin[8], exc[8];
+        if (fresh) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { mean[e] = 0.f; m2[e] = 0.f; vmax[e] = -INFINITY; vmin[e] = INFINITY; imax[e] = 0; imin[e] = 0; exc[e] = 0; }
+        } else {
+            if constexpr (MOMENTS) { load8(o.mean + at, mean); load8(o.m2 + at, m2); }
+            if constexpr (EXTREMA) { load8(o.vmax + at, vmax); load8(o.vmin + at, vmin); load8(o.imax + at, imax); load8(o.imin + at, imin); }
+            if constexpr (EXCEED) load8(o.exceed + at, exc);
+        }
+        for (int b0 = 0; b0 < p.B; b0 += EN_FLIGHT) {          // EN_FLIGHT members per round, loads first
+            Raw8<T> r[EN_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < EN_FLIGHT; ++u)                  // past the last member: its row again, loaded and not used
+                raw_load(y + ((long)min(b0 + u, p.B - 1) * p.T + t) * p.ldy + c.c0, r[u]);
+#pragma unroll
+            for (int u = 0; u < EN_FLIGHT; ++u) {
+                const int b = b0 + u;
+                if (b >= p.B) break;
+                const int m = count_before + b;
+                const float rkb = rk[b];
+                float v[8], gm[8], gr[8];
+                raw_unpack(r[u], v);
+                if (two) {
+                    const float2 lo = tab[b][g_lo], hi = tab[b][g_hi];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const bool up = (int)((gidx >> (8 * e)) & 0xff) != g_lo;
+                        gm[e] = up ? hi.x : lo.x; gr[e] = up ? hi.y : lo.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float2 w = tab[b][(int)((gidx >> (8 * e)) & 0xff)];
+                        gm[e] = w.x; gr[e] = w.y;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // every product and sum below rounds on its own (no fused multiply-add, which the compiler would form in some
+                    // instantiations and not in others), and x is the stored value before it meets the state
+#pragma clang fp contract(off)
+                    const float x = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
+                    if constexpr (MOMENTS) {          // Welford, one member at a time
+                        const float d = x - mean[e];
+                        mean[e] = mean[e] + d * rkb;
+                        m2[e] = m2[e] + d * (x - mean[e]);
+                    }
+                    if constexpr (EXTREMA) {          // ascending m: a strict comparison keeps the earliest member
+                        if (x > vmax[e]) { vmax[e] = x; imax[e] = m; }
+                        if (x < vmin[e]) { vmin[e] = x; imin[e] = m; }
+                    }
+                    if constexpr (EXCEED) exc[e] += x > lim[e] ? 1 : 0;
+                }
+            }
+        }
+        if constexpr (MOMENTS) { store8(o.mean + at, mean); store8(o.m2 + at, m2); }
+        if constexpr (EXTREMA) { store8(o.vmax + at, vmax); store8(o.vmin + at, vmin); store8(o.imax + at, imax); store8(o.imin + at, imin); }
+        if constexpr (EXCEED) store8(o.exceed + at, exc);
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: any of the three groups of ReconEnsemble (sgv_ew.h), each complete;
+// count_before members are already in the state (0: the state is not read).  A batch of more than EN_MAX_B members goes out as
+// several launches with count_before advanced, which is bitwise the same.  Non-zero (nothing launched): -1 null input, -2 no
+// group or half a group, -3 bad shape, -4 y or a state array not 16-byte aligned (limit 4), -5 count_before < 0 or
+// count_before + B > 2^24 (beyond that (float)k is not exact)
+int ew_recon_ensemble(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconEnsemble& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    const bool mo = o.mean || o.m2, ex = o.vmax || o.vmin || o.imax || o.imin, ec = o.exceed || o.limit;
+    if (!mo && !ex && !ec) return -2;
+    if ((mo && !(o.mean && o.m2)) || (ex && !(o.vmax && o.vmin && o.imax && o.imin)) || (ec && !(o.exceed && o.limit))) return -2;
+    if (((uintptr_t)p.y | (uintptr_t)o.mean | (uintptr_t)o.m2 | (uintptr_t)o.vmax | (uintptr_t)o.vmin | (uintptr_t)o.imax | (uintptr_t)o.imin |
+         (uintptr_t)o.exceed) & 15) return -4;
+    if ((uintptr_t)o.limit & 3) return -4;
+    if (count_before < 0 || count_before + p.B > (1L << 24)) return -5;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const RSGeom g = rs_geom(p.C);
+    const int RL = 256 / g.CV;
+    const int rowchunks = std::max(1, std::min(cdiv_i(p.T, RL), cdiv_i(2048, g.colblocks)));      // >= ~2048 blocks, at least one row per row lane
+    const dim3 grid(g.colblocks, rowchunks, 1);
+    const int B = p.B;
+    const size_t esz = dtype == 1 ? 2 : 4;
+    for (int b0 = 0; b0 < B; b0 += EN_MAX_B) {
+        GNParams ps = p;
+        ps.B = std::min(EN_MAX_B, B - b0);
+        ps.y = (const char*)p.y + (size_t)b0 * p.T * p.ldy * esz;
+        ps.sums = p.sums + (size_t)b0 * p.G * 2;
+        const int cb = (int)count_before + b0;
+        auto launch = [&](auto el, auto mo_c, auto ex_c, auto ec_c) {
+            hipLaunchKernelGGL((recon_ensemble_kernel<typename decltype(el)::type, decltype(mo_c)::value, decltype(ex_c)::value, decltype(ec_c)::value>), grid,
+                               dim3(256), 0, s, ps, q, o, cb);
+        };
+        recon_dispatch(launch, dtype, mo, ex, ec);
+    }
+    return 0;
+}

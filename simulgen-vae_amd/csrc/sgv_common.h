@@ -45,6 +45,15 @@ __device__ __forceinline__ void store8(bf16_t* p, const float v[8]) {
     for (int i = 0; i < 8; ++i) a[i] = (bf16_t)v[i];
     *reinterpret_cast<bf16x8*>(p) = a;
 }
+__device__ __forceinline__ void load8(const int* p, int v[8]) {
+    const int4 a = *reinterpret_cast<const int4*>(p);
+    const int4 b = *reinterpret_cast<const int4*>(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+__device__ __forceinline__ void store8(int* p, const int v[8]) {
+    *reinterpret_cast<int4*>(p) = make_int4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<int4*>(p + 4) = make_int4(v[4], v[5], v[6], v[7]);
+}
 
 // 8 consecutive elements as loaded (16 B of bf16 / 32 B of fp32): lets a thread issue several loads before unpacking any
 template <typename T> struct Raw8;

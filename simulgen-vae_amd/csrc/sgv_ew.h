@@ -1,4 +1,4 @@
-// Host-callable launchers of the elementwise / normalisation / optimizer kernels (ew.hip, optim.hip).
+// Host-callable launchers of the elementwise / normalisation / optimizer kernels (ew.hip, recon_out.hip, optim.hip).
 #pragma once
 #include "sgv_common.h"
 #include <vector>
@@ -110,6 +110,7 @@ int ew_gn_max_blocks(int B, int T, int C);
 int ew_act_part_rows(int B, int T, int C);         // rows of per-block column sums an ew_act launch with dbias writes          // upper bound of the per-block <G,W_eff> partials one launch writes
 int ew_recon_loss(int dtype, int train, GNParams p, hipStream_t s);
 int ew_recon_bwd_apply(int dtype, GNParams p, hipStream_t s);
+// ---- the recon tails (recon_out.hip): passes that replace the loss tail of the recon head ----
 // recon head -> physical-unit fp32 field: out = (tanh(GroupNorm(y)) - mn) / scale per channel; layout 0 [B][T][C], 1 [B][C][T] (dense).
 // Non-zero (nothing launched): -1 null pointer, -2 unknown layout, -3 bad shape, -4 y or out not 16-byte aligned
 int ew_recon_physical(int dtype, GNParams p, const float* scale, const float* mn, int layout, float* out, hipStream_t s);

@@ -164,7 +164,7 @@ int sgv_test_gemm_tn(int dtype, const void* A, const void* Bm, float* dW, int M,
     return gemm_hook_done(r, "launch_gemm_tn", "gemm_tn", stream, {partial});
 }
 
-// ---- test hooks for the non-GEMM kernels (ew.hip): argument checks, the launcher the engine calls, sync ----
+// ---- test hooks for the non-GEMM kernels (ew.hip, recon_out.hip): argument checks, the launcher the engine calls, sync ----
 static int ew_hook_done(int r, const char* what, void* stream) {
     const hipError_t le = hipGetLastError();
     const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
@@ -245,136 +245,91 @@ int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long
     }
     return ew_hook_done(r, "sgv_test_recon_loss", stream);
 }
-int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
-                            const float* scale, const float* min, int layout, float* out, int B, int T, int C, void* stream) {
-    const char* me = "sgv_test_recon_physical";
+// The four recon-tail hooks (recon_out.hip).  Front: the checks on what they all take, the model's group rule G = min(8, max(1, C / 4))
+// and the GNParams of the recon head's map.  Back: a workspace [statistics | extra_floats for the pass], the statistics of y, the pass
+// itself -- pass(p, extra, s) -> the launcher's code -- the sync and the free.
+static int recon_hook_front(const char* me, int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, int B, int T, int C, GNParams& p) {
     if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
-    if (!y || !sums || !gamma || !beta || !scale || !min || !out) return fail(SGV_ERR_ARG, "%s: null argument", me);
-    if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "%s: unknown layout %d", me, layout);
+    if (!y || !sums || !gamma || !beta || !scale || !min) return fail(SGV_ERR_ARG, "%s: null argument", me);
     if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
     if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
-    if (((uintptr_t)y | (uintptr_t)out) & 15) return fail(SGV_ERR_ARG, "%s: y and out must be 16-byte aligned", me);
-    GNParams p;
+    if ((uintptr_t)y & 15) return fail(SGV_ERR_ARG, "%s: misaligned pointer (y 16 bytes)", me);
     p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
     if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
     p.y = y; p.ldy = ldy; p.sums = sums;
+    return SGV_OK;
+}
+extern "C++" template <typename Pass>
+static int recon_hook_run(const char* me, int dtype, GNParams& p, size_t extra_floats, void* stream, Pass pass) {
+    const size_t stat_floats = align_up(ew_gn_part_floats(p.B, p.T, p.C), 4);
     float* work = nullptr;
-    HIPCHK(hipMalloc((void**)&work, sizeof(float) * ew_gn_part_floats(B, T, C)));
+    HIPCHK(hipMalloc((void**)&work, sizeof(float) * (stat_floats + extra_floats)));
     p.part = work;
     hipStream_t s = (hipStream_t)stream;
     int r = ew_gn_stats(dtype, p, s);
-    if (!r) r = ew_recon_physical(dtype, p, scale, min, layout, out, s);
+    if (!r) r = pass(p, work + stat_floats, s);
     const int rc = ew_hook_done(r, me, stream);
     hipFree(work);
     return rc;
+}
+int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, int layout, float* out, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_physical";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    if (!out) return fail(SGV_ERR_ARG, "%s: null argument", me);
+    if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "%s: unknown layout %d", me, layout);
+    if ((uintptr_t)out & 15) return fail(SGV_ERR_ARG, "%s: out must be 16-byte aligned", me);
+    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) { return ew_recon_physical(dtype, q, scale, min, layout, out, s); });
 }
 int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                            const float* scale, const float* min, const sgv_summary_out* out, const int32_t* probes_host,
                            int n_probes, int B, int T, int C, void* stream) {
     const char* me = "sgv_test_recon_summary";
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
-    if (!y || !sums || !gamma || !beta || !scale || !min || !out) return fail(SGV_ERR_ARG, "%s: null argument", me);
-    if (!out->node_stats && !out->node_when && !out->frame_stats && !out->frame_where && !out->probes)
-        return fail(SGV_ERR_ARG, "%s: all five outputs are NULL", me);
-    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
-    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(summary_out_ok(me, "pointer", out));
     if (out->probes && (!probes_host || n_probes < 1)) return fail(SGV_ERR_ARG, "%s: probes asked for, but no probe nodes are given", me);
     if (!out->probes) n_probes = 0;
     if (n_probes > SGV_MAX_PROBES) return fail(SGV_ERR_ARG, "%s: %d probe nodes, at most %d", me, n_probes, SGV_MAX_PROBES);
     const int bad = first_bad_probe(probes_host, n_probes, C);
     if (bad >= 0) return fail(SGV_ERR_ARG, "%s: probe nodes[%d] = %d is outside [0, %d)", me, bad, (int)probes_host[bad], C);
-    if (((uintptr_t)y & 15) || (((uintptr_t)out->node_stats | (uintptr_t)out->node_when) & 15) ||
-        (((uintptr_t)out->frame_stats | (uintptr_t)out->frame_where) & 7) || ((uintptr_t)out->probes & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (y, node_stats / node_when 16 bytes, frame_stats / frame_where 8, probes 4)", me);
-    GNParams p;
-    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
-    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
-    p.y = y; p.ldy = ldy; p.sums = sums;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t stat_floats = align_up(ew_gn_part_floats(B, T, C), 4);          // [statistics workspace | frame partials | probe nodes]
-    const size_t frame_floats = ew_recon_summary_work_floats(B, T, C);
-    float* work = nullptr;
-    HIPCHK(hipMalloc((void**)&work, sizeof(float) * (stat_floats + frame_floats + (size_t)n_probes)));
-    p.part = work;
-    ReconSummary o;
-    o.node_stats = out->node_stats; o.node_when = out->node_when; o.frame_stats = out->frame_stats; o.frame_where = out->frame_where;
-    o.probes = out->probes; o.work = work + stat_floats;
+    int* nodes = nullptr;
     if (n_probes) {
-        o.probe_nodes = reinterpret_cast<const int*>(work + stat_floats + frame_floats); o.n_probes = n_probes;
-        if (hipMemcpy(work + stat_floats + frame_floats, probes_host, sizeof(int32_t) * n_probes, hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(work);
+        HIPCHK(hipMalloc((void**)&nodes, sizeof(int32_t) * n_probes));
+        if (hipMemcpy(nodes, probes_host, sizeof(int32_t) * n_probes, hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(nodes);
             return fail(SGV_ERR_HIP, "%s: the probe nodes could not be copied to the device", me);
         }
     }
-    int r = ew_gn_stats(dtype, p, s);
-    if (!r) r = ew_recon_summary(dtype, p, scale, min, o, s);
-    const int rc = ew_hook_done(r, me, stream);
-    hipFree(work);
+    const int rc = recon_hook_run(me, dtype, p, ew_recon_summary_work_floats(B, T, C), stream, [&](const GNParams& q, float* frames, hipStream_t s) {
+        return ew_recon_summary(dtype, q, scale, min, recon_summary_of(*out, nodes, n_probes, frames), s);
+    });
+    hipFree(nodes);          // after the sync of recon_hook_run
     return rc;
 }
 int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                          const float* scale, const float* min, const float* truth, const sgv_score_out* out, int B, int T, int C,
                          void* stream) {
     const char* me = "sgv_test_recon_score";
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
-    if (!y || !sums || !gamma || !beta || !scale || !min || !truth || !out) return fail(SGV_ERR_ARG, "%s: null argument", me);
-    if (!out->node_err && !out->node_when && !out->frame_err && !out->frame_where) return fail(SGV_ERR_ARG, "%s: all four outputs are NULL", me);
-    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
-    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
-    if ((((uintptr_t)y | (uintptr_t)truth | (uintptr_t)out->node_err | (uintptr_t)out->node_when) & 15) ||
-        (((uintptr_t)out->frame_err | (uintptr_t)out->frame_where) & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (y, truth, node_err / node_when 16 bytes, frame_err / frame_where 4)", me);
     GNParams p;
-    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
-    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
-    p.y = y; p.ldy = ldy; p.sums = sums;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t stat_floats = align_up(ew_gn_part_floats(B, T, C), 4);          // [statistics workspace | frame partials]
-    float* work = nullptr;
-    HIPCHK(hipMalloc((void**)&work, sizeof(float) * (stat_floats + ew_recon_summary_work_floats(B, T, C))));
-    p.part = work;
-    ReconScore o;
-    o.node_err = out->node_err; o.node_when = out->node_when; o.frame_err = out->frame_err; o.frame_where = out->frame_where;
-    o.work = work + stat_floats;
-    int r = ew_gn_stats(dtype, p, s);
-    if (!r) r = ew_recon_score(dtype, p, scale, min, truth, o, s);
-    const int rc = ew_hook_done(r, me, stream);
-    hipFree(work);
-    return rc;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(score_out_ok(me, "truth", truth, out));
+    return recon_hook_run(me, dtype, p, ew_recon_summary_work_floats(B, T, C), stream, [&](const GNParams& q, float* extra, hipStream_t s) {
+        return ew_recon_score(dtype, q, scale, min, truth, recon_score_of(*out, extra), s);
+    });
 }
 int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, long count_before, const sgv_ensemble_state* st, int B, int T,
                             int C, void* stream) {
     const char* me = "sgv_test_recon_ensemble";
-    if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
-    if (!y || !sums || !gamma || !beta || !scale || !min || !st) return fail(SGV_ERR_ARG, "%s: null argument", me);
-    const bool mo = st->mean || st->m2, ex = st->max || st->min || st->arg_max || st->arg_min, ec = st->exceed || st->limit;
-    if (!mo && !ex && !ec) return fail(SGV_ERR_ARG, "%s: no group of the state is given", me);
-    if ((mo && !(st->mean && st->m2)) || (ex && !(st->max && st->min && st->arg_max && st->arg_min)) || (ec && !(st->exceed && st->limit)))
-        return fail(SGV_ERR_ARG, "%s: half a group (mean + m2, max + min + arg_max + arg_min, limit + exceed go together)", me);
-    if (B < 1 || T < 1 || C < 8 || C % 8) return fail(SGV_ERR_ARG, "%s: B, T >= 1 and C %% 8 == 0 required (B %d, T %d, C %d)", me, B, T, C);
-    if (!ld_ok(ldy, C)) return fail(SGV_ERR_ARG, "%s: the row stride must be >= C and a multiple of 8", me);
-    if ((((uintptr_t)y | (uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->max | (uintptr_t)st->min | (uintptr_t)st->arg_max |
-          (uintptr_t)st->arg_min | (uintptr_t)st->exceed) & 15) || ((uintptr_t)st->limit & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (y and the state arrays 16 bytes, limit 4)", me);
-    if (count_before < 0 || count_before + B > (1L << 24))
-        return fail(SGV_ERR_ARG, "%s: count_before = %ld with B = %d is outside [0, 2^24]", me, count_before, B);
     GNParams p;
-    p.B = B; p.T = T; p.C = C; p.G = std::min(8, std::max(1, C / 4)); p.Cg = C / p.G; p.gamma = gamma; p.beta = beta;
-    if (C % p.G) return fail(SGV_ERR_ARG, "%s: C = %d is not a multiple of its %d groups", me, C, p.G);
-    p.y = y; p.ldy = ldy; p.sums = sums;
-    hipStream_t s = (hipStream_t)stream;
-    float* work = nullptr;
-    HIPCHK(hipMalloc((void**)&work, sizeof(float) * ew_gn_part_floats(B, T, C)));          // statistics workspace
-    p.part = work;
-    ReconEnsemble o;
-    o.mean = st->mean; o.m2 = st->m2; o.vmax = st->max; o.vmin = st->min; o.imax = st->arg_max; o.imin = st->arg_min;
-    o.limit = st->limit; o.exceed = st->exceed;
-    int r = ew_gn_stats(dtype, p, s);
-    if (!r) r = ew_recon_ensemble(dtype, p, scale, min, count_before, o, s);
-    const int rc = ew_hook_done(r, me, stream);
-    hipFree(work);
-    return rc;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(ensemble_state_ok(me, "B", st, count_before, B));
+    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
+        return ew_recon_ensemble(dtype, q, scale, min, count_before, recon_ensemble_of(*st), s);
+    });
 }
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,

@@ -440,18 +440,15 @@ class Engine:
         if layout not in LAYOUTS:
             raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, not {layout!r}")
         N, T = self.cfg.num_node, self.cfg.num_time
-        B, z, xs_t = self._latents(z, xs)
-        self._scaler(scale, min)
-        shape = (B, T, N) if layout == "TN" else (B, N, T)
-        if out is None:
-            out = t.empty(shape, dtype=t.float32, device="cuda")
-        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and tuple(out.shape) == shape):
-            raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
-        _check(self.lib, self.lib.sgv_generate(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
-                                               C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), LAYOUTS[layout],
-                                               C.c_void_p(out.data_ptr())), "sgv_generate")
-        self.batch = B
-        return out
+
+        def tail(B, out=out):
+            shape = (B, T, N) if layout == "TN" else (B, N, T)
+            if out is None:
+                out = t.empty(shape, dtype=t.float32, device="cuda")
+            elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
+            return (LAYOUTS[layout], C.c_void_p(out.data_ptr())), out
+        return self._surrogate("sgv_generate", z, xs, scale, min, fix, tail)
 
     def _latents(self, z, xs):
         """the checks generate and summarize share: z [B, latent] and xs as fp32 CUDA tensors"""
@@ -468,6 +465,30 @@ class Engine:
         for name, v in (("scale", scale), ("min", min)):
             if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == N):
                 raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
+
+    def _surrogate(self, entry, z, xs, scale, min, fix, tail):
+        """the call generate, summarize, score and ensemble share: the checks on z, xs, scale and min, then tail(B) -> (the entry
+        point's trailing arguments, what to return), which checks whatever depends on the batch, then the C call"""
+        B, z, xs_t = self._latents(z, xs)
+        self._scaler(scale, min)
+        args, res = tail(B)
+        _check(self.lib, getattr(self.lib, entry)(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
+                                                  C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), *args), entry)
+        self.batch = B
+        return res
+
+    def _named_outputs(self, shapes, out):
+        """name -> CUDA tensor for every name -> (shape, dtype) of `shapes`: out[name] where the caller gave one (checked), else a new one"""
+        t = self.torch
+        res = {}
+        for name, (shape, dt) in shapes.items():
+            v = None if out is None else out.get(name)
+            if v is None:
+                v = t.empty(shape, dtype=dt, device="cuda")
+            elif not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
+                raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
+            res[name] = v
+        return res
 
     def set_probes(self, nodes):
         """The probe nodes of summarize(): a 1-D integer sequence of at most MAX_PROBES node indices in [0, num_node); an empty
@@ -496,29 +517,19 @@ class Engine:
             raise ValueError(f"want must name at least one of {SUMMARY_PARTS}, not {want!r}")
         if "probes" in want and self.n_probes < 1:
             raise ValueError("want includes 'probes', but no probe nodes are set (set_probes)")
-        B, z, xs_t = self._latents(z, xs)
-        self._scaler(scale, min)
         N, T = self.cfg.num_node, self.cfg.num_time
-        shapes = {}
-        if "node" in want:
-            shapes.update(node_stats=((B, 3, N), t.float32), node_when=((B, 2, N), t.int32))
-        if "frame" in want:
-            shapes.update(frame_stats=((B, T, 2), t.float32), frame_where=((B, T, 2), t.int32))
-        if "probes" in want:
-            shapes.update(probes=((B, T, self.n_probes), t.float32))
-        res = {}
-        for name, (shape, dt) in shapes.items():
-            v = None if out is None else out.get(name)
-            if v is None:
-                v = t.empty(shape, dtype=dt, device="cuda")
-            elif not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
-                raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
-            res[name] = v
-        so = SummaryOut(**{name: v.data_ptr() for name, v in res.items()})
-        _check(self.lib, self.lib.sgv_summarize(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
-                                                C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), C.byref(so)), "sgv_summarize")
-        self.batch = B
-        return res
+
+        def tail(B):
+            shapes = {}
+            if "node" in want:
+                shapes.update(node_stats=((B, 3, N), t.float32), node_when=((B, 2, N), t.int32))
+            if "frame" in want:
+                shapes.update(frame_stats=((B, T, 2), t.float32), frame_where=((B, T, 2), t.int32))
+            if "probes" in want:
+                shapes.update(probes=((B, T, self.n_probes), t.float32))
+            res = self._named_outputs(shapes, out)
+            return (C.byref(SummaryOut(**{name: v.data_ptr() for name, v in res.items()})),), res
+        return self._surrogate("sgv_summarize", z, xs, scale, min, fix, tail)
 
     def score(self, z, xs, scale, min, truth, fix=True, want=SCORE_PARTS, out=None):
         """The error of the field generate() would write against `truth` (contiguous fp32 CUDA [B, T, N], physical units), reduced by
@@ -532,30 +543,19 @@ class Engine:
         want = tuple(want)
         if not want or any(w not in SCORE_PARTS for w in want):
             raise ValueError(f"want must name at least one of {SCORE_PARTS}, not {want!r}")
-        B, z, xs_t = self._latents(z, xs)
-        self._scaler(scale, min)
         N, T = self.cfg.num_node, self.cfg.num_time
-        if not (t.is_tensor(truth) and truth.is_cuda and truth.dtype == t.float32 and truth.is_contiguous() and tuple(truth.shape) == (B, T, N)):
-            raise ValueError(f"truth must be a contiguous float32 CUDA tensor of shape {(B, T, N)}")
-        shapes = {}
-        if "node" in want:
-            shapes.update(node_err=((B, 3, N), t.float32), node_when=((B, N), t.int32))
-        if "frame" in want:
-            shapes.update(frame_err=((B, T, 3), t.float32), frame_where=((B, T), t.int32))
-        res = {}
-        for name, (shape, dt) in shapes.items():
-            v = None if out is None else out.get(name)
-            if v is None:
-                v = t.empty(shape, dtype=dt, device="cuda")
-            elif not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
-                raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
-            res[name] = v
-        so = ScoreOut(**{name: v.data_ptr() for name, v in res.items()})
-        _check(self.lib, self.lib.sgv_score(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
-                                            C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), C.c_void_p(truth.data_ptr()),
-                                            C.byref(so)), "sgv_score")
-        self.batch = B
-        return res
+
+        def tail(B):
+            if not (t.is_tensor(truth) and truth.is_cuda and truth.dtype == t.float32 and truth.is_contiguous() and tuple(truth.shape) == (B, T, N)):
+                raise ValueError(f"truth must be a contiguous float32 CUDA tensor of shape {(B, T, N)}")
+            shapes = {}
+            if "node" in want:
+                shapes.update(node_err=((B, 3, N), t.float32), node_when=((B, N), t.int32))
+            if "frame" in want:
+                shapes.update(frame_err=((B, T, 3), t.float32), frame_where=((B, T), t.int32))
+            res = self._named_outputs(shapes, out)
+            return (C.c_void_p(truth.data_ptr()), C.byref(ScoreOut(**{name: v.data_ptr() for name, v in res.items()}))), res
+        return self._surrogate("sgv_score", z, xs, scale, min, fix, tail)
 
     def ensemble(self, z, xs, scale, min, state, count_before, fix=True):
         """Merges the fields generate() would write for this batch into the running statistics `state`, per (time step, node), by
@@ -586,17 +586,13 @@ class Engine:
             shape = (N,) if k == "limit" else (T, N)
             if not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
                 raise ValueError(f"state[{k!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
-        B, z, xs_t = self._latents(z, xs)
-        self._scaler(scale, min)
-        count_before = int(count_before)
-        if count_before < 0 or count_before + B > ENSEMBLE_MAX_COUNT:
-            raise ValueError(f"count_before = {count_before} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
-        st = EnsembleState(**{k: v.data_ptr() for k, v in state.items() if v is not None})
-        _check(self.lib, self.lib.sgv_ensemble(self.h, C.c_void_p(z.data_ptr()), C.c_void_p(xs_t.data_ptr()), B, int(fix),
-                                               C.c_void_p(scale.data_ptr()), C.c_void_p(min.data_ptr()), count_before, C.byref(st)),
-               "sgv_ensemble")
-        self.batch = B
-        return state
+
+        def tail(B):
+            cb = int(count_before)
+            if cb < 0 or cb + B > ENSEMBLE_MAX_COUNT:
+                raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
+            return (cb, C.byref(EnsembleState(**{k: v.data_ptr() for k, v in state.items() if v is not None}))), state
+        return self._surrogate("sgv_ensemble", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -1,4 +1,4 @@
-"""numpy float32 emulation of the ensemble pass (csrc/ew.hip: recon_ensemble_kernel): the contract of its
+"""numpy float32 emulation of the ensemble pass (csrc/recon_out.hip: recon_ensemble_kernel): the contract of its
 arithmetic, one np.float32 operation -- one rounding -- per operation of the kernel, members one after the other.
 
 For member b of a call, index m = count_before + b, value x (an fp32 array [T, N]):

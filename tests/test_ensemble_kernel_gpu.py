@@ -1,4 +1,4 @@
-"""The ensemble pass alone (csrc/ew.hip: recon_ensemble_kernel; include/sgvae.h: sgv_test_recon_ensemble): the values
+"""The ensemble pass alone (csrc/recon_out.hip: recon_ensemble_kernel; include/sgvae.h: sgv_test_recon_ensemble): the values
 val[b, t, n] = (tanh(GroupNorm(y)) - min_n) / scale_n  of the members b of a launch are merged, member after member, into a running
 state per (t, n) -- Welford mean / M2, max / min with the member's index, the count above a limit -- and never stored.  Inputs as
 tests/test_summary_kernel_gpu.py builds them; a quarter of the scales are negative.
@@ -25,12 +25,10 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ensemble_reference as ER  # noqa: E402
+from recon_kernel_common import _bf16, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs, margins_intact, padding_intact  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 768.0
-ICANARY = -777
-MARGIN = 64         # elements of canary in front of and behind every buffer (keeps it 16-byte aligned)
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 80), (16, 3, 72, 72), (4, 9, 2080, 2080)]     # (B, T, C, ldy)
 GROUPS = {"moments": ("mean", "m2"), "extrema": ("max", "min", "arg_max", "arg_min"), "exceed": ("limit", "exceed")}
 ALL = tuple(GROUPS)
@@ -39,46 +37,12 @@ INT = ("arg_max", "arg_min", "exceed")
 DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
 
 
-def _groups(Cn):
-    return min(8, max(1, Cn // 4))
-
-
 def make_inputs(B, T, Cn, dtype):
     import torch
-    rng = np.random.default_rng(1000 * Cn + 10 * T + B + dtype)
-    y = (rng.standard_normal((B, T, Cn)) * 2 + 0.5).astype(np.float32)
-    gamma = (1.6 + 0.4 * rng.standard_normal(Cn)).astype(np.float32)
-    beta = (0.3 * rng.standard_normal(Cn)).astype(np.float32)
-    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), Cn)).astype(np.float32)
-    mn = (rng.standard_normal(Cn) * np.where(rng.random(Cn) < 0.5, 1.0, 30.0)).astype(np.float32)
-    scale = np.where(rng.random(Cn) < 0.25, -scale, scale).astype(np.float32)
+    c = base_inputs(B, T, Cn, dtype)
     if dtype == 1:
-        y = torch.from_numpy(y).to(torch.bfloat16).to(torch.float32).numpy()
-    return dict(y=y, gamma=gamma, beta=beta, scale=scale, mn=mn)
-
-
-def device_inputs(c, y, ldy, dtype):
-    """y [b, T, C]: the members of this launch"""
-    import torch
-    b, T, Cn = y.shape
-    ymap = torch.full((b * T, ldy), CANARY, dtype=torch.bfloat16 if dtype == 1 else torch.float32, device="cuda")
-    ymap[:, :Cn] = torch.from_numpy(np.array(y).reshape(b * T, Cn)).cuda().to(ymap.dtype)
-    f = lambda a: torch.from_numpy(np.array(a)).cuda()
-    sums = torch.full((b * _groups(Cn) * 2,), float("nan"), dtype=torch.float64, device="cuda")
-    return dict(y=ymap, gamma=f(c["gamma"]), beta=f(c["beta"]), scale=f(c["scale"]), mn=f(c["mn"]), sums=sums)
-
-
-def field(c, y, ldy, dtype):
-    """F: the existing output pass on the same inputs, [b, T, C] fp32"""
-    import torch
-    lib = E.load_library()
-    b, T, Cn = y.shape
-    d = device_inputs(c, y, ldy, dtype)
-    out = torch.full((b * T * Cn,), float("nan"), dtype=torch.float32, device="cuda")
-    rc = lib.sgv_test_recon_physical(dtype, d["y"].data_ptr(), ldy, d["sums"].data_ptr(), d["gamma"].data_ptr(), d["beta"].data_ptr(),
-                                     d["scale"].data_ptr(), d["mn"].data_ptr(), 0, out.data_ptr(), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    return out.cpu().numpy().reshape(b, T, Cn)
+        c["y"] = _bf16(torch, c["y"])
+    return c
 
 
 _CASES = {}
@@ -102,19 +66,7 @@ def case(B, T, Cn, ldy, dtype):
 
 def buffers(T, Cn):
     """name -> (whole buffer with canary margins, the array's view), for the seven state arrays and the limit"""
-    import torch
-    bufs = {}
-    for name in STATE + ("limit",):
-        n = Cn if name == "limit" else T * Cn
-        integer = name in INT
-        buf = torch.full((n + 2 * MARGIN,), ICANARY if integer else CANARY, dtype=torch.int32 if integer else torch.float32, device="cuda")
-        bufs[name] = (buf, buf[MARGIN:MARGIN + n])
-        assert bufs[name][1].data_ptr() % 16 == 0
-    return bufs
-
-
-def margins_intact(bufs):
-    return all(bool((b[:MARGIN] == b[0]).all()) and bool((b[-MARGIN:] == b[0]).all()) and float(b[0]) in (CANARY, ICANARY) for b, _ in bufs.values())
+    return canary_buffers({name: Cn if name == "limit" else T * Cn for name in STATE + ("limit",)}, integer=INT)
 
 
 FILL = {True: -5, False: float("nan")}          # what a state array holds before a launch from empty: must not be read
@@ -139,20 +91,14 @@ def launch(c, y, ldy, dtype, groups=ALL, count_before=0, state=None, limit=None)
     before = {n: v.clone() for n, (_, v) in bufs.items()}
     asked = [k for g in groups for k in GROUPS[g]]
     st = E.EnsembleState(**{k: bufs[k][1].data_ptr() for k in asked})
-    rc = lib.sgv_test_recon_ensemble(dtype, d["y"].data_ptr(), ldy, d["sums"].data_ptr(), d["gamma"].data_ptr(), d["beta"].data_ptr(),
-                                     d["scale"].data_ptr(), d["mn"].data_ptr(), count_before, C.byref(st), b, T, Cn, None)
+    rc = lib.sgv_test_recon_ensemble(dtype, *hook_inputs(d, ldy), count_before, C.byref(st), b, T, Cn, None)
     assert rc == 0, lib.sgv_last_error().decode()
     assert margins_intact(bufs), "a margin around a buffer was written"
-    assert bool((d["y"][:, Cn:].float() == CANARY).all()), "the padding columns of y were written"
+    assert padding_intact(d, Cn), "the padding columns of y were written"
     for name in bufs:
         if name not in asked or name == "limit":
             assert bool((bufs[name][1].view(torch.int32) == before[name].view(torch.int32)).all()), f"{name} was written"
     return {n: bufs[n][1].cpu().numpy().reshape(T, Cn) for n in STATE}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
 
 
 def same(a, b, names=STATE):

@@ -1,4 +1,4 @@
-"""The output pass of surrogate prediction alone (csrc/ew.hip: recon_phys_*; include/sgvae.h: sgv_test_recon_physical) against
+"""The output pass of surrogate prediction alone (csrc/recon_out.hip: recon_phys_*; include/sgvae.h: sgv_test_recon_physical) against
 float64:  out[b, t, n] = (tanh(GroupNorm(y)[b, t, n]) - min_n) / scale_n,  layouts [B][T][N] and [B][N][T], fp32 out.
 
 x_hat_ref comes from tests/ew_reference.py (GroupNorm + tanh in float64, as tests/test_ew_kernels_gpu.py uses it); the descale is
@@ -25,21 +25,11 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
+from recon_kernel_common import CANARY, ELT32, MARGIN, _bf16, _groups, base_inputs, device_inputs, hook_inputs, padding_intact  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ELT32 = 2e-5        # tests/test_ew_kernels_gpu.py
-CANARY = 768.0
-MARGIN = 64         # floats of canary in front of and behind the output (keeps it 16-byte aligned)
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 72), (2, 10, 72, 80), (2, 200, 2080, 2080)]     # (B, T, C, ldy)
-
-
-def _groups(Cn):
-    return min(8, max(1, Cn // 4))
-
-
-def _bf16(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
 _CASES = {}
@@ -50,14 +40,10 @@ def case(B, T, Cn, dtype):
     key = (B, T, Cn, dtype)
     if key not in _CASES:
         import torch
-        rng = np.random.default_rng(1000 * Cn + 10 * T + B + dtype)
-        y = (rng.standard_normal((B, T, Cn)) * 2 + 0.5).astype(np.float32)
+        c = base_inputs(B, T, Cn, dtype, signed=False)
+        y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
         if dtype == 1:
             y = _bf16(torch, y)
-        gamma = (1.6 + 0.4 * rng.standard_normal(Cn)).astype(np.float32)          # spread enough that tanh saturates somewhere
-        beta = (0.3 * rng.standard_normal(Cn)).astype(np.float32)
-        scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), Cn)).astype(np.float32)   # mixed magnitudes in [1e-3, 50]
-        mn = (rng.standard_normal(Cn) * np.where(rng.random(Cn) < 0.5, 1.0, 30.0)).astype(np.float32)   # both signs
         xhat = R.gn_forward(y, _groups(Cn), gamma, beta, 2)["out"]
         assert np.abs(xhat).max() > 0.99, "the inputs do not reach tanh's saturation"
         ref = (xhat - mn.astype(np.float64)) / scale.astype(np.float64)
@@ -70,22 +56,16 @@ def run(c, B, T, Cn, ldy, dtype, layout):
     """-> (out [B, T, C] float64 in the reference's axis order, raw buffer) after one call of the hook"""
     import torch
     lib = E.load_library()
-    ymap = torch.full((B * T, ldy), CANARY, dtype=torch.bfloat16 if dtype == 1 else torch.float32, device="cuda")
-    ymap[:, :Cn] = torch.from_numpy(c["y"].reshape(B * T, Cn)).cuda().to(ymap.dtype)
-    f = lambda a: torch.from_numpy(a).cuda()
-    gamma, beta, scale, mn = f(c["gamma"]), f(c["beta"]), f(c["scale"]), f(c["mn"])
-    G = _groups(Cn)
-    sums = torch.full((B * G * 2,), float("nan"), dtype=torch.float64, device="cuda")
+    d = device_inputs(c, c["y"], ldy, dtype)
     n = B * T * Cn
     buf = torch.full((n + 2 * MARGIN,), CANARY, dtype=torch.float32, device="cuda")
     buf[MARGIN:MARGIN + n] = float("nan")
     out = buf[MARGIN:MARGIN + n]
     assert out.data_ptr() % 16 == 0
-    rc = lib.sgv_test_recon_physical(dtype, ymap.data_ptr(), ldy, sums.data_ptr(), gamma.data_ptr(), beta.data_ptr(), scale.data_ptr(),
-                                     mn.data_ptr(), layout, out.data_ptr(), B, T, Cn, None)
+    rc = lib.sgv_test_recon_physical(dtype, *hook_inputs(d, ldy), layout, out.data_ptr(), B, T, Cn, None)
     assert rc == 0, lib.sgv_last_error().decode()
     assert bool((buf[:MARGIN] == CANARY).all()) and bool((buf[MARGIN + n:] == CANARY).all()), "the margin around the output was written"
-    assert bool((ymap[:, Cn:].float() == CANARY).all()), "the padding columns of y were written"
+    assert padding_intact(d, Cn), "the padding columns of y were written"
     got = out.double().cpu().numpy()
     got = got.reshape(B, T, Cn) if layout == 0 else got.reshape(B, Cn, T).transpose(0, 2, 1)
     return got, buf.clone()

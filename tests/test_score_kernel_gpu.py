@@ -1,4 +1,4 @@
-"""The error pass of surrogate scoring alone (csrc/ew.hip: recon_score_kernel, recon_score_frames_kernel; include/sgvae.h:
+"""The error pass of surrogate scoring alone (csrc/recon_out.hip: recon_score_kernel, recon_frames_kernel; include/sgvae.h:
 sgv_test_recon_score): reductions of  e[b, t, n] = val[b, t, n] - truth[b, t, n],  val = (tanh(GroupNorm(y)) - min_n) / scale_n,
 that store neither val nor e.  Inputs as tests/test_summary_kernel_gpu.py builds them (a quarter of the scales negative); truth is
 the float64 reference rounded to fp32 and perturbed, ref * (1 + 0.1 g1) + 0.05 g2 / |scale_n|, so that the errors are neither zero
@@ -37,25 +37,15 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
+from recon_kernel_common import (CANARY, ELT32, ICANARY, _bf16, _groups, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs,  # noqa: E402
+                                 margins_intact, padding_intact)
 
 pytestmark = pytest.mark.gpu
 
-ELT32 = 2e-5        # tests/test_ew_kernels_gpu.py
 U = 2.0 ** -24
-CANARY = 768.0
-ICANARY = -777
-MARGIN = 64         # elements of canary in front of and behind every output (keeps it 16-byte aligned)
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 72), (2, 10, 72, 80), (2, 200, 2080, 2080)]     # (B, T, C, ldy)
 OUTPUTS = ("node_err", "node_when", "frame_err", "frame_where")
 BLOCK_CHANNELS = 512          # 8 channels x 64 column lanes
-
-
-def _groups(Cn):
-    return min(8, max(1, Cn // 4))
-
-
-def _bf16(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
 def make_inputs(B, T, Cn, dtype, variant=None):
@@ -63,13 +53,8 @@ def make_inputs(B, T, Cn, dtype, variant=None):
     node n2 a copy of node n1 (column of y, gamma, beta, scale, min and truth), dominant in |e|.  Adds the float64 reference `ref`,
     its element bound `tol` and `truth` (fp32)."""
     import torch
-    rng = np.random.default_rng(1000 * Cn + 10 * T + B + dtype)
-    y = (rng.standard_normal((B, T, Cn)) * 2 + 0.5).astype(np.float32)
-    gamma = (1.6 + 0.4 * rng.standard_normal(Cn)).astype(np.float32)
-    beta = (0.3 * rng.standard_normal(Cn)).astype(np.float32)
-    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), Cn)).astype(np.float32)
-    mn = (rng.standard_normal(Cn) * np.where(rng.random(Cn) < 0.5, 1.0, 30.0)).astype(np.float32)
-    scale = np.where(rng.random(Cn) < 0.25, -scale, scale).astype(np.float32)
+    c = base_inputs(B, T, Cn, dtype)
+    y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
     if variant == "rows":
         y[:] = y[:, :1]
     elif variant is not None:
@@ -107,63 +92,30 @@ def case(B, T, Cn, dtype):
     return _CASES[key]
 
 
-def device_inputs(c, B, T, Cn, ldy, dtype):
-    import torch
-    ymap = torch.full((B * T, ldy), CANARY, dtype=torch.bfloat16 if dtype == 1 else torch.float32, device="cuda")
-    ymap[:, :Cn] = torch.from_numpy(c["y"].reshape(B * T, Cn)).cuda().to(ymap.dtype)
-    f = lambda a: torch.from_numpy(a).cuda()
-    sums = torch.full((B * _groups(Cn) * 2,), float("nan"), dtype=torch.float64, device="cuda")
-    return dict(y=ymap, gamma=f(c["gamma"]), beta=f(c["beta"]), scale=f(c["scale"]), mn=f(c["mn"]), sums=sums)
-
-
 def out_buffers(B, T, Cn, which=OUTPUTS):
     """name -> (whole buffer with canary margins, the output's view)"""
-    import torch
     sizes = dict(node_err=B * 3 * Cn, node_when=B * Cn, frame_err=B * T * 3, frame_where=B * T)
-    bufs = {}
-    for name in which:
-        integer = name in ("node_when", "frame_where")
-        buf = torch.full((sizes[name] + 2 * MARGIN,), ICANARY if integer else CANARY, dtype=torch.int32 if integer else torch.float32, device="cuda")
-        bufs[name] = (buf, buf[MARGIN:MARGIN + sizes[name]])
-        assert bufs[name][1].data_ptr() % 16 == 0
-    return bufs
-
-
-def margins_intact(bufs):
-    return all(bool((b[:MARGIN] == b[0]).all()) and bool((b[-MARGIN:] == b[0]).all()) and float(b[0]) in (CANARY, ICANARY) for b, _ in bufs.values())
+    return canary_buffers({name: sizes[name] for name in which}, integer=("node_when", "frame_where"))
 
 
 def score(c, B, T, Cn, ldy, dtype, which=OUTPUTS, truth=None):
     """one call of the hook -> (dict of numpy outputs in their documented shapes, dict of the raw buffers)"""
     import torch
     lib = E.load_library()
-    d = device_inputs(c, B, T, Cn, ldy, dtype)
+    d = device_inputs(c, c["y"], ldy, dtype)
     tr = torch.from_numpy(np.ascontiguousarray(c["truth"] if truth is None else truth, np.float32)).cuda()
     keep = tr.clone()
     bufs = out_buffers(B, T, Cn, which)
     for _, view in bufs.values():
         view.fill_(float("nan") if view.dtype == torch.float32 else -1)
     so = E.ScoreOut(**{name: view.data_ptr() for name, (_, view) in bufs.items()})
-    rc = lib.sgv_test_recon_score(dtype, d["y"].data_ptr(), ldy, d["sums"].data_ptr(), d["gamma"].data_ptr(), d["beta"].data_ptr(),
-                                  d["scale"].data_ptr(), d["mn"].data_ptr(), tr.data_ptr(), C.byref(so), B, T, Cn, None)
+    rc = lib.sgv_test_recon_score(dtype, *hook_inputs(d, ldy), tr.data_ptr(), C.byref(so), B, T, Cn, None)
     assert rc == 0, lib.sgv_last_error().decode()
     assert margins_intact(bufs), "a margin around an output was written"
-    assert bool((d["y"][:, Cn:].float() == CANARY).all()), "the padding columns of y were written"
+    assert padding_intact(d, Cn), "the padding columns of y were written"
     assert bool((tr.view(torch.int32) == keep.view(torch.int32)).all()), "the truth was written"
     shapes = dict(node_err=(B, 3, Cn), node_when=(B, Cn), frame_err=(B, T, 3), frame_where=(B, T))
     return {n: v.cpu().numpy().reshape(shapes[n]) for n, (_, v) in bufs.items()}, {n: b.clone() for n, (b, _) in bufs.items()}
-
-
-def field(c, B, T, Cn, ldy, dtype):
-    """F: the existing output pass on the same inputs, [B, T, C] fp32"""
-    import torch
-    lib = E.load_library()
-    d = device_inputs(c, B, T, Cn, ldy, dtype)
-    out = torch.full((B * T * Cn,), float("nan"), dtype=torch.float32, device="cuda")
-    rc = lib.sgv_test_recon_physical(dtype, d["y"].data_ptr(), ldy, d["sums"].data_ptr(), d["gamma"].data_ptr(), d["beta"].data_ptr(),
-                                     d["scale"].data_ptr(), d["mn"].data_ptr(), 0, out.data_ptr(), B, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    return out.cpu().numpy().reshape(B, T, Cn)
 
 
 _RUNS = {}
@@ -174,12 +126,8 @@ def run_once(B, T, Cn, ldy, dtype):
     if key not in _RUNS:
         c = case(B, T, Cn, dtype)
         got, raw = score(c, B, T, Cn, ldy, dtype)
-        _RUNS[key] = (got, raw, field(c, B, T, Cn, ldy, dtype))
+        _RUNS[key] = (got, raw, field(c, c["y"], ldy, dtype))
     return _RUNS[key]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def sum_bound(abs_terms, axis, m):
@@ -280,7 +228,7 @@ def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     assert n1 // Cg == n2 // Cg and n1 // 8 != n2 // 8 and (Cn < 2080 or n1 // BLOCK_CHANNELS != n2 // BLOCK_CHANNELS)
     c = make_inputs(B, T, Cn, dtype, pair)
     got, _ = score(c, B, T, Cn, ldy, dtype)
-    E32 = field(c, B, T, Cn, ldy, dtype) - c["truth"]
+    E32 = field(c, c["y"], ldy, dtype) - c["truth"]
     assert np.array_equal(bits(E32[:, :, n1]), bits(E32[:, :, n2]))
     assert_exact(got, E32)
     at_max = np.abs(E32[:, :, n1]) == np.abs(E32).max(axis=2)

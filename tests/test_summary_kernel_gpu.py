@@ -1,4 +1,4 @@
-"""The summary pass of the surrogate sweep alone (csrc/ew.hip: recon_summary_*, recon_probe_kernel; include/sgvae.h:
+"""The summary pass of the surrogate sweep alone (csrc/recon_out.hip: recon_summary_*, recon_probe_kernel; include/sgvae.h:
 sgv_test_recon_summary): reductions of  val[b, t, n] = (tanh(GroupNorm(y)[b, t, n]) - min_n) / scale_n  that never store val.
 
 Two references.
@@ -33,23 +33,13 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
+from recon_kernel_common import (CANARY, ELT32, ICANARY, _bf16, _groups, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs,  # noqa: E402
+                                 margins_intact, padding_intact)
 
 pytestmark = pytest.mark.gpu
 
-ELT32 = 2e-5        # tests/test_ew_kernels_gpu.py
-CANARY = 768.0
-ICANARY = -777
-MARGIN = 64         # elements of canary in front of and behind every output (keeps it 16-byte aligned)
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 72), (2, 10, 72, 80), (2, 200, 2080, 2080)]     # (B, T, C, ldy)
 OUTPUTS = ("node_stats", "node_when", "frame_stats", "frame_where", "probes")
-
-
-def _groups(Cn):
-    return min(8, max(1, Cn // 4))
-
-
-def _bf16(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
 def probe_list(Cn, K):
@@ -60,13 +50,8 @@ def make_inputs(B, T, Cn, dtype, variant=None):
     """the inputs of tests/test_generate_kernel_gpu.py with a quarter of the scales negative; variant "rows": every row a copy of
     row 0; variant (n1, n2): node n2 a copy of node n1 (column of y, gamma, beta, scale, min), dominant in magnitude"""
     import torch
-    rng = np.random.default_rng(1000 * Cn + 10 * T + B + dtype)
-    y = (rng.standard_normal((B, T, Cn)) * 2 + 0.5).astype(np.float32)
-    gamma = (1.6 + 0.4 * rng.standard_normal(Cn)).astype(np.float32)
-    beta = (0.3 * rng.standard_normal(Cn)).astype(np.float32)
-    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), Cn)).astype(np.float32)
-    mn = (rng.standard_normal(Cn) * np.where(rng.random(Cn) < 0.5, 1.0, 30.0)).astype(np.float32)
-    scale = np.where(rng.random(Cn) < 0.25, -scale, scale).astype(np.float32)
+    c = base_inputs(B, T, Cn, dtype)
+    y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
     if variant == "rows":
         y[:] = y[:, :1]
     elif variant is not None:
@@ -97,61 +82,28 @@ def case(B, T, Cn, dtype):
     return _CASES[key]
 
 
-def device_inputs(c, B, T, Cn, ldy, dtype):
-    import torch
-    ymap = torch.full((B * T, ldy), CANARY, dtype=torch.bfloat16 if dtype == 1 else torch.float32, device="cuda")
-    ymap[:, :Cn] = torch.from_numpy(c["y"].reshape(B * T, Cn)).cuda().to(ymap.dtype)
-    f = lambda a: torch.from_numpy(a).cuda()
-    sums = torch.full((B * _groups(Cn) * 2,), float("nan"), dtype=torch.float64, device="cuda")
-    return dict(y=ymap, gamma=f(c["gamma"]), beta=f(c["beta"]), scale=f(c["scale"]), mn=f(c["mn"]), sums=sums)
-
-
 def out_buffers(B, T, Cn, K, which=OUTPUTS):
     """name -> (whole buffer with canary margins, the output's view)"""
-    import torch
     sizes = dict(node_stats=B * 3 * Cn, node_when=B * 2 * Cn, frame_stats=B * T * 2, frame_where=B * T * 2, probes=B * T * K)
-    bufs = {}
-    for name in which:
-        integer = name in ("node_when", "frame_where")
-        buf = torch.full((sizes[name] + 2 * MARGIN,), ICANARY if integer else CANARY, dtype=torch.int32 if integer else torch.float32, device="cuda")
-        bufs[name] = (buf, buf[MARGIN:MARGIN + sizes[name]])
-        assert bufs[name][1].data_ptr() % 16 == 0
-    return bufs
-
-
-def margins_intact(bufs):
-    return all(bool((b[:MARGIN] == b[0]).all()) and bool((b[-MARGIN:] == b[0]).all()) and float(b[0]) in (CANARY, ICANARY) for b, _ in bufs.values())
+    return canary_buffers({name: sizes[name] for name in which}, integer=("node_when", "frame_where"))
 
 
 def summary(c, B, T, Cn, ldy, dtype, K, which=OUTPUTS):
     """one call of the hook -> (dict of numpy outputs in their documented shapes, dict of the raw buffers)"""
     import torch
     lib = E.load_library()
-    d = device_inputs(c, B, T, Cn, ldy, dtype)
+    d = device_inputs(c, c["y"], ldy, dtype)
     bufs = out_buffers(B, T, Cn, K, which)
     for _, view in bufs.values():
         view.fill_(float("nan") if view.dtype == torch.float32 else -1)
     so = E.SummaryOut(**{name: view.data_ptr() for name, (_, view) in bufs.items()})
     nodes = probe_list(Cn, K)
-    rc = lib.sgv_test_recon_summary(dtype, d["y"].data_ptr(), ldy, d["sums"].data_ptr(), d["gamma"].data_ptr(), d["beta"].data_ptr(),
-                                    d["scale"].data_ptr(), d["mn"].data_ptr(), C.byref(so), nodes.ctypes.data_as(C.c_void_p), K, B, T, Cn, None)
+    rc = lib.sgv_test_recon_summary(dtype, *hook_inputs(d, ldy), C.byref(so), nodes.ctypes.data_as(C.c_void_p), K, B, T, Cn, None)
     assert rc == 0, lib.sgv_last_error().decode()
     assert margins_intact(bufs), "a margin around an output was written"
-    assert bool((d["y"][:, Cn:].float() == CANARY).all()), "the padding columns of y were written"
+    assert padding_intact(d, Cn), "the padding columns of y were written"
     shapes = dict(node_stats=(B, 3, Cn), node_when=(B, 2, Cn), frame_stats=(B, T, 2), frame_where=(B, T, 2), probes=(B, T, K))
     return {n: v.cpu().numpy().reshape(shapes[n]) for n, (_, v) in bufs.items()}, {n: b.clone() for n, (b, _) in bufs.items()}
-
-
-def field(c, B, T, Cn, ldy, dtype):
-    """F: the existing output pass on the same inputs, [B, T, C] fp32"""
-    import torch
-    lib = E.load_library()
-    d = device_inputs(c, B, T, Cn, ldy, dtype)
-    out = torch.full((B * T * Cn,), float("nan"), dtype=torch.float32, device="cuda")
-    rc = lib.sgv_test_recon_physical(dtype, d["y"].data_ptr(), ldy, d["sums"].data_ptr(), d["gamma"].data_ptr(), d["beta"].data_ptr(),
-                                     d["scale"].data_ptr(), d["mn"].data_ptr(), 0, out.data_ptr(), B, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    return out.cpu().numpy().reshape(B, T, Cn)
 
 
 _RUNS = {}
@@ -163,13 +115,9 @@ def run_once(B, T, Cn, ldy, dtype, K):
         c = case(B, T, Cn, dtype)
         got, raw = summary(c, B, T, Cn, ldy, dtype, K)
         if (B, T, Cn, ldy, dtype) not in _RUNS:
-            _RUNS[(B, T, Cn, ldy, dtype)] = field(c, B, T, Cn, ldy, dtype)
+            _RUNS[(B, T, Cn, ldy, dtype)] = field(c, c["y"], ldy, dtype)
         _RUNS[key] = (got, raw, _RUNS[(B, T, Cn, ldy, dtype)])
     return _RUNS[key]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def assert_exact(got, F, nodes):
@@ -250,7 +198,7 @@ def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     assert n1 // Cg == n2 // Cg and n2 - n1 >= 8
     c = make_inputs(B, T, Cn, dtype, pair)
     got, _ = summary(c, B, T, Cn, ldy, dtype, 1)
-    F = field(c, B, T, Cn, ldy, dtype)
+    F = field(c, c["y"], ldy, dtype)
     assert np.array_equal(bits(F[:, :, n1]), bits(F[:, :, n2]))
     assert_exact(got, F, probe_list(Cn, 1))
     at_max, at_min = F[:, :, n1] == F.max(axis=2), F[:, :, n1] == F.min(axis=2)

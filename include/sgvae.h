@@ -269,6 +269,26 @@ typedef struct {
  * the checks of sgv_decode.  Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
 int sgv_ensemble(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                  const float* min_dev, long count_before, const sgv_ensemble_state* st);
+/* The running sums of a variance-based sensitivity study (Sobol indices by Jansen's estimators) per (time step, node).  Device
+ * pointers, 16-byte aligned, dense: mean, m2 fp32 [T][N] (Welford over the A and B members); first_sq, total_sq fp32 [d][T][N],
+ * d = n_params (sums of squared differences per parameter).  mean and m2 are required and at least one of first_sq, total_sq.
+ * The state belongs to the caller and persists across calls: the kernel reads, updates and writes it in place.  With n base
+ * samples in it: var = m2 / (2 n), S_i = 1 - first_sq[i] / (2 n var), ST_i = total_sq[i] / (2 n var). */
+typedef struct { float* mean; float* m2; float* first_sq; float* total_sq; } sgv_sobol_state;
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the Sobol pass.  The batch holds whole
+ * blocks of n_params + 2 members in this order: A_j, B_j, AB_1_j .. AB_d_j, where AB_i_j is base sample A_j with the inputs of
+ * parameter i taken from B_j; block j of the call is base sample blocks_before + j.  With x the value sgv_generate would store
+ * (SGV_LAYOUT_TN), all in fp32 and every operation rounded on its own, j ascending: Welford's update of mean / m2 with A_j
+ * (k = 2 j + 1) and then B_j (k = 2 j + 2), r = 1.0f / k, d = x - mean, mean += d * r, m2 += d * (x - mean); for every parameter
+ * e = xB - xAB_i, first_sq[i] += e * e and e = xA - xAB_i, total_sq[i] += e * e.  With blocks_before == 0 the state is not read.
+ * Any cut of the same blocks into calls gives the same bits, the decoder's noise included: it follows the member's index
+ * blocks_before * (n_params + 2) + b by the mechanism of sgv_ensemble, and the draw position is left where it is.  No atomics, no
+ * workspace, nothing allocated.  SGV_ERR_ARG before anything is enqueued: e, z_dev, scale_dev, min_dev or st NULL, mean or m2
+ * missing, neither first_sq nor total_sq, a misaligned pointer, n_params outside [1, 30], batch no multiple of n_params + 2,
+ * blocks_before < 0 or 2 (blocks_before + blocks) > 2^24, the checks of sgv_decode.  Synchronises nothing.  Afterwards there is no
+ * forward pass to read from, as after sgv_generate. */
+int sgv_sobol(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+              const float* min_dev, int n_params, long blocks_before, const sgv_sobol_state* st);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -550,6 +570,14 @@ int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const
 int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, long count_before, const sgv_ensemble_state* st, int B, int T,
                             int C, void* stream);
+/* The kernel of sgv_sobol on caller-owned buffers: inputs as sgv_test_recon_physical, B = whole blocks of n_params + 2 members,
+ * then the statistics of y and the Sobol pass into *st (shapes of sgv_sobol_state with N = C).  SGV_ERR_ARG, nothing launched: a
+ * NULL input, st NULL, mean or m2 missing, neither first_sq nor total_sq, B or T < 1, C < 8 or C % 8 != 0, a bad row stride, a
+ * misaligned pointer (y and the state arrays 16 bytes), n_params outside [1, 30], B no multiple of n_params + 2,
+ * blocks_before < 0 or 2 (blocks_before + blocks) > 2^24. */
+int sgv_test_recon_sobol(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                         const float* scale, const float* min, int n_params, long blocks_before, const sgv_sobol_state* st, int B,
+                         int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

@@ -888,23 +888,28 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 }
 
 // What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
-// (sgv_summarize), its error against the truth (sgv_score) or the ensemble statistics (sgv_ensemble); only the members of `kind` are read.
+// (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble) or the sums of a Sobol study
+// (sgv_sobol); only the members of `kind` are read.
 struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE } kind;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL } kind;
     const float* scale; const float* mn;
     int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
     ReconSummary sum;                                          // SUMMARY
     ReconScore score; const float* truth = nullptr;            // SCORE
     ReconEnsemble ens; long ens_count = 0;                     // ENSEMBLE
+    ReconSobol sob; int sob_params = 0; long sob_blocks = 0;   // SOBOL
+    // ENSEMBLE, SOBOL: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
+    bool by_member() const { return kind == ENSEMBLE || kind == SOBOL; }
+    long members_before() const { return kind == SOBOL ? sob_blocks * (sob_params + 2) : ens_count; }
 };
 // The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass go
 // to e->colpart, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
-// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace.
+// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor does the Sobol pass.
 static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble"};
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol"};
     static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
                                            "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
-                                           "sgv_ensemble: the ensemble pass rejected its arguments (%d)"};
+                                           "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)"};
     ScopedTimer tm(e, tag[g.kind], nullptr);
     int r = 0;
     switch (g.kind) {
@@ -912,6 +917,7 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
     case GenOut::SUMMARY: { ReconSummary o = g.sum; o.work = e->colpart; r = ew_recon_summary(e->dt, p, g.scale, g.mn, o, e->stream); break; }
     case GenOut::SCORE: { ReconScore o = g.score; o.work = e->colpart; r = ew_recon_score(e->dt, p, g.scale, g.mn, g.truth, o, e->stream); break; }
     case GenOut::ENSEMBLE: r = ew_recon_ensemble(e->dt, p, g.scale, g.mn, g.ens_count, g.ens, e->stream); break;
+    case GenOut::SOBOL: r = ew_recon_sobol(e->dt, p, g.scale, g.mn, g.sob_params, g.sob_blocks, g.sob, e->stream); break;
     }
     return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
 }
@@ -920,13 +926,13 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
 static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
-    // sgv_ensemble: the noise of member m is a function of (seed, m, site) alone -- the rows count_before + b of the streams the first
-    // call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size
-    const bool ens = gen && gen->kind == GenOut::ENSEMBLE;
+    // sgv_ensemble, sgv_sobol: the noise of member m is a function of (seed, m, site) alone -- the rows members_before + b of the streams
+    // the first call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size
+    const bool ens = gen && gen->by_member();
     uint64_t ens_draw = 0;
     for (int s = 1; s < n_st; ++s) {
         if (!e->eps_set[s]) ew_randn(e->eps[s], M * e->dec[s], e->seed, (ens ? ens_draw++ : e->draw++) * 8 + s, e->stream, (long)e->T * e->dec[s], e->shard_world, e->shard_rank,
-                                     ens ? gen->ens_count : 0);
+                                     ens ? gen->members_before() : 0);
     }
     {
         const Layer& l = e->layers[e->start_lin];
@@ -1050,7 +1056,7 @@ int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch
     return SGV_OK;
 }
 
-// what the four surrogate entry points share behind their own argument checks: decode_begin, no forward left to read (the maps of an
+// what the five surrogate entry points share behind their own argument checks: decode_begin, no forward left to read (the maps of an
 // earlier forward are overwritten from here on, and these passes leave no x_hat behind), the decoder with `gen` as its tail
 static int surrogate_pass(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const char* who, const GenOut& gen) {
     CHK(decode_begin(e, z_dev, xs_dev, batch, who));
@@ -1114,6 +1120,15 @@ int sgv_ensemble(sgv_engine* e, const float* z_dev, const float* xs_dev, int bat
     GenOut gen = {GenOut::ENSEMBLE, scale_dev, min_dev};
     gen.ens = recon_ensemble_of(*st); gen.ens_count = count_before;
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_ensemble", gen);
+}
+
+int sgv_sobol(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+              const float* min_dev, int n_params, long blocks_before, const sgv_sobol_state* st) {
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_sobol: null argument");
+    CHK(sobol_state_ok("sgv_sobol", "batch", st, n_params, blocks_before, batch));
+    GenOut gen = {GenOut::SOBOL, scale_dev, min_dev};
+    gen.sob = recon_sobol_of(*st); gen.sob_params = n_params; gen.sob_blocks = blocks_before;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_sobol", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

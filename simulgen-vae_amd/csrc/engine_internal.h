@@ -289,6 +289,25 @@ static inline ReconEnsemble recon_ensemble_of(const sgv_ensemble_state& st) {
     r.limit = st.limit; r.exceed = st.exceed;
     return r;
 }
+constexpr int SGV_SOBOL_MAX_PARAMS = 30;      // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
+static inline int sobol_state_ok(const char* who, const char* batch_name, const sgv_sobol_state* st, int n_params, long blocks_before, int batch) {
+    if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (!st->mean || !st->m2) return fail(SGV_ERR_ARG, "%s: mean and m2 are required", who);
+    if (!st->first_sq && !st->total_sq) return fail(SGV_ERR_ARG, "%s: neither first_sq nor total_sq is given", who);
+    if (((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->first_sq | (uintptr_t)st->total_sq) & 15)
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (the state arrays 16 bytes)", who);
+    if (n_params < 1 || n_params > SGV_SOBOL_MAX_PARAMS) return fail(SGV_ERR_ARG, "%s: n_params = %d is outside [1, %d]", who, n_params, SGV_SOBOL_MAX_PARAMS);
+    if (batch < 1 || batch % (n_params + 2))
+        return fail(SGV_ERR_ARG, "%s: %s = %d is not a positive multiple of n_params + 2 = %d (whole blocks A, B, AB_1 .. AB_d)", who, batch_name, batch, n_params + 2);
+    if (blocks_before < 0 || blocks_before > (1L << 23) || 2 * (blocks_before + batch / (n_params + 2)) > (1L << 24))
+        return fail(SGV_ERR_ARG, "%s: blocks_before = %ld with %d blocks: 2 (blocks_before + blocks) is outside [0, 2^24]", who, blocks_before, batch / (n_params + 2));
+    return 0;
+}
+static inline ReconSobol recon_sobol_of(const sgv_sobol_state& st) {
+    ReconSobol r;
+    r.mean = st.mean; r.m2 = st.m2; r.first_sq = st.first_sq; r.total_sq = st.total_sq;
+    return r;
+}
 
 #pragma GCC visibility push(hidden)       // shared among the engine's files only: kept out of the library's dynamic symbols
 // The release policy of the gradient buckets, on backward_impl's stack for one backward pass (engine_optim.hip): the transport (none,

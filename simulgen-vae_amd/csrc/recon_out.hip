@@ -1,6 +1,6 @@
 // The recon tails (gfx950): passes that replace the loss tail of the recon head in surrogate use -- the physical-unit field
-// (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score) and the running statistics over the
-// members of an ensemble (sgv_ensemble).  All of them stream y = the recon head's convolution output once, form the same value per
+// (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
+// members of an ensemble (sgv_ensemble) and the running sums of a Sobol sensitivity study (sgv_sobol).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -562,6 +562,46 @@ int ew_recon_score(int dtype, GNParams p, const float* scale, const float* mn, c
 constexpr int EN_MAX_B = 32;          // members per launch (the table); ew_recon_ensemble cuts a larger batch into several launches
 constexpr int EN_FLIGHT = 4;          // members whose y loads are issued before the first is used
 
+// The member table and the octet's group lookup of the kernels that take several members per launch, as functions: what
+// recon_ensemble_kernel does in line (moved into these helpers its register allocation changed: 12 -> 36 bytes of scratch per lane in
+// the bf16 kernel with all groups, so it keeps its own copy) and recon_sobol_kernel calls.  The block's table of (mean, rstd) per
+// (member, group), filled through gn_mean_rstd by all 256 threads (the caller's barrier follows) ...
+__device__ __forceinline__ void member_table_fill(const GNParams& p, float2 (*tab)[SGV_GN_MAX_GROUPS]) {
+    for (int i = threadIdx.x; i < p.B * p.G; i += 256) {
+        float m, r;
+        gn_mean_rstd(p, i / p.G, i % p.G, m, r);
+        tab[i / p.G][i % p.G] = make_float2(m, r);
+    }
+}
+// ... and the octet's group lookup: the group of each of a thread's 8 channels, one byte each; with Cg >= 8 (block-uniform) the octet
+// lies in at most two groups, lo and hi, and two table reads per member do
+struct OctetGroups { unsigned long long idx; int lo, hi; bool two; };
+__device__ __forceinline__ OctetGroups octet_groups(const GNParams& p, int c0) {
+    OctetGroups og;
+    og.idx = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) og.idx |= (unsigned long long)min((c0 + e) / p.Cg, p.G - 1) << (8 * e);
+    og.lo = (int)(og.idx & 0xff); og.hi = (int)(og.idx >> 56);
+    og.two = p.Cg >= 8;
+    return og;
+}
+__device__ __forceinline__ void octet_mean_rstd(const float2 (*tab)[SGV_GN_MAX_GROUPS], int b, const OctetGroups& og, float gm[8], float gr[8]) {
+    if (og.two) {
+        const float2 lo = tab[b][og.lo], hi = tab[b][og.hi];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const bool up = (int)((og.idx >> (8 * e)) & 0xff) != og.lo;
+            gm[e] = up ? hi.x : lo.x; gr[e] = up ? hi.y : lo.y;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float2 w = tab[b][(int)((og.idx >> (8 * e)) & 0xff)];
+            gm[e] = w.x; gr[e] = w.y;
+        }
+    }
+}
+
 // 3 waves / SIMD asked for: unasked, the kernel with all groups takes 176 VGPRs (bf16; fp32 192) and runs at 2 waves;
 // held to 168 it keeps 12 bytes per lane in scratch (fp32 68) and is faster, 0.339 against 0.365 ms in one job -- the pass is bound by memory
 // and the third wave hides more latency than the three spilled dwords cost.  Every other instantiation is below 168 anyway.
@@ -688,6 +728,167 @@ int ew_recon_ensemble(int dtype, GNParams p, const float* scale, const float* mn
                                dim3(256), 0, s, ps, q, o, cb);
         };
         recon_dispatch(launch, dtype, mo, ex, ec);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Sobol sensitivity indices (sgv_sobol): the first tail that combines the members of a launch with each other.  A launch holds whole
+// blocks of d + 2 members, in this order: A_j, B_j, AB_1_j .. AB_d_j (AB_i_j: the condition A_j with the columns of parameter i taken
+// from B_j).  Per (t, n), with x the value recon_phys_val gives for a member, all fp32, every operation rounded on its own:
+//   mean, m2       Welford over A_0, B_0, A_1, B_1, ..: A_j has k = 2 j + 1, B_j k = 2 j + 2, the arithmetic of recon_ensemble_kernel
+//   first_sq[i]    e = xB - xAB_i;  first_sq[i] = first_sq[i] + e * e      (Jansen's first-order form), ascending j
+//   total_sq[i]    e = xA - xAB_i;  total_sq[i] = total_sq[i] + e * e      (Jansen's total form), ascending j
+// j counts from blocks_before; every update is sequential in j and the state is stored as it is held, so any cut of the same blocks
+// into launches gives the same bits.  With blocks_before == 0 the state is not read.
+// Geometry, ownership, the member table and the group lookup are recon_ensemble_kernel's: a thread owns its (t, octet) for all members,
+// no reduction across threads, no atomics, no workspace.  Loop order: the A and B values of the launch's blocks stay in registers
+// (16 floats per block); then parameter i's two state arrays are streamed through once per launch -- load, update over the blocks,
+// store -- while the y rows of parameter i + 1 are already on their way.
+// ------------------------------------------------------------------------------------------
+constexpr int SB_MAX_D = EN_MAX_B - 2;          // parameters (column groups): one block must fit the member table
+// blocks per launch: 16 VGPRs of A / B values each, and a row in flight for this parameter and one for the next (4 / 8 VGPRs each).  Four
+// blocks keep the bf16 kernel out of scratch (a batch of 16 is then one launch for every d); the fp32 kernel kept 72 bytes per lane
+// in scratch with four and none with three
+template <typename T> constexpr int sb_max_blk() { return sizeof(T) == 2 ? 4 : 3; }
+
+// 2 waves / SIMD asked for; the compiler's numbers (gfx950) stand there: no instantiation uses scratch.
+template <typename T, bool FIRST, bool TOTAL>
+__global__ __launch_bounds__(256, 2) void recon_sobol_kernel(const GNParams p, const ReconPhys q, const ReconSobol o, const int d, const int nbl,
+                                                             const int blocks_before) {
+    __shared__ float2 tab[EN_MAX_B][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of member b; p.B = nbl * (d + 2) <= EN_MAX_B
+    constexpr int NB = sb_max_blk<T>();
+    __shared__ float rk[2 * NB];                         // 1 / k of A_j (2 j) and B_j (2 j + 1), k = 2 (blocks_before + j) + 1, + 2
+    member_table_fill(p, tab);
+    if ((int)threadIdx.x < 2 * nbl) rk[threadIdx.x] = 1.0f / (float)(2 * blocks_before + (int)threadIdx.x + 1);
+    __syncthreads();
+    const GNCtx c = gn_ctx(p);          // blockIdx.z == 0; c.b is not a member here
+    if (!c.col_ok) return;              // no barrier below: lanes past C touch nothing
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const OctetGroups og = octet_groups(p, c.c0);
+    const T* y = reinterpret_cast<const T*>(p.y);
+    const bool fresh = blocks_before == 0;
+    const int S = d + 2;
+    const long TC = (long)p.T * p.C;
+    // x[8] of member b from its loaded row: the value the output pass would store
+    auto value = [&](const Raw8<T>& r, int b, float x[8]) {
+        float v[8], gm[8], gr[8];
+        raw_unpack(r, v);
+        octet_mean_rstd(tab, b, og, gm, gr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
+    };
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += c.RL) {
+        const long at = (long)t * p.C + c.c0;
+        // row t of member j * S + m; past the launch's last block: that block's row again, loaded and not used
+        auto row = [&](int j, int m) { return y + ((long)(min(j, nbl - 1) * S + m) * p.T + t) * p.ldy + c.c0; };
+        float xa[NB][8], xb[NB][8];
+        Raw8<T> cur[NB];          // the rows of AB_i_j, parameter i
+        {
+            float mean[8], m2[8];
+            if (fresh) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { mean[e] = 0.f; m2[e] = 0.f; }
+            } else { load8(o.mean + at, mean); load8(o.m2 + at, m2); }
+#pragma unroll
+            for (int j0 = 0; j0 < NB; j0 += 2) {          // two blocks per round: EN_FLIGHT rows, loads first
+                if (j0 >= nbl) break;
+                Raw8<T> ra[2], rb[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) { raw_load(row(j0 + u, 0), ra[u]); raw_load(row(j0 + u, 1), rb[u]); }
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int j = j0 + u;
+                    if (j >= NB || j >= nbl) break;
+                    value(ra[u], j * S, xa[j]);
+                    value(rb[u], j * S + 1, xb[j]);
+                    const float ra_k = rk[2 * j], rb_k = rk[2 * j + 1];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        // Welford, A_j then B_j; no fused multiply-add anywhere (see recon_ensemble_kernel)
+#pragma clang fp contract(off)
+                        float dl = xa[j][e] - mean[e];
+                        mean[e] = mean[e] + dl * ra_k;
+                        m2[e] = m2[e] + dl * (xa[j][e] - mean[e]);
+                        dl = xb[j][e] - mean[e];
+                        mean[e] = mean[e] + dl * rb_k;
+                        m2[e] = m2[e] + dl * (xb[j][e] - mean[e]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NB; ++j) raw_load(row(j, 2), cur[j]);          // parameter 0, on its way while the moments go out
+            store8(o.mean + at, mean); store8(o.m2 + at, m2);
+        }
+        for (int i = 0; i < d; ++i) {
+            const long ai = (long)i * TC + at;
+            float fs[8], ts[8];
+            if (fresh) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { fs[e] = 0.f; ts[e] = 0.f; }
+            } else {
+                if constexpr (FIRST) load8(o.first_sq + ai, fs);
+                if constexpr (TOTAL) load8(o.total_sq + ai, ts);
+            }
+            Raw8<T> nxt[NB];          // parameter i + 1 (after the last one: its rows again, loaded and not used)
+            const int in = min(i + 1, d - 1);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) raw_load(row(j, 2 + in), nxt[j]);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                if (j >= nbl) break;
+                float x[8];
+                value(cur[j], j * S + 2 + i, x);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // the difference, its square and the sum round one after the other
+#pragma clang fp contract(off)
+                    if constexpr (FIRST) { const float df = xb[j][e] - x[e]; fs[e] = fs[e] + df * df; }
+                    if constexpr (TOTAL) { const float dt = xa[j][e] - x[e]; ts[e] = ts[e] + dt * dt; }
+                }
+            }
+            if constexpr (FIRST) store8(o.first_sq + ai, fs);
+            if constexpr (TOTAL) store8(o.total_sq + ai, ts);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) cur[j] = nxt[j];
+        }
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only), p.B = whole blocks of n_params + 2 members; o: ReconSobol (sgv_ew.h), mean and m2
+// and at least one of first_sq, total_sq; blocks_before blocks are already in the state (0: the state is not read).  More blocks than a
+// launch holds (sb_max_blk, and EN_MAX_B members) go out as several launches cut at block boundaries with blocks_before advanced,
+// which is bitwise the same.  Non-zero (nothing launched): -1 null input, -2 neither first_sq nor total_sq, or mean / m2 missing,
+// -3 bad shape, n_params outside [1, SB_MAX_D] or B no multiple of n_params + 2, -4 y or a state array not 16-byte aligned,
+// -5 blocks_before < 0 or 2 (blocks_before + blocks) > 2^24 (beyond that (float)k is not exact)
+int ew_recon_sobol(int dtype, GNParams p, const float* scale, const float* mn, int n_params, long blocks_before, const ReconSobol& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if ((!o.first_sq && !o.total_sq) || !o.mean || !o.m2) return -2;
+    if (n_params < 1 || n_params > SB_MAX_D || p.B % (n_params + 2)) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.mean | (uintptr_t)o.m2 | (uintptr_t)o.first_sq | (uintptr_t)o.total_sq) & 15) return -4;
+    const int S = n_params + 2, blocks = p.B / S;
+    if (blocks_before < 0 || blocks_before > (1L << 23) || 2 * (blocks_before + blocks) > (1L << 24)) return -5;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const RSGeom g = rs_geom(p.C);
+    const int RL = 256 / g.CV;
+    const int rowchunks = std::max(1, std::min(cdiv_i(p.T, RL), cdiv_i(2048, g.colblocks)));      // as ew_recon_ensemble
+    const dim3 grid(g.colblocks, rowchunks, 1);
+    const int per = std::min(dtype == 1 ? sb_max_blk<bf16_t>() : sb_max_blk<float>(), EN_MAX_B / S);          // >= 1: S <= EN_MAX_B
+    const size_t esz = dtype == 1 ? 2 : 4;
+    for (int j0 = 0; j0 < blocks; j0 += per) {
+        GNParams ps = p;
+        const int nbl = std::min(per, blocks - j0);
+        ps.B = nbl * S;
+        ps.y = (const char*)p.y + (size_t)j0 * S * p.T * p.ldy * esz;
+        ps.sums = p.sums + (size_t)j0 * S * p.G * 2;
+        const int bb = (int)blocks_before + j0;
+        auto launch = [&](auto el, auto fi_c, auto to_c) {
+            hipLaunchKernelGGL((recon_sobol_kernel<typename decltype(el)::type, decltype(fi_c)::value, decltype(to_c)::value>), grid, dim3(256), 0, s,
+                               ps, q, o, n_params, nbl, bb);
+        };
+        recon_dispatch(launch, dtype, o.first_sq != nullptr, o.total_sq != nullptr);
     }
     return 0;
 }

@@ -150,6 +150,19 @@ struct ReconEnsemble {
     const float* limit = nullptr; int* exceed = nullptr;
 };
 int ew_recon_ensemble(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconEnsemble& o, hipStream_t s);
+// recon head -> the running sums of a Sobol sensitivity study per (t, channel), the field never stored.  The batch holds whole blocks
+// of n_params + 2 members, A_j, B_j, AB_1_j .. AB_d_j (AB_i_j: A_j with the columns of parameter i from B_j); x is the value
+// ew_recon_physical would store, everything fp32 with one rounding per operation, j ascending from blocks_before:
+//   mean, m2      [T][C]     Welford over A_0, B_0, A_1, B_1, .. (k = 2 j + 1 for A_j, 2 j + 2 for B_j), as ReconEnsemble's moments
+//   first_sq      [d][T][C]  first_sq[i] += (xB - xAB_i)^2    (Jansen's first-order form: S_i = 1 - first_sq[i] / (2 n var))
+//   total_sq      [d][T][C]  total_sq[i] += (xA - xAB_i)^2    (Jansen's total form: ST_i = total_sq[i] / (2 n var))
+// mean and m2 are required, and at least one of first_sq, total_sq; every array dense and 16-byte aligned.  With blocks_before == 0
+// the state is not read.  Any cut of the same blocks into launches gives the same bits.
+struct ReconSobol {
+    float* mean = nullptr; float* m2 = nullptr;
+    float* first_sq = nullptr; float* total_sq = nullptr;
+};
+int ew_recon_sobol(int dtype, GNParams p, const float* scale, const float* mn, int n_params, long blocks_before, const ReconSobol& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

@@ -331,6 +331,17 @@ int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, co
         return ew_recon_ensemble(dtype, q, scale, min, count_before, recon_ensemble_of(*st), s);
     });
 }
+int sgv_test_recon_sobol(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                         const float* scale, const float* min, int n_params, long blocks_before, const sgv_sobol_state* st, int B,
+                         int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_sobol";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(sobol_state_ok(me, "B", st, n_params, blocks_before, B));
+    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
+        return ew_recon_sobol(dtype, q, scale, min, n_params, blocks_before, recon_sobol_of(*st), s);
+    });
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -73,11 +73,19 @@ class EnsembleState(C.Structure):
                 ("arg_min", C.c_void_p), ("limit", C.c_void_p), ("exceed", C.c_void_p)]
 
 
+class SobolState(C.Structure):
+    """sgv_sobol_state (include/sgvae.h): the running sums of sgv_sobol, device pointers; mean and m2 always, first_sq and / or total_sq"""
+    _fields_ = [("mean", C.c_void_p), ("m2", C.c_void_p), ("first_sq", C.c_void_p), ("total_sq", C.c_void_p)]
+
+
 MAX_PROBES = 4096
 SUMMARY_PARTS = ("node", "frame", "probes")      # `want` of Engine.summarize
 SCORE_PARTS = ("node", "frame")                  # `want` of Engine.score
 ENSEMBLE_GROUPS = {"moments": ("mean", "m2"), "extrema": ("max", "min", "arg_max", "arg_min"), "exceed": ("limit", "exceed")}      # the state of Engine.ensemble
 ENSEMBLE_MAX_COUNT = 1 << 24                     # members of one ensemble: beyond that float(k) is not exact
+SOBOL_FIELDS = ("mean", "m2", "first_sq", "total_sq")      # the state of Engine.sobol: mean, m2 [T, N]; first_sq, total_sq [n_params, T, N]
+SOBOL_MAX_PARAMS = 30                            # a block of n_params + 2 members fits the kernel's member table of 32
+SOBOL_MAX_BLOCKS = 1 << 23                       # base samples of one study: 2 per block enter the moments, and float(k) is exact to 2^24
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")      # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -129,6 +137,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_summarize.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.POINTER(SummaryOut)]
     lib.sgv_score.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, C.POINTER(ScoreOut)]
     lib.sgv_ensemble.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.c_long, C.POINTER(EnsembleState)]
+    lib.sgv_sobol.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, C.c_long, C.POINTER(SobolState)]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -194,6 +203,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_summary.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, C.POINTER(SummaryOut), vp, i32, i32, i32, i32, vp]
     lib.sgv_test_recon_score.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, C.POINTER(ScoreOut), i32, i32, i32, vp]
     lib.sgv_test_recon_ensemble.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, lg, C.POINTER(EnsembleState), i32, i32, i32, vp]
+    lib.sgv_test_recon_sobol.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, lg, C.POINTER(SobolState), i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -467,7 +477,7 @@ class Engine:
                 raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
 
     def _surrogate(self, entry, z, xs, scale, min, fix, tail):
-        """the call generate, summarize, score and ensemble share: the checks on z, xs, scale and min, then tail(B) -> (the entry
+        """the call generate, summarize, score, ensemble and sobol share: the checks on z, xs, scale and min, then tail(B) -> (the entry
         point's trailing arguments, what to return), which checks whatever depends on the batch, then the C call"""
         B, z, xs_t = self._latents(z, xs)
         self._scaler(scale, min)
@@ -593,6 +603,44 @@ class Engine:
                 raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
             return (cb, C.byref(EnsembleState(**{k: v.data_ptr() for k, v in state.items() if v is not None}))), state
         return self._surrogate("sgv_ensemble", z, xs, scale, min, fix, tail)
+
+    def sobol(self, z, xs, scale, min, state, n_params, blocks_before, fix=True):
+        """Merges this batch into the running sums `state` of a Sobol sensitivity study, per (time step, node), by the recon head's
+        last pass itself; the fields are never stored.  Same inputs and checks as summarize().  The batch holds whole blocks of
+        n_params + 2 members in this order: A_j, B_j, AB_1_j .. AB_d_j (AB_i_j: base sample A_j with the inputs of parameter i
+        taken from B_j); block j of the call is base sample blocks_before + j.  state: a dict of contiguous fp32 CUDA tensors,
+        "mean" and "m2" [T, N] (Welford over the A and B members: variance = m2 / (2 n)), and "first_sq" and / or "total_sq"
+        [n_params, T, N] (sums of (xB - xAB_i)^2 and of (xA - xAB_i)^2: Jansen's estimators).  With blocks_before == 0 the state is
+        not read.  The tensors are updated in place and `state` is returned.  Any cut of the same blocks into calls gives the same
+        bits, the decoder's noise included: unless set with set_eps() it follows the member's index
+        blocks_before * (n_params + 2) + b, as in ensemble(), and the draw position does not move.  Nothing synchronises;
+        afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        d = int(n_params)
+        if d < 1 or d > SOBOL_MAX_PARAMS:
+            raise ValueError(f"n_params = {d} is outside [1, {SOBOL_MAX_PARAMS}]")
+        if not isinstance(state, dict) or not state:
+            raise ValueError("state must be a dict with the tensors 'mean', 'm2' and at least one of 'first_sq', 'total_sq'")
+        for k in state:
+            if k not in SOBOL_FIELDS:
+                raise ValueError(f"state[{k!r}] is not a tensor of the Sobol state ({SOBOL_FIELDS})")
+        have = [k for k in SOBOL_FIELDS if state.get(k) is not None]
+        if "mean" not in have or "m2" not in have or len(have) < 3:
+            raise ValueError(f"state needs 'mean', 'm2' and at least one of 'first_sq', 'total_sq', got only {have}")
+        for k in have:
+            v, shape = state[k], (T, N) if k in ("mean", "m2") else (d, T, N)
+            if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and tuple(v.shape) == shape):
+                raise ValueError(f"state[{k!r}] must be a contiguous {t.float32} CUDA tensor of shape {shape}")
+
+        def tail(B):
+            bb = int(blocks_before)
+            if B % (d + 2):
+                raise ValueError(f"a batch of {B} members is not whole blocks of n_params + 2 = {d + 2}")
+            if bb < 0 or bb + B // (d + 2) > SOBOL_MAX_BLOCKS:
+                raise ValueError(f"blocks_before = {bb} with {B // (d + 2)} blocks is outside [0, {SOBOL_MAX_BLOCKS}]")
+            return (d, bb, C.byref(SobolState(**{k: state[k].data_ptr() for k in have}))), state
+        return self._surrogate("sgv_sobol", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

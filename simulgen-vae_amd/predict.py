@@ -22,6 +22,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     ens = s.ensemble(conditions.repeat(1000, 1), limit=250.0, mode="random")   # statistics ACROSS draws per (time step, node): mean,
                                                    # ens.std(), envelope, which draw was worst, how often the limit is exceeded
                                                    # (DESIGN.md section 19); [T, N] running state instead of 1000 fields
+    A, B = sobol_design(lo, hi, n=1000)            # two independent sample matrices [n, F] over the parameter ranges
+    sens = s.sobol(A, B)                           # which input drives the response, where and when: sens.first_order() and
+                                                   # sens.total_order() [F, T, N], Sobol indices by Jansen's estimators (DESIGN.md
+                                                   # section 20); (2 + 2 F) running arrays [T, N] instead of n (F + 2) fields
 """
 from __future__ import annotations
 
@@ -181,6 +185,124 @@ class EnsembleResult:
         if self.count < 1:
             raise ValueError("exceed_fraction: the ensemble is empty")
         return self._on_stream(lambda: self.exceed.float() / float(self.count))
+
+
+SOBOL_MAX_PARAMS = 30          # SGV_SOBOL_MAX_PARAMS of the engine: a block of d + 2 members fits the kernel's member table
+SOBOL_MAX_COUNT = 1 << 23      # base samples of one study: two values per sample enter the moments, and float(k) is exact to 2^24
+
+
+def sobol_groups(groups, F):
+    """The parameters of Surrogate.sobol as a list of d int64 index vectors into the F columns of a condition.  None: one parameter
+    per column (d = F).  Otherwise a sequence of d non-empty 1-D integer index lists, each entry in [0, F); a column may appear in
+    several groups (overlapping groups are allowed) and the order is kept.  ValueError naming the first bad group or index
+    otherwise, and for d > SOBOL_MAX_PARAMS.  numpy only."""
+    F = int(F)
+    if groups is None:
+        groups = [[c] for c in range(F)]
+    try:
+        groups = list(groups)
+    except TypeError:
+        raise ValueError(f"groups: a sequence of index lists is required, not {type(groups).__name__}") from None
+    if len(groups) < 1:
+        raise ValueError("groups: at least one group is required")
+    if len(groups) > SOBOL_MAX_PARAMS:
+        raise ValueError(f"groups: {len(groups)} groups, at most {SOBOL_MAX_PARAMS} parameters are supported")
+    res = []
+    for i, g in enumerate(groups):
+        a = np.asarray(g)
+        if a.ndim != 1 or a.size < 1:
+            raise ValueError(f"groups[{i}]: a non-empty 1-D list of column indices is required, got shape {a.shape}")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"groups[{i}]: an integer dtype is required, not {a.dtype}")
+        bad = np.flatnonzero((a < 0) | (a >= F))
+        if bad.size:
+            raise ValueError(f"groups[{i}][{int(bad[0])}] = {int(a[bad[0]])} is outside [0, {F})")
+        res.append(a.astype(np.int64))
+    return res
+
+
+def sobol_design(lo, hi, n, seed=0):
+    """Two independent sample matrices A, B [n, F] float32 for Surrogate.sobol, uniform in [lo[c], hi[c]] per column, from
+    np.random.default_rng(seed) (A is drawn first).  ValueError for bounds of different lengths or not 1-D, a bound that is not
+    finite (the first one is named), hi < lo, or n < 1.  numpy only."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    if lo.ndim != 1 or hi.ndim != 1 or lo.size != hi.size or lo.size < 1:
+        raise ValueError(f"sobol_design: lo and hi must be 1-D and of one length >= 1, got shapes {lo.shape} and {hi.shape}")
+    for name, v in (("lo", lo), ("hi", hi)):
+        bad = np.flatnonzero(~np.isfinite(v))
+        if bad.size:
+            raise ValueError(f"sobol_design: {name}[{int(bad[0])}] = {float(v[bad[0]])!r} is not finite")
+    bad = np.flatnonzero(hi < lo)
+    if bad.size:
+        raise ValueError(f"sobol_design: hi[{int(bad[0])}] = {float(hi[bad[0]])!r} is below lo[{int(bad[0])}] = {float(lo[bad[0]])!r}")
+    if int(n) != n or int(n) < 1:
+        raise ValueError(f"sobol_design: n = {n!r}, at least one base sample is required")
+    rng = np.random.default_rng(seed)
+    A, B = (lo + (hi - lo) * rng.random((int(n), lo.size)) for _ in range(2))
+    return A.astype(np.float32), B.astype(np.float32)
+
+
+def sobol_members(A, B, groups):
+    """The member matrix of a Sobol study, [n (d + 2), F] float32: base sample j yields the block A_j, B_j, AB_1_j .. AB_d_j, where
+    AB_i_j is A_j with the columns of groups[i] (sobol_groups) taken from B_j.  What Surrogate.sobol builds on the device batch by
+    batch; predict() on this matrix gives the fields the study reduces.  numpy only."""
+    A, B = np.asarray(A, np.float32), np.asarray(B, np.float32)
+    if A.ndim != 2 or A.shape != B.shape:
+        raise ValueError(f"A and B must be [n, F] and of one shape, got {A.shape} and {B.shape}")
+    groups = sobol_groups(groups, A.shape[1])
+    M = np.repeat(A[:, None, :], len(groups) + 2, axis=1)
+    M[:, 1] = B
+    for i, g in enumerate(groups):
+        M[:, 2 + i, g] = B[:, g]
+    return np.ascontiguousarray(M.reshape(-1, A.shape[1]))
+
+
+class SobolResult:
+    """Surrogate.sobol's result: the running sums of a Sobol sensitivity study over `count` base samples and `n_params` parameters,
+    device tensors that ARE the running state (pass the result back as `into=` to go on accumulating).  mean, m2 fp32 [T, N]:
+    Welford over the 2 count values of the A and B members; first_sq, total_sq fp32 [n_params, T, N]: sum_j (f(B_j) - f(AB_i_j))^2
+    and sum_j (f(A_j) - f(AB_i_j))^2 (Jansen's estimators); one not asked for is None."""
+    FIELDS = ("count", "n_params", "mean", "m2", "first_sq", "total_sq")
+    PARTS = {"first": "first_sq", "total": "total_sq"}
+
+    def __init__(self, stream=None, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+        self._stream = stream          # the engine stream (a torch stream): var / first_order / total_order run there
+
+    _on_stream = EnsembleResult._on_stream
+
+    def want(self):
+        """the parts this result holds, in the order of PARTS"""
+        return tuple(w for w, k in self.PARTS.items() if getattr(self, k) is not None)
+
+    def state(self):
+        """the tensors of the running state by their names in Engine.sobol"""
+        return {k: getattr(self, k) for k in ("mean", "m2", "first_sq", "total_sq") if getattr(self, k) is not None}
+
+    def var(self, ddof=0):
+        """m2 / (2 count - ddof) [T, N] fp32: the variance of the response over the A and B samples"""
+        if 2 * self.count - ddof <= 0:
+            raise ValueError(f"var: 2 count - ddof = {2 * self.count} - {ddof} is not positive")
+        return self._on_stream(lambda: self.m2 / float(2 * self.count - ddof))
+
+    def first_order(self):
+        """S_i = 1 - first_sq[i] / (2 count var) [n_params, T, N] fp32: the share of the variance parameter i explains on its own.
+        Where the variance is 0 the result is inf or nan, as the division says."""
+        if self.first_sq is None:
+            raise ValueError("first_order: 'first' was not asked for")
+        if self.count < 1:
+            raise ValueError("first_order: the study is empty")
+        return self._on_stream(lambda: 1.0 - self.first_sq / (float(2 * self.count) * (self.m2 / float(2 * self.count))))
+
+    def total_order(self):
+        """ST_i = total_sq[i] / (2 count var) [n_params, T, N] fp32: the share of the variance that involves parameter i at all
+        (its own effect and every interaction).  Where the variance is 0 the result is inf or nan, as the division says."""
+        if self.total_sq is None:
+            raise ValueError("total_order: 'total' was not asked for")
+        if self.count < 1:
+            raise ValueError("total_order: the study is empty")
+        return self._on_stream(lambda: self.total_sq / (float(2 * self.count) * (self.m2 / float(2 * self.count))))
 
 
 class SweepResult:
@@ -464,6 +586,83 @@ class Surrogate:
         if t.cuda.current_stream() != self._stream:
             t.cuda.current_stream().wait_stream(self._stream)
         return EnsembleResult(stream=self._stream, count=count + P, **{k: state.get(k) for k in EnsembleResult.FIELDS if k != "count"})
+
+    def sobol(self, A, B, groups=None, want=("first", "total"), into=None):
+        """Variance-based global sensitivity of the response to its inputs per (time step, node), without the fields: which
+        parameter drives the field, where on the mesh and when -> a SobolResult of device tensors.  A, B [n, F]: two independent
+        sample matrices of conditions (sobol_design; host arrays or CUDA tensors, preprocessed as the conditioner's training set
+        holds them).  groups: the d parameters as lists of column indices (sobol_groups; None: every column is a parameter).
+        Base sample j is evaluated at A_j, B_j and AB_1_j .. AB_d_j (A_j with the columns of parameter i from B_j): n (d + 2) decoder
+        passes, whose last pass keeps only running sums -- the result tensors themselves, updated in place batch after batch.
+        want: "first" (result.first_order(): S_i, the share of the variance of the response that parameter i explains alone;
+        sum_i S_i <= 1, the rest is interaction) and / or "total" (result.total_order(): ST_i >= S_i, the share that involves
+        parameter i at all; ST_i = 0 means the parameter can be fixed).  Both are Jansen's estimators, sums of squared differences:
+        non-negative, no centring, fp32-safe; their sampling error falls as 1 / sqrt(n), and an S_i of a weak parameter can come
+        out slightly negative.  There is no `mode`: a sensitivity study needs a deterministic response, so the decoder always runs
+        in the reference's "fix" mode, whose latent noise is scaled by 1e-10 -- numerically negligible but not bit-zero: it follows
+        the member's index in the study (as in ensemble()), so the same seed gives the same bits at any batch size and for any cut
+        into `into=` calls.  A batch takes self.batch // (d + 2) whole blocks.  into: an earlier result to go on accumulating into
+        (same d, same want; its tensors are updated and returned in a new result with the larger count): equal to one call on
+        the concatenated samples, bit for bit.  At most 2^23 base samples.  The single input-range decision of predict() is taken
+        over A and B together; no host wait between batches."""
+        t = self.torch
+        A, n, _, remap_a = self._args(A, "TN", "fix")
+        B, nb_, _, remap_b = self._args(B, "TN", "fix")
+        if tuple(A.shape) != tuple(B.shape):
+            raise ValueError(f"A and B must be of one shape [n, F], got {tuple(A.shape)} and {tuple(B.shape)}")
+        remap = None if remap_a is None else (remap_a or remap_b)
+        F = int(A.shape[1])
+        groups = sobol_groups(groups, F)
+        d = len(groups)
+        want = tuple(want)
+        if any(w not in SobolResult.PARTS for w in want):
+            raise ValueError(f"want must name parts of {tuple(SobolResult.PARTS)}, not {want!r}")
+        want = tuple(w for w in SobolResult.PARTS if w in want)
+        if not want:
+            raise ValueError(f"want must name at least one of {tuple(SobolResult.PARTS)}")
+        per = self.batch // (d + 2)
+        if per < 1:
+            raise ValueError(f"a block of d + 2 = {d + 2} members does not fit a batch of {self.batch}: build the Surrogate with batch >= {d + 2}")
+        shapes = {"mean": (self.T, self.N), "m2": (self.T, self.N), "first_sq": (d, self.T, self.N), "total_sq": (d, self.T, self.N)}
+        if into is not None:
+            if not isinstance(into, SobolResult):
+                raise ValueError(f"into must be a SobolResult, not {type(into).__name__}")
+            if int(into.n_params) != d:
+                raise ValueError(f"into holds {into.n_params} parameters, this call has {d}")
+            if into.want() != want:
+                raise ValueError(f"into holds the parts {into.want()}, this call asks for {want}")
+            state = into.state()
+            for k in ("mean", "m2") + tuple(SobolResult.PARTS[w] for w in want):
+                v = state.get(k)
+                if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and tuple(v.shape) == shapes[k]):
+                    raise ValueError(f"into.{k} must be a contiguous {t.float32} CUDA tensor of shape {shapes[k]}")
+            count = int(into.count)
+            if count < 0:
+                raise ValueError(f"into.count = {count} is negative")
+        else:
+            state, count = {}, 0
+        if count + n > SOBOL_MAX_COUNT:
+            raise ValueError(f"{count} + {n} base samples: a study holds at most 2^23")
+        take = np.zeros((d + 2, F), bool)          # which columns of a member come from B
+        take[1] = True
+        for i, g in enumerate(groups):
+            take[2 + i, g] = True
+        self._stream.wait_stream(t.cuda.current_stream())
+        with t.cuda.stream(self._stream):
+            if into is None:
+                for k in ("mean", "m2") + tuple(SobolResult.PARTS[w] for w in want):
+                    state[k] = (t.zeros if n == 0 else t.empty)(shapes[k], dtype=t.float32, device="cuda")
+            take = t.from_numpy(take).cuda()[None]
+            for lo in range(0, n, per):
+                hi = min(n, lo + per)
+                a, b = self._batch(A, lo, hi)[:, None, :], self._batch(B, lo, hi)[:, None, :]
+                members = t.where(take, b, a).reshape((hi - lo) * (d + 2), F)          # A_j, B_j, AB_1_j .. AB_d_j per base sample
+                lat, xs = self._latents(members, remap)
+                self.eng.sobol(lat, xs, self.data_scale, self.data_min, state, d, count + lo, fix=True)
+        if t.cuda.current_stream() != self._stream:
+            t.cuda.current_stream().wait_stream(self._stream)
+        return SobolResult(stream=self._stream, count=count + n, n_params=d, mean=state["mean"], m2=state["m2"],
+                           first_sq=state.get("first_sq"), total_sq=state.get("total_sq"))
 
     def predict_to_host(self, conditions, out=None, layout="TN", mode="fix"):
         """The same result in pinned host memory: two device batch buffers alternate, each batch's device-to-host copy runs on the

@@ -221,6 +221,13 @@ def load_library(path: str = LIB_PATH):
     return lib
 
 
+def is_tensor_of(v, dtype, shape=None, device="cuda"):
+    """whether v is a contiguous tensor of `dtype` on `device` and, unless None, of `shape`: the form in which a tensor crosses the C ABI"""
+    import torch
+    return (torch.is_tensor(v) and v.device.type == device and v.dtype == dtype and v.is_contiguous()
+            and (shape is None or tuple(v.shape) == tuple(shape)))
+
+
 def _check(lib, rc: int, what: str):
     if rc != 0:
         raise SgvError(f"{what} failed ({rc}): {lib.sgv_last_error().decode()}")
@@ -370,7 +377,7 @@ class Engine:
     def _snapshot_buffer(self, buf, what, pinned):
         t = self.torch
         n = self.snapshot_floats()
-        if not t.is_tensor(buf) or buf.device.type != "cpu" or buf.dtype != t.float32 or not buf.is_contiguous():
+        if not is_tensor_of(buf, t.float32, device="cpu"):
             raise ValueError(f"{what}: the buffer must be a contiguous torch.float32 CPU tensor")
         if buf.numel() != n:
             raise ValueError(f"{what}: the buffer holds {buf.numel()} floats, the engine's state has {n}")
@@ -455,7 +462,7 @@ class Engine:
             shape = (B, T, N) if layout == "TN" else (B, N, T)
             if out is None:
                 out = t.empty(shape, dtype=t.float32, device="cuda")
-            elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            elif not is_tensor_of(out, t.float32, shape):
                 raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
             return (LAYOUTS[layout], C.c_void_p(out.data_ptr())), out
         return self._surrogate("sgv_generate", z, xs, scale, min, fix, tail)
@@ -473,7 +480,7 @@ class Engine:
     def _scaler(self, scale, min):
         t, N = self.torch, self.cfg.num_node
         for name, v in (("scale", scale), ("min", min)):
-            if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == N):
+            if not (is_tensor_of(v, t.float32) and v.numel() == N):
                 raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
 
     def _surrogate(self, entry, z, xs, scale, min, fix, tail):
@@ -495,10 +502,25 @@ class Engine:
             v = None if out is None else out.get(name)
             if v is None:
                 v = t.empty(shape, dtype=dt, device="cuda")
-            elif not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
+            elif not is_tensor_of(v, dt, shape):
                 raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
             res[name] = v
         return res
+
+    def _state(self, state, spec, what, needs):
+        """the names, in the order of spec = {name: (shape, dtype)}, of the tensors the running state `state` of ensemble or sobol
+        holds: a non-empty dict (ValueError(needs) otherwise) of names of `spec` with tensors as `spec` has them, or None"""
+        if not isinstance(state, dict) or not state:
+            raise ValueError(needs)
+        for k in state:
+            if k not in spec:
+                raise ValueError(f"state[{k!r}] is not a tensor of the {what}")
+        have = [k for k in spec if state.get(k) is not None]
+        for k in have:
+            shape, dt = spec[k]
+            if not is_tensor_of(state[k], dt, shape):
+                raise ValueError(f"state[{k!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
+        return have
 
     def set_probes(self, nodes):
         """The probe nodes of summarize(): a 1-D integer sequence of at most MAX_PROBES node indices in [0, num_node); an empty
@@ -556,7 +578,7 @@ class Engine:
         N, T = self.cfg.num_node, self.cfg.num_time
 
         def tail(B):
-            if not (t.is_tensor(truth) and truth.is_cuda and truth.dtype == t.float32 and truth.is_contiguous() and tuple(truth.shape) == (B, T, N)):
+            if not is_tensor_of(truth, t.float32, (B, T, N)):
                 raise ValueError(f"truth must be a contiguous float32 CUDA tensor of shape {(B, T, N)}")
             shapes = {}
             if "node" in want:
@@ -579,23 +601,14 @@ class Engine:
         draw position does not move.  Nothing synchronises; afterwards xhat() raises, as after generate()."""
         t = self.torch
         N, T = self.cfg.num_node, self.cfg.num_time
-        if not isinstance(state, dict) or not state:
-            raise ValueError(f"state must be a dict with the tensors of at least one of the groups {ENSEMBLE_GROUPS}")
-        known = {k: g for g, names in ENSEMBLE_GROUPS.items() for k in names}
-        for k in state:
-            if k not in known:
-                raise ValueError(f"state[{k!r}] is not a tensor of the ensemble state ({sorted(known)})")
+        spec = {k: ((N,) if k == "limit" else (T, N), t.int32 if k in ("arg_max", "arg_min", "exceed") else t.float32)
+                for names in ENSEMBLE_GROUPS.values() for k in names}
+        held = self._state(state, spec, f"ensemble state ({sorted(spec)})",
+                           f"state must be a dict with the tensors of at least one of the groups {ENSEMBLE_GROUPS}")
         for g, names in ENSEMBLE_GROUPS.items():
-            have = [k for k in names if state.get(k) is not None]
+            have = [k for k in names if k in held]
             if have and len(have) != len(names):
                 raise ValueError(f"state: group {g!r} needs all of {names}, got only {have}")
-        for k, v in state.items():
-            if v is None:
-                continue
-            dt = t.int32 if k in ("arg_max", "arg_min", "exceed") else t.float32
-            shape = (N,) if k == "limit" else (T, N)
-            if not (t.is_tensor(v) and v.is_cuda and v.dtype == dt and v.is_contiguous() and tuple(v.shape) == shape):
-                raise ValueError(f"state[{k!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
 
         def tail(B):
             cb = int(count_before)
@@ -620,18 +633,11 @@ class Engine:
         d = int(n_params)
         if d < 1 or d > SOBOL_MAX_PARAMS:
             raise ValueError(f"n_params = {d} is outside [1, {SOBOL_MAX_PARAMS}]")
-        if not isinstance(state, dict) or not state:
-            raise ValueError("state must be a dict with the tensors 'mean', 'm2' and at least one of 'first_sq', 'total_sq'")
-        for k in state:
-            if k not in SOBOL_FIELDS:
-                raise ValueError(f"state[{k!r}] is not a tensor of the Sobol state ({SOBOL_FIELDS})")
-        have = [k for k in SOBOL_FIELDS if state.get(k) is not None]
+        spec = {k: ((T, N) if k in ("mean", "m2") else (d, T, N), t.float32) for k in SOBOL_FIELDS}
+        have = self._state(state, spec, f"Sobol state ({SOBOL_FIELDS})",
+                           "state must be a dict with the tensors 'mean', 'm2' and at least one of 'first_sq', 'total_sq'")
         if "mean" not in have or "m2" not in have or len(have) < 3:
             raise ValueError(f"state needs 'mean', 'm2' and at least one of 'first_sq', 'total_sq', got only {have}")
-        for k in have:
-            v, shape = state[k], (T, N) if k in ("mean", "m2") else (d, T, N)
-            if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and tuple(v.shape) == shape):
-                raise ValueError(f"state[{k!r}] must be a contiguous {t.float32} CUDA tensor of shape {shape}")
 
         def tail(B):
             bb = int(blocks_before)

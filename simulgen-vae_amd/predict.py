@@ -29,13 +29,15 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
 """
 from __future__ import annotations
 
+import contextlib
 import inspect
 import os
 import pickle
 
 import numpy as np
 
-from .engine import LAYOUTS
+from .engine import ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_PROBES, SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of
+from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
 FILES = {"vae": "SimulGen-VAE", "conditioner": "LatentConditioner", "data_scaler": "scaler.pkl",
          "latent_scaler": "latent_vectors_scaler.pkl", "xs_scaler": "xs_scaler.pkl"}      # names the mirrors write under model_save/
@@ -60,7 +62,77 @@ def scaler_vectors(scaler, name, length, what):
     return s32, mn.astype(np.float32)
 
 
-MAX_PROBES = 4096          # SGV_MAX_PROBES of the engine
+@contextlib.contextmanager
+def _engine_stream(stream):
+    """The handoff of every surrogate call: `stream` (the engine's) waits for the caller's current stream, is the current stream
+    inside the block, and the caller's stream waits for it afterwards, unless the two are one."""
+    import torch
+    cur = torch.cuda.current_stream()
+    stream.wait_stream(cur)             # conditions / out may come from the caller's stream
+    with torch.cuda.stream(stream):
+        yield
+    if cur != stream:
+        cur.wait_stream(stream)
+
+
+def _wanted(want, known, unknown, empty):
+    """the names of `known` that the tuple `want` holds, in the order of `known`; ValueError(unknown) if it holds another name,
+    ValueError(empty) if it holds none"""
+    if any(w not in known for w in want):
+        raise ValueError(unknown)
+    want = tuple(k for k in known if k in want)
+    if not want:
+        raise ValueError(empty)
+    return want
+
+
+class _Result:
+    """a result whose attributes are the names in its FIELDS, given by keyword"""
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+
+class _RunningResult(_Result):
+    """a result whose device tensors (those of its STATE that are not None) ARE the running state of a study over `count` members"""
+    PER_COUNT = 1          # values that enter the moments per unit of count
+
+    def __init__(self, stream=None, **kw):
+        super().__init__(**kw)
+        self._stream = stream          # the engine stream (a torch stream): what is derived from the state is computed there
+
+    def state(self):
+        """the tensors of the running state by their names in the engine's entry point (Engine.ensemble, Engine.sobol)"""
+        return {k: getattr(self, k) for k in self.STATE if getattr(self, k) is not None}
+
+    def _on_stream(self, fn):
+        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
+            return fn()
+
+    def _dof(self, what, ddof):
+        n = self.PER_COUNT * self.count
+        if n - ddof <= 0:
+            raise ValueError(f"{what}: {'count' if self.PER_COUNT == 1 else f'{self.PER_COUNT} count'} - ddof = {n} - {ddof} is not positive")
+        return n - ddof
+
+    @classmethod
+    def require(cls, into):
+        """the first check of `into=`, apart from continued(): what a caller compares of the earlier study comes between the two"""
+        if not isinstance(into, cls):
+            raise ValueError(f"into must be {'an' if cls.__name__[0] in 'AEIOU' else 'a'} {cls.__name__}, not {type(into).__name__}")
+
+    def continued(self, spec):
+        """(state(), count) for a call that goes on accumulating into this result, which must hold a contiguous CUDA tensor for
+        every name of spec = {name: (shape, dtype)} and a count that is not negative"""
+        state = self.state()
+        for k, (shape, dtype) in spec.items():
+            if not is_tensor_of(state.get(k), dtype, shape):
+                raise ValueError(f"into.{k} must be a contiguous {dtype} CUDA tensor of shape {shape}")
+        count = int(self.count)
+        if count < 0:
+            raise ValueError(f"into.count = {count} is negative")
+        return state, count
 
 
 def probe_nodes(nodes, num_node):
@@ -95,7 +167,7 @@ def truth_fields(truth, P, T, N):
     return a
 
 
-class ScoreResult:
+class ScoreResult(_Result):
     """Surrogate.score's result for P conditions, device tensors; e = predicted field - truth.  node_max_abs / node_bias / node_mse
     [P, N] fp32 (max over time of |e|, mean of e, mean of e^2 per node) and t_worst [P, N] int32 (the time step of the largest |e|);
     frame_max_abs / frame_mse / frame_truth_ms [P, T] fp32 (max over the mesh of |e|, mean of e^2, mean of truth^2 per time step)
@@ -104,10 +176,6 @@ class ScoreResult:
     max_abs = max_t frame_max_abs [P] fp32."""
     FIELDS = ("node_max_abs", "node_bias", "node_mse", "t_worst", "frame_max_abs", "frame_mse", "frame_truth_ms", "n_worst",
               "rmse", "rel_l2", "max_abs")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
 
 
 def exceed_limit(limit, N):
@@ -128,55 +196,33 @@ def exceed_limit(limit, N):
     return np.array(v)          # a copy: the broadcast view is read-only
 
 
-class EnsembleResult:
+class EnsembleResult(_RunningResult):
     """Surrogate.ensemble's result: statistics over `count` members per (time step, node), device tensors [T, N] that ARE the running
     state (pass the result back as `into=` to go on accumulating).  mean, m2 fp32 (Welford: m2 is the sum of squared deviations
     from the mean); max, min fp32 with arg_max, arg_min int32 (the index, in call order, of the condition that produced the
     extremum; the earliest on a tie); exceed int32 (members with field > limit, strict) with limit fp32 [N].  Groups not asked for
     are None."""
     FIELDS = ("count", "mean", "m2", "max", "min", "arg_max", "arg_min", "exceed", "limit")
-    GROUPS = {"moments": ("mean", "m2"), "extrema": ("max", "min", "arg_max", "arg_min"), "exceed": ("limit", "exceed")}
-
-    def __init__(self, stream=None, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
-        self._stream = stream          # the engine stream (a torch stream): var / std / exceed_fraction run there
+    GROUPS = ENSEMBLE_GROUPS
+    STATE = tuple(k for names in ENSEMBLE_GROUPS.values() for k in names)
 
     def groups(self):
         """the groups this result holds, in the order of GROUPS"""
         return tuple(g for g, names in self.GROUPS.items() if getattr(self, names[0]) is not None)
 
-    def state(self):
-        """the tensors of the running state by their names in Engine.ensemble"""
-        return {k: getattr(self, k) for names in self.GROUPS.values() for k in names if getattr(self, k) is not None}
-
-    def _on_stream(self, fn):
-        if self._stream is None:
-            return fn()
-        import torch
-        cur = torch.cuda.current_stream()
-        self._stream.wait_stream(cur)
-        with torch.cuda.stream(self._stream):
-            r = fn()
-        if cur != self._stream:
-            cur.wait_stream(self._stream)
-        return r
-
     def var(self, ddof=0):
         """m2 / (count - ddof) [T, N] fp32"""
         if self.m2 is None:
             raise ValueError("var: the moments were not asked for")
-        if self.count - ddof <= 0:
-            raise ValueError(f"var: count - ddof = {self.count} - {ddof} is not positive")
-        return self._on_stream(lambda: self.m2 / float(self.count - ddof))
+        dof = self._dof("var", ddof)
+        return self._on_stream(lambda: self.m2 / float(dof))
 
     def std(self, ddof=0):
         """sqrt(var(ddof))"""
         if self.m2 is None:
             raise ValueError("std: the moments were not asked for")
-        if self.count - ddof <= 0:
-            raise ValueError(f"std: count - ddof = {self.count} - {ddof} is not positive")
-        return self._on_stream(lambda: (self.m2 / float(self.count - ddof)).sqrt())
+        dof = self._dof("std", ddof)
+        return self._on_stream(lambda: (self.m2 / float(dof)).sqrt())
 
     def exceed_fraction(self):
         """exceed / count [T, N] fp32: how often the limit is exceeded"""
@@ -185,10 +231,6 @@ class EnsembleResult:
         if self.count < 1:
             raise ValueError("exceed_fraction: the ensemble is empty")
         return self._on_stream(lambda: self.exceed.float() / float(self.count))
-
-
-SOBOL_MAX_PARAMS = 30          # SGV_SOBOL_MAX_PARAMS of the engine: a block of d + 2 members fits the kernel's member table
-SOBOL_MAX_COUNT = 1 << 23      # base samples of one study: two values per sample enter the moments, and float(k) is exact to 2^24
 
 
 def sobol_groups(groups, F):
@@ -257,34 +299,24 @@ def sobol_members(A, B, groups):
     return np.ascontiguousarray(M.reshape(-1, A.shape[1]))
 
 
-class SobolResult:
+class SobolResult(_RunningResult):
     """Surrogate.sobol's result: the running sums of a Sobol sensitivity study over `count` base samples and `n_params` parameters,
     device tensors that ARE the running state (pass the result back as `into=` to go on accumulating).  mean, m2 fp32 [T, N]:
     Welford over the 2 count values of the A and B members; first_sq, total_sq fp32 [n_params, T, N]: sum_j (f(B_j) - f(AB_i_j))^2
     and sum_j (f(A_j) - f(AB_i_j))^2 (Jansen's estimators); one not asked for is None."""
     FIELDS = ("count", "n_params", "mean", "m2", "first_sq", "total_sq")
     PARTS = {"first": "first_sq", "total": "total_sq"}
-
-    def __init__(self, stream=None, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
-        self._stream = stream          # the engine stream (a torch stream): var / first_order / total_order run there
-
-    _on_stream = EnsembleResult._on_stream
+    STATE = SOBOL_FIELDS
+    PER_COUNT = 2
 
     def want(self):
         """the parts this result holds, in the order of PARTS"""
         return tuple(w for w, k in self.PARTS.items() if getattr(self, k) is not None)
 
-    def state(self):
-        """the tensors of the running state by their names in Engine.sobol"""
-        return {k: getattr(self, k) for k in ("mean", "m2", "first_sq", "total_sq") if getattr(self, k) is not None}
-
     def var(self, ddof=0):
         """m2 / (2 count - ddof) [T, N] fp32: the variance of the response over the A and B samples"""
-        if 2 * self.count - ddof <= 0:
-            raise ValueError(f"var: 2 count - ddof = {2 * self.count} - {ddof} is not positive")
-        return self._on_stream(lambda: self.m2 / float(2 * self.count - ddof))
+        dof = self._dof("var", ddof)
+        return self._on_stream(lambda: self.m2 / float(dof))
 
     def first_order(self):
         """S_i = 1 - first_sq[i] / (2 count var) [n_params, T, N] fp32: the share of the variance parameter i explains on its own.
@@ -305,15 +337,11 @@ class SobolResult:
         return self._on_stream(lambda: self.total_sq / (float(2 * self.count) * (self.m2 / float(2 * self.count))))
 
 
-class SweepResult:
+class SweepResult(_Result):
     """Surrogate.sweep's result for P conditions, device tensors: node_max / node_min / node_mean [P, N] fp32 and t_max / t_min
     [P, N] int32 (extrema over time per node, the time step of each, the mean over time); frame_max / frame_min [P, T] fp32 and
     n_max / n_min [P, T] int32 (extrema over the mesh per time step and their node); probes [P, T, K] fp32 or None."""
     FIELDS = ("node_max", "node_min", "node_mean", "t_max", "t_min", "frame_max", "frame_min", "n_max", "n_min", "probes")
-
-    def __init__(self, **kw):
-        for k in self.FIELDS:
-            setattr(self, k, kw[k])
 
 
 class Surrogate:
@@ -417,6 +445,17 @@ class Surrogate:
     def _batch(self, conditions, lo, hi):
         return conditions[lo:hi].to(device="cuda", dtype=self.torch.float32, non_blocking=True)
 
+    @staticmethod
+    def _batches(P, step):
+        """(lo, hi) of the batches of `step` that P rows fall into; the last one may be ragged"""
+        for lo in range(0, P, step):
+            yield lo, min(P, lo + step)
+
+    def _latent_batches(self, conditions, P, remap):
+        """(lo, hi, lat, xs) batch by batch: rows lo .. hi of `conditions` and the decoder's latents for them"""
+        for lo, hi in self._batches(P, self.batch):
+            yield (lo, hi) + self._latents(self._batch(conditions, lo, hi), remap)
+
     def predict(self, conditions, out=None, layout="TN", mode="fix"):
         """conditions [P, F] (host array or CUDA tensor, preprocessed as the conditioner's training set holds them) -> fp32 device
         tensor [P, T, N] (layout "TN") or [P, N, T] ("NT") in physical units.  mode "fix": the mean (the reference's "fix": the
@@ -429,15 +468,11 @@ class Surrogate:
         conditions, P, shape, remap = self._args(conditions, layout, mode)
         if out is None:
             out = t.empty(shape, dtype=t.float32, device="cuda")
-        elif not (t.is_tensor(out) and out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+        elif not is_tensor_of(out, t.float32, shape):
             raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
-        self._stream.wait_stream(t.cuda.current_stream())             # conditions / out may come from the caller's stream
-        with t.cuda.stream(self._stream):
-            for lo in range(0, P, self.batch):
-                hi = min(P, lo + self.batch)
+        with _engine_stream(self._stream):
+            for lo, hi in self._batches(P, self.batch):
                 self._generate(self._batch(conditions, lo, hi), out[lo:hi], layout, mode == "fix", remap)
-        if t.cuda.current_stream() != self._stream:
-            t.cuda.current_stream().wait_stream(self._stream)
         return out
 
     def sweep(self, conditions, probes=None, mode="fix"):
@@ -458,14 +493,11 @@ class Surrogate:
         node, when = t.empty((3, P, self.N), **f32), t.empty((2, P, self.N), **i32)          # the results: the caller's stream owns them
         frame, where = t.empty((2, P, self.T), **f32), t.empty((2, P, self.T), **i32)
         hist = t.empty((P, self.T, K), **f32) if probes is not None else None
-        self._stream.wait_stream(t.cuda.current_stream())
-        with t.cuda.stream(self._stream):
+        with _engine_stream(self._stream):
             b0 = min(self.batch, max(P, 1))
             buf = dict(node_stats=t.empty((b0, 3, self.N), **f32), node_when=t.empty((b0, 2, self.N), **i32),
                        frame_stats=t.empty((b0, self.T, 2), **f32), frame_where=t.empty((b0, self.T, 2), **i32))
-            for lo in range(0, P, self.batch):
-                hi = min(P, lo + self.batch)
-                lat, xs = self._latents(self._batch(conditions, lo, hi), remap)
+            for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
                 out = {k: v[:hi - lo] for k, v in buf.items()}
                 if hist is not None:
                     out["probes"] = hist[lo:hi]                  # [b, T, K] is the result's own layout: written in place
@@ -474,8 +506,6 @@ class Surrogate:
                 when[:, lo:hi].copy_(out["node_when"].transpose(0, 1))
                 frame[:, lo:hi].copy_(out["frame_stats"].permute(2, 0, 1))
                 where[:, lo:hi].copy_(out["frame_where"].permute(2, 0, 1))
-        if t.cuda.current_stream() != self._stream:
-            t.cuda.current_stream().wait_stream(self._stream)
         return SweepResult(node_max=node[0], node_min=node[1], node_mean=node[2], t_max=when[0], t_min=when[1],
                            frame_max=frame[0], frame_min=frame[1], n_max=where[0], n_min=where[1], probes=hist)
 
@@ -495,13 +525,10 @@ class Surrogate:
         i32 = dict(dtype=t.int32, device="cuda")
         node, when = t.empty((3, P, self.N), **f32), t.empty((P, self.N), **i32)          # the results: the caller's stream owns them
         frame, where = t.empty((3, P, self.T), **f32), t.empty((P, self.T), **i32)
-        self._stream.wait_stream(t.cuda.current_stream())
-        with t.cuda.stream(self._stream):
+        with _engine_stream(self._stream):
             b0 = min(self.batch, max(P, 1))
             buf = dict(node_err=t.empty((b0, 3, self.N), **f32), frame_err=t.empty((b0, self.T, 3), **f32))
-            for lo in range(0, P, self.batch):
-                hi = min(P, lo + self.batch)
-                lat, xs = self._latents(self._batch(conditions, lo, hi), remap)
+            for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
                 out = {k: v[:hi - lo] for k, v in buf.items()}
                 out.update(node_when=when[lo:hi], frame_where=where[lo:hi])          # the results' own layout: written in place
                 self.eng.score(lat, xs, self.data_scale, self.data_min, self._batch(truth, lo, hi).contiguous(), fix=mode == "fix", out=out)
@@ -511,8 +538,6 @@ class Surrogate:
             rmse = mse64.mean(dim=1).sqrt()
             rel_l2 = (mse64.sum(dim=1) / tms64.sum(dim=1)).sqrt()
             max_abs = frame[0].max(dim=1).values
-        if t.cuda.current_stream() != self._stream:
-            t.cuda.current_stream().wait_stream(self._stream)
         return ScoreResult(node_max_abs=node[0], node_bias=node[1], node_mse=node[2], t_worst=when, frame_max_abs=frame[0],
                            frame_mse=frame[1], frame_truth_ms=frame[2], n_worst=where, rmse=rmse, rel_l2=rel_l2, max_abs=max_abs)
 
@@ -535,56 +560,34 @@ class Surrogate:
         t = self.torch
         conditions, P, _, remap = self._args(conditions, "TN", mode)
         want = tuple(want)
-        groups = EnsembleResult.GROUPS
-        if any(w not in groups for w in want):
-            raise ValueError(f"want must name groups of {tuple(groups)}, not {want!r}")
+        groups = ENSEMBLE_GROUPS
+        want = _wanted(want + (("exceed",) if limit is not None else ()), groups,          # a limit asks for "exceed" by itself
+                       f"want must name groups of {tuple(groups)}, not {want!r}", f"want must name at least one of {tuple(groups)}")
         if limit is None and "exceed" in want:
             raise ValueError("want names 'exceed' but no limit is given")
-        if limit is not None and "exceed" not in want:
-            want += ("exceed",)
-        want = tuple(g for g in groups if g in want)
-        if not want:
-            raise ValueError(f"want must name at least one of {tuple(groups)}")
         lim = None if limit is None else exceed_limit(limit, self.N)
-        f32 = dict(dtype=t.float32, device="cuda")
-        i32 = dict(dtype=t.int32, device="cuda")
-        dtypes = dict(mean=t.float32, m2=t.float32, max=t.float32, min=t.float32, arg_max=t.int32, arg_min=t.int32, exceed=t.int32, limit=t.float32)
+        spec = {k: ((self.N,) if k == "limit" else (self.T, self.N), t.int32 if k in ("arg_max", "arg_min", "exceed") else t.float32)
+                for g in want for k in groups[g]}          # the tensors of this ensemble
+        state, count = {}, 0
         if into is not None:
-            if not isinstance(into, EnsembleResult):
-                raise ValueError(f"into must be an EnsembleResult, not {type(into).__name__}")
+            EnsembleResult.require(into)
             if into.groups() != want:
                 raise ValueError(f"into holds the groups {into.groups()}, this call asks for {want}")
-            state = into.state()
-            for k, v in state.items():
-                shape = (self.N,) if k == "limit" else (self.T, self.N)
-                if not (t.is_tensor(v) and v.is_cuda and v.dtype == dtypes[k] and v.is_contiguous() and tuple(v.shape) == shape):
-                    raise ValueError(f"into.{k} must be a contiguous {dtypes[k]} CUDA tensor of shape {shape}")
+            state, count = into.continued(spec)
             if lim is not None and not np.array_equal(state["limit"].cpu().numpy(), lim):
                 raise ValueError("into was accumulated against another limit")
-            count = int(into.count)
-            if count < 0:
-                raise ValueError(f"into.count = {count} is negative")
-        else:
-            state, count = {}, 0
-        if count + P > (1 << 24):
+        if count + P > ENSEMBLE_MAX_COUNT:
             raise ValueError(f"{count} + {P} members: an ensemble holds at most 2^24")
-        self._stream.wait_stream(t.cuda.current_stream())
-        with t.cuda.stream(self._stream):
+        with _engine_stream(self._stream):
             if into is None:
-                for g in want:
-                    for k in groups[g]:
-                        state[k] = (t.from_numpy(lim).cuda() if k == "limit"
-                                    else t.empty((self.T, self.N), **(i32 if dtypes[k] == t.int32 else f32)))
+                for k, (shape, dtype) in spec.items():
+                    state[k] = t.from_numpy(lim).cuda() if k == "limit" else t.empty(shape, dtype=dtype, device="cuda")
                 if P == 0:          # the empty ensemble, as the first batch would have found it
                     for k, v in state.items():
                         if k != "limit":
                             v.fill_({"max": float("-inf"), "min": float("inf")}.get(k, 0))
-            for lo in range(0, P, self.batch):
-                hi = min(P, lo + self.batch)
-                lat, xs = self._latents(self._batch(conditions, lo, hi), remap)
+            for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
                 self.eng.ensemble(lat, xs, self.data_scale, self.data_min, state, count + lo, fix=mode == "fix")
-        if t.cuda.current_stream() != self._stream:
-            t.cuda.current_stream().wait_stream(self._stream)
         return EnsembleResult(stream=self._stream, count=count + P, **{k: state.get(k) for k in EnsembleResult.FIELDS if k != "count"})
 
     def sobol(self, A, B, groups=None, want=("first", "total"), into=None):
@@ -615,52 +618,37 @@ class Surrogate:
         groups = sobol_groups(groups, F)
         d = len(groups)
         want = tuple(want)
-        if any(w not in SobolResult.PARTS for w in want):
-            raise ValueError(f"want must name parts of {tuple(SobolResult.PARTS)}, not {want!r}")
-        want = tuple(w for w in SobolResult.PARTS if w in want)
-        if not want:
-            raise ValueError(f"want must name at least one of {tuple(SobolResult.PARTS)}")
+        want = _wanted(want, SobolResult.PARTS, f"want must name parts of {tuple(SobolResult.PARTS)}, not {want!r}",
+                       f"want must name at least one of {tuple(SobolResult.PARTS)}")
         per = self.batch // (d + 2)
         if per < 1:
             raise ValueError(f"a block of d + 2 = {d + 2} members does not fit a batch of {self.batch}: build the Surrogate with batch >= {d + 2}")
-        shapes = {"mean": (self.T, self.N), "m2": (self.T, self.N), "first_sq": (d, self.T, self.N), "total_sq": (d, self.T, self.N)}
+        shapes = {"mean": (self.T, self.N), "m2": (self.T, self.N)}
+        shapes.update({SobolResult.PARTS[w]: (d, self.T, self.N) for w in want})          # the tensors of this study
+        state, count = {}, 0
         if into is not None:
-            if not isinstance(into, SobolResult):
-                raise ValueError(f"into must be a SobolResult, not {type(into).__name__}")
+            SobolResult.require(into)
             if int(into.n_params) != d:
                 raise ValueError(f"into holds {into.n_params} parameters, this call has {d}")
             if into.want() != want:
                 raise ValueError(f"into holds the parts {into.want()}, this call asks for {want}")
-            state = into.state()
-            for k in ("mean", "m2") + tuple(SobolResult.PARTS[w] for w in want):
-                v = state.get(k)
-                if not (t.is_tensor(v) and v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and tuple(v.shape) == shapes[k]):
-                    raise ValueError(f"into.{k} must be a contiguous {t.float32} CUDA tensor of shape {shapes[k]}")
-            count = int(into.count)
-            if count < 0:
-                raise ValueError(f"into.count = {count} is negative")
-        else:
-            state, count = {}, 0
+            state, count = into.continued({k: (shape, t.float32) for k, shape in shapes.items()})
         if count + n > SOBOL_MAX_COUNT:
             raise ValueError(f"{count} + {n} base samples: a study holds at most 2^23")
         take = np.zeros((d + 2, F), bool)          # which columns of a member come from B
         take[1] = True
         for i, g in enumerate(groups):
             take[2 + i, g] = True
-        self._stream.wait_stream(t.cuda.current_stream())
-        with t.cuda.stream(self._stream):
+        with _engine_stream(self._stream):
             if into is None:
-                for k in ("mean", "m2") + tuple(SobolResult.PARTS[w] for w in want):
-                    state[k] = (t.zeros if n == 0 else t.empty)(shapes[k], dtype=t.float32, device="cuda")
+                for k, shape in shapes.items():
+                    state[k] = (t.zeros if n == 0 else t.empty)(shape, dtype=t.float32, device="cuda")
             take = t.from_numpy(take).cuda()[None]
-            for lo in range(0, n, per):
-                hi = min(n, lo + per)
+            for lo, hi in self._batches(n, per):
                 a, b = self._batch(A, lo, hi)[:, None, :], self._batch(B, lo, hi)[:, None, :]
                 members = t.where(take, b, a).reshape((hi - lo) * (d + 2), F)          # A_j, B_j, AB_1_j .. AB_d_j per base sample
                 lat, xs = self._latents(members, remap)
                 self.eng.sobol(lat, xs, self.data_scale, self.data_min, state, d, count + lo, fix=True)
-        if t.cuda.current_stream() != self._stream:
-            t.cuda.current_stream().wait_stream(self._stream)
         return SobolResult(stream=self._stream, count=count + n, n_params=d, mean=state["mean"], m2=state["m2"],
                            first_sq=state.get("first_sq"), total_sq=state.get("total_sq"))
 
@@ -671,8 +659,7 @@ class Surrogate:
         conditions, P, shape, remap = self._args(conditions, layout, mode)
         if out is None:
             out = t.empty(shape, dtype=t.float32, pin_memory=True)
-        elif not (t.is_tensor(out) and out.device.type == "cpu" and out.is_pinned() and out.dtype == t.float32 and out.is_contiguous()
-                  and tuple(out.shape) == shape):
+        elif not (is_tensor_of(out, t.float32, shape, device="cpu") and out.is_pinned()):
             raise ValueError(f"out must be a contiguous pinned float32 CPU tensor of shape {shape}")
         if self._copy_stream is None:
             self._copy_stream = t.cuda.ExternalStream(self.eng.copy_stream())
@@ -681,8 +668,7 @@ class Surrogate:
         with t.cuda.stream(self._stream):
             bufs = [t.empty((self.batch,) + shape[1:], dtype=t.float32, device="cuda") for _ in range(min(2, (P + self.batch - 1) // self.batch))]
         copied = [None, None]
-        for i, lo in enumerate(range(0, P, self.batch)):
-            hi = min(P, lo + self.batch)
+        for i, (lo, hi) in enumerate(self._batches(P, self.batch)):
             buf = bufs[i % 2][:hi - lo]
             with t.cuda.stream(self._stream):
                 if copied[i % 2] is not None:

@@ -11,47 +11,26 @@ members in four batches.  Recorded, not asserted.
       var and (F > limit).sum over dim 0.
 
 Prints one JSON line.  Usage: python tests/micro/ensemble_bench.py [--batches 10] [--blocks 3] [--members 64] [--small-net]"""
-import argparse
 import itertools
 import json
-import os
-import statistics
-import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-import simulgen_vae_amd  # noqa: E402,F401
-from simulgen_vae_amd.engine import ENSEMBLE_GROUPS  # noqa: E402
-from simulgen_vae_amd.modules.VAE_network import VAE  # noqa: E402
+import recon_bench_common as RB
+from simulgen_vae_amd.engine import ENSEMBLE_GROUPS
 
-ENC = [1024, 512, 256, 128]
 STATE_ARRAYS = {"moments": 2, "extrema": 4, "exceed": 1}          # [T, N] arrays of 4 bytes a group reads and writes
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, default=10, help="calls per timed block of the kernel timers")
-    ap.add_argument("--blocks", type=int, default=3, help="alternations of the variants")
-    ap.add_argument("--batch", type=int, default=16)
+    ap = RB.parser(batches_help="calls per timed block of the kernel timers")
     ap.add_argument("--members", type=int, default=64, help="P: members of one study")
-    ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--small-net", action="store_true", help="N = 4096, T = 32: a quick functional run of this script")
     args = ap.parse_args()
-    N, T = (4096, 32) if args.small_net else (95008, 200)
-    B, nb, P = args.batch, args.batches, args.members
+    env = RB.setup(args)
+    N, T, B, nb, P, el, eng, stream, gen, scale, mn = env.N, env.T, env.B, env.nb, args.members, env.el, env.eng, env.stream, env.gen, env.scale, env.mn
     assert P % B == 0
-    vae = VAE(32, 8, ENC, ENC[::-1], N, T, lossfun="MSE", batch_size=B, small=True, compute_dtype=args.dtype).eval()
-    eng = vae._eng(B)
-    stream = torch.cuda.ExternalStream(eng.stream) if eng.stream else torch.cuda.current_stream()
-    gen = torch.Generator(device="cuda").manual_seed(1)
     z = torch.randn((P, 32), generator=gen, device="cuda")
     xs = torch.randn((3, P, 8), generator=gen, device="cuda") * 0.5
-    rng = np.random.default_rng(2)
-    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), N)).astype(np.float32)
-    scale = torch.from_numpy(np.where(rng.random(N) < 0.25, -scale, scale).astype(np.float32)).cuda()
-    mn = torch.from_numpy(rng.standard_normal(N).astype(np.float32)).cuda()
     fields = torch.empty((P, T, N), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
 
@@ -77,7 +56,6 @@ def main():
                 eng.generate(zb[i], xb[i], scale, mn, out=fields[i * B:(i + 1) * B])
             return fields.max(dim=0), fields.min(dim=0), fields.mean(dim=0), fields.var(dim=0, unbiased=False), (fields > limit).sum(dim=0)
 
-        el = 2 if args.dtype == "bf16" else 4
         subsets = [s for r in (1, 2, 3) for s in itertools.combinations(ENSEMBLE_GROUPS, r)]
         bytes_ = {"recon_phys": B * T * N * el + B * T * N * 4}
         for s in subsets:
@@ -90,47 +68,12 @@ def main():
         for s in subsets:
             passes["+".join(s)] = lambda s=s: one(s, B)
         passes["first:" + "+".join(ENSEMBLE_GROUPS)] = lambda: one(tuple(ENSEMBLE_GROUPS), 0)
-        for fn in passes.values():
-            fn()
-        torch.cuda.synchronize()
-        kern = {k: [] for k in passes}
-        for _ in range(args.blocks):
-            for k, fn in passes.items():
-                eng.kernel_time_reset(True)
-                for _ in range(nb):
-                    fn()
-                ms, n = eng.kernel_time("recon_phys" if k == "recon_phys" else "recon_ensemble")
-                assert n == nb, (k, n)
-                kern[k].append(ms / n)
-        eng.kernel_time_reset(False)
-        for k, v in kern.items():
-            out[k + "_kernel_ms_blocks"] = [round(t, 4) for t in v]
-            out[k + "_kernel_ms"] = round(statistics.mean(v), 4)
-            out[k + "_tb_per_s"] = round(bytes_[k] / (statistics.mean(v) * 1e-3) / 1e12, 3)
+        out.update(RB.kernel_blocks(eng, passes, lambda k: "recon_phys" if k == "recon_phys" else "recon_ensemble", bytes_, nb, args.blocks))
 
         # ---- whole studies of P members ----
-        def timed(fn, n):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            a.record(stream)
-            for _ in range(n):
-                fn()
-            b.record(stream)
-            torch.cuda.synchronize()
-            return a.elapsed_time(b) / n
-
         calls = {"generate_only": lambda: [eng.generate(zb[i], xb[i], scale, mn, out=fields[i * B:(i + 1) * B]) for i in range(P // B)],
                  "generate_then_torch_reduce": generate_then_reduce, "ensemble": study}
-        for fn in calls.values():
-            timed(fn, 1)
-        res = {k: [] for k in calls}
-        reps = max(1, nb // 3)
-        for _ in range(args.blocks):
-            for k, fn in calls.items():
-                res[k].append(timed(fn, reps))
-        for k, v in res.items():
-            out[k + "_study_ms_blocks"] = [round(t, 3) for t in v]
-            out[k + "_study_ms"] = round(statistics.mean(v), 3)
+        out.update(RB.alternating(stream, calls, 1, max(1, nb // 3), args.blocks, "_study_ms"))
     print(json.dumps(out))
 
 

@@ -13,49 +13,32 @@ time is the mean over --batches batches after a warm-up, per block, and the bloc
   (e) Surrogate.predict_to_host per batch, with the device-to-host rate that comes to.
 
 Prints one JSON line.  Usage: python tests/micro/predict_bench.py [--batches 20] [--blocks 3] [--host-batches 6] [--only ab] [--small-net]"""
-import argparse
 import ctypes as C
 import json
-import os
 import statistics
-import sys
 import time
 import types
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-import simulgen_vae_amd  # noqa: E402,F401
-from simulgen_vae_amd.modules.VAE_network import VAE  # noqa: E402
-from simulgen_vae_amd.modules.latent_conditioner_model_cnn import LatentConditionerImg  # noqa: E402
-from simulgen_vae_amd.predict import Surrogate  # noqa: E402
+import recon_bench_common as RB
+from simulgen_vae_amd.modules.latent_conditioner_model_cnn import LatentConditionerImg
+from simulgen_vae_amd.predict import Surrogate
 
-ENC = [1024, 512, 256, 128]
 LC_FILTERS = [32, 64, 128, 256, 512, 1024]          # tests/micro/e2e_bench.py
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, default=20, help="batches per timed block")
-    ap.add_argument("--blocks", type=int, default=3, help="alternations of the variants")
+    ap = RB.parser(batches=20, batches_help="batches per timed block", small_net_help="N = 4096, T = 32, 64 x 64 images: a quick functional run of this script")
     ap.add_argument("--host-batches", type=int, default=6, help="batches per block of (e): its pinned result is batches x 1.2 GB")
-    ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--only", default="abde", help="which of a, b, d, e to run")
-    ap.add_argument("--small-net", action="store_true", help="N = 4096, T = 32, 64 x 64 images: a quick functional run of this script")
     args = ap.parse_args()
-    n_node, n_time, side = (4096, 32, 64) if args.small_net else (95008, 200, 256)
-    B, nb = args.batch, args.batches
-    vae = VAE(32, 8, ENC, ENC[::-1], n_node, n_time, lossfun="MSE", batch_size=B, small=True, compute_dtype=args.dtype).eval()
-    eng = vae._eng(B)
-    stream = torch.cuda.current_stream()
-    gen = torch.Generator(device="cuda").manual_seed(1)
+    side = 64 if args.small_net else 256
+    env = RB.setup(args, signed=False)
+    n_node, n_time, B, nb, vae, eng, gen, scale, mn = env.N, env.T, env.B, env.nb, env.vae, env.eng, env.gen, env.scale, env.mn
     z = torch.randn((B, 32), generator=gen, device="cuda")
     xs = torch.randn((3, B, 8), generator=gen, device="cuda") * 0.5
-    rng = np.random.default_rng(2)
-    scale = torch.from_numpy(np.exp(rng.uniform(np.log(1e-3), np.log(50.0), n_node)).astype(np.float32)).cuda()
-    mn = torch.from_numpy(rng.standard_normal(n_node).astype(np.float32)).cuda()
     out_tn = torch.empty((B, n_time, n_node), dtype=torch.float32, device="cuda")
     out_nt = torch.empty((B, n_node, n_time), dtype=torch.float32, device="cuda")
     lib, vp = eng.lib, C.c_void_p
@@ -87,30 +70,12 @@ def main():
         nh = min(nb, args.host_batches)
         out_host = torch.empty((B * nh, n_time, n_node), dtype=torch.float32, pin_memory=True) if "e" in args.only else None
 
-    def timed(fn, n):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record(stream)
-        for _ in range(n):
-            fn()
-        b.record(stream)
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / n
-
-    for fn in variants.values():            # warm-up
-        timed(fn, 3)
-    res = {k: [] for k in variants}
-    for _ in range(args.blocks):
-        for k, fn in variants.items():
-            res[k].append(timed(fn, nb))
     out = {"config": f"preset-1 small, N={n_node}, T={n_time}, batch {B}, {args.dtype}, {nb} batches per block",
-           "c_bytes": B * n_time * n_node * ((2 if args.dtype == "bf16" else 4) + 4)}
-    for k, v in res.items():
-        out[k + "_ms_blocks"] = [round(t, 3) for t in v]
-        out[k + "_ms"] = round(statistics.mean(v), 3)
+           "c_bytes": B * n_time * n_node * (env.el + 4)}
+    out.update(RB.alternating(env.stream, variants, 3, nb, args.blocks, "_ms"))
     if "d" in args.only:
         sur.predict(cond[:2 * B], out=out_dev[:2 * B])
-        d = [timed(lambda: sur.predict(cond, out=out_dev), 1) / nb for _ in range(args.blocks)]
+        d = [RB.timed(env.stream, lambda: sur.predict(cond, out=out_dev), 1) / nb for _ in range(args.blocks)]
         out["d_predict_ms_per_batch_blocks"], out["d_predict_ms_per_batch"] = [round(t, 3) for t in d], round(statistics.mean(d), 3)
     if "e" in args.only:
         sur.predict_to_host(cond[:2 * B], out=out_host[:2 * B])

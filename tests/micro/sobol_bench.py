@@ -11,57 +11,25 @@ d = 6 parameters.  Recorded, not asserted.
       variance), and the two sums of squared differences per parameter -- accumulated over the batches.
 
 Prints one JSON line.  Usage: python tests/micro/sobol_bench.py [--batches 10] [--blocks 3] [--samples 64] [--small-net]"""
-import argparse
 import json
-import os
-import statistics
-import sys
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-import simulgen_vae_amd  # noqa: E402,F401
-from simulgen_vae_amd.modules.VAE_network import VAE  # noqa: E402
+import recon_bench_common as RB
 
-ENC = [1024, 512, 256, 128]
 PARTS = {"first+total": ("first_sq", "total_sq"), "first": ("first_sq",), "total": ("total_sq",)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, default=10, help="calls per timed block of the kernel timers")
-    ap.add_argument("--blocks", type=int, default=3, help="alternations of the variants")
-    ap.add_argument("--batch", type=int, default=16)
+    ap = RB.parser(batches_help="calls per timed block of the kernel timers")
     ap.add_argument("--samples", type=int, default=64, help="n: base samples of one study")
     ap.add_argument("--params", type=int, nargs="+", default=[2, 6], help="d: parameters")
-    ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--small-net", action="store_true", help="N = 4096, T = 32: a quick functional run of this script")
     args = ap.parse_args()
-    N, T = (4096, 32) if args.small_net else (95008, 200)
-    B, nb, n = args.batch, args.batches, args.samples
-    vae = VAE(32, 8, ENC, ENC[::-1], N, T, lossfun="MSE", batch_size=B, small=True, compute_dtype=args.dtype).eval()
-    eng = vae._eng(B)
-    stream = torch.cuda.ExternalStream(eng.stream) if eng.stream else torch.cuda.current_stream()
-    gen = torch.Generator(device="cuda").manual_seed(1)
-    rng = np.random.default_rng(2)
-    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), N)).astype(np.float32)
-    scale = torch.from_numpy(np.where(rng.random(N) < 0.25, -scale, scale).astype(np.float32)).cuda()
-    mn = torch.from_numpy(rng.standard_normal(N).astype(np.float32)).cuda()
+    env = RB.setup(args)
+    N, T, B, nb, n, el, eng, stream, gen, scale, mn = env.N, env.T, env.B, env.nb, args.samples, env.el, env.eng, env.stream, env.gen, env.scale, env.mn
     fields = torch.empty((B, T, N), dtype=torch.float32, device="cuda")
-    el = 2 if args.dtype == "bf16" else 4
     out = {"config": f"preset-1 small, N={N}, T={T}, batch {B}, {args.dtype}, n={n}, {nb} calls per block"}
     torch.cuda.synchronize()
-
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record(stream)
-        for _ in range(reps):
-            fn()
-        b.record(stream)
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / reps
 
     with torch.cuda.stream(stream):
         for d in args.params:
@@ -117,35 +85,12 @@ def main():
             for name, parts in PARTS.items():
                 passes[name] = lambda parts=parts: one(parts, per)
             passes["first:first+total"] = lambda: one(PARTS["first+total"], 0)
-            for fn in passes.values():
-                fn()
-            torch.cuda.synchronize()
-            kern = {k: [] for k in passes}
-            for _ in range(args.blocks):
-                for k, fn in passes.items():
-                    eng.kernel_time_reset(True)
-                    for _ in range(nb):
-                        fn()
-                    ms, cnt = eng.kernel_time("recon_phys" if k == "recon_phys" else "recon_sobol")
-                    assert cnt == nb, (k, cnt)
-                    kern[k].append(ms / cnt)
-            eng.kernel_time_reset(False)
-            for k, v in kern.items():
-                out[tag + k + "_kernel_ms_blocks"] = [round(t, 4) for t in v]
-                out[tag + k + "_kernel_ms"] = round(statistics.mean(v), 4)
-                out[tag + k + "_tb_per_s"] = round(bytes_[k] / (statistics.mean(v) * 1e-3) / 1e12, 3)
+            kern = RB.kernel_blocks(eng, passes, lambda k: "recon_phys" if k == "recon_phys" else "recon_sobol", bytes_, nb, args.blocks)
+            out.update({tag + k: v for k, v in kern.items()})
 
             # ---- whole studies of n base samples ----
             calls = {"generate_only": generate_only, "generate_then_torch_reduce": generate_then_reduce, "sobol": study}
-            for fn in calls.values():
-                timed(fn, 1)
-            res = {k: [] for k in calls}
-            for _ in range(args.blocks):
-                for k, fn in calls.items():
-                    res[k].append(timed(fn, 1))
-            for k, v in res.items():
-                out[tag + k + "_study_ms_blocks"] = [round(t, 3) for t in v]
-                out[tag + k + "_study_ms"] = round(statistics.mean(v), 3)
+            out.update({tag + k: v for k, v in RB.alternating(stream, calls, 1, 1, args.blocks, "_study_ms").items()})
             del state, acc, z, xs, zb, xb
     print(json.dumps(out))
 

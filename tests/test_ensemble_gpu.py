@@ -25,7 +25,8 @@ import simulgen_vae_amd  # noqa: F401
 from simulgen_vae_amd import engine as E
 from simulgen_vae_amd.predict import EnsembleResult
 from tests.gpu_common import G0, make_cfg
-from tests.test_predict_gpu import MAXB, _fresh, _same_state, _train_step, engine, latents, node_scaler, surrogate
+from tests.surrogate_common import (MAXB, bits, engine, latents, no_forward_after, same_result, signed_scaler, state_as_numpy, surrogate,
+                                    training_unaffected)
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ensemble_reference as ER  # noqa: E402
@@ -33,13 +34,6 @@ import ensemble_reference as ER  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 INT = ("arg_max", "arg_min", "exceed")
-
-
-def signed_scaler(N):
-    """node_scaler with about a quarter of the scales negative"""
-    scale, mn = node_scaler(N)
-    flip = np.random.default_rng(17).random(N) < 0.25
-    return np.where(flip, -scale, scale).astype(np.float32), mn
 
 
 def new_state(T, N, limit=None, groups=("moments", "extrema", "exceed")):
@@ -56,13 +50,7 @@ def new_state(T, N, limit=None, groups=("moments", "extrema", "exceed")):
 
 def as_numpy(res):
     """an EnsembleResult, or Engine.ensemble's dict, as numpy arrays under the emulation's names"""
-    get = (lambda k: getattr(res, k)) if isinstance(res, EnsembleResult) else res.get
-    return {k: get(k).cpu().numpy() for k in ER.STATE if get(k) is not None}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32) if a.dtype == np.float32 else a
+    return state_as_numpy(res, ER.STATE)
 
 
 def assert_reduces(got, F, limit=None, want=None):
@@ -178,55 +166,19 @@ def test_ensemble_checks_its_arguments():
 
 def test_no_forward_to_read_after_ensemble_and_generate_is_unchanged():
     cfg, eng = engine("G0", "bf16")
-    z, xs, eps = latents(cfg, 2)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    eng.set_eps(eps)
-    before = eng.generate(z, xs, scale, mn, fix=True).clone()
-    eng.set_eps(eps)
-    eng.decode(z, xs, fix=True)
-    eng.xhat()                                                   # readable after decode ...
-    eng.set_eps(eps)
-    eng.ensemble(z, xs, scale, mn, new_state(cfg.num_time, cfg.num_node, groups=("extrema",)), 0)
-    for call in (eng.xhat, lambda: eng.activation("x_hat", (2, cfg.num_node, cfg.num_time)), lambda: eng.backward(1.0, 1.0)):
-        with pytest.raises(E.SgvError, match=r"\(-3\)"):          # ... SGV_ERR_STATE after ensemble
-            call()
-    eng.set_eps(eps)
-    assert torch.equal(eng.generate(z, xs, scale, mn, fix=True), before)
+    st = new_state(cfg.num_time, cfg.num_node, groups=("extrema",))
+    no_forward_after(eng, cfg, lambda z, xs, scale, mn, before: eng.ensemble(z, xs, scale, mn, st, 0),
+                     (eng.xhat, lambda: eng.activation("x_hat", (2, cfg.num_node, cfg.num_time)), lambda: eng.backward(1.0, 1.0)))
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_training_is_unaffected_by_ensemble(dtype):
     cfg = make_cfg(G0)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    z, xs, eps = latents(cfg, 2)
     st = new_state(cfg.num_time, cfg.num_node, np.zeros(cfg.num_node, np.float32))
-    a, b = _fresh(cfg, dtype), _fresh(cfg, dtype)
-    try:
-        a.set_eps(eps)
-        a.ensemble(z, xs, scale, mn, st, 0)
-        _train_step(a, cfg, 0)
-        _train_step(b, cfg, 0)
-        assert _same_state(a, b) == []
-        a.set_eps(eps[:1])                                        # sites 1.. drawn by the engine, by member index: the draw position stays
-        a.ensemble(z, xs, scale, mn, st, 2)
-        _train_step(a, cfg, 1)
-        _train_step(b, cfg, 1)
-        assert _same_state(a, b) == []
-        assert a.train_state()["draw"] == b.train_state()["draw"]
-    finally:
-        a.close(); b.close()
+    training_unaffected(dtype, lambda eng, z, xs, scale, mn, i: eng.ensemble(z, xs, scale, mn, st, 2 * i), False)
 
 
 # ---- Surrogate.ensemble ----
-def _equal(a, b):
-    assert a.count == b.count
-    for k in EnsembleResult.FIELDS[1:]:
-        va, vb = getattr(a, k), getattr(b, k)
-        assert (va is None) == (vb is None), k
-        if va is not None:
-            assert va.dtype == vb.dtype and va.shape == vb.shape and torch.equal(va.view(torch.int32), vb.view(torch.int32)), k
-
-
 @pytest.mark.parametrize("mode", ["fix", "random"])
 @pytest.mark.parametrize("kind", ["img", "mlp"])
 def test_ensemble_reduces_what_predict_writes(kind, mode):
@@ -257,7 +209,7 @@ def test_batch_size_does_not_show_in_the_result(mode):
     assert a.count == 7 and a.arg_max.max() <= 6
     s, x, _ = surrogate("img", "f32", batch=7, seed=11)
     b = s.ensemble(x7, limit=0.0, mode=mode)                     # one batch of 7
-    _equal(a, b)
+    same_result(a, b)
     if mode == "random":                                         # members 0 and 6 share their condition and differ by their draws
         assert int(a.arg_max.max()) == 6 and bool((a.m2 > 0).all())
 
@@ -272,9 +224,9 @@ def test_into_continues_and_equals_one_call_and_host_conditions_equal_device_con
     ptrs = {k: v.data_ptr() for k, v in first.state().items()}
     second = s.ensemble(torch.from_numpy(x[3:]).cuda(), limit=limit, into=first)      # device conditions
     assert second.count == 6 and {k: v.data_ptr() for k, v in second.state().items()} == ptrs          # the same tensors, updated in place
-    _equal(whole, second)
+    same_result(whole, second)
     s, x, _ = surrogate("mlp", "f32", seed=11)
-    _equal(whole, s.ensemble(torch.from_numpy(x).cuda(), limit=limit))
+    same_result(whole, s.ensemble(torch.from_numpy(x).cuda(), limit=limit))
     # a subset of the groups gives the bits of the full call
     s, x, _ = surrogate("mlp", "f32", seed=11)
     ext = s.ensemble(x, want=("extrema",))
@@ -298,4 +250,4 @@ def test_into_continues_and_equals_one_call_and_host_conditions_equal_device_con
         s.ensemble(x, mode="mean")
     empty = s.ensemble(x[:0], limit=limit)
     assert empty.count == 0 and not empty.exceed.any() and bool(torch.isinf(empty.max).all())
-    _equal(whole, surrogate("mlp", "f32", seed=11)[0].ensemble(x, limit=limit, into=empty))
+    same_result(whole, surrogate("mlp", "f32", seed=11)[0].ensemble(x, limit=limit, into=empty))

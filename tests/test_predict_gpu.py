@@ -19,52 +19,21 @@ import torch
 
 import simulgen_vae_amd  # noqa: F401
 from simulgen_vae_amd import engine as E
-from simulgen_vae_amd.init import init_state, lc_csv_synthetic, lc_init_state, lc_synthetic, synthetic_samples
-from simulgen_vae_amd.modules.VAE_network import VAE
+from simulgen_vae_amd.init import lc_synthetic
 from simulgen_vae_amd.modules.latent_conditioner_model_cnn import LatentConditionerImg
-from simulgen_vae_amd.modules.latent_conditioner_model_parametric import LatentConditioner
 from simulgen_vae_amd.predict import Surrogate
-from tests.gpu_common import G0, G1, GOLD, make_cfg
+from tests.gpu_common import G0, make_cfg
+from tests.surrogate_common import MAXB, _fixture, _fresh, _same_state, _train_step, engine, latents, node_scaler, surrogate
 
 pytestmark = pytest.mark.gpu
 
 ELT32 = 2e-5
-MAXB = 4
 # worst |error| * |scale_n| of Surrogate.predict on bf16 models (VAE and, for "img", the conditioner) against the fixture, measured on
 # an MI355X: image conditioner 1.978e-1, parametric 3.751e-2 (the fp32 models: 1.65e-5 and 7.5e-6 against the bound of 3e-4)
 BF16_BOUND = {"img": 3 * 1.978e-1, "mlp": 3 * 3.751e-2}
 # the mean over the field of the same quantity, measured: image conditioner 1.193e-2, parametric 3.947e-3; asserted at 3 x as well (the
 # maximum's bound is wide against the scaled range of 1.4: the mean is what notices a decoder that is wrong everywhere a little)
 BF16_MEAN_BOUND = {"img": 3 * 1.193e-2, "mlp": 3 * 3.947e-3}
-
-_ENGINES = {}
-
-
-def engine(name, dtype):
-    """one engine per (configuration, dtype) for the read-only tests"""
-    if (name, dtype) not in _ENGINES:
-        cfg = make_cfg({"G0": G0, "G1": G1}[name])
-        eng = E.Engine(cfg, max_batch=MAXB, compute_dtype=dtype)
-        eng.load_state(init_state(cfg, 7))
-        _ENGINES[(name, dtype)] = (cfg, eng)
-    return _ENGINES[(name, dtype)]
-
-
-def latents(cfg, B, seed=3):
-    rng = np.random.default_rng(seed)
-    z = torch.from_numpy(rng.standard_normal((B, cfg.latent_dim)).astype(np.float32)).cuda()
-    xs = [torch.from_numpy((0.5 * rng.standard_normal((B, cfg.hierarchical_dim))).astype(np.float32)).cuda() for _ in range(len(cfg.num_filter_enc) - 1)]
-    eps = [torch.zeros(B, cfg.latent_dim).cuda()] + [torch.from_numpy(rng.standard_normal((B, c, cfg.num_time)).astype(np.float32)).cuda()
-                                                     for c in cfg.num_filter_dec[1:-1]]
-    return z, xs, eps
-
-
-def node_scaler(N, seed=5):
-    rng = np.random.default_rng(seed)
-    scale = np.exp(rng.uniform(np.log(1e-3), np.log(50.0), N)).astype(np.float32)
-    mn = (rng.standard_normal(N) * np.where(rng.random(N) < 0.5, 1.0, 30.0)).astype(np.float32)
-    return scale, mn
-
 
 def descale64(xhat_bnt, scale, mn, layout):
     """float64 (x_hat - min) / scale of a reference-layout [B, N, T] array, in the layout asked for"""
@@ -144,33 +113,6 @@ def test_no_forward_to_read_after_generate():
     eng.xhat()
 
 
-def _train_step(eng, cfg, k):
-    x = synthetic_samples(20251003, range(3 * k, 3 * k + 3), cfg.num_node, cfg.num_time)
-    rng = np.random.default_rng(100 + k)
-    eps = [torch.from_numpy(rng.standard_normal((3, cfg.latent_dim)).astype(np.float32)).cuda()] + [
-        torch.from_numpy(rng.standard_normal((3, c, cfg.num_time)).astype(np.float32)).cuda() for c in cfg.num_filter_dec[1:-1]]
-    eng.set_input(torch.from_numpy(x).cuda())
-    eng.set_eps(eps)
-    eng.forward(train=True)
-    eng.backward_step(1e6, 1e-4, 1e-3)
-
-
-def _fresh(cfg, dtype):
-    eng = E.Engine(cfg, max_batch=MAXB, compute_dtype=dtype)
-    eng.load_state(init_state(cfg, 7))
-    return eng
-
-
-def _same_state(a, b):
-    sa, sb = a.state_dict(), b.state_dict()
-    bad = [k for k in sa if not np.array_equal(sa[k], sb[k])]
-    for k in [k for k in sa if k.endswith("weight_orig")][::7]:          # and the optimizer's moments of a few weights
-        ma, mb = a.adam_state(k), b.adam_state(k)
-        if not (np.array_equal(ma[0], mb[0]) and np.array_equal(ma[1], mb[1])):
-            bad.append("adam." + k)
-    return bad
-
-
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_training_is_unaffected_by_generate(dtype):
     cfg = make_cfg(G0)
@@ -194,40 +136,6 @@ def test_training_is_unaffected_by_generate(dtype):
 
 
 # ---- Surrogate against the reference ----
-def _fixture():
-    return np.load(f"{GOLD}/predict_small.npz")
-
-
-_SUR = {}
-
-
-def surrogate(kind, dtype, batch=MAXB, seed=0):
-    """(Surrogate, conditions [6, F]) on the fixture's models; VAE and conditioner are built once per (kind, dtype)"""
-    g = _fixture()
-    P, data_seed, _, img, img_seed, n_param, mlp_seed, vae_seed = (int(v) for v in g["meta"])
-    if (kind, dtype) not in _SUR:
-        cfg = make_cfg(G1)
-        vae = VAE(cfg.latent_dim, cfg.hierarchical_dim, cfg.num_filter_enc, cfg.num_filter_dec, cfg.num_node, cfg.num_time, lossfun="MSE",
-                  batch_size=MAXB, small=True, compute_dtype=dtype)
-        vae.load_state_dict({k: torch.from_numpy(v) for k, v in init_state(cfg, vae_seed).items()})
-        vae.eval()
-        if kind == "img":
-            lc = LatentConditionerImg([int(v) for v in g["img_filters"]], cfg.latent_dim, (1, img, img), cfg.hierarchical_dim, 3, (img, img),
-                                      dropout_rate=0.0, use_attention=True, compute_dtype=dtype)
-            seed_lc = img_seed
-            x = lc_synthetic(data_seed, P, img * img, cfg.latent_dim, 3, cfg.hierarchical_dim)[0]
-        else:
-            lc = LatentConditioner([int(v) for v in g["mlp_filters"]], cfg.latent_dim, n_param, cfg.hierarchical_dim, 3, dropout_rate=0.3)
-            seed_lc = mlp_seed
-            x = lc_csv_synthetic(data_seed, P, n_param, cfg.latent_dim, 3, cfg.hierarchical_dim)[0]
-        st = lc_init_state({k: tuple(v.shape) for k, v in lc.state_dict().items()}, seed_lc)
-        lc.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()})
-        _SUR[(kind, dtype)] = (vae, lc, x)
-    vae, lc, x = _SUR[(kind, dtype)]
-    sc = [types.SimpleNamespace(scale_=g[n + "_scale"], min_=g[n + "_min"]) for n in ("latent", "xs", "data")]
-    return Surrogate(vae, lc, sc[0], sc[1], sc[2], batch=batch, seed=seed), x, g
-
-
 @pytest.mark.parametrize("kind", ["img", "mlp"])
 def test_predict_matches_the_reference_fp32(kind):
     s, x, g = surrogate(kind, "f32")

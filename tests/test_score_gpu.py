@@ -24,21 +24,13 @@ import torch
 import simulgen_vae_amd  # noqa: F401
 from simulgen_vae_amd import engine as E
 from simulgen_vae_amd.predict import ScoreResult
-from tests.gpu_common import G0, make_cfg
-from tests.test_predict_gpu import MAXB, _fresh, _same_state, _train_step, engine, latents, node_scaler, surrogate
+from tests.surrogate_common import MAXB, engine, latents, no_forward_after, same_result, signed_scaler, surrogate, training_unaffected
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 INT_FIELDS = ("t_worst", "n_worst")
 F64_FIELDS = ("rmse", "rel_l2")
-
-
-def signed_scaler(N):
-    """node_scaler with about a quarter of the scales negative"""
-    scale, mn = node_scaler(N)
-    flip = np.random.default_rng(17).random(N) < 0.25
-    return np.where(flip, -scale, scale).astype(np.float32), mn
 
 
 def perturbed(F, scale, seed=41):
@@ -173,43 +165,13 @@ def test_score_checks_its_arguments():
 
 def test_no_forward_to_read_after_score_and_generate_is_unchanged():
     cfg, eng = engine("G0", "bf16")
-    z, xs, eps = latents(cfg, 2)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    eng.set_eps(eps)
-    before = eng.generate(z, xs, scale, mn, fix=True).clone()
-    eng.set_eps(eps)
-    eng.decode(z, xs, fix=True)
-    eng.xhat()                                                   # readable after decode ...
-    eng.set_eps(eps)
-    eng.score(z, xs, scale, mn, before * 1.25)
-    for call in (eng.xhat, lambda: eng.activation("x_hat", (2, cfg.num_node, cfg.num_time)), lambda: eng.backward(1.0, 1.0)):
-        with pytest.raises(E.SgvError, match=r"\(-3\)"):          # ... SGV_ERR_STATE after score
-            call()
-    eng.set_eps(eps)
-    assert torch.equal(eng.generate(z, xs, scale, mn, fix=True), before)
+    no_forward_after(eng, cfg, lambda z, xs, scale, mn, before: eng.score(z, xs, scale, mn, before * 1.25),
+                     (eng.xhat, lambda: eng.activation("x_hat", (2, cfg.num_node, cfg.num_time)), lambda: eng.backward(1.0, 1.0)))
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_training_is_unaffected_by_score(dtype):
-    cfg = make_cfg(G0)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    z, xs, eps = latents(cfg, 2)
-    tr = torch.ones(2, cfg.num_time, cfg.num_node, device="cuda")
-    a, b = _fresh(cfg, dtype), _fresh(cfg, dtype)
-    try:
-        a.set_eps(eps)
-        a.score(z, xs, scale, mn, tr)
-        _train_step(a, cfg, 0)
-        _train_step(b, cfg, 0)
-        assert _same_state(a, b) == []
-        a.set_eps(eps[:1])                                        # sites 1.. drawn by the engine: only the draw counter moves
-        a.score(z, xs, scale, mn, tr)
-        _train_step(a, cfg, 1)
-        _train_step(b, cfg, 1)
-        assert _same_state(a, b) == []
-        assert a.train_state()["draw"] > b.train_state()["draw"]
-    finally:
-        a.close(); b.close()
+    training_unaffected(dtype, lambda eng, z, xs, scale, mn, i: eng.score(z, xs, scale, mn, torch.ones(2, eng.cfg.num_time, eng.cfg.num_node, device="cuda")), True)
 
 
 # ---- Surrogate.score ----
@@ -263,14 +225,6 @@ def test_score_reduces_what_predict_writes_bf16(kind):
     assert_per_condition(got)
 
 
-def _equal(a, b):
-    for k in ScoreResult.FIELDS:
-        va, vb = getattr(a, k), getattr(b, k)
-        assert va.dtype == vb.dtype and va.shape == vb.shape, k
-        as_bits = torch.int64 if va.dtype == torch.float64 else torch.int32
-        assert torch.equal(va.contiguous().view(as_bits), vb.contiguous().view(as_bits)), k
-
-
 def test_ragged_last_batch_equals_split_calls_and_host_truth_equals_device_truth():
     s, x, g = surrogate("img", "f32", seed=11)
     truth = perturbed(g["img_fields"], g["data_scale"])
@@ -278,11 +232,11 @@ def test_ragged_last_batch_equals_split_calls_and_host_truth_equals_device_truth
     assert whole.node_mse.shape == (6, 520) and whole.n_worst.shape == (6, 12)
     s, x, _ = surrogate("img", "f32", seed=11)
     first, second = s.score(x[:4], truth[:4]), s.score(torch.from_numpy(x[4:]).cuda(), torch.from_numpy(truth[4:]).cuda())
-    _equal(whole, ScoreResult(**{k: torch.cat([getattr(first, k), getattr(second, k)]) for k in ScoreResult.FIELDS}))
+    same_result(whole, ScoreResult(**{k: torch.cat([getattr(first, k), getattr(second, k)]) for k in ScoreResult.FIELDS}))
     s, x, _ = surrogate("img", "f32", seed=11)
-    _equal(whole, s.score(x, torch.from_numpy(truth).cuda()))    # device truth
+    same_result(whole, s.score(x, torch.from_numpy(truth).cuda()))    # device truth
     s, x, _ = surrogate("img", "f32", seed=11)
-    _equal(whole, s.score(x, torch.from_numpy(truth)))           # CPU tensor
+    same_result(whole, s.score(x, torch.from_numpy(truth)))           # CPU tensor
     with pytest.raises(ValueError, match="truth: dimension P is 5, expected P = 6"):
         s.score(x, truth[:5])
     with pytest.raises(ValueError, match="truth: dtype float32 is required, not float64"):

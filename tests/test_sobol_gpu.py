@@ -19,8 +19,7 @@ import simulgen_vae_amd  # noqa: F401
 from simulgen_vae_amd import engine as E
 from simulgen_vae_amd.predict import SobolResult, sobol_members
 from tests.gpu_common import G0, make_cfg
-from tests.test_ensemble_gpu import signed_scaler
-from tests.test_predict_gpu import _fresh, _same_state, _train_step, engine, latents, surrogate
+from tests.surrogate_common import bits, engine, latents, no_forward_after, same_result, signed_scaler, state_as_numpy, surrogate, training_unaffected
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sobol_reference as SR  # noqa: E402
@@ -28,10 +27,6 @@ import sobol_reference as SR  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 def new_state(d, T, N, parts=("first_sq", "total_sq")):
@@ -42,8 +37,7 @@ def new_state(d, T, N, parts=("first_sq", "total_sq")):
 
 
 def as_numpy(res):
-    get = (lambda k: getattr(res, k)) if isinstance(res, SobolResult) else res.get
-    return {k: get(k).cpu().numpy() for k in SR.STATE if get(k) is not None}
+    return state_as_numpy(res, SR.STATE)
 
 
 def assert_same(got, want):
@@ -164,43 +158,16 @@ def test_sobol_checks_its_arguments():
 
 def test_no_forward_to_read_after_sobol_and_generate_is_unchanged():
     cfg, eng = engine("G0", "bf16")
-    z, xs, eps = latents(cfg, 3)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    eng.set_eps(eps)
-    before = eng.generate(z, xs, scale, mn, fix=True).clone()
-    eng.set_eps(eps)
-    eng.decode(z, xs, fix=True)
-    eng.xhat()                                                   # readable after decode ...
-    eng.set_eps(eps)
-    eng.sobol(z, xs, scale, mn, new_state(1, cfg.num_time, cfg.num_node, parts=("total_sq",)), 1, 0)
-    for call in (eng.xhat, lambda: eng.activation("x_hat", (3, cfg.num_node, cfg.num_time)), lambda: eng.backward(1.0, 1.0)):
-        with pytest.raises(E.SgvError, match=r"\(-3\)"):          # ... SGV_ERR_STATE after sobol
-            call()
-    eng.set_eps(eps)
-    assert torch.equal(eng.generate(z, xs, scale, mn, fix=True), before)
+    st = new_state(1, cfg.num_time, cfg.num_node, parts=("total_sq",))
+    no_forward_after(eng, cfg, lambda z, xs, scale, mn, before: eng.sobol(z, xs, scale, mn, st, 1, 0),
+                     (eng.xhat, lambda: eng.activation("x_hat", (3, cfg.num_node, cfg.num_time)), lambda: eng.backward(1.0, 1.0)), B=3)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_training_is_unaffected_by_sobol(dtype):
     cfg = make_cfg(G0)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    z, xs, eps = latents(cfg, 4)
     st = new_state(2, cfg.num_time, cfg.num_node)
-    a, b = _fresh(cfg, dtype), _fresh(cfg, dtype)
-    try:
-        a.set_eps(eps)
-        a.sobol(z, xs, scale, mn, st, 2, 0)
-        _train_step(a, cfg, 0)
-        _train_step(b, cfg, 0)
-        assert _same_state(a, b) == []
-        a.set_eps(eps[:1])                                        # sites 1.. drawn by the engine, by member index: the draw position stays
-        a.sobol(z, xs, scale, mn, st, 2, 1)
-        _train_step(a, cfg, 1)
-        _train_step(b, cfg, 1)
-        assert _same_state(a, b) == []
-        assert a.train_state()["draw"] == b.train_state()["draw"]
-    finally:
-        a.close(); b.close()
+    training_unaffected(dtype, lambda eng, z, xs, scale, mn, i: eng.sobol(z, xs, scale, mn, st, 2, i), False, B=4)
 
 
 # ---- Surrogate.sobol ----
@@ -210,15 +177,6 @@ GROUPS = [[0], [1, 2]]          # d = 2: blocks of 4 members
 def design(x):
     """A, B [3, F] from the fixture's six conditions, as copies: the conditions are shared with the other test modules"""
     return np.array(x[:3], np.float32), np.array(x[3:], np.float32)
-
-
-def _equal(a, b):
-    assert a.count == b.count and a.n_params == b.n_params
-    for k in SR.STATE:
-        va, vb = getattr(a, k), getattr(b, k)
-        assert (va is None) == (vb is None), k
-        if va is not None:
-            assert va.dtype == vb.dtype and va.shape == vb.shape and torch.equal(va.view(torch.int32), vb.view(torch.int32)), k
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
@@ -244,15 +202,15 @@ def test_batch_size_into_and_host_or_device_inputs_do_not_show_in_the_result():
     A, B = design(x)
     whole = s.sobol(A, B, groups=GROUPS)                          # 1 + 1 + 1 blocks; host inputs (numpy)
     s, _, _ = surrogate("mlp", "f32", batch=11, seed=11)
-    _equal(whole, s.sobol(A, B, groups=GROUPS))                   # 2 + 1 blocks: 11 // 4 = 2
+    same_result(whole, s.sobol(A, B, groups=GROUPS))                   # 2 + 1 blocks: 11 // 4 = 2
     s, _, _ = surrogate("mlp", "f32", batch=12, seed=11)
-    _equal(whole, s.sobol(torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda(), groups=GROUPS))      # one batch; device inputs
+    same_result(whole, s.sobol(torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda(), groups=GROUPS))      # one batch; device inputs
     s, _, _ = surrogate("mlp", "f32", batch=8, seed=11)
     first = s.sobol(A[:1], B[:1], groups=GROUPS)
     ptrs = {k: v.data_ptr() for k, v in first.state().items()}
     second = s.sobol(torch.from_numpy(A[1:]).cuda(), B[1:], groups=GROUPS, into=first)
     assert second.count == 3 and {k: v.data_ptr() for k, v in second.state().items()} == ptrs          # the same tensors, updated in place
-    _equal(whole, second)
+    same_result(whole, second)
     # one part alone gives the bits of the full call
     s, _, _ = surrogate("mlp", "f32", batch=8, seed=11)
     tot = s.sobol(A, B, groups=GROUPS, want=("total",))
@@ -274,7 +232,7 @@ def test_batch_size_into_and_host_or_device_inputs_do_not_show_in_the_result():
         s.sobol(A, B, groups=[[0], [99]])
     empty = s.sobol(A[:0], B[:0], groups=GROUPS)
     assert empty.count == 0 and not empty.total_sq.any()
-    _equal(whole, surrogate("mlp", "f32", batch=8, seed=11)[0].sobol(A, B, groups=GROUPS, into=empty))
+    same_result(whole, surrogate("mlp", "f32", batch=8, seed=11)[0].sobol(A, B, groups=GROUPS, into=empty))
 
 
 def test_a_block_larger_than_the_batch_is_refused():

@@ -18,17 +18,9 @@ import torch
 import simulgen_vae_amd  # noqa: F401
 from simulgen_vae_amd import engine as E
 from simulgen_vae_amd.predict import SweepResult
-from tests.gpu_common import G0, make_cfg
-from tests.test_predict_gpu import MAXB, _fresh, _same_state, _train_step, engine, latents, node_scaler, surrogate
+from tests.surrogate_common import MAXB, engine, latents, no_forward_after, same_result, signed_scaler, surrogate, training_unaffected
 
 pytestmark = pytest.mark.gpu
-
-
-def signed_scaler(N):
-    """node_scaler with about a quarter of the scales negative"""
-    scale, mn = node_scaler(N)
-    flip = np.random.default_rng(17).random(N) < 0.25
-    return np.where(flip, -scale, scale).astype(np.float32), mn
 
 
 def probes_for(N):
@@ -130,43 +122,14 @@ def test_summarize_checks_its_arguments():
 
 def test_no_forward_to_read_after_summarize_and_generate_is_unchanged():
     cfg, eng = engine("G0", "bf16")
-    z, xs, eps = latents(cfg, 2)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    eng.set_eps(eps)
-    before = eng.generate(z, xs, scale, mn, fix=True).clone()
-    eng.set_eps(eps)
-    eng.decode(z, xs, fix=True)
-    eng.xhat()                                                   # readable after decode ...
-    eng.set_eps(eps)
-    eng.summarize(z, xs, scale, mn, want=("node", "frame"))
-    for call in (eng.xhat, lambda: eng.backward(1.0, 1.0)):
-        with pytest.raises(E.SgvError, match=r"\(-3\)"):          # ... SGV_ERR_STATE after summarize
-            call()
-    eng.set_eps(eps)
-    assert torch.equal(eng.generate(z, xs, scale, mn, fix=True), before)
+    no_forward_after(eng, cfg, lambda z, xs, scale, mn, before: eng.summarize(z, xs, scale, mn, want=("node", "frame")),
+                     (eng.xhat, lambda: eng.backward(1.0, 1.0)))
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_training_is_unaffected_by_summarize(dtype):
-    cfg = make_cfg(G0)
-    scale, mn = (torch.from_numpy(a).cuda() for a in signed_scaler(cfg.num_node))
-    z, xs, eps = latents(cfg, 2)
-    a, b = _fresh(cfg, dtype), _fresh(cfg, dtype)
-    try:
-        a.set_probes(probes_for(cfg.num_node))
-        a.set_eps(eps)
-        a.summarize(z, xs, scale, mn)
-        _train_step(a, cfg, 0)
-        _train_step(b, cfg, 0)
-        assert _same_state(a, b) == []
-        a.set_eps(eps[:1])                                        # sites 1.. drawn by the engine: only the draw counter moves
-        a.summarize(z, xs, scale, mn)
-        _train_step(a, cfg, 1)
-        _train_step(b, cfg, 1)
-        assert _same_state(a, b) == []
-        assert a.train_state()["draw"] > b.train_state()["draw"]
-    finally:
-        a.close(); b.close()
+    training_unaffected(dtype, lambda eng, z, xs, scale, mn, i: eng.summarize(z, xs, scale, mn), True,
+                        prepare=lambda eng: eng.set_probes(probes_for(eng.cfg.num_node)))
 
 
 # ---- Surrogate.sweep ----
@@ -210,15 +173,6 @@ def test_sweep_reduces_what_predict_writes_bf16(kind):
     assert_reduces(as_numpy(s.sweep(x, probes=nodes)), F, nodes)
 
 
-def _equal(a, b):
-    for k in SweepResult.FIELDS:
-        va, vb = getattr(a, k), getattr(b, k)
-        if va is None or vb is None:
-            assert va is None and vb is None, k
-        else:
-            assert va.dtype == vb.dtype and torch.equal(va, vb), k
-
-
 def test_ragged_last_batch_equals_split_calls():
     s, x, _ = surrogate("img", "f32", seed=11)
     whole = s.sweep(x, probes=[5, 5, 519])                       # 6 conditions at batch 4: 4 + 2
@@ -226,11 +180,11 @@ def test_ragged_last_batch_equals_split_calls():
     s, x, _ = surrogate("img", "f32", seed=11)
     first, second = s.sweep(x[:4], probes=[5, 5, 519]), s.sweep(torch.from_numpy(x[4:]).cuda(), probes=[5, 5, 519])
     parts = SweepResult(**{k: torch.cat([getattr(first, k), getattr(second, k)]) for k in SweepResult.FIELDS})
-    _equal(whole, parts)
+    same_result(whole, parts)
     s, x, _ = surrogate("img", "f32", seed=11)
     bare = s.sweep(x)
     assert bare.probes is None
-    _equal(bare, SweepResult(**dict({k: getattr(whole, k) for k in SweepResult.FIELDS}, probes=None)))
+    same_result(bare, SweepResult(**dict({k: getattr(whole, k) for k in SweepResult.FIELDS}, probes=None)))
     with pytest.raises(ValueError, match=r"probes\[1\] = 520 is outside"):
         s.sweep(x, probes=[0, 520])
     with pytest.raises(ValueError, match="mode must be"):

@@ -289,6 +289,27 @@ typedef struct { float* mean; float* m2; float* first_sq; float* total_sq; } sgv
  * forward pass to read from, as after sgv_generate. */
 int sgv_sobol(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
               const float* min_dev, int n_params, long blocks_before, const sgv_sobol_state* st);
+/* The empirical distribution of many generated fields per (time step, node): a histogram of K = bins uniform bins, 2 <= K <= 64,
+ * between bounds the caller gives -- in a study, the envelope (min, max) an extrema pass of sgv_ensemble found over the same members.
+ * Device pointers, dense, 16-byte aligned: lo, hi fp32 [T][N] (inputs, hi >= lo, finite: not checked); counts int32 [K + 2][T][N]:
+ * row 0 counts the members below lo, rows 1 .. K are the bins, row K + 1 counts the members above hi.  The state belongs to the
+ * caller and persists across calls: the kernel only ever adds to counts, so a new state must be zeroed by the caller. */
+typedef struct { const float* lo; const float* hi; int32_t* counts; int bins; } sgv_distribution_state;
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the distribution pass: with x the value
+ * sgv_generate would store for a sample (SGV_LAYOUT_TN), all in fp32 and every operation rounded on its own,
+ *   invw = hi > lo ? (float)K / (hi - lo) : 0.0f
+ *   row  = x < lo ? 0 : x > hi ? K + 1 : 1 + min((int)((x - lo) * invw), K - 1);    counts[row][t][n] += 1
+ * so x == hi lands in the last bin and, where hi == lo, x == lo in bin 1; a NaN is counted in some row, which one is not specified.
+ * The columns of counts sum to the number of members.  Integer counts do not depend on the order of the members: any cut of the same
+ * members into calls gives the same bits.  Sample b of the batch is member count_before + b, which places it in the noise streams by
+ * the mechanism of sgv_ensemble -- it is bit for bit the member sgv_ensemble saw at that index, so with lo / hi the extrema of an
+ * ensemble pass over the same members nothing falls outside -- and leaves the draw position where it is; count_before does not
+ * decide whether the state is read: it always is.  No atomics, no workspace, nothing allocated.  SGV_ERR_ARG before anything is
+ * enqueued: e, z_dev, scale_dev, min_dev or st NULL, lo, hi or counts NULL, bins outside [2, 64], a misaligned pointer,
+ * count_before < 0 or count_before + batch > 2^24, the checks of sgv_decode.  Synchronises nothing.  Afterwards there is no forward
+ * pass to read from, as after sgv_generate. */
+int sgv_distribution(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                     const float* min_dev, long count_before, const sgv_distribution_state* st);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -578,6 +599,13 @@ int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, co
 int sgv_test_recon_sobol(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                          const float* scale, const float* min, int n_params, long blocks_before, const sgv_sobol_state* st, int B,
                          int T, int C, void* stream);
+/* The kernel of sgv_distribution on caller-owned buffers: inputs as sgv_test_recon_physical, then the statistics of y and the
+ * distribution pass into *st (shapes of sgv_distribution_state with N = C).  SGV_ERR_ARG, nothing launched: a NULL input, st NULL,
+ * lo, hi or counts NULL, bins outside [2, 64], B or T < 1, C < 8 or C % 8 != 0, a bad row stride, a misaligned pointer (y, lo, hi
+ * and counts 16 bytes), count_before < 0 or count_before + B > 2^24. */
+int sgv_test_recon_distribution(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                                const float* scale, const float* min, long count_before, const sgv_distribution_state* st, int B,
+                                int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

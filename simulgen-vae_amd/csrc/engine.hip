@@ -888,28 +888,31 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 }
 
 // What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
-// (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble) or the sums of a Sobol study
-// (sgv_sobol); only the members of `kind` are read.
+// (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble), the sums of a Sobol study
+// (sgv_sobol) or the histogram of the members (sgv_distribution); only the members of `kind` are read.
 struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL } kind;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION } kind;
     const float* scale; const float* mn;
     int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
     ReconSummary sum;                                          // SUMMARY
     ReconScore score; const float* truth = nullptr;            // SCORE
     ReconEnsemble ens; long ens_count = 0;                     // ENSEMBLE
     ReconSobol sob; int sob_params = 0; long sob_blocks = 0;   // SOBOL
-    // ENSEMBLE, SOBOL: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
-    bool by_member() const { return kind == ENSEMBLE || kind == SOBOL; }
-    long members_before() const { return kind == SOBOL ? sob_blocks * (sob_params + 2) : ens_count; }
+    ReconDistribution dist; long dist_count = 0;               // DISTRIBUTION
+    // ENSEMBLE, SOBOL, DISTRIBUTION: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
+    bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION; }
+    long members_before() const { return kind == SOBOL ? sob_blocks * (sob_params + 2) : kind == DISTRIBUTION ? dist_count : ens_count; }
 };
 // The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass go
 // to e->colpart, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
-// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor does the Sobol pass.
+// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol and
+// the distribution pass.
 static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol"};
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist"};
     static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
                                            "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
-                                           "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)"};
+                                           "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)",
+                                           "sgv_distribution: the distribution pass rejected its arguments (%d)"};
     ScopedTimer tm(e, tag[g.kind], nullptr);
     int r = 0;
     switch (g.kind) {
@@ -918,6 +921,7 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
     case GenOut::SCORE: { ReconScore o = g.score; o.work = e->colpart; r = ew_recon_score(e->dt, p, g.scale, g.mn, g.truth, o, e->stream); break; }
     case GenOut::ENSEMBLE: r = ew_recon_ensemble(e->dt, p, g.scale, g.mn, g.ens_count, g.ens, e->stream); break;
     case GenOut::SOBOL: r = ew_recon_sobol(e->dt, p, g.scale, g.mn, g.sob_params, g.sob_blocks, g.sob, e->stream); break;
+    case GenOut::DISTRIBUTION: r = ew_recon_distribution(e->dt, p, g.scale, g.mn, g.dist_count, g.dist, e->stream); break;
     }
     return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
 }
@@ -1129,6 +1133,15 @@ int sgv_sobol(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch,
     GenOut gen = {GenOut::SOBOL, scale_dev, min_dev};
     gen.sob = recon_sobol_of(*st); gen.sob_params = n_params; gen.sob_blocks = blocks_before;
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_sobol", gen);
+}
+
+int sgv_distribution(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                     const float* min_dev, long count_before, const sgv_distribution_state* st) {
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_distribution: null argument");
+    CHK(distribution_state_ok("sgv_distribution", "batch", st, count_before, batch));
+    GenOut gen = {GenOut::DISTRIBUTION, scale_dev, min_dev};
+    gen.dist = recon_distribution_of(*st); gen.dist_count = count_before;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_distribution", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

@@ -289,7 +289,23 @@ static inline ReconEnsemble recon_ensemble_of(const sgv_ensemble_state& st) {
     r.limit = st.limit; r.exceed = st.exceed;
     return r;
 }
-constexpr int SGV_SOBOL_MAX_PARAMS = 30;      // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
+constexpr int SGV_DISTRIBUTION_MIN_BINS = 2, SGV_DISTRIBUTION_MAX_BINS = 64;      // HI_MIN_BINS, HI_MAX_BINS of recon_out.hip: the block's byte histogram fits the LDS
+static inline int distribution_state_ok(const char* who, const char* batch_name, const sgv_distribution_state* st, long count_before, int batch) {
+    if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (!st->lo || !st->hi || !st->counts) return fail(SGV_ERR_ARG, "%s: lo, hi and counts are all required", who);
+    if (st->bins < SGV_DISTRIBUTION_MIN_BINS || st->bins > SGV_DISTRIBUTION_MAX_BINS)
+        return fail(SGV_ERR_ARG, "%s: bins = %d is outside [%d, %d]", who, st->bins, SGV_DISTRIBUTION_MIN_BINS, SGV_DISTRIBUTION_MAX_BINS);
+    if (((uintptr_t)st->lo | (uintptr_t)st->hi | (uintptr_t)st->counts) & 15) return fail(SGV_ERR_ARG, "%s: misaligned pointer (lo, hi and counts 16 bytes)", who);
+    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
+        return fail(SGV_ERR_ARG, "%s: count_before = %ld with %s = %d is outside [0, 2^24]", who, count_before, batch_name, batch);
+    return 0;
+}
+static inline ReconDistribution recon_distribution_of(const sgv_distribution_state& st) {
+    ReconDistribution r;
+    r.lo = st.lo; r.hi = st.hi; r.counts = st.counts; r.bins = st.bins;
+    return r;
+}
+constexpr int SGV_SOBOL_MAX_PARAMS = 30;     // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
 static inline int sobol_state_ok(const char* who, const char* batch_name, const sgv_sobol_state* st, int n_params, long blocks_before, int batch) {
     if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
     if (!st->mean || !st->m2) return fail(SGV_ERR_ARG, "%s: mean and m2 are required", who);

@@ -1,6 +1,7 @@
 // The recon tails (gfx950): passes that replace the loss tail of the recon head in surrogate use -- the physical-unit field
 // (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
-// members of an ensemble (sgv_ensemble) and the running sums of a Sobol sensitivity study (sgv_sobol).  All of them stream y = the recon head's convolution output once, form the same value per
+// members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol) and the histogram of the members
+// between given bounds (sgv_distribution).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -889,6 +890,153 @@ int ew_recon_sobol(int dtype, GNParams p, const float* scale, const float* mn, i
                                ps, q, o, n_params, nbl, bb);
         };
         recon_dispatch(launch, dtype, o.first_sq != nullptr, o.total_sq != nullptr);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate distributions (sgv_distribution): the histogram of the members per (t, n), between bounds lo / hi [T][C] the caller gives
+// (the envelope an extrema pass of sgv_ensemble found over the same members).  With x the value recon_phys_val gives for a member and
+// K bins, all fp32 and every operation rounded on its own:
+//   invw = hi > lo ? (float)K / (hi - lo) : 0.0f              (one subtraction, one correctly rounded division)
+//   row  = x < lo ? 0 : x > hi ? K + 1 : 1 + min((int)((x - lo) * invw), K - 1)
+//   counts[row][t][n] += 1                                    (int32 [K + 2][T][C]: underflow, the K bins, overflow)
+// The pass only adds: integer counts are exact and independent of order, so any cut of the members into launches gives the same bits
+// and there is no "state not read" mode -- a new state is zeroed by the caller.
+// Geometry, ownership, the member table and the group lookup are recon_ensemble_kernel's: a thread owns its (t, octet) for all members,
+// no reduction across threads, no atomics, no workspace.  The bin index depends on the data, so counters in registers would be indexed
+// dynamically and end in scratch; they live in LDS instead, one byte per (row, thread, channel) -- a launch holds at most EN_MAX_B = 32
+// members.  Layout [K + 2][2][256] dwords: dword (row, h, tid) holds the bytes of channels 4 h .. 4 h + 3 of thread tid, so the 32
+// lanes the LDS serves per cycle touch 32 different banks whatever their rows are (a row is 512 dwords).  With the 8 bytes of a thread
+// side by side, lanes l and l + 16 of every such group would share a bank.  (K + 2) * 2 KiB of dynamic LDS per block: 68 KiB at K = 32
+// (two blocks per CU), 132 KiB at K = 64 (one).
+// Per row t: the launch's members are counted into the thread's own bytes -- the 8 bytes of a member are read, then written, and the
+// LDS serves a wave's operations in order, so the next member sees them -- then the rows of the state are flushed HI_FLIGHT at a
+// time: the thread's two dwords of each are read, and where one is not zero the 32-byte octet of counts is loaded, the bytes are added,
+// the octet is stored and the dwords are zeroed again.  Rows without an increment cost no global traffic.
+// ------------------------------------------------------------------------------------------
+constexpr int HI_MIN_BINS = 2, HI_MAX_BINS = 64;
+constexpr int HI_FLIGHT = 4;          // rows of the state whose octets are loaded before the first is used
+constexpr int HI_ROW_DWORDS = 512;    // one row of the block's byte histogram: [2][256] dwords
+static size_t hist_lds_bytes(int bins) { return (size_t)(bins + 2) * HI_ROW_DWORDS * 4; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void recon_hist_kernel(const GNParams p, const ReconPhys q, const ReconDistribution o) {
+    extern __shared__ unsigned int hist_lds[];                   // [K + 2][2][256]
+    __shared__ float2 tab[EN_MAX_B][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of member b
+    const int K = o.bins, tid = threadIdx.x;
+    member_table_fill(p, tab);
+    for (int r = 0; r < K + 2; ++r) { hist_lds[r * HI_ROW_DWORDS + tid] = 0u; hist_lds[r * HI_ROW_DWORDS + 256 + tid] = 0u; }
+    __syncthreads();
+    const GNCtx c = gn_ctx(p);          // blockIdx.z == 0; c.b is not a member here
+    if (!c.col_ok) return;              // no barrier below: lanes past C touch nothing
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const OctetGroups og = octet_groups(p, c.c0);
+    const T* y = reinterpret_cast<const T*>(p.y);
+    unsigned int* const mine = hist_lds + tid;                                        // dword (row, h): mine[row * HI_ROW_DWORDS + 256 h]
+    unsigned char* const mine_b = reinterpret_cast<unsigned char*>(mine);             // byte of channel e in row 0: mine_b[1024 (e / 4) + e % 4]
+    const long TC = (long)p.T * p.C;
+    const float fK = (float)K, fKm1 = (float)(K - 1);
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += c.RL) {
+        const long at = (long)t * p.C + c.c0;
+        float lo[8], hi[8], invw[8];
+        load8(o.lo + at, lo); load8(o.hi + at, hi);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)
+            invw[e] = hi[e] > lo[e] ? fK / (hi[e] - lo[e]) : 0.0f;
+        }
+        for (int b0 = 0; b0 < p.B; b0 += EN_FLIGHT) {          // EN_FLIGHT members per round, loads first
+            Raw8<T> r[EN_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < EN_FLIGHT; ++u)                  // past the last member: its row again, loaded and not used
+                raw_load(y + ((long)min(b0 + u, p.B - 1) * p.T + t) * p.ldy + c.c0, r[u]);
+#pragma unroll
+            for (int u = 0; u < EN_FLIGHT; ++u) {
+                const int b = b0 + u;
+                if (b >= p.B) break;
+                float v[8], gm[8], gr[8];
+                raw_unpack(r[u], v);
+                octet_mean_rstd(tab, b, og, gm, gr);
+                int off[8];          // the byte of (row, channel e), from mine_b
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // x is the stored value; the difference and the product round one after the other (no fused multiply-add)
+#pragma clang fp contract(off)
+                    const float x = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
+                    const float s = (x - lo[e]) * invw[e];
+                    // s >= 0 wherever the rule is defined, and there min((int)s, K - 1) == (int)min(s, K - 1); clamped as a float, a NaN
+                    // or a range turned round still gives a row of the block's histogram
+                    const int j = (int)fminf(fmaxf(s, 0.0f), fKm1);
+                    const int row = x < lo[e] ? 0 : x > hi[e] ? K + 1 : 1 + j;
+                    off[e] = row * (HI_ROW_DWORDS * 4) + (e >> 2) * 1024 + (e & 3);
+                }
+                unsigned char n[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) n[e] = mine_b[off[e]];          // 8 different bytes: channel e has its own
+#pragma unroll
+                for (int e = 0; e < 8; ++e) mine_b[off[e]] = (unsigned char)(n[e] + 1);
+            }
+        }
+        for (int r0 = 0; r0 < K + 2; r0 += HI_FLIGHT) {          // HI_FLIGHT rows of the state per round, loads first
+            unsigned int w0[HI_FLIGHT], w1[HI_FLIGHT];
+            int cnt[HI_FLIGHT][8];
+#pragma unroll
+            for (int u = 0; u < HI_FLIGHT; ++u) {
+                const bool in = r0 + u < K + 2;
+                w0[u] = in ? mine[(r0 + u) * HI_ROW_DWORDS] : 0u;
+                w1[u] = in ? mine[(r0 + u) * HI_ROW_DWORDS + 256] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < HI_FLIGHT; ++u)
+                if (w0[u] | w1[u]) load8(o.counts + (long)(r0 + u) * TC + at, cnt[u]);
+#pragma unroll
+            for (int u = 0; u < HI_FLIGHT; ++u) {
+                if (!(w0[u] | w1[u])) continue;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) cnt[u][e] += (int)(((e < 4 ? w0[u] : w1[u]) >> (8 * (e & 3))) & 0xffu);
+                store8(o.counts + (long)(r0 + u) * TC + at, cnt[u]);
+                mine[(r0 + u) * HI_ROW_DWORDS] = 0u;
+                mine[(r0 + u) * HI_ROW_DWORDS + 256] = 0u;
+            }
+        }
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconDistribution (sgv_ew.h), all of lo, hi, counts; count_before members are
+// already in the state, which bounds the study and nothing else.  A batch of more than EN_MAX_B members goes out as several launches
+// (a counter of a launch fits a byte), which is bitwise the same.  Non-zero (nothing launched): -1 null input, -2 lo, hi or counts
+// missing, -3 bad shape or bins outside [2, 64], -4 y, lo, hi or counts not 16-byte aligned, -5 count_before < 0 or
+// count_before + B > 2^24, -6 the kernel's dynamic LDS limit could not be raised
+int ew_recon_distribution(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconDistribution& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.lo || !o.hi || !o.counts) return -2;
+    if (o.bins < HI_MIN_BINS || o.bins > HI_MAX_BINS) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.lo | (uintptr_t)o.hi | (uintptr_t)o.counts) & 15) return -4;
+    if (count_before < 0 || count_before + p.B > (1L << 24)) return -5;
+    // more than 64 KiB of dynamic LDS has to be asked for, once per kernel
+    static bool raised[2] = {false, false};
+    if (!raised[dtype == 1]) {
+        const void* fn = dtype == 1 ? reinterpret_cast<const void*>(&recon_hist_kernel<bf16_t>) : reinterpret_cast<const void*>(&recon_hist_kernel<float>);
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds_bytes(HI_MAX_BINS)) != hipSuccess) return -6;
+        raised[dtype == 1] = true;
+    }
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const RSGeom g = rs_geom(p.C);
+    const int RL = 256 / g.CV;
+    const int rowchunks = std::max(1, std::min(cdiv_i(p.T, RL), cdiv_i(2048, g.colblocks)));      // as ew_recon_ensemble
+    const dim3 grid(g.colblocks, rowchunks, 1);
+    const int B = p.B;
+    const size_t esz = dtype == 1 ? 2 : 4, lds = hist_lds_bytes(o.bins);
+    for (int b0 = 0; b0 < B; b0 += EN_MAX_B) {
+        GNParams ps = p;
+        ps.B = std::min(EN_MAX_B, B - b0);
+        ps.y = (const char*)p.y + (size_t)b0 * p.T * p.ldy * esz;
+        ps.sums = p.sums + (size_t)b0 * p.G * 2;
+        auto launch = [&](auto el, auto) { hipLaunchKernelGGL((recon_hist_kernel<typename decltype(el)::type>), grid, dim3(256), lds, s, ps, q, o); };
+        recon_dispatch(launch, dtype, true);
     }
     return 0;
 }

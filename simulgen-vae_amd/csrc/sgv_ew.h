@@ -163,6 +163,18 @@ struct ReconSobol {
     float* first_sq = nullptr; float* total_sq = nullptr;
 };
 int ew_recon_sobol(int dtype, GNParams p, const float* scale, const float* mn, int n_params, long blocks_before, const ReconSobol& o, hipStream_t s);
+// recon head -> a histogram over the members of a batch (and of the batches before it) per (t, channel), the field never stored.  x is
+// the value ew_recon_physical would store (layout [B][T][C]), K = bins in [2, 64], lo and hi fp32 [T][C] (inputs), counts int32
+// [K + 2][T][C]: row 0 underflow, rows 1 .. K the bins, row K + 1 overflow; every array dense and 16-byte aligned.  All fp32, every
+// operation rounded on its own:
+//   invw = hi > lo ? (float)K / (hi - lo) : 0.0f
+//   row  = x < lo ? 0 : x > hi ? K + 1 : 1 + min((int)((x - lo) * invw), K - 1);   counts[row][t][c] += 1
+// The pass only adds to counts (there is no "state not read" mode: the caller zeroes a new state), so any cut of the same members
+// into launches gives the same bits; count_before only bounds the size of the study.
+struct ReconDistribution {
+    const float* lo = nullptr; const float* hi = nullptr; int* counts = nullptr; int bins = 0;
+};
+int ew_recon_distribution(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconDistribution& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

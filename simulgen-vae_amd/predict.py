@@ -26,6 +26,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     sens = s.sobol(A, B)                           # which input drives the response, where and when: sens.first_order() and
                                                    # sens.total_order() [F, T, N], Sobol indices by Jansen's estimators (DESIGN.md
                                                    # section 20); (2 + 2 F) running arrays [T, N] instead of n (F + 2) fields
+    env = s.ensemble(draws, want=("extrema",), mode="random")       # percentile bands of a Monte-Carlo study in two passes: the
+    dist = s.distribution(draws, env, bins=32, mode="random")       # envelope, then a histogram between it per (time step, node);
+    p5, p50, p95 = dist.quantile([0.05, 0.5, 0.95])                 # integer counts [bins + 2, T, N] instead of the fields and a
+                                                   # sort over them
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ import pickle
 
 import numpy as np
 
-from .engine import ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_PROBES, SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of
+from .engine import DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_PROBES, SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
 FILES = {"vae": "SimulGen-VAE", "conditioner": "LatentConditioner", "data_scaler": "scaler.pkl",
@@ -231,6 +235,138 @@ class EnsembleResult(_RunningResult):
         if self.count < 1:
             raise ValueError("exceed_fraction: the ensemble is empty")
         return self._on_stream(lambda: self.exceed.float() / float(self.count))
+
+
+def _is_device_tensor(v):
+    """a CUDA tensor, judged by its attributes alone (numpy only: torch is not imported for the question)"""
+    return hasattr(v, "data_ptr") and getattr(getattr(v, "device", None), "type", None) == "cuda"
+
+
+def hist_range(range, T, N):
+    """The bounds of Surrogate.distribution as (lo, hi), each [T, N] float32 in physical units.  `range` is an EnsembleResult that
+    holds the extrema (its min and max tensors are returned as they are), or a pair (lo, hi) of scalars (every time step and
+    node), of 1-D arrays of N entries (node by node, every time step) or of [T, N] arrays -- host forms, which come back as new
+    numpy arrays -- or a pair of float32 CUDA tensors [T, N], which are returned as they are after a look at shape and dtype
+    (their values are not read).  ValueError naming the problem otherwise: not a pair, a rank above 2 or a length other than N /
+    a shape other than [T, N], an entry that is not finite as float32, or hi < lo (the first offender is named).  numpy only."""
+    T, N = int(T), int(N)
+    if isinstance(range, EnsembleResult):
+        if range.min is None or range.max is None:
+            raise ValueError("range: the EnsembleResult does not hold the extrema (want=('extrema',))")
+        pair, names = (range.min, range.max), ("range.min", "range.max")
+    else:
+        if not isinstance(range, (tuple, list)) or len(range) != 2:
+            raise ValueError("range: an EnsembleResult with the extrema or a pair (lo, hi) is required")
+        pair, names = tuple(range), ("lo", "hi")
+    if any(_is_device_tensor(v) for v in pair):
+        for name, v in zip(names, pair):
+            if not _is_device_tensor(v):
+                raise ValueError(f"range: {name} is not a CUDA tensor, but the other bound is one")
+            shape = tuple(int(d) for d in v.shape)
+            if shape != (T, N):
+                raise ValueError(f"range: {name} has shape {shape}, expected [T, N] = {[T, N]}")
+            if str(v.dtype).replace("torch.", "") != "float32":
+                raise ValueError(f"range: {name}: dtype float32 is required, not {v.dtype}")
+            if hasattr(v, "is_contiguous") and not v.is_contiguous():
+                raise ValueError(f"range: {name} must be contiguous")
+        return pair
+    out = []
+    for name, v in zip(names, pair):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim > 2:
+            raise ValueError(f"range: {name}: a scalar, a 1-D array of N = {N} entries or a [T, N] = {[T, N]} array is required, got shape {a.shape}")
+        if a.ndim == 1 and a.size != N:
+            raise ValueError(f"range: {name}: {a.size} entries, expected N = {N} (or a scalar, or [T, N])")
+        if a.ndim == 2 and a.shape != (T, N):
+            raise ValueError(f"range: {name} has shape {a.shape}, expected [T, N] = {[T, N]}")
+        with np.errstate(over="ignore"):          # a value beyond float32 becomes inf and is reported below
+            v32 = np.broadcast_to(a.astype(np.float32), (T, N))
+        bad = np.argwhere(~np.isfinite(v32))
+        if bad.size:
+            i = tuple(int(k) for k in bad[0])
+            where = {0: name, 1: f"{name}[{i[1]}]", 2: f"{name}[{i[0]}, {i[1]}]"}[a.ndim]
+            raise ValueError(f"range: {where} = {float(np.broadcast_to(a, (T, N))[i])!r} is not finite as float32")
+        out.append(np.array(v32, order="C"))          # a dense copy: the broadcast view is read-only and has strides of 0
+    lo, hi = out
+    bad = np.argwhere(hi < lo)
+    if bad.size:
+        t, n = (int(k) for k in bad[0])
+        raise ValueError(f"range: hi < lo at [t, n] = [{t}, {n}]: lo = {float(lo[t, n])!r}, hi = {float(hi[t, n])!r}")
+    return lo, hi
+
+
+def quantile_rank(q, count):
+    """r = max(ceil(q count), 1): the q-quantile of `count` values is the r-th smallest (the empirical distribution function's
+    inverse), 0 < q <= 1"""
+    return max(int(np.ceil(np.float64(q) * int(count))), 1)
+
+
+class DistributionResult(_RunningResult):
+    """Surrogate.distribution's result: the histogram of `count` members per (time step, node) in `bins` uniform bins between lo and
+    hi, device tensors.  counts int32 [bins + 2, T, N] IS the running state (pass the result back as `into=` to go on counting):
+    row 0 the members below lo, rows 1 .. bins the bins, row bins + 1 the members above hi; every column sums to count.  lo, hi
+    fp32 [T, N] are the bounds the call was given (the tensors of the EnsembleResult, if it was one)."""
+    FIELDS = ("count", "bins", "lo", "hi", "counts")
+    STATE = ("lo", "hi", "counts")
+    CHUNK = 1 << 26          # elements of counts quantile() looks at in one piece: its temporaries take a few times 4 bytes each
+
+    @property
+    def under(self):
+        """counts[0] [T, N] int32 (a view): members below lo"""
+        return self.counts[0]
+
+    @property
+    def over(self):
+        """counts[bins + 1] [T, N] int32 (a view): members above hi"""
+        return self.counts[self.bins + 1]
+
+    def fractions(self):
+        """counts[1 : bins + 1] / count [bins, T, N] fp32: the share of the members in each bin"""
+        if self.count < 1:
+            raise ValueError("fractions: the distribution is empty")
+        return self._on_stream(lambda: self.counts[1:self.bins + 1].float() / float(self.count))
+
+    def quantile(self, q):
+        """The q-quantile per (time step, node), fp32 [T, N] for a scalar q and [Q, T, N] for a sequence, 0 < q <= 1: with
+        r = max(ceil(q count), 1) and j the first row of counts at which the running sum over the rows reaches r, lo for j = 0, hi
+        for j = bins + 1 and otherwise lo + (j - 1 + (r - sum below row j) / counts[j]) (hi - lo) / bins, never above hi -- the r-th
+        smallest member is in bin j, and the members of a bin are taken as evenly spread over it, so the result is within one bin
+        width (hi - lo) / bins of that member.  Computed on the engine stream in torch, in pieces along T of at most CHUNK counts."""
+        if self.count < 1:
+            raise ValueError("quantile: the distribution is empty")
+        qs = np.asarray(q, dtype=np.float64)
+        if qs.ndim > 1 or qs.size < 1:
+            raise ValueError(f"quantile: q must be a scalar or a non-empty 1-D sequence, got shape {qs.shape}")
+        bad = np.flatnonzero(~((qs.reshape(-1) > 0.0) & (qs.reshape(-1) <= 1.0)))
+        if bad.size:
+            raise ValueError(f"quantile: q = {float(qs.reshape(-1)[bad[0]])!r} is outside (0, 1]")
+        ranks = [quantile_rank(v, self.count) for v in qs.reshape(-1)]
+        K = int(self.bins)
+
+        def run():
+            import torch
+            T, N = self.lo.shape
+            out = torch.empty((len(ranks), T, N), dtype=torch.float32, device=self.lo.device)
+            step = max(1, self.CHUNK // ((K + 2) * N))
+            fK = torch.full((), float(K), dtype=torch.float32, device=self.lo.device)          # a tensor: a true division, not a product with 1 / K
+            for t0 in range(0, T, step):
+                c = self.counts[:, t0:t0 + step]
+                lo, hi = self.lo[t0:t0 + step], self.hi[t0:t0 + step]
+                cum = c.cumsum(0, dtype=torch.int32)          # at most 2^24 members
+                for i, r in enumerate(ranks):
+                    j = (cum < r).sum(0).clamp_(max=K + 1)    # the first row whose running sum reaches r
+                    below = torch.where(j > 0, cum.gather(0, (j - 1).clamp_(min=0)[None])[0], 0)
+                    inside = c.gather(0, j[None])[0]
+                    pos = (j - 1).float() + (r - below).float() / inside.float()
+                    v = torch.minimum(lo + pos * (hi - lo) / fK, hi)
+                    out[i, t0:t0 + step] = torch.where(j == 0, lo, torch.where(j == K + 1, hi, v))
+            return out
+        res = self._on_stream(run)
+        return res[0] if qs.ndim == 0 else res
+
+    def median(self):
+        """quantile(0.5)"""
+        return self.quantile(0.5)
 
 
 def sobol_groups(groups, F):
@@ -589,6 +725,47 @@ class Surrogate:
             for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
                 self.eng.ensemble(lat, xs, self.data_scale, self.data_min, state, count + lo, fix=mode == "fix")
         return EnsembleResult(stream=self._stream, count=count + P, **{k: state.get(k) for k in EnsembleResult.FIELDS if k != "count"})
+
+    def distribution(self, conditions, range, bins=32, mode="fix", into=None):
+        """The empirical distribution of the fields of all `conditions` per (time step, node), without the fields: percentile bands
+        (result.quantile([0.05, 0.5, 0.95])) and the histogram behind them -> a DistributionResult of device tensors.  The second
+        pass of a study: range gives the bounds between which `bins` uniform bins lie (DISTRIBUTION_MIN_BINS <= bins <=
+        DISTRIBUTION_MAX_BINS), normally the EnsembleResult of ensemble(conditions, want=("extrema",), mode=mode) on the same seed,
+        whose min / max tensors are used as they are, without a copy; or a pair (lo, hi) of scalars, of [N] arrays or of [T, N]
+        arrays or CUDA tensors in physical units (hist_range).  The decoder's noise of a draw follows its index, as in ensemble(),
+        so this pass regenerates the fields of the first one bit for bit and no draw falls outside its envelope: result.under and
+        result.over are zero, in mode "random" too.  The recon head's last pass bins the values predict() would store and adds to
+        result.counts, which is the running state: integer counts, exact and independent of order and batch size.  A value equal
+        to hi is in the last bin; where hi == lo every value equal to them is in the first.  into: an earlier result to go on
+        counting into (same bins, same bounds; its counts are updated and returned in a new result with the larger count): equal
+        to one call on the concatenated conditions, bit for bit.  Batching, streams, the single input-range decision and `mode`
+        are ensemble()'s: no host wait between batches, the last batch may be ragged."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        K = int(bins)
+        if K != bins or K < DISTRIBUTION_MIN_BINS or K > DISTRIBUTION_MAX_BINS:
+            raise ValueError(f"bins = {bins!r} is outside [{DISTRIBUTION_MIN_BINS}, {DISTRIBUTION_MAX_BINS}]")
+        lo, hi = hist_range(range, self.T, self.N)
+        spec = {"lo": ((self.T, self.N), t.float32), "hi": ((self.T, self.N), t.float32), "counts": ((K + 2, self.T, self.N), t.int32)}
+        state, count = None, 0
+        if into is not None:
+            DistributionResult.require(into)
+            if int(into.bins) != K:
+                raise ValueError(f"into holds {into.bins} bins, this call asks for {K}")
+            state, count = into.continued(spec)
+            for name, v in (("lo", lo), ("hi", hi)):
+                same = v is state[name] or (t.equal(v, state[name]) if t.is_tensor(v) else np.array_equal(state[name].cpu().numpy(), v))
+                if not same:
+                    raise ValueError(f"into was counted between other bounds ({name} differs)")
+        if count + P > ENSEMBLE_MAX_COUNT:
+            raise ValueError(f"{count} + {P} members: a distribution holds at most 2^24")
+        with _engine_stream(self._stream):
+            if state is None:
+                state = {"lo": lo if t.is_tensor(lo) else t.from_numpy(lo).cuda(), "hi": hi if t.is_tensor(hi) else t.from_numpy(hi).cuda(),
+                         "counts": t.zeros(spec["counts"][0], dtype=t.int32, device="cuda")}          # the pass only ever adds
+            for b_lo, b_hi, lat, xs in self._latent_batches(conditions, P, remap):
+                self.eng.distribution(lat, xs, self.data_scale, self.data_min, state, count + b_lo, fix=mode == "fix")
+        return DistributionResult(stream=self._stream, count=count + P, bins=K, lo=state["lo"], hi=state["hi"], counts=state["counts"])
 
     def sobol(self, A, B, groups=None, want=("first", "total"), into=None):
         """Variance-based global sensitivity of the response to its inputs per (time step, node), without the fields: which

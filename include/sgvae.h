@@ -310,6 +310,25 @@ typedef struct { const float* lo; const float* hi; int32_t* counts; int bins; } 
  * pass to read from, as after sgv_generate. */
 int sgv_distribution(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                      const float* min_dev, long count_before, const sgv_distribution_state* st);
+/* The running state of a linear response surface of the field on K = n_cov covariates per member, 1 <= K <= 32, per (time step,
+ * node).  Device pointers, dense, 16-byte aligned: mean, m2 fp32 [T][N] (Welford, exactly the moments of sgv_ensemble_state);
+ * comoment fp32 [K][T][N]: sum over the members of (x - xbar)(y_i - ybar_i), x the field and y_i covariate i.  All three are
+ * required.  The state belongs to the caller and persists across calls: the kernel reads, updates and writes it in place. */
+typedef struct { float* mean; float* m2; float* comoment; } sgv_regress_state;
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the regression pass: sample b of the
+ * batch is member m = count_before + b, k = m + 1, and with x the value sgv_generate would store for it (SGV_LAYOUT_TN), members
+ * in ascending order, all in fp32 and every operation rounded on its own,
+ *   d = x - mean;  mean = mean + d * (1.0f / (float)k);  m2 = m2 + d * (x - mean);  comoment[i] = comoment[i] + d * w[b][i]
+ * for i = 0 .. n_cov - 1.  weights_dev, fp32 [batch][n_cov] on the device (4-byte aligned), are the centred covariates, which the
+ * caller forms member by member in float64: ybar = ybar + (y_m - ybar) / k, w[b][:] = (float)(y_m - ybar), the running mean
+ * including member m (the updating identity C_n = C_n-1 + (x_n - xbar_n-1)(y_n - ybar_n)).  With count_before == 0 the state is
+ * not read: it starts empty.  Any cut of the same members into calls gives the same bits, the decoder's noise included: it follows
+ * the member index by the mechanism of sgv_ensemble, and the draw position is left where it is.  No atomics, no workspace, nothing
+ * allocated.  SGV_ERR_ARG before anything is enqueued: e, z_dev, scale_dev, min_dev, weights_dev or st NULL, mean, m2 or comoment
+ * NULL, n_cov outside [1, 32], a misaligned pointer, count_before < 0 or count_before + batch > 2^24, the checks of sgv_decode.
+ * Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
+int sgv_regress(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                const float* min_dev, int n_cov, const float* weights_dev, long count_before, const sgv_regress_state* st);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -606,6 +625,13 @@ int sgv_test_recon_sobol(int dtype, const void* y, long ldy, double* sums, const
 int sgv_test_recon_distribution(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                                 const float* scale, const float* min, long count_before, const sgv_distribution_state* st, int B,
                                 int T, int C, void* stream);
+/* The kernel of sgv_regress on caller-owned buffers: inputs as sgv_test_recon_physical, weights fp32 [B][n_cov] on the device, then
+ * the statistics of y and the regression pass into *st (shapes of sgv_regress_state with N = C).  SGV_ERR_ARG, nothing launched: a
+ * NULL input (weights included), st NULL, mean, m2 or comoment NULL, n_cov outside [1, 32], B or T < 1, C < 8 or C % 8 != 0, a bad
+ * row stride, a misaligned pointer (y and the state arrays 16 bytes; weights 4), count_before < 0 or count_before + B > 2^24. */
+int sgv_test_recon_regress(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                           const float* scale, const float* min, int n_cov, const float* weights, long count_before,
+                           const sgv_regress_state* st, int B, int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

@@ -889,9 +889,10 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 
 // What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
 // (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble), the sums of a Sobol study
-// (sgv_sobol) or the histogram of the members (sgv_distribution); only the members of `kind` are read.
+// (sgv_sobol), the histogram of the members (sgv_distribution) or their co-moments with the covariates (sgv_regress); only the members of
+// `kind` are read.
 struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION } kind;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS } kind;
     const float* scale; const float* mn;
     int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
     ReconSummary sum;                                          // SUMMARY
@@ -899,20 +900,24 @@ struct GenOut {
     ReconEnsemble ens; long ens_count = 0;                     // ENSEMBLE
     ReconSobol sob; int sob_params = 0; long sob_blocks = 0;   // SOBOL
     ReconDistribution dist; long dist_count = 0;               // DISTRIBUTION
-    // ENSEMBLE, SOBOL, DISTRIBUTION: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
-    bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION; }
-    long members_before() const { return kind == SOBOL ? sob_blocks * (sob_params + 2) : kind == DISTRIBUTION ? dist_count : ens_count; }
+    ReconRegress reg; int reg_cov = 0; long reg_count = 0;     // REGRESS
+    // ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
+    bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION || kind == REGRESS; }
+    long members_before() const {
+        return kind == SOBOL ? sob_blocks * (sob_params + 2) : kind == DISTRIBUTION ? dist_count : kind == REGRESS ? reg_count : ens_count;
+    }
 };
 // The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass go
 // to e->colpart, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
-// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol and
-// the distribution pass.
+// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol, the
+// distribution and the regression pass.
 static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist"};
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress"};
     static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
                                            "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
                                            "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)",
-                                           "sgv_distribution: the distribution pass rejected its arguments (%d)"};
+                                           "sgv_distribution: the distribution pass rejected its arguments (%d)",
+                                           "sgv_regress: the regression pass rejected its arguments (%d)"};
     ScopedTimer tm(e, tag[g.kind], nullptr);
     int r = 0;
     switch (g.kind) {
@@ -922,6 +927,7 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
     case GenOut::ENSEMBLE: r = ew_recon_ensemble(e->dt, p, g.scale, g.mn, g.ens_count, g.ens, e->stream); break;
     case GenOut::SOBOL: r = ew_recon_sobol(e->dt, p, g.scale, g.mn, g.sob_params, g.sob_blocks, g.sob, e->stream); break;
     case GenOut::DISTRIBUTION: r = ew_recon_distribution(e->dt, p, g.scale, g.mn, g.dist_count, g.dist, e->stream); break;
+    case GenOut::REGRESS: r = ew_recon_regress(e->dt, p, g.scale, g.mn, g.reg_cov, g.reg_count, g.reg, e->stream); break;
     }
     return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
 }
@@ -1142,6 +1148,15 @@ int sgv_distribution(sgv_engine* e, const float* z_dev, const float* xs_dev, int
     GenOut gen = {GenOut::DISTRIBUTION, scale_dev, min_dev};
     gen.dist = recon_distribution_of(*st); gen.dist_count = count_before;
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_distribution", gen);
+}
+
+int sgv_regress(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                const float* min_dev, int n_cov, const float* weights_dev, long count_before, const sgv_regress_state* st) {
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_regress: null argument");
+    CHK(regress_state_ok("sgv_regress", "batch", st, n_cov, weights_dev, count_before, batch));
+    GenOut gen = {GenOut::REGRESS, scale_dev, min_dev};
+    gen.reg = recon_regress_of(*st, weights_dev); gen.reg_cov = n_cov; gen.reg_count = count_before;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_regress", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

@@ -305,7 +305,24 @@ static inline ReconDistribution recon_distribution_of(const sgv_distribution_sta
     r.lo = st.lo; r.hi = st.hi; r.counts = st.counts; r.bins = st.bins;
     return r;
 }
-constexpr int SGV_SOBOL_MAX_PARAMS = 30;     // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
+constexpr int SGV_REGRESS_MAX_COVARIATES = 32;      // RG_MAX_K of recon_out.hip: the launch's weights fit the block's LDS table
+static inline int regress_state_ok(const char* who, const char* batch_name, const sgv_regress_state* st, int n_cov, const float* weights, long count_before,
+                                   int batch) {
+    if (!st || !weights) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (!st->mean || !st->m2 || !st->comoment) return fail(SGV_ERR_ARG, "%s: mean, m2 and comoment are all required", who);
+    if (n_cov < 1 || n_cov > SGV_REGRESS_MAX_COVARIATES) return fail(SGV_ERR_ARG, "%s: n_cov = %d is outside [1, %d]", who, n_cov, SGV_REGRESS_MAX_COVARIATES);
+    if ((((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->comoment) & 15) || ((uintptr_t)weights & 3))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (the state arrays 16 bytes, weights 4)", who);
+    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
+        return fail(SGV_ERR_ARG, "%s: count_before = %ld with %s = %d is outside [0, 2^24]", who, count_before, batch_name, batch);
+    return 0;
+}
+static inline ReconRegress recon_regress_of(const sgv_regress_state& st, const float* weights) {
+    ReconRegress r;
+    r.mean = st.mean; r.m2 = st.m2; r.co = st.comoment; r.w = weights;
+    return r;
+}
+constexpr int SGV_SOBOL_MAX_PARAMS = 30;    // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
 static inline int sobol_state_ok(const char* who, const char* batch_name, const sgv_sobol_state* st, int n_params, long blocks_before, int batch) {
     if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
     if (!st->mean || !st->m2) return fail(SGV_ERR_ARG, "%s: mean and m2 are required", who);

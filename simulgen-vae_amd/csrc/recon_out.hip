@@ -1,7 +1,7 @@
 // The recon tails (gfx950): passes that replace the loss tail of the recon head in surrogate use -- the physical-unit field
 // (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
-// members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol) and the histogram of the members
-// between given bounds (sgv_distribution).  All of them stream y = the recon head's convolution output once, form the same value per
+// members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol), the histogram of the members
+// between given bounds (sgv_distribution) and the co-moments of the members with their covariates (sgv_regress).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -1036,6 +1036,156 @@ int ew_recon_distribution(int dtype, GNParams p, const float* scale, const float
         ps.y = (const char*)p.y + (size_t)b0 * p.T * p.ldy * esz;
         ps.sums = p.sums + (size_t)b0 * p.G * 2;
         auto launch = [&](auto el, auto) { hipLaunchKernelGGL((recon_hist_kernel<typename decltype(el)::type>), grid, dim3(256), lds, s, ps, q, o); };
+        recon_dispatch(launch, dtype, true);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate response surfaces (sgv_regress): the co-moments of the field with K covariates the caller has per member (the inputs of a
+// design study, or any scalar per draw), beside the moments of the ensemble pass.  The host centres the covariates -- w[m][i] =
+// float32(y_m,i - ybar_i), ybar the running mean including member m, in float64 -- and per (t, n), with x the value recon_phys_val gives
+// for member m, k = m + 1, all fp32 and every operation rounded on its own, members in ascending order:
+//   d = x - mean;  mean = mean + d * (1.0f / (float)k);  m2 = m2 + d * (x - mean)          (recon_ensemble_kernel's moments, bit for bit)
+//   co[i] = co[i] + d * w[m][i]      for i = 0 .. K - 1                                       (C_n = C_n-1 + (x_n - xbar_n-1)(y_n - ybar_n))
+// m counts from count_before; every update is sequential in m and the state is stored as it is held, so any cut of the same members
+// into launches gives the same bits.  With count_before == 0 the state is not read.
+// Geometry, ownership, the member table and the group lookup are recon_ensemble_kernel's: a thread owns its (t, octet) for all members,
+// no reduction across threads, no atomics, no workspace.  Loop order (recon_sobol_kernel's): Welford over the launch's members first,
+// each member's d[8] staying in registers, then covariate i's state row is streamed through once per launch -- load, update over the
+// members, store -- while the row of covariate i + 1 is already on its way.  The launch's weights [members][K] lie in LDS beside the
+// member table; every thread of the block reads the same word, a broadcast.
+// ------------------------------------------------------------------------------------------
+constexpr int RG_MAX_K = 32;          // covariates
+// members per launch: 8 VGPRs of d each.  Fewer members mean more passes over the (2 + K) state arrays per batch, more cost occupancy;
+// 16 measured faster than 8 in bf16, and fp32 takes the larger candidate without scratch
+template <typename T> constexpr int rg_members() { return sizeof(T) == 2 ? 16 : 8; }
+
+// f(integral_constant<b0>) for b0 = B0, B0 + STEP, .. while b0 < min(n, NM): the members of recon_regress_kernel, or rounds of them
+template <int B0, int NM, int STEP, typename F>
+__device__ __forceinline__ void rg_rounds(int n, F&& f) {
+    if constexpr (B0 < NM) {
+        if (B0 < n) {
+            f(std::integral_constant<int, B0>{});
+            rg_rounds<B0 + STEP, NM, STEP>(n, f);
+        }
+    }
+}
+
+// 2 waves / SIMD asked for: 243 VGPRs for bf16 with 16 members, 190 for fp32 with 8, neither with scratch.  bf16 with 8 members and 3 waves
+// asked for kept 28 bytes per lane in scratch and was slower.
+template <typename T, int NM>
+__global__ __launch_bounds__(256, 2) void recon_regress_kernel(const GNParams p, const ReconPhys q, const ReconRegress o, const int K, const int count_before) {
+    __shared__ float2 tab[NM][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of member b; p.B <= NM
+    __shared__ float rk[NM];                               // 1 / k, k = count_before + b + 1: one correctly rounded division per member
+    __shared__ float wl[NM * RG_MAX_K];                    // w[b][i] at wl[b * K + i]
+    member_table_fill(p, tab);
+    if ((int)threadIdx.x < p.B) rk[threadIdx.x] = 1.0f / (float)(count_before + (int)threadIdx.x + 1);
+    for (int i = threadIdx.x; i < p.B * K; i += 256) wl[i] = o.w[i];
+    __syncthreads();
+    const GNCtx c = gn_ctx(p);          // blockIdx.z == 0; c.b is not a member here
+    if (!c.col_ok) return;              // no barrier below: lanes past C touch nothing
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const OctetGroups og = octet_groups(p, c.c0);
+    const T* y = reinterpret_cast<const T*>(p.y);
+    const bool fresh = count_before == 0;
+    const long TC = (long)p.T * p.C;
+    for (int t = c.t_lo + c.ty; t < c.t_hi; t += c.RL) {
+        const long at = (long)t * p.C + c.c0;
+        float d[NM][8];          // x - mean before the member entered the mean
+        Raw8<float> cur;         // co[i] of this (t, octet)
+        raw_zero(cur);
+        {
+            float mean[8], m2[8];
+            if (fresh) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { mean[e] = 0.f; m2[e] = 0.f; }
+            } else { load8(o.mean + at, mean); load8(o.m2 + at, m2); }
+            // EN_FLIGHT members per round, loads first; the rounds are written out at compile time (rg_rounds), so that every index into d
+            // is a constant whatever the unroller decides: d must never be addressed dynamically
+            rg_rounds<0, NM, EN_FLIGHT>(p.B, [&](auto b0c) {
+                constexpr int b0 = decltype(b0c)::value;
+                Raw8<T> r[EN_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < EN_FLIGHT; ++u)                  // past the last member: its row again, loaded and not used
+                    raw_load(y + ((long)min(b0 + u, p.B - 1) * p.T + t) * p.ldy + c.c0, r[u]);
+#pragma unroll
+                for (int u = 0; u < EN_FLIGHT; ++u) {
+                    if (b0 + u >= p.B) break;
+                    const float rkb = rk[b0 + u];
+                    float v[8], gm[8], gr[8];
+                    raw_unpack(r[u], v);
+                    octet_mean_rstd(tab, b0 + u, og, gm, gr);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        // Welford, one member at a time; no fused multiply-add anywhere (see recon_ensemble_kernel)
+#pragma clang fp contract(off)
+                        const float x = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
+                        d[b0 + u][e] = x - mean[e];
+                        mean[e] = mean[e] + d[b0 + u][e] * rkb;
+                        m2[e] = m2[e] + d[b0 + u][e] * (x - mean[e]);
+                    }
+                }
+            });
+            if (!fresh) raw_load(o.co + at, cur);          // covariate 0, on its way while the moments go out
+            store8(o.mean + at, mean); store8(o.m2 + at, m2);
+        }
+        for (int i = 0; i < K; ++i) {
+            const long ai = (long)i * TC + at;
+            Raw8<float> nxt;         // covariate i + 1 (after the last one: its row again, loaded and not used)
+            raw_zero(nxt);
+            if (!fresh) raw_load(o.co + (long)min(i + 1, K - 1) * TC + at, nxt);
+            float co[8];
+            raw_unpack(cur, co);
+            rg_rounds<0, NM, 1>(p.B, [&](auto bc) {
+                constexpr int b = decltype(bc)::value;
+                const float w = wl[b * K + i];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    // the product and the sum round one after the other
+#pragma clang fp contract(off)
+                    co[e] = co[e] + d[b][e] * w;
+                }
+            });
+            store8(o.co + ai, co);
+            cur = nxt;
+        }
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconRegress (sgv_ew.h), all of mean, m2, co and w; n_cov = K covariates;
+// count_before members are already in the state (0: the state is not read).  A batch of more than rg_members members goes out as
+// several launches with count_before advanced, which is bitwise the same.  Non-zero (nothing launched): -1 null input, -2 mean, m2,
+// co or w missing, -3 bad shape or n_cov outside [1, 32], -4 y or a state array not 16-byte aligned or w not 4-byte aligned,
+// -5 count_before < 0 or count_before + B > 2^24 (beyond that (float)k is not exact)
+int ew_recon_regress(int dtype, GNParams p, const float* scale, const float* mn, int n_cov, long count_before, const ReconRegress& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.mean || !o.m2 || !o.co || !o.w) return -2;
+    if (n_cov < 1 || n_cov > RG_MAX_K) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.mean | (uintptr_t)o.m2 | (uintptr_t)o.co) & 15) return -4;
+    if ((uintptr_t)o.w & 3) return -4;
+    if (count_before < 0 || count_before + p.B > (1L << 24)) return -5;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const RSGeom g = rs_geom(p.C);
+    const int RL = 256 / g.CV;
+    const int rowchunks = std::max(1, std::min(cdiv_i(p.T, RL), cdiv_i(2048, g.colblocks)));      // as ew_recon_ensemble
+    const dim3 grid(g.colblocks, rowchunks, 1);
+    const int B = p.B, per = dtype == 1 ? rg_members<bf16_t>() : rg_members<float>();
+    const size_t esz = dtype == 1 ? 2 : 4;
+    for (int b0 = 0; b0 < B; b0 += per) {
+        GNParams ps = p;
+        ps.B = std::min(per, B - b0);
+        ps.y = (const char*)p.y + (size_t)b0 * p.T * p.ldy * esz;
+        ps.sums = p.sums + (size_t)b0 * p.G * 2;
+        ReconRegress os = o;
+        os.w = o.w + (size_t)b0 * n_cov;
+        const int cb = (int)count_before + b0;
+        auto launch = [&](auto el, auto) {
+            using T = typename decltype(el)::type;
+            hipLaunchKernelGGL((recon_regress_kernel<T, rg_members<T>()>), grid, dim3(256), 0, s, ps, q, os, n_cov, cb);
+        };
         recon_dispatch(launch, dtype, true);
     }
     return 0;

@@ -175,6 +175,18 @@ struct ReconDistribution {
     const float* lo = nullptr; const float* hi = nullptr; int* counts = nullptr; int bins = 0;
 };
 int ew_recon_distribution(int dtype, GNParams p, const float* scale, const float* mn, long count_before, const ReconDistribution& o, hipStream_t s);
+// recon head -> the running co-moments of the field with n_cov = K covariates per member, 1 <= K <= 32, per (t, channel), the field never
+// stored.  x is the value ew_recon_physical would store (layout [B][T][C]); w fp32 [B][K] (input, 4-byte aligned) holds the centred
+// covariates of the batch's members, w[b][i] = y_b,i - ybar_i with ybar the running mean including that member (formed by the caller);
+// mean, m2 fp32 [T][C] and co fp32 [K][T][C], dense and 16-byte aligned.  Member b has k = count_before + b + 1; all fp32, every
+// operation rounded on its own, members in ascending order:
+//   d = x - mean;  mean = mean + d * (1.0f / (float)k);  m2 = m2 + d * (x - mean);  co[i] = co[i] + d * w[b][i]
+// mean and m2 are ReconEnsemble's moments bit for bit.  With count_before == 0 the state is not read.  Any cut of the same members into
+// launches gives the same bits.
+struct ReconRegress {
+    float* mean = nullptr; float* m2 = nullptr; float* co = nullptr; const float* w = nullptr;
+};
+int ew_recon_regress(int dtype, GNParams p, const float* scale, const float* mn, int n_cov, long count_before, const ReconRegress& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

@@ -353,6 +353,17 @@ int sgv_test_recon_distribution(int dtype, const void* y, long ldy, double* sums
         return ew_recon_distribution(dtype, q, scale, min, count_before, recon_distribution_of(*st), s);
     });
 }
+int sgv_test_recon_regress(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                           const float* scale, const float* min, int n_cov, const float* weights, long count_before,
+                           const sgv_regress_state* st, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_regress";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(regress_state_ok(me, "B", st, n_cov, weights, count_before, B));
+    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
+        return ew_recon_regress(dtype, q, scale, min, n_cov, count_before, recon_regress_of(*st, weights), s);
+    });
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -83,6 +83,11 @@ class DistributionState(C.Structure):
     _fields_ = [("lo", C.c_void_p), ("hi", C.c_void_p), ("counts", C.c_void_p), ("bins", C.c_int)]
 
 
+class RegressState(C.Structure):
+    """sgv_regress_state (include/sgvae.h): the running state of sgv_regress, device pointers"""
+    _fields_ = [("mean", C.c_void_p), ("m2", C.c_void_p), ("comoment", C.c_void_p)]
+
+
 MAX_PROBES = 4096
 SUMMARY_PARTS = ("node", "frame", "probes")      # `want` of Engine.summarize
 SCORE_PARTS = ("node", "frame")                  # `want` of Engine.score
@@ -94,6 +99,8 @@ SOBOL_MAX_BLOCKS = 1 << 23                       # base samples of one study: 2 
 DISTRIBUTION_FIELDS = ("lo", "hi", "counts")      # the state of Engine.distribution: lo, hi [T, N] fp32 (inputs); counts [bins + 2, T, N] int32
 DISTRIBUTION_MIN_BINS = 2
 DISTRIBUTION_MAX_BINS = 64                       # the kernel's byte histogram of a block, (bins + 2) * 2 KiB, fits the LDS of a CU
+REGRESS_FIELDS = ("mean", "m2", "comoment")       # the state of Engine.regress: mean, m2 [T, N]; comoment [n_cov, T, N], all fp32
+REGRESS_MAX_COVARIATES = 32                      # the weights of a launch fit the kernel's LDS table
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")     # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -147,6 +154,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_ensemble.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.c_long, C.POINTER(EnsembleState)]
     lib.sgv_sobol.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, C.c_long, C.POINTER(SobolState)]
     lib.sgv_distribution.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.c_long, C.POINTER(DistributionState)]
+    lib.sgv_regress.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_long, C.POINTER(RegressState)]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -214,6 +222,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_ensemble.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, lg, C.POINTER(EnsembleState), i32, i32, i32, vp]
     lib.sgv_test_recon_sobol.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, lg, C.POINTER(SobolState), i32, i32, i32, vp]
     lib.sgv_test_recon_distribution.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, lg, C.POINTER(DistributionState), i32, i32, i32, vp]
+    lib.sgv_test_recon_regress.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, lg, C.POINTER(RegressState), i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -689,6 +698,39 @@ class Engine:
             st = DistributionState(lo=state["lo"].data_ptr(), hi=state["hi"].data_ptr(), counts=state["counts"].data_ptr(), bins=bins)
             return (cb, C.byref(st)), state
         return self._surrogate("sgv_distribution", z, xs, scale, min, fix, tail)
+
+    def regress(self, z, xs, scale, min, state, weights, count_before, fix=True):
+        """Merges the fields generate() would write for this batch into the running state `state` of a linear response surface on
+        the covariates, per (time step, node), by the recon head's last pass itself; the fields are never stored.  Same inputs and
+        checks as summarize().  state: a dict of contiguous fp32 CUDA tensors, all three required: "mean", "m2" [T, N] (Welford,
+        bit for bit the moments of ensemble()) and "comoment" [n_cov, T, N], 1 <= n_cov <= REGRESS_MAX_COVARIATES: the sum over the
+        members of (field - its mean)(covariate i - its mean).  weights: contiguous fp32 CUDA [B, n_cov], the centred covariates of
+        this batch's members as predict.regression_weights forms them (y_m - ybar, ybar the running mean including member m).
+        Sample b of the batch is member count_before + b; with count_before == 0 the state is not read.  The tensors are updated in
+        place and `state` is returned.  Any cut of the same members into calls gives the same bits, the decoder's noise included:
+        it follows the member's index as in ensemble() and the draw position does not move.  Nothing synchronises; afterwards xhat()
+        raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        needs = "state must be a dict with the tensors 'mean', 'm2' [T, N] and 'comoment' [n_cov, T, N]"
+        co = state.get("comoment") if isinstance(state, dict) else None
+        K = int(co.shape[0]) if t.is_tensor(co) and co.dim() == 3 else 1
+        if K < 1 or K > REGRESS_MAX_COVARIATES:
+            raise ValueError(f"state['comoment'] has {K} rows: n_cov is outside [1, {REGRESS_MAX_COVARIATES}]")
+        spec = {"mean": ((T, N), t.float32), "m2": ((T, N), t.float32), "comoment": ((K, T, N), t.float32)}
+        have = self._state(state, spec, f"regression state ({REGRESS_FIELDS})", needs)
+        if len(have) != 3:
+            raise ValueError(f"state needs all of {REGRESS_FIELDS}, got only {have}")
+
+        def tail(B):
+            cb = int(count_before)
+            if not is_tensor_of(weights, t.float32, (B, K)):
+                raise ValueError(f"weights must be a contiguous float32 CUDA tensor of shape {(B, K)}")
+            if cb < 0 or cb + B > ENSEMBLE_MAX_COUNT:
+                raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
+            st = RegressState(mean=state["mean"].data_ptr(), m2=state["m2"].data_ptr(), comoment=state["comoment"].data_ptr())
+            return (K, C.c_void_p(weights.data_ptr()), cb, C.byref(st)), state
+        return self._surrogate("sgv_regress", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -30,6 +30,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     dist = s.distribution(draws, env, bins=32, mode="random")       # envelope, then a histogram between it per (time step, node);
     p5, p50, p95 = dist.quantile([0.05, 0.5, 0.95])                 # integer counts [bins + 2, T, N] instead of the fields and a
                                                    # sort over them
+    fit = s.regress(draws)                         # the linear response surface of the field on the inputs from the draws of such a
+    beta, r2 = fit.coefficients(), fit.r2()        # study: coefficients [K, T, N] and the share of the variance they explain, from
+                                                   # (2 + K) running arrays [T, N]; fit.covariance() with any scalar per draw
+                                                   # (covariates=...)
 """
 from __future__ import annotations
 
@@ -40,7 +44,8 @@ import pickle
 
 import numpy as np
 
-from .engine import DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_PROBES, SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of
+from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_PROBES, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
+                     SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of)
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
 FILES = {"vae": "SimulGen-VAE", "conditioner": "LatentConditioner", "data_scaler": "scaler.pkl",
@@ -367,6 +372,126 @@ class DistributionResult(_RunningResult):
     def median(self):
         """quantile(0.5)"""
         return self.quantile(0.5)
+
+
+def regression_covariates(covariates, P):
+    """The covariates of Surrogate.regress as a float64 array [P, K]: one row per member, 1 <= K <= REGRESS_MAX_COVARIATES columns,
+    every entry finite.  ValueError naming the problem otherwise: a rank other than 2, a number of rows other than P, K outside its
+    range, or an entry that is not finite (the first one is named).  numpy only."""
+    a = np.asarray(covariates, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"covariates: a [P, K] array is required, got shape {a.shape}")
+    if a.shape[0] != int(P):
+        raise ValueError(f"covariates: {a.shape[0]} rows, expected P = {int(P)} (one per condition)")
+    if a.shape[1] < 1 or a.shape[1] > REGRESS_MAX_COVARIATES:
+        raise ValueError(f"covariates: K = {a.shape[1]} columns, between 1 and {REGRESS_MAX_COVARIATES} are required")
+    bad = np.argwhere(~np.isfinite(a))
+    if bad.size:
+        m, i = (int(k) for k in bad[0])
+        raise ValueError(f"covariates[{m}, {i}] = {float(a[m, i])!r} is not finite")
+    return a
+
+
+def regression_weights(Y, mean=None, gram=None, count=0):
+    """The host half of the regression pass, float64 and sequential: for member m of Y [P, K], k = count + m + 1,
+        ybar_new = ybar + (y_m - ybar) / k;   w[m] = float32(y_m - ybar_new);   S = S + outer(y_m - ybar, y_m - ybar_new)
+    -> (w float32 [P, K], ybar [K], S [K, K]).  w holds the covariates centred on the running mean that includes the member, which
+    is what the kernel multiplies with the field's deviation from the mean before the member (the updating identity of the
+    co-moment); S is the centred Gram matrix of the covariates, sum (y - ybar)(y - ybar)^T.  mean / gram: the ybar and S of the
+    `count` members before these (None: zeros); the arguments are left alone.  Member by member, so any cut of Y into calls gives the
+    same bits.  numpy only."""
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ValueError(f"regression_weights: Y must be [P, K], got shape {Y.shape}")
+    K = Y.shape[1]
+    ybar = np.zeros(K) if mean is None else np.array(mean, dtype=np.float64)
+    S = np.zeros((K, K)) if gram is None else np.array(gram, dtype=np.float64)
+    if ybar.shape != (K,) or S.shape != (K, K) or int(count) < 0:
+        raise ValueError(f"regression_weights: mean {ybar.shape} / gram {S.shape} / count {count} do not fit K = {K} covariates")
+    w = np.empty(Y.shape, np.float32)
+    for m in range(Y.shape[0]):
+        before = Y[m] - ybar
+        ybar = ybar + before / float(int(count) + m + 1)
+        after = Y[m] - ybar
+        w[m] = after
+        S = S + np.outer(before, after)
+    return w, ybar, S
+
+
+class RegressionResult(_RunningResult):
+    """Surrogate.regress's result: the linear response surface of the field on K covariates over `count` members per (time step,
+    node).  mean, m2 fp32 [T, N] (Welford, as EnsembleResult's) and comoment fp32 [K, T, N], sum (x - xbar)(y_i - ybar_i), are device
+    tensors that ARE the running state (pass the result back as `into=` to go on accumulating); cov_mean [K] and cov_gram [K, K],
+    float64 numpy arrays, are the mean and the centred Gram matrix sum (y - ybar)(y - ybar)^T of the covariates, kept on the host."""
+    FIELDS = ("count", "mean", "m2", "comoment", "cov_mean", "cov_gram")
+    STATE = REGRESS_FIELDS
+
+    @property
+    def n_cov(self):
+        return int(self.comoment.shape[0])
+
+    def var(self, ddof=0):
+        """m2 / (count - ddof) [T, N] fp32"""
+        dof = self._dof("var", ddof)
+        return self._on_stream(lambda: self.m2 / float(dof))
+
+    def std(self, ddof=0):
+        """sqrt(var(ddof))"""
+        dof = self._dof("std", ddof)
+        return self._on_stream(lambda: (self.m2 / float(dof)).sqrt())
+
+    def covariance(self, ddof=0):
+        """comoment / (count - ddof) [K, T, N] fp32: the covariance of the field with each covariate"""
+        dof = self._dof("covariance", ddof)
+        return self._on_stream(lambda: self.comoment / float(dof))
+
+    def _host(self, a, shape):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.comoment.device).reshape(shape)
+
+    def correlation(self):
+        """comoment_i / sqrt(m2 gram_ii) [K, T, N] fp32: Pearson's correlation of the field with each covariate; NaN or inf where
+        the field or the covariate does not vary, as the division says"""
+        diag = np.diag(np.asarray(self.cov_gram, np.float64))
+        return self._on_stream(lambda: self.comoment / (self.m2[None] * self._host(diag, (-1, 1, 1))).sqrt())
+
+    def gram_inverse(self):
+        """The inverse of cov_gram [K, K], float64 on the host, through the unit-diagonal (correlation) form of the matrix.
+        ValueError where the regression is not determined: count <= K, a covariate that does not vary (it is named), or a
+        unit-diagonal Gram matrix that numpy.linalg.matrix_rank (default tolerance) finds rank-deficient."""
+        K = self.n_cov
+        G = np.asarray(self.cov_gram, np.float64)
+        if self.count <= K:
+            raise ValueError(f"coefficients: count = {self.count} members do not determine {K} coefficients and an intercept (count > K is required)")
+        diag = np.diag(G)
+        flat = np.flatnonzero(~(diag > 0.0))
+        if flat.size:
+            raise ValueError(f"coefficients: covariate {int(flat[0])} does not vary (gram[{int(flat[0])}, {int(flat[0])}] = {float(diag[flat[0]])!r})")
+        s = 1.0 / np.sqrt(diag)
+        R = G * s[:, None] * s[None, :]
+        rank = int(np.linalg.matrix_rank(R))
+        if rank < K:
+            raise ValueError(f"coefficients: the covariates are linearly dependent (rank {rank} of {K})")
+        return np.linalg.inv(R) * s[:, None] * s[None, :]
+
+    def coefficients(self):
+        """beta = gram^-1 comoment [K, T, N] fp32: the regression coefficients of the field on the covariates (with an intercept),
+        per unit of each covariate.  The inverse is taken in float64 on the host (gram_inverse, which raises where the design is
+        singular) and applied in fp32 on the engine stream."""
+        ginv = self.gram_inverse()
+        K = self.n_cov
+        return self._on_stream(lambda: (self._host(ginv, (K, K)) @ self.comoment.reshape(K, -1)).reshape(self.comoment.shape))
+
+    def intercept(self):
+        """mean - sum_i beta_i cov_mean_i [T, N] fp32: the response surface is intercept + sum_i beta_i y_i"""
+        beta = self.coefficients()
+        return self._on_stream(lambda: self.mean - (self._host(self.cov_mean, (1, -1)) @ beta.reshape(self.n_cov, -1)).reshape(self.mean.shape))
+
+    def r2(self):
+        """sum_i beta_i comoment_i / m2 [T, N] fp32: the share of the variance over the members that the linear surface explains;
+        NaN or inf where the field does not vary, as the division says"""
+        beta = self.coefficients()
+        return self._on_stream(lambda: (beta * self.comoment).sum(0) / self.m2)
 
 
 def sobol_groups(groups, F):
@@ -766,6 +891,54 @@ class Surrogate:
             for b_lo, b_hi, lat, xs in self._latent_batches(conditions, P, remap):
                 self.eng.distribution(lat, xs, self.data_scale, self.data_min, state, count + b_lo, fix=mode == "fix")
         return DistributionResult(stream=self._stream, count=count + P, bins=K, lo=state["lo"], hi=state["hi"], counts=state["counts"])
+
+    def regress(self, conditions, covariates=None, mode="fix", into=None):
+        """The linear response surface of the fields of all `conditions` on K covariates per (time step, node), without the fields:
+        what the draws of a Monte-Carlo or space-filling study say about which input drives the response -> a RegressionResult.
+        result.coefficients() [K, T, N] are the regression coefficients, result.r2() [T, N] the share of the variance they explain:
+        where it is close to 1 the coefficients are the sensitivities and no Sobol study is needed, where it is not, that is where
+        to spend one.  covariates: [P, K] values per condition (regression_covariates; a host array or a tensor, 1 <= K <=
+        REGRESS_MAX_COVARIATES), e.g. a probe history column of sweep(), to ask what co-varies with it; None: the columns of
+        `conditions` themselves (conditions on the device are read back once for that).  The recon head's last pass merges the values
+        predict() would store into mean, m2 (the moments of ensemble(), bit for bit) and the co-moments, the result tensors
+        themselves; the covariates are centred on the host in float64 (regression_weights), which also keeps their mean and Gram
+        matrix.  into: an earlier result of the same K to go on accumulating into (count, device state, cov_mean and cov_gram
+        continue): equal to one call on the concatenated conditions, bit for bit, wherever the cut falls.  Batching, streams, the
+        single input-range decision, `mode` and the noise that follows the member index are ensemble()'s."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        if covariates is None:
+            if int(conditions.shape[1]) > REGRESS_MAX_COVARIATES:
+                raise ValueError(f"conditions have {int(conditions.shape[1])} columns, more than {REGRESS_MAX_COVARIATES}: give explicit covariates "
+                                 f"[P, K] (covariates=...)")
+            covariates = conditions
+        if t.is_tensor(covariates):
+            covariates = covariates.detach().cpu().numpy()
+        Y = regression_covariates(covariates, P)
+        K = Y.shape[1]
+        spec = {"mean": ((self.T, self.N), t.float32), "m2": ((self.T, self.N), t.float32), "comoment": ((K, self.T, self.N), t.float32)}
+        state, count, ybar, gram = {}, 0, None, None
+        if into is not None:
+            RegressionResult.require(into)
+            if not t.is_tensor(into.comoment) or into.comoment.dim() != 3 or int(into.comoment.shape[0]) != K:
+                raise ValueError(f"into holds {int(into.comoment.shape[0]) if t.is_tensor(into.comoment) and into.comoment.dim() == 3 else 'no'} covariates, "
+                                 f"this call has {K}")
+            state, count = into.continued(spec)
+            ybar, gram = np.asarray(into.cov_mean, np.float64), np.asarray(into.cov_gram, np.float64)
+            if ybar.shape != (K,) or gram.shape != (K, K):
+                raise ValueError(f"into.cov_mean / into.cov_gram must be [K] / [K, K] with K = {K}, got {ybar.shape} / {gram.shape}")
+        if count + P > ENSEMBLE_MAX_COUNT:
+            raise ValueError(f"{count} + {P} members: a regression holds at most 2^24")
+        w, ybar, gram = regression_weights(Y, ybar, gram, count)
+        with _engine_stream(self._stream):
+            if into is None:
+                for k, (shape, dtype) in spec.items():
+                    state[k] = (t.zeros if P == 0 else t.empty)(shape, dtype=dtype, device="cuda")
+            w = t.from_numpy(w).cuda()
+            for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
+                self.eng.regress(lat, xs, self.data_scale, self.data_min, state, w[lo:hi], count + lo, fix=mode == "fix")
+        return RegressionResult(stream=self._stream, count=count + P, mean=state["mean"], m2=state["m2"], comoment=state["comoment"],
+                                cov_mean=ybar, cov_gram=gram)
 
     def sobol(self, A, B, groups=None, want=("first", "total"), into=None):
         """Variance-based global sensitivity of the response to its inputs per (time step, node), without the fields: which

@@ -159,7 +159,7 @@ int sgv_op_mixup_rows(const float* x, const int* perm, float lam, float* out, in
  * gw = {<G,W_orig>}, sigma2 = {sigma, 1/sigma}.  conv_weight_pack/unpack: reference [Cout][Cin][KH][KW] fp32 <-> the
  * GEMM layout [Cout][(kh*KW+kw)*Cin+ci] padded to a multiple of 8 (compute dtype / fp32).
  * Gradient clipping (latent_conditioner.py:304): sumsq accumulates sum g^2 into a double, clip_coef writes
- * {min(1, max_norm/(norm+1e-6)), norm}; sgv_op_adamw = torch.optim.AdamW on one tensor with g scaled by gscale[0]. */
+ * {min(1, max_norm/(norm+1e-6)), norm} (max_norm <= 0: no clipping, {1, norm}); sgv_op_adamw = torch.optim.AdamW on one tensor with g scaled by gscale[0]. */
 int sgv_op_l2_normalize(const float* x, float* out, long n, float eps, void* stream);
 int sgv_op_dot(const float* a, const float* b, float* out4, long n, void* stream);     /* out4: {a.b, 1/(a.b), 8 bytes of scratch} */
 int sgv_op_matvec_t(const float* W, const float* x, float* out, int rows, int cols, void* stream);   /* out = W^T x */

@@ -904,10 +904,11 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* g, long n, doub
     __syncthreads();
     if (threadIdx.x == 0) acc[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];      // block partial; fin_rows_kernel adds them onto the running total
 }
-// torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6)); out = {coef, total_norm}
+// torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6)); out = {coef, total_norm}.  max_norm <= 0: no
+// clipping (coef 1), as sgv_pset_step reads it
 __global__ void clip_coef_kernel(const double* sumsq, float max_norm, float* out) {
     const float tn = (float)sqrt(sumsq[0]);
-    out[0] = fminf(1.f, max_norm / (tn + 1e-6f));
+    out[0] = max_norm > 0.f ? fminf(1.f, max_norm / (tn + 1e-6f)) : 1.f;
     out[1] = tn;
 }
 // torch.optim.AdamW step on one tensor; gscale (device scalar, may be NULL) multiplies the gradient first

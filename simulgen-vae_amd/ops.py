@@ -624,8 +624,8 @@ class ParamSet:
         _ck(lib().sgv_pset_power_iteration(self.h, int(train), _stream()), "sgv_pset_power_iteration")
 
     def sigma_ptr(self, entry):
-        """device address of {sigma, 1/sigma} of a normalised entry"""
-        return int(lib().sgv_pset_sigma(self.h, entry))
+        """device address of {sigma, 1/sigma} of a normalised entry; 0 for an entry that is not normalised"""
+        return int(lib().sgv_pset_sigma(self.h, entry) or 0)
 
     def step(self, lr, weight_decay, max_norm, want_norm=True):
         out = C.c_float(0.0)

@@ -3,7 +3,9 @@
 rows x (taps*cols): row r holds W[:, r, :] flattened in (tap, col) order.  Inputs are numpy arrays holding the numbers the
 kernel reads (already rounded to fp32 / bf16 where it reads those); everything is computed in float64.  No GPU is touched.
 
-tests/test_optim_reference_host.py pins this file to oracle/vae_oracle.py, torch.optim.AdamW and torch.nn.utils.spectral_norm."""
+tests/test_optim_reference_host.py pins this file to oracle/vae_oracle.py, torch.optim.AdamW and torch.nn.utils.spectral_norm;
+tests/test_lc_param_reference_host.py pins the plain [rows][cols] use of it (taps = 1), the conv-weight packing and the clip
+coefficient to torch in float64."""
 import numpy as np
 import torch
 
@@ -125,3 +127,43 @@ def wct_copy(p):
     """wct[taps-1-tap][c][r] = p[tap][r][c]"""
     p = np.asarray(p)
     return np.ascontiguousarray(p[::-1].transpose(0, 2, 1))
+
+
+# ---- the latent conditioner's parameter side (include/sgvae_ops.h) ----
+def as_taps(W):
+    """a plain [rows][cols] matrix in the layout above (one tap)"""
+    W = np.asarray(W)
+    return W.reshape(1, W.shape[0], W.shape[1])
+
+
+def conv_weight_pack(w, align=8):
+    """reference Conv2d weight [Cout][Cin][KH][KW] -> the GEMM layout [Cout][(kh*KW + kw)*Cin + ci], rows zero-padded to a
+    multiple of `align` columns; written as loops on purpose (the host test pins it to permute + reshape)"""
+    w = np.asarray(w)
+    cout, cin, kh_, kw_ = w.shape
+    k = kh_ * kw_ * cin
+    out = np.zeros((cout, (k + align - 1) // align * align), w.dtype)
+    for co in range(cout):
+        for ci in range(cin):
+            for kh in range(kh_):
+                for kw in range(kw_):
+                    out[co, (kh * kw_ + kw) * cin + ci] = w[co, ci, kh, kw]
+    return out
+
+
+def conv_weight_unpack(packed, shape):
+    """the inverse: the pad columns are not read"""
+    packed = np.asarray(packed)
+    cout, cin, kh_, kw_ = shape
+    w = np.empty(shape, packed.dtype)
+    for co in range(cout):
+        for ci in range(cin):
+            for kh in range(kh_):
+                for kw in range(kw_):
+                    w[co, ci, kh, kw] = packed[co, (kh * kw_ + kw) * cin + ci]
+    return w
+
+
+def clip_coef(total_norm, max_norm, eps=1e-6):
+    """torch.nn.utils.clip_grad_norm_: the factor every gradient is multiplied by, min(1, max_norm / (total_norm + 1e-6))"""
+    return min(1.0, float(max_norm) / (float(total_norm) + eps))

@@ -47,17 +47,14 @@ from simulgen_vae_amd import engine as E
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
 import optim_reference as O  # noqa: E402
+from optim_checks import (B1, B2, EPS, LR, TINY, U, check_abs, check_red, check_update, coef, mags, norm_bound, red_tol,  # noqa: E402
+                          same, sigma_bound, sn_grad_bound, sq_err)
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-FLOOR = 2.0 ** -22
 CANARY = 768.0       # bf16-exact
 PAD = 64
-TINY = 1e-300
 F32, BF16 = 0, 1
-B1, B2, EPS = float(np.float32(0.9)), float(np.float32(0.999)), float(np.float32(1e-8))
-LR = float(np.float32(1e-3))
 
 
 def _torch():
@@ -67,11 +64,6 @@ def _torch():
 
 def _ok(lib, rc):
     assert rc == 0, lib.sgv_last_error().decode()
-
-
-def mags(rng, shape, scale=1.0):
-    """random signs, magnitudes in [0.25, 1] x scale, fp32"""
-    return (rng.choice([-1.0, 1.0], shape) * rng.uniform(0.25, 1.0, shape) * scale).astype(np.float32)
 
 
 class Buf:
@@ -189,46 +181,6 @@ class Set:
 
     def snapshot(self):
         return [b for e in self.ents for b in e.snapshot()]
-
-
-def same(a, b):
-    torch = _torch()
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
-
-
-def red_tol(measured):
-    return max(4.0 * measured, FLOOR)
-
-
-def check_abs(got, ref, tol, what):
-    ref = np.asarray(ref, np.float64)
-    got = np.asarray(got, np.float64).reshape(ref.shape)
-    tol = np.broadcast_to(np.asarray(tol, np.float64), ref.shape)
-    assert np.isfinite(got).all(), f"{what}: non-finite output (an element was not written?)"
-    err = np.abs(got - ref)
-    worst = np.max(err / np.maximum(tol, TINY)) if err.size else 0.0
-    print(f"  {what}: max err {err.max():.3e}, max|ref| {np.abs(ref).max():.3e}, worst err/tol {worst:.3f}")
-    assert np.all(err <= tol), f"{what}: {int((err > tol).sum())} elements off, worst err/tol {worst:.3g} at {np.unravel_index(np.argmax(err - tol), ref.shape)}"
-
-
-def check_red(got, ref, mag, measured, what, extra=0.0):
-    tol = red_tol(measured)
-    print(f"  {what}: tolerance {tol:.3e} of the sum of magnitudes (float32 re-summation {measured:.3e})")
-    check_abs(got, ref, tol * np.asarray(mag, np.float64) + extra, what)
-
-
-def norm_bound(x_ref, dx, tol_n):
-    """bound of x / max(|x|, 1e-12) given the elementwise bound dx of x and the reduction tolerance of the squared norm"""
-    N = max(float(np.linalg.norm(x_ref)), O.SN_EPS)
-    return dx / N + np.abs(x_ref) / N * (tol_n + float(np.linalg.norm(dx)) / N + 4 * U)
-
-
-def sigma_bound(s_ref, ds, tol_n):
-    return (1.5 * (tol_n + 2.0 * float(np.linalg.norm(ds)) / max(float(np.linalg.norm(s_ref)), TINY)) + 3 * U)
-
-
-def sq_err(x):
-    return R.f32_sum_error(np.asarray(x, np.float64) ** 2)[0]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -429,10 +381,6 @@ def test_grad_dot():
 # ------------------------------------------------------------------------------------------------
 # AdamW
 # ------------------------------------------------------------------------------------------------
-def coef(step):
-    return float(np.float32(1.0 - 0.9 ** step)), float(np.float32(np.sqrt(1.0 - 0.999 ** step)))
-
-
 def ref_grad(e, g, dot_got, sigma_got):
     """float64 gradient wrt the original weight from the kernel's own summed dot and 1/sigma, and its error bound e_g"""
     g = O.f64(g).reshape(e.shape)
@@ -443,33 +391,7 @@ def ref_grad(e, g, dot_got, sigma_got):
         cdot = np.float32(cdot + np.float32(dot_got[k]))
     is_ = float(np.float32(sigma_got[1]))
     go = O.chain_rule(g, float(cdot), is_, e.h["u"], e.h["v_sn"])
-    uv = np.abs(O.f64(e.h["u"])[None, :, None] * O.f64(e.h["v_sn"]).reshape(e.taps, 1, e.cols) * float(cdot) * is_)
-    return go, 2 * U * (np.abs(go) + uv)
-
-
-def check_update(tag, e, g_ref, e_g, got, old, lr, wd, step, gscale):
-    """got / old: dicts of p, m, v.  The bounds are derived in the module docstring, one term per line here."""
-    bc1, bc2s = coef(step)
-    sh = e.shape
-    p0, m0, v0 = (O.f64(old[k]).reshape(sh) for k in ("p", "m", "v"))
-    r = O.adamw(p0, g_ref, m0, v0, lr, step, wd, eps=EPS, b1=B1, b2=B2, gscale=gscale, bc1=bc1, bc2sqrt=bc2s)
-    g = r["g"]
-    if gscale is not None:
-        e_g = e_g * abs(gscale) + U * np.abs(g)                                 # g * gscale
-    e_m = (3 * U * (np.abs(m0) * B1 + (1 - B1) * np.abs(g))                    # m b1, (1 - b1) g, their sum
-           + (1 - B1) * e_g)                                                    # the gradient's own error
-    e_v = (3 * U * r["v"]                                                       # (1 - b2) g, * g, v b2 / the sum (positive terms)
-           + (1 - B2) * (2 * np.abs(g) * e_g + e_g * e_g))                      # the gradient's own error
-    rel_v = np.where(r["v"] > 0, e_v / np.maximum(2 * r["v"], TINY), 0.0)       # sqrt halves the relative error
-    e_u = ((lr / bc1) * e_m / r["denom"]                                        # the numerator's error
-           + np.abs(r["update"]) * (rel_v + 9 * U))                             # sqrt 2, / bc2sqrt 2, + eps 1, quotient 2, lr / bc1 1, product 1
-    e_inc = (e_u
-             + (np.abs(p0) * 2.0 ** -25 + U * np.abs(p0 * r["decay"]) if r["decay"] != 1.0 else 0.0)   # decay rounded next to 1; p * decay
-             + U * np.abs(r["p"]))                                              # the final subtraction
-    check_abs(got["m"], r["m"], e_m + TINY, f"{tag} m")
-    check_abs(got["v"], r["v"], e_v + TINY, f"{tag} v")
-    check_abs(O.f64(got["p"]).reshape(sh) - p0, r["p"] - p0, e_inc + TINY, f"{tag} p_new - p_old")
-    return r
+    return go, sn_grad_bound(go, e.h["u"], e.h["v_sn"], float(cdot), is_, e.shape)
 
 
 def plant(e, rng, step):
@@ -541,7 +463,7 @@ def test_adamw_flat(step, dtype, wd):
                 if e.sn:
                     check_dot(e, dot_got)
                 g_ref, e_g = ref_grad(e, e.h["g"], dot_got, e.h["sigma"] if e.sn else None)
-                check_update(f"entry {i} {e.shape}", e, g_ref, e_g, got, e.h, LR, wd, step, gscale)
+                check_update(f"entry {i} {e.shape}", e.shape, g_ref, e_g, got, e.h, LR, wd, step, gscale)
                 check_planted(e, got, LR, wd, step)
                 terms.append((g_ref * g_ref).ravel())
                 extra += float((2 * np.abs(g_ref) * e_g + U * g_ref * g_ref).sum())
@@ -565,7 +487,7 @@ TILE_CASES = [(s, dtype, (1, 10, 1000)[(i + dtype) % 3]) for i, s in enumerate(T
 
 def check_tiled(e, st, got, g_vals, lr, wd, step, dtype, gn, tag):
     g_ref, e_g = ref_grad(e, g_vals, e.h["dot"], e.h["sigma"])
-    check_update(tag, e, g_ref, e_g, got, e.h, lr, wd, step, None)
+    check_update(tag, e.shape, g_ref, e_g, got, e.h, lr, wd, step, None)
     pn = got["p"].reshape(e.shape)
     if e.b["wc"] is not None:
         if dtype == BF16:

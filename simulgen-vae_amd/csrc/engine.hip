@@ -520,6 +520,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     for (auto& g : e->gns) e->colpart_floats = std::max(e->colpart_floats, ew_gn_part_floats(e->maxB, e->T, g.C));
     for (auto& l : e->layers) if (l.op != OP_LINEAR) e->colpart_floats = std::max(e->colpart_floats, ew_gn_part_floats(e->maxB, e->T, l.cout));
     e->colpart_floats = std::max(e->colpart_floats, ew_recon_summary_work_floats(e->maxB, e->T, e->N));   // sgv_summarize's frame partials (smaller up to T of several hundred)
+    e->colpart_floats = std::max(e->colpart_floats, ew_recon_project_work_floats(e->maxB, e->T, e->N, SGV_MAX_FUNCTIONALS));   // sgv_project's partials at 32 rows
     e->xpose_floats = (size_t)M * std::max(e->N, 8);
     for (int i = 0; i < e->n; ++i) e->xpose_floats = std::max(e->xpose_floats, (size_t)M * e->enc[i] * 2);
 #define ALLOC(ptr, bytes)                                                                                      \
@@ -841,6 +842,12 @@ int sgv_set_shard(sgv_engine* e, int rank, int world) {
     e->shard_rank = rank; e->shard_world = world;
     return SGV_OK;
 }
+int sgv_set_draw_row(sgv_engine* e, long first_row) {
+    if (!e) return fail(SGV_ERR_ARG, "null engine");
+    if (first_row < 0) return fail(SGV_ERR_ARG, "sgv_set_draw_row: first_row = %ld is negative", first_row);
+    e->draw_row = first_row;
+    return SGV_OK;
+}
 int sgv_seed(sgv_engine* e, uint64_t seed) {
     if (!e) return fail(SGV_ERR_ARG, "null engine");
     e->seed = seed; e->draw = 0;
@@ -889,10 +896,10 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 
 // What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
 // (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble), the sums of a Sobol study
-// (sgv_sobol), the histogram of the members (sgv_distribution) or their co-moments with the covariates (sgv_regress); only the members of
-// `kind` are read.
+// (sgv_sobol), the histogram of the members (sgv_distribution), their co-moments with the covariates (sgv_regress) or weighted sums
+// over the mesh (sgv_project); only the members of `kind` are read.
 struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS } kind;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS, PROJECT } kind;
     const float* scale; const float* mn;
     int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
     ReconSummary sum;                                          // SUMMARY
@@ -901,23 +908,25 @@ struct GenOut {
     ReconSobol sob; int sob_params = 0; long sob_blocks = 0;   // SOBOL
     ReconDistribution dist; long dist_count = 0;               // DISTRIBUTION
     ReconRegress reg; int reg_cov = 0; long reg_count = 0;     // REGRESS
+    ReconProject proj;                                         // PROJECT
     // ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
     bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION || kind == REGRESS; }
     long members_before() const {
         return kind == SOBOL ? sob_blocks * (sob_params + 2) : kind == DISTRIBUTION ? dist_count : kind == REGRESS ? reg_count : ens_count;
     }
 };
-// The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass go
-// to e->colpart, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
+// The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass and
+// the per-block partials of the project pass go to e->colpart, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
 // the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol, the
 // distribution and the regression pass.
 static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress"};
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress", "recon_project"};
     static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
                                            "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
                                            "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)",
                                            "sgv_distribution: the distribution pass rejected its arguments (%d)",
-                                           "sgv_regress: the regression pass rejected its arguments (%d)"};
+                                           "sgv_regress: the regression pass rejected its arguments (%d)",
+                                           "sgv_project: the project pass rejected its arguments (%d)"};
     ScopedTimer tm(e, tag[g.kind], nullptr);
     int r = 0;
     switch (g.kind) {
@@ -928,6 +937,7 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
     case GenOut::SOBOL: r = ew_recon_sobol(e->dt, p, g.scale, g.mn, g.sob_params, g.sob_blocks, g.sob, e->stream); break;
     case GenOut::DISTRIBUTION: r = ew_recon_distribution(e->dt, p, g.scale, g.mn, g.dist_count, g.dist, e->stream); break;
     case GenOut::REGRESS: r = ew_recon_regress(e->dt, p, g.scale, g.mn, g.reg_cov, g.reg_count, g.reg, e->stream); break;
+    case GenOut::PROJECT: { ReconProject o = g.proj; o.work = e->colpart; r = ew_recon_project(e->dt, p, g.scale, g.mn, o, e->stream); break; }
     }
     return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
 }
@@ -937,12 +947,13 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenO
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
     // sgv_ensemble, sgv_sobol: the noise of member m is a function of (seed, m, site) alone -- the rows members_before + b of the streams
-    // the first call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size
+    // the first call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size.
+    // The other surrogate passes draw per call, from row e->draw_row on (sgv_set_draw_row; 0 unless a caller cuts a study into batches itself)
     const bool ens = gen && gen->by_member();
     uint64_t ens_draw = 0;
     for (int s = 1; s < n_st; ++s) {
         if (!e->eps_set[s]) ew_randn(e->eps[s], M * e->dec[s], e->seed, (ens ? ens_draw++ : e->draw++) * 8 + s, e->stream, (long)e->T * e->dec[s], e->shard_world, e->shard_rank,
-                                     ens ? gen->members_before() : 0);
+                                     ens ? gen->members_before() : gen ? e->draw_row : 0);
     }
     {
         const Layer& l = e->layers[e->start_lin];
@@ -1157,6 +1168,15 @@ int sgv_regress(sgv_engine* e, const float* z_dev, const float* xs_dev, int batc
     GenOut gen = {GenOut::REGRESS, scale_dev, min_dev};
     gen.reg = recon_regress_of(*st, weights_dev); gen.reg_cov = n_cov; gen.reg_count = count_before;
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_regress", gen);
+}
+
+int sgv_project(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                const float* min_dev, const float* weights_dev, int n_func, float* out_dev) {
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_project: null argument");
+    CHK(project_args_ok("sgv_project", weights_dev, n_func, out_dev));
+    GenOut gen = {GenOut::PROJECT, scale_dev, min_dev};
+    gen.proj.weights = weights_dev; gen.proj.n_func = n_func; gen.proj.out = out_dev;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_project", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

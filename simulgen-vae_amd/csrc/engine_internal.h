@@ -171,7 +171,7 @@ struct sgv_engine {
     bool use_side = true, side_dirty = false;
     float* xpose_tmp = nullptr; size_t xpose_floats = 0;
     float* recon_unit = nullptr;   // [3][N] unit-scale dgamma/dbeta/dbias of the recon head
-    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace (also the frame partials of sgv_summarize)
+    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace (also the frame partials of sgv_summarize and the partials of sgv_project)
     int* probes_dev = nullptr; int n_probes = 0;           // sgv_set_probes: SGV_MAX_PROBES checked node indices (allocated on first use)
     std::vector<int32_t> probes_host;                      // the source of the last upload stays alive until the next one
     // graph
@@ -220,6 +220,7 @@ struct sgv_engine {
     std::vector<FinDot> fin_dots; std::vector<FinAffine> fin_affine;
     int dot_counts[512];
     uint64_t seed = 0x5347564145ull, draw = 0;
+    long draw_row = 0;                          // sgv_set_draw_row: sample b of a per-call draw takes row draw_row + b of its stream
     int shard_rank = 0, shard_world = 1;        // sgv_set_shard: sample b of this engine's batch is sample b * world + rank of the global batch
     long step = 0;
     float scalars_host[SGV_MAX_SCALARS];
@@ -322,7 +323,14 @@ static inline ReconRegress recon_regress_of(const sgv_regress_state& st, const f
     r.mean = st.mean; r.m2 = st.m2; r.co = st.comoment; r.w = weights;
     return r;
 }
-constexpr int SGV_SOBOL_MAX_PARAMS = 30;    // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
+// sgv_project and its test hook: SGV_MAX_FUNCTIONALS (sgv_ew.h) weight rows at most
+static inline int project_args_ok(const char* who, const float* weights, int n_func, const float* out) {
+    if (!weights || !out) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (n_func < 1 || n_func > SGV_MAX_FUNCTIONALS) return fail(SGV_ERR_ARG, "%s: n_func = %d is outside [1, %d]", who, n_func, SGV_MAX_FUNCTIONALS);
+    if (((uintptr_t)weights & 15) || ((uintptr_t)out & 3)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (weights 16 bytes, out 4)", who);
+    return 0;
+}
+constexpr int SGV_SOBOL_MAX_PARAMS = 30;   // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
 static inline int sobol_state_ok(const char* who, const char* batch_name, const sgv_sobol_state* st, int n_params, long blocks_before, int batch) {
     if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
     if (!st->mean || !st->m2) return fail(SGV_ERR_ARG, "%s: mean and m2 are required", who);

@@ -1,7 +1,8 @@
 // The recon tails (gfx950): passes that replace the loss tail of the recon head in surrogate use -- the physical-unit field
 // (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
 // members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol), the histogram of the members
-// between given bounds (sgv_distribution) and the co-moments of the members with their covariates (sgv_regress).  All of them stream y = the recon head's convolution output once, form the same value per
+// between given bounds (sgv_distribution), the co-moments of the members with their covariates (sgv_regress) and weighted sums over the
+// mesh (sgv_project).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -1188,5 +1189,147 @@ int ew_recon_regress(int dtype, GNParams p, const float* scale, const float* mn,
         };
         recon_dispatch(launch, dtype, true);
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate linear functionals (sgv_project): R weighted sums over the mesh per (sample, t), out[b][t][r] = sum_n W[r][n] x[b][t][n] with
+// x the value recon_phys_val gives -- the first tail shaped like a GEMM, [B*T] x [C] x [R <= 32], and the first on the matrix cores:
+// v_mfma_f32_32x32x2_f32 with the 32 columns the functionals (rows of W past R are zeros), exact fp32 products and one fused
+// multiply-add chain per output, ascending in k.
+// Geometry: the rows m = b * T + t are taken flat, PJ_M tiles of 32 per block; a tile may span samples, so every lane keeps the sample
+// of each of its rows and takes (mean, rstd) from a block table [row's sample][group] filled through gn_mean_rstd.  The MFMA's A operand
+// wants lane l to hold row l & 31 and k = l >> 5, so the load geometry is the operand's: lane l loads 8 channels (16 / 32 bytes) of
+// row l & 31 at channel cb + 8 (l >> 5), and MFMA e = 0..7 of the step takes channels cb + e (k = 0) and cb + 8 + e (k = 1); the B
+// operand is 8 consecutive weights of row l & 31 at the same channels, and the channel constants are those channels'.  The weights and
+// constants of a step serve all PJ_M row tiles.
+// Shares: a block owns PJ_CHUNK channels, its four waves PJ_WAVE_COLS contiguous ones each.  A wave's chain runs over its channels in
+// the order above; the four waves meet through LDS and are added in wave order in fp32; the per-block partials [B*T][chunks][R] go
+// to the workspace and recon_project_finish_kernel adds them in ascending chunk order in fp64 and rounds once.  The shares depend on C alone,
+// and an output element of the MFMA depends on its own row of A and column of B alone: hence the invariances of sgv_ew.h.  Lanes past C
+// carry zeros on both operands and load nothing there; rows past B*T load the last row again and are not written.
+// ------------------------------------------------------------------------------------------
+constexpr int PJ_ROWS = 32;                         // rows of an MFMA tile
+constexpr int PJ_M = 2;                             // row tiles per block: what one load of weights and constants serves
+constexpr int PJ_WAVE_COLS = 1024;                  // channels of a wave's chain (a multiple of 16)
+constexpr int PJ_CHUNK = 4 * PJ_WAVE_COLS;          // channels per block, per partial
+static int pj_chunks(int C) { return cdiv_i(C, PJ_CHUNK); }
+size_t ew_recon_project_work_floats(int B, int T, int C, int R) { return ((size_t)B * T * pj_chunks(C) * R + 3) & ~(size_t)3; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void recon_project_kernel(const GNParams p, const ReconPhys q, const ReconProject o) {
+    __shared__ float2 tab[PJ_M * PJ_ROWS][SGV_GN_MAX_GROUPS];          // (mean, rstd) of group g of the block's i-th sample
+    __shared__ float red[4][PJ_M * PJ_ROWS * 32];                      // the waves' accumulators: [wave][tile][row][r]
+    const long rows = (long)p.B * p.T, row0 = (long)blockIdx.y * (PJ_M * PJ_ROWS);
+    const int b_first = (int)(row0 / p.T), b_last = (int)(min(rows - 1, row0 + PJ_M * PJ_ROWS - 1) / p.T);
+    for (int i = threadIdx.x; i < (b_last - b_first + 1) * p.G; i += 256) {
+        float m, r;
+        gn_mean_rstd(p, b_first + i / p.G, i % p.G, m, r);
+        tab[i / p.G][i % p.G] = make_float2(m, r);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
+    const T* yrow[PJ_M];
+    int bi[PJ_M];
+#pragma unroll
+    for (int m = 0; m < PJ_M; ++m) {
+        const long row = min(row0 + m * PJ_ROWS + lr, rows - 1);
+        yrow[m] = reinterpret_cast<const T*>(p.y) + row * p.ldy;
+        bi[m] = (int)(row / p.T) - b_first;
+    }
+    const bool r_ok = lr < o.n_func;
+    const float* const wrow = o.weights + (long)(r_ok ? lr : 0) * p.C;
+    const int c_lo = blockIdx.x * PJ_CHUNK + wv * PJ_WAVE_COLS, c_hi = min(p.C, c_lo + PJ_WAVE_COLS);
+    f32x16 acc[PJ_M];
+#pragma unroll
+    for (int m = 0; m < PJ_M; ++m)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[m][v] = 0.f;
+    for (int cb = c_lo; cb < c_hi; cb += 16) {          // wave-uniform; c_hi is a multiple of 8: only the upper half of the last step can be past it
+        const bool ok = cb + 8 * h < c_hi;
+        const int c0 = ok ? cb + 8 * h : cb;            // a half past the end loads the lower half's addresses and uses nothing
+        Raw8<T> ry[PJ_M];
+#pragma unroll
+        for (int m = 0; m < PJ_M; ++m) raw_load(yrow[m] + c0, ry[m]);
+        float w[8], gam[8], bet[8], mn[8], inv[8];
+        load8(wrow + c0, w);
+        load8(p.gamma + c0, gam); load8(p.beta + c0, bet); load8(q.mn + c0, mn); load8(q.scale + c0, inv);
+        const bool w_ok = ok && r_ok;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { w[e] = w_ok ? w[e] : 0.f; inv[e] = recon_phys_inv(inv[e]); }
+        // the groups of the octet: with Cg >= 8 (block-uniform) at most two, the first n_lo channels in g_lo
+        const int g0 = c0 / p.Cg, n_lo = p.Cg - (c0 - g0 * p.Cg);
+        const int g_lo = min(g0, p.G - 1), g_hi = min(g0 + 1, p.G - 1);
+        float x[PJ_M][8];
+#pragma unroll
+        for (int m = 0; m < PJ_M; ++m) {
+            float v[8], gm[8], gr[8];
+            raw_unpack(ry[m], v);
+            if (p.Cg >= 8) {
+                const float2 lo = tab[bi[m]][g_lo], hi = tab[bi[m]][g_hi];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { gm[e] = e < n_lo ? lo.x : hi.x; gr[e] = e < n_lo ? lo.y : hi.y; }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float2 k = tab[bi[m]][min((c0 + e) / p.Cg, p.G - 1)];
+                    gm[e] = k.x; gr[e] = k.y;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float val = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], inv[e]);
+                x[m][e] = ok ? val : 0.f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int m = 0; m < PJ_M; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[m][e], w[e], acc[m], 0, 0, 0);
+    }
+    // C / D map of the 32x32 forms: register v of lane l holds row (v & 3) + 8 (v >> 2) + 4 (l >> 5), column l & 31
+#pragma unroll
+    for (int m = 0; m < PJ_M; ++m)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) red[wv][(m * PJ_ROWS + (v & 3) + 8 * (v >> 2) + 4 * h) * 32 + lr] = acc[m][v];
+    __syncthreads();
+    const int nchunk = gridDim.x;
+    for (int i = threadIdx.x; i < PJ_M * PJ_ROWS * 32; i += 256) {
+        const long row = row0 + (i >> 5);
+        const int r = i & 31;
+        if (row < rows && r < o.n_func)
+            o.work[(row * nchunk + blockIdx.x) * o.n_func + r] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];          // wave order
+    }
+}
+
+// partials [rows][nchunk][R] -> out [rows][R]: one thread per output, its partials in ascending chunk order in fp64, rounded once
+__global__ __launch_bounds__(256) void recon_project_finish_kernel(const float* __restrict__ part, long n_out, int nchunk, int R, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_out) return;
+    const long row = i / R;
+    const int r = (int)(i - row * R);
+    double s = 0.0;
+    for (int j = 0; j < nchunk; ++j) s += (double)part[(row * nchunk + j) * R + r];
+    out[i] = (float)s;
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconProject (sgv_ew.h), o.work = ew_recon_project_work_floats floats.  Non-zero
+// (nothing launched): -1 null input, -2 no output, -3 bad shape or n_func outside [1, 32], -4 y, weights or work not 16-byte aligned
+// or out not 4-byte aligned, -6 no workspace
+int ew_recon_project(int dtype, GNParams p, const float* scale, const float* mn, const ReconProject& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.weights) return -1;
+    if (!o.out) return -2;
+    if (o.n_func < 1 || o.n_func > SGV_MAX_FUNCTIONALS) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.weights | (uintptr_t)o.work) & 15) return -4;
+    if ((uintptr_t)o.out & 3) return -4;
+    if (!o.work) return -6;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const long rows = (long)p.B * p.T;
+    const int nchunk = pj_chunks(p.C);
+    const dim3 grid(nchunk, cdiv_i(rows, PJ_M * PJ_ROWS), 1);
+    if (dtype == 1) hipLaunchKernelGGL((recon_project_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o);
+    else hipLaunchKernelGGL((recon_project_kernel<float>), grid, dim3(256), 0, s, p, q, o);
+    hipLaunchKernelGGL(recon_project_finish_kernel, dim3(cdiv_i(rows * o.n_func, 256)), dim3(256), 0, s, o.work, rows * o.n_func, nchunk, o.n_func, o.out);
     return 0;
 }

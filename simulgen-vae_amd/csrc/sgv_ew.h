@@ -187,6 +187,21 @@ struct ReconRegress {
     float* mean = nullptr; float* m2 = nullptr; float* co = nullptr; const float* w = nullptr;
 };
 int ew_recon_regress(int dtype, GNParams p, const float* scale, const float* mn, int n_cov, long count_before, const ReconRegress& o, hipStream_t s);
+// recon head -> n_func = R linear functionals of the physical field, 1 <= R <= SGV_MAX_FUNCTIONALS, the field never stored:
+//   out[b][t][r] = sum over n of weights[r][n] * x[b][t][n],  x the value ew_recon_physical would store (layout [B][T][C]).
+// weights fp32 [R][C] dense, 16-byte aligned (input); out fp32 [B][T][R], 4-byte aligned; work: ew_recon_project_work_floats floats,
+// 16-byte aligned.  fp32 fused multiply-adds in ascending n inside a fixed share of the channels, the shares combined in ascending
+// order in fp64 and rounded to fp32 once: out[b][t][r] depends on sample b, row t and weight row r alone -- not on B, on the
+// sample's place in the batch, on R or on the other rows -- and two launches are bitwise equal.  No atomics.
+// Non-zero (nothing launched): -1 null input (weights included), -2 no output, -3 bad shape or R outside [1, 32], -4 y, weights or
+// work not 16-byte aligned or out not 4-byte aligned, -6 no workspace
+constexpr int SGV_MAX_FUNCTIONALS = 32;
+struct ReconProject {
+    const float* weights = nullptr; int n_func = 0; float* out = nullptr;
+    float* work = nullptr;
+};
+size_t ew_recon_project_work_floats(int B, int T, int C, int R);
+int ew_recon_project(int dtype, GNParams p, const float* scale, const float* mn, const ReconProject& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

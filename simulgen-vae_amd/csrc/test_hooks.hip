@@ -364,6 +364,19 @@ int sgv_test_recon_regress(int dtype, const void* y, long ldy, double* sums, con
         return ew_recon_regress(dtype, q, scale, min, n_cov, count_before, recon_regress_of(*st, weights), s);
     });
 }
+int sgv_test_recon_project(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                           const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
+                           void* stream) {
+    const char* me = "sgv_test_recon_project";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(project_args_ok(me, weights, n_func, out));
+    return recon_hook_run(me, dtype, p, ew_recon_project_work_floats(B, T, C, n_func), stream, [&](const GNParams& q, float* work, hipStream_t s) {
+        ReconProject o;
+        o.weights = weights; o.n_func = n_func; o.out = out; o.work = work;
+        return ew_recon_project(dtype, q, scale, min, o, s);
+    });
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -101,6 +101,7 @@ DISTRIBUTION_MIN_BINS = 2
 DISTRIBUTION_MAX_BINS = 64                       # the kernel's byte histogram of a block, (bins + 2) * 2 KiB, fits the LDS of a CU
 REGRESS_FIELDS = ("mean", "m2", "comoment")       # the state of Engine.regress: mean, m2 [T, N]; comoment [n_cov, T, N], all fp32
 REGRESS_MAX_COVARIATES = 32                      # the weights of a launch fit the kernel's LDS table
+MAX_FUNCTIONALS = 32                             # SGV_MAX_FUNCTIONALS: the weight rows of Engine.project are the 32 columns of the kernel's MFMA tile
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")     # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -143,6 +144,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_set_eps.argtypes = [vp, i32, vp, i32]
     lib.sgv_seed.argtypes = [vp, C.c_uint64]
     lib.sgv_set_shard.argtypes = [vp, i32, i32]
+    lib.sgv_set_draw_row.argtypes = [vp, C.c_long]
     lib.sgv_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.sgv_forward.argtypes = [vp, i32, i32, vp]
     lib.sgv_encode.argtypes = [vp, vp, vp, vp]
@@ -155,6 +157,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_sobol.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, C.c_long, C.POINTER(SobolState)]
     lib.sgv_distribution.argtypes = [vp, vp, vp, i32, i32, vp, vp, C.c_long, C.POINTER(DistributionState)]
     lib.sgv_regress.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_long, C.POINTER(RegressState)]
+    lib.sgv_project.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -223,6 +226,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_sobol.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, lg, C.POINTER(SobolState), i32, i32, i32, vp]
     lib.sgv_test_recon_distribution.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, lg, C.POINTER(DistributionState), i32, i32, i32, vp]
     lib.sgv_test_recon_regress.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, lg, C.POINTER(RegressState), i32, i32, i32, vp]
+    lib.sgv_test_recon_project.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -432,6 +436,12 @@ class Engine:
         """Sample b of this engine's batch is sample b * world + rank of the global batch: the engine's noise draws are keyed by
         that global row (include/sgvae.h: sgv_set_shard), so the same seed on every rank gives world-size-invariant noise."""
         _check(self.lib, self.lib.sgv_set_shard(self.h, int(rank), int(world)), "sgv_set_shard")
+
+    def set_draw_row(self, first_row: int):
+        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project) takes
+        row first_row + b of the streams the call draws from (include/sgvae.h: sgv_set_draw_row).  With the draw position put back in
+        front of every batch (set_train_state) a study cut into batches gets the noise one call over all of it would get.  Default 0."""
+        _check(self.lib, self.lib.sgv_set_draw_row(self.h, int(first_row)), "sgv_set_draw_row")
 
     def set_input(self, x):
         """x: torch float32 CUDA tensor [B, num_node, num_time] (reference layout)."""
@@ -731,6 +741,28 @@ class Engine:
             st = RegressState(mean=state["mean"].data_ptr(), m2=state["m2"].data_ptr(), comoment=state["comoment"].data_ptr())
             return (K, C.c_void_p(weights.data_ptr()), cb, C.byref(st)), state
         return self._surrogate("sgv_regress", z, xs, scale, min, fix, tail)
+
+    def project(self, z, xs, scale, min, weights, fix=True, out=None):
+        """Linear functionals of the field generate() would write, by the recon head's last pass itself; the field is never stored.
+        Same inputs and checks as summarize().  weights: contiguous fp32 CUDA [R, N], 1 <= R <= MAX_FUNCTIONALS (predict.functional_weights
+        validates and uploads a host array).  Returns fp32 CUDA [B, T, R], values[b, t, r] = sum over n of weights[r, n] * field[b, t, n]:
+        fp32 fused multiply-adds in a fixed order inside fixed shares of the mesh, the shares added in float64 and rounded once.  A
+        value depends on its sample, its row and its weight row alone, so any cut of the conditions into batches gives the same
+        bits.  out: a contiguous fp32 CUDA tensor [B, T, R] to write into (a slice along the first axis of a larger one will do).
+        Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        R = int(weights.shape[0]) if t.is_tensor(weights) and weights.dim() == 2 else 0
+        if R < 1 or R > MAX_FUNCTIONALS or not is_tensor_of(weights, t.float32, (R, N)):
+            raise ValueError(f"weights must be a contiguous float32 CUDA tensor of shape [R, {N}] with 1 <= R <= {MAX_FUNCTIONALS}")
+
+        def tail(B, out=out):
+            if out is None:
+                out = t.empty((B, T, R), dtype=t.float32, device="cuda")
+            elif not is_tensor_of(out, t.float32, (B, T, R)):
+                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {(B, T, R)}")
+            return (C.c_void_p(weights.data_ptr()), R, C.c_void_p(out.data_ptr())), out
+        return self._surrogate("sgv_project", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -34,6 +34,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     beta, r2 = fit.coefficients(), fit.r2()        # study: coefficients [K, T, N] and the share of the variance they explain, from
                                                    # (2 + K) running arrays [T, N]; fit.covariance() with any scalar per draw
                                                    # (covariates=...)
+    W = region_weights(part_of_node, node_weights=nodal_area)      # quantities of interest that are weighted sums over the mesh: the
+    qoi = s.project(conditions, W)                 # area-weighted mean over every part, or any rows [R, N] (section forces, modal
+    top, when = qoi.peak()                         # amplitudes): qoi.values [P, T, R] from the pass that would store the fields
+                                                   # 
 """
 from __future__ import annotations
 
@@ -44,7 +48,7 @@ import pickle
 
 import numpy as np
 
-from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_PROBES, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
+from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_FUNCTIONALS, MAX_PROBES, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
                      SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of)
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
@@ -174,6 +178,126 @@ def truth_fields(truth, P, T, N):
     if str(a.dtype).replace("torch.", "") != "float32":
         raise ValueError(f"truth: dtype float32 is required, not {a.dtype}")
     return a
+
+
+def functional_weights(weights, num_node):
+    """The weight rows of Surrogate.project as contiguous float32 [R, N]: `weights` of shape [R, N], or [N] for a single functional
+    (then R = 1), 1 <= R <= MAX_FUNCTIONALS, N = num_node, of a floating dtype.  A CUDA tensor stays on the device and comes back as
+    a contiguous float32 CUDA tensor; it is judged by its shape and dtype alone and NOT read back, so its entries are not looked at
+    (a non-finite weight then gives non-finite values).  Anything else is looked at through np.asarray and comes back as a numpy
+    array, every entry finite as float32.  ValueError naming the problem otherwise: a rank other than 1 or 2, a last dimension other
+    than N, R outside its range, a dtype that is not floating, or -- host data -- an entry that is not finite (the first one is
+    named).  numpy only for host data."""
+    dev = _is_device_tensor(weights)
+    a = weights if dev else np.asarray(weights)
+    shape = tuple(int(d) for d in a.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"weights: an [R, N] or [N] array is required, got shape {shape}")
+    if shape[-1] != int(num_node):
+        raise ValueError(f"weights: the last dimension is {shape[-1]}, expected N = {int(num_node)} (shape {shape})")
+    R = shape[0] if len(shape) == 2 else 1
+    if R < 1 or R > MAX_FUNCTIONALS:
+        raise ValueError(f"weights: R = {R} rows, between 1 and {MAX_FUNCTIONALS} are required (call twice for more)")
+    if dev:
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"weights: a floating dtype is required, not {a.dtype}")
+        import torch
+        return a.reshape(R, shape[-1]).to(dtype=torch.float32).contiguous()
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError(f"weights: a floating dtype is required, not {a.dtype}")
+    a = a.reshape(R, shape[-1])
+    with np.errstate(over="ignore"):          # a value beyond float32 becomes inf and is reported below
+        w = np.ascontiguousarray(a, dtype=np.float32)
+    bad = np.argwhere(~np.isfinite(w))
+    if bad.size:
+        r, n = (int(k) for k in bad[0])
+        raise ValueError(f"weights[{r}, {n}] = {float(a[r, n])!r} is not finite as float32")
+    return w
+
+
+def region_weights(labels, num_regions=None, node_weights=None, reduce="mean"):
+    """The weight rows of the most common functionals, means or sums over parts of the mesh, as float32 [R, N] on the host.
+    labels: integer [N], the region of every node, -1 for a node in no region; num_regions: R (default: the largest label + 1);
+    node_weights: [N], finite, the weight of every node inside its region -- a nodal area or mass -- default 1; reduce: "sum" (row
+    r is node_weights on the nodes of region r and 0 elsewhere) or "mean" (that row divided by its sum, in float64, then rounded to
+    float32, so row r gives the weighted mean over region r).  ValueError naming the problem otherwise: labels not 1-D or not of
+    integer dtype, a label below -1 or >= num_regions, more than MAX_FUNCTIONALS regions or none, node_weights of another shape or
+    with an entry that is not finite, and under "mean" a region without nodes or whose weights sum to zero.  numpy only."""
+    if reduce not in ("mean", "sum"):
+        raise ValueError(f"reduce must be 'mean' or 'sum', not {reduce!r}")
+    lab = np.asarray(labels)
+    if lab.ndim != 1:
+        raise ValueError(f"labels: a 1-D array of N region labels is required, got shape {lab.shape}")
+    if not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"labels: an integer dtype is required, not {lab.dtype}")
+    N = lab.size
+    bad = np.flatnonzero(lab < -1)
+    if bad.size:
+        raise ValueError(f"labels[{int(bad[0])}] = {int(lab[bad[0]])} is below -1 (-1 means: in no region)")
+    R = (int(lab.max()) + 1 if N else 0) if num_regions is None else int(num_regions)
+    if R < 1:
+        raise ValueError(f"region_weights: {R} regions, at least one is required")
+    if R > MAX_FUNCTIONALS:
+        raise ValueError(f"region_weights: {R} regions, at most {MAX_FUNCTIONALS} fit one call of project")
+    bad = np.flatnonzero(lab >= R)
+    if bad.size:
+        raise ValueError(f"labels[{int(bad[0])}] = {int(lab[bad[0]])} is outside [-1, num_regions = {R})")
+    if node_weights is None:
+        nw = np.ones(N, np.float64)
+    else:
+        nw = np.asarray(node_weights, dtype=np.float64)
+        if nw.shape != (N,):
+            raise ValueError(f"node_weights: shape {nw.shape}, expected (N,) = {(N,)} as labels")
+        bad = np.flatnonzero(~np.isfinite(nw))
+        if bad.size:
+            raise ValueError(f"node_weights[{int(bad[0])}] = {float(nw[bad[0]])!r} is not finite")
+    W = np.zeros((R, N), np.float64)
+    inside = np.flatnonzero(lab >= 0)
+    W[lab[inside], inside] = nw[inside]
+    if reduce == "mean":
+        for r in range(R):
+            if not np.any(lab == r):
+                raise ValueError(f"region {r} has no nodes: its mean is not defined")
+            total = W[r].sum()
+            if total == 0.0:
+                raise ValueError(f"region {r}: its node weights sum to zero, its mean is not defined")
+            W[r] /= total
+    return W.astype(np.float32)
+
+
+class ProjectResult(_Result):
+    """Surrogate.project's result for P conditions: values [P, T, R] fp32, a device tensor that is the caller's --
+    values[p, t, r] = sum over n of weights[r, n] * field[p, t, n], the time histories of R quantities of interest.  What is derived
+    from it is computed on the engine stream."""
+    FIELDS = ("values",)
+
+    def __init__(self, stream=None, **kw):
+        super().__init__(**kw)
+        self._stream = stream
+
+    def _on_stream(self, fn):
+        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
+            return fn()
+
+    def peak(self):
+        """(the maximum over t [P, R] fp32, its time step [P, R] int64); the smallest t on a tie"""
+        import torch
+
+        def fn():
+            v = self.values
+            T = v.shape[1]
+            top = v.max(dim=1).values
+            steps = torch.arange(T, device=v.device).view(1, T, 1)
+            when = torch.where(v == top.unsqueeze(1), steps, T).min(dim=1).values
+            return top, when
+        return self._on_stream(fn)
+
+    def time_integral(self, dt=1.0):
+        """the trapezoid rule over t at spacing dt, summed in float64: [P, R] fp32 (zero for a single time step)"""
+        def fn():
+            v = self.values.double()
+            return ((v[:, 1:] + v[:, :-1]).sum(dim=1) * (float(dt) / 2.0)).float()
+        return self._on_stream(fn)
 
 
 class ScoreResult(_Result):
@@ -769,6 +893,41 @@ class Surrogate:
                 where[:, lo:hi].copy_(out["frame_where"].permute(2, 0, 1))
         return SweepResult(node_max=node[0], node_min=node[1], node_mean=node[2], t_max=when[0], t_min=when[1],
                            frame_max=frame[0], frame_min=frame[1], n_max=where[0], n_min=where[1], probes=hist)
+
+    def project(self, conditions, weights, mode="fix"):
+        """Quantities of interest of predict(conditions) that are weighted sums over the mesh, without the fields: weights [R, N] or
+        [N] (see functional_weights; region_weights builds the rows of means or sums over parts) -> a ProjectResult whose values
+        [P, T, R] are sum_n weights[r, n] * field[p, t, n] -- resultant forces, weighted means, interpolated sensors, modal
+        amplitudes.  The recon head's last pass multiplies the values predict() would store (bit for bit the same) into the weight
+        rows on the matrix cores, fp32, in a fixed order inside fixed shares of the mesh, and adds the shares in float64: a value
+        depends on its condition, time step and weight row alone, and the decoder's noise of condition p is row p of the streams
+        one call over all conditions would draw from (Engine.set_draw_row; mode "fix" scales the noise by 1e-10, it does not remove
+        it), so the batch size does not show in the bits in either mode, and 4 T R bytes per condition leave the decoder instead
+        of 4 T N.  The weights are uploaded once per call and every batch is written straight
+        into its rows of `values`.  Batching, streams, the single input-range decision and `mode` are sweep()'s: no host wait between
+        batches.  values[:, t, :] is a [P, R] array of scalars per draw: what regress(covariates=...) takes."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        w = functional_weights(weights, self.N)
+        if not t.is_tensor(w):
+            w = t.from_numpy(w)
+        values = t.empty((P, self.T, w.shape[0]), dtype=t.float32, device="cuda")          # the result: the caller's stream owns it
+        eng = self.eng
+        at = eng.train_state()
+        with _engine_stream(self._stream):
+            w = w.to(device="cuda", non_blocking=True)
+            if w.data_ptr() % 16:
+                w = w.clone()          # a view at an odd offset: the kernel loads 16 bytes at a time
+            try:
+                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
+                    # every batch draws from the streams of the call's first draw, condition p from their row p: the noise one batch
+                    # over all conditions would get, so the draw position ends where one call leaves it
+                    eng.set_train_state(at["step"], at["seed"], at["draw"])
+                    eng.set_draw_row(lo)
+                    eng.project(lat, xs, self.data_scale, self.data_min, w, fix=mode == "fix", out=values[lo:hi])
+            finally:
+                eng.set_draw_row(0)
+        return ProjectResult(stream=self._stream, values=values)
 
     def score(self, conditions, truth, mode="fix"):
         """How wrong predict(conditions) is against held-out fields, without the fields: truth [P, T, N] fp32 in physical units (the

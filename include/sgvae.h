@@ -150,7 +150,7 @@ int sgv_seed(sgv_engine* e, uint64_t seed);
  * exactly the noise one rank draws for B samples.  Default (0, 1). */
 int sgv_set_shard(sgv_engine* e, int rank, int world);
 /* Noise of a study that is cut into batches: with first_row = r, sample b of the following decoder passes that draw their noise
- * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project) takes row r + b of the streams the call draws from instead of
+ * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal) takes row r + b of the streams the call draws from instead of
  * row b.  sgv_forward and sgv_decode are not affected.  A caller that puts the draw position back in front of every batch (sgv_set_train_state) and sets
  * first_row to the index of the batch's first sample gives sample p of the study the noise one call over all samples would give
  * it, whatever the batch size; Surrogate.project does.  The passes that count members themselves (sgv_ensemble, sgv_sobol,
@@ -348,6 +348,18 @@ int sgv_regress(sgv_engine* e, const float* z_dev, const float* xs_dev, int batc
  * is no forward pass to read from, as after sgv_generate. */
 int sgv_project(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                 const float* min_dev, const float* weights_dev, int n_func, float* out_dev);
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the temporal pass: n_func = R linear
+ * functionals of the field over TIME, 1 <= R <= 32, the field itself never stored.  weights_dev fp32 [R][T] dense on the device,
+ * 4-byte aligned; out_dev fp32 [batch][R][N] on the device, 16-byte aligned (its rows are written 32 bytes at a time):
+ *   out[b][r][n] = sum over t of weights[r][t] * x[b][t][n],  x the value sgv_generate would store (SGV_LAYOUT_TN).
+ * One fp32 fused multiply-add chain per output over t ascending, on the matrix cores; no partial sums, no atomics.  out[b][r][n]
+ * depends on sample b, weight row r and node n alone, so any cut of the conditions into batches, any R and any order of the rows
+ * give the same bits.  A transposed copy of the weights lies in the engine's workspace (sized at sgv_prepare); nothing is
+ * allocated.  SGV_ERR_ARG before anything is enqueued: e, z_dev, scale_dev, min_dev, weights_dev or out_dev NULL, n_func outside
+ * [1, 32], a misaligned pointer, the checks of sgv_decode.  Synchronises nothing.  Afterwards there is no forward pass to read
+ * from, as after sgv_generate. */
+int sgv_temporal(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                 const float* min_dev, const float* weights_dev, int n_func, float* out_dev);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -658,6 +670,13 @@ int sgv_test_recon_regress(int dtype, const void* y, long ldy, double* sums, con
 int sgv_test_recon_project(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                            const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
                            void* stream);
+/* The kernel of sgv_temporal on caller-owned buffers: inputs as sgv_test_recon_physical, weights fp32 [n_func][T] and out fp32
+ * [B][n_func][C] on the device, then the statistics of y and the temporal pass with a workspace of its own.  SGV_ERR_ARG, nothing
+ * launched: a NULL input (weights included), out NULL, n_func outside [1, 32], B or T < 1, C < 8 or C % 8 != 0, a bad row stride, a
+ * misaligned pointer (y and out 16 bytes; weights 4). */
+int sgv_test_recon_temporal(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
+                            void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

@@ -1333,3 +1333,128 @@ int ew_recon_project(int dtype, GNParams p, const float* scale, const float* mn,
     hipLaunchKernelGGL(recon_project_finish_kernel, dim3(cdiv_i(rows * o.n_func, 256)), dim3(256), 0, s, o.work, rows * o.n_func, nchunk, o.n_func, o.out);
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------
+// Surrogate temporal functionals (sgv_temporal): R weighted sums over time per (sample, node), out[b][r][n] = sum_t W[r][t] x[b][t][n]
+// with x the value recon_phys_val gives -- the dual of sgv_project and the second tail on the matrix cores, v_mfma_f32_32x32x2_f32 again:
+// exact fp32 products and one fused multiply-add chain per output, ascending in t.
+// Geometry: the contraction index t is the MFMA's k, two time rows per step.  The weights are the A operand: lane l holds
+// W[r = l & 31][t0 + (l >> 5)], rows past R zeros; the kernel reads them from a transposed, zero-padded copy wt [T_pad][32] (T_pad = T
+// rounded up to 2) that recon_temporal_weights_kernel writes in front of it, one coalesced dword per lane and step.  The field is the B
+// operand: lane l loads 8 channels (16 / 32 bytes) of row t0 + (l >> 5) at channel c0 = c_w + 8 (l & 31), and MFMA e = 0..7 of the step
+// takes the lane's channel e, so a wave reads two contiguous rows of TP_WAVE_COLS = 256 channels per step and owns 8 accumulator tiles
+// of 32 functionals x 32 channels.  In the C / D map register v of lane l is functional (v & 3) + 8 (v >> 2) + 4 (l >> 5) at the lane's
+// own column, i.e. at its 8 consecutive channels over the 8 tiles: the stores to out[b][r][c0 .. c0 + 7] are 32 bytes per lane and
+// 1 KiB contiguous per half-wave, straight from the registers.  The channel constants and the sample's (mean, rstd) of the lane's 8
+// channels are loaded once for all T.
+// Shares: a block is one sample and TP_BLOCK_COLS channels, its four waves TP_WAVE_COLS contiguous ones each; they never meet: no
+// reduction across threads, no LDS besides gn_consts' table, no workspace besides wt, no finish kernel, no atomics.  An output's chain
+// runs over t alone and an output element of the MFMA depends on its own row of A and column of B alone: hence the invariances of
+// sgv_ew.h.  For odd T the upper half of the last step carries zeros on both operands and loads row T - 1 again; lanes past C load
+// the wave's first octet again, carry zeros on B (and their weight on A) and store nothing.  The y rows (and the weights) of
+// tp_flight() steps are in flight: a register ring, the loads of step s + tp_flight() are issued as soon as step s is unpacked.
+// ------------------------------------------------------------------------------------------
+constexpr int TP_WAVE_COLS = 256;                   // channels of a wave: 32 lanes x 8
+constexpr int TP_BLOCK_COLS = 4 * TP_WAVE_COLS;     // channels of a block
+template <typename T> constexpr int tp_flight() { return sizeof(T) == 2 ? 8 : 4; }          // steps in flight: 8 KiB of y per wave and 32 registers per lane in either dtype
+static int tp_tpad(int T) { return (T + 1) & ~1; }
+size_t ew_recon_temporal_work_floats(int T) { return (size_t)tp_tpad(T) * SGV_MAX_TEMPORAL; }
+
+// weights [R][T] -> wt [T_pad][32], zeros at r >= R and t >= T: one thread per element of wt
+__global__ __launch_bounds__(256) void recon_temporal_weights_kernel(const float* __restrict__ w, int R, int T, int n, float* __restrict__ wt) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int t = i >> 5, r = i & 31;
+    wt[i] = r < R && t < T ? w[(long)r * T + t] : 0.f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, 2) void recon_temporal_kernel(const GNParams p, const ReconPhys q, const ReconTemporal o) {
+    constexpr int F = tp_flight<T>();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
+    const int c_w = blockIdx.x * TP_BLOCK_COLS + wv * TP_WAVE_COLS;
+    GNCtx c;
+    c.b = blockIdx.z;
+    c.c0 = c_w + 8 * lr;
+    c.col_ok = c.c0 < p.C;
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);          // all 256 threads
+    if (c_w >= p.C) return;               // a whole wave past C; no barrier below
+    // An MFMA reads the registers of every lane whatever EXEC says, and a lane's A operand (its weight) goes into its functional at
+    // ALL columns: the lanes past C stay in the loop and carry their weights.  Their B operand reaches their own columns only; it is
+    // zero, their y loads are the wave's first octet again and nothing of theirs is stored.
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, c.col_ok); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const T* const y = reinterpret_cast<const T*>(p.y) + (long)c.b * p.T * p.ldy + (c.col_ok ? c.c0 : c_w);
+    const float* const wt = o.work + lr;
+    const int nsteps = (p.T + 1) >> 1;
+    f32x16 acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[e][v] = 0.f;
+    // step s: rows 2 s + h.  A row past T - 1 (the upper half of the last step of an odd T, or a step past the last) is row T - 1 again,
+    // loaded and not used; wt is read inside [0, T_pad) only
+    Raw8<T> ry[F];
+    float a[F];
+#pragma unroll
+    for (int u = 0; u < F; ++u) {
+        const int t = 2 * min(u, nsteps - 1) + h;
+        raw_load(y + (long)min(t, p.T - 1) * p.ldy, ry[u]);
+        a[u] = wt[t * 32];
+    }
+    for (int s0 = 0; s0 < nsteps; s0 += F) {
+#pragma unroll
+        for (int u = 0; u < F; ++u) {
+            const int s = s0 + u;
+            if (s >= nsteps) break;          // wave-uniform
+            float v[8];
+            raw_unpack(ry[u], v);
+            const float au = a[u];
+            const bool t_ok = c.col_ok && 2 * s + h < p.T;
+            {
+                const int t = 2 * min(s + F, nsteps - 1) + h;
+                raw_load(y + (long)min(t, p.T - 1) * p.ldy, ry[u]);
+                a[u] = wt[t * 32];
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float x = recon_phys_val(v[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+                acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(au, t_ok ? x : 0.f, acc[e], 0, 0, 0);
+            }
+        }
+    }
+    // C / D map of the 32x32 forms: register v of lane l holds row (v & 3) + 8 (v >> 2) + 4 (l >> 5), column l & 31
+    float* const out = o.out + (long)c.b * o.n_func * p.C + c.c0;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int r = (v & 3) + 8 * (v >> 2) + 4 * h;
+        if (c.col_ok && r < o.n_func) {
+            float x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = acc[e][v];
+            store8(out + (long)r * p.C, x);
+        }
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconTemporal (sgv_ew.h), o.work = ew_recon_temporal_work_floats floats.  Non-zero
+// (nothing launched): -1 null input (weights included), -2 no output, -3 bad shape or n_func outside [1, 32], -4 y or out not 16-byte
+// aligned or weights or work not 4-byte aligned, -6 no workspace
+int ew_recon_temporal(int dtype, GNParams p, const float* scale, const float* mn, const ReconTemporal& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.weights) return -1;
+    if (!o.out) return -2;
+    if (o.n_func < 1 || o.n_func > SGV_MAX_TEMPORAL) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.out) & 15) return -4;
+    if (((uintptr_t)o.weights | (uintptr_t)o.work) & 3) return -4;
+    if (!o.work) return -6;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const int n = tp_tpad(p.T) * SGV_MAX_TEMPORAL;
+    hipLaunchKernelGGL(recon_temporal_weights_kernel, dim3(cdiv_i(n, 256)), dim3(256), 0, s, o.weights, o.n_func, p.T, n, o.work);
+    const dim3 grid(cdiv_i(p.C, TP_BLOCK_COLS), 1, p.B);
+    if (dtype == 1) hipLaunchKernelGGL((recon_temporal_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o);
+    else hipLaunchKernelGGL((recon_temporal_kernel<float>), grid, dim3(256), 0, s, p, q, o);
+    return 0;
+}

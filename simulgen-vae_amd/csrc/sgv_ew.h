@@ -202,6 +202,23 @@ struct ReconProject {
 };
 size_t ew_recon_project_work_floats(int B, int T, int C, int R);
 int ew_recon_project(int dtype, GNParams p, const float* scale, const float* mn, const ReconProject& o, hipStream_t s);
+// recon head -> n_func = R linear functionals over TIME of the physical field, 1 <= R <= SGV_MAX_TEMPORAL, the field never stored:
+//   out[b][r][n] = sum over t of weights[r][t] * x[b][t][n],  x the value ew_recon_physical would store (layout [B][T][C]).
+// weights fp32 [R][T] dense, 4-byte aligned (input; read once by a kernel that writes the transposed, zero-padded copy the pass
+// reads); out fp32 [B][R][C], 16-byte aligned (its rows are written 32 bytes at a time, and C % 8 == 0 keeps every row aligned);
+// work: ew_recon_temporal_work_floats floats, that copy.  One fp32 fused multiply-add chain per output over t ascending, from 0,
+// nothing else: out[b][r][n] depends on sample b, weight row r and channel n alone -- a row gives alone the bits it gives among
+// 32, in any order of the rows; a sample gives the bits it gives in any batch and at any place in it -- and two launches are
+// bitwise equal.  No atomics, no partial sums.
+// Non-zero (nothing launched): -1 null input (weights included), -2 no output, -3 bad shape or R outside [1, 32], -4 y or out not
+// 16-byte aligned or weights or work not 4-byte aligned, -6 no workspace
+constexpr int SGV_MAX_TEMPORAL = 32;
+struct ReconTemporal {
+    const float* weights = nullptr; int n_func = 0; float* out = nullptr;
+    float* work = nullptr;
+};
+size_t ew_recon_temporal_work_floats(int T);
+int ew_recon_temporal(int dtype, GNParams p, const float* scale, const float* mn, const ReconTemporal& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

@@ -377,6 +377,19 @@ int sgv_test_recon_project(int dtype, const void* y, long ldy, double* sums, con
         return ew_recon_project(dtype, q, scale, min, o, s);
     });
 }
+int sgv_test_recon_temporal(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                            const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
+                            void* stream) {
+    const char* me = "sgv_test_recon_temporal";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(temporal_args_ok(me, weights, n_func, out));
+    return recon_hook_run(me, dtype, p, ew_recon_temporal_work_floats(T), stream, [&](const GNParams& q, float* work, hipStream_t s) {
+        ReconTemporal o;
+        o.weights = weights; o.n_func = n_func; o.out = out; o.work = work;
+        return ew_recon_temporal(dtype, q, scale, min, o, s);
+    });
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

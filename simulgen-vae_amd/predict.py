@@ -38,6 +38,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     qoi = s.project(conditions, W)                 # area-weighted mean over every part, or any rows [R, N] (section forces, modal
     top, when = qoi.peak()                         # amplitudes): qoi.values [P, T, R] from the pass that would store the fields
                                                    # 
+    spec = s.temporal(conditions, fourier_rows(T, [f1, f2], dt))   # quantities that are weighted sums over time, per node: Fourier
+    amp, phi = spec.amplitude(), spec.phase()      # amplitude and phase at a few frequencies, window means (window_rows), time
+                                                   # integrals, filtered values, any rows [R, T]: spec.values [P, R, N], 4 R N bytes
+                                                   # per condition instead of 4 T N
 """
 from __future__ import annotations
 
@@ -48,7 +52,7 @@ import pickle
 
 import numpy as np
 
-from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_FUNCTIONALS, MAX_PROBES, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
+from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_FUNCTIONALS, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
                      SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of)
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
@@ -297,6 +301,171 @@ class ProjectResult(_Result):
         def fn():
             v = self.values.double()
             return ((v[:, 1:] + v[:, :-1]).sum(dim=1) * (float(dt) / 2.0)).float()
+        return self._on_stream(fn)
+
+
+def temporal_weights(weights, T):
+    """The weight rows of Surrogate.temporal as contiguous float32 [R, T]: `weights` of shape [R, T], or [T] for a single functional
+    (then R = 1), 1 <= R <= MAX_TEMPORAL, T = num_time, of a floating dtype.  A CUDA tensor stays on the device and comes back as a
+    contiguous float32 CUDA tensor; it is judged by its shape and dtype alone and NOT read back, so its entries are not looked at (a
+    non-finite weight then gives non-finite values).  Anything else is looked at through np.asarray and comes back as a numpy array,
+    every entry finite as float32.  ValueError naming the problem otherwise: a rank other than 1 or 2, a last dimension other than
+    T, R outside its range, a dtype that is not floating, or -- host data -- an entry that is not finite (the first one is named by
+    row and time step).  numpy only for host data."""
+    dev = _is_device_tensor(weights)
+    a = weights if dev else np.asarray(weights)
+    shape = tuple(int(d) for d in a.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError(f"weights: an [R, T] or [T] array is required, got shape {shape}")
+    if shape[-1] != int(T):
+        raise ValueError(f"weights: the last dimension is {shape[-1]}, expected T = {int(T)} (shape {shape})")
+    R = shape[0] if len(shape) == 2 else 1
+    if R < 1 or R > MAX_TEMPORAL:
+        raise ValueError(f"weights: R = {R} rows, between 1 and {MAX_TEMPORAL} are required (call twice for more)")
+    if dev:
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"weights: a floating dtype is required, not {a.dtype}")
+        import torch
+        return a.reshape(R, shape[-1]).to(dtype=torch.float32).contiguous()
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError(f"weights: a floating dtype is required, not {a.dtype}")
+    a = a.reshape(R, shape[-1])
+    with np.errstate(over="ignore"):          # a value beyond float32 becomes inf and is reported below
+        w = np.ascontiguousarray(a, dtype=np.float32)
+    bad = np.argwhere(~np.isfinite(w))
+    if bad.size:
+        r, t = (int(k) for k in bad[0])
+        raise ValueError(f"weights: row {r} is not finite as float32 at time step {t}: weights[{r}, {t}] = {float(a[r, t])!r}")
+    return w
+
+
+def fourier_rows(T, freqs, dt=1.0, window=None):
+    """The weight rows of Fourier amplitudes at a few frequencies, float32 [2 F, T] on the host: for frequency f (in cycles per unit
+    of dt, 0 <= f <= 1 / (2 dt)) row 2 i is c w[t] cos(2 pi f t dt) and row 2 i + 1 is c w[t] sin(2 pi f t dt), w the window
+    (default: all ones) and c = 2 / sum(w), or 1 / sum(w) where the sine row vanishes (f = 0, and the Nyquist frequency of an even
+    T): a sinusoid A cos(2 pi f t dt - phi) at an exact bin frequency f = k / (T dt) then gives (A cos phi, A sin phi), so
+    TemporalResult.amplitude() is A and .phase() is phi.  window: an optional taper of length T, finite, with a non-zero sum; it
+    is folded into the rows and the rows are renormalised by its sum, so the amplitude of a bin-centred sinusoid is still A (under
+    a taper the neighbouring bins leak into it as they do into any windowed transform).  Computed in float64 and rounded to
+    float32 once.  ValueError naming the problem otherwise: T < 1, no frequency or more than MAX_TEMPORAL / 2, a frequency that is
+    not finite, negative or above Nyquist, dt that is not positive and finite, a window of another shape, with an entry that is not
+    finite, or whose sum is zero.  numpy only."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"fourier_rows: T = {T}, at least one time step is required")
+    dt = float(dt)
+    if not (np.isfinite(dt) and dt > 0.0):
+        raise ValueError(f"fourier_rows: dt = {dt!r} must be positive and finite")
+    f = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    if f.ndim != 1 or f.size < 1:
+        raise ValueError(f"fourier_rows: a list of frequencies is required, got shape {f.shape}")
+    if 2 * f.size > MAX_TEMPORAL:
+        raise ValueError(f"fourier_rows: {f.size} frequencies give {2 * f.size} rows, at most {MAX_TEMPORAL} fit one call of temporal")
+    nyq = 0.5 / dt
+    for i, fi in enumerate(f):
+        if not np.isfinite(fi) or fi < 0.0 or fi > nyq * (1.0 + 1e-12):
+            raise ValueError(f"fourier_rows: freqs[{i}] = {float(fi)!r} is outside [0, 1 / (2 dt) = {nyq!r}]")
+    if window is None:
+        w = np.ones(T, np.float64)
+    else:
+        w = np.asarray(window, dtype=np.float64)
+        if w.shape != (T,):
+            raise ValueError(f"fourier_rows: window has shape {w.shape}, expected (T,) = {(T,)}")
+        bad = np.flatnonzero(~np.isfinite(w))
+        if bad.size:
+            raise ValueError(f"fourier_rows: window[{int(bad[0])}] = {float(w[bad[0]])!r} is not finite")
+    total = w.sum()
+    if total == 0.0:
+        raise ValueError("fourier_rows: the window sums to zero, the rows cannot be normalised")
+    steps = np.arange(T, dtype=np.float64)
+    rows = np.empty((2 * f.size, T), np.float64)
+    for i, fi in enumerate(f):
+        cyc = fi * dt * steps          # cycles at every time step; reduced mod 1 in float64 before the 2 pi, exact at bin frequencies of moderate T
+        ang = 2.0 * np.pi * (cyc - np.floor(cyc))
+        s = np.sin(ang)
+        alone = not np.any(np.abs(s) > 1e-9)          # f = 0 or Nyquist on the grid: the cosine row carries the whole amplitude
+        c = (1.0 if alone else 2.0) / total
+        rows[2 * i] = c * w * np.cos(ang)
+        rows[2 * i + 1] = 0.0 if alone else c * w * s
+    return rows.astype(np.float32)
+
+
+def window_rows(T, edges):
+    """The weight rows of means over time windows, float32 [len(edges) - 1, T] on the host: row i is 1 / (edges[i + 1] - edges[i])
+    on the time steps edges[i] : edges[i + 1] and 0 elsewhere, so every row sums to 1 -- a coarse time history, or with two edges
+    the mean over one window.  edges: integers, strictly increasing, within [0, T].  ValueError naming the problem otherwise: T < 1,
+    edges not 1-D, not of integer dtype, fewer than two, more than MAX_TEMPORAL + 1, outside [0, T] or not strictly increasing (the
+    first offending edge is named).  numpy only."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"window_rows: T = {T}, at least one time step is required")
+    e = np.asarray(edges)
+    if e.ndim != 1:
+        raise ValueError(f"window_rows: edges must be a 1-D array, got shape {e.shape}")
+    if not np.issubdtype(e.dtype, np.integer):
+        raise ValueError(f"window_rows: edges must be of an integer dtype, not {e.dtype}")
+    if e.size < 2:
+        raise ValueError(f"window_rows: {e.size} edges, at least two are required")
+    if e.size - 1 > MAX_TEMPORAL:
+        raise ValueError(f"window_rows: {e.size - 1} windows, at most {MAX_TEMPORAL} fit one call of temporal")
+    for i, v in enumerate(e):
+        if v < 0 or v > T:
+            raise ValueError(f"window_rows: edges[{i}] = {int(v)} is outside [0, T = {T}]")
+        if i and v <= e[i - 1]:
+            raise ValueError(f"window_rows: edges[{i}] = {int(v)} is not above edges[{i - 1}] = {int(e[i - 1])}: strictly increasing edges are required")
+    rows = np.zeros((e.size - 1, T), np.float64)
+    for i in range(e.size - 1):
+        rows[i, int(e[i]):int(e[i + 1])] = 1.0 / float(int(e[i + 1]) - int(e[i]))
+    return rows.astype(np.float32)
+
+
+class TemporalResult(_Result):
+    """Surrogate.temporal's result for P conditions: values [P, R, N] fp32, a device tensor that is the caller's --
+    values[p, r, n] = sum over t of weights[r, t] * field[p, t, n], R fields of quantities over time.  What is derived from it is
+    computed on the engine stream."""
+    FIELDS = ("values",)
+
+    def __init__(self, stream=None, **kw):
+        super().__init__(**kw)
+        self._stream = stream
+
+    def _on_stream(self, fn):
+        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
+            return fn()
+
+    def _pairs(self):
+        v = self.values
+        if v.shape[1] % 2:
+            raise ValueError(f"the rows are taken as consecutive (cos, sin) pairs (fourier_rows): R = {v.shape[1]} is odd")
+        return v[:, 0::2], v[:, 1::2]
+
+    def amplitude(self):
+        """hypot(cos row, sin row) of every consecutive pair of rows: [P, R / 2, N] fp32; ValueError for an odd R"""
+        def fn():
+            c, s = self._pairs()
+            return c.hypot(s)
+        return self._on_stream(fn)
+
+    def phase(self):
+        """atan2(sin row, cos row) of every consecutive pair of rows, in (-pi, pi]: [P, R / 2, N] fp32 -- phi of A cos(w t - phi)
+        under fourier_rows; ValueError for an odd R"""
+        def fn():
+            c, s = self._pairs()
+            return s.atan2(c)
+        return self._on_stream(fn)
+
+    def peak(self):
+        """(the node of the largest |value| [P, R] int64, that value with its sign [P, R] fp32); the smallest node on a tie"""
+        import torch
+
+        def fn():
+            v = self.values
+            N = v.shape[2]
+            mag = v.abs()
+            top = mag.max(dim=2).values
+            nodes = torch.arange(N, device=v.device).view(1, 1, N)
+            where = torch.where(mag == top.unsqueeze(2), nodes, N).min(dim=2).values
+            return where, v.gather(2, where.clamp(max=N - 1).unsqueeze(2)).squeeze(2)
         return self._on_stream(fn)
 
 
@@ -928,6 +1097,37 @@ class Surrogate:
             finally:
                 eng.set_draw_row(0)
         return ProjectResult(stream=self._stream, values=values)
+
+    def temporal(self, conditions, weights, mode="fix"):
+        """Quantities of predict(conditions) that are weighted sums over time, per node, without the fields: weights [R, T] or [T]
+        (see temporal_weights; fourier_rows builds the rows of Fourier amplitudes, window_rows those of window means) -> a
+        TemporalResult whose values [P, R, N] are sum_t weights[r, t] * field[p, t, n] -- spectral amplitudes, window means, time
+        integrals, filtered values, amplitudes on temporal modes.  The recon head's last pass multiplies the values predict() would
+        store (bit for bit the same) into the weight rows on the matrix cores, one fp32 fused multiply-add chain per value over t
+        ascending: a value depends on its condition, weight row and node alone, and the decoder's noise of condition p is row p of
+        the streams one call over all conditions would draw from (Engine.set_draw_row), so the batch size does not show in the
+        bits in either mode, and 4 R N bytes per condition leave the decoder instead of 4 T N.  The weights are uploaded once per
+        call and every batch is written straight into its rows of `values`.  Batching, streams, the single input-range decision and
+        `mode` are project()'s: no host wait between batches."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        w = temporal_weights(weights, self.T)
+        if not t.is_tensor(w):
+            w = t.from_numpy(w)
+        values = t.empty((P, w.shape[0], self.N), dtype=t.float32, device="cuda")          # the result: the caller's stream owns it
+        eng = self.eng
+        at = eng.train_state()
+        with _engine_stream(self._stream):
+            w = w.to(device="cuda", non_blocking=True)
+            try:
+                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
+                    # as in project(): every batch draws from the streams of the call's first draw, condition p from their row p
+                    eng.set_train_state(at["step"], at["seed"], at["draw"])
+                    eng.set_draw_row(lo)
+                    eng.temporal(lat, xs, self.data_scale, self.data_min, w, fix=mode == "fix", out=values[lo:hi])
+            finally:
+                eng.set_draw_row(0)
+        return TemporalResult(stream=self._stream, values=values)
 
     def score(self, conditions, truth, mode="fix"):
         """How wrong predict(conditions) is against held-out fields, without the fields: truth [P, T, N] fp32 in physical units (the

@@ -150,7 +150,7 @@ int sgv_seed(sgv_engine* e, uint64_t seed);
  * exactly the noise one rank draws for B samples.  Default (0, 1). */
 int sgv_set_shard(sgv_engine* e, int rank, int world);
 /* Noise of a study that is cut into batches: with first_row = r, sample b of the following decoder passes that draw their noise
- * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal) takes row r + b of the streams the call draws from instead of
+ * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal, sgv_gram) takes row r + b of the streams the call draws from instead of
  * row b.  sgv_forward and sgv_decode are not affected.  A caller that puts the draw position back in front of every batch (sgv_set_train_state) and sets
  * first_row to the index of the batch's first sample gives sample p of the study the noise one call over all samples would give
  * it, whatever the batch size; Surrogate.project does.  The passes that count members themselves (sgv_ensemble, sgv_sobol,
@@ -360,6 +360,21 @@ int sgv_project(sgv_engine* e, const float* z_dev, const float* xs_dev, int batc
  * from, as after sgv_generate. */
 int sgv_temporal(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                  const float* min_dev, const float* weights_dev, int n_func, float* out_dev);
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the Gram pass: the temporal Gram matrix of
+ * the field per sample, the field itself never stored.  node_weights_dev_or_NULL = w and offset_dev_or_NULL = m fp32 [N] on the
+ * device, 16-byte aligned, NULL for w = 1 / m = 0 (arrays of ones / zeros give the same bits); out_dev fp32 [batch][T][T] dense on the
+ * device, 4-byte aligned:
+ *   out[b][t][t'] = sum over n of w[n] * (x[b][t][n] - m[n]) * (x[b][t'][n] - m[n]),  x the value sgv_generate would store.
+ * num_time <= 256 (SGV_MAX_GRAM_T).  x - m is rounded once to fp32 and is both operands of the matrix cores' fp32 multiply-add; for
+ * t <= t' the element is the chain of fl(w[n] d[t][n]) * d[t'][n] (the smaller time index carries the weight) over blocks of 6144
+ * nodes, the blocks added in ascending order in fp64 and rounded once, and (t', t) is its copy: out is bitwise symmetric, its
+ * diagonal is >= 0 for w >= 0, and out[b] depends on sample b alone, so any cut of the conditions into batches gives the same bits.
+ * The per-block partials lie in the engine's workspace (sized at sgv_create when num_time is within the limit); nothing is allocated,
+ * no atomics.  The entries of w and m are not looked at: a negative weight is taken as it is.  SGV_ERR_ARG before anything is
+ * enqueued: e, z_dev, scale_dev, min_dev or out_dev NULL, num_time > 256, a misaligned pointer, the checks of sgv_decode.
+ * Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
+int sgv_gram(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+             const float* min_dev, const float* node_weights_dev_or_NULL, const float* offset_dev_or_NULL, float* out_dev);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -677,6 +692,12 @@ int sgv_test_recon_project(int dtype, const void* y, long ldy, double* sums, con
 int sgv_test_recon_temporal(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
                             void* stream);
+/* The kernel of sgv_gram on caller-owned buffers: inputs as sgv_test_recon_physical, node_weights and offset fp32 [C] on the device
+ * or NULL, out fp32 [B][T][T] on the device, then the statistics of y and the Gram pass with a workspace of its own.  SGV_ERR_ARG,
+ * nothing launched: a NULL input, out NULL, B or T < 1, T > 256, C < 8 or C % 8 != 0, a bad row stride, a misaligned pointer (y,
+ * node_weights and offset 16 bytes; out 4). */
+int sgv_test_recon_gram(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta, const float* scale,
+                        const float* min, const float* node_weights, const float* offset, float* out, int B, int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

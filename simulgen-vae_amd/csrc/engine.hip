@@ -522,6 +522,7 @@ int sgv_create(const sgv_config* cfg, void* hip_stream, sgv_engine** out) {
     e->colpart_floats = std::max(e->colpart_floats, ew_recon_summary_work_floats(e->maxB, e->T, e->N));   // sgv_summarize's frame partials (smaller up to T of several hundred)
     e->colpart_floats = std::max(e->colpart_floats, ew_recon_project_work_floats(e->maxB, e->T, e->N, SGV_MAX_FUNCTIONALS));   // sgv_project's partials at 32 rows
     e->colpart_floats = std::max(e->colpart_floats, ew_recon_temporal_work_floats(e->T));   // sgv_temporal's transposed weights [T_pad][32]
+    if (e->T <= SGV_MAX_GRAM_T) e->colpart_floats = std::max(e->colpart_floats, ew_recon_gram_work_floats(e->maxB, e->T, e->N));   // sgv_gram's per-block tile partials
     e->xpose_floats = (size_t)M * std::max(e->N, 8);
     for (int i = 0; i < e->n; ++i) e->xpose_floats = std::max(e->xpose_floats, (size_t)M * e->enc[i] * 2);
 #define ALLOC(ptr, bytes)                                                                                      \
@@ -898,9 +899,9 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 // What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
 // (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble), the sums of a Sobol study
 // (sgv_sobol), the histogram of the members (sgv_distribution), their co-moments with the covariates (sgv_regress), weighted sums
-// over the mesh (sgv_project) or weighted sums over time (sgv_temporal); only the members of `kind` are read.
+// over the mesh (sgv_project), weighted sums over time (sgv_temporal) or the temporal Gram matrix (sgv_gram); only the members of `kind` are read.
 struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS, PROJECT, TEMPORAL } kind;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS, PROJECT, TEMPORAL, GRAM } kind;
     const float* scale; const float* mn;
     int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
     ReconSummary sum;                                          // SUMMARY
@@ -911,6 +912,7 @@ struct GenOut {
     ReconRegress reg; int reg_cov = 0; long reg_count = 0;     // REGRESS
     ReconProject proj;                                         // PROJECT
     ReconTemporal temp;                                        // TEMPORAL
+    ReconGram gram;                                            // GRAM
     // ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
     bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION || kind == REGRESS; }
     long members_before() const {
@@ -918,18 +920,19 @@ struct GenOut {
     }
 };
 // The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass and
-// the per-block partials of the project pass go to e->colpart, as does the transposed copy of the weights of the temporal pass, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
+// the per-block partials of the project and the Gram pass go to e->colpart, as does the transposed copy of the weights of the temporal pass, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
 // the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol, the
 // distribution and the regression pass.
 static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress", "recon_project", "recon_temporal"};
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress", "recon_project", "recon_temporal", "recon_gram"};
     static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
                                            "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
                                            "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)",
                                            "sgv_distribution: the distribution pass rejected its arguments (%d)",
                                            "sgv_regress: the regression pass rejected its arguments (%d)",
                                            "sgv_project: the project pass rejected its arguments (%d)",
-                                           "sgv_temporal: the temporal pass rejected its arguments (%d)"};
+                                           "sgv_temporal: the temporal pass rejected its arguments (%d)",
+                                           "sgv_gram: the Gram pass rejected its arguments (%d)"};
     ScopedTimer tm(e, tag[g.kind], nullptr);
     int r = 0;
     switch (g.kind) {
@@ -942,6 +945,7 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
     case GenOut::REGRESS: r = ew_recon_regress(e->dt, p, g.scale, g.mn, g.reg_cov, g.reg_count, g.reg, e->stream); break;
     case GenOut::PROJECT: { ReconProject o = g.proj; o.work = e->colpart; r = ew_recon_project(e->dt, p, g.scale, g.mn, o, e->stream); break; }
     case GenOut::TEMPORAL: { ReconTemporal o = g.temp; o.work = e->colpart; r = ew_recon_temporal(e->dt, p, g.scale, g.mn, o, e->stream); break; }
+    case GenOut::GRAM: { ReconGram o = g.gram; o.work = e->colpart; r = ew_recon_gram(e->dt, p, g.scale, g.mn, o, e->stream); break; }
     }
     return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
 }
@@ -1190,6 +1194,15 @@ int sgv_temporal(sgv_engine* e, const float* z_dev, const float* xs_dev, int bat
     GenOut gen = {GenOut::TEMPORAL, scale_dev, min_dev};
     gen.temp.weights = weights_dev; gen.temp.n_func = n_func; gen.temp.out = out_dev;
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_temporal", gen);
+}
+
+int sgv_gram(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+             const float* min_dev, const float* node_weights_dev_or_NULL, const float* offset_dev_or_NULL, float* out_dev) {
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_gram: null argument");
+    CHK(gram_args_ok("sgv_gram", e->T, node_weights_dev_or_NULL, offset_dev_or_NULL, out_dev));
+    GenOut gen = {GenOut::GRAM, scale_dev, min_dev};
+    gen.gram.node_weights = node_weights_dev_or_NULL; gen.gram.offset = offset_dev_or_NULL; gen.gram.out = out_dev;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_gram", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

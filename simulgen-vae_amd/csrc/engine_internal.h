@@ -171,7 +171,7 @@ struct sgv_engine {
     bool use_side = true, side_dirty = false;
     float* xpose_tmp = nullptr; size_t xpose_floats = 0;
     float* recon_unit = nullptr;   // [3][N] unit-scale dgamma/dbeta/dbias of the recon head
-    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace (also the frame partials of sgv_summarize, the partials of sgv_project and the transposed weights of sgv_temporal)
+    float* colpart = nullptr; size_t colpart_floats = 0;   // per-block column-sum workspace (also the frame partials of sgv_summarize, the partials of sgv_project and sgv_gram and the transposed weights of sgv_temporal)
     int* probes_dev = nullptr; int n_probes = 0;           // sgv_set_probes: SGV_MAX_PROBES checked node indices (allocated on first use)
     std::vector<int32_t> probes_host;                      // the source of the last upload stays alive until the next one
     // graph
@@ -335,6 +335,13 @@ static inline int temporal_args_ok(const char* who, const float* weights, int n_
     if (!weights || !out) return fail(SGV_ERR_ARG, "%s: null argument", who);
     if (n_func < 1 || n_func > SGV_MAX_TEMPORAL) return fail(SGV_ERR_ARG, "%s: n_func = %d is outside [1, %d]", who, n_func, SGV_MAX_TEMPORAL);
     if (((uintptr_t)weights & 3) || ((uintptr_t)out & 15)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (weights 4 bytes, out 16)", who);
+    return 0;
+}
+// sgv_gram and its test hook: T <= SGV_MAX_GRAM_T (sgv_ew.h) row tiles fit the kernel's accumulators; the weights and the offset may be null
+static inline int gram_args_ok(const char* who, int T, const float* node_weights, const float* offset, const float* out) {
+    if (!out) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (T > SGV_MAX_GRAM_T) return fail(SGV_ERR_ARG, "%s: T = %d is beyond the limit of %d time steps", who, T, SGV_MAX_GRAM_T);
+    if ((((uintptr_t)node_weights | (uintptr_t)offset) & 15) || ((uintptr_t)out & 3)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (node_weights and offset 16 bytes, out 4)", who);
     return 0;
 }
 constexpr int SGV_SOBOL_MAX_PARAMS = 30;   // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table

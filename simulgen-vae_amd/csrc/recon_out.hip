@@ -1,8 +1,8 @@
 // The recon tails (gfx950): passes that replace the loss tail of the recon head in surrogate use -- the physical-unit field
 // (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
 // members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol), the histogram of the members
-// between given bounds (sgv_distribution), the co-moments of the members with their covariates (sgv_regress) and weighted sums over the
-// mesh (sgv_project).  All of them stream y = the recon head's convolution output once, form the same value per
+// between given bounds (sgv_distribution), the co-moments of the members with their covariates (sgv_regress), weighted sums over the
+// mesh (sgv_project) or over time (sgv_temporal) and the temporal Gram matrix (sgv_gram).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -1456,5 +1456,233 @@ int ew_recon_temporal(int dtype, GNParams p, const float* scale, const float* mn
     const dim3 grid(cdiv_i(p.C, TP_BLOCK_COLS), 1, p.B);
     if (dtype == 1) hipLaunchKernelGGL((recon_temporal_kernel<bf16_t>), grid, dim3(256), 0, s, p, q, o);
     else hipLaunchKernelGGL((recon_temporal_kernel<float>), grid, dim3(256), 0, s, p, q, o);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate Gram matrices (sgv_gram): the temporal Gram matrix per sample, G[b][t][t'] = sum_n w[n] (x[b][t][n] - m[n]) (x[b][t'][n] - m[n])
+// with x the value recon_phys_val gives -- the first tail that is quadratic in the field, the first with the field on BOTH sides of
+// the MFMA (v_mfma_f32_32x32x2_f32 again: exact fp32 products, one fused multiply-add chain per output) and the first that stages its
+// values through LDS: tanh makes every tail VALU-bound, so a value d = fl(x - m) is formed ONCE per block and read by every tile pair
+// that needs it.
+// Geometry: the T rows are cut into NT = ceil(T / 32) row tiles, the channels of the block into steps of GR_STEP = 16.  The fragment of
+// tile ti in a step at channel cb is recon_project_kernel's: lane l holds d[32 ti + (l & 31)][cb + 8 (l >> 5) + e], e = 0..7.  Wave
+// wv forms the fragments of tiles wv and wv + 4 and writes them to LDS in operand order, frag[buffer][tile][e][lane] -- a lane's own
+// position, conflict-free on both sides.  The tile pairs ti <= tj (NT (NT + 1) / 2 of them, 28 at T = 200, 36 at the limit) are dealt
+// to the four waves round robin, pair id = wv + 4 j for the wave's j-th accumulator; MFMA e of a step is
+//   acc[ti][tj] += A(fl(w d_ti[e])) * B(d_tj[e])        k = 0: channel cb + e, k = 1: channel cb + 8 + e,
+// so THE ROW INDEX t (the smaller tile) CARRIES THE WEIGHT: the element kept for t <= t' is the chain of fma(fl(w[n] d[t][n]),
+// d[t'][n], .) and (t', t) is its copy.  In a diagonal tile both (t, t') and (t', t) are computed; the one with row <= column is
+// kept.  w d is rounded once, by the consuming wave (w of the lane's 8 channels is the same for every tile); w == nullptr is w = 1
+// and m == nullptr is m = 0, which give the same bits as arrays of ones and zeros since 1 * d and x - 0 are exact.
+// The LDS is double-buffered, one barrier per step: in step s the waves form step s + 1 into the other buffer (from y and channel
+// constants loaded a step earlier), then multiply step s.  Rows past T carry zeros and load row T - 1 again, the upper half of a
+// last step past the chunk's end carries zeros and loads the lower half's addresses; an MFMA reads every lane's registers whatever
+// EXEC says, and here every lane's operands come from LDS words that were written.  Tiles past NT are neither written nor read.
+// Shares: a block is one sample and GR_CHUNK channels (C alone decides), all T rows.  An output's chain runs over the block's channels
+// in the order above, from 0; the per-block partials go to the workspace as [B][chunks][pairs * 1024] in the C / D register order
+// (v * 64 + lane) and recon_gram_finish_kernel adds them in ascending chunk order in fp64, rounds once and writes (t, t') and (t', t).
+// No atomics; neither the batch nor the grid shows in the bits.
+// ------------------------------------------------------------------------------------------
+constexpr int GR_STEP = 16;                         // channels of a step: 8 MFMAs of k = 2 per tile pair
+constexpr int GR_CHUNK = 6144;                      // channels per block, per partial (a multiple of GR_STEP)
+constexpr int GR_MAX_TILES = SGV_MAX_GRAM_T / 32;   // 8
+static int gr_chunks(int C) { return cdiv_i(C, GR_CHUNK); }
+static int gr_tiles(int T) { return cdiv_i(T, 32); }
+static int gr_pairs(int T) { return gr_tiles(T) * (gr_tiles(T) + 1) / 2; }
+size_t ew_recon_gram_work_floats(int B, int T, int C) { return (size_t)B * gr_chunks(C) * gr_pairs(T) * 1024; }
+// pair id -> (ti, tj), ti <= tj, row by row: (0,0) (0,1) .. (0,NT-1) (1,1) ..
+__device__ __forceinline__ void gr_pair(int pid, int nt, int& ti, int& tj) {
+    int i = 0, rem = pid;
+    while (rem >= nt - i) { rem -= nt - i; ++i; }
+    ti = i; tj = i + rem;
+}
+
+// d = fl(x - m): x rounded as ew_recon_physical would store it, then the difference, rounded on its own.  Without the pragma the
+// subtraction is contracted into recon_phys_val's multiply by 1 / scale (one rounding instead of two) and d is no longer the difference of
+// the stored value; __fsub_rn is a plain x - y in the compiler's headers and is contracted all the same.
+__device__ __forceinline__ float gr_diff(float x, float m) {
+#pragma clang fp contract(off)
+    return x - m;
+}
+// NJ: accumulator tiles per wave, 7 up to 7 row tiles (T <= 224) and 9 at 8
+template <typename T, int NJ>
+__global__ __launch_bounds__(256) void recon_gram_kernel(const GNParams p, const ReconPhys q, const ReconGram o) {
+    __shared__ float frag[2][GR_MAX_TILES][8][64];          // d in operand order, double-buffered: 32 KiB
+    __shared__ float2 tab[SGV_GN_MAX_GROUPS];               // (mean, rstd) of the sample's groups
+    const int b = blockIdx.z;
+    if ((int)threadIdx.x < p.G) {
+        float m, r;
+        gn_mean_rstd(p, b, threadIdx.x, m, r);
+        tab[threadIdx.x] = make_float2(m, r);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
+    const int nt = (p.T + 31) >> 5, npairs = nt * (nt + 1) / 2;
+    const int c_lo = blockIdx.x * GR_CHUNK, c_hi = min(p.C, c_lo + GR_CHUNK);
+    const int nsteps = (c_hi - c_lo + GR_STEP - 1) / GR_STEP;
+    // the rows this lane forms: tiles wv and wv + 4
+    const T* yrow[2];
+    bool row_ok[2], tile_ok[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int t = 32 * (wv + 4 * u) + lr;
+        tile_ok[u] = wv + 4 * u < nt;
+        row_ok[u] = t < p.T;
+        yrow[u] = reinterpret_cast<const T*>(p.y) + ((long)b * p.T + min(t, p.T - 1)) * p.ldy;
+    }
+    // the tile pairs this wave multiplies
+    int pa[NJ], pb[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        int ti = 0, tj = 0;
+        if (wv + 4 * j < npairs) gr_pair(wv + 4 * j, nt, ti, tj);
+        pa[j] = ti * 512 + lane; pb[j] = tj * 512 + lane;
+    }
+    f32x16 acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
+
+    // what a step needs from memory: y of the lane's two rows, the constants, offset and weight of its 8 channels
+    Raw8<T> ry[2];
+    float gam[8], bet[8], mn[8], inv[8], off[8], wgt[8];
+    auto fetch = [&](int s) {          // s < nsteps
+        const int cb = c_lo + s * GR_STEP;
+        const int c0 = cb + 8 * h < c_hi ? cb + 8 * h : cb;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+            if (tile_ok[u]) raw_load(yrow[u] + c0, ry[u]);
+        load8(p.gamma + c0, gam); load8(p.beta + c0, bet); load8(q.mn + c0, mn); load8(q.scale + c0, inv);
+        if (o.offset) load8(o.offset + c0, off);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) off[e] = 0.f;
+        }
+    };
+    auto fetch_w = [&](int s) {
+        const int cb = c_lo + s * GR_STEP;
+        const int c0 = cb + 8 * h < c_hi ? cb + 8 * h : cb;
+        if (o.node_weights) load8(o.node_weights + c0, wgt);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) wgt[e] = 1.f;
+        }
+    };
+    // forms step s from what fetch(s) loaded and writes it to buffer s & 1
+    auto produce = [&](int s) {
+        const int cb = c_lo + s * GR_STEP;
+        const bool ok = cb + 8 * h < c_hi;
+        const int c0 = ok ? cb + 8 * h : cb;
+        // the groups of the octet: with Cg >= 8 (block-uniform) at most two, the first n_lo channels in g_lo
+        const int g0 = c0 / p.Cg, n_lo = p.Cg - (c0 - g0 * p.Cg);
+        float gm[8], gr[8];
+        if (p.Cg >= 8) {
+            const float2 lo = tab[min(g0, p.G - 1)], hi = tab[min(g0 + 1, p.G - 1)];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { gm[e] = e < n_lo ? lo.x : hi.x; gr[e] = e < n_lo ? lo.y : hi.y; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float2 k = tab[min((c0 + e) / p.Cg, p.G - 1)];
+                gm[e] = k.x; gr[e] = k.y;
+            }
+        }
+        float iv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) iv[e] = recon_phys_inv(inv[e]);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (!tile_ok[u]) continue;          // wave-uniform
+            float v[8];
+            raw_unpack(ry[u], v);
+            float* const dst = &frag[s & 1][wv + 4 * u][0][lane];
+            const bool use = ok && row_ok[u];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float x = recon_phys_val(v[e], gm[e], gr[e], gam[e], bet[e], mn[e], iv[e]);
+                dst[e * 64] = use ? gr_diff(x, off[e]) : 0.f;
+            }
+        }
+    };
+
+    fetch(0);
+    produce(0);
+    fetch(min(1, nsteps - 1));
+    fetch_w(0);
+    __syncthreads();
+    for (int s = 0; s < nsteps; ++s) {
+        if (s + 1 < nsteps) {
+            produce(s + 1);
+            fetch(min(s + 2, nsteps - 1));
+        }
+        const float* const src = &frag[s & 1][0][0][0];
+        float w[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) w[e] = wgt[e];
+        fetch_w(min(s + 1, nsteps - 1));
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (wv + 4 * j >= npairs) break;          // wave-uniform
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float a = w[e] * src[pa[j] + e * 64], bb = src[pb[j] + e * 64];
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc[j], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // the partials, in the C / D register order: element v * 64 + lane of the pair
+    float* const part = o.work + ((long)b * gridDim.x + blockIdx.x) * npairs * 1024 + lane;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        if (wv + 4 * j >= npairs) break;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) part[(long)(wv + 4 * j) * 1024 + v * 64] = acc[j][v];
+    }
+}
+
+// partials [B][nchunk][npairs * 1024] -> out [B][T][T]: one thread per element of a pair's tile, its partials in ascending chunk order in
+// fp64, rounded once.  C / D map of the 32x32 forms: register v of lane l holds row (v & 3) + 8 (v >> 2) + 4 (l >> 5), column l & 31.  An
+// element with t <= t' < T is written to (t, t') and (t', t); the lower triangle of a diagonal tile and what lies past T is dropped.
+__global__ __launch_bounds__(256) void recon_gram_finish_kernel(const float* __restrict__ part, int B, int T, int nchunk, float* __restrict__ out) {
+    const int nt = (T + 31) >> 5, npairs = nt * (nt + 1) / 2;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * npairs * 1024) return;
+    const int b = (int)(i / (npairs * 1024)), k = (int)(i - (long)b * npairs * 1024);
+    const int pid = k >> 10, v = (k >> 6) & 15, l = k & 63;
+    int ti, tj;
+    gr_pair(pid, nt, ti, tj);
+    const int t = 32 * ti + (v & 3) + 8 * (v >> 2) + 4 * (l >> 5), u = 32 * tj + (l & 31);
+    if (t > u || u >= T) return;
+    double s = 0.0;
+    for (int j = 0; j < nchunk; ++j) s += (double)part[((long)b * nchunk + j) * npairs * 1024 + k];
+    const float g = (float)s;
+    out[((long)b * T + t) * T + u] = g;
+    out[((long)b * T + u) * T + t] = g;
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconGram (sgv_ew.h), o.work = ew_recon_gram_work_floats floats.  Non-zero
+// (nothing launched): -1 null input, -2 no output, -3 bad shape or T beyond SGV_MAX_GRAM_T, -4 y, node_weights, offset or work not
+// 16-byte aligned or out not 4-byte aligned, -6 no workspace
+int ew_recon_gram(int dtype, GNParams p, const float* scale, const float* mn, const ReconGram& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.out) return -2;
+    if (p.T > SGV_MAX_GRAM_T) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.node_weights | (uintptr_t)o.offset | (uintptr_t)o.work) & 15) return -4;
+    if ((uintptr_t)o.out & 3) return -4;
+    if (!o.work) return -6;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const int nchunk = gr_chunks(p.C);
+    const dim3 grid(nchunk, 1, p.B);
+    auto launch = [&](auto el, auto) {
+        using T = typename decltype(el)::type;
+        if (gr_tiles(p.T) <= 7) hipLaunchKernelGGL((recon_gram_kernel<T, 7>), grid, dim3(256), 0, s, p, q, o);
+        else hipLaunchKernelGGL((recon_gram_kernel<T, 9>), grid, dim3(256), 0, s, p, q, o);
+    };
+    recon_dispatch(launch, dtype, true);
+    const long n = (long)p.B * gr_pairs(p.T) * 1024;
+    hipLaunchKernelGGL(recon_gram_finish_kernel, dim3(cdiv_i(n, 256)), dim3(256), 0, s, o.work, p.B, p.T, nchunk, o.out);
     return 0;
 }

@@ -219,6 +219,24 @@ struct ReconTemporal {
 };
 size_t ew_recon_temporal_work_floats(int T);
 int ew_recon_temporal(int dtype, GNParams p, const float* scale, const float* mn, const ReconTemporal& o, hipStream_t s);
+// recon head -> the temporal Gram matrix of the physical field per sample, the field never stored:
+//   out[b][t][t'] = sum over n of w[n] * (x[b][t][n] - m[n]) * (x[b][t'][n] - m[n]),  x the value ew_recon_physical would store
+// (layout [B][T][C]), T <= SGV_MAX_GRAM_T.  node_weights = w [C] and offset = m [C] fp32, 16-byte aligned, either may be null (w = 1,
+// m = 0; arrays of ones / zeros give the same bits); out fp32 [B][T][T] dense, 4-byte aligned; work: ew_recon_gram_work_floats
+// floats, 16-byte aligned.  d = fl(x - m) is rounded once and is both operands; for t <= t' the element is one fp32 fused
+// multiply-add chain of fl(w[n] d[t][n]) * d[t'][n] -- the SMALLER time index carries the weight -- over the channels of a block of
+// 6144 in the kernel's order, from 0; the blocks' partials are added in ascending order in fp64 and rounded once; (t', t) is the
+// copy of (t, t'), so out is bitwise symmetric and its diagonal is >= 0 for w >= 0.  out[b] depends on sample b alone -- a sample
+// gives the bits it gives in any batch and at any place in it -- and two launches are bitwise equal.  No atomics.
+// Non-zero (nothing launched): -1 null input, -2 no output, -3 bad shape or T > SGV_MAX_GRAM_T, -4 y, node_weights, offset or work not
+// 16-byte aligned or out not 4-byte aligned, -6 no workspace
+constexpr int SGV_MAX_GRAM_T = 256;
+struct ReconGram {
+    const float* node_weights = nullptr; const float* offset = nullptr; float* out = nullptr;
+    float* work = nullptr;
+};
+size_t ew_recon_gram_work_floats(int B, int T, int C);
+int ew_recon_gram(int dtype, GNParams p, const float* scale, const float* mn, const ReconGram& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

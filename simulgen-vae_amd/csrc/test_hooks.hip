@@ -390,6 +390,18 @@ int sgv_test_recon_temporal(int dtype, const void* y, long ldy, double* sums, co
         return ew_recon_temporal(dtype, q, scale, min, o, s);
     });
 }
+int sgv_test_recon_gram(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta, const float* scale,
+                        const float* min, const float* node_weights, const float* offset, float* out, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_gram";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(gram_args_ok(me, T, node_weights, offset, out));
+    return recon_hook_run(me, dtype, p, ew_recon_gram_work_floats(B, T, C), stream, [&](const GNParams& q, float* work, hipStream_t s) {
+        ReconGram o;
+        o.node_weights = node_weights; o.offset = offset; o.out = out; o.work = work;
+        return ew_recon_gram(dtype, q, scale, min, o, s);
+    });
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_temporal", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_temporal", "sgv_gram", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_recon_temporal", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_recon_temporal", "sgv_test_recon_gram", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -103,6 +103,7 @@ REGRESS_FIELDS = ("mean", "m2", "comoment")       # the state of Engine.regress:
 REGRESS_MAX_COVARIATES = 32                      # the weights of a launch fit the kernel's LDS table
 MAX_FUNCTIONALS = 32                             # SGV_MAX_FUNCTIONALS: the weight rows of Engine.project are the 32 columns of the kernel's MFMA tile
 MAX_TEMPORAL = 32                                # SGV_MAX_TEMPORAL: the weight rows of Engine.temporal are the 32 rows of the kernel's MFMA tile
+MAX_GRAM_T = 256                                 # SGV_MAX_GRAM_T: the time steps of Engine.gram are at most 8 row tiles of the kernel's accumulators
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")     # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -160,6 +161,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_regress.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp, C.c_long, C.POINTER(RegressState)]
     lib.sgv_project.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.sgv_temporal.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
+    lib.sgv_gram.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -230,6 +232,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_regress.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, i32, vp, lg, C.POINTER(RegressState), i32, i32, i32, vp]
     lib.sgv_test_recon_project.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_temporal.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
+    lib.sgv_test_recon_gram.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -441,7 +444,7 @@ class Engine:
         _check(self.lib, self.lib.sgv_set_shard(self.h, int(rank), int(world)), "sgv_set_shard")
 
     def set_draw_row(self, first_row: int):
-        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project, temporal) takes
+        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project, temporal, gram) takes
         row first_row + b of the streams the call draws from (include/sgvae.h: sgv_set_draw_row).  With the draw position put back in
         front of every batch (set_train_state) a study cut into batches gets the noise one call over all of it would get.  Default 0."""
         _check(self.lib, self.lib.sgv_set_draw_row(self.h, int(first_row)), "sgv_set_draw_row")
@@ -788,6 +791,31 @@ class Engine:
                 raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {(B, R, N)}")
             return (C.c_void_p(weights.data_ptr()), R, C.c_void_p(out.data_ptr())), out
         return self._surrogate("sgv_temporal", z, xs, scale, min, fix, tail)
+
+    def gram(self, z, xs, scale, min, node_weights=None, offset=None, fix=True, out=None):
+        """The temporal Gram matrix of the field generate() would write, by the recon head's last pass itself; the field is never
+        stored.  Same inputs and checks as summarize(); num_time <= MAX_GRAM_T.  node_weights (w) and offset (m): contiguous fp32
+        CUDA [N] or None for w = 1 / m = 0 (predict.gram_weights and gram_offset validate and upload host arrays).  Returns fp32
+        CUDA [B, T, T], values[b, t, t'] = sum over n of w[n] * (field[b, t, n] - m[n]) * (field[b, t', n] - m[n]) on the matrix
+        cores in fp32: bitwise symmetric, the diagonal >= 0 for w >= 0.  A matrix depends on its sample alone, so any cut of the
+        conditions into batches gives the same bits.  out: a contiguous fp32 CUDA tensor [B, T, T] to write into (a slice along the
+        first axis of a larger one will do).  Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        if T > MAX_GRAM_T:
+            raise ValueError(f"num_time = {T} is beyond the limit of {MAX_GRAM_T} time steps of the Gram pass")
+        for name, a in (("node_weights", node_weights), ("offset", offset)):
+            if a is not None and not is_tensor_of(a, t.float32, (N,)):
+                raise ValueError(f"{name} must be None or a contiguous float32 CUDA tensor of shape [{N}]")
+
+        def tail(B, out=out):
+            if out is None:
+                out = t.empty((B, T, T), dtype=t.float32, device="cuda")
+            elif not is_tensor_of(out, t.float32, (B, T, T)):
+                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {(B, T, T)}")
+            ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+            return (ptr(node_weights), ptr(offset), C.c_void_p(out.data_ptr())), out
+        return self._surrogate("sgv_gram", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -42,6 +42,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     amp, phi = spec.amplitude(), spec.phase()      # amplitude and phase at a few frequencies, window means (window_rows), time
                                                    # integrals, filtered values, any rows [R, T]: spec.values [P, R, N], 4 R N bytes
                                                    # per condition instead of 4 T N
+    g = s.gram(conditions, node_weights=area)      # the temporal Gram matrix per condition, g.values [P, T, T]: energy histories,
+    rows, lam, frac = g.modes(energy=0.99)         # autocorrelation / MAC, and the POD temporal modes of the whole study by
+    pod = s.pod(conditions, rank=8, node_weights=area)   # numpy.linalg.eigh on the host; pod() chains gram -> modes -> temporal
+                                                   # into a rank-R compression with coefficients [P, R, N]
 """
 from __future__ import annotations
 
@@ -52,7 +56,7 @@ import pickle
 
 import numpy as np
 
-from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_FUNCTIONALS, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
+from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_FUNCTIONALS, MAX_GRAM_T, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
                      SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of)
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
@@ -467,6 +471,153 @@ class TemporalResult(_Result):
             where = torch.where(mag == top.unsqueeze(2), nodes, N).min(dim=2).values
             return where, v.gather(2, where.clamp(max=N - 1).unsqueeze(2)).squeeze(2)
         return self._on_stream(fn)
+
+
+def _gram_vector(v, N, name, nonneg):
+    if v is None:
+        return None
+    dev = _is_device_tensor(v)
+    a = v if dev else np.asarray(v)
+    shape = tuple(int(d) for d in a.shape)
+    if shape != (int(N),):
+        raise ValueError(f"{name}: an [N] array with N = {int(N)} is required, got shape {shape}")
+    if dev:
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"{name}: a floating dtype is required, not {a.dtype}")
+        import torch
+        w = a.to(dtype=torch.float32).contiguous()
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError(f"{name}: an entry is not finite as float32")
+        if nonneg and bool((w < 0).any()):
+            raise ValueError(f"{name}: an entry is negative; the weights of a Gram matrix are non-negative")
+        return w
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError(f"{name}: a floating dtype is required, not {a.dtype}")
+    with np.errstate(over="ignore"):          # a value beyond float32 becomes inf and is reported below
+        w = np.ascontiguousarray(a, dtype=np.float32)
+    bad = np.flatnonzero(~np.isfinite(w))
+    if bad.size:
+        raise ValueError(f"{name}[{int(bad[0])}] = {float(a[bad[0]])!r} is not finite as float32")
+    if nonneg:
+        bad = np.flatnonzero(w < 0)
+        if bad.size:
+            raise ValueError(f"{name}[{int(bad[0])}] = {float(a[bad[0]])!r} is negative; the weights of a Gram matrix are non-negative")
+    return w
+
+
+def gram_weights(node_weights, N):
+    """The node weights of Surrogate.gram (a nodal mass or area) as contiguous float32 [N], or None for None (every weight 1).  A
+    host array comes back as a numpy array, a CUDA tensor as a CUDA tensor; both are read: every entry finite as float32 and
+    >= 0 (a CUDA tensor costs one host wait for that).  ValueError naming the problem otherwise: a shape other than [N], a dtype
+    that is not floating, an entry that is not finite or negative (host data: the first one is named)."""
+    return _gram_vector(node_weights, N, "node_weights", True)
+
+
+def gram_offset(offset, N):
+    """The reference field of Surrogate.gram (what is subtracted from every time step: a mean field, an initial state) as contiguous
+    float32 [N], or None for None (no offset).  As gram_weights, without the sign condition."""
+    return _gram_vector(offset, N, "offset", False)
+
+
+def _host64(v):
+    return (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float64)
+
+
+class GramResult(_Result):
+    """Surrogate.gram's result for P conditions: values [P, T, T] fp32, a device tensor that is the caller's --
+    values[p, t, t'] = sum over n of w[n] (field[p, t, n] - m[n]) (field[p, t', n] - m[n]), bitwise symmetric -- and num_node = N.
+    What is derived from it is computed on the host in float64 (numpy; the first call waits for the device and keeps the copy)."""
+    FIELDS = ("values", "num_node")
+
+    def __init__(self, stream=None, **kw):
+        super().__init__(**kw)
+        self._stream = stream
+        self._g64 = None
+
+    def host(self):
+        """values as float64 [P, T, T] on the host"""
+        if self._g64 is None:
+            if self._stream is not None:
+                self._stream.synchronize()
+            self._g64 = _host64(self.values)
+        return self._g64
+
+    def energy(self):
+        """[P, T]: the diagonal, the weighted energy of every time step about the offset"""
+        return np.diagonal(self.host(), axis1=1, axis2=2).copy()
+
+    def total(self):
+        """[T, T]: the sum over the conditions, X X^T of the stacked snapshot matrix of the whole study"""
+        return self.host().sum(axis=0)
+
+    def correlation(self):
+        """[P, T, T]: values[p, t, t'] / sqrt(values[p, t, t] values[p, t', t']), the temporal autocorrelation (squared: the MAC
+        matrix between time steps); 0 where a diagonal entry is 0"""
+        g = self.host()
+        d = np.sqrt(np.clip(self.energy(), 0.0, None))
+        den = d[:, :, None] * d[:, None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0, g / den, 0.0)
+
+    def centered(self):
+        """[P, T, T]: H G H with H = I - 1 1^T / T, the Gram matrix of the field minus its own mean over time"""
+        g = self.host()
+        T = g.shape[-1]
+        H = np.eye(T) - np.full((T, T), 1.0 / T)
+        return H @ g @ H
+
+    def noise_floor(self):
+        """(N + 3) 2^-24 trace(total()): for w >= 0 an upper bound of the Frobenius norm of the rounding error of total() -- every
+        entry is within (N + 3) 2^-24 sum_n |w d_t d_t'| of the exact sum and Cauchy-Schwarz bounds that by the geometric mean of
+        the two diagonal entries -- and by Weyl's inequality of the error of each of its eigenvalues"""
+        return (int(self.num_node) + 3) * 2.0 ** -24 * float(np.trace(self.total()))
+
+    def modes(self, rank=None, energy=None):
+        """The POD temporal modes of the study (method of snapshots): eigh of total(), eigenvalues descending, negative ones clamped
+        to 0, truncated to `rank` modes or to the smallest rank whose eigenvalues reach the fraction `energy` of their sum (give one
+        of the two, or neither for all T).  Returns (rows [R, T] float32 -- orthonormal, ready for Surrogate.temporal --,
+        eigenvalues [R] float64, the fraction of the energy they capture)."""
+        if rank is not None and energy is not None:
+            raise ValueError("modes: give rank or energy, not both")
+        lam, vec = np.linalg.eigh(self.total())
+        order = np.argsort(lam)[::-1]
+        lam, vec = np.clip(lam[order], 0.0, None), vec[:, order]
+        T = lam.size
+        whole = float(lam.sum())
+        if rank is not None:
+            R = int(rank)
+            if R < 1 or R > T:
+                raise ValueError(f"modes: rank = {rank} is outside [1, T = {T}]")
+        elif energy is not None:
+            f = float(energy)
+            if not (0.0 < f <= 1.0):
+                raise ValueError(f"modes: energy = {energy!r} is outside (0, 1]")
+            cum = np.cumsum(lam)
+            R = T if whole == 0.0 else min(T, int(np.searchsorted(cum, f * whole * (1.0 - 1e-15))) + 1)
+        else:
+            R = T
+        frac = 1.0 if whole == 0.0 else float(lam[:R].sum() / whole)
+        return np.ascontiguousarray(vec[:, :R].T, dtype=np.float32), lam[:R].copy(), frac
+
+
+class PodResult(_Result):
+    """Surrogate.pod's result: rows [R, T] float32 (the temporal modes, host), eigenvalues [R] float64, fraction (of the energy the
+    modes capture), coefficients [P, R, N] fp32 -- coefficients[p, r, n] = sum_t rows[r, t] (field[p, t, n] - m[n]), a device
+    tensor that is the caller's -- and offset (m as float32 [N], or None)."""
+    FIELDS = ("rows", "eigenvalues", "fraction", "coefficients", "offset")
+
+    def reconstruct(self, p):
+        """rows^T coefficients[p] + offset: the rank-R field of condition p, [T, N] float64, where the coefficients live"""
+        c = self.coefficients[p]
+        if hasattr(c, "detach"):
+            import torch
+            rows = torch.as_tensor(np.asarray(self.rows, np.float64), device=c.device)
+            x = rows.t() @ c.to(torch.float64)
+            if self.offset is not None:
+                x += torch.as_tensor(self.offset, device=c.device).to(torch.float64)
+            return x
+        x = np.asarray(self.rows, np.float64).T @ np.asarray(c, np.float64)
+        return x if self.offset is None else x + np.asarray(self.offset, np.float64)
 
 
 class ScoreResult(_Result):
@@ -1128,6 +1279,72 @@ class Surrogate:
             finally:
                 eng.set_draw_row(0)
         return TemporalResult(stream=self._stream, values=values)
+
+    def gram(self, conditions, node_weights=None, offset=None, mode="fix"):
+        """The temporal Gram matrix of predict(conditions) per condition, without the fields: a GramResult whose values [P, T, T] are
+        sum_n w[n] (field[p, t, n] - m[n]) (field[p, t', n] - m[n]), with node_weights w [N] (a nodal mass or area; see
+        gram_weights) and offset m [N] (a reference field; see gram_offset), either None -- energy histories, autocorrelation and
+        MAC between time steps, and, summed over the conditions, X X^T of the study, whose eigenvectors are its POD temporal modes
+        (GramResult.modes).  num_time <= MAX_GRAM_T.  The recon head's last pass multiplies the values predict() would store (bit
+        for bit the same) with themselves on the matrix cores in fp32, in a fixed order inside fixed shares of the mesh, and adds
+        the shares in float64: a matrix depends on its condition alone, and the decoder's noise of condition p is row p of the
+        streams one call over all conditions would draw from (Engine.set_draw_row), so the batch size does not show in the bits
+        in either mode, and 4 T T bytes per condition leave the decoder instead of 4 T N.  Batching, streams, the single
+        input-range decision and `mode` are project()'s: no host wait between batches."""
+        t = self.torch
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        if self.T > MAX_GRAM_T:
+            raise ValueError(f"gram: num_time = {self.T} is beyond the limit of {MAX_GRAM_T} time steps")
+        w, m = gram_weights(node_weights, self.N), gram_offset(offset, self.N)
+        values = t.empty((P, self.T, self.T), dtype=t.float32, device="cuda")          # the result: the caller's stream owns it
+        eng = self.eng
+        at = eng.train_state()
+        with _engine_stream(self._stream):
+            w, m = (self._gram_device(v) for v in (w, m))
+            try:
+                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
+                    # as in project(): every batch draws from the streams of the call's first draw, condition p from their row p
+                    eng.set_train_state(at["step"], at["seed"], at["draw"])
+                    eng.set_draw_row(lo)
+                    eng.gram(lat, xs, self.data_scale, self.data_min, node_weights=w, offset=m, fix=mode == "fix", out=values[lo:hi])
+            finally:
+                eng.set_draw_row(0)
+        return GramResult(stream=self._stream, values=values, num_node=self.N)
+
+    def _gram_device(self, v):
+        """a validated weight or offset vector on the device, 16-byte aligned (the kernel loads 16 bytes at a time)"""
+        if v is None:
+            return None
+        t = self.torch
+        if not t.is_tensor(v):
+            v = t.from_numpy(v)
+        v = v.to(device="cuda", non_blocking=True)
+        return v.clone() if v.data_ptr() % 16 else v
+
+    def pod(self, conditions, rank=None, energy=None, node_weights=None, offset=None, mode="fix"):
+        """A rank-R compression of predict(conditions) by the method of snapshots, the fields never stored: gram() gives the Gram
+        matrices, GramResult.modes(rank, energy) the temporal modes rows [R, T] of the whole study, and temporal() the coefficients
+        coefficients[p, r, n] = sum_t rows[r, t] (field[p, t, n] - m[n]), formed on the device in fp32 as temporal(rows)[p, r, n]
+        - S_r m[n] with S_r = sum_t rows[r, t].  Every pass starts from the same draw position, so all of them see the same fields
+        in either mode; the position ends where one pass leaves it.  More than MAX_TEMPORAL modes take several temporal passes.
+        Returns a PodResult; PodResult.reconstruct(p) is rows^T coefficients[p] + m.  One host wait, for the Gram matrices."""
+        t = self.torch
+        eng = self.eng
+        at = eng.train_state()
+        g = self.gram(conditions, node_weights=node_weights, offset=offset, mode=mode)
+        rows, lam, frac = g.modes(rank=rank, energy=energy)
+        m = gram_offset(offset, self.N)
+        parts = []
+        for lo in range(0, rows.shape[0], MAX_TEMPORAL):
+            eng.set_train_state(at["step"], at["seed"], at["draw"])
+            parts.append(self.temporal(conditions, rows[lo:lo + MAX_TEMPORAL], mode=mode).values)
+        with _engine_stream(self._stream):
+            coeff = parts[0] if len(parts) == 1 else t.cat(parts, dim=1)
+            if m is not None:
+                m = self._gram_device(m)
+                S = t.from_numpy(rows.astype(np.float64).sum(axis=1).astype(np.float32)).to(device="cuda")
+                coeff -= S.view(1, -1, 1) * m.view(1, 1, -1)
+        return PodResult(rows=rows, eigenvalues=lam, fraction=frac, coefficients=coeff, offset=m)
 
     def score(self, conditions, truth, mode="fix"):
         """How wrong predict(conditions) is against held-out fields, without the fields: truth [P, T, N] fp32 in physical units (the

@@ -46,6 +46,7 @@ typedef enum {
 enum { SGV_DTYPE_F32 = 0, SGV_DTYPE_BF16 = 1 };
 enum { SGV_LOSS_MSE = 0, SGV_LOSS_MAE = 1, SGV_LOSS_SMOOTHL1 = 2, SGV_LOSS_HUBER = 3 };
 enum { SGV_MAX_LEVELS = 8 };
+enum { SGV_SIDE_ABOVE = 0, SGV_SIDE_BELOW = 1 };   /* sgv_exceedance: a step exceeds its level when the value is above / below it (strict) */
 enum { SGV_LAYOUT_TN = 0, SGV_LAYOUT_NT = 1 };   /* sgv_generate output: [B][T][N] (the data set's own order) or [B][N][T] (the reference's tensors) */
 
 /* Mirrors the constructor arguments of modules.VAE_network.VAE (modules/VAE_network.py:60):
@@ -150,7 +151,7 @@ int sgv_seed(sgv_engine* e, uint64_t seed);
  * exactly the noise one rank draws for B samples.  Default (0, 1). */
 int sgv_set_shard(sgv_engine* e, int rank, int world);
 /* Noise of a study that is cut into batches: with first_row = r, sample b of the following decoder passes that draw their noise
- * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal, sgv_gram) takes row r + b of the streams the call draws from instead of
+ * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal, sgv_gram, sgv_exceedance) takes row r + b of the streams the call draws from instead of
  * row b.  sgv_forward and sgv_decode are not affected.  A caller that puts the draw position back in front of every batch (sgv_set_train_state) and sets
  * first_row to the index of the batch's first sample gives sample p of the study the noise one call over all samples would give
  * it, whatever the batch size; Surrogate.project does.  The passes that count members themselves (sgv_ensemble, sgv_sobol,
@@ -375,6 +376,25 @@ int sgv_temporal(sgv_engine* e, const float* z_dev, const float* xs_dev, int bat
  * Synchronises nothing.  Afterwards there is no forward pass to read from, as after sgv_generate. */
 int sgv_gram(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
              const float* min_dev, const float* node_weights_dev_or_NULL, const float* offset_dev_or_NULL, float* out_dev);
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the exceedance pass: the level-crossing
+ * statistics of every node's time history against n_level = L levels per node, 1 <= L <= 4, the field itself never stored.
+ * levels_dev fp32 [L][N] dense on the device, 4-byte aligned; side SGV_SIDE_ABOVE or SGV_SIDE_BELOW.  With x[t] the value
+ * sgv_generate would store at (b, t, n) (SGV_LAYOUT_TN), lam = levels[l][n] and e[t] = (x[t] > lam) above, (x[t] < lam) below --
+ * strict, on the descaled value, so negative scales are fine; a NaN exceeds nothing:
+ *   stats[b][0][l][n] = count, the number of t with e[t];  [1] first, the smallest such t, -1 if none;  [2] last, the largest, -1 if
+ *   none;  [3] longest, the length of the longest run of consecutive exceeding steps, 0 if none;  [4] runs, the number of t with
+ *   e[t] and (t == 0 or not e[t - 1]), i.e. of maximal runs
+ *   excess[b][l][n] = s after: s = +0.0; for t ascending, where e[t]: s = fl(s + d[t]) with d[t] = fl(x[t] - lam) above and
+ *   fl(lam - x[t]) below, the difference of the stored value rounded on its own; exactly +0.0 where nothing exceeds
+ * stats_dev_or_NULL int32 [batch][5][L][N] and excess_dev_or_NULL fp32 [batch][L][N] on the device, 16-byte aligned; either may be
+ * NULL, not both.  num_time <= 65535.  Every output depends on its sample, its level row and its node alone, so any cut of the
+ * conditions into batches, any L, any order of the levels and either output alone give the same bits.  No workspace, no atomics.
+ * SGV_ERR_ARG before anything is enqueued: e, z_dev, scale_dev, min_dev or levels_dev NULL, both outputs NULL, n_level outside
+ * [1, 4], an unknown side, num_time > 65535, a misaligned pointer, the checks of sgv_decode.  Synchronises nothing.  Afterwards
+ * there is no forward pass to read from, as after sgv_generate. */
+int sgv_exceedance(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                   const float* min_dev, const float* levels_dev, int n_level, int side, int32_t* stats_dev_or_NULL,
+                   float* excess_dev_or_NULL);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -698,6 +718,13 @@ int sgv_test_recon_temporal(int dtype, const void* y, long ldy, double* sums, co
  * node_weights and offset 16 bytes; out 4). */
 int sgv_test_recon_gram(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta, const float* scale,
                         const float* min, const float* node_weights, const float* offset, float* out, int B, int T, int C, void* stream);
+/* The kernel of sgv_exceedance on caller-owned buffers: inputs as sgv_test_recon_physical, levels fp32 [n_level][C], stats int32
+ * [B][5][n_level][C] or NULL and excess fp32 [B][n_level][C] or NULL on the device, then the statistics of y and the exceedance
+ * pass.  SGV_ERR_ARG, nothing launched: a NULL input (levels included), both outputs NULL, n_level outside [1, 4], an unknown
+ * side, B or T < 1, T > 65535, C < 8 or C % 8 != 0, a bad row stride, a misaligned pointer (y, stats and excess 16 bytes; levels 4). */
+int sgv_test_recon_exceedance(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                              const float* scale, const float* min, const float* levels, int n_level, int side, int32_t* stats,
+                              float* excess, int B, int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

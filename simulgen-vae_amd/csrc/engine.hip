@@ -899,9 +899,9 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
 // What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
 // (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble), the sums of a Sobol study
 // (sgv_sobol), the histogram of the members (sgv_distribution), their co-moments with the covariates (sgv_regress), weighted sums
-// over the mesh (sgv_project), weighted sums over time (sgv_temporal) or the temporal Gram matrix (sgv_gram); only the members of `kind` are read.
+// over the mesh (sgv_project), weighted sums over time (sgv_temporal), the temporal Gram matrix (sgv_gram) or the level-crossing statistics (sgv_exceedance); only the members of `kind` are read.
 struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS, PROJECT, TEMPORAL, GRAM } kind;
+    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS, PROJECT, TEMPORAL, GRAM, EXCEED } kind;
     const float* scale; const float* mn;
     int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
     ReconSummary sum;                                          // SUMMARY
@@ -913,6 +913,7 @@ struct GenOut {
     ReconProject proj;                                         // PROJECT
     ReconTemporal temp;                                        // TEMPORAL
     ReconGram gram;                                            // GRAM
+    ReconExceed exc;                                           // EXCEED
     // ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
     bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION || kind == REGRESS; }
     long members_before() const {
@@ -924,7 +925,7 @@ struct GenOut {
 // the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol, the
 // distribution and the regression pass.
 static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress", "recon_project", "recon_temporal", "recon_gram"};
+    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress", "recon_project", "recon_temporal", "recon_gram", "recon_exceed"};
     static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
                                            "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
                                            "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)",
@@ -932,7 +933,8 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
                                            "sgv_regress: the regression pass rejected its arguments (%d)",
                                            "sgv_project: the project pass rejected its arguments (%d)",
                                            "sgv_temporal: the temporal pass rejected its arguments (%d)",
-                                           "sgv_gram: the Gram pass rejected its arguments (%d)"};
+                                           "sgv_gram: the Gram pass rejected its arguments (%d)",
+                                           "sgv_exceedance: the exceedance pass rejected its arguments (%d)"};
     ScopedTimer tm(e, tag[g.kind], nullptr);
     int r = 0;
     switch (g.kind) {
@@ -945,6 +947,7 @@ static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
     case GenOut::REGRESS: r = ew_recon_regress(e->dt, p, g.scale, g.mn, g.reg_cov, g.reg_count, g.reg, e->stream); break;
     case GenOut::PROJECT: { ReconProject o = g.proj; o.work = e->colpart; r = ew_recon_project(e->dt, p, g.scale, g.mn, o, e->stream); break; }
     case GenOut::TEMPORAL: { ReconTemporal o = g.temp; o.work = e->colpart; r = ew_recon_temporal(e->dt, p, g.scale, g.mn, o, e->stream); break; }
+    case GenOut::EXCEED: r = ew_recon_exceedance(e->dt, p, g.scale, g.mn, g.exc, e->stream); break;
     case GenOut::GRAM: { ReconGram o = g.gram; o.work = e->colpart; r = ew_recon_gram(e->dt, p, g.scale, g.mn, o, e->stream); break; }
     }
     return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
@@ -1203,6 +1206,17 @@ int sgv_gram(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, 
     GenOut gen = {GenOut::GRAM, scale_dev, min_dev};
     gen.gram.node_weights = node_weights_dev_or_NULL; gen.gram.offset = offset_dev_or_NULL; gen.gram.out = out_dev;
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_gram", gen);
+}
+
+int sgv_exceedance(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+                   const float* min_dev, const float* levels_dev, int n_level, int side, int32_t* stats_dev_or_NULL,
+                   float* excess_dev_or_NULL) {
+    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_exceedance: null argument");
+    CHK(exceedance_args_ok("sgv_exceedance", e->T, levels_dev, n_level, side, stats_dev_or_NULL, excess_dev_or_NULL));
+    GenOut gen = {GenOut::EXCEED, scale_dev, min_dev};
+    gen.exc.levels = levels_dev; gen.exc.n_level = n_level; gen.exc.above = side == SGV_SIDE_ABOVE;
+    gen.exc.stats = stats_dev_or_NULL; gen.exc.excess = excess_dev_or_NULL;
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_exceedance", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

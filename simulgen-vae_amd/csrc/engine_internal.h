@@ -344,6 +344,17 @@ static inline int gram_args_ok(const char* who, int T, const float* node_weights
     if ((((uintptr_t)node_weights | (uintptr_t)offset) & 15) || ((uintptr_t)out & 3)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (node_weights and offset 16 bytes, out 4)", who);
     return 0;
 }
+// sgv_exceedance and its test hook: SGV_MAX_EXCEED_LEVELS (sgv_ew.h) levels at most, T within the kernel's packed 16-bit counters; the
+// rows of both outputs are written 32 bytes at a time
+static inline int exceedance_args_ok(const char* who, int T, const float* levels, int n_level, int side, const int32_t* stats, const float* excess) {
+    if (!levels) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    if (!stats && !excess) return fail(SGV_ERR_ARG, "%s: no output (stats and excess are both null)", who);
+    if (n_level < 1 || n_level > SGV_MAX_EXCEED_LEVELS) return fail(SGV_ERR_ARG, "%s: n_level = %d is outside [1, %d]", who, n_level, SGV_MAX_EXCEED_LEVELS);
+    if (side != SGV_SIDE_ABOVE && side != SGV_SIDE_BELOW) return fail(SGV_ERR_ARG, "%s: unknown side %d", who, side);
+    if (T > 65535) return fail(SGV_ERR_ARG, "%s: T = %d is beyond the limit of 65535 time steps", who, T);
+    if (((uintptr_t)levels & 3) || (((uintptr_t)stats | (uintptr_t)excess) & 15)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (levels 4 bytes, stats and excess 16)", who);
+    return 0;
+}
 constexpr int SGV_SOBOL_MAX_PARAMS = 30;   // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
 static inline int sobol_state_ok(const char* who, const char* batch_name, const sgv_sobol_state* st, int n_params, long blocks_before, int batch) {
     if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);

@@ -2,7 +2,8 @@
 // (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
 // members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol), the histogram of the members
 // between given bounds (sgv_distribution), the co-moments of the members with their covariates (sgv_regress), weighted sums over the
-// mesh (sgv_project) or over time (sgv_temporal) and the temporal Gram matrix (sgv_gram).  All of them stream y = the recon head's convolution output once, form the same value per
+// mesh (sgv_project) or over time (sgv_temporal), the temporal Gram matrix (sgv_gram) and the level-crossing statistics over time
+// (sgv_exceedance).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -1684,5 +1685,143 @@ int ew_recon_gram(int dtype, GNParams p, const float* scale, const float* mn, co
     recon_dispatch(launch, dtype, true);
     const long n = (long)p.B * gr_pairs(p.T) * 1024;
     hipLaunchKernelGGL(recon_gram_finish_kernel, dim3(cdiv_i(n, 256)), dim3(256), 0, s, o.work, p.B, p.T, nchunk, o.out);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate exceedance durations (sgv_exceedance): the level-crossing statistics of every node's time history against L levels per
+// node, e_t = (x_t > level) or (x_t < level), strict, x the value recon_phys_val gives: how many steps exceed, the first and the last of
+// them, the number of maximal runs of consecutive exceeding steps, the longest run, and the fp32 sum of the excess fl(x_t - level)
+// (fl(level - x_t) below) over the exceeding steps, t ascending from +0.0.  The first tail whose result depends on the ORDER of the
+// time steps.
+// Geometry: a thread owns its 8 channels of one sample for all T, t ascending -- the ownership of recon_temporal_kernel without the
+// MFMA: thread i of a block has channels 8 i .. 8 i + 7 of the block's XC_BLOCK_COLS, so a wave reads XC_WAVE_COLS contiguous channels
+// of a row per step, 16 bytes (bf16) or 32 bytes (fp32) per lane.  The channel constants, the sample's (mean, rstd) and the lane's
+// L x 8 levels are loaded once; the y rows of xc_flight() steps are in flight in a register ring, the load of step t + xc_flight() issued as
+// soon as step t is unpacked.  No reduction across threads, no LDS besides gn_consts' table, no workspace, no finish kernel, no
+// atomics: an output depends on its sample, its level and its channel alone.
+// State, 4 words per (channel, level), 128 registers at L = 4 (unpacked it would be 7 words): count | current run << 16;
+// runs | longest << 16; first | (0xffff - last) << 16, both halves kept by one packed 16-bit minimum; the sum.  Every half stays below
+// 2^16 while T < 65536 (t <= 65534, so 0xffff is free as "none"); the launcher refuses a longer T.  The levels are a run-time count
+// 1 <= L <= SGV_MAX_EXCEED_LEVELS behind wave-uniform branches of the unrolled loop; the state of the levels past L is dead.
+// ------------------------------------------------------------------------------------------
+constexpr int XC_WAVE_COLS = 512;                   // channels of a wave: 64 lanes x 8
+constexpr int XC_BLOCK_COLS = 4 * XC_WAVE_COLS;     // channels of a block
+template <typename T> constexpr int xc_flight() { return sizeof(T) == 2 ? 4 : 2; }          // steps in flight: 4 KiB of y per wave and 16 registers per lane in either dtype
+constexpr int XC_MAX_T = 65535;                     // the packed 16-bit halves of the state
+
+typedef unsigned short xc_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned xc_pk_min(unsigned a, unsigned b) {          // v_pk_min_u16
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(xc_u16x2, a), __builtin_bit_cast(xc_u16x2, b)));
+}
+
+template <typename T, bool ABOVE, bool STEPS, bool EXCESS>
+__global__ __launch_bounds__(256, 2) void recon_exceed_kernel(const GNParams p, const ReconPhys q, const ReconExceed o) {
+    constexpr int F = xc_flight<T>(), LM = SGV_MAX_EXCEED_LEVELS;
+    GNCtx c;
+    c.b = blockIdx.z;
+    c.c0 = blockIdx.x * XC_BLOCK_COLS + threadIdx.x * 8;
+    c.col_ok = c.c0 < p.C;
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);          // all 256 threads
+    if (!c.col_ok) return;                // no barrier, no shuffle below
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, true); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const int L = o.n_level;
+    float lev[LM][8], sum[LM][8];
+    unsigned cc[LM][8], rl[LM][8], fl[LM][8];          // count | current << 16; runs | longest << 16; first | (0xffff - last) << 16
+#pragma unroll
+    for (int l = 0; l < LM; ++l)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            lev[l][e] = l < L ? o.levels[(long)l * p.C + c.c0 + e] : 0.f;
+            sum[l][e] = 0.f; cc[l][e] = 0u; rl[l][e] = 0u; fl[l][e] = 0xffffffffu;
+        }
+    const T* const y = reinterpret_cast<const T*>(p.y) + (long)c.b * p.T * p.ldy + c.c0;
+    // a row past T - 1 is row T - 1 again, loaded and not used
+    Raw8<T> ry[F];
+#pragma unroll
+    for (int u = 0; u < F; ++u) raw_load(y + (long)min(u, p.T - 1) * p.ldy, ry[u]);
+    for (int t0 = 0; t0 < p.T; t0 += F) {
+#pragma unroll
+        for (int u = 0; u < F; ++u) {
+            const int t = t0 + u;
+            if (t >= p.T) break;          // uniform
+            float x[8];
+            raw_unpack(ry[u], x);
+            raw_load(y + (long)min(t + F, p.T - 1) * p.ldy, ry[u]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = recon_phys_val(x[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+            const unsigned here = (unsigned)t | (0xffffu - (unsigned)t) << 16;
+#pragma unroll
+            for (int l = 0; l < LM; ++l) {
+                if (l >= L) break;          // uniform
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const bool ex = ABOVE ? x[e] > lev[l][e] : x[e] < lev[l][e];
+                    if constexpr (STEPS) {
+                        const unsigned start = ex && cc[l][e] < 0x10000u ? 1u : 0u;
+                        cc[l][e] = ex ? cc[l][e] + 0x10001u : cc[l][e] & 0xffffu;
+                        const unsigned r = rl[l][e] + start;
+                        rl[l][e] = max(r, (cc[l][e] & 0xffff0000u) | (r & 0xffffu));
+                        fl[l][e] = xc_pk_min(fl[l][e], ex ? here : 0xffffffffu);
+                    }
+                    if constexpr (EXCESS) {
+                        // the difference of the stored value, rounded on its own (gr_diff), then one add
+                        const float d = ABOVE ? gr_diff(x[e], lev[l][e]) : gr_diff(lev[l][e], x[e]);
+                        sum[l][e] = ex ? sum[l][e] + d : sum[l][e];
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < LM; ++l) {
+        if (l >= L) break;
+        if constexpr (STEPS) {
+            int* const st = o.stats + ((long)c.b * 5 * L + l) * p.C + c.c0;          // [B][5][L][C]: count, first, last, longest, runs
+            const long plane = (long)L * p.C;
+            int v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (int)(cc[l][e] & 0xffffu);
+            store8(st, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = cc[l][e] & 0xffffu ? (int)(fl[l][e] & 0xffffu) : -1;
+            store8(st + plane, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = cc[l][e] & 0xffffu ? (int)(0xffffu - (fl[l][e] >> 16)) : -1;
+            store8(st + 2 * plane, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (int)(rl[l][e] >> 16);
+            store8(st + 3 * plane, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (int)(rl[l][e] & 0xffffu);
+            store8(st + 4 * plane, v);
+        }
+        if constexpr (EXCESS) store8(o.excess + ((long)c.b * L + l) * p.C + c.c0, sum[l]);
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconExceed (sgv_ew.h).  Non-zero (nothing launched): -1 null input (levels
+// included), -2 no output, -3 bad shape, n_level outside [1, SGV_MAX_EXCEED_LEVELS] or T > 65535 (the packed state), -4 y, stats or excess
+// not 16-byte aligned or levels not 4-byte aligned
+int ew_recon_exceedance(int dtype, GNParams p, const float* scale, const float* mn, const ReconExceed& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.levels) return -1;
+    if (!o.stats && !o.excess) return -2;
+    if (o.n_level < 1 || o.n_level > SGV_MAX_EXCEED_LEVELS || p.T > XC_MAX_T) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.stats | (uintptr_t)o.excess) & 15) return -4;
+    if ((uintptr_t)o.levels & 3) return -4;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const dim3 grid(cdiv_i(p.C, XC_BLOCK_COLS), 1, p.B);
+    auto launch = [&](auto el, auto ab, auto st, auto ex) {
+        if constexpr (decltype(st)::value || decltype(ex)::value)
+            hipLaunchKernelGGL((recon_exceed_kernel<typename decltype(el)::type, decltype(ab)::value, decltype(st)::value, decltype(ex)::value>), grid, dim3(256), 0, s,
+                               p, q, o);
+    };
+    // recon_dispatch leaves out the combination with every flag false only; the launcher above never instantiates the kernel without an output
+    if (o.above) recon_dispatch<true>(launch, dtype, o.stats != nullptr, o.excess != nullptr);
+    else recon_dispatch<false>(launch, dtype, o.stats != nullptr, o.excess != nullptr);
     return 0;
 }

@@ -237,6 +237,28 @@ struct ReconGram {
 };
 size_t ew_recon_gram_work_floats(int B, int T, int C);
 int ew_recon_gram(int dtype, GNParams p, const float* scale, const float* mn, const ReconGram& o, hipStream_t s);
+// recon head -> the level-crossing statistics over TIME of the physical field against n_level = L levels per channel,
+// 1 <= L <= SGV_MAX_EXCEED_LEVELS, the field never stored.  With x[t] the value ew_recon_physical would store at (b, t, n) (layout
+// [B][T][C]), lam = levels[l][n] and e[t] = (x[t] > lam) for above, (x[t] < lam) otherwise (strict; a NaN exceeds nothing):
+//   stats[b][0][l][n] = count:   the number of t with e[t]
+//   stats[b][1][l][n] = first:   the smallest t with e[t], -1 if none
+//   stats[b][2][l][n] = last:    the largest t with e[t], -1 if none
+//   stats[b][3][l][n] = longest: the length of the longest run of consecutive t with e[t], 0 if none
+//   stats[b][4][l][n] = runs:    the number of t with e[t] and (t == 0 or not e[t - 1])
+//   excess[b][l][n]   = s after: s = +0.0; for t ascending, where e[t]: s = fl(s + d[t]), d[t] = fl(x[t] - lam) (fl(lam - x[t])
+//                       below) -- the difference of the stored value, rounded on its own.  Exactly +0.0 where nothing exceeds.
+// levels fp32 [L][C] dense, 4-byte aligned (input); stats int32 [B][5][L][C] and excess fp32 [B][L][C], 16-byte aligned, either may
+// be null, not both.  T <= 65535 (the kernel packs its counters into 16-bit halves).  An output depends on sample b, level row l
+// and channel n alone -- a level gives alone the bits it gives among 4, in any order; a sample the bits it gives in any batch; an
+// output the bits it gives with or without the other -- and two launches are bitwise equal.  No atomics, no workspace.
+// Non-zero (nothing launched): -1 null input (levels included), -2 no output, -3 bad shape, L outside [1, SGV_MAX_EXCEED_LEVELS] or
+// T > 65535, -4 y, stats or excess not 16-byte aligned or levels not 4-byte aligned
+constexpr int SGV_MAX_EXCEED_LEVELS = 4;          // (SGV_MAX_LEVELS of include/sgvae.h is the depth of the hierarchy, another thing)
+struct ReconExceed {
+    const float* levels = nullptr; int n_level = 0; bool above = true;
+    int* stats = nullptr; float* excess = nullptr;
+};
+int ew_recon_exceedance(int dtype, GNParams p, const float* scale, const float* mn, const ReconExceed& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

@@ -402,6 +402,19 @@ int sgv_test_recon_gram(int dtype, const void* y, long ldy, double* sums, const 
         return ew_recon_gram(dtype, q, scale, min, o, s);
     });
 }
+int sgv_test_recon_exceedance(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
+                              const float* scale, const float* min, const float* levels, int n_level, int side, int32_t* stats,
+                              float* excess, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_exceedance";
+    GNParams p;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(exceedance_args_ok(me, T, levels, n_level, side, stats, excess));
+    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
+        ReconExceed o;
+        o.levels = levels; o.n_level = n_level; o.above = side == SGV_SIDE_ABOVE; o.stats = stats; o.excess = excess;
+        return ew_recon_exceedance(dtype, q, scale, min, o, s);
+    });
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

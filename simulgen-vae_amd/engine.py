@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_temporal", "sgv_gram", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_temporal", "sgv_gram", "sgv_exceedance", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_recon_temporal", "sgv_test_recon_gram", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_recon_temporal", "sgv_test_recon_gram", "sgv_test_recon_exceedance", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -104,6 +104,10 @@ REGRESS_MAX_COVARIATES = 32                      # the weights of a launch fit t
 MAX_FUNCTIONALS = 32                             # SGV_MAX_FUNCTIONALS: the weight rows of Engine.project are the 32 columns of the kernel's MFMA tile
 MAX_TEMPORAL = 32                                # SGV_MAX_TEMPORAL: the weight rows of Engine.temporal are the 32 rows of the kernel's MFMA tile
 MAX_GRAM_T = 256                                 # SGV_MAX_GRAM_T: the time steps of Engine.gram are at most 8 row tiles of the kernel's accumulators
+MAX_LEVELS = 4                                   # SGV_MAX_EXCEED_LEVELS: the levels of Engine.exceedance are what the kernel's per-thread state holds in registers
+EXCEEDANCE_MAX_T = 65535                         # the kernel packs its step counters into 16-bit halves
+EXCEEDANCE_SIDES = {"above": 0, "below": 1}      # SGV_SIDE_*
+EXCEEDANCE_STATS = ("count", "first", "last", "longest", "runs")      # the planes of Engine.exceedance's stats, in this order
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")     # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -162,6 +166,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_project.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.sgv_temporal.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.sgv_gram.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.sgv_exceedance.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -233,6 +238,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_project.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_temporal.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_gram.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.sgv_test_recon_exceedance.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -444,7 +450,7 @@ class Engine:
         _check(self.lib, self.lib.sgv_set_shard(self.h, int(rank), int(world)), "sgv_set_shard")
 
     def set_draw_row(self, first_row: int):
-        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project, temporal, gram) takes
+        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project, temporal, gram, exceedance) takes
         row first_row + b of the streams the call draws from (include/sgvae.h: sgv_set_draw_row).  With the draw position put back in
         front of every batch (set_train_state) a study cut into batches gets the noise one call over all of it would get.  Default 0."""
         _check(self.lib, self.lib.sgv_set_draw_row(self.h, int(first_row)), "sgv_set_draw_row")
@@ -816,6 +822,43 @@ class Engine:
             ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
             return (ptr(node_weights), ptr(offset), C.c_void_p(out.data_ptr())), out
         return self._surrogate("sgv_gram", z, xs, scale, min, fix, tail)
+
+    def exceedance(self, z, xs, scale, min, levels, side="above", fix=True, stats=True, excess=True):
+        """The level-crossing statistics over time of the field generate() would write, by the recon head's last pass itself; the
+        field is never stored.  Same inputs and checks as summarize(); num_time <= EXCEEDANCE_MAX_T.  levels: contiguous fp32 CUDA
+        [L, N], 1 <= L <= MAX_LEVELS (predict.exceedance_levels validates and shapes a host array); side "above" or "below": a
+        time step exceeds its level when the value is strictly above / below it.  stats, excess: True for a new tensor, False to
+        leave that output out (not both), or a contiguous CUDA tensor to write into, int32 [B, 5, L, N] / fp32 [B, L, N] (a slice
+        along the first axis of a larger one will do).  Returns {"stats": ..., "excess": ...} with the outputs asked for:
+        stats[b, k] for k in EXCEEDANCE_STATS order is count (steps that exceed), first and last (their smallest and largest time
+        step, -1 if none), longest (the longest run of consecutive exceeding steps) and runs (the number of maximal runs);
+        excess[b, l, n] is the fp32 sum over the exceeding steps, t ascending, of fl(value - level) (fl(level - value) below),
+        exactly +0.0 where nothing exceeds.  Every output depends on its sample, level and node alone, so any cut of the conditions
+        into batches gives the same bits.  Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        if T > EXCEEDANCE_MAX_T:
+            raise ValueError(f"num_time = {T} is beyond the limit of {EXCEEDANCE_MAX_T} time steps of the exceedance pass")
+        if side not in EXCEEDANCE_SIDES:
+            raise ValueError(f"side must be one of {sorted(EXCEEDANCE_SIDES)}, not {side!r}")
+        L = int(levels.shape[0]) if t.is_tensor(levels) and levels.dim() == 2 else 0
+        if L < 1 or L > MAX_LEVELS or not is_tensor_of(levels, t.float32, (L, N)):
+            raise ValueError(f"levels must be a contiguous float32 CUDA tensor of shape [L, {N}] with 1 <= L <= {MAX_LEVELS}")
+        if stats is False and excess is False:
+            raise ValueError("nothing to compute: stats and excess are both False")
+
+        def tail(B):
+            res = {}
+            for name, v, dt, shape in (("stats", stats, t.int32, (B, 5, L, N)), ("excess", excess, t.float32, (B, L, N))):
+                if v is True:
+                    res[name] = t.empty(shape, dtype=dt, device="cuda")
+                elif v is not False:
+                    if not is_tensor_of(v, dt, shape):
+                        raise ValueError(f"{name} must be True, False or a contiguous {dt} CUDA tensor of shape {shape}")
+                    res[name] = v
+            ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+            return (C.c_void_p(levels.data_ptr()), L, EXCEEDANCE_SIDES[side], ptr(res.get("stats")), ptr(res.get("excess"))), res
+        return self._surrogate("sgv_exceedance", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -46,6 +46,10 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     rows, lam, frac = g.modes(energy=0.99)         # autocorrelation / MAC, and the POD temporal modes of the whole study by
     pod = s.pod(conditions, rank=8, node_weights=area)   # numpy.linalg.eigh on the host; pod() chains gram -> modes -> temporal
                                                    # into a rank-R compression with coefficients [P, R, N]
+    dur = s.exceedance(conditions, [allowable, 1.2 * allowable])   # what depends on the ORDER of the time steps: how long each node
+    hot = dur.duration(dt), dur.longest_duration(dt)   # stays above a level, when it first crosses and is last above, one long
+    node, steps = dur.worst()                      # excursion or many short ones (dur.runs), the accumulated excess: 24 L N bytes
+                                                   # per condition instead of 4 T N
 """
 from __future__ import annotations
 
@@ -56,7 +60,7 @@ import pickle
 
 import numpy as np
 
-from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, LAYOUTS, MAX_FUNCTIONALS, MAX_GRAM_T, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
+from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, EXCEEDANCE_MAX_T, EXCEEDANCE_SIDES, EXCEEDANCE_STATS, LAYOUTS, MAX_LEVELS, MAX_FUNCTIONALS, MAX_GRAM_T, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
                      SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of)
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
@@ -618,6 +622,122 @@ class PodResult(_Result):
             return x
         x = np.asarray(self.rows, np.float64).T @ np.asarray(c, np.float64)
         return x if self.offset is None else x + np.asarray(self.offset, np.float64)
+
+
+def exceedance_levels(levels, N):
+    """The levels of Surrogate.exceedance as contiguous float32 [L, N] in physical units, 1 <= L <= MAX_LEVELS: a scalar is one
+    level for every node, a 1-D array of L entries is L levels, each broadcast over the nodes, an [L, N] array is taken node by
+    node.  A CUDA tensor stays on the device and comes back as a contiguous float32 CUDA tensor; it is judged by its shape and
+    dtype alone and NOT read back, so its entries are not looked at (nothing exceeds a NaN level).  Anything else is looked at
+    through np.asarray and comes back as a numpy array, every entry finite as float32.  ValueError naming the problem otherwise:
+    a rank above 2, a last dimension of an [L, N] array other than N, L outside its range, or -- host data -- an entry that is not
+    finite (the first one is named).  numpy only for host data."""
+    N = int(N)
+    dev = _is_device_tensor(levels)
+    a = levels if dev else np.asarray(levels, dtype=np.float64)
+    shape = tuple(int(d) for d in a.shape)
+    if len(shape) > 2:
+        raise ValueError(f"levels: a scalar, an [L] vector or an [L, N] array is required, got shape {shape}")
+    if len(shape) == 2 and shape[1] != N:
+        raise ValueError(f"levels: the last dimension is {shape[1]}, expected N = {N} (shape {shape})")
+    L = shape[0] if shape else 1
+    if L < 1 or L > MAX_LEVELS:
+        raise ValueError(f"levels: L = {L} levels, between 1 and {MAX_LEVELS} are required (call again for more"
+                         + (f"; an [L] vector is L levels for every node, one level per node is [1, N] = [1, {N}])" if len(shape) == 1 else ")"))
+    if dev:
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"levels: a floating dtype is required, not {a.dtype}")
+        import torch
+        return a.to(dtype=torch.float32).reshape(L, -1).expand(L, N).contiguous()
+    with np.errstate(over="ignore"):          # a value beyond float32 becomes inf and is reported below
+        v = a.astype(np.float32).reshape(L, -1)
+    bad = np.argwhere(~np.isfinite(v))
+    if bad.size:
+        l, n = (int(k) for k in bad[0])
+        where = "levels" if not shape else f"levels[{l}]" if len(shape) == 1 else f"levels[{l}, {n}]"
+        raise ValueError(f"{where} = {float(a.reshape(L, -1)[l, n])!r} is not finite as float32")
+    return np.array(np.broadcast_to(v, (L, N)), order="C")          # a copy: the broadcast view is read-only
+
+
+class ExceedanceResult(_Result):
+    """Surrogate.exceedance's result for P conditions against L levels: the level-crossing statistics of every node's T time steps,
+    device tensors that are the caller's.  A step exceeds its level when the field is strictly above it (side "above") or below it
+    ("below").  stats int32 [P, 5, L, N] with the views count (the steps that exceed), first and last (their smallest and largest
+    time step, -1 if none), longest (the longest run of consecutive exceeding steps, 0 if none) and runs (the number of such
+    maximal runs), each [P, L, N]; excess fp32 [P, L, N], the sum over the exceeding steps of field - level (level - field below),
+    exactly 0 where nothing exceeds; levels fp32 [L, N] as they were used.  An output that was not asked for is None and its
+    methods raise ValueError.  What is derived is plain torch on the small result, computed on the engine stream."""
+    FIELDS = ("stats", "excess", "levels", "side", "T")
+
+    def __init__(self, stream=None, **kw):
+        super().__init__(**kw)
+        self._stream = stream
+
+    def _on_stream(self, fn):
+        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
+            return fn()
+
+    def _plane(self, name):
+        if self.stats is None:
+            raise ValueError(f"{name}: the step statistics were not asked for (want=(\"steps\", ...))")
+        return self.stats[:, EXCEEDANCE_STATS.index(name)]
+
+    count = property(lambda self: self._plane("count"))
+    first = property(lambda self: self._plane("first"))
+    last = property(lambda self: self._plane("last"))
+    longest = property(lambda self: self._plane("longest"))
+    runs = property(lambda self: self._plane("runs"))
+
+    def _excess(self, what):
+        if self.excess is None:
+            raise ValueError(f"{what}: the excess was not asked for (want=(..., \"excess\"))")
+        return self.excess
+
+    def ever(self):
+        """count > 0: bool [P, L, N], whether the node exceeds the level at any time step"""
+        return self._on_stream(lambda: self.count > 0)
+
+    def fraction(self):
+        """count / T: fp32 [P, L, N], the share of the time steps that exceed"""
+        return self._on_stream(lambda: self.count.float() / float(self.T))
+
+    def duration(self, dt=1.0):
+        """count * dt: fp32 [P, L, N], the total time beyond the level"""
+        return self._on_stream(lambda: self.count.float() * float(dt))
+
+    def longest_duration(self, dt=1.0):
+        """longest * dt: fp32 [P, L, N], the length of the longest uninterrupted excursion"""
+        return self._on_stream(lambda: self.longest.float() * float(dt))
+
+    def first_time(self, dt=1.0):
+        """first * dt, NaN where the node never exceeds: fp32 [P, L, N]"""
+        def fn():
+            f = self.first
+            return (f.float() * float(dt)).masked_fill(f < 0, float("nan"))
+        return self._on_stream(fn)
+
+    def excess_integral(self, dt=1.0):
+        """excess * dt: fp32 [P, L, N], the rectangle-rule integral over time of the part of the field beyond the level"""
+        return self._on_stream(lambda: self._excess("excess_integral") * float(dt))
+
+    def mean_excess(self):
+        """excess / count, 0 where count = 0: fp32 [P, L, N], how far beyond the level the node is while it exceeds"""
+        def fn():
+            c = self.count
+            return (self._excess("mean_excess") / c.clamp(min=1).float()).masked_fill(c == 0, 0.0)
+        return self._on_stream(fn)
+
+    def worst(self):
+        """(the node with the largest count [P, L] int64, that count [P, L] int32); the smallest node on a tie"""
+        import torch
+
+        def fn():
+            c = self.count
+            N = c.shape[2]
+            top = c.max(dim=2).values
+            nodes = torch.arange(N, device=c.device).view(1, 1, N)
+            return torch.where(c == top.unsqueeze(2), nodes, N).min(dim=2).values, top
+        return self._on_stream(fn)
 
 
 class ScoreResult(_Result):
@@ -1345,6 +1465,46 @@ class Surrogate:
                 S = t.from_numpy(rows.astype(np.float64).sum(axis=1).astype(np.float32)).to(device="cuda")
                 coeff -= S.view(1, -1, 1) * m.view(1, 1, -1)
         return PodResult(rows=rows, eigenvalues=lam, fraction=frac, coefficients=coeff, offset=m)
+
+    def exceedance(self, conditions, levels, side="above", want=("steps", "excess"), mode="fix"):
+        """What depends on the order of the time steps of predict(conditions), per node and level, without the fields: levels a
+        scalar, an [L] vector or [L, N] in physical units, 1 <= L <= MAX_LEVELS (see exceedance_levels); side "above" or "below";
+        want: "steps" for the integer statistics (count, first, last, longest, runs), "excess" for the accumulated excess -> an
+        ExceedanceResult.  The recon head's last pass compares the values predict() would store (bit for bit the same) with the
+        levels, strictly, one thread per node going through the time steps in order: the result is integer apart from the excess,
+        which is one fp32 sum over t ascending, so it depends on its condition, level and node alone, and the decoder's noise of
+        condition p is row p of the streams one call over all conditions would draw from (Engine.set_draw_row): the batch size does
+        not show in the bits in either mode, and 24 L N bytes per condition leave the decoder instead of 4 T N.  The levels are
+        uploaded once per call and every batch is written straight into its rows of the result.  Batching, streams, the single
+        input-range decision and `mode` are temporal()'s: no host wait between batches."""
+        t = self.torch
+        if side not in EXCEEDANCE_SIDES:
+            raise ValueError(f"side must be one of {sorted(EXCEEDANCE_SIDES)}, not {side!r}")
+        want = _wanted(want, ("steps", "excess"), f"want: a tuple of 'steps' and 'excess' is required, not {want!r}",
+                       "want: nothing to compute")
+        if self.T > EXCEEDANCE_MAX_T:
+            raise ValueError(f"num_time = {self.T} is beyond the limit of {EXCEEDANCE_MAX_T} time steps of the exceedance pass")
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        lv = exceedance_levels(levels, self.N)
+        if not t.is_tensor(lv):
+            lv = t.from_numpy(lv)
+        L = lv.shape[0]
+        stats = t.empty((P, 5, L, self.N), dtype=t.int32, device="cuda") if "steps" in want else None          # the result: the caller's stream owns it
+        excess = t.empty((P, L, self.N), dtype=t.float32, device="cuda") if "excess" in want else None
+        eng = self.eng
+        at = eng.train_state()
+        with _engine_stream(self._stream):
+            lv = lv.to(device="cuda", non_blocking=True)
+            try:
+                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
+                    # as in temporal(): every batch draws from the streams of the call's first draw, condition p from their row p
+                    eng.set_train_state(at["step"], at["seed"], at["draw"])
+                    eng.set_draw_row(lo)
+                    eng.exceedance(lat, xs, self.data_scale, self.data_min, lv, side=side, fix=mode == "fix",
+                                   stats=False if stats is None else stats[lo:hi], excess=False if excess is None else excess[lo:hi])
+            finally:
+                eng.set_draw_row(0)
+        return ExceedanceResult(stream=self._stream, stats=stats, excess=excess, levels=lv, side=side, T=self.T)
 
     def score(self, conditions, truth, mode="fix"):
         """How wrong predict(conditions) is against held-out fields, without the fields: truth [P, T, N] fp32 in physical units (the

@@ -1,7 +1,7 @@
 // libsgvae engine: parameter/optimizer arenas, layer graph of the hierarchical VAE, forward /
 // backward orchestration on one HIP stream, and the engine's part of the C ABI of include/sgvae.h.
 // Beside it, sharing engine_internal.h: engine_build.hip (what runs once at creation), engine_optim.hip (gradient buckets, AdamW), engine_comm.hip (RCCL),
-// engine_streams.hip (auxiliary streams), engine_input.hip, engine_ckpt.hip, test_hooks.hip.
+// engine_streams.hip (auxiliary streams), engine_input.hip, engine_ckpt.hip, engine_surrogate.hip (the surrogate entry points), test_hooks.hip.
 //
 // Graph restated from the reference (channels-last, weights [tap][Cout][Cin]):
 //   VAE.forward modules/VAE_network.py:79-121 ; Encoder modules/encoder.py:96-167 ;
@@ -9,6 +9,7 @@
 //   training step modules/train.py:139-168.
 // The backward pass is written out by hand (the reference uses autograd).
 #include "engine_internal.h"
+#include "recon_tails.h"
 
 // ---- error state of the library: one thread-local message, written through sgv_set_error by every translation unit ----
 static thread_local char g_err[1024] = "";
@@ -896,75 +897,19 @@ static int encoder_fwd(sgv_engine* e, int B, bool join_lane) {
     return 0;
 }
 
-// What replaces the loss tail of the recon head in a surrogate pass (recon_out.hip): the physical field (sgv_generate), its summaries
-// (sgv_summarize), its error against the truth (sgv_score), the ensemble statistics (sgv_ensemble), the sums of a Sobol study
-// (sgv_sobol), the histogram of the members (sgv_distribution), their co-moments with the covariates (sgv_regress), weighted sums
-// over the mesh (sgv_project), weighted sums over time (sgv_temporal), the temporal Gram matrix (sgv_gram) or the level-crossing statistics (sgv_exceedance); only the members of `kind` are read.
-struct GenOut {
-    enum Kind { FIELD, SUMMARY, SCORE, ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS, PROJECT, TEMPORAL, GRAM, EXCEED } kind;
-    const float* scale; const float* mn;
-    int layout = SGV_LAYOUT_TN; float* out = nullptr;          // FIELD
-    ReconSummary sum;                                          // SUMMARY
-    ReconScore score; const float* truth = nullptr;            // SCORE
-    ReconEnsemble ens; long ens_count = 0;                     // ENSEMBLE
-    ReconSobol sob; int sob_params = 0; long sob_blocks = 0;   // SOBOL
-    ReconDistribution dist; long dist_count = 0;               // DISTRIBUTION
-    ReconRegress reg; int reg_cov = 0; long reg_count = 0;     // REGRESS
-    ReconProject proj;                                         // PROJECT
-    ReconTemporal temp;                                        // TEMPORAL
-    ReconGram gram;                                            // GRAM
-    ReconExceed exc;                                           // EXCEED
-    // ENSEMBLE, SOBOL, DISTRIBUTION, REGRESS: sample b of the batch is member members_before() + b of its study, and the decoder's noise follows that index
-    bool by_member() const { return kind == ENSEMBLE || kind == SOBOL || kind == DISTRIBUTION || kind == REGRESS; }
-    long members_before() const {
-        return kind == SOBOL ? sob_blocks * (sob_params + 2) : kind == DISTRIBUTION ? dist_count : kind == REGRESS ? reg_count : ens_count;
-    }
-};
-// The tail itself, on the recon head's convolution output and statistics in p.  The frame partials of the summary and the score pass and
-// the per-block partials of the project and the Gram pass go to e->colpart, as does the transposed copy of the weights of the temporal pass, which nothing uses once the statistics are done; the ensemble pass merges the batch into the caller's running state and
-// the field goes straight to the caller's buffer (no loss, no read of x_in, no x_hat): neither needs a workspace, nor do the Sobol, the
-// distribution and the regression pass.
-static int recon_tail(sgv_engine* e, const GNParams& p, const GenOut& g) {
-    static const char* const tag[] = {"recon_phys", "recon_summary", "recon_score", "recon_ensemble", "recon_sobol", "recon_hist", "recon_regress", "recon_project", "recon_temporal", "recon_gram", "recon_exceed"};
-    static const char* const rejected[] = {"sgv_generate: the output pass rejected its arguments (%d: out_dev must be 16-byte aligned)",
-                                           "sgv_summarize: the summary pass rejected its arguments (%d)", "sgv_score: the error pass rejected its arguments (%d)",
-                                           "sgv_ensemble: the ensemble pass rejected its arguments (%d)", "sgv_sobol: the Sobol pass rejected its arguments (%d)",
-                                           "sgv_distribution: the distribution pass rejected its arguments (%d)",
-                                           "sgv_regress: the regression pass rejected its arguments (%d)",
-                                           "sgv_project: the project pass rejected its arguments (%d)",
-                                           "sgv_temporal: the temporal pass rejected its arguments (%d)",
-                                           "sgv_gram: the Gram pass rejected its arguments (%d)",
-                                           "sgv_exceedance: the exceedance pass rejected its arguments (%d)"};
-    ScopedTimer tm(e, tag[g.kind], nullptr);
-    int r = 0;
-    switch (g.kind) {
-    case GenOut::FIELD: r = ew_recon_physical(e->dt, p, g.scale, g.mn, g.layout, g.out, e->stream); break;
-    case GenOut::SUMMARY: { ReconSummary o = g.sum; o.work = e->colpart; r = ew_recon_summary(e->dt, p, g.scale, g.mn, o, e->stream); break; }
-    case GenOut::SCORE: { ReconScore o = g.score; o.work = e->colpart; r = ew_recon_score(e->dt, p, g.scale, g.mn, g.truth, o, e->stream); break; }
-    case GenOut::ENSEMBLE: r = ew_recon_ensemble(e->dt, p, g.scale, g.mn, g.ens_count, g.ens, e->stream); break;
-    case GenOut::SOBOL: r = ew_recon_sobol(e->dt, p, g.scale, g.mn, g.sob_params, g.sob_blocks, g.sob, e->stream); break;
-    case GenOut::DISTRIBUTION: r = ew_recon_distribution(e->dt, p, g.scale, g.mn, g.dist_count, g.dist, e->stream); break;
-    case GenOut::REGRESS: r = ew_recon_regress(e->dt, p, g.scale, g.mn, g.reg_cov, g.reg_count, g.reg, e->stream); break;
-    case GenOut::PROJECT: { ReconProject o = g.proj; o.work = e->colpart; r = ew_recon_project(e->dt, p, g.scale, g.mn, o, e->stream); break; }
-    case GenOut::TEMPORAL: { ReconTemporal o = g.temp; o.work = e->colpart; r = ew_recon_temporal(e->dt, p, g.scale, g.mn, o, e->stream); break; }
-    case GenOut::EXCEED: r = ew_recon_exceedance(e->dt, p, g.scale, g.mn, g.exc, e->stream); break;
-    case GenOut::GRAM: { ReconGram o = g.gram; o.work = e->colpart; r = ew_recon_gram(e->dt, p, g.scale, g.mn, o, e->stream); break; }
-    }
-    return r ? fail(SGV_ERR_ARG, rejected[g.kind], r) : 0;
-}
-// Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `gen`, the recon head's
-// convolution and statistics followed by recon_tail instead of the loss tail.
-static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenOut* gen = nullptr) {
+// Decoder.forward (decoder.py:170-216) from e->zlat / e->xs_raw, then the recon head + loss pass -- or, with `tail`, the recon head's
+// convolution and statistics followed by that recon tail instead of the loss tail (a surrogate pass: recon_tails.h).
+extern "C++" int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const ReconTail* tail) {
     const int n = e->n, n_st = e->n_st;
     const long M = (long)B * e->T;
-    // sgv_ensemble, sgv_sobol: the noise of member m is a function of (seed, m, site) alone -- the rows members_before + b of the streams
+    // A tail with members_before >= 0: the noise of member m is a function of (seed, m, site) alone -- the rows members_before + b of the streams
     // the first call after sgv_seed draws from -- and the draw position is left where it is: a study gives the same bits at any batch size.
     // The other surrogate passes draw per call, from row e->draw_row on (sgv_set_draw_row; 0 unless a caller cuts a study into batches itself)
-    const bool ens = gen && gen->by_member();
+    const bool ens = tail && tail->members_before >= 0;
     uint64_t ens_draw = 0;
     for (int s = 1; s < n_st; ++s) {
         if (!e->eps_set[s]) ew_randn(e->eps[s], M * e->dec[s], e->seed, (ens ? ens_draw++ : e->draw++) * 8 + s, e->stream, (long)e->T * e->dec[s], e->shard_world, e->shard_rank,
-                                     ens ? gen->members_before() : gen ? e->draw_row : 0);
+                                     ens ? tail->members_before : tail ? e->draw_row : 0);
     }
     {
         const Layer& l = e->layers[e->start_lin];
@@ -1012,7 +957,13 @@ static int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const GenO
         CHK(conv_fwd(e, L, e->dec_out[n_st - 1], S.y, M));
         ew_gn_stats(e->dt, p, e->stream);
     }
-    if (gen) return recon_tail(e, p, *gen);
+    if (tail) {
+        // the tail's workspace is e->colpart, which nothing uses once the statistics are done (sized in sgv_create); the field and the
+        // running states go straight to the caller's buffers (no loss, no read of x_in, no x_hat)
+        ScopedTimer tm(e, tail->tag, nullptr);
+        const int r = tail->run(e->dt, p, e->colpart, e->stream);
+        return r ? fail(SGV_ERR_ARG, tail->rejected, r) : 0;
+    }
     p.dout = e->x_in.p; p.lddout = e->x_in.ld; p.loss_type = e->cfg.loss_type;
     p.loss_sums = e->scal;
     if (e->write_xhat || !train) { p.out = e->xhat.p; p.ldout = e->xhat.ld; }
@@ -1058,9 +1009,9 @@ int sgv_forward(sgv_engine* e, int train, int mode_fix, float* scalars_host) {
     return SGV_OK;
 }
 
-// what sgv_decode and sgv_generate share in front of decoder_fwd: argument checks, fresh weight copies, eval-mode spectral norm,
+// what sgv_decode and the surrogate entry points (engine_surrogate.hip) share in front of decoder_fwd: argument checks, fresh weight copies, eval-mode spectral norm,
 // the caller's latents into e->zlat / e->xs_raw
-static int decode_begin(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, const char* who) {
+extern "C++" int decode_begin(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, const char* who) {
     if (!e || !z_dev) return fail(SGV_ERR_ARG, "null argument");
     if (batch < 1 || batch > e->maxB) return fail(SGV_ERR_ARG, "batch %d outside [1,%d]", batch, e->maxB);
     if (!xs_dev)
@@ -1086,137 +1037,6 @@ int sgv_decode(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch
     for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
     if (scalars_host) CHK(read_scalars(e, batch, scalars_host));
     return SGV_OK;
-}
-
-// what the five surrogate entry points share behind their own argument checks: decode_begin, no forward left to read (the maps of an
-// earlier forward are overwritten from here on, and these passes leave no x_hat behind), the decoder with `gen` as its tail
-static int surrogate_pass(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const char* who, const GenOut& gen) {
-    CHK(decode_begin(e, z_dev, xs_dev, batch, who));
-    e->have_fwd = false;
-    e->fwd_train = false;
-    CHK(decoder_fwd(e, batch, 0, mode_fix, &gen));
-    for (int s = 0; s < e->n_st; ++s) e->eps_set[s] = 0;
-    return SGV_OK;
-}
-
-int sgv_generate(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                 const float* min_dev, int layout, float* out_dev) {
-    if (!e || !z_dev || !scale_dev || !min_dev || !out_dev) return fail(SGV_ERR_ARG, "sgv_generate: null argument");
-    if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "sgv_generate: unknown layout %d", layout);
-    if ((uintptr_t)out_dev & 15) return fail(SGV_ERR_ARG, "sgv_generate: out_dev must be 16-byte aligned");
-    GenOut gen = {GenOut::FIELD, scale_dev, min_dev};
-    gen.layout = layout; gen.out = out_dev;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_generate", gen);
-}
-
-int sgv_set_probes(sgv_engine* e, const int32_t* nodes_host, int count) {
-    if (!e) return fail(SGV_ERR_ARG, "sgv_set_probes: null engine");
-    if (count < 0 || count > SGV_MAX_PROBES) return fail(SGV_ERR_ARG, "sgv_set_probes: count %d outside [0, %d]", count, SGV_MAX_PROBES);
-    if (count > 0 && !nodes_host) return fail(SGV_ERR_ARG, "sgv_set_probes: null node list");
-    const int bad = first_bad_probe(nodes_host, count, e->N);
-    if (bad >= 0) return fail(SGV_ERR_ARG, "sgv_set_probes: nodes[%d] = %d is outside [0, %d)", bad, (int)nodes_host[bad], e->N);
-    if (count > 0) {
-        if (!e->probes_dev) HIPCHK(hipMalloc((void**)&e->probes_dev, sizeof(int32_t) * SGV_MAX_PROBES));
-        // an upload still in flight reads the old vector: let it finish before the storage changes
-        if (!e->probes_host.empty()) HIPCHK(hipStreamSynchronize(e->stream));
-        e->probes_host.assign(nodes_host, nodes_host + count);
-        HIPCHK(hipMemcpyAsync(e->probes_dev, e->probes_host.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, e->stream));
-    }
-    e->n_probes = count;
-    return SGV_OK;
-}
-
-int sgv_summarize(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                  const float* min_dev, const sgv_summary_out* out) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_summarize: null argument");
-    CHK(summary_out_ok("sgv_summarize", "output", out));
-    if (out->probes && e->n_probes < 1) return fail(SGV_ERR_ARG, "sgv_summarize: probes asked for, but no probe nodes are set (sgv_set_probes)");
-    GenOut gen = {GenOut::SUMMARY, scale_dev, min_dev};
-    gen.sum = recon_summary_of(*out, e->probes_dev, e->n_probes, nullptr);
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_summarize", gen);
-}
-
-int sgv_score(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-              const float* min_dev, const float* truth_dev, const sgv_score_out* out) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_score: null argument");
-    CHK(score_out_ok("sgv_score", "truth_dev", truth_dev, out));
-    GenOut gen = {GenOut::SCORE, scale_dev, min_dev};
-    gen.score = recon_score_of(*out, nullptr); gen.truth = truth_dev;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_score", gen);
-}
-
-int sgv_ensemble(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                 const float* min_dev, long count_before, const sgv_ensemble_state* st) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_ensemble: null argument");
-    CHK(ensemble_state_ok("sgv_ensemble", "batch", st, count_before, batch));
-    GenOut gen = {GenOut::ENSEMBLE, scale_dev, min_dev};
-    gen.ens = recon_ensemble_of(*st); gen.ens_count = count_before;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_ensemble", gen);
-}
-
-int sgv_sobol(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-              const float* min_dev, int n_params, long blocks_before, const sgv_sobol_state* st) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_sobol: null argument");
-    CHK(sobol_state_ok("sgv_sobol", "batch", st, n_params, blocks_before, batch));
-    GenOut gen = {GenOut::SOBOL, scale_dev, min_dev};
-    gen.sob = recon_sobol_of(*st); gen.sob_params = n_params; gen.sob_blocks = blocks_before;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_sobol", gen);
-}
-
-int sgv_distribution(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                     const float* min_dev, long count_before, const sgv_distribution_state* st) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_distribution: null argument");
-    CHK(distribution_state_ok("sgv_distribution", "batch", st, count_before, batch));
-    GenOut gen = {GenOut::DISTRIBUTION, scale_dev, min_dev};
-    gen.dist = recon_distribution_of(*st); gen.dist_count = count_before;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_distribution", gen);
-}
-
-int sgv_regress(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                const float* min_dev, int n_cov, const float* weights_dev, long count_before, const sgv_regress_state* st) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_regress: null argument");
-    CHK(regress_state_ok("sgv_regress", "batch", st, n_cov, weights_dev, count_before, batch));
-    GenOut gen = {GenOut::REGRESS, scale_dev, min_dev};
-    gen.reg = recon_regress_of(*st, weights_dev); gen.reg_cov = n_cov; gen.reg_count = count_before;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_regress", gen);
-}
-
-int sgv_project(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                const float* min_dev, const float* weights_dev, int n_func, float* out_dev) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_project: null argument");
-    CHK(project_args_ok("sgv_project", weights_dev, n_func, out_dev));
-    GenOut gen = {GenOut::PROJECT, scale_dev, min_dev};
-    gen.proj.weights = weights_dev; gen.proj.n_func = n_func; gen.proj.out = out_dev;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_project", gen);
-}
-
-int sgv_temporal(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                 const float* min_dev, const float* weights_dev, int n_func, float* out_dev) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_temporal: null argument");
-    CHK(temporal_args_ok("sgv_temporal", weights_dev, n_func, out_dev));
-    GenOut gen = {GenOut::TEMPORAL, scale_dev, min_dev};
-    gen.temp.weights = weights_dev; gen.temp.n_func = n_func; gen.temp.out = out_dev;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_temporal", gen);
-}
-
-int sgv_gram(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-             const float* min_dev, const float* node_weights_dev_or_NULL, const float* offset_dev_or_NULL, float* out_dev) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_gram: null argument");
-    CHK(gram_args_ok("sgv_gram", e->T, node_weights_dev_or_NULL, offset_dev_or_NULL, out_dev));
-    GenOut gen = {GenOut::GRAM, scale_dev, min_dev};
-    gen.gram.node_weights = node_weights_dev_or_NULL; gen.gram.offset = offset_dev_or_NULL; gen.gram.out = out_dev;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_gram", gen);
-}
-
-int sgv_exceedance(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
-                   const float* min_dev, const float* levels_dev, int n_level, int side, int32_t* stats_dev_or_NULL,
-                   float* excess_dev_or_NULL) {
-    if (!e || !z_dev || !scale_dev || !min_dev) return fail(SGV_ERR_ARG, "sgv_exceedance: null argument");
-    CHK(exceedance_args_ok("sgv_exceedance", e->T, levels_dev, n_level, side, stats_dev_or_NULL, excess_dev_or_NULL));
-    GenOut gen = {GenOut::EXCEED, scale_dev, min_dev};
-    gen.exc.levels = levels_dev; gen.exc.n_level = n_level; gen.exc.above = side == SGV_SIDE_ABOVE;
-    gen.exc.stats = stats_dev_or_NULL; gen.exc.excess = excess_dev_or_NULL;
-    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, "sgv_exceedance", gen);
 }
 
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host) {

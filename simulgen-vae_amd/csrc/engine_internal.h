@@ -1,4 +1,5 @@
 // Private to engine*.hip and test_hooks.hip: the engine's data model and the few helpers that more than one of those files calls.
+// (What the surrogate output passes check and launch is in recon_tails.h.)
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -237,144 +238,6 @@ struct sgv_engine {
     struct CkptState* ckpt = nullptr;
 };
 
-constexpr int SGV_MAX_PROBES = 4096;
-// position of the first probe node outside [0, N), -1 if none (sgv_set_probes, sgv_test_recon_summary)
-static inline int first_bad_probe(const int32_t* nodes, int count, int N) {
-    for (int i = 0; i < count; ++i) if (nodes[i] < 0 || nodes[i] >= N) return i;
-    return -1;
-}
-// The output structs of the surrogate passes, checked and converted in one place for the entry points (engine.hip) and the kernel
-// hooks (test_hooks.hip).  *_ok: 0, or SGV_ERR_ARG with the message set; `who` is the caller's name, the prefix of the message, and the
-// second string the one word in which the texts of an entry point and of its hook differ.
-static inline int summary_out_ok(const char* who, const char* noun, const sgv_summary_out* o) {
-    if (!o) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (!o->node_stats && !o->node_when && !o->frame_stats && !o->frame_where && !o->probes) return fail(SGV_ERR_ARG, "%s: all five outputs are NULL", who);
-    if ((((uintptr_t)o->node_stats | (uintptr_t)o->node_when) & 15) || (((uintptr_t)o->frame_stats | (uintptr_t)o->frame_where) & 7) || ((uintptr_t)o->probes & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned %s (node_stats / node_when 16 bytes, frame_stats / frame_where 8, probes 4)", who, noun);
-    return 0;
-}
-static inline ReconSummary recon_summary_of(const sgv_summary_out& o, const int* probe_nodes, int n_probes, float* work) {
-    ReconSummary r;
-    r.node_stats = o.node_stats; r.node_when = o.node_when; r.frame_stats = o.frame_stats; r.frame_where = o.frame_where;
-    r.probes = o.probes; r.probe_nodes = probe_nodes; r.n_probes = n_probes; r.work = work;
-    return r;
-}
-static inline int score_out_ok(const char* who, const char* truth_name, const float* truth, const sgv_score_out* o) {
-    if (!truth || !o) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (!o->node_err && !o->node_when && !o->frame_err && !o->frame_where) return fail(SGV_ERR_ARG, "%s: all four outputs are NULL", who);
-    if ((((uintptr_t)truth | (uintptr_t)o->node_err | (uintptr_t)o->node_when) & 15) || (((uintptr_t)o->frame_err | (uintptr_t)o->frame_where) & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (%s, node_err / node_when 16 bytes, frame_err / frame_where 4)", who, truth_name);
-    return 0;
-}
-static inline ReconScore recon_score_of(const sgv_score_out& o, float* work) {
-    ReconScore r;
-    r.node_err = o.node_err; r.node_when = o.node_when; r.frame_err = o.frame_err; r.frame_where = o.frame_where; r.work = work;
-    return r;
-}
-static inline int ensemble_state_ok(const char* who, const char* batch_name, const sgv_ensemble_state* st, long count_before, int batch) {
-    if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    const bool mo = st->mean || st->m2, ex = st->max || st->min || st->arg_max || st->arg_min, ec = st->exceed || st->limit;
-    if (!mo && !ex && !ec) return fail(SGV_ERR_ARG, "%s: no group of the state is given", who);
-    if ((mo && !(st->mean && st->m2)) || (ex && !(st->max && st->min && st->arg_max && st->arg_min)) || (ec && !(st->exceed && st->limit)))
-        return fail(SGV_ERR_ARG, "%s: half a group (mean + m2, max + min + arg_max + arg_min, limit + exceed go together)", who);
-    if ((((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->max | (uintptr_t)st->min | (uintptr_t)st->arg_max | (uintptr_t)st->arg_min |
-          (uintptr_t)st->exceed) & 15) || ((uintptr_t)st->limit & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (the state arrays 16 bytes, limit 4)", who);
-    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
-        return fail(SGV_ERR_ARG, "%s: count_before = %ld with %s = %d is outside [0, 2^24]", who, count_before, batch_name, batch);
-    return 0;
-}
-static inline ReconEnsemble recon_ensemble_of(const sgv_ensemble_state& st) {
-    ReconEnsemble r;
-    r.mean = st.mean; r.m2 = st.m2; r.vmax = st.max; r.vmin = st.min; r.imax = st.arg_max; r.imin = st.arg_min;
-    r.limit = st.limit; r.exceed = st.exceed;
-    return r;
-}
-constexpr int SGV_DISTRIBUTION_MIN_BINS = 2, SGV_DISTRIBUTION_MAX_BINS = 64;      // HI_MIN_BINS, HI_MAX_BINS of recon_out.hip: the block's byte histogram fits the LDS
-static inline int distribution_state_ok(const char* who, const char* batch_name, const sgv_distribution_state* st, long count_before, int batch) {
-    if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (!st->lo || !st->hi || !st->counts) return fail(SGV_ERR_ARG, "%s: lo, hi and counts are all required", who);
-    if (st->bins < SGV_DISTRIBUTION_MIN_BINS || st->bins > SGV_DISTRIBUTION_MAX_BINS)
-        return fail(SGV_ERR_ARG, "%s: bins = %d is outside [%d, %d]", who, st->bins, SGV_DISTRIBUTION_MIN_BINS, SGV_DISTRIBUTION_MAX_BINS);
-    if (((uintptr_t)st->lo | (uintptr_t)st->hi | (uintptr_t)st->counts) & 15) return fail(SGV_ERR_ARG, "%s: misaligned pointer (lo, hi and counts 16 bytes)", who);
-    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
-        return fail(SGV_ERR_ARG, "%s: count_before = %ld with %s = %d is outside [0, 2^24]", who, count_before, batch_name, batch);
-    return 0;
-}
-static inline ReconDistribution recon_distribution_of(const sgv_distribution_state& st) {
-    ReconDistribution r;
-    r.lo = st.lo; r.hi = st.hi; r.counts = st.counts; r.bins = st.bins;
-    return r;
-}
-constexpr int SGV_REGRESS_MAX_COVARIATES = 32;      // RG_MAX_K of recon_out.hip: the launch's weights fit the block's LDS table
-static inline int regress_state_ok(const char* who, const char* batch_name, const sgv_regress_state* st, int n_cov, const float* weights, long count_before,
-                                   int batch) {
-    if (!st || !weights) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (!st->mean || !st->m2 || !st->comoment) return fail(SGV_ERR_ARG, "%s: mean, m2 and comoment are all required", who);
-    if (n_cov < 1 || n_cov > SGV_REGRESS_MAX_COVARIATES) return fail(SGV_ERR_ARG, "%s: n_cov = %d is outside [1, %d]", who, n_cov, SGV_REGRESS_MAX_COVARIATES);
-    if ((((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->comoment) & 15) || ((uintptr_t)weights & 3))
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (the state arrays 16 bytes, weights 4)", who);
-    if (count_before < 0 || batch < 1 || count_before + batch > (1L << 24))
-        return fail(SGV_ERR_ARG, "%s: count_before = %ld with %s = %d is outside [0, 2^24]", who, count_before, batch_name, batch);
-    return 0;
-}
-static inline ReconRegress recon_regress_of(const sgv_regress_state& st, const float* weights) {
-    ReconRegress r;
-    r.mean = st.mean; r.m2 = st.m2; r.co = st.comoment; r.w = weights;
-    return r;
-}
-// sgv_project and its test hook: SGV_MAX_FUNCTIONALS (sgv_ew.h) weight rows at most
-static inline int project_args_ok(const char* who, const float* weights, int n_func, const float* out) {
-    if (!weights || !out) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (n_func < 1 || n_func > SGV_MAX_FUNCTIONALS) return fail(SGV_ERR_ARG, "%s: n_func = %d is outside [1, %d]", who, n_func, SGV_MAX_FUNCTIONALS);
-    if (((uintptr_t)weights & 15) || ((uintptr_t)out & 3)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (weights 16 bytes, out 4)", who);
-    return 0;
-}
-// sgv_temporal and its test hook: SGV_MAX_TEMPORAL (sgv_ew.h) weight rows at most; the rows of out are written 32 bytes at a time
-static inline int temporal_args_ok(const char* who, const float* weights, int n_func, const float* out) {
-    if (!weights || !out) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (n_func < 1 || n_func > SGV_MAX_TEMPORAL) return fail(SGV_ERR_ARG, "%s: n_func = %d is outside [1, %d]", who, n_func, SGV_MAX_TEMPORAL);
-    if (((uintptr_t)weights & 3) || ((uintptr_t)out & 15)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (weights 4 bytes, out 16)", who);
-    return 0;
-}
-// sgv_gram and its test hook: T <= SGV_MAX_GRAM_T (sgv_ew.h) row tiles fit the kernel's accumulators; the weights and the offset may be null
-static inline int gram_args_ok(const char* who, int T, const float* node_weights, const float* offset, const float* out) {
-    if (!out) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (T > SGV_MAX_GRAM_T) return fail(SGV_ERR_ARG, "%s: T = %d is beyond the limit of %d time steps", who, T, SGV_MAX_GRAM_T);
-    if ((((uintptr_t)node_weights | (uintptr_t)offset) & 15) || ((uintptr_t)out & 3)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (node_weights and offset 16 bytes, out 4)", who);
-    return 0;
-}
-// sgv_exceedance and its test hook: SGV_MAX_EXCEED_LEVELS (sgv_ew.h) levels at most, T within the kernel's packed 16-bit counters; the
-// rows of both outputs are written 32 bytes at a time
-static inline int exceedance_args_ok(const char* who, int T, const float* levels, int n_level, int side, const int32_t* stats, const float* excess) {
-    if (!levels) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (!stats && !excess) return fail(SGV_ERR_ARG, "%s: no output (stats and excess are both null)", who);
-    if (n_level < 1 || n_level > SGV_MAX_EXCEED_LEVELS) return fail(SGV_ERR_ARG, "%s: n_level = %d is outside [1, %d]", who, n_level, SGV_MAX_EXCEED_LEVELS);
-    if (side != SGV_SIDE_ABOVE && side != SGV_SIDE_BELOW) return fail(SGV_ERR_ARG, "%s: unknown side %d", who, side);
-    if (T > 65535) return fail(SGV_ERR_ARG, "%s: T = %d is beyond the limit of 65535 time steps", who, T);
-    if (((uintptr_t)levels & 3) || (((uintptr_t)stats | (uintptr_t)excess) & 15)) return fail(SGV_ERR_ARG, "%s: misaligned pointer (levels 4 bytes, stats and excess 16)", who);
-    return 0;
-}
-constexpr int SGV_SOBOL_MAX_PARAMS = 30;   // SB_MAX_D of recon_out.hip: a block of n_params + 2 members fits the kernel's member table
-static inline int sobol_state_ok(const char* who, const char* batch_name, const sgv_sobol_state* st, int n_params, long blocks_before, int batch) {
-    if (!st) return fail(SGV_ERR_ARG, "%s: null argument", who);
-    if (!st->mean || !st->m2) return fail(SGV_ERR_ARG, "%s: mean and m2 are required", who);
-    if (!st->first_sq && !st->total_sq) return fail(SGV_ERR_ARG, "%s: neither first_sq nor total_sq is given", who);
-    if (((uintptr_t)st->mean | (uintptr_t)st->m2 | (uintptr_t)st->first_sq | (uintptr_t)st->total_sq) & 15)
-        return fail(SGV_ERR_ARG, "%s: misaligned pointer (the state arrays 16 bytes)", who);
-    if (n_params < 1 || n_params > SGV_SOBOL_MAX_PARAMS) return fail(SGV_ERR_ARG, "%s: n_params = %d is outside [1, %d]", who, n_params, SGV_SOBOL_MAX_PARAMS);
-    if (batch < 1 || batch % (n_params + 2))
-        return fail(SGV_ERR_ARG, "%s: %s = %d is not a positive multiple of n_params + 2 = %d (whole blocks A, B, AB_1 .. AB_d)", who, batch_name, batch, n_params + 2);
-    if (blocks_before < 0 || blocks_before > (1L << 23) || 2 * (blocks_before + batch / (n_params + 2)) > (1L << 24))
-        return fail(SGV_ERR_ARG, "%s: blocks_before = %ld with %d blocks: 2 (blocks_before + blocks) is outside [0, 2^24]", who, blocks_before, batch / (n_params + 2));
-    return 0;
-}
-static inline ReconSobol recon_sobol_of(const sgv_sobol_state& st) {
-    ReconSobol r;
-    r.mean = st.mean; r.m2 = st.m2; r.first_sq = st.first_sq; r.total_sq = st.total_sq;
-    return r;
-}
-
 #pragma GCC visibility push(hidden)       // shared among the engine's files only: kept out of the library's dynamic symbols
 // The release policy of the gradient buckets, on backward_impl's stack for one backward pass (engine_optim.hip): the transport (none,
 // bucket callback, engine-issued RCCL), the wire format, where a bucket's AdamW runs (`early`: side stream, `dearly`: optimizer
@@ -405,6 +268,10 @@ bool wire_lp_active(sgv_engine* e);
 int lp_sync(sgv_engine* e);
 int set_grad_bf16(sgv_engine* e, int value);
 hipEvent_t next_event(sgv_engine* e);                                                       // engine_streams.hip: from the engine's pool (rewound by every backward)
+// engine.hip, for engine_surrogate.hip
+struct ReconTail;                                                                           // recon_tails.h
+int decode_begin(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, const char* who);   // checks, fresh copies, the caller's latents in place
+int decoder_fwd(sgv_engine* e, int B, int train, int mode_fix, const ReconTail* tail = nullptr);        // the decoder, then the loss tail or `tail`
 #pragma GCC visibility pop
 
 // ---- helpers that more than one translation unit calls, under the file that defines them: engine.hip ----

@@ -1,7 +1,8 @@
 // Test hooks (sgv_test_* of include/sgvae.h): caller-owned device buffers in, the launcher the engine calls, a sync, an error code out.
-// Only sgv_test_stream_overlap looks inside an engine (the others take fail / HIPCHK / CHK / align_up / sum_slabs from the private header);
+// Only sgv_test_stream_overlap looks inside an engine (the others take fail / HIPCHK / CHK / align_up / sum_slabs from the private header, the recon-tail hooks their tails from recon_tails.h);
 // sgv_test_fake_collective lives with the collective it replaces (engine_comm.hip).
 #include "engine_internal.h"
+#include "recon_tails.h"
 
 // a dense NT problem on caller-owned buffers: A [M][K], W [taps][N][K], C and addend [M][N]
 static GemmNT dense_nt(const void* A, const void* W, void* C, const float* bias, const float* scale, const void* addend, int M, int N,
@@ -245,9 +246,10 @@ int sgv_test_recon_loss(int dtype, int train, int loss_type, const void* y, long
     }
     return ew_hook_done(r, "sgv_test_recon_loss", stream);
 }
-// The four recon-tail hooks (recon_out.hip).  Front: the checks on what they all take, the model's group rule G = min(8, max(1, C / 4))
-// and the GNParams of the recon head's map.  Back: a workspace [statistics | extra_floats for the pass], the statistics of y, the pass
-// itself -- pass(p, extra, s) -> the launcher's code -- the sync and the free.
+// The recon-tail hooks (recon_out.hip), each three steps.  Front: the checks on what they all take, the model's group rule
+// G = min(8, max(1, C / 4)) and the GNParams of the recon head's map.  The tail's builder (recon_tails.h), the one the entry point calls.
+// Back: a workspace [statistics | extra_floats for the pass], the statistics of y, the pass itself -- pass(dtype, p, extra, s) -> the
+// launcher's code -- the sync and the free.
 static int recon_hook_front(const char* me, int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, int B, int T, int C, GNParams& p) {
     if (dtype != SGV_DTYPE_F32 && dtype != SGV_DTYPE_BF16) return fail(SGV_ERR_ARG, "%s: dtype must be SGV_DTYPE_F32 or SGV_DTYPE_BF16", me);
@@ -261,14 +263,14 @@ static int recon_hook_front(const char* me, int dtype, const void* y, long ldy, 
     return SGV_OK;
 }
 extern "C++" template <typename Pass>
-static int recon_hook_run(const char* me, int dtype, GNParams& p, size_t extra_floats, void* stream, Pass pass) {
+static int recon_hook_run(const char* me, int dtype, GNParams& p, size_t extra_floats, void* stream, const Pass& pass) {
     const size_t stat_floats = align_up(ew_gn_part_floats(p.B, p.T, p.C), 4);
     float* work = nullptr;
     HIPCHK(hipMalloc((void**)&work, sizeof(float) * (stat_floats + extra_floats)));
     p.part = work;
     hipStream_t s = (hipStream_t)stream;
     int r = ew_gn_stats(dtype, p, s);
-    if (!r) r = pass(p, work + stat_floats, s);
+    if (!r) r = pass(dtype, p, work + stat_floats, s);
     const int rc = ew_hook_done(r, me, stream);
     hipFree(work);
     return rc;
@@ -276,18 +278,16 @@ static int recon_hook_run(const char* me, int dtype, GNParams& p, size_t extra_f
 int sgv_test_recon_physical(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, int layout, float* out, int B, int T, int C, void* stream) {
     const char* me = "sgv_test_recon_physical";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    if (!out) return fail(SGV_ERR_ARG, "%s: null argument", me);
-    if (layout != SGV_LAYOUT_TN && layout != SGV_LAYOUT_NT) return fail(SGV_ERR_ARG, "%s: unknown layout %d", me, layout);
-    if ((uintptr_t)out & 15) return fail(SGV_ERR_ARG, "%s: out must be 16-byte aligned", me);
-    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) { return ew_recon_physical(dtype, q, scale, min, layout, out, s); });
+    CHK(tail_field(me, "out", scale, min, layout, out, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                            const float* scale, const float* min, const sgv_summary_out* out, const int32_t* probes_host,
                            int n_probes, int B, int T, int C, void* stream) {
     const char* me = "sgv_test_recon_summary";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
     CHK(summary_out_ok(me, "pointer", out));
     if (out->probes && (!probes_host || n_probes < 1)) return fail(SGV_ERR_ARG, "%s: probes asked for, but no probe nodes are given", me);
@@ -303,9 +303,8 @@ int sgv_test_recon_summary(int dtype, const void* y, long ldy, double* sums, con
             return fail(SGV_ERR_HIP, "%s: the probe nodes could not be copied to the device", me);
         }
     }
-    const int rc = recon_hook_run(me, dtype, p, ew_recon_summary_work_floats(B, T, C), stream, [&](const GNParams& q, float* frames, hipStream_t s) {
-        return ew_recon_summary(dtype, q, scale, min, recon_summary_of(*out, nodes, n_probes, frames), s);
-    });
+    int rc = tail_summary(me, "pointer", scale, min, out, nodes, n_probes, tail);       // the outputs were checked above: fills the tail
+    if (!rc) rc = recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
     hipFree(nodes);          // after the sync of recon_hook_run
     return rc;
 }
@@ -313,107 +312,81 @@ int sgv_test_recon_score(int dtype, const void* y, long ldy, double* sums, const
                          const float* scale, const float* min, const float* truth, const sgv_score_out* out, int B, int T, int C,
                          void* stream) {
     const char* me = "sgv_test_recon_score";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(score_out_ok(me, "truth", truth, out));
-    return recon_hook_run(me, dtype, p, ew_recon_summary_work_floats(B, T, C), stream, [&](const GNParams& q, float* extra, hipStream_t s) {
-        return ew_recon_score(dtype, q, scale, min, truth, recon_score_of(*out, extra), s);
-    });
+    CHK(tail_score(me, "truth", scale, min, truth, out, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_ensemble(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, long count_before, const sgv_ensemble_state* st, int B, int T,
                             int C, void* stream) {
     const char* me = "sgv_test_recon_ensemble";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(ensemble_state_ok(me, "B", st, count_before, B));
-    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
-        return ew_recon_ensemble(dtype, q, scale, min, count_before, recon_ensemble_of(*st), s);
-    });
+    CHK(tail_ensemble(me, "B", scale, min, count_before, st, B, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_sobol(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                          const float* scale, const float* min, int n_params, long blocks_before, const sgv_sobol_state* st, int B,
                          int T, int C, void* stream) {
     const char* me = "sgv_test_recon_sobol";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(sobol_state_ok(me, "B", st, n_params, blocks_before, B));
-    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
-        return ew_recon_sobol(dtype, q, scale, min, n_params, blocks_before, recon_sobol_of(*st), s);
-    });
+    CHK(tail_sobol(me, "B", scale, min, n_params, blocks_before, st, B, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_distribution(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                                 const float* scale, const float* min, long count_before, const sgv_distribution_state* st, int B,
                                 int T, int C, void* stream) {
     const char* me = "sgv_test_recon_distribution";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(distribution_state_ok(me, "B", st, count_before, B));
-    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
-        return ew_recon_distribution(dtype, q, scale, min, count_before, recon_distribution_of(*st), s);
-    });
+    CHK(tail_distribution(me, "B", scale, min, count_before, st, B, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_regress(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                            const float* scale, const float* min, int n_cov, const float* weights, long count_before,
                            const sgv_regress_state* st, int B, int T, int C, void* stream) {
     const char* me = "sgv_test_recon_regress";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(regress_state_ok(me, "B", st, n_cov, weights, count_before, B));
-    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
-        return ew_recon_regress(dtype, q, scale, min, n_cov, count_before, recon_regress_of(*st, weights), s);
-    });
+    CHK(tail_regress(me, "B", scale, min, n_cov, weights, count_before, st, B, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_project(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                            const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
                            void* stream) {
     const char* me = "sgv_test_recon_project";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(project_args_ok(me, weights, n_func, out));
-    return recon_hook_run(me, dtype, p, ew_recon_project_work_floats(B, T, C, n_func), stream, [&](const GNParams& q, float* work, hipStream_t s) {
-        ReconProject o;
-        o.weights = weights; o.n_func = n_func; o.out = out; o.work = work;
-        return ew_recon_project(dtype, q, scale, min, o, s);
-    });
+    CHK(tail_project(me, scale, min, weights, n_func, out, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_temporal(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                             const float* scale, const float* min, const float* weights, int n_func, float* out, int B, int T, int C,
                             void* stream) {
     const char* me = "sgv_test_recon_temporal";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(temporal_args_ok(me, weights, n_func, out));
-    return recon_hook_run(me, dtype, p, ew_recon_temporal_work_floats(T), stream, [&](const GNParams& q, float* work, hipStream_t s) {
-        ReconTemporal o;
-        o.weights = weights; o.n_func = n_func; o.out = out; o.work = work;
-        return ew_recon_temporal(dtype, q, scale, min, o, s);
-    });
+    CHK(tail_temporal(me, scale, min, weights, n_func, out, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_gram(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta, const float* scale,
                         const float* min, const float* node_weights, const float* offset, float* out, int B, int T, int C, void* stream) {
     const char* me = "sgv_test_recon_gram";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(gram_args_ok(me, T, node_weights, offset, out));
-    return recon_hook_run(me, dtype, p, ew_recon_gram_work_floats(B, T, C), stream, [&](const GNParams& q, float* work, hipStream_t s) {
-        ReconGram o;
-        o.node_weights = node_weights; o.offset = offset; o.out = out; o.work = work;
-        return ew_recon_gram(dtype, q, scale, min, o, s);
-    });
+    CHK(tail_gram(me, scale, min, T, node_weights, offset, out, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_recon_exceedance(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                               const float* scale, const float* min, const float* levels, int n_level, int side, int32_t* stats,
                               float* excess, int B, int T, int C, void* stream) {
     const char* me = "sgv_test_recon_exceedance";
-    GNParams p;
+    GNParams p; ReconTail tail;
     CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
-    CHK(exceedance_args_ok(me, T, levels, n_level, side, stats, excess));
-    return recon_hook_run(me, dtype, p, 0, stream, [&](const GNParams& q, float*, hipStream_t s) {
-        ReconExceed o;
-        o.levels = levels; o.n_level = n_level; o.above = side == SGV_SIDE_ABOVE; o.stats = stats; o.excess = excess;
-        return ew_recon_exceedance(dtype, q, scale, min, o, s);
-    });
+    CHK(tail_exceedance(me, scale, min, T, levels, n_level, side, stats, excess, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,

@@ -263,6 +263,38 @@ def is_tensor_of(v, dtype, shape=None, device="cuda"):
             and (shape is None or tuple(v.shape) == tuple(shape)))
 
 
+def _out_tensor(out, shape, dtype, what="out must be a contiguous float32 CUDA tensor", new=None):
+    """an output of a surrogate pass: a new CUDA tensor when `out` is `new`, else `out`, checked (ValueError: `what` of shape ...)"""
+    import torch
+    if out is new:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    if not is_tensor_of(out, dtype, shape):
+        raise ValueError(f"{what} of shape {shape}")
+    return out
+
+
+def _member_range(count_before, B) -> int:
+    """count_before as an int, the members count_before .. count_before + B - 1 of a study checked against ENSEMBLE_MAX_COUNT"""
+    cb = int(count_before)
+    if cb < 0 or cb + B > ENSEMBLE_MAX_COUNT:
+        raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
+    return cb
+
+
+def _weight_rows(w, cols, limit, name="weights", rows="R") -> int:
+    """the number of rows of w, a contiguous fp32 CUDA tensor [rows, cols] with 1 <= rows <= limit"""
+    import torch
+    R = int(w.shape[0]) if torch.is_tensor(w) and w.dim() == 2 else 0
+    if R < 1 or R > limit or not is_tensor_of(w, torch.float32, (R, cols)):
+        raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of shape [{rows}, {cols}] with 1 <= {rows} <= {limit}")
+    return R
+
+
+def _ptr(a):
+    """the device pointer of a tensor as a ctypes argument, None (NULL) for None"""
+    return C.c_void_p(a.data_ptr()) if a is not None else None
+
+
 def _check(lib, rc: int, what: str):
     if rc != 0:
         raise SgvError(f"{what} failed ({rc}): {lib.sgv_last_error().decode()}")
@@ -499,13 +531,9 @@ class Engine:
             raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, not {layout!r}")
         N, T = self.cfg.num_node, self.cfg.num_time
 
-        def tail(B, out=out):
-            shape = (B, T, N) if layout == "TN" else (B, N, T)
-            if out is None:
-                out = t.empty(shape, dtype=t.float32, device="cuda")
-            elif not is_tensor_of(out, t.float32, shape):
-                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {shape}")
-            return (LAYOUTS[layout], C.c_void_p(out.data_ptr())), out
+        def tail(B):
+            res = _out_tensor(out, (B, T, N) if layout == "TN" else (B, N, T), t.float32)
+            return (LAYOUTS[layout], _ptr(res)), res
         return self._surrogate("sgv_generate", z, xs, scale, min, fix, tail)
 
     def _latents(self, z, xs):
@@ -525,7 +553,7 @@ class Engine:
                 raise ValueError(f"{name} must be a contiguous float32 CUDA tensor of {N} elements")
 
     def _surrogate(self, entry, z, xs, scale, min, fix, tail):
-        """the call generate, summarize, score, ensemble and sobol share: the checks on z, xs, scale and min, then tail(B) -> (the entry
+        """the call the surrogate passes share: the checks on z, xs, scale and min, then tail(B) -> (the entry
         point's trailing arguments, what to return), which checks whatever depends on the batch, then the C call"""
         B, z, xs_t = self._latents(z, xs)
         self._scaler(scale, min)
@@ -540,12 +568,7 @@ class Engine:
         t = self.torch
         res = {}
         for name, (shape, dt) in shapes.items():
-            v = None if out is None else out.get(name)
-            if v is None:
-                v = t.empty(shape, dtype=dt, device="cuda")
-            elif not is_tensor_of(v, dt, shape):
-                raise ValueError(f"out[{name!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
-            res[name] = v
+            res[name] = _out_tensor(None if out is None else out.get(name), shape, dt, f"out[{name!r}] must be a contiguous {dt} CUDA tensor")
         return res
 
     def _state(self, state, spec, what, needs):
@@ -652,10 +675,7 @@ class Engine:
                 raise ValueError(f"state: group {g!r} needs all of {names}, got only {have}")
 
         def tail(B):
-            cb = int(count_before)
-            if cb < 0 or cb + B > ENSEMBLE_MAX_COUNT:
-                raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
-            return (cb, C.byref(EnsembleState(**{k: v.data_ptr() for k, v in state.items() if v is not None}))), state
+            return (_member_range(count_before, B), C.byref(EnsembleState(**{k: v.data_ptr() for k, v in state.items() if v is not None}))), state
         return self._surrogate("sgv_ensemble", z, xs, scale, min, fix, tail)
 
     def sobol(self, z, xs, scale, min, state, n_params, blocks_before, fix=True):
@@ -714,9 +734,7 @@ class Engine:
             raise ValueError(f"state needs all of {DISTRIBUTION_FIELDS}, got only {have}")
 
         def tail(B):
-            cb = int(count_before)
-            if cb < 0 or cb + B > ENSEMBLE_MAX_COUNT:
-                raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
+            cb = _member_range(count_before, B)
             st = DistributionState(lo=state["lo"].data_ptr(), hi=state["hi"].data_ptr(), counts=state["counts"].data_ptr(), bins=bins)
             return (cb, C.byref(st)), state
         return self._surrogate("sgv_distribution", z, xs, scale, min, fix, tail)
@@ -748,8 +766,7 @@ class Engine:
             cb = int(count_before)
             if not is_tensor_of(weights, t.float32, (B, K)):
                 raise ValueError(f"weights must be a contiguous float32 CUDA tensor of shape {(B, K)}")
-            if cb < 0 or cb + B > ENSEMBLE_MAX_COUNT:
-                raise ValueError(f"count_before = {cb} with a batch of {B} is outside [0, {ENSEMBLE_MAX_COUNT}]")
+            _member_range(cb, B)
             st = RegressState(mean=state["mean"].data_ptr(), m2=state["m2"].data_ptr(), comoment=state["comoment"].data_ptr())
             return (K, C.c_void_p(weights.data_ptr()), cb, C.byref(st)), state
         return self._surrogate("sgv_regress", z, xs, scale, min, fix, tail)
@@ -764,16 +781,11 @@ class Engine:
         Nothing synchronises; afterwards xhat() raises, as after generate()."""
         t = self.torch
         N, T = self.cfg.num_node, self.cfg.num_time
-        R = int(weights.shape[0]) if t.is_tensor(weights) and weights.dim() == 2 else 0
-        if R < 1 or R > MAX_FUNCTIONALS or not is_tensor_of(weights, t.float32, (R, N)):
-            raise ValueError(f"weights must be a contiguous float32 CUDA tensor of shape [R, {N}] with 1 <= R <= {MAX_FUNCTIONALS}")
+        R = _weight_rows(weights, N, MAX_FUNCTIONALS)
 
-        def tail(B, out=out):
-            if out is None:
-                out = t.empty((B, T, R), dtype=t.float32, device="cuda")
-            elif not is_tensor_of(out, t.float32, (B, T, R)):
-                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {(B, T, R)}")
-            return (C.c_void_p(weights.data_ptr()), R, C.c_void_p(out.data_ptr())), out
+        def tail(B):
+            res = _out_tensor(out, (B, T, R), t.float32)
+            return (_ptr(weights), R, _ptr(res)), res
         return self._surrogate("sgv_project", z, xs, scale, min, fix, tail)
 
     def temporal(self, z, xs, scale, min, weights, fix=True, out=None):
@@ -786,16 +798,11 @@ class Engine:
         afterwards xhat() raises, as after generate()."""
         t = self.torch
         N, T = self.cfg.num_node, self.cfg.num_time
-        R = int(weights.shape[0]) if t.is_tensor(weights) and weights.dim() == 2 else 0
-        if R < 1 or R > MAX_TEMPORAL or not is_tensor_of(weights, t.float32, (R, T)):
-            raise ValueError(f"weights must be a contiguous float32 CUDA tensor of shape [R, {T}] with 1 <= R <= {MAX_TEMPORAL}")
+        R = _weight_rows(weights, T, MAX_TEMPORAL)
 
-        def tail(B, out=out):
-            if out is None:
-                out = t.empty((B, R, N), dtype=t.float32, device="cuda")
-            elif not is_tensor_of(out, t.float32, (B, R, N)):
-                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {(B, R, N)}")
-            return (C.c_void_p(weights.data_ptr()), R, C.c_void_p(out.data_ptr())), out
+        def tail(B):
+            res = _out_tensor(out, (B, R, N), t.float32)
+            return (_ptr(weights), R, _ptr(res)), res
         return self._surrogate("sgv_temporal", z, xs, scale, min, fix, tail)
 
     def gram(self, z, xs, scale, min, node_weights=None, offset=None, fix=True, out=None):
@@ -814,13 +821,9 @@ class Engine:
             if a is not None and not is_tensor_of(a, t.float32, (N,)):
                 raise ValueError(f"{name} must be None or a contiguous float32 CUDA tensor of shape [{N}]")
 
-        def tail(B, out=out):
-            if out is None:
-                out = t.empty((B, T, T), dtype=t.float32, device="cuda")
-            elif not is_tensor_of(out, t.float32, (B, T, T)):
-                raise ValueError(f"out must be a contiguous float32 CUDA tensor of shape {(B, T, T)}")
-            ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-            return (ptr(node_weights), ptr(offset), C.c_void_p(out.data_ptr())), out
+        def tail(B):
+            res = _out_tensor(out, (B, T, T), t.float32)
+            return (_ptr(node_weights), _ptr(offset), _ptr(res)), res
         return self._surrogate("sgv_gram", z, xs, scale, min, fix, tail)
 
     def exceedance(self, z, xs, scale, min, levels, side="above", fix=True, stats=True, excess=True):
@@ -841,23 +844,16 @@ class Engine:
             raise ValueError(f"num_time = {T} is beyond the limit of {EXCEEDANCE_MAX_T} time steps of the exceedance pass")
         if side not in EXCEEDANCE_SIDES:
             raise ValueError(f"side must be one of {sorted(EXCEEDANCE_SIDES)}, not {side!r}")
-        L = int(levels.shape[0]) if t.is_tensor(levels) and levels.dim() == 2 else 0
-        if L < 1 or L > MAX_LEVELS or not is_tensor_of(levels, t.float32, (L, N)):
-            raise ValueError(f"levels must be a contiguous float32 CUDA tensor of shape [L, {N}] with 1 <= L <= {MAX_LEVELS}")
+        L = _weight_rows(levels, N, MAX_LEVELS, "levels", "L")
         if stats is False and excess is False:
             raise ValueError("nothing to compute: stats and excess are both False")
 
         def tail(B):
             res = {}
             for name, v, dt, shape in (("stats", stats, t.int32, (B, 5, L, N)), ("excess", excess, t.float32, (B, L, N))):
-                if v is True:
-                    res[name] = t.empty(shape, dtype=dt, device="cuda")
-                elif v is not False:
-                    if not is_tensor_of(v, dt, shape):
-                        raise ValueError(f"{name} must be True, False or a contiguous {dt} CUDA tensor of shape {shape}")
-                    res[name] = v
-            ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-            return (C.c_void_p(levels.data_ptr()), L, EXCEEDANCE_SIDES[side], ptr(res.get("stats")), ptr(res.get("excess"))), res
+                if v is not False:
+                    res[name] = _out_tensor(v, shape, dt, f"{name} must be True, False or a contiguous {dt} CUDA tensor", new=True)
+            return (_ptr(levels), L, EXCEEDANCE_SIDES[side], _ptr(res.get("stats")), _ptr(res.get("excess"))), res
         return self._surrogate("sgv_exceedance", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:

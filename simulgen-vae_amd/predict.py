@@ -119,21 +119,25 @@ class _Result:
             setattr(self, k, kw[k])
 
 
-class _RunningResult(_Result):
-    """a result whose device tensors (those of its STATE that are not None) ARE the running state of a study over `count` members"""
-    PER_COUNT = 1          # values that enter the moments per unit of count
+class _StreamResult(_Result):
+    """a result that keeps the engine stream (a torch stream): what is derived from its device tensors is computed there"""
 
     def __init__(self, stream=None, **kw):
         super().__init__(**kw)
-        self._stream = stream          # the engine stream (a torch stream): what is derived from the state is computed there
-
-    def state(self):
-        """the tensors of the running state by their names in the engine's entry point (Engine.ensemble, Engine.sobol)"""
-        return {k: getattr(self, k) for k in self.STATE if getattr(self, k) is not None}
+        self._stream = stream
 
     def _on_stream(self, fn):
         with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
             return fn()
+
+
+class _RunningResult(_StreamResult):
+    """a result whose device tensors (those of its STATE that are not None) ARE the running state of a study over `count` members"""
+    PER_COUNT = 1          # values that enter the moments per unit of count
+
+    def state(self):
+        """the tensors of the running state by their names in the engine's entry point (Engine.ensemble, Engine.sobol)"""
+        return {k: getattr(self, k) for k in self.STATE if getattr(self, k) is not None}
 
     def _dof(self, what, ddof):
         n = self.PER_COUNT * self.count
@@ -277,19 +281,11 @@ def region_weights(labels, num_regions=None, node_weights=None, reduce="mean"):
     return W.astype(np.float32)
 
 
-class ProjectResult(_Result):
+class ProjectResult(_StreamResult):
     """Surrogate.project's result for P conditions: values [P, T, R] fp32, a device tensor that is the caller's --
     values[p, t, r] = sum over n of weights[r, n] * field[p, t, n], the time histories of R quantities of interest.  What is derived
     from it is computed on the engine stream."""
     FIELDS = ("values",)
-
-    def __init__(self, stream=None, **kw):
-        super().__init__(**kw)
-        self._stream = stream
-
-    def _on_stream(self, fn):
-        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
-            return fn()
 
     def peak(self):
         """(the maximum over t [P, R] fp32, its time step [P, R] int64); the smallest t on a tie"""
@@ -427,19 +423,11 @@ def window_rows(T, edges):
     return rows.astype(np.float32)
 
 
-class TemporalResult(_Result):
+class TemporalResult(_StreamResult):
     """Surrogate.temporal's result for P conditions: values [P, R, N] fp32, a device tensor that is the caller's --
     values[p, r, n] = sum over t of weights[r, t] * field[p, t, n], R fields of quantities over time.  What is derived from it is
     computed on the engine stream."""
     FIELDS = ("values",)
-
-    def __init__(self, stream=None, **kw):
-        super().__init__(**kw)
-        self._stream = stream
-
-    def _on_stream(self, fn):
-        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
-            return fn()
 
     def _pairs(self):
         v = self.values
@@ -527,15 +515,14 @@ def _host64(v):
     return (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float64)
 
 
-class GramResult(_Result):
+class GramResult(_StreamResult):
     """Surrogate.gram's result for P conditions: values [P, T, T] fp32, a device tensor that is the caller's --
     values[p, t, t'] = sum over n of w[n] (field[p, t, n] - m[n]) (field[p, t', n] - m[n]), bitwise symmetric -- and num_node = N.
     What is derived from it is computed on the host in float64 (numpy; the first call waits for the device and keeps the copy)."""
     FIELDS = ("values", "num_node")
 
-    def __init__(self, stream=None, **kw):
+    def __init__(self, **kw):
         super().__init__(**kw)
-        self._stream = stream
         self._g64 = None
 
     def host(self):
@@ -659,7 +646,7 @@ def exceedance_levels(levels, N):
     return np.array(np.broadcast_to(v, (L, N)), order="C")          # a copy: the broadcast view is read-only
 
 
-class ExceedanceResult(_Result):
+class ExceedanceResult(_StreamResult):
     """Surrogate.exceedance's result for P conditions against L levels: the level-crossing statistics of every node's T time steps,
     device tensors that are the caller's.  A step exceeds its level when the field is strictly above it (side "above") or below it
     ("below").  stats int32 [P, 5, L, N] with the views count (the steps that exceed), first and last (their smallest and largest
@@ -668,14 +655,6 @@ class ExceedanceResult(_Result):
     exactly 0 where nothing exceeds; levels fp32 [L, N] as they were used.  An output that was not asked for is None and its
     methods raise ValueError.  What is derived is plain torch on the small result, computed on the engine stream."""
     FIELDS = ("stats", "excess", "levels", "side", "T")
-
-    def __init__(self, stream=None, **kw):
-        super().__init__(**kw)
-        self._stream = stream
-
-    def _on_stream(self, fn):
-        with _engine_stream(self._stream) if self._stream is not None else contextlib.nullcontext():
-            return fn()
 
     def _plane(self, name):
         if self.stats is None:
@@ -1281,6 +1260,33 @@ class Surrogate:
         for lo, hi in self._batches(P, self.batch):
             yield (lo, hi) + self._latents(self._batch(conditions, lo, hi), remap)
 
+    def _condition_batches(self, conditions, P, remap):
+        """_latent_batches for a pass that draws its noise per call (project, temporal, gram, exceedance): every batch draws from the
+        streams of the call's first draw, condition p from their row p (Engine.set_draw_row) -- the noise one batch over all
+        conditions would get, so the batch size does not show in the bits and the draw position ends where one call leaves it.
+        The training state is read when the first batch is asked for.  The row is back at 0 once the generator is closed: callers wrap it in contextlib.closing, so that an exception in their
+        loop body resets it at once."""
+        eng = self.eng
+        at = eng.train_state()
+        try:
+            for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
+                eng.set_train_state(at["step"], at["seed"], at["draw"])
+                eng.set_draw_row(lo)
+                yield lo, hi, lat, xs
+        finally:
+            eng.set_draw_row(0)
+
+    def _to_device(self, v, align16):
+        """a validated host array or tensor on the device (None stays None), uploaded on the current stream.  align16: cloned when it
+        is a view at an odd offset, for a kernel that loads 16 bytes at a time"""
+        if v is None:
+            return None
+        t = self.torch
+        if not t.is_tensor(v):
+            v = t.from_numpy(v)
+        v = v.to(device="cuda", non_blocking=True)
+        return v.clone() if align16 and v.data_ptr() % 16 else v
+
     def predict(self, conditions, out=None, layout="TN", mode="fix"):
         """conditions [P, F] (host array or CUDA tensor, preprocessed as the conditioner's training set holds them) -> fp32 device
         tensor [P, T, N] (layout "TN") or [P, N, T] ("NT") in physical units.  mode "fix": the mean (the reference's "fix": the
@@ -1349,24 +1355,11 @@ class Surrogate:
         t = self.torch
         conditions, P, _, remap = self._args(conditions, "TN", mode)
         w = functional_weights(weights, self.N)
-        if not t.is_tensor(w):
-            w = t.from_numpy(w)
         values = t.empty((P, self.T, w.shape[0]), dtype=t.float32, device="cuda")          # the result: the caller's stream owns it
-        eng = self.eng
-        at = eng.train_state()
-        with _engine_stream(self._stream):
-            w = w.to(device="cuda", non_blocking=True)
-            if w.data_ptr() % 16:
-                w = w.clone()          # a view at an odd offset: the kernel loads 16 bytes at a time
-            try:
-                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
-                    # every batch draws from the streams of the call's first draw, condition p from their row p: the noise one batch
-                    # over all conditions would get, so the draw position ends where one call leaves it
-                    eng.set_train_state(at["step"], at["seed"], at["draw"])
-                    eng.set_draw_row(lo)
-                    eng.project(lat, xs, self.data_scale, self.data_min, w, fix=mode == "fix", out=values[lo:hi])
-            finally:
-                eng.set_draw_row(0)
+        with _engine_stream(self._stream), contextlib.closing(self._condition_batches(conditions, P, remap)) as batches:
+            w = self._to_device(w, align16=True)
+            for lo, hi, lat, xs in batches:
+                self.eng.project(lat, xs, self.data_scale, self.data_min, w, fix=mode == "fix", out=values[lo:hi])
         return ProjectResult(stream=self._stream, values=values)
 
     def temporal(self, conditions, weights, mode="fix"):
@@ -1375,29 +1368,19 @@ class Surrogate:
         TemporalResult whose values [P, R, N] are sum_t weights[r, t] * field[p, t, n] -- spectral amplitudes, window means, time
         integrals, filtered values, amplitudes on temporal modes.  The recon head's last pass multiplies the values predict() would
         store (bit for bit the same) into the weight rows on the matrix cores, one fp32 fused multiply-add chain per value over t
-        ascending: a value depends on its condition, weight row and node alone, and the decoder's noise of condition p is row p of
-        the streams one call over all conditions would draw from (Engine.set_draw_row), so the batch size does not show in the
-        bits in either mode, and 4 R N bytes per condition leave the decoder instead of 4 T N.  The weights are uploaded once per
+        ascending: a value depends on its condition, weight row and node alone, and the decoder's noise is placed as in
+        project() (_condition_batches), so the batch size does not show in the bits in either mode, and 4 R N bytes per condition
+        leave the decoder instead of 4 T N.  The weights are uploaded once per
         call and every batch is written straight into its rows of `values`.  Batching, streams, the single input-range decision and
         `mode` are project()'s: no host wait between batches."""
         t = self.torch
         conditions, P, _, remap = self._args(conditions, "TN", mode)
         w = temporal_weights(weights, self.T)
-        if not t.is_tensor(w):
-            w = t.from_numpy(w)
         values = t.empty((P, w.shape[0], self.N), dtype=t.float32, device="cuda")          # the result: the caller's stream owns it
-        eng = self.eng
-        at = eng.train_state()
-        with _engine_stream(self._stream):
-            w = w.to(device="cuda", non_blocking=True)
-            try:
-                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
-                    # as in project(): every batch draws from the streams of the call's first draw, condition p from their row p
-                    eng.set_train_state(at["step"], at["seed"], at["draw"])
-                    eng.set_draw_row(lo)
-                    eng.temporal(lat, xs, self.data_scale, self.data_min, w, fix=mode == "fix", out=values[lo:hi])
-            finally:
-                eng.set_draw_row(0)
+        with _engine_stream(self._stream), contextlib.closing(self._condition_batches(conditions, P, remap)) as batches:
+            w = self._to_device(w, align16=False)
+            for lo, hi, lat, xs in batches:
+                self.eng.temporal(lat, xs, self.data_scale, self.data_min, w, fix=mode == "fix", out=values[lo:hi])
         return TemporalResult(stream=self._stream, values=values)
 
     def gram(self, conditions, node_weights=None, offset=None, mode="fix"):
@@ -1407,9 +1390,9 @@ class Surrogate:
         MAC between time steps, and, summed over the conditions, X X^T of the study, whose eigenvectors are its POD temporal modes
         (GramResult.modes).  num_time <= MAX_GRAM_T.  The recon head's last pass multiplies the values predict() would store (bit
         for bit the same) with themselves on the matrix cores in fp32, in a fixed order inside fixed shares of the mesh, and adds
-        the shares in float64: a matrix depends on its condition alone, and the decoder's noise of condition p is row p of the
-        streams one call over all conditions would draw from (Engine.set_draw_row), so the batch size does not show in the bits
-        in either mode, and 4 T T bytes per condition leave the decoder instead of 4 T N.  Batching, streams, the single
+        the shares in float64: a matrix depends on its condition alone, and the decoder's noise is placed as in project()
+        (_condition_batches), so the batch size does not show in the bits in either mode, and 4 T T bytes per condition leave the
+        decoder instead of 4 T N.  Batching, streams, the single
         input-range decision and `mode` are project()'s: no host wait between batches."""
         t = self.torch
         conditions, P, _, remap = self._args(conditions, "TN", mode)
@@ -1417,29 +1400,11 @@ class Surrogate:
             raise ValueError(f"gram: num_time = {self.T} is beyond the limit of {MAX_GRAM_T} time steps")
         w, m = gram_weights(node_weights, self.N), gram_offset(offset, self.N)
         values = t.empty((P, self.T, self.T), dtype=t.float32, device="cuda")          # the result: the caller's stream owns it
-        eng = self.eng
-        at = eng.train_state()
-        with _engine_stream(self._stream):
-            w, m = (self._gram_device(v) for v in (w, m))
-            try:
-                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
-                    # as in project(): every batch draws from the streams of the call's first draw, condition p from their row p
-                    eng.set_train_state(at["step"], at["seed"], at["draw"])
-                    eng.set_draw_row(lo)
-                    eng.gram(lat, xs, self.data_scale, self.data_min, node_weights=w, offset=m, fix=mode == "fix", out=values[lo:hi])
-            finally:
-                eng.set_draw_row(0)
+        with _engine_stream(self._stream), contextlib.closing(self._condition_batches(conditions, P, remap)) as batches:
+            w, m = (self._to_device(v, align16=True) for v in (w, m))
+            for lo, hi, lat, xs in batches:
+                self.eng.gram(lat, xs, self.data_scale, self.data_min, node_weights=w, offset=m, fix=mode == "fix", out=values[lo:hi])
         return GramResult(stream=self._stream, values=values, num_node=self.N)
-
-    def _gram_device(self, v):
-        """a validated weight or offset vector on the device, 16-byte aligned (the kernel loads 16 bytes at a time)"""
-        if v is None:
-            return None
-        t = self.torch
-        if not t.is_tensor(v):
-            v = t.from_numpy(v)
-        v = v.to(device="cuda", non_blocking=True)
-        return v.clone() if v.data_ptr() % 16 else v
 
     def pod(self, conditions, rank=None, energy=None, node_weights=None, offset=None, mode="fix"):
         """A rank-R compression of predict(conditions) by the method of snapshots, the fields never stored: gram() gives the Gram
@@ -1461,7 +1426,7 @@ class Surrogate:
         with _engine_stream(self._stream):
             coeff = parts[0] if len(parts) == 1 else t.cat(parts, dim=1)
             if m is not None:
-                m = self._gram_device(m)
+                m = self._to_device(m, align16=True)
                 S = t.from_numpy(rows.astype(np.float64).sum(axis=1).astype(np.float32)).to(device="cuda")
                 coeff -= S.view(1, -1, 1) * m.view(1, 1, -1)
         return PodResult(rows=rows, eigenvalues=lam, fraction=frac, coefficients=coeff, offset=m)
@@ -1472,9 +1437,9 @@ class Surrogate:
         want: "steps" for the integer statistics (count, first, last, longest, runs), "excess" for the accumulated excess -> an
         ExceedanceResult.  The recon head's last pass compares the values predict() would store (bit for bit the same) with the
         levels, strictly, one thread per node going through the time steps in order: the result is integer apart from the excess,
-        which is one fp32 sum over t ascending, so it depends on its condition, level and node alone, and the decoder's noise of
-        condition p is row p of the streams one call over all conditions would draw from (Engine.set_draw_row): the batch size does
-        not show in the bits in either mode, and 24 L N bytes per condition leave the decoder instead of 4 T N.  The levels are
+        which is one fp32 sum over t ascending, so it depends on its condition, level and node alone, and the decoder's noise is
+        placed as in project() (_condition_batches): the batch size does not show in the bits in either mode, and 24 L N bytes per
+        condition leave the decoder instead of 4 T N.  The levels are
         uploaded once per call and every batch is written straight into its rows of the result.  Batching, streams, the single
         input-range decision and `mode` are temporal()'s: no host wait between batches."""
         t = self.torch
@@ -1486,24 +1451,14 @@ class Surrogate:
             raise ValueError(f"num_time = {self.T} is beyond the limit of {EXCEEDANCE_MAX_T} time steps of the exceedance pass")
         conditions, P, _, remap = self._args(conditions, "TN", mode)
         lv = exceedance_levels(levels, self.N)
-        if not t.is_tensor(lv):
-            lv = t.from_numpy(lv)
         L = lv.shape[0]
         stats = t.empty((P, 5, L, self.N), dtype=t.int32, device="cuda") if "steps" in want else None          # the result: the caller's stream owns it
         excess = t.empty((P, L, self.N), dtype=t.float32, device="cuda") if "excess" in want else None
-        eng = self.eng
-        at = eng.train_state()
-        with _engine_stream(self._stream):
-            lv = lv.to(device="cuda", non_blocking=True)
-            try:
-                for lo, hi, lat, xs in self._latent_batches(conditions, P, remap):
-                    # as in temporal(): every batch draws from the streams of the call's first draw, condition p from their row p
-                    eng.set_train_state(at["step"], at["seed"], at["draw"])
-                    eng.set_draw_row(lo)
-                    eng.exceedance(lat, xs, self.data_scale, self.data_min, lv, side=side, fix=mode == "fix",
-                                   stats=False if stats is None else stats[lo:hi], excess=False if excess is None else excess[lo:hi])
-            finally:
-                eng.set_draw_row(0)
+        with _engine_stream(self._stream), contextlib.closing(self._condition_batches(conditions, P, remap)) as batches:
+            lv = self._to_device(lv, align16=False)
+            for lo, hi, lat, xs in batches:
+                self.eng.exceedance(lat, xs, self.data_scale, self.data_min, lv, side=side, fix=mode == "fix",
+                                    stats=False if stats is None else stats[lo:hi], excess=False if excess is None else excess[lo:hi])
         return ExceedanceResult(stream=self._stream, stats=stats, excess=excess, levels=lv, side=side, T=self.T)
 
     def score(self, conditions, truth, mode="fix"):

@@ -151,7 +151,7 @@ int sgv_seed(sgv_engine* e, uint64_t seed);
  * exactly the noise one rank draws for B samples.  Default (0, 1). */
 int sgv_set_shard(sgv_engine* e, int rank, int world);
 /* Noise of a study that is cut into batches: with first_row = r, sample b of the following decoder passes that draw their noise
- * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal, sgv_gram, sgv_exceedance) takes row r + b of the streams the call draws from instead of
+ * per call (sgv_generate, sgv_summarize, sgv_score, sgv_project, sgv_temporal, sgv_gram, sgv_exceedance, sgv_cycles) takes row r + b of the streams the call draws from instead of
  * row b.  sgv_forward and sgv_decode are not affected.  A caller that puts the draw position back in front of every batch (sgv_set_train_state) and sets
  * first_row to the index of the batch's first sample gives sample p of the study the noise one call over all samples would give
  * it, whatever the batch size; Surrogate.project does.  The passes that count members themselves (sgv_ensemble, sgv_sobol,
@@ -395,6 +395,45 @@ int sgv_gram(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, 
 int sgv_exceedance(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
                    const float* min_dev, const float* levels_dev, int n_level, int side, int32_t* stats_dev_or_NULL,
                    float* excess_dev_or_NULL);
+/* The outputs of sgv_cycles, device pointers, 16-byte aligned, in two groups; a group is given whole or left NULL, at least one is
+ * required.  x[t] is the value sgv_generate would store at (b, t, n) (SGV_LAYOUT_TN), h = gate[n] >= 0, m = exponent, fl() one fp32
+ * rounding; every difference is formed from the stored value and rounded on its own, every product of the power and every
+ * accumulation likewise (nothing is contracted into an fma); all comparisons are strict.
+ * The turns -- ASTM E1049 simple-range counting behind a hysteresis gate, a machine of three states per node, dir in {0, +1, -1},
+ * from dir = 0, hi = lo = x[0]; for t = 1 .. T - 1, x = x[t]:
+ *   dir = 0:  fl(x - lo) > h: a valley is confirmed: last = lo, cand = x, dir = +1, reversals += 1; else fl(hi - x) > h: a peak:
+ *             last = hi, cand = x, dir = -1, reversals += 1; else hi = max(hi, x), lo = min(lo, x).  The first turning point
+ *             carries no range.
+ *   dir = +1: x > cand: cand = x; else fl(cand - x) > h: a peak is confirmed: R = fl(cand - last) is counted, last = cand, cand = x,
+ *             dir = -1, reversals += 1.
+ *   dir = -1: x < cand: cand = x; else fl(x - cand) > h: a valley: R = fl(last - cand) is counted, last = cand, cand = x, dir = +1,
+ *             reversals += 1.
+ *   counted:  range_sum = fl(range_sum + R); range_max = R if R > range_max; damage = fl(damage + P) with P = R, then m - 1 times
+ *             P = fl(P * R); all three from +0.0.
+ *   open, the unfinished excursion: fl(hi - lo) at dir = 0, fl(cand - last) at +1, fl(last - cand) at -1.
+ *   reversals int32 [B][N];  ranges fp32 [B][4][N] = range_sum, range_max, damage, open.  The counted ranges (half cycles) number
+ *   max(reversals - 1, 0).  With h = 0 every strict local extremum of the history with its plateaus collapsed is a turning point; a
+ *   constant history gives 0 and +0.0 throughout; a gate above the node's peak-to-peak gives reversals 0 and open = fl(max - min).
+ * The rates -- for t = 1 .. T - 1, r[t] = fl(x[t] - x[t-1]):
+ *   rate_when int32 [B][2][N] = rise_when, fall_when;  rates fp32 [B][3][N] = rise, fall, path: rise = max r[t], fall = min r[t],
+ *   the steps those of each, the smallest on a tie (strict > / < updates starting from r[1]); path = s after s = +0.0;
+ *   s = fl(s + |r[t]|), t ascending.  T = 1: rise = fall = path = +0.0 and both steps -1. */
+typedef struct {
+    int32_t* reversals;
+    float* ranges;
+    int32_t* rate_when;
+    float* rates;
+} sgv_cycles_out;
+/* Decoder.forward(z, xs, mode) as sgv_summarize (same arguments, same checks), followed by the cycles pass: the load cycles and
+ * the rates of every node's time history (sgv_cycles_out), the field itself never stored.  gate_dev fp32 [N] on the device, 4-byte
+ * aligned, >= 0 (not checked: a negative or NaN gate is the caller's); exponent an integer in [1, 8].  num_time <= 65535.  Every
+ * output depends on its sample and its node alone, so any cut of the conditions into batches and either group alone give the same
+ * bits; the exponent shows in damage alone.  No workspace, no atomics.  SGV_ERR_ARG before anything is enqueued: e, z_dev,
+ * scale_dev, min_dev, gate_dev or out NULL, no group, half a group, an exponent outside [1, 8], num_time > 65535, a misaligned
+ * pointer, the checks of sgv_decode.  Synchronises nothing.  Afterwards there is no forward pass to read from, as after
+ * sgv_generate. */
+int sgv_cycles(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+               const float* min_dev, const float* gate_dev, int exponent, const sgv_cycles_out* out);
 /* Encoder.forward only (utils.py:492): mu, log_var [B,latent], xs [n_levels-1][B,hier] to host. [sync] */
 int sgv_encode(sgv_engine* e, float* mu_host, float* logvar_host, float* xs_host);
 /* Reconstruction of the last forward, reference layout [B, num_node, num_time] fp32 on device. */
@@ -725,6 +764,12 @@ int sgv_test_recon_gram(int dtype, const void* y, long ldy, double* sums, const 
 int sgv_test_recon_exceedance(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta,
                               const float* scale, const float* min, const float* levels, int n_level, int side, int32_t* stats,
                               float* excess, int B, int T, int C, void* stream);
+/* The kernel of sgv_cycles on caller-owned buffers: inputs as sgv_test_recon_physical, gate fp32 [C] and the outputs of out
+ * ([B][C], [B][4][C], [B][2][C], [B][3][C]) on the device, then the statistics of y and the cycles pass.  SGV_ERR_ARG, nothing
+ * launched: a NULL input (gate and out included), no group, half a group, an exponent outside [1, 8], B or T < 1, T > 65535,
+ * C < 8 or C % 8 != 0, a bad row stride, a misaligned pointer (y and the outputs 16 bytes; gate 4). */
+int sgv_test_recon_cycles(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta, const float* scale,
+                          const float* min, const float* gate, int exponent, const sgv_cycles_out* out, int B, int T, int C, void* stream);
 /* GELU without GroupNorm.  mode 0: out = gelu(y).  mode 1: out = dout * rscale * gelu'(y), dbias = column sums of out,
  * cdot[0] = sum out * (y - cbias).  mode 2: y holds a gradient dY: dbias = its column sums, cdot[0] = sum dY * (yf32 - cbias)
  * (yf32 [B*T][ldyf] fp32; cdot needs it). */

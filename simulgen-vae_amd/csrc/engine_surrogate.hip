@@ -136,4 +136,13 @@ int sgv_exceedance(sgv_engine* e, const float* z_dev, const float* xs_dev, int b
     CHK(tail_exceedance(me, scale_dev, min_dev, e->T, levels_dev, n_level, side, stats_dev_or_NULL, excess_dev_or_NULL, tail));
     return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, me, tail);
 }
+
+int sgv_cycles(sgv_engine* e, const float* z_dev, const float* xs_dev, int batch, int mode_fix, const float* scale_dev,
+               const float* min_dev, const float* gate_dev, int exponent, const sgv_cycles_out* out) {
+    const char* me = "sgv_cycles";
+    ReconTail tail;
+    CHK(common_ok(me, e, z_dev, scale_dev, min_dev));
+    CHK(tail_cycles(me, scale_dev, min_dev, e->T, gate_dev, exponent, out, tail));
+    return surrogate_pass(e, z_dev, xs_dev, batch, mode_fix, me, tail);
+}
 }  // extern "C"

@@ -2,8 +2,8 @@
 // (sgv_generate), its summaries (sgv_summarize), its error against held-out fields (sgv_score), the running statistics over the
 // members of an ensemble (sgv_ensemble), the running sums of a Sobol sensitivity study (sgv_sobol), the histogram of the members
 // between given bounds (sgv_distribution), the co-moments of the members with their covariates (sgv_regress), weighted sums over the
-// mesh (sgv_project) or over time (sgv_temporal), the temporal Gram matrix (sgv_gram) and the level-crossing statistics over time
-// (sgv_exceedance).  All of them stream y = the recon head's convolution output once, form the same value per
+// mesh (sgv_project) or over time (sgv_temporal), the temporal Gram matrix (sgv_gram), the level-crossing statistics over time
+// (sgv_exceedance) and the load cycles and rates of the time histories (sgv_cycles).  All of them stream y = the recon head's convolution output once, form the same value per
 // element (recon_phys_val) and differ in what they do with it; DESIGN.md, "the recon tails", describes the shared pieces below.
 #include <algorithm>
 #include <type_traits>
@@ -1823,5 +1823,172 @@ int ew_recon_exceedance(int dtype, GNParams p, const float* scale, const float* 
     // recon_dispatch leaves out the combination with every flag false only; the launcher above never instantiates the kernel without an output
     if (o.above) recon_dispatch<true>(launch, dtype, o.stats != nullptr, o.excess != nullptr);
     else recon_dispatch<false>(launch, dtype, o.stats != nullptr, o.excess != nullptr);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Surrogate load cycles and rates (sgv_cycles): per channel, the turning points of its time history behind a hysteresis gate -- ASTM
+// E1049 simple-range counting, the ranges between successive confirmed reversals, their number, sum, maximum and damage sum
+// sum R^m, the unfinished excursion at the end -- and the statistics of the first differences: the largest rise and fall, their
+// steps, the path length.  The contract, to the rounding, is in sgv_ew.h (ReconCycles); x is the value recon_phys_val gives.
+// Geometry: recon_exceed_kernel's.  A thread owns its 8 channels of one sample for all T, t ascending, the rows of xc_flight() steps in
+// flight in a register ring, a row past T - 1 being row T - 1 again; no reduction across threads, no LDS besides gn_consts' table, no
+// workspace, no finish kernel, no atomics.  Step 0 only sets the state (hi = lo = the previous x = x[0]); it is loaded beside the ring,
+// which starts at step 1, so the loop over t has one body: with the step-0 case inside it the fp32 kernel took 256 registers and
+// 36 bytes of scratch.
+// State, 11 words per channel: a = hi (dir 0) or cand; b = lo (dir 0) or last; st = reversals | (dir != 0) << 16 | (dir == -1) << 31;
+// range_sum, range_max, damage; the previous x; rise, fall, rise_when | fall_when << 16 (0xffff: none yet), path.  Every half stays
+// below 2^16 while T < 65536; the launcher refuses a longer T.  The two directions share one code path through the sign bit:
+// fl(a - b) = fl((-b) - (-a)) exactly.  Differences go through gr_diff, the power and the sums through cy_count, so that nothing is
+// contracted with recon_phys_val's multiply by 1 / scale or with each other.  The power is a run-time loop, the same for every lane;
+// a channel that confirms nothing at a step counts R = +0.0, which leaves its three sums as they are (s + 0 = s, 0 > max never), so
+// the step has no divergent branch.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void cy_count(const float R[8], int m, float rsum[8], float rmax[8], float dmg[8]) {
+#pragma clang fp contract(off)
+    float P[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) P[e] = R[e];
+    for (int k = 1; k < m; ++k)           // uniform
+#pragma unroll
+        for (int e = 0; e < 8; ++e) P[e] = P[e] * R[e];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        rsum[e] = rsum[e] + R[e];
+        rmax[e] = R[e] > rmax[e] ? R[e] : rmax[e];
+        dmg[e] = dmg[e] + P[e];
+    }
+}
+__device__ __forceinline__ float cy_flip(float v, unsigned sign) { return __uint_as_float(__float_as_uint(v) ^ sign); }
+
+template <typename T, bool TURNS, bool RATES>
+__global__ __launch_bounds__(256, 2) void recon_cycles_kernel(const GNParams p, const ReconPhys q, const ReconCycles o) {
+    constexpr int F = xc_flight<T>();
+    GNCtx c;
+    c.b = blockIdx.z;
+    c.c0 = blockIdx.x * XC_BLOCK_COLS + threadIdx.x * 8;
+    c.col_ok = c.c0 < p.C;
+    float mean[8], rstd[8];
+    gn_consts(p, c, mean, rstd);          // all 256 threads
+    if (!c.col_ok) return;                // no barrier, no shuffle below
+    float gam[8], bet[8], mn[8], inv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float4 k = recon_channel(p, q, c.c0 + e, true); gam[e] = k.x; bet[e] = k.y; mn[e] = k.z; inv[e] = k.w; }
+    const int m = o.exponent;
+    float gate[8], a[8], b[8], rsum[8], rmax[8], dmg[8];          // the turns
+    unsigned st[8];
+    float prev[8], rise[8], fall[8], path[8];                      // the rates
+    unsigned wh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        gate[e] = TURNS ? o.gate[c.c0 + e] : 0.f;
+        a[e] = b[e] = rsum[e] = rmax[e] = dmg[e] = 0.f; st[e] = 0u;
+        prev[e] = rise[e] = fall[e] = path[e] = 0.f; wh[e] = 0xffffffffu;
+    }
+    const T* const y = reinterpret_cast<const T*>(p.y) + (long)c.b * p.T * p.ldy + c.c0;
+    // the ring holds steps 1 .. F, slot u of a round the step t0 + u; a row past T - 1 is row T - 1 again, loaded and not used
+    Raw8<T> ry[F], r0;
+#pragma unroll
+    for (int u = 0; u < F; ++u) raw_load(y + (long)min(1 + u, p.T - 1) * p.ldy, ry[u]);
+    raw_load(y, r0);
+    {          // step 0: hi = lo = x[0], no difference yet
+        float x[8];
+        raw_unpack(r0, x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = b[e] = prev[e] = recon_phys_val(x[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+    }
+    for (int t0 = 1; t0 < p.T; t0 += F) {
+#pragma unroll
+        for (int u = 0; u < F; ++u) {
+            const int t = t0 + u;
+            if (t >= p.T) break;          // uniform
+            float x[8];
+            raw_unpack(ry[u], x);
+            raw_load(y + (long)min(t + F, p.T - 1) * p.ldy, ry[u]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = recon_phys_val(x[e], mean[e], rstd[e], gam[e], bet[e], mn[e], inv[e]);
+            if constexpr (RATES) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float xx = x[e];
+                    const float r = gr_diff(xx, prev[e]);
+                    const bool first = t == 1, up = first || r > rise[e], dn = first || r < fall[e];
+                    rise[e] = up ? r : rise[e];
+                    fall[e] = dn ? r : fall[e];
+                    wh[e] = up ? (wh[e] & 0xffff0000u) | (unsigned)t : wh[e];
+                    wh[e] = dn ? (wh[e] & 0xffffu) | (unsigned)t << 16 : wh[e];
+                    path[e] = path[e] + fabsf(r);
+                    prev[e] = xx;
+                }
+            }
+            if constexpr (TURNS) {
+                float R[8];               // the range confirmed at this step, +0.0 where none is
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float xx = x[e];
+                    const unsigned sg = st[e] & 0x80000000u;          // dir = -1: the rising direction of the negated history
+                    const bool idle = !(st[e] & 0x10000u);            // dir = 0
+                    const float A = a[e], Bv = b[e], h = gate[e];
+                    const float xs = cy_flip(xx, sg), As = cy_flip(A, sg);
+                    // one difference serves dir = 0 (hi - x, the peak), +1 (cand - x) and -1 (x - cand); dir = 0 tries the valley first
+                    const bool ext = xs > As, up0 = idle && gr_diff(xx, Bv) > h;
+                    const bool rev = gr_diff(As, xs) > h && !(idle ? up0 : ext);
+                    R[e] = rev && !idle ? gr_diff(As, cy_flip(Bv, sg)) : 0.f;
+                    b[e] = rev ? A : idle && !up0 && xx < Bv ? xx : Bv;
+                    a[e] = up0 || rev || ext ? xx : A;
+                    st[e] = ((st[e] + (up0 || rev ? 0x1u : 0u)) | (up0 || rev ? 0x10000u : 0u)) ^ (rev ? 0x80000000u : 0u);
+                }
+                cy_count(R, m, rsum, rmax, dmg);
+            }
+        }
+    }
+    if constexpr (TURNS) {
+        int v[8];
+        float w[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (int)(st[e] & 0xffffu);
+        store8(o.reversals + (long)c.b * p.C + c.c0, v);
+        float* const rg = o.ranges + (long)c.b * 4 * p.C + c.c0;          // [B][4][C]: range_sum, range_max, damage, open
+        store8(rg, rsum);
+        store8(rg + p.C, rmax);
+        store8(rg + 2L * p.C, dmg);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) w[e] = st[e] & 0x80000000u ? gr_diff(b[e], a[e]) : gr_diff(a[e], b[e]);
+        store8(rg + 3L * p.C, w);
+    }
+    if constexpr (RATES) {
+        int* const rw = o.rate_when + (long)c.b * 2 * p.C + c.c0;          // [B][2][C]: rise_when, fall_when
+        int v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (wh[e] & 0xffffu) == 0xffffu ? -1 : (int)(wh[e] & 0xffffu);
+        store8(rw, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = wh[e] >> 16 == 0xffffu ? -1 : (int)(wh[e] >> 16);
+        store8(rw + p.C, v);
+        float* const rt = o.rates + (long)c.b * 3 * p.C + c.c0;            // [B][3][C]: rise, fall, path
+        store8(rt, rise);
+        store8(rt + p.C, fall);
+        store8(rt + 2L * p.C, path);
+    }
+}
+
+// p as for ew_recon_physical (layout [B][T][C] only); o: ReconCycles (sgv_ew.h).  Non-zero (nothing launched): -1 null input (gate
+// included), -2 no group or half a group, -3 bad shape, exponent outside [1, SGV_MAX_CYCLES_EXPONENT] or T > 65535 (the packed state),
+// -4 y or an output not 16-byte aligned or gate not 4-byte aligned
+int ew_recon_cycles(int dtype, GNParams p, const float* scale, const float* mn, const ReconCycles& o, hipStream_t s) {
+    if (const int r = recon_args_ok(p, scale, mn)) return r;
+    if (!o.gate) return -1;
+    const bool turns = o.reversals || o.ranges, rates = o.rate_when || o.rates;
+    if (!turns && !rates) return -2;
+    if ((turns && !(o.reversals && o.ranges)) || (rates && !(o.rate_when && o.rates))) return -2;
+    if (o.exponent < 1 || o.exponent > SGV_MAX_CYCLES_EXPONENT || p.T > XC_MAX_T) return -3;
+    if (((uintptr_t)p.y | (uintptr_t)o.reversals | (uintptr_t)o.ranges | (uintptr_t)o.rate_when | (uintptr_t)o.rates) & 15) return -4;
+    if ((uintptr_t)o.gate & 3) return -4;
+    const ReconPhys q = recon_setup(p, scale, mn);
+    const dim3 grid(cdiv_i(p.C, XC_BLOCK_COLS), 1, p.B);
+    auto launch = [&](auto el, auto tu, auto ra) {
+        hipLaunchKernelGGL((recon_cycles_kernel<typename decltype(el)::type, decltype(tu)::value, decltype(ra)::value>), grid, dim3(256), 0, s, p, q, o);
+    };
+    recon_dispatch(launch, dtype, turns, rates);
     return 0;
 }

@@ -216,3 +216,23 @@ static inline int tail_exceedance(const char* who, const float* scale, const flo
     tail.run = [=](int dtype, const GNParams& p, float*, hipStream_t s) { return ew_recon_exceedance(dtype, p, scale, mn, r, s); };
     return 0;
 }
+// exponent within [1, SGV_MAX_CYCLES_EXPONENT] (sgv_ew.h), T within the kernel's packed 16-bit counters; a group of outputs whole or not
+// at all; the rows of the outputs are written 32 bytes at a time
+static inline int tail_cycles(const char* who, const float* scale, const float* mn, int T, const float* gate, int exponent, const sgv_cycles_out* o,
+                              ReconTail& tail) {
+    if (!gate || !o) return fail(SGV_ERR_ARG, "%s: null argument", who);
+    const bool turns = o->reversals || o->ranges, rates = o->rate_when || o->rates;
+    if (!turns && !rates) return fail(SGV_ERR_ARG, "%s: no group of the outputs is given", who);
+    if ((turns && !(o->reversals && o->ranges)) || (rates && !(o->rate_when && o->rates)))
+        return fail(SGV_ERR_ARG, "%s: half a group (reversals + ranges, rate_when + rates go together)", who);
+    if (exponent < 1 || exponent > SGV_MAX_CYCLES_EXPONENT) return fail(SGV_ERR_ARG, "%s: exponent = %d is outside [1, %d]", who, exponent, SGV_MAX_CYCLES_EXPONENT);
+    if (T > 65535) return fail(SGV_ERR_ARG, "%s: T = %d is beyond the limit of 65535 time steps", who, T);
+    if (((uintptr_t)gate & 3) || (((uintptr_t)o->reversals | (uintptr_t)o->ranges | (uintptr_t)o->rate_when | (uintptr_t)o->rates) & 15))
+        return fail(SGV_ERR_ARG, "%s: misaligned pointer (gate 4 bytes, the outputs 16)", who);
+    ReconCycles r;
+    r.gate = gate; r.exponent = exponent; r.reversals = o->reversals; r.ranges = o->ranges; r.rate_when = o->rate_when; r.rates = o->rates;
+    tail.tag = "recon_cycles";
+    tail.rejected = "sgv_cycles: the cycles pass rejected its arguments (%d)";
+    tail.run = [=](int dtype, const GNParams& p, float*, hipStream_t s) { return ew_recon_cycles(dtype, p, scale, mn, r, s); };
+    return 0;
+}

@@ -259,6 +259,43 @@ struct ReconExceed {
     int* stats = nullptr; float* excess = nullptr;
 };
 int ew_recon_exceedance(int dtype, GNParams p, const float* scale, const float* mn, const ReconExceed& o, hipStream_t s);
+// recon head -> the load cycles and the rates of every channel's time history, the field never stored: ASTM E1049 simple-range
+// counting behind a hysteresis gate (peak-valley filtering) and the statistics of the first differences.  x[t] is the value
+// ew_recon_physical would store at (b, t, n) (layout [B][T][C]), h = gate[n] >= 0, m = exponent in [1, SGV_MAX_CYCLES_EXPONENT], fl()
+// one fp32 rounding.  Every difference is formed from the stored value and rounded on its own, every product of the power and every
+// accumulation likewise: nothing is contracted into an fma.  All comparisons are strict.
+// Rates, t = 1 .. T - 1, r[t] = fl(x[t] - x[t-1]):
+//   rates[b][0][n] = rise = max r[t], rates[b][1][n] = fall = min r[t]; rate_when[b][0][n], [1][n] = the step t of each, the smallest on
+//   a tie (strict > / < updates starting from r[1]); rates[b][2][n] = path = s after s = +0.0; s = fl(s + |r[t]|), t ascending.
+//   T = 1: rise = fall = path = +0.0, both steps -1.
+// Turns, a machine of three states per channel, dir in {0, +1, -1}, from dir = 0, hi = lo = x[0]; for t = 1 .. T - 1, x = x[t]:
+//   dir = 0:  fl(x - lo) > h: a valley is confirmed, last = lo, cand = x, dir = +1, reversals += 1; else fl(hi - x) > h: a peak,
+//             last = hi, cand = x, dir = -1, reversals += 1; else hi = max(hi, x), lo = min(lo, x).  (Both cannot hold for h >= 0; the
+//             order is the definition.)  The first turning point carries no range.
+//   dir = +1: x > cand: cand = x; else fl(cand - x) > h: a peak is confirmed, R = fl(cand - last) is counted, last = cand, cand = x,
+//             dir = -1, reversals += 1.
+//   dir = -1: x < cand: cand = x; else fl(x - cand) > h: a valley, R = fl(last - cand) is counted, last = cand, cand = x, dir = +1,
+//             reversals += 1.
+//   counted: range_sum = fl(range_sum + R); range_max = R if R > range_max; damage = fl(damage + P), P = R, then m - 1 times
+//            P = fl(P * R); all three from +0.0.
+//   open, the unfinished excursion at the end: fl(hi - lo) at dir = 0, fl(cand - last) at +1, fl(last - cand) at -1.
+//   reversals[b][n]; ranges[b][0..3][n] = range_sum, range_max, damage, open.  The counted ranges (half cycles) number
+//   max(reversals - 1, 0); a constant history gives 0 and +0.0 throughout; a gate above the peak-to-peak gives reversals 0 and
+//   open = fl(max - min).
+// gate fp32 [C], 4-byte aligned (input); reversals int32 [B][C] with ranges fp32 [B][4][C] (the turns), rate_when int32 [B][2][C] with
+// rates fp32 [B][3][C] (the rates), 16-byte aligned; a group may be absent, not both, and not half of one.  T <= 65535 (the kernel packs
+// its counters and steps into 16-bit halves).  An output depends on sample b and channel n alone -- a sample gives the bits it gives in
+// any batch, a group the bits it gives with or without the other, the exponent shows in damage alone -- and two launches are bitwise
+// equal.  No atomics, no workspace.
+// Non-zero (nothing launched): -1 null input (gate included), -2 no group or half a group, -3 bad shape, exponent outside
+// [1, SGV_MAX_CYCLES_EXPONENT] or T > 65535, -4 y or an output not 16-byte aligned or gate not 4-byte aligned
+constexpr int SGV_MAX_CYCLES_EXPONENT = 8;
+struct ReconCycles {
+    const float* gate = nullptr; int exponent = 0;
+    int* reversals = nullptr; float* ranges = nullptr;          // the turns
+    int* rate_when = nullptr; float* rates = nullptr;           // the rates
+};
+int ew_recon_cycles(int dtype, GNParams p, const float* scale, const float* mn, const ReconCycles& o, hipStream_t s);
 int ew_act(int dtype, int mode, GNParams p, hipStream_t s);
 int ew_add3(int dtype, const void* a, long lda, const void* b, long ldb, const void* c, long ldc, void* out, long ldo,
             int rows, int C, hipStream_t s);

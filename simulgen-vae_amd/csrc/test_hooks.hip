@@ -388,6 +388,14 @@ int sgv_test_recon_exceedance(int dtype, const void* y, long ldy, double* sums, 
     CHK(tail_exceedance(me, scale, min, T, levels, n_level, side, stats, excess, tail));
     return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
 }
+int sgv_test_recon_cycles(int dtype, const void* y, long ldy, double* sums, const float* gamma, const float* beta, const float* scale,
+                          const float* min, const float* gate, int exponent, const sgv_cycles_out* out, int B, int T, int C, void* stream) {
+    const char* me = "sgv_test_recon_cycles";
+    GNParams p; ReconTail tail;
+    CHK(recon_hook_front(me, dtype, y, ldy, sums, gamma, beta, scale, min, B, T, C, p));
+    CHK(tail_cycles(me, scale, min, T, gate, exponent, out, tail));
+    return recon_hook_run(me, dtype, p, tail.work_floats(B, T, C), stream, tail.run);
+}
 int sgv_test_act(int dtype, int mode, const void* y, long ldy, const void* dout, long lddout, float rscale, void* out, long ldout,
                  float* dbias, float* cdot, const float* cbias, const float* yf32, long ldyf, float* work, size_t work_floats, int B,
                  int T, int C, void* stream) {

@@ -25,7 +25,7 @@ LAYOUTS = {"TN": 0, "NT": 1}             # SGV_LAYOUT_*: generate() writes [B, T
 ABI_SYMBOLS = [
     "sgv_last_error", "sgv_create", "sgv_destroy", "sgv_param_count", "sgv_param_info", "sgv_load_state",
     "sgv_export_state", "sgv_export_grad", "sgv_export_adam", "sgv_prepare", "sgv_set_input", "sgv_set_eps",
-    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_temporal", "sgv_gram", "sgv_exceedance", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
+    "sgv_seed", "sgv_set_shard", "sgv_set_draw_row", "sgv_set_option", "sgv_forward", "sgv_decode", "sgv_generate", "sgv_set_probes", "sgv_summarize", "sgv_score", "sgv_ensemble", "sgv_sobol", "sgv_distribution", "sgv_regress", "sgv_project", "sgv_temporal", "sgv_gram", "sgv_exceedance", "sgv_cycles", "sgv_encode", "sgv_get_xhat", "sgv_get_activation",
     "sgv_backward", "sgv_set_bucket_callback", "sgv_grad_buffer", "sgv_scale_grads", "sgv_grad_norm",
     "sgv_adamw_step", "sgv_augment_collate", "sgv_dataset_convert", "sgv_dataset_sample_bytes",
     "sgv_adamw_step_range", "sgv_bucket_count", "sgv_bucket_dots", "sgv_wire_stream", "sgv_opt_stream", "sgv_adamw_bucket_async", "sgv_set_grad_payload", "sgv_grad_payload_buffer", "sgv_grad_payload_unpack", "sgv_memory_info", "sgv_recompute_bytes", "sgv_last_grad_norm", "sgv_scalars_accumulate", "sgv_scalars_read", "sgv_backward_step",
@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "sgv_load_adam", "sgv_get_train_state", "sgv_set_train_state",
     "sgv_snapshot_floats", "sgv_snapshot_slice", "sgv_snapshot_begin", "sgv_snapshot_wait", "sgv_restore", "sgv_copy_stream",
     "sgv_kernel_time", "sgv_kernel_time_reset", "sgv_kernel_time_tag", "sgv_test_gemm_nt", "sgv_test_gemm_nt_stats", "sgv_test_gemm_nt256", "sgv_test_conv_gn_fwd", "sgv_test_conv_gn_bwd", "sgv_test_gemm_tn", "sgv_test_stream_overlap", "sgv_test_occupy", "sgv_test_fake_collective",
-    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_recon_temporal", "sgv_test_recon_gram", "sgv_test_recon_exceedance", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
+    "sgv_test_gn_workspace_floats", "sgv_test_gn_fwd", "sgv_test_gn_bwd", "sgv_test_recon_loss", "sgv_test_recon_physical", "sgv_test_recon_summary", "sgv_test_recon_score", "sgv_test_recon_ensemble", "sgv_test_recon_sobol", "sgv_test_recon_distribution", "sgv_test_recon_regress", "sgv_test_recon_project", "sgv_test_recon_temporal", "sgv_test_recon_gram", "sgv_test_recon_exceedance", "sgv_test_recon_cycles", "sgv_test_act", "sgv_test_latent", "sgv_test_stage", "sgv_test_linear_head", "sgv_test_linear_expand",
     "sgv_test_optset_create", "sgv_test_optset_destroy", "sgv_test_optset_power_iteration", "sgv_test_optset_grad_dot", "sgv_test_optset_grad_norm",
     "sgv_test_optset_adamw", "sgv_test_optset_make_copies",
 ]
@@ -88,6 +88,11 @@ class RegressState(C.Structure):
     _fields_ = [("mean", C.c_void_p), ("m2", C.c_void_p), ("comoment", C.c_void_p)]
 
 
+class CyclesOut(C.Structure):
+    """sgv_cycles_out (include/sgvae.h): the outputs of sgv_cycles, device pointers; a group (reversals + ranges, rate_when + rates) whole or not at all"""
+    _fields_ = [("reversals", C.c_void_p), ("ranges", C.c_void_p), ("rate_when", C.c_void_p), ("rates", C.c_void_p)]
+
+
 MAX_PROBES = 4096
 SUMMARY_PARTS = ("node", "frame", "probes")      # `want` of Engine.summarize
 SCORE_PARTS = ("node", "frame")                  # `want` of Engine.score
@@ -108,6 +113,10 @@ MAX_LEVELS = 4                                   # SGV_MAX_EXCEED_LEVELS: the le
 EXCEEDANCE_MAX_T = 65535                         # the kernel packs its step counters into 16-bit halves
 EXCEEDANCE_SIDES = {"above": 0, "below": 1}      # SGV_SIDE_*
 EXCEEDANCE_STATS = ("count", "first", "last", "longest", "runs")      # the planes of Engine.exceedance's stats, in this order
+MAX_CYCLES_EXPONENT = 8                          # SGV_MAX_CYCLES_EXPONENT: the exponent m of the damage sum of Engine.cycles, an integer in [1, 8]
+CYCLES_MAX_T = 65535                             # the kernel packs its counters and steps into 16-bit halves
+CYCLES_RANGES = ("range_sum", "range_max", "damage", "open")      # the planes of Engine.cycles' ranges, in this order
+CYCLES_RATES = ("rise", "fall", "path")          # the planes of Engine.cycles' rates; rate_when holds the steps of rise and fall
 SNAPSHOT_PARTS = ("value", "exp_avg", "exp_avg_sq")     # `which` of sgv_snapshot_slice
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 _lib = None
@@ -167,6 +176,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_temporal.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.sgv_gram.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.sgv_exceedance.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp]
+    lib.sgv_cycles.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.sgv_copy_stream.argtypes = [vp, C.POINTER(vp)]
     lib.sgv_get_xhat.argtypes = [vp, vp]
     lib.sgv_get_activation.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
@@ -239,6 +249,7 @@ def load_library(path: str = LIB_PATH):
     lib.sgv_test_recon_temporal.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_gram.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.sgv_test_recon_exceedance.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp]
+    lib.sgv_test_recon_cycles.argtypes = [i32, vp, lg, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]
     lib.sgv_test_act.argtypes = [i32, i32, vp, lg, vp, lg, f32, vp, lg, vp, vp, vp, vp, lg, vp, sz, i32, i32, i32, vp]
     lib.sgv_test_latent.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     lib.sgv_test_stage.argtypes = [i32, vp, vp, vp, vp, lg, vp, lg, vp, f32, f32, vp, vp, vp, lg, vp, vp, f32, i32, i32, vp]
@@ -482,7 +493,7 @@ class Engine:
         _check(self.lib, self.lib.sgv_set_shard(self.h, int(rank), int(world)), "sgv_set_shard")
 
     def set_draw_row(self, first_row: int):
-        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project, temporal, gram, exceedance) takes
+        """Sample b of the following passes that draw their noise per call (generate, summarize, score, project, temporal, gram, exceedance, cycles) takes
         row first_row + b of the streams the call draws from (include/sgvae.h: sgv_set_draw_row).  With the draw position put back in
         front of every batch (set_train_state) a study cut into batches gets the noise one call over all of it would get.  Default 0."""
         _check(self.lib, self.lib.sgv_set_draw_row(self.h, int(first_row)), "sgv_set_draw_row")
@@ -855,6 +866,45 @@ class Engine:
                     res[name] = _out_tensor(v, shape, dt, f"{name} must be True, False or a contiguous {dt} CUDA tensor", new=True)
             return (_ptr(levels), L, EXCEEDANCE_SIDES[side], _ptr(res.get("stats")), _ptr(res.get("excess"))), res
         return self._surrogate("sgv_exceedance", z, xs, scale, min, fix, tail)
+
+    def cycles(self, z, xs, scale, min, gate, exponent=3, fix=True, turns=True, rates=True):
+        """The load cycles and the rates of every node's time history in the field generate() would write, by the recon head's last
+        pass itself; the field is never stored.  Same inputs and checks as summarize(); num_time <= CYCLES_MAX_T.  gate: contiguous
+        fp32 CUDA [N], >= 0 (predict.cycles_gate validates a host array); exponent: the integer m of the damage sum, 1 <= m <=
+        MAX_CYCLES_EXPONENT.  turns, rates: True for new tensors, False to leave the group out (not both), or a pair of contiguous
+        CUDA tensors to write into, (reversals int32 [B, N], ranges fp32 [B, 4, N]) / (rate_when int32 [B, 2, N], rates fp32
+        [B, 3, N]) (slices along the first axis of larger ones will do).  Returns a dict with the tensors of the groups asked for.
+        The turns are ASTM E1049 simple-range counting behind the hysteresis gate: reversals is the number of confirmed turning
+        points, ranges[b, k] for k in CYCLES_RANGES order the sum and the largest of the ranges between successive turning points,
+        the damage sum of range^m and the open excursion at the end; rates[b, k] for k in CYCLES_RATES order is the largest and the
+        smallest first difference and the path length, rate_when[b] the steps of the first two (-1 at num_time = 1); the contract,
+        to the rounding, is in include/sgvae.h (sgv_cycles_out).  Every output depends on its sample and node alone, so any cut of
+        the conditions into batches gives the same bits.  Nothing synchronises; afterwards xhat() raises, as after generate()."""
+        t = self.torch
+        N, T = self.cfg.num_node, self.cfg.num_time
+        if T > CYCLES_MAX_T:
+            raise ValueError(f"num_time = {T} is beyond the limit of {CYCLES_MAX_T} time steps of the cycles pass")
+        if not is_tensor_of(gate, t.float32, (N,)):
+            raise ValueError(f"gate must be a contiguous float32 CUDA tensor of shape [{N}]")
+        m = int(exponent)
+        if m != exponent or m < 1 or m > MAX_CYCLES_EXPONENT:
+            raise ValueError(f"exponent = {exponent!r} is not an integer in [1, {MAX_CYCLES_EXPONENT}]")
+        if turns is False and rates is False:
+            raise ValueError("nothing to compute: turns and rates are both False")
+
+        def tail(B):
+            res = {}
+            groups = (("turns", turns, (("reversals", t.int32, (B, N)), ("ranges", t.float32, (B, 4, N)))),
+                      ("rates", rates, (("rate_when", t.int32, (B, 2, N)), ("rates", t.float32, (B, 3, N)))))
+            for group, v, parts in groups:
+                if v is False:
+                    continue
+                if v is not True and not (isinstance(v, (tuple, list)) and len(v) == len(parts)):
+                    raise ValueError(f"{group} must be True, False or a pair of CUDA tensors ({parts[0][0]}, {parts[1][0]})")
+                for k, (name, dt, shape) in enumerate(parts):
+                    res[name] = _out_tensor(True if v is True else v[k], shape, dt, f"{name} must be a contiguous {dt} CUDA tensor", new=True)
+            return (_ptr(gate), m, C.byref(CyclesOut(**{name: v.data_ptr() for name, v in res.items()}))), res
+        return self._surrogate("sgv_cycles", z, xs, scale, min, fix, tail)
 
     def copy_stream(self) -> int:
         """Raw HIP stream of the engine's device-to-host copies (include/sgvae.h: sgv_copy_stream); wrap with torch.cuda.ExternalStream."""

@@ -50,6 +50,9 @@ the parametric conditioner has no such test.  `predict_to_host` adds its one wai
     hot = dur.duration(dt), dur.longest_duration(dt)   # stays above a level, when it first crosses and is last above, one long
     node, steps = dur.worst()                      # excursion or many short ones (dur.runs), the accumulated excess: 24 L N bytes
                                                    # per condition instead of 4 T N
+    cyc = s.cycles(conditions, gate=0.05 * allowable, exponent=3)   # fatigue and rate questions: the reversals of every node's
+    dmg, node = cyc.damage(coefficient=Cf), cyc.worst()[0]   # history behind a hysteresis gate, the ranges between them, sum range^m,
+    rate = cyc.peak_rate(dt)                       # the largest rise and fall and when: 40 N bytes per condition
 """
 from __future__ import annotations
 
@@ -60,7 +63,7 @@ import pickle
 
 import numpy as np
 
-from .engine import (DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, EXCEEDANCE_MAX_T, EXCEEDANCE_SIDES, EXCEEDANCE_STATS, LAYOUTS, MAX_LEVELS, MAX_FUNCTIONALS, MAX_GRAM_T, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
+from .engine import (CYCLES_MAX_T, CYCLES_RANGES, CYCLES_RATES, MAX_CYCLES_EXPONENT, DISTRIBUTION_MAX_BINS, DISTRIBUTION_MIN_BINS, ENSEMBLE_GROUPS, ENSEMBLE_MAX_COUNT, EXCEEDANCE_MAX_T, EXCEEDANCE_SIDES, EXCEEDANCE_STATS, LAYOUTS, MAX_LEVELS, MAX_FUNCTIONALS, MAX_GRAM_T, MAX_PROBES, MAX_TEMPORAL, REGRESS_FIELDS, REGRESS_MAX_COVARIATES,
                      SOBOL_FIELDS, SOBOL_MAX_PARAMS, is_tensor_of)
 from .engine import SOBOL_MAX_BLOCKS as SOBOL_MAX_COUNT          # base samples of one study
 
@@ -719,6 +722,120 @@ class ExceedanceResult(_StreamResult):
         return self._on_stream(fn)
 
 
+def cycles_gate(gate, N):
+    """The hysteresis gate of Surrogate.cycles as contiguous float32 [N] in physical units: a scalar is one gate for every node, an
+    [N] array is taken node by node.  A CUDA tensor stays on the device and comes back as a contiguous float32 CUDA tensor; it is
+    judged by its shape and dtype alone and NOT read back (a negative or NaN gate on the device is the caller's).  Anything else
+    is looked at through np.asarray and comes back as a numpy array, every entry >= 0 as float32 and not NaN (inf is allowed:
+    nothing turns).  ValueError naming the problem otherwise: a shape other than () or [N], or -- host data -- a negative or NaN
+    entry (the first one is named).  numpy only for host data."""
+    N = int(N)
+    dev = _is_device_tensor(gate)
+    a = gate if dev else np.asarray(gate, dtype=np.float64)
+    shape = tuple(int(d) for d in a.shape)
+    if shape not in ((), (N,)):
+        raise ValueError(f"gate: a scalar or an [N] = [{N}] vector is required, got shape {shape}")
+    if dev:
+        if not a.dtype.is_floating_point:
+            raise ValueError(f"gate: a floating dtype is required, not {a.dtype}")
+        import torch
+        return a.to(dtype=torch.float32).reshape(-1).expand(N).contiguous()
+    with np.errstate(over="ignore"):
+        v = a.astype(np.float32).reshape(-1)
+    bad = np.flatnonzero(~(v >= 0))          # a NaN fails the comparison too
+    if bad.size:
+        n = int(bad[0])
+        where = f"gate[{n}]" if shape else "gate"
+        raise ValueError(f"{where} = {float(a.reshape(-1)[n])!r} is not a gate: a value >= 0 is required")
+    return np.array(np.broadcast_to(v, (N,)), order="C")          # a copy: the broadcast view is read-only
+
+
+class CyclesResult(_StreamResult):
+    """Surrogate.cycles' result for P conditions: the load cycles and the rates of every node's T time steps, device tensors that are
+    the caller's.  The turns (ASTM E1049 simple-range counting behind the hysteresis gate): reversals int32 [P, N], the confirmed
+    turning points, and ranges fp32 [P, 4, N] with the views range_sum, range_max, damage_sum (the sum of range^exponent over the
+    counted ranges) and open (the unfinished excursion at the end), each [P, N].  The rates: rate_when int32 [P, 2, N] with the views
+    rise_when, fall_when (-1 at T = 1) and rates fp32 [P, 3, N] with the views rise, fall (the largest and the smallest first
+    difference) and path (the sum of their magnitudes).  gate fp32 [N] as it was used, exponent, T.  A group that was not asked for
+    is None and its methods raise ValueError.  What is derived is plain torch on the small result, computed on the engine stream."""
+    FIELDS = ("reversals", "ranges", "rate_when", "rates", "gate", "exponent", "T")
+
+    def _turns(self, name):
+        if self.ranges is None:
+            raise ValueError(f"{name}: the turns were not asked for (want=(\"turns\", ...))")
+        return self.ranges[:, CYCLES_RANGES.index(name)] if name in CYCLES_RANGES else self.reversals
+
+    def _rates(self, name):
+        if self.rates is None:
+            raise ValueError(f"{name}: the rates were not asked for (want=(..., \"rates\"))")
+        return self.rates[:, CYCLES_RATES.index(name)] if name in CYCLES_RATES else self.rate_when[:, ("rise_when", "fall_when").index(name)]
+
+    range_sum = property(lambda self: self._turns("range_sum"))
+    range_max = property(lambda self: self._turns("range_max"))
+    damage_sum = property(lambda self: self._turns("damage"))
+    open = property(lambda self: self._turns("open"))
+    rise = property(lambda self: self._rates("rise"))
+    fall = property(lambda self: self._rates("fall"))
+    path = property(lambda self: self._rates("path"))
+    rise_when = property(lambda self: self._rates("rise_when"))
+    fall_when = property(lambda self: self._rates("fall_when"))
+
+    def half_cycles(self):
+        """max(reversals - 1, 0): int32 [P, N], the number of counted ranges (half cycles)"""
+        return self._on_stream(lambda: (self._turns("half_cycles") - 1).clamp(min=0))
+
+    def mean_range(self):
+        """range_sum / half_cycles, 0 where no range is counted: fp32 [P, N]"""
+        def fn():
+            k = (self._turns("mean_range") - 1).clamp(min=0)
+            return (self.range_sum / k.clamp(min=1).float()).masked_fill(k == 0, 0.0)
+        return self._on_stream(fn)
+
+    def damage(self, coefficient=1.0, include_open=True):
+        """0.5 (damage_sum + open^exponent) / coefficient: fp32 [P, N], Miner's sum for an S-N curve N(R) = coefficient / R^exponent,
+        every counted range half a cycle; include_open counts the unfinished excursion at the end as one more half cycle"""
+        def fn():
+            d = self._turns("damage")
+            if include_open:
+                d = d + self.open ** int(self.exponent)
+            return d * (0.5 / float(coefficient))
+        return self._on_stream(fn)
+
+    def peak_rate(self, dt=1.0):
+        """max(|rise|, |fall|) / dt: fp32 [P, N], the largest rate of change in either direction"""
+        return self._on_stream(lambda: self._rates("rise").abs().maximum(self.fall.abs()) / float(dt))
+
+    def _time(self, name, dt):
+        def fn():
+            w = self._rates(name)
+            return (w.float() * float(dt)).masked_fill(w < 0, float("nan"))
+        return self._on_stream(fn)
+
+    def rise_time(self, dt=1.0):
+        """rise_when * dt, NaN at T = 1: fp32 [P, N], the end of the step with the largest rise"""
+        return self._time("rise_when", dt)
+
+    def fall_time(self, dt=1.0):
+        """fall_when * dt, NaN at T = 1: fp32 [P, N], the end of the step with the largest fall"""
+        return self._time("fall_when", dt)
+
+    def path_length(self):
+        """path: fp32 [P, N], the total variation of the node's history"""
+        return self._on_stream(lambda: self._rates("path"))
+
+    def worst(self, coefficient=1.0, include_open=True):
+        """(the node with the largest damage(coefficient, include_open) [P] int64, that damage [P] fp32); the smallest node on a tie"""
+        import torch
+
+        def fn():
+            d = self.damage(coefficient, include_open)
+            N = d.shape[1]
+            top = d.max(dim=1).values
+            nodes = torch.arange(N, device=d.device).view(1, N)
+            return torch.where(d == top.unsqueeze(1), nodes, N).min(dim=1).values, top
+        return self._on_stream(fn)
+
+
 class ScoreResult(_Result):
     """Surrogate.score's result for P conditions, device tensors; e = predicted field - truth.  node_max_abs / node_bias / node_mse
     [P, N] fp32 (max over time of |e|, mean of e, mean of e^2 per node) and t_worst [P, N] int32 (the time step of the largest |e|);
@@ -1261,7 +1378,7 @@ class Surrogate:
             yield (lo, hi) + self._latents(self._batch(conditions, lo, hi), remap)
 
     def _condition_batches(self, conditions, P, remap):
-        """_latent_batches for a pass that draws its noise per call (project, temporal, gram, exceedance): every batch draws from the
+        """_latent_batches for a pass that draws its noise per call (project, temporal, gram, exceedance, cycles): every batch draws from the
         streams of the call's first draw, condition p from their row p (Engine.set_draw_row) -- the noise one batch over all
         conditions would get, so the batch size does not show in the bits and the draw position ends where one call leaves it.
         The training state is read when the first batch is asked for.  The row is back at 0 once the generator is closed: callers wrap it in contextlib.closing, so that an exception in their
@@ -1460,6 +1577,38 @@ class Surrogate:
                 self.eng.exceedance(lat, xs, self.data_scale, self.data_min, lv, side=side, fix=mode == "fix",
                                     stats=False if stats is None else stats[lo:hi], excess=False if excess is None else excess[lo:hi])
         return ExceedanceResult(stream=self._stream, stats=stats, excess=excess, levels=lv, side=side, T=self.T)
+
+    def cycles(self, conditions, gate=0.0, exponent=3, want=("turns", "rates"), mode="fix"):
+        """The load cycles and the rates of every node's time history in predict(conditions), without the fields: gate a scalar or
+        [N] in physical units, >= 0 (see cycles_gate), the hysteresis below which a reversal is not counted; exponent the integer
+        m of the damage sum, 1 <= m <= MAX_CYCLES_EXPONENT; want: "turns" for the reversals, the sum and the largest of the
+        ranges between them, the damage sum of range^m and the open excursion (ASTM E1049 simple-range counting), "rates" for the
+        largest rise and fall between two steps, their steps and the path length -> a CyclesResult.  The recon head's last pass walks
+        the values predict() would store (bit for bit the same), one thread per node going through the time steps in order, every
+        difference, product and sum rounded on its own in fp32: a value depends on its condition and node alone, and the decoder's
+        noise is placed as in project() (_condition_batches): the batch size does not show in the bits in either mode, and 40 N
+        bytes per condition leave the decoder instead of 4 T N.  The gate is uploaded once per call and every batch is written
+        straight into its rows of the result.  Batching, streams, the single input-range decision and `mode` are temporal()'s: no
+        host wait between batches."""
+        t = self.torch
+        want = _wanted(want, ("turns", "rates"), f"want: a tuple of 'turns' and 'rates' is required, not {want!r}", "want: nothing to compute")
+        m = int(exponent)
+        if m != exponent or m < 1 or m > MAX_CYCLES_EXPONENT:
+            raise ValueError(f"exponent = {exponent!r} is not an integer in [1, {MAX_CYCLES_EXPONENT}]")
+        if self.T > CYCLES_MAX_T:
+            raise ValueError(f"num_time = {self.T} is beyond the limit of {CYCLES_MAX_T} time steps of the cycles pass")
+        conditions, P, _, remap = self._args(conditions, "TN", mode)
+        g = cycles_gate(gate, self.N)
+        new = lambda on, dt, *shape: t.empty((P,) + shape, dtype=dt, device="cuda") if on else None          # the result: the caller's stream owns it
+        reversals, ranges = new("turns" in want, t.int32, self.N), new("turns" in want, t.float32, 4, self.N)
+        rate_when, rates = new("rates" in want, t.int32, 2, self.N), new("rates" in want, t.float32, 3, self.N)
+        with _engine_stream(self._stream), contextlib.closing(self._condition_batches(conditions, P, remap)) as batches:
+            g = self._to_device(g, align16=False)
+            for lo, hi, lat, xs in batches:
+                self.eng.cycles(lat, xs, self.data_scale, self.data_min, g, exponent=m, fix=mode == "fix",
+                                turns=False if ranges is None else (reversals[lo:hi], ranges[lo:hi]),
+                                rates=False if rates is None else (rate_when[lo:hi], rates[lo:hi]))
+        return CyclesResult(stream=self._stream, reversals=reversals, ranges=ranges, rate_when=rate_when, rates=rates, gate=g, exponent=m, T=self.T)
 
     def score(self, conditions, truth, mode="fix"):
         """How wrong predict(conditions) is against held-out fields, without the fields: truth [P, T, N] fp32 in physical units (the

@@ -1,7 +1,9 @@
-"""What the integration tests of the surrogate layer share: tests/test_predict_gpu.py, test_sweep_gpu.py, test_score_gpu.py,
-test_ensemble_gpu.py and test_sobol_gpu.py take their engines, latents, scalers and Surrogates from here, and the two checks every
+"""What the integration tests of the surrogate layer share: tests/test_{predict,sweep,score,ensemble,sobol,distribution,regression,
+project,temporal,gram,exceedance,cycles}_gpu.py take their engines, latents, scalers and Surrogates from here, and the two checks every
 output pass repeats (what it leaves behind in the engine, and that training does not notice it).  The caches live in this module
-alone, imported as tests.surrogate_common, so a session builds each engine and each model once."""
+alone, imported as tests.surrogate_common, so a session builds each engine and each model once.  `bits` comes from
+tests.recon_kernel_common, a second module object beside the `recon_kernel_common` of the kernel tests: nothing else is taken from
+it, so its memo of cases stays under that other name."""
 import types
 
 import numpy as np

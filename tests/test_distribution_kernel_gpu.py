@@ -11,7 +11,6 @@ the group table); (2, 33, 72, 80) has padding columns and ragged row lanes; 16 m
 five column blocks, the last partly filled; 40 members are more than a launch takes (32: a counter of a launch is a byte), so the
 launcher cuts the batch.  Bins: 2 (the smallest), 7 (odd, and K + 2 = 9 rows are not a multiple of the rows the flush takes per
 round), 32 (two blocks per CU), 64 (the largest: 132 KiB of LDS, which needs the raised limit)."""
-import ctypes as C
 import os
 import sys
 
@@ -23,54 +22,29 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import distribution_reference as DR  # noqa: E402
-from recon_kernel_common import (ICANARY, _bf16, base_inputs, canary_buffers, device_inputs, field, hook_inputs, margins_intact,  # noqa: E402
-                                 padding_intact)
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import DTYPES, ICANARY  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 80), (16, 3, 72, 72), (4, 9, 2080, 2080), (40, 2, 72, 72)]     # (B, T, C, ldy)
 BINS = [2, 7, 32, 64]
-DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
-
-_CASES = {}
+PASS = H.Pass("distribution", lambda b, T, Cn, bins, count_before: {"lo": (T, Cn), "hi": (T, Cn), "counts": (bins + 2, T, Cn)}, ("counts",),
+              lambda a: (a["count_before"], H.struct(E.DistributionState, a, ("lo", "hi", "counts"), bins=a["bins"])), integer=("counts",))
 
 
 def case(B, T, Cn, ldy, dtype):
     """inputs, the stored field F and its envelope of one (shape, dtype), computed once and left alone"""
-    key = (B, T, Cn, ldy, dtype)
-    if key not in _CASES:
-        import torch
-        c = base_inputs(B, T, Cn, dtype)
-        if dtype == 1:
-            c["y"] = _bf16(torch, c["y"])
-        c["F"] = field(c, c["y"], ldy, dtype)
-        assert np.isfinite(c["F"]).all()
-        c["lo"], c["hi"] = c["F"].min(0), c["F"].max(0)
-        for v in c.values():
-            v.setflags(write=False)
-        _CASES[key] = c
-    return _CASES[key]
+    c = H.case(__name__, B, T, Cn, ldy, dtype, extras=lambda c: {"lo": c["F"].min(0), "hi": c["F"].max(0)})
+    assert np.isfinite(c["F"]).all()
+    return c
 
 
 def launch(c, y, ldy, dtype, K, lo, hi, counts=None, count_before=0):
     """one call of the hook on the members y [b, T, C] -> counts [K + 2, T, C] int32.  counts: the state to add to (None: zeros)."""
-    import torch
-    lib = E.load_library()
     b, T, Cn = y.shape
-    d = device_inputs(c, y, ldy, dtype)
-    bufs = canary_buffers({"lo": T * Cn, "hi": T * Cn, "counts": (K + 2) * T * Cn}, integer=("counts",))
-    for name, a in (("lo", lo), ("hi", hi)):
-        bufs[name][1].copy_(torch.from_numpy(np.array(a, np.float32).reshape(-1)).cuda())
-    bufs["counts"][1].copy_(torch.from_numpy(np.ascontiguousarray(np.zeros((K + 2, T, Cn), np.int32) if counts is None else counts).reshape(-1)).cuda())
-    before = {n: bufs[n][1].clone() for n in ("lo", "hi")}
-    st = E.DistributionState(lo=bufs["lo"][1].data_ptr(), hi=bufs["hi"][1].data_ptr(), counts=bufs["counts"][1].data_ptr(), bins=K)
-    rc = lib.sgv_test_recon_distribution(dtype, *hook_inputs(d, ldy), count_before, C.byref(st), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around a buffer was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    for n in before:
-        assert bool((bufs[n][1].view(torch.int32) == before[n].view(torch.int32)).all()), f"{n} was written"
-    return bufs["counts"][1].cpu().numpy().reshape(K + 2, T, Cn)
+    state = {"counts": np.zeros((K + 2, T, Cn), np.int32) if counts is None else counts}
+    return H.launch(PASS, c, y, ldy, dtype, {"lo": lo, "hi": hi}, state=state, bins=K, count_before=count_before)["counts"]
 
 
 def report(got, want):
@@ -171,7 +145,7 @@ def test_duplicated_members_in_a_degenerate_range_all_land_in_bin_one(K, dtype):
     c = dict(case(B, T, Cn, ldy, dtype))
     y = np.array(c["y"])
     y[1] = y[0]                                   # identical rows and identical statistics
-    F = field(c, y, ldy, dtype)
+    F = H.field(c, y, ldy, dtype)
     assert np.array_equal(F[0].view(np.int32), F[1].view(np.int32))
     got = launch(c, y, ldy, dtype, K, F[0], F[0])
     want = np.zeros((K + 2, T, Cn), np.int32)
@@ -195,39 +169,19 @@ def test_the_largest_count_is_accepted():
 
 def test_rejected_arguments_write_nothing():
     import torch
-    lib = E.load_library()
     B, T, Cn, ldy, dtype, K = 3, 5, 40, 40, 0, 7
     c = case(B, T, Cn, ldy, dtype)
-    d = device_inputs(c, c["y"], ldy, dtype)
-    bufs = canary_buffers({"lo": T * Cn, "hi": T * Cn, "counts": (K + 2) * T * Cn}, integer=("counts",))
+    d = H.device_inputs(c, c["y"], ldy, dtype)
+    bufs = H.canary_buffers(H.sizes(PASS, B, T, Cn, bins=K, count_before=0), integer=PASS.integer)
     bufs["lo"][1].copy_(torch.from_numpy(np.array(c["lo"]).reshape(-1)).cuda())
     bufs["hi"][1].copy_(torch.from_numpy(np.array(c["hi"]).reshape(-1)).cuda())
     bufs["counts"][1].zero_()
-    keep = {n: b.clone() for n, (b, _) in bufs.items()}
-    ptr = {n: v.data_ptr() for n, (_, v) in bufs.items()}
-    good = dict(dtype=dtype, y=d["y"].data_ptr(), ldy=ldy, sums=d["sums"].data_ptr(), gamma=d["gamma"].data_ptr(), beta=d["beta"].data_ptr(),
-                scale=d["scale"].data_ptr(), mn=d["mn"].data_ptr(), count_before=0, B=B, T=T, Cn=Cn, st=True, bins=K, **ptr)
-
-    def call(**over):
-        a = dict(good, **over)
-        st = E.DistributionState(lo=a["lo"], hi=a["hi"], counts=a["counts"], bins=a["bins"])
-        return lib.sgv_test_recon_distribution(a["dtype"], a["y"], a["ldy"], a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], a["count_before"],
-                                               C.byref(st) if a["st"] else None, a["B"], a["T"], a["Cn"], None)
-
-    bad = [(dict([(k, None)]), "null argument") for k in ("y", "sums", "gamma", "beta", "scale", "mn")]
-    bad += [(dict(st=False), "null argument"), (dict(dtype=2), "dtype must be")]
-    bad += [(dict([(k, None)]), "lo, hi and counts are all required") for k in ptr]
+    good = H.hook_args(d, bufs, ldy, dtype, B, T, Cn, bins=K, count_before=0)
+    bad = H.common_rejections(good) + [(dict(no_struct=True), "null argument")]
+    bad += [({k: None}, "lo, hi and counts are all required") for k in bufs]
     bad += [(dict(bins=v), "is outside [2, 64]") for v in (-1, 0, 1, 65, 1 << 20)]
-    bad += [(dict(B=0), "B, T >= 1"), (dict(T=0), "B, T >= 1"), (dict(Cn=0), "C % 8 == 0"), (dict(Cn=4), "C % 8 == 0"), (dict(Cn=36), "C % 8 == 0")]
-    bad += [(dict(ldy=32), "row stride"), (dict(ldy=44), "row stride")]
-    bad += [(dict(y=good["y"] + 4), "misaligned")] + [(dict([(k, ptr[k] + 4)]), "misaligned") for k in ptr]
-    bad += [(dict(count_before=-1), "outside [0, 2^24]"), (dict(count_before=(1 << 24) - B + 1), "outside [0, 2^24]"), (dict(count_before=1 << 40), "outside [0, 2^24]")]
-    for kw, msg in bad:
-        assert call(**kw) == -1, kw          # SGV_ERR_ARG
-        assert msg in lib.sgv_last_error().decode(), (kw, lib.sgv_last_error().decode())
-    torch.cuda.synchronize()
-    for n, (b, _) in bufs.items():
-        assert bool((b.view(torch.int32) == keep[n].view(torch.int32)).all()), f"{n} was written by a rejected call"
+    bad += [({k: good[k] + 4}, "misaligned pointer") for k in bufs]
+    bad += [(dict(count_before=v), "outside [0, 2^24]") for v in (-1, (1 << 24) - B + 1, 1 << 40)]
+    H.reject_all(PASS, d, bufs, good, bad)
     assert int(bufs["counts"][0][0]) == ICANARY
-    assert call() == 0, lib.sgv_last_error().decode()
-    assert np.array_equal(bufs["counts"][1].cpu().numpy().reshape(K + 2, T, Cn), run_once(B, T, Cn, ldy, dtype, K))
+    assert np.array_equal(H.outputs_of(PASS, bufs, B, T, Cn, bins=K, count_before=0)["counts"], run_once(B, T, Cn, ldy, dtype, K))

@@ -12,7 +12,6 @@ Shapes (B, T, C, ldy): the smallest case; C = 40 has groups of 5 channels, so a 
 general path of the group table); (2, 33, 72, 80) has padding columns, which hold a canary and must come back unchanged, and 33
 rows leave row lanes ragged; 16 members are a full batch (four rounds of loads); 2080 channels are five column blocks, the last
 partly filled; 40 members are more than the block's table holds (32), so the launcher cuts the batch."""
-import ctypes as C
 import itertools
 import os
 import sys
@@ -25,7 +24,8 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ensemble_reference as ER  # noqa: E402
-from recon_kernel_common import _bf16, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs, margins_intact, padding_intact  # noqa: E402
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import DTYPES, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,75 +34,31 @@ GROUPS = {"moments": ("mean", "m2"), "extrema": ("max", "min", "arg_max", "arg_m
 ALL = tuple(GROUPS)
 STATE = ER.STATE                                   # the seven arrays the kernel writes
 INT = ("arg_max", "arg_min", "exceed")
-DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
-
-
-def make_inputs(B, T, Cn, dtype):
-    import torch
-    c = base_inputs(B, T, Cn, dtype)
-    if dtype == 1:
-        c["y"] = _bf16(torch, c["y"])
-    return c
-
-
-_CASES = {}
+PASS = H.Pass("ensemble", lambda b, T, Cn, count_before: dict({k: (T, Cn) for k in STATE}, limit=(Cn,)), STATE,
+              lambda a: (a["count_before"], H.struct(E.EnsembleState, a, STATE + ("limit",))), integer=INT)
 
 
 def case(B, T, Cn, ldy, dtype):
     """inputs, the stored field F, the limit and the emulation's state of one (shape, dtype), computed once and left alone"""
-    key = (B, T, Cn, ldy, dtype)
-    if key not in _CASES:
-        c = make_inputs(B, T, Cn, dtype)
-        assert (c["scale"] < 0).any() or Cn == 8
-        c["F"] = field(c, c["y"], ldy, dtype)
-        c["limit"] = np.median(c["F"].reshape(B * T, Cn), axis=0).astype(np.float32)
-        c["want"] = ER.update(c["F"], limit=c["limit"])
-        for v in c.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _CASES[key] = c
-    return _CASES[key]
-
-
-def buffers(T, Cn):
-    """name -> (whole buffer with canary margins, the array's view), for the seven state arrays and the limit"""
-    return canary_buffers({name: Cn if name == "limit" else T * Cn for name in STATE + ("limit",)}, integer=INT)
-
-
-FILL = {True: -5, False: float("nan")}          # what a state array holds before a launch from empty: must not be read
+    def extras(c):
+        limit = np.median(c["F"].reshape(B * T, Cn), axis=0).astype(np.float32)
+        return {"limit": limit, "want": ER.update(c["F"], limit=limit)}
+    c = H.case(__name__, B, T, Cn, ldy, dtype, extras=extras)
+    assert (c["scale"] < 0).any() or Cn == 8
+    return c
 
 
 def launch(c, y, ldy, dtype, groups=ALL, count_before=0, state=None, limit=None):
     """one call of the hook on the members y [b, T, C] -> the state as a dict of numpy arrays [T, C] (the arrays of groups not
-    asked for come back as they were filled).  state: the state to continue from (count_before > 0), else every array is filled
-    with NaN / -5 first."""
-    import torch
-    lib = E.load_library()
-    b, T, Cn = y.shape
-    d = device_inputs(c, y, ldy, dtype)
-    bufs = buffers(T, Cn)
-    for name, (_, view) in bufs.items():
-        if name == "limit":
-            view.copy_(torch.from_numpy(np.array(c["limit"] if limit is None else limit, np.float32)).cuda())
-        elif state is not None:
-            view.copy_(torch.from_numpy(np.ascontiguousarray(state[name]).reshape(-1)).cuda())
-        else:
-            view.fill_(FILL[name in INT])
-    before = {n: v.clone() for n, (_, v) in bufs.items()}
-    asked = [k for g in groups for k in GROUPS[g]]
-    st = E.EnsembleState(**{k: bufs[k][1].data_ptr() for k in asked})
-    rc = lib.sgv_test_recon_ensemble(dtype, *hook_inputs(d, ldy), count_before, C.byref(st), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around a buffer was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    for name in bufs:
-        if name not in asked or name == "limit":
-            assert bool((bufs[name][1].view(torch.int32) == before[name].view(torch.int32)).all()), f"{name} was written"
-    return {n: bufs[n][1].cpu().numpy().reshape(T, Cn) for n in STATE}
+    asked for come back as they were filled).  state: the state to continue from (count_before > 0), else every array holds
+    NaN / UNWRITTEN first."""
+    limit = (c["limit"] if limit is None else limit) if "exceed" in groups else None
+    asked = [k for g in groups for k in GROUPS[g] if k != "limit"]
+    return H.launch(PASS, c, y, ldy, dtype, {"limit": limit}, want=asked, state=state, count_before=count_before)
 
 
 def same(a, b, names=STATE):
-    return [k for k in names if not np.array_equal(bits(a[k]), bits(b[k]))]
+    return H.same(a, b, names)
 
 
 _RUNS = {}
@@ -158,7 +114,7 @@ def test_a_tie_keeps_the_earliest_member(dtype):
     c = dict(case(B, T, Cn, ldy, dtype))
     y = np.array(c["y"])
     y[1] = y[0]                                   # identical rows and identical statistics: every (t, n) is a tie
-    F = field(c, y, ldy, dtype)
+    F = H.field(c, y, ldy, dtype)
     assert np.array_equal(bits(F[0]), bits(F[1]))
     got = launch(c, y, ldy, dtype)
     assert not got["arg_max"].any() and not got["arg_min"].any()
@@ -170,7 +126,7 @@ def test_a_tie_keeps_the_earliest_member(dtype):
     assert not same(second, got)
     # and a later member that is larger somewhere does take over there, with its own index
     y3 = np.concatenate([y, np.array(c["y"][1:2])])
-    F3 = field(c, y3, ldy, dtype)
+    F3 = H.field(c, y3, ldy, dtype)
     got3 = launch(c, y3, ldy, dtype)
     assert np.array_equal(got3["arg_max"], np.argmax(F3, 0)) and np.array_equal(got3["arg_min"], np.argmin(F3, 0))
     assert set(np.unique(got3["arg_max"])) == {0, 2}
@@ -205,7 +161,7 @@ def test_every_subset_of_the_groups_gives_the_bits_of_the_full_call(B, T, Cn, ld
         got = launch(c, c["y"], ldy, dtype, groups=sub)
         assert not same(got, full, names), (sub, same(got, full, names))
         for k in set(STATE) - set(names):          # launch() has checked that they were not written; they still hold the fill
-            assert (got[k] == FILL[True]).all() if k in INT else np.isnan(got[k]).all()
+            assert (got[k] == H.UNWRITTEN).all() if k in INT else np.isnan(got[k]).all()
         if h:
             first = launch(c, c["y"][:h], ldy, dtype, groups=sub)
             rest = {k: (first[k] if k in names else full[k]) for k in STATE}
@@ -233,41 +189,20 @@ def test_the_largest_count_is_accepted_and_the_index_is_the_members():
 
 def test_rejected_arguments_write_nothing():
     import torch
-    lib = E.load_library()
     B, T, Cn, ldy, dtype = 3, 5, 40, 40, 0
     c = case(B, T, Cn, ldy, dtype)
-    d = device_inputs(c, c["y"], ldy, dtype)
-    bufs = buffers(T, Cn)
+    d = H.device_inputs(c, c["y"], ldy, dtype)
+    bufs = H.canary_buffers(H.sizes(PASS, B, T, Cn, count_before=0), integer=INT)
     bufs["limit"][1].copy_(torch.from_numpy(np.array(c["limit"])).cuda())
-    for name, (_, v) in bufs.items():
-        if name != "limit":
-            v.fill_(FILL[name in INT])
-    keep = {n: b.clone() for n, (b, _) in bufs.items()}
-    ptr = {n: v.data_ptr() for n, (_, v) in bufs.items()}
-    good = dict(dtype=dtype, y=d["y"].data_ptr(), ldy=ldy, sums=d["sums"].data_ptr(), gamma=d["gamma"].data_ptr(), beta=d["beta"].data_ptr(),
-                scale=d["scale"].data_ptr(), mn=d["mn"].data_ptr(), count_before=0, B=B, T=T, Cn=Cn, st=True, **ptr)
-
-    def call(**over):
-        a = dict(good, **over)
-        st = E.EnsembleState(**{k: a[k] for k in ptr})
-        return lib.sgv_test_recon_ensemble(a["dtype"], a["y"], a["ldy"], a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], a["count_before"],
-                                           C.byref(st) if a["st"] else None, a["B"], a["T"], a["Cn"], None)
-
-    none = {k: None for k in ptr}
-    bad = [(dict([(k, None)]), "null argument") for k in ("y", "sums", "gamma", "beta", "scale", "mn")]
-    bad += [(dict(st=False), "null argument"), (dict(dtype=2), "dtype must be"), (none, "no group of the state is given")]
-    bad += [(dict([(k, None)]), "half a group") for k in ptr]                                        # each array missing from its group
-    bad += [(dict(none, **{k: ptr[k]}), "half a group") for k in ptr]                                # each array alone
-    bad += [(dict(B=0), "B, T >= 1"), (dict(T=0), "B, T >= 1"), (dict(Cn=0), "C % 8 == 0"), (dict(Cn=4), "C % 8 == 0"), (dict(Cn=36), "C % 8 == 0")]
-    bad += [(dict(ldy=32), "row stride"), (dict(ldy=44), "row stride")]
-    bad += [(dict(y=good["y"] + 4), "misaligned")] + [(dict([(k, ptr[k] + 4)]), "misaligned") for k in STATE] + [(dict(limit=ptr["limit"] + 2), "misaligned")]
-    bad += [(dict(count_before=-1), "outside [0, 2^24]"), (dict(count_before=(1 << 24) - B + 1), "outside [0, 2^24]"), (dict(count_before=1 << 40), "outside [0, 2^24]")]
-    for kw, msg in bad:
-        assert call(**kw) == -1, kw          # SGV_ERR_ARG
-        assert msg in lib.sgv_last_error().decode(), (kw, lib.sgv_last_error().decode())
-    torch.cuda.synchronize()
-    for n, (b, _) in bufs.items():
-        assert bool((b.view(torch.int32) == keep[n].view(torch.int32)).all()), f"{n} was written by a rejected call"
-    assert call() == 0, lib.sgv_last_error().decode()
-    got = {n: bufs[n][1].cpu().numpy().reshape(T, Cn) for n in STATE}
-    assert not same(got, run_once(B, T, Cn, ldy, dtype))
+    for name in STATE:
+        bufs[name][1].fill_(H.UNWRITTEN if name in INT else float("nan"))
+    good = H.hook_args(d, bufs, ldy, dtype, B, T, Cn, count_before=0)
+    none = {k: None for k in bufs}
+    bad = H.common_rejections(good)
+    bad += [(dict(no_struct=True), "null argument"), (none, "no group of the state is given")]
+    bad += [({k: None}, "half a group") for k in bufs]                                               # each array missing from its group
+    bad += [(dict(none, **{k: good[k]}), "half a group") for k in bufs]                              # each array alone
+    bad += [({k: good[k] + 4}, "misaligned pointer") for k in STATE] + [(dict(limit=good["limit"] + 2), "misaligned pointer")]
+    bad += [(dict(count_before=v), "outside [0, 2^24]") for v in (-1, (1 << 24) - B + 1, 1 << 40)]
+    H.reject_all(PASS, d, bufs, good, bad)
+    assert not same(H.outputs_of(PASS, bufs, B, T, Cn, count_before=0), run_once(B, T, Cn, ldy, dtype))

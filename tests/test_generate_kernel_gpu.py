@@ -13,7 +13,10 @@ Measured on an MI355X over all cases: worst err / tol 0.30, at (2, 200, 2080) (s
 Shapes: the five of the issue.  (1, 1, 8) is one row; under the model's rule it has G = 2, Cg = 4.  (3, 5, 40): Cg = 5, a group
 boundary inside every 8-channel vector, 5 column vectors on 8 lanes.  (2, 33, 72): Cg = 9, T one past the [B][N][T] kernel's 32-row
 tile and C 8 past its 64-channel tile.  (2, 10, 72) with ldy = 80: padded rows.  (2, 200, 2080): the other ew tests' width, several
-blocks per sample in both kernels."""
+blocks per sample in both kernels.
+
+The pass is the harness's own FIELD (tests/recon_kernel_common.py), the reference of the other eleven files; here it has no stored
+field to lean on, so the cases carry none (ldy None) and positive scales."""
 import os
 import sys
 
@@ -21,62 +24,41 @@ import numpy as np
 import pytest
 
 import simulgen_vae_amd  # noqa: F401
-from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
-from recon_kernel_common import CANARY, ELT32, MARGIN, _bf16, _groups, base_inputs, device_inputs, hook_inputs, padding_intact  # noqa: E402
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import CANARY, DTYPES, ELT32, _groups, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 72), (2, 10, 72, 80), (2, 200, 2080, 2080)]     # (B, T, C, ldy)
 
 
-_CASES = {}
+def reference(c):
+    xhat = R.gn_forward(c["y"], _groups(c["y"].shape[2]), c["gamma"], c["beta"], 2)["out"]
+    assert np.abs(xhat).max() > 0.99, "the inputs do not reach tanh's saturation"
+    mn64, sc64 = c["mn"].astype(np.float64), c["scale"].astype(np.float64)
+    return {"ref": (xhat - mn64) / sc64, "tol": (ELT32 * np.abs(xhat).max() + 4 * 2.0 ** -24 * (np.abs(xhat) + np.abs(mn64))) / np.abs(sc64)}
 
 
 def case(B, T, Cn, dtype):
     """inputs and the float64 reference of one (shape, dtype), computed once"""
-    key = (B, T, Cn, dtype)
-    if key not in _CASES:
-        import torch
-        c = base_inputs(B, T, Cn, dtype, signed=False)
-        y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
-        if dtype == 1:
-            y = _bf16(torch, y)
-        xhat = R.gn_forward(y, _groups(Cn), gamma, beta, 2)["out"]
-        assert np.abs(xhat).max() > 0.99, "the inputs do not reach tanh's saturation"
-        ref = (xhat - mn.astype(np.float64)) / scale.astype(np.float64)
-        tol = (ELT32 * np.abs(xhat).max() + 4 * 2.0 ** -24 * (np.abs(xhat) + np.abs(mn.astype(np.float64)))) / np.abs(scale.astype(np.float64))
-        _CASES[key] = dict(y=y, gamma=gamma, beta=beta, scale=scale, mn=mn, ref=ref, tol=tol)
-    return _CASES[key]
+    return H.case(__name__, B, T, Cn, None, dtype, extras=reference, signed=False)
 
 
-def run(c, B, T, Cn, ldy, dtype, layout):
-    """-> (out [B, T, C] float64 in the reference's axis order, raw buffer) after one call of the hook"""
-    import torch
-    lib = E.load_library()
-    d = device_inputs(c, c["y"], ldy, dtype)
-    n = B * T * Cn
-    buf = torch.full((n + 2 * MARGIN,), CANARY, dtype=torch.float32, device="cuda")
-    buf[MARGIN:MARGIN + n] = float("nan")
-    out = buf[MARGIN:MARGIN + n]
-    assert out.data_ptr() % 16 == 0
-    rc = lib.sgv_test_recon_physical(dtype, *hook_inputs(d, ldy), layout, out.data_ptr(), B, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert bool((buf[:MARGIN] == CANARY).all()) and bool((buf[MARGIN + n:] == CANARY).all()), "the margin around the output was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    got = out.double().cpu().numpy()
-    got = got.reshape(B, T, Cn) if layout == 0 else got.reshape(B, Cn, T).transpose(0, 2, 1)
-    return got, buf.clone()
+def run(c, ldy, dtype, layout):
+    """-> out [B, T, C] fp32 in the reference's axis order after one call of the hook"""
+    out = H.launch(H.FIELD, c, c["y"], ldy, dtype, layout=layout)["out"]
+    return out if layout == 0 else out.transpose(0, 2, 1)
 
 
 @pytest.mark.parametrize("layout", [0, 1], ids=["TN", "NT"])
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_recon_physical_matches_float64(B, T, Cn, ldy, dtype, layout):
     c = case(B, T, Cn, dtype)
-    got, raw = run(c, B, T, Cn, ldy, dtype, layout)
+    got = run(c, ldy, dtype, layout)
     assert np.isfinite(got).all(), "an element of the output was not written"
     err = np.abs(got - c["ref"])
     ratio = err / c["tol"]
@@ -84,9 +66,7 @@ def test_recon_physical_matches_float64(B, T, Cn, ldy, dtype, layout):
           f"worst err/tol {ratio.max():.3f}")
     assert np.all(err <= c["tol"]), f"{int((err > c['tol']).sum())} elements off, worst err/tol {ratio.max():.3f} at {np.unravel_index(np.argmax(ratio), err.shape)}"
     # a second launch on the same inputs: bitwise equal (no atomics, no workspace)
-    _, raw2 = run(c, B, T, Cn, ldy, dtype, layout)
-    import torch
-    assert bool((raw.view(torch.int32) == raw2.view(torch.int32)).all()), "two launches differ"
+    assert np.array_equal(bits(run(c, ldy, dtype, layout)), bits(got)), "two launches differ"
 
 
 def test_layouts_agree_bitwise():
@@ -94,34 +74,16 @@ def test_layouts_agree_bitwise():
     B, T, Cn, ldy = SHAPES[2]
     for dtype in (0, 1):
         c = case(B, T, Cn, dtype)
-        a, _ = run(c, B, T, Cn, ldy, dtype, 0)
-        b, _ = run(c, B, T, Cn, ldy, dtype, 1)
-        assert np.array_equal(a, b)
+        assert np.array_equal(run(c, ldy, dtype, 0), run(c, ldy, dtype, 1))
 
 
 def test_argument_errors_launch_nothing():
-    import torch
-    lib = E.load_library()
     B, T, Cn = 2, 3, 16
-    y = torch.zeros((B * T, Cn), dtype=torch.float32, device="cuda")
-    v = torch.ones(Cn, dtype=torch.float32, device="cuda")
-    sums = torch.zeros(B * 4 * 2, dtype=torch.float64, device="cuda")
-    out = torch.full((B * T * Cn,), CANARY, dtype=torch.float32, device="cuda")
-    good = dict(y=y.data_ptr(), sums=sums.data_ptr(), gamma=v.data_ptr(), beta=v.data_ptr(), scale=v.data_ptr(), mn=v.data_ptr(), out=out.data_ptr())
-
-    def call(layout=0, **kw):
-        a = dict(good, **kw)
-        return lib.sgv_test_recon_physical(0, a["y"], Cn, a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], layout, a["out"], B, T, Cn, None)
-
-    for name in good:
-        assert call(**{name: None}) == -1, name
-        assert "null argument" in lib.sgv_last_error().decode()
-    for layout in (2, -1):
-        assert call(layout=layout) == -1
-        assert "unknown layout" in lib.sgv_last_error().decode()
-    assert lib.sgv_test_recon_physical(0, good["y"], Cn, good["sums"], good["gamma"], good["beta"], good["scale"], good["mn"], 0, good["out"] + 4,
-                                       B, T, Cn, None) == -1                     # misaligned output
-    torch.cuda.synchronize()
-    assert bool((out == CANARY).all()), "a rejected call wrote the output"
-    assert call() == 0
-    assert not bool((out == CANARY).any())
+    c = H.inputs(B, T, Cn, 0, signed=False)
+    d = H.device_inputs(c, c["y"], Cn, 0)
+    bufs = H.canary_buffers(H.sizes(H.FIELD, B, T, Cn, layout=0))
+    good = H.hook_args(d, bufs, Cn, 0, B, T, Cn, layout=0)
+    bad = H.common_rejections(good) + [(dict(out=None), "null argument"), (dict(layout=2), "unknown layout"), (dict(layout=-1), "unknown layout")]
+    bad += [(dict(out=good["out"] + 4), "out must be 16-byte aligned")]
+    H.reject_all(H.FIELD, d, bufs, good, bad)
+    assert not bool((bufs["out"][1] == CANARY).any()) and H.margins_intact(bufs)

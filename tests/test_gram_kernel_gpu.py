@@ -21,11 +21,11 @@ import numpy as np
 import pytest
 
 import simulgen_vae_amd  # noqa: F401
-from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gram_reference as GR  # noqa: E402
-from recon_kernel_common import _bf16, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs, margins_intact, padding_intact  # noqa: E402
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import DTYPES, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -33,52 +33,17 @@ CASES = [(1, 1, 8, 8), (3, 2, 8, 32), (3, 5, 72, 72), (1, 31, 72, 96), (3, 32, 8
          (1, 200, 8, 8), (3, 200, 72, 96), (1, 256, 8, 32), (1, 5, 6136, 6136), (3, 2, 6144, 6168), (1, 33, 6152, 6152),
          (3, 5, 6152, 6176)]          # (B, T, C, ldy)
 SMALL = [(1, 1, 8, 8), (3, 5, 72, 72), (3, 33, 72, 96), (3, 65, 8, 32), (3, 200, 72, 96), (1, 256, 8, 32), (3, 2, 6144, 6168), (3, 5, 6152, 6176)]
-DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
-SGV_ERR_ARG = -1
-
-_CASES = {}
+PASS = H.Pass("gram", lambda b, T, Cn: {"w": (Cn,), "m": (Cn,), "out": (b, T, T)}, ("out",), lambda a: (a["w"], a["m"], a["out"]))
 
 
 def case(B, T, Cn, ldy, dtype):
     """inputs, the stored field F, weights and an offset of one (shape, dtype), computed once and left alone"""
-    import torch
-    key = (B, T, Cn, ldy, dtype)
-    if key not in _CASES:
-        c = base_inputs(B, T, Cn, dtype)
-        if dtype == 1:
-            c["y"] = _bf16(torch, c["y"])
-        c["F"] = field(c, c["y"], ldy, dtype)
-        c["w"] = GR.mixed_weights(Cn)
-        c["m"] = GR.mixed_offset(c["F"])
-        for v in c.values():
-            v.setflags(write=False)
-        _CASES[key] = c
-    return _CASES[key]
+    return H.case(__name__, B, T, Cn, ldy, dtype, extras=lambda c: {"w": GR.mixed_weights(Cn), "m": GR.mixed_offset(c["F"])})
 
 
 def launch(c, y, w, m, ldy, dtype):
-    """one call of the hook on the samples y [b, T, C] with weights w and offset m ([C] or None) -> out [b, T, T]; `out` starts as
-    NaN, so every element must have been written, and nothing around it"""
-    import torch
-    lib = E.load_library()
-    b, T, Cn = y.shape
-    d = device_inputs(c, y, ldy, dtype)
-    bufs = canary_buffers({"w": Cn, "m": Cn, "out": b * T * T})
-    for name, v in (("w", w), ("m", m)):
-        if v is not None:
-            bufs[name][1].copy_(torch.from_numpy(np.array(v, np.float32)).cuda())
-    bufs["out"][1].fill_(float("nan"))
-    ptr = lambda name, v: bufs[name][1].data_ptr() if v is not None else None
-    rc = lib.sgv_test_recon_gram(dtype, *hook_inputs(d, ldy), ptr("w", w), ptr("m", m), bufs["out"][1].data_ptr(), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around a buffer was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    for name, v in (("w", w), ("m", m)):
-        if v is not None:
-            assert np.array_equal(bits(bufs[name][1].cpu().numpy()), bits(np.ascontiguousarray(v, np.float32))), f"{name} was written"
-    out = bufs["out"][1].cpu().numpy().reshape(b, T, T)
-    assert np.isfinite(out).all(), "an element of out was not written"
-    return out
+    """one call of the hook on the samples y [b, T, C] with weights w and offset m ([C] or None) -> out [b, T, T]"""
+    return H.launch(PASS, c, y, ldy, dtype, {"w": w, "m": m})["out"]
 
 
 @DTYPES
@@ -128,10 +93,7 @@ def test_ones_and_zeros_are_the_null_pointers(B, T, Cn, ldy, dtype):
 def test_a_sample_does_not_depend_on_its_batch(T, Cn, ldy, dtype):
     """each sample of B = 3 launched alone, and the last two together, give the bits they have in the batch"""
     c = case(3, T, Cn, ldy, dtype)
-    g = launch(c, c["y"], c["w"], c["m"], ldy, dtype)
-    for b in range(3):
-        assert np.array_equal(bits(launch(c, c["y"][b:b + 1], c["w"], c["m"], ldy, dtype)), bits(g[b:b + 1])), b
-    assert np.array_equal(bits(launch(c, c["y"][1:], c["w"], c["m"], ldy, dtype)), bits(g[1:]))
+    H.assert_batch_independent(lambda y: {"out": launch(c, y, c["w"], c["m"], ldy, dtype)}, c["y"])
 
 
 def test_the_weight_rides_on_the_smaller_time_index():
@@ -152,42 +114,17 @@ def test_the_weight_rides_on_the_smaller_time_index():
 
 
 def test_rejected_arguments_launch_nothing():
-    import torch
-    lib = E.load_library()
     B, T, Cn, ldy = 3, 5, 72, 96
     c = case(B, T, Cn, ldy, 0)
-    d = device_inputs(c, c["y"], ldy, 0)
-    bufs = canary_buffers({"w": Cn + 8, "m": Cn + 8, "out": B * 257 * 257})
-    w, m, out = bufs["w"][1].data_ptr(), bufs["m"][1].data_ptr(), bufs["out"][1].data_ptr()
-    hook = list(hook_inputs(d, ldy))
-
-    def rejected(msg, inputs=None, wp=w, mp=m, o=out, Bn=B, Tn=T, C_=Cn):
-        a = hook if inputs is None else inputs
-        assert lib.sgv_test_recon_gram(0, *a, wp, mp, o, Bn, Tn, C_, None) == SGV_ERR_ARG, msg
-        assert msg in lib.sgv_last_error().decode(), lib.sgv_last_error().decode()
-
-    for i in (0, 2, 3, 4, 5, 6):          # y, sums, gamma, beta, scale, min
-        rejected("null argument", inputs=hook[:i] + [None] + hook[i + 1:])
-    rejected("null argument", o=None)
-    rejected("T = 257 is beyond the limit of 256", Tn=257)
-    rejected("misaligned pointer", wp=w + 4)
-    rejected("misaligned pointer", mp=m + 8)
-    rejected("misaligned pointer", o=out + 2)
-    rejected("misaligned pointer", inputs=[hook[0] + 4] + hook[1:])
-    rejected("C % 8 == 0 required", C_=76)
-    rejected("C % 8 == 0 required", C_=0)
-    rejected("B, T >= 1", Bn=0)
-    rejected("B, T >= 1", Tn=0)
-    rejected("row stride", inputs=hook[:1] + [64] + hook[2:])
-    rejected("row stride", inputs=hook[:1] + [ldy + 4] + hook[2:])
-    assert lib.sgv_test_recon_gram(2, *hook, w, m, out, B, T, Cn, None) == SGV_ERR_ARG          # an unknown dtype
-    torch.cuda.synchronize()
-    assert all(bool((buf == buf[0]).all()) for buf, _ in bufs.values()), "a rejected call wrote something"
-    assert torch.isnan(d["sums"]).all(), "a rejected call computed the statistics"
-    assert padding_intact(d, Cn)
-    # and out may sit at any 4-byte boundary
-    sub = bufs["out"][1][1:1 + B * T * T]
+    d = H.device_inputs(c, c["y"], ldy, 0)
+    bufs = H.canary_buffers({"w": Cn + 8, "m": Cn + 8, "out": B * 257 * 257})
+    ptr = H.hook_args(d, bufs, ldy, 0, B, T, Cn)
+    sub = bufs["out"][1][1:1 + B * T * T]          # out may sit at any 4-byte boundary: the good call has it there, and no w or m
     assert sub.data_ptr() % 16 == 4
-    assert lib.sgv_test_recon_gram(0, *hook, None, None, sub.data_ptr(), B, T, Cn, None) == 0, lib.sgv_last_error().decode()
+    good = dict(ptr, w=None, m=None, out=sub.data_ptr())
+    bad = H.common_rejections(good)
+    bad += [(dict(out=None), "null argument"), (dict(T=257), "T = 257 is beyond the limit of 256")]
+    bad += [(over, "misaligned pointer") for over in (dict(w=ptr["w"] + 4), dict(m=ptr["m"] + 8), dict(out=ptr["out"] + 2))]
+    H.reject_all(PASS, d, bufs, good, bad)
     assert np.array_equal(bits(sub.cpu().numpy().reshape(B, T, T)), bits(launch(c, c["y"], None, None, ldy, 0)))
-    assert bool((bufs["out"][1][1 + B * T * T:] == 768.0).all()) and float(bufs["out"][1][0]) == 768.0 and margins_intact(bufs)
+    assert bool((bufs["out"][1][1 + B * T * T:] == 768.0).all()) and float(bufs["out"][1][0]) == 768.0 and H.margins_intact(bufs)

@@ -18,56 +18,27 @@ import numpy as np
 import pytest
 
 import simulgen_vae_amd  # noqa: F401
-from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import project_reference as PR  # noqa: E402
-from recon_kernel_common import _bf16, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs, margins_intact, padding_intact  # noqa: E402
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import DTYPES, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(1, 1, 8, 8, 1), (3, 33, 8, 32, 32), (3, 5, 72, 72, 3), (3, 5, 72, 96, 32), (1, 33, 520, 520, 32), (3, 33, 520, 544, 3),
          (1, 5, 1032, 1032, 32), (3, 1, 1032, 1056, 1), (3, 5, 1032, 1032, 3), (1, 1, 4104, 4104, 3)]          # (B, T, C, ldy, R)
-DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
-SGV_ERR_ARG = -1
-
-_CASES = {}
+PASS = H.Pass("project", lambda b, T, Cn, n_func: {"w": (n_func, Cn), "out": (b, T, n_func)}, ("out",), lambda a: (a["w"], a["n_func"], a["out"]))
 
 
 def case(B, T, Cn, ldy, dtype):
     """inputs and the stored field F of one (shape, dtype), computed once and left alone"""
-    import torch
-    key = (B, T, Cn, ldy, dtype)
-    if key not in _CASES:
-        c = base_inputs(B, T, Cn, dtype)
-        if dtype == 1:
-            c["y"] = _bf16(torch, c["y"])
-        c["F"] = field(c, c["y"], ldy, dtype)
-        for v in c.values():
-            v.setflags(write=False)
-        _CASES[key] = c
-    return _CASES[key]
+    return H.case(__name__, B, T, Cn, ldy, dtype)
 
 
 def launch(c, y, W, ldy, dtype):
-    """one call of the hook on the samples y [b, T, C] with weight rows W [R, C] -> out [b, T, R]; `out` starts as NaN, so every
-    element must have been written, and nothing around it"""
-    import torch
-    lib = E.load_library()
-    b, T, Cn = y.shape
-    R = W.shape[0]
-    d = device_inputs(c, y, ldy, dtype)
-    bufs = canary_buffers({"w": R * Cn, "out": b * T * R})
-    bufs["w"][1].copy_(torch.from_numpy(np.ascontiguousarray(W, np.float32).reshape(-1)).cuda())
-    bufs["out"][1].fill_(float("nan"))
-    rc = lib.sgv_test_recon_project(dtype, *hook_inputs(d, ldy), bufs["w"][1].data_ptr(), R, bufs["out"][1].data_ptr(), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around a buffer was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    assert np.array_equal(bits(bufs["w"][1].cpu().numpy()), bits(np.ascontiguousarray(W, np.float32).reshape(-1))), "the weights were written"
-    out = bufs["out"][1].cpu().numpy().reshape(b, T, R)
-    assert np.isfinite(out).all(), "an element of out was not written"
-    return out
+    """one call of the hook on the samples y [b, T, C] with weight rows W [R, C] -> out [b, T, R]"""
+    return H.launch(PASS, c, y, ldy, dtype, {"w": W}, n_func=W.shape[0])["out"]
 
 
 @DTYPES
@@ -121,54 +92,25 @@ def test_a_sample_does_not_depend_on_its_batch(T, Cn, ldy, R, dtype):
     """B = 3: row tiles span samples (T = 5: all three in one tile); each sample launched alone gives the bits of its rows"""
     c = case(3, T, Cn, ldy, dtype)
     W = PR.mixed_weights(R, Cn)
-    q = launch(c, c["y"], W, ldy, dtype)
-    for b in range(3):
-        assert np.array_equal(bits(launch(c, c["y"][b:b + 1], W, ldy, dtype)), bits(q[b:b + 1])), b
-    assert np.array_equal(bits(launch(c, c["y"][1:], W, ldy, dtype)), bits(q[1:]))
+    H.assert_batch_independent(lambda y: {"out": launch(c, y, W, ldy, dtype)}, c["y"])
 
 
 def test_rejected_arguments_launch_nothing():
     import torch
-    lib = E.load_library()
     B, T, Cn, ldy, R = 3, 5, 72, 96, 3
     c = case(B, T, Cn, ldy, 0)
-    d = device_inputs(c, c["y"], ldy, 0)
-    bufs = canary_buffers({"w": 32 * Cn, "out": B * T * 32})
-    w, out = bufs["w"][1].data_ptr(), bufs["out"][1].data_ptr()
-    hook = list(hook_inputs(d, ldy))
-
-    def rejected(msg, inputs=None, weights=w, n_func=R, o=out, Bn=B, Tn=T, C_=Cn):
-        a = hook if inputs is None else inputs
-        assert lib.sgv_test_recon_project(0, *a, weights, n_func, o, Bn, Tn, C_, None) == SGV_ERR_ARG, msg
-        assert msg in lib.sgv_last_error().decode(), lib.sgv_last_error().decode()
-
-    for i in (0, 2, 3, 4, 5, 6):          # y, sums, gamma, beta, scale, min
-        rejected("null argument", inputs=hook[:i] + [None] + hook[i + 1:])
-    rejected("null argument", weights=None)
-    rejected("null argument", o=None)
-    rejected("n_func = 0 is outside [1, 32]", n_func=0)
-    rejected("n_func = 33 is outside [1, 32]", n_func=33)
-    rejected("n_func = -1 is outside [1, 32]", n_func=-1)
-    rejected("misaligned pointer", weights=w + 4)
-    rejected("misaligned pointer", weights=w + 8)
-    rejected("misaligned pointer", o=out + 2)
-    rejected("misaligned pointer", inputs=[hook[0] + 4] + hook[1:])
-    rejected("C % 8 == 0 required", C_=76)
-    rejected("C % 8 == 0 required", C_=0)
-    rejected("B, T >= 1", Bn=0)
-    rejected("B, T >= 1", Tn=0)
-    rejected("row stride", inputs=hook[:1] + [64] + hook[2:])
-    rejected("row stride", inputs=hook[:1] + [ldy + 4] + hook[2:])
-    assert lib.sgv_test_recon_project(2, *hook, w, R, out, B, T, Cn, None) == SGV_ERR_ARG          # an unknown dtype
-    torch.cuda.synchronize()
-    assert all(bool((buf == buf[0]).all()) for buf, _ in bufs.values()), "a rejected call wrote something"
-    assert torch.isnan(d["sums"]).all(), "a rejected call computed the statistics"
-    assert padding_intact(d, Cn)
-    # and out may sit at any 4-byte boundary
-    sub = bufs["out"][1][1:1 + B * T * R]
-    assert sub.data_ptr() % 16 == 4
+    d = H.device_inputs(c, c["y"], ldy, 0)
+    bufs = H.canary_buffers({"w": 32 * Cn, "out": B * T * 32})
     W = PR.mixed_weights(R, Cn)
     bufs["w"][1][:R * Cn].copy_(torch.from_numpy(W.reshape(-1)).cuda())
-    assert lib.sgv_test_recon_project(0, *hook, w, R, sub.data_ptr(), B, T, Cn, None) == 0, lib.sgv_last_error().decode()
+    sub = bufs["out"][1][1:1 + B * T * R]          # out may sit at any 4-byte boundary: the good call has it there
+    assert sub.data_ptr() % 16 == 4
+    ptr = H.hook_args(d, bufs, ldy, 0, B, T, Cn, n_func=R)
+    good = dict(ptr, out=sub.data_ptr())
+    bad = H.common_rejections(good)
+    bad += [(dict(w=None), "null argument"), (dict(out=None), "null argument")]
+    bad += [(dict(n_func=v), f"n_func = {v} is outside [1, 32]") for v in (0, 33, -1)]
+    bad += [(over, "misaligned pointer") for over in (dict(w=ptr["w"] + 4), dict(w=ptr["w"] + 8), dict(out=ptr["out"] + 2))]
+    H.reject_all(PASS, d, bufs, good, bad)
     assert np.array_equal(bits(sub.cpu().numpy().reshape(B, T, R)), bits(launch(c, c["y"], W, ldy, 0)))
-    assert float(bufs["out"][1][0]) == 768.0 and bool((bufs["out"][1][1 + B * T * R:] == 768.0).all()) and margins_intact(bufs)
+    assert float(bufs["out"][1][0]) == 768.0 and bool((bufs["out"][1][1 + B * T * R:] == 768.0).all()) and H.margins_intact(bufs)

@@ -13,7 +13,6 @@ Shapes (B, T, C, ldy): the ensemble pass's -- the smallest case; C = 40 with gro
 (2, 33, 72, 80) with canary padding columns and ragged row lanes; 16 members; 2080 channels in five column blocks -- and 20 members,
 more than a launch holds in either dtype (16 in bf16, 8 in fp32), and 40, more than the 32-member table of the other tails.
 K = 1, 3 and 32 covariates."""
-import ctypes as C
 import os
 import sys
 
@@ -26,33 +25,25 @@ from simulgen_vae_amd.predict import regression_weights
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import regression_reference as RR  # noqa: E402
-from recon_kernel_common import _bf16, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs, margins_intact, padding_intact  # noqa: E402
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import DTYPES, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 80), (16, 3, 72, 72), (4, 9, 2080, 2080), (20, 2, 72, 72), (40, 2, 72, 72)]     # (B, T, C, ldy)
 KS = [1, 3, 32]
 STATE = RR.STATE
-DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
 KPAR = pytest.mark.parametrize("K", KS)
-
-_CASES = {}
+PASS = H.Pass("regress", lambda b, T, Cn, n_cov, count_before: {"mean": (T, Cn), "m2": (T, Cn), "comoment": (n_cov, T, Cn), "w": (b, n_cov)}, STATE,
+              lambda a: (a["n_cov"], a["w"], a["count_before"], H.struct(E.RegressState, a, STATE)))
+MOMENTS = H.Pass("ensemble", lambda b, T, Cn: {"mean": (T, Cn), "m2": (T, Cn)}, ("mean", "m2"), lambda a: (0, H.struct(E.EnsembleState, a, ("mean", "m2"))))
 
 
 def case(B, T, Cn, ldy, dtype):
     """inputs and the stored field F of one (shape, dtype), computed once and left alone"""
-    import torch
-    key = (B, T, Cn, ldy, dtype)
-    if key not in _CASES:
-        c = base_inputs(B, T, Cn, dtype)
-        if dtype == 1:
-            c["y"] = _bf16(torch, c["y"])
-        assert (c["scale"] < 0).any() or Cn == 8
-        c["F"] = field(c, c["y"], ldy, dtype)
-        for v in c.values():
-            v.setflags(write=False)
-        _CASES[key] = c
-    return _CASES[key]
+    c = H.case(__name__, B, T, Cn, ldy, dtype)
+    assert (c["scale"] < 0).any() or Cn == 8
+    return c
 
 
 _WEIGHTS = {}
@@ -79,36 +70,14 @@ def want(B, T, Cn, ldy, dtype, K):
     return _WANT[key]
 
 
-def buffers(b, T, Cn, K):
-    return canary_buffers({"mean": T * Cn, "m2": T * Cn, "comoment": K * T * Cn, "w": b * K})
-
-
 def launch(c, y, W, ldy, dtype, count_before=0, state=None):
     """one call of the hook on the members y [b, T, C] with weights W [b, K] -> the state as a dict of numpy arrays.  state: the state
-    to continue from (count_before > 0), else every array is filled with NaN first, which a launch from empty must not read."""
-    import torch
-    lib = E.load_library()
-    b, T, Cn = y.shape
-    K = W.shape[1]
-    d = device_inputs(c, y, ldy, dtype)
-    bufs = buffers(b, T, Cn, K)
-    bufs["w"][1].copy_(torch.from_numpy(np.array(W, np.float32).reshape(-1)).cuda())
-    for name in STATE:
-        if state is not None:
-            bufs[name][1].copy_(torch.from_numpy(np.ascontiguousarray(state[name]).reshape(-1)).cuda())
-        else:
-            bufs[name][1].fill_(float("nan"))
-    st = E.RegressState(**{k: bufs[k][1].data_ptr() for k in STATE})
-    rc = lib.sgv_test_recon_regress(dtype, *hook_inputs(d, ldy), K, bufs["w"][1].data_ptr(), count_before, C.byref(st), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around a buffer was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    assert np.array_equal(bits(bufs["w"][1].cpu().numpy()), bits(np.ascontiguousarray(W).reshape(-1))), "the weights were written"
-    return {n: bufs[n][1].cpu().numpy().reshape((K, T, Cn) if n == "comoment" else (T, Cn)) for n in STATE}
+    to continue from (count_before > 0), else every array holds NaN first, which a launch from empty must not read."""
+    return H.launch(PASS, c, y, ldy, dtype, {"w": W}, state=state, n_cov=W.shape[1], count_before=count_before)
 
 
 def same(a, b, names=STATE):
-    return [k for k in names if not np.array_equal(bits(a[k]), bits(b[k]))]
+    return H.same(a, b, names)
 
 
 _RUNS = {}
@@ -144,17 +113,8 @@ def test_from_empty_equals_the_emulation_on_the_stored_field(B, T, Cn, ldy, K, d
 @DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_the_moments_are_the_ensemble_passes(B, T, Cn, ldy, dtype):
-    import torch
-    lib = E.load_library()
     c = case(B, T, Cn, ldy, dtype)
-    d = device_inputs(c, c["y"], ldy, dtype)
-    bufs = canary_buffers({"mean": T * Cn, "m2": T * Cn})
-    for _, v in bufs.values():
-        v.fill_(float("nan"))
-    st = E.EnsembleState(mean=bufs["mean"][1].data_ptr(), m2=bufs["m2"][1].data_ptr())
-    rc = lib.sgv_test_recon_ensemble(dtype, *hook_inputs(d, ldy), 0, C.byref(st), B, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    ens = {n: bufs[n][1].cpu().numpy().reshape(T, Cn) for n in bufs}
+    ens = H.launch(MOMENTS, c, c["y"], ldy, dtype)
     assert not same(run_once(B, T, Cn, ldy, dtype, 3), ens, ("mean", "m2"))
 
 
@@ -213,42 +173,21 @@ def test_rejected_arguments_write_nothing():
     lib = E.load_library()
     B, T, Cn, ldy, dtype, K = 3, 5, 40, 40, 0, 3
     c = case(B, T, Cn, ldy, dtype)
-    d = device_inputs(c, c["y"], ldy, dtype)
-    bufs = buffers(B, T, Cn, K)
+    d = H.device_inputs(c, c["y"], ldy, dtype)
+    bufs = H.canary_buffers(H.sizes(PASS, B, T, Cn, n_cov=K, count_before=0))
     bufs["w"][1].copy_(torch.from_numpy(np.array(weights(B, K)).reshape(-1)).cuda())
     for name in STATE:
         bufs[name][1].fill_(float("nan"))
-    keep = {n: b.clone() for n, (b, _) in bufs.items()}
-    ptr = {n: bufs[n][1].data_ptr() for n in STATE}
-    good = dict(dtype=dtype, y=d["y"].data_ptr(), ldy=ldy, sums=d["sums"].data_ptr(), gamma=d["gamma"].data_ptr(), beta=d["beta"].data_ptr(),
-                scale=d["scale"].data_ptr(), mn=d["mn"].data_ptr(), K=K, w=bufs["w"][1].data_ptr(), count_before=0, B=B, T=T, Cn=Cn, st=True, **ptr)
-
-    def call(**over):
-        a = dict(good, **over)
-        st = E.RegressState(**{k: a[k] for k in ptr})
-        return lib.sgv_test_recon_regress(a["dtype"], a["y"], a["ldy"], a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], a["K"], a["w"],
-                                          a["count_before"], C.byref(st) if a["st"] else None, a["B"], a["T"], a["Cn"], None)
-
-    bad = [(dict([(k, None)]), "null argument") for k in ("y", "sums", "gamma", "beta", "scale", "mn", "w")]
-    bad += [(dict(st=False), "null argument"), (dict(dtype=2), "dtype must be")]
-    bad += [(dict([(k, None)]), "mean, m2 and comoment are all required") for k in ptr]
-    bad += [(dict(K=0), "n_cov = 0 is outside [1, 32]"), (dict(K=33), "n_cov = 33 is outside [1, 32]"), (dict(K=-1), "is outside [1, 32]")]
-    bad += [(dict(B=0), "B, T >= 1"), (dict(T=0), "B, T >= 1"), (dict(Cn=0), "C % 8 == 0"), (dict(Cn=4), "C % 8 == 0"), (dict(Cn=36), "C % 8 == 0")]
-    bad += [(dict(ldy=32), "row stride"), (dict(ldy=44), "row stride")]
-    bad += [(dict(y=good["y"] + 4), "misaligned")] + [(dict([(k, ptr[k] + 4)]), "misaligned") for k in STATE] + [(dict(w=good["w"] + 2), "misaligned")]
-    bad += [(dict(count_before=-1), "outside [0, 2^24]"), (dict(count_before=(1 << 24) - B + 1), "outside [0, 2^24]"), (dict(count_before=1 << 40), "outside [0, 2^24]")]
-    for kw, msg in bad:
-        assert call(**kw) == -1, kw          # SGV_ERR_ARG
-        assert msg in lib.sgv_last_error().decode(), (kw, lib.sgv_last_error().decode())
-    torch.cuda.synchronize()
-    for n, (b, _) in bufs.items():
-        assert bool((b.view(torch.int32) == keep[n].view(torch.int32)).all()), f"{n} was written by a rejected call"
-    assert call() == 0, lib.sgv_last_error().decode()
-    got = {n: bufs[n][1].cpu().numpy().reshape((K, T, Cn) if n == "comoment" else (T, Cn)) for n in STATE}
-    assert not same(got, run_once(B, T, Cn, ldy, dtype, K))
+    good = H.hook_args(d, bufs, ldy, dtype, B, T, Cn, n_cov=K, count_before=0)
+    bad = H.common_rejections(good) + [(dict(w=None), "null argument"), (dict(no_struct=True), "null argument")]
+    bad += [({k: None}, "mean, m2 and comoment are all required") for k in STATE]
+    bad += [(dict(n_cov=0), "n_cov = 0 is outside [1, 32]"), (dict(n_cov=33), "n_cov = 33 is outside [1, 32]"), (dict(n_cov=-1), "is outside [1, 32]")]
+    bad += [({k: good[k] + 4}, "misaligned pointer") for k in STATE] + [(dict(w=good["w"] + 2), "misaligned pointer")]
+    bad += [(dict(count_before=v), "outside [0, 2^24]") for v in (-1, (1 << 24) - B + 1, 1 << 40)]
+    H.reject_all(PASS, d, bufs, good, bad)
+    assert not same(H.outputs_of(PASS, bufs, B, T, Cn, n_cov=K, count_before=0), run_once(B, T, Cn, ldy, dtype, K))
     # the weights need 4-byte alignment only
     w4 = torch.zeros(B * K + 1, device="cuda")
     w4[1:].copy_(bufs["w"][1])
-    assert call(w=w4.data_ptr() + 4) == 0, lib.sgv_last_error().decode()
-    got = {n: bufs[n][1].cpu().numpy().reshape((K, T, Cn) if n == "comoment" else (T, Cn)) for n in STATE}
-    assert not same(got, run_once(B, T, Cn, ldy, dtype, K))
+    assert H.call(PASS, dict(good, w=w4.data_ptr() + 4)) == 0, lib.sgv_last_error().decode()
+    assert not same(H.outputs_of(PASS, bufs, B, T, Cn, n_cov=K, count_before=0), run_once(B, T, Cn, ldy, dtype, K))

@@ -24,7 +24,6 @@ truth^2 0.13 (maxima and indices exact); against float64: node max 0.27, frame m
 Shapes: the five of tests/test_generate_kernel_gpu.py; 2080 channels are five column blocks, so the frame finalize combines
 partials, and 200 rows keep every row lane busy; (2, 10, 72, 80) has padding columns: they hold a canary and must come back
 unchanged."""
-import ctypes as C
 import itertools
 import os
 import sys
@@ -37,8 +36,8 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
-from recon_kernel_common import (CANARY, ELT32, ICANARY, _bf16, _groups, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs,  # noqa: E402
-                                 margins_intact, padding_intact)
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import CANARY, DTYPES, ELT32, ICANARY, _groups, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -46,76 +45,63 @@ U = 2.0 ** -24
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 72), (2, 10, 72, 80), (2, 200, 2080, 2080)]     # (B, T, C, ldy)
 OUTPUTS = ("node_err", "node_when", "frame_err", "frame_where")
 BLOCK_CHANNELS = 512          # 8 channels x 64 column lanes
+PASS = H.Pass("score", lambda b, T, Cn: dict(truth=(b, T, Cn), node_err=(b, 3, Cn), node_when=(b, Cn), frame_err=(b, T, 3), frame_where=(b, T)), OUTPUTS,
+              lambda a: (a["truth"], H.struct(E.ScoreOut, a, OUTPUTS)), integer=("node_when", "frame_where"))
 
 
-def make_inputs(B, T, Cn, dtype, variant=None):
-    """the inputs of tests/test_summary_kernel_gpu.py, with the truth.  variant "rows": every row a copy of row 0; variant (n1, n2):
-    node n2 a copy of node n1 (column of y, gamma, beta, scale, min and truth), dominant in |e|.  Adds the float64 reference `ref`,
-    its element bound `tol` and `truth` (fp32)."""
-    import torch
-    c = base_inputs(B, T, Cn, dtype)
-    y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
-    if variant == "rows":
-        y[:] = y[:, :1]
-    elif variant is not None:
-        n1, n2 = variant
-        scale[n1], mn[n1] = 1e-8, 0.0          # |val| up to 1e8 at the pair and |e| about a tenth of that; elsewhere |e| stays below 1e5
-        y[:, :, n2] = y[:, :, n1]
-        for a in (gamma, beta, scale, mn):
-            a[n2] = a[n1]
-    if dtype == 1:
-        y = _bf16(torch, y)
-    c = dict(y=y, gamma=gamma, beta=beta, scale=scale, mn=mn)
-    xhat = R.gn_forward(y, _groups(Cn), gamma, beta, 2)["out"]
-    mn64, sc64 = mn.astype(np.float64), scale.astype(np.float64)
-    c["ref"] = (xhat - mn64) / sc64
-    c["tol"] = (ELT32 * np.abs(xhat).max() + 4 * U * (np.abs(xhat) + np.abs(mn64))) / np.abs(sc64)
-    g = np.random.default_rng(77 + 1000 * Cn + 10 * T + B + dtype)
-    g1, g2 = g.standard_normal((B, T, Cn)), g.standard_normal((B, T, Cn))
-    if variant == "rows":
-        g1[:], g2[:] = g1[:, :1], g2[:, :1]
-    elif variant is not None:
-        g1[:, :, n2], g2[:, :, n2] = g1[:, :, n1], g2[:, :, n1]
-    c["truth"] = (c["ref"].astype(np.float32).astype(np.float64) * (1 + 0.1 * g1) + 0.05 * g2 / np.abs(sc64)).astype(np.float32)
+def variant(kind):
+    """an edit of the inputs of tests/test_summary_kernel_gpu.py: "rows": every row a copy of row 0; (n1, n2): node n2 a copy of node
+    n1 (column of y, gamma, beta, scale, min), dominant in |e|"""
+    def edit(c):
+        y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
+        if kind == "rows":
+            y[:] = y[:, :1]
+        else:
+            n1, n2 = kind
+            scale[n1], mn[n1] = 1e-8, 0.0          # |val| up to 1e8 at the pair and |e| about a tenth of that; elsewhere |e| stays below 1e5
+            y[:, :, n2] = y[:, :, n1]
+            for a in (gamma, beta, scale, mn):
+                a[n2] = a[n1]
+    return edit
+
+
+def reference(dtype, kind=None):
+    """-> what to add to the inputs c: the float64 reference `ref`, its element bound `tol` and `truth` (fp32), which follows the
+    variant's copies of rows or of a node"""
+    def extras(c):
+        B, T, Cn = c["y"].shape
+        xhat = R.gn_forward(c["y"], _groups(Cn), c["gamma"], c["beta"], 2)["out"]
+        mn64, sc64 = c["mn"].astype(np.float64), c["scale"].astype(np.float64)
+        ref = (xhat - mn64) / sc64
+        g = np.random.default_rng(77 + 1000 * Cn + 10 * T + B + dtype)
+        g1, g2 = g.standard_normal((B, T, Cn)), g.standard_normal((B, T, Cn))
+        if kind == "rows":
+            g1[:], g2[:] = g1[:, :1], g2[:, :1]
+        elif kind is not None:
+            n1, n2 = kind
+            g1[:, :, n2], g2[:, :, n2] = g1[:, :, n1], g2[:, :, n1]
+        return {"ref": ref, "tol": (ELT32 * np.abs(xhat).max() + 4 * U * (np.abs(xhat) + np.abs(mn64))) / np.abs(sc64),
+                "truth": (ref.astype(np.float32).astype(np.float64) * (1 + 0.1 * g1) + 0.05 * g2 / np.abs(sc64)).astype(np.float32)}
+    return extras
+
+
+def make_inputs(B, T, Cn, dtype, kind):
+    c = H.inputs(B, T, Cn, dtype, variant(kind))
+    c.update(reference(dtype, kind)(c))
     return c
 
 
-_CASES = {}
+def case(B, T, Cn, ldy, dtype):
+    """inputs, the stored field F, truth and the float64 reference of one (shape, dtype), computed once and left alone"""
+    c = H.case(__name__, B, T, Cn, ldy, dtype, extras=reference(dtype))
+    assert (c["scale"] < 0).any() or Cn == 8
+    return c
 
 
-def case(B, T, Cn, dtype):
-    """inputs, truth and the float64 reference of one (shape, dtype), computed once and left alone"""
-    key = (B, T, Cn, dtype)
-    if key not in _CASES:
-        _CASES[key] = make_inputs(B, T, Cn, dtype)
-        assert (_CASES[key]["scale"] < 0).any() or Cn == 8
-    return _CASES[key]
-
-
-def out_buffers(B, T, Cn, which=OUTPUTS):
-    """name -> (whole buffer with canary margins, the output's view)"""
-    sizes = dict(node_err=B * 3 * Cn, node_when=B * Cn, frame_err=B * T * 3, frame_where=B * T)
-    return canary_buffers({name: sizes[name] for name in which}, integer=("node_when", "frame_where"))
-
-
-def score(c, B, T, Cn, ldy, dtype, which=OUTPUTS, truth=None):
-    """one call of the hook -> (dict of numpy outputs in their documented shapes, dict of the raw buffers)"""
-    import torch
-    lib = E.load_library()
-    d = device_inputs(c, c["y"], ldy, dtype)
-    tr = torch.from_numpy(np.ascontiguousarray(c["truth"] if truth is None else truth, np.float32)).cuda()
-    keep = tr.clone()
-    bufs = out_buffers(B, T, Cn, which)
-    for _, view in bufs.values():
-        view.fill_(float("nan") if view.dtype == torch.float32 else -1)
-    so = E.ScoreOut(**{name: view.data_ptr() for name, (_, view) in bufs.items()})
-    rc = lib.sgv_test_recon_score(dtype, *hook_inputs(d, ldy), tr.data_ptr(), C.byref(so), B, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around an output was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    assert bool((tr.view(torch.int32) == keep.view(torch.int32)).all()), "the truth was written"
-    shapes = dict(node_err=(B, 3, Cn), node_when=(B, Cn), frame_err=(B, T, 3), frame_where=(B, T))
-    return {n: v.cpu().numpy().reshape(shapes[n]) for n, (_, v) in bufs.items()}, {n: b.clone() for n, (b, _) in bufs.items()}
+def score(c, ldy, dtype, which=OUTPUTS, truth=None):
+    """one call of the hook on all of c["y"] -> dict of the outputs in `which`, in their documented shapes"""
+    res = H.launch(PASS, c, c["y"], ldy, dtype, {"truth": c["truth"] if truth is None else truth}, want=which)
+    return {k: res[k] for k in which}
 
 
 _RUNS = {}
@@ -124,9 +110,8 @@ _RUNS = {}
 def run_once(B, T, Cn, ldy, dtype):
     key = (B, T, Cn, ldy, dtype)
     if key not in _RUNS:
-        c = case(B, T, Cn, dtype)
-        got, raw = score(c, B, T, Cn, ldy, dtype)
-        _RUNS[key] = (got, raw, field(c, c["y"], ldy, dtype))
+        c = case(B, T, Cn, ldy, dtype)
+        _RUNS[key] = (score(c, ldy, dtype), c["F"])
     return _RUNS[key]
 
 
@@ -142,11 +127,11 @@ def assert_exact(got, E32):
     assert np.array_equal(bits(got["frame_err"][:, :, 0]), bits(A.max(axis=2))) and np.array_equal(got["frame_where"], A.argmax(axis=2))
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_score_equals_reductions_of_the_stored_field_minus_truth(B, T, Cn, ldy, dtype):
-    got, _, F = run_once(B, T, Cn, ldy, dtype)
-    truth = case(B, T, Cn, dtype)["truth"]
+    got, F = run_once(B, T, Cn, ldy, dtype)
+    truth = case(B, T, Cn, ldy, dtype)["truth"]
     assert np.isfinite(F).all()
     E32 = F - truth
     assert E32.dtype == np.float32
@@ -171,11 +156,11 @@ def _index_ok(a_ref, te, idx, axis):
     return np.abs(pick(a_ref, idx) - pick(a_ref, j)) <= pick(te, idx) + pick(te, j)
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_score_matches_float64(B, T, Cn, ldy, dtype):
-    got, _, _ = run_once(B, T, Cn, ldy, dtype)
-    c = case(B, T, Cn, dtype)
+    got, _ = run_once(B, T, Cn, ldy, dtype)
+    c = case(B, T, Cn, ldy, dtype)
     e = c["ref"] - c["truth"].astype(np.float64)
     a = np.abs(e)
     te = c["tol"] + U * a
@@ -198,11 +183,11 @@ def test_score_matches_float64(B, T, Cn, ldy, dtype):
     assert (got["node_when"] >= 0).all() and (got["node_when"] < T).all() and (got["frame_where"] >= 0).all() and (got["frame_where"] < Cn).all()
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_truth_equal_to_the_stored_field_scores_exactly_zero(B, T, Cn, ldy, dtype):
-    _, _, F = run_once(B, T, Cn, ldy, dtype)
-    got, _ = score(case(B, T, Cn, dtype), B, T, Cn, ldy, dtype, truth=F)
+    _, F = run_once(B, T, Cn, ldy, dtype)
+    got = score(case(B, T, Cn, ldy, dtype), ldy, dtype, truth=F)
     assert not bits(got["node_err"]).any(), "a node maximum, bias or mean square is not +0.0"
     assert not bits(got["frame_err"][:, :, :2]).any(), "a frame maximum or mean square is not +0.0"
     assert not got["node_when"].any() and not got["frame_where"].any()
@@ -210,15 +195,15 @@ def test_truth_equal_to_the_stored_field_scores_exactly_zero(B, T, Cn, ldy, dtyp
     assert np.all(np.abs(got["frame_err"][:, :, 2] - (t64 ** 2).mean(axis=2)) <= sum_bound(t64 ** 2, 2, min(Cn, BLOCK_CHANNELS)))
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", [SHAPES[2], SHAPES[4]])
 def test_identical_rows_tie_at_the_first(B, T, Cn, ldy, dtype):
     c = make_inputs(B, T, Cn, dtype, "rows")
-    got, _ = score(c, B, T, Cn, ldy, dtype, ("node_err", "node_when"))
+    got = score(c, ldy, dtype, ("node_err", "node_when"))
     assert (got["node_when"] == 0).all()
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy,pair", [SHAPES[2] + ((0, 8),), SHAPES[4] + ((511, 512),)])
 def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     """(0, 8): neighbouring threads of one block; (511, 512): the last thread of column block 0 and the first of block 1, so the
@@ -227,8 +212,8 @@ def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     Cg = Cn // _groups(Cn)
     assert n1 // Cg == n2 // Cg and n1 // 8 != n2 // 8 and (Cn < 2080 or n1 // BLOCK_CHANNELS != n2 // BLOCK_CHANNELS)
     c = make_inputs(B, T, Cn, dtype, pair)
-    got, _ = score(c, B, T, Cn, ldy, dtype)
-    E32 = field(c, c["y"], ldy, dtype) - c["truth"]
+    got = score(c, ldy, dtype)
+    E32 = H.field(c, c["y"], ldy, dtype) - c["truth"]
     assert np.array_equal(bits(E32[:, :, n1]), bits(E32[:, :, n2]))
     assert_exact(got, E32)
     at_max = np.abs(E32[:, :, n1]) == np.abs(E32).max(axis=2)
@@ -236,23 +221,20 @@ def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     assert (got["frame_where"][at_max] == n1).all()
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_two_launches_are_bitwise_equal(B, T, Cn, ldy, dtype):
-    import torch
-    _, raw, _ = run_once(B, T, Cn, ldy, dtype)
-    _, raw2 = score(case(B, T, Cn, dtype), B, T, Cn, ldy, dtype)          # margins, padding and truth are checked inside
-    for name in OUTPUTS:
-        assert bool((raw[name].view(torch.int32) == raw2[name].view(torch.int32)).all()), f"{name}: two launches differ"
+    got, _ = run_once(B, T, Cn, ldy, dtype)
+    assert not H.same(score(case(B, T, Cn, ldy, dtype), ldy, dtype), got)          # margins, padding and truth are checked inside
 
 
 def test_every_proper_subset_of_the_outputs():
     """any subset of the outputs may be asked for; what is computed does not depend on the others"""
     B, T, Cn, ldy = SHAPES[2]
-    full, _, _ = run_once(B, T, Cn, ldy, 1)
+    full, _ = run_once(B, T, Cn, ldy, 1)
     for k in (1, 2, 3):
         for which in itertools.combinations(OUTPUTS, k):
-            got, _ = score(case(B, T, Cn, 1), B, T, Cn, ldy, 1, which)
+            got = score(case(B, T, Cn, ldy, 1), ldy, 1, which)
             assert set(got) == set(which)
             for name in which:
                 assert np.array_equal(got[name].view(np.int32), full[name].view(np.int32)), (which, name)
@@ -260,45 +242,20 @@ def test_every_proper_subset_of_the_outputs():
 
 def test_argument_errors_launch_nothing():
     import torch
-    lib = E.load_library()
     B, T, Cn = 2, 3, 16
-    y = torch.zeros((B * T, Cn), dtype=torch.float32, device="cuda")
-    v = torch.ones(Cn, dtype=torch.float32, device="cuda")
-    tr = torch.ones(B * T * Cn + 4, dtype=torch.float32, device="cuda")
-    sums = torch.zeros(B * 4 * 2, dtype=torch.float64, device="cuda")
-    bufs = out_buffers(B, T, Cn)
-    for _, view in bufs.values():
-        view.fill_(ICANARY if view.dtype == torch.int32 else CANARY)
-    good = dict(y=y.data_ptr(), sums=sums.data_ptr(), gamma=v.data_ptr(), beta=v.data_ptr(), scale=v.data_ptr(), mn=v.data_ptr(), truth=tr.data_ptr())
-    outs = {name: view.data_ptr() for name, (_, view) in bufs.items()}
-
-    def call(out=outs, Cn=Cn, ldy=Cn, **kw):
-        a = dict(good, **kw)
-        so = None if out is None else C.byref(E.ScoreOut(**out))
-        return lib.sgv_test_recon_score(0, a["y"], ldy, a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], a["truth"], so, B, T, Cn, None)
-
-    def rejected(msg, **kw):
-        assert call(**kw) == -1, kw          # SGV_ERR_ARG
-        assert msg in lib.sgv_last_error().decode(), lib.sgv_last_error().decode()
-
-    for name in good:
-        rejected("null argument", **{name: None})
-    rejected("null argument", out=None)
-    rejected("all four outputs are NULL", out={})
-    rejected("C % 8 == 0 required", Cn=12, ldy=16)
-    rejected("C % 8 == 0 required", Cn=0)
-    rejected("row stride", ldy=Cn - 8)
-    for name, step in (("node_err", 4), ("node_when", 8), ("frame_err", 2), ("frame_where", 1)):
-        rejected("misaligned pointer", out=dict(outs, **{name: outs[name] + step}))
-    rejected("misaligned pointer", y=good["y"] + 8)
-    rejected("misaligned pointer", truth=good["truth"] + 4)
-    torch.cuda.synchronize()
-    for name, (buf, _) in bufs.items():
-        assert bool((buf == buf[0]).all()), f"a rejected call wrote {name}"
-    assert call() == 0
-    for name, (_, view) in bufs.items():
+    c = H.inputs(B, T, Cn, 0)
+    d = H.device_inputs(c, c["y"], Cn, 0)
+    bufs = H.canary_buffers(H.sizes(PASS, B, T, Cn), integer=PASS.integer)
+    bufs["truth"][1].fill_(1.0)
+    good = H.hook_args(d, bufs, Cn, 0, B, T, Cn)
+    bad = H.common_rejections(good)          # among them C = 12 under ldy = 16 and ldy = C - 8
+    bad += [(dict(truth=None), "null argument"), (dict(no_struct=True), "null argument"), ({k: None for k in OUTPUTS}, "all four outputs are NULL")]
+    bad += [({name: good[name] + step}, "misaligned pointer") for name, step in (("node_err", 4), ("node_when", 8), ("frame_err", 2), ("frame_where", 1))]
+    bad += [(dict(y=good["y"] + 8), "misaligned pointer"), (dict(truth=good["truth"] + 4), "misaligned pointer")]
+    H.reject_all(PASS, d, bufs, good, bad)
+    for name in OUTPUTS:
+        view = bufs[name][1]
         assert not bool((view == (ICANARY if view.dtype == torch.int32 else CANARY)).any()), name
     # frame outputs need 4-byte alignment only
-    odd = dict(outs, frame_err=outs["frame_err"] + 4, frame_where=outs["frame_where"] + 4)
-    assert call(out=odd) == 0
-    assert margins_intact({k: v for k, v in bufs.items() if k.startswith("node")})
+    assert H.call(PASS, dict(good, frame_err=good["frame_err"] + 4, frame_where=good["frame_where"] + 4)) == 0
+    assert H.margins_intact({k: v for k, v in bufs.items() if k.startswith("node")})

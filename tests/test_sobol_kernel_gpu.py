@@ -14,7 +14,6 @@ general path of the group table); (2, 3, 33, 72, 80) has padding columns, which 
 rows leave row lanes ragged; d = 14 is a full batch of 16 in one block; 2080 channels are five column blocks, the last partly
 filled; 5 blocks of 8 are 40 members, more than a launch holds, so the launcher cuts at a block boundary (the fp32 kernel
 takes three blocks per launch, so it cuts the four blocks of (4, 2, 9, ..) too); d = 30 fills the member table."""
-import ctypes as C
 import os
 import sys
 
@@ -26,7 +25,8 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sobol_reference as SR  # noqa: E402
-from recon_kernel_common import _bf16, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs, margins_intact, padding_intact  # noqa: E402
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import DTYPES, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -34,63 +34,29 @@ SHAPES = [(1, 1, 1, 8, 8), (3, 2, 5, 40, 40), (2, 3, 33, 72, 80), (1, 14, 3, 72,
           (1, 30, 2, 72, 72)]     # (nb, d, T, C, ldy)
 BOTH = ("first", "total")
 ARRAY = {"first": "first_sq", "total": "total_sq"}
-DTYPES = pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
 SHAPE = pytest.mark.parametrize("nb,d,T,Cn,ldy", SHAPES)
+PASS = H.Pass("sobol", lambda b, T, Cn, d, blocks_before: {"mean": (T, Cn), "m2": (T, Cn), "first_sq": (d, T, Cn), "total_sq": (d, T, Cn)}, SR.STATE,
+              lambda a: (a["d"], a["blocks_before"], H.struct(E.SobolState, a, SR.STATE)))
 
-_CASES, _RUNS = {}, {}
+_RUNS = {}
 
 
 def case(nb, d, T, Cn, ldy, dtype):
     """inputs, the stored field F and the emulation's state of one (shape, dtype), computed once and left alone"""
-    import torch
-    key = (nb, d, T, Cn, ldy, dtype)
-    if key not in _CASES:
-        c = base_inputs(nb * (d + 2), T, Cn, dtype)
-        if dtype == 1:
-            c["y"] = _bf16(torch, c["y"])
-        c["F"] = field(c, c["y"], ldy, dtype)
-        assert np.isfinite(c["F"]).all()
-        c["want"] = SR.update(c["F"], d)
-        for v in c.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _CASES[key] = c
-    return _CASES[key]
-
-
-def sizes(d, T, Cn):
-    return {"mean": T * Cn, "m2": T * Cn, "first_sq": d * T * Cn, "total_sq": d * T * Cn}
+    c = H.case((__name__, d), nb * (d + 2), T, Cn, ldy, dtype, extras=lambda c: {"want": SR.update(c["F"], d)})
+    assert np.isfinite(c["F"]).all()
+    return c
 
 
 def launch(c, y, ldy, dtype, d, parts=BOTH, blocks_before=0, state=None):
     """one call of the hook on the members y [nb (d + 2), T, C] -> the state as a dict of numpy arrays.  state: the state to continue
-    from (blocks_before > 0); else every array is filled with NaN first, which a launch from empty must not read.  The array of a
-    part not asked for comes back as it was filled, and is checked not to have been written."""
-    import torch
-    lib = E.load_library()
-    b, T, Cn = y.shape
-    dev = device_inputs(c, y, ldy, dtype)
-    bufs = canary_buffers(sizes(d, T, Cn))
-    for name, (_, view) in bufs.items():
-        if state is not None:
-            view.copy_(torch.from_numpy(np.ascontiguousarray(state[name]).reshape(-1)).cuda())
-        else:
-            view.fill_(float("nan"))
-    before = {n: v.clone() for n, (_, v) in bufs.items()}
-    asked = ["mean", "m2"] + [ARRAY[p] for p in parts]
-    st = E.SobolState(**{k: bufs[k][1].data_ptr() for k in asked})
-    rc = lib.sgv_test_recon_sobol(dtype, *hook_inputs(dev, ldy), d, blocks_before, C.byref(st), b, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around a buffer was written"
-    assert padding_intact(dev, Cn), "the padding columns of y were written"
-    for name in bufs:
-        if name not in asked:
-            assert bool((bufs[name][1].view(torch.int32) == before[name].view(torch.int32)).all()), f"{name} was written"
-    return {n: bufs[n][1].cpu().numpy().reshape((T, Cn) if n in ("mean", "m2") else (d, T, Cn)) for n in SR.STATE}
+    from (blocks_before > 0); else every array holds NaN first, which a launch from empty must not read.  The array of a part not
+    asked for comes back as it was filled, and is checked not to have been written."""
+    return H.launch(PASS, c, y, ldy, dtype, want=["mean", "m2"] + [ARRAY[p] for p in parts], state=state, d=d, blocks_before=blocks_before)
 
 
 def same(a, b, names=SR.STATE):
-    return [k for k in names if not np.array_equal(bits(a[k]), bits(b[k]))]
+    return H.same(a, b, names)
 
 
 def run_once(nb, d, T, Cn, ldy, dtype):
@@ -178,7 +144,7 @@ def test_a_parameter_that_changes_nothing_or_everything_gives_exact_zeros(nb, d,
     assert not got["total_sq"][0].any() and not got["first_sq"][d - 1].any()
     assert got["first_sq"][0].any() and got["total_sq"][d - 1].any()
     assert np.array_equal(bits(got["first_sq"][0]), bits(got["total_sq"][d - 1]))          # both sum (xA - xB)^2 in the same order
-    assert not same(got, SR.update(field(c, y, ldy, dtype), d))
+    assert not same(got, SR.update(H.field(c, y, ldy, dtype), d))
 
 
 @DTYPES
@@ -198,41 +164,19 @@ def test_the_largest_count_is_accepted():
 
 
 def test_rejected_arguments_write_nothing():
-    import torch
-    lib = E.load_library()
     nb, d, T, Cn, ldy, dtype = 3, 2, 5, 40, 40, 0
     B = nb * (d + 2)
     c = case(nb, d, T, Cn, ldy, dtype)
-    dev = device_inputs(c, c["y"], ldy, dtype)
-    bufs = canary_buffers(sizes(d, T, Cn))
+    dev = H.device_inputs(c, c["y"], ldy, dtype)
+    bufs = H.canary_buffers(H.sizes(PASS, B, T, Cn, d=d, blocks_before=0))
     for _, v in bufs.values():
         v.fill_(float("nan"))
-    keep = {n: b.clone() for n, (b, _) in bufs.items()}
-    ptr = {n: v.data_ptr() for n, (_, v) in bufs.items()}
-    good = dict(dtype=dtype, y=dev["y"].data_ptr(), ldy=ldy, sums=dev["sums"].data_ptr(), gamma=dev["gamma"].data_ptr(), beta=dev["beta"].data_ptr(),
-                scale=dev["scale"].data_ptr(), mn=dev["mn"].data_ptr(), d=d, before=0, B=B, T=T, Cn=Cn, st=True, **ptr)
-
-    def call(**over):
-        a = dict(good, **over)
-        st = E.SobolState(**{k: a[k] for k in ptr})
-        return lib.sgv_test_recon_sobol(a["dtype"], a["y"], a["ldy"], a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], a["d"], a["before"],
-                                        C.byref(st) if a["st"] else None, a["B"], a["T"], a["Cn"], None)
-
-    bad = [(dict([(k, None)]), "null argument") for k in ("y", "sums", "gamma", "beta", "scale", "mn")]
-    bad += [(dict(st=False), "null argument"), (dict(dtype=2), "dtype must be")]
+    good = H.hook_args(dev, bufs, ldy, dtype, B, T, Cn, d=d, blocks_before=0)
+    bad = H.common_rejections(good) + [(dict(no_struct=True), "null argument")]
     bad += [(dict(mean=None), "mean and m2 are required"), (dict(m2=None), "mean and m2 are required"), (dict(first_sq=None, total_sq=None), "neither first_sq nor total_sq")]
-    bad += [(dict(B=0), "B, T >= 1"), (dict(T=0), "B, T >= 1"), (dict(Cn=0), "C % 8 == 0"), (dict(Cn=4), "C % 8 == 0"), (dict(Cn=36), "C % 8 == 0")]
-    bad += [(dict(ldy=32), "row stride"), (dict(ldy=44), "row stride")]
-    bad += [(dict(y=good["y"] + 4), "misaligned")] + [(dict([(k, ptr[k] + 4)]), "misaligned") for k in ptr]
+    bad += [({k: good[k] + 4}, "misaligned pointer") for k in bufs]
     bad += [(dict(d=0), "n_params = 0 is outside [1, 30]"), (dict(d=-1), "outside [1, 30]"), (dict(d=31), "n_params = 31 is outside [1, 30]")]
     bad += [(dict(d=3), "not a positive multiple of n_params + 2 = 5"), (dict(B=B - 1), "not a positive multiple of n_params + 2 = 4"), (dict(d=B), "not a positive multiple")]
-    bad += [(dict(before=-1), "outside [0, 2^24]"), (dict(before=(1 << 23) - nb + 1), "outside [0, 2^24]"), (dict(before=1 << 40), "outside [0, 2^24]")]
-    for kw, msg in bad:
-        assert call(**kw) == -1, kw          # SGV_ERR_ARG
-        assert msg in lib.sgv_last_error().decode(), (kw, lib.sgv_last_error().decode())
-    torch.cuda.synchronize()
-    for n, (b, _) in bufs.items():
-        assert bool((b.view(torch.int32) == keep[n].view(torch.int32)).all()), f"{n} was written by a rejected call"
-    assert call() == 0, lib.sgv_last_error().decode()
-    got = {n: bufs[n][1].cpu().numpy().reshape((T, Cn) if n in ("mean", "m2") else (d, T, Cn)) for n in SR.STATE}
-    assert not same(got, run_once(nb, d, T, Cn, ldy, dtype))
+    bad += [(dict(blocks_before=v), "outside [0, 2^24]") for v in (-1, (1 << 23) - nb + 1, 1 << 40)]
+    H.reject_all(PASS, dev, bufs, good, bad)
+    assert not same(H.outputs_of(PASS, bufs, B, T, Cn, d=d, blocks_before=0), run_once(nb, d, T, Cn, ldy, dtype))

@@ -33,77 +33,57 @@ from simulgen_vae_amd import engine as E
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ew_reference as R  # noqa: E402
-from recon_kernel_common import (CANARY, ELT32, ICANARY, _bf16, _groups, base_inputs, bits, canary_buffers, device_inputs, field, hook_inputs,  # noqa: E402
-                                 margins_intact, padding_intact)
+import recon_kernel_common as H  # noqa: E402
+from recon_kernel_common import CANARY, DTYPES, ELT32, ICANARY, _groups, bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 8, 8), (3, 5, 40, 40), (2, 33, 72, 72), (2, 10, 72, 80), (2, 200, 2080, 2080)]     # (B, T, C, ldy)
 OUTPUTS = ("node_stats", "node_when", "frame_stats", "frame_where", "probes")
+PASS = H.Pass("summary", lambda b, T, Cn, nodes, n_probes: dict(node_stats=(b, 3, Cn), node_when=(b, 2, Cn), frame_stats=(b, T, 2), frame_where=(b, T, 2),
+                                                               probes=(b, T, n_probes)), OUTPUTS,
+              lambda a: (H.struct(E.SummaryOut, a, OUTPUTS), None if a["nodes"] is None else a["nodes"].ctypes.data_as(C.c_void_p), a["n_probes"]),
+              integer=("node_when", "frame_where"))
 
 
 def probe_list(Cn, K):
     return np.array([Cn // 2] if K == 1 else [0, Cn - 1, Cn // 3, Cn // 3, min(5, Cn - 2)], np.int32)
 
 
-def make_inputs(B, T, Cn, dtype, variant=None):
-    """the inputs of tests/test_generate_kernel_gpu.py with a quarter of the scales negative; variant "rows": every row a copy of
-    row 0; variant (n1, n2): node n2 a copy of node n1 (column of y, gamma, beta, scale, min), dominant in magnitude"""
-    import torch
-    c = base_inputs(B, T, Cn, dtype)
-    y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
-    if variant == "rows":
-        y[:] = y[:, :1]
-    elif variant is not None:
-        n1, n2 = variant
-        scale[n1], mn[n1] = 1e-6, 0.0          # |val| up to 1e6 at the pair: the frame maximum where tanh > 0, the minimum where < 0
-        y[:, :, n2] = y[:, :, n1]
-        for a in (gamma, beta, scale, mn):
-            a[n2] = a[n1]
-    if dtype == 1:
-        y = _bf16(torch, y)
-    return dict(y=y, gamma=gamma, beta=beta, scale=scale, mn=mn)
+def variant(kind):
+    """an edit of the inputs (a quarter of the scales negative): "rows": every row a copy of row 0; (n1, n2): node n2 a copy of node
+    n1 (column of y, gamma, beta, scale, min), dominant in magnitude"""
+    def edit(c):
+        y, gamma, beta, scale, mn = (c[k] for k in ("y", "gamma", "beta", "scale", "mn"))
+        if kind == "rows":
+            y[:] = y[:, :1]
+        else:
+            n1, n2 = kind
+            scale[n1], mn[n1] = 1e-6, 0.0          # |val| up to 1e6 at the pair: the frame maximum where tanh > 0, the minimum where < 0
+            y[:, :, n2] = y[:, :, n1]
+            for a in (gamma, beta, scale, mn):
+                a[n2] = a[n1]
+    return edit
 
 
-_CASES = {}
+def reference(c):
+    Cn = c["y"].shape[2]
+    xhat = R.gn_forward(c["y"], _groups(Cn), c["gamma"], c["beta"], 2)["out"]
+    mn64, sc64 = c["mn"].astype(np.float64), c["scale"].astype(np.float64)
+    return {"ref": (xhat - mn64) / sc64, "tol": (ELT32 * np.abs(xhat).max() + 4 * 2.0 ** -24 * (np.abs(xhat) + np.abs(mn64))) / np.abs(sc64)}
 
 
-def case(B, T, Cn, dtype):
-    """inputs and the float64 reference of one (shape, dtype), computed once and left alone"""
-    key = (B, T, Cn, dtype)
-    if key not in _CASES:
-        c = make_inputs(B, T, Cn, dtype)
-        xhat = R.gn_forward(c["y"], _groups(Cn), c["gamma"], c["beta"], 2)["out"]
-        mn64, sc64 = c["mn"].astype(np.float64), c["scale"].astype(np.float64)
-        c["ref"] = (xhat - mn64) / sc64
-        c["tol"] = (ELT32 * np.abs(xhat).max() + 4 * 2.0 ** -24 * (np.abs(xhat) + np.abs(mn64))) / np.abs(sc64)
-        assert (c["scale"] < 0).any() or Cn == 8
-        _CASES[key] = c
-    return _CASES[key]
+def case(B, T, Cn, ldy, dtype):
+    """inputs, the stored field F and the float64 reference of one (shape, dtype), computed once and left alone"""
+    c = H.case(__name__, B, T, Cn, ldy, dtype, extras=reference)
+    assert (c["scale"] < 0).any() or Cn == 8
+    return c
 
 
-def out_buffers(B, T, Cn, K, which=OUTPUTS):
-    """name -> (whole buffer with canary margins, the output's view)"""
-    sizes = dict(node_stats=B * 3 * Cn, node_when=B * 2 * Cn, frame_stats=B * T * 2, frame_where=B * T * 2, probes=B * T * K)
-    return canary_buffers({name: sizes[name] for name in which}, integer=("node_when", "frame_where"))
-
-
-def summary(c, B, T, Cn, ldy, dtype, K, which=OUTPUTS):
-    """one call of the hook -> (dict of numpy outputs in their documented shapes, dict of the raw buffers)"""
-    import torch
-    lib = E.load_library()
-    d = device_inputs(c, c["y"], ldy, dtype)
-    bufs = out_buffers(B, T, Cn, K, which)
-    for _, view in bufs.values():
-        view.fill_(float("nan") if view.dtype == torch.float32 else -1)
-    so = E.SummaryOut(**{name: view.data_ptr() for name, (_, view) in bufs.items()})
-    nodes = probe_list(Cn, K)
-    rc = lib.sgv_test_recon_summary(dtype, *hook_inputs(d, ldy), C.byref(so), nodes.ctypes.data_as(C.c_void_p), K, B, T, Cn, None)
-    assert rc == 0, lib.sgv_last_error().decode()
-    assert margins_intact(bufs), "a margin around an output was written"
-    assert padding_intact(d, Cn), "the padding columns of y were written"
-    shapes = dict(node_stats=(B, 3, Cn), node_when=(B, 2, Cn), frame_stats=(B, T, 2), frame_where=(B, T, 2), probes=(B, T, K))
-    return {n: v.cpu().numpy().reshape(shapes[n]) for n, (_, v) in bufs.items()}, {n: b.clone() for n, (b, _) in bufs.items()}
+def summary(c, ldy, dtype, K, which=OUTPUTS):
+    """one call of the hook on all of c["y"] -> dict of the outputs in `which`, in their documented shapes"""
+    res = H.launch(PASS, c, c["y"], ldy, dtype, want=which, nodes=probe_list(c["y"].shape[2], K), n_probes=K)
+    return {k: res[k] for k in which}
 
 
 _RUNS = {}
@@ -112,11 +92,8 @@ _RUNS = {}
 def run_once(B, T, Cn, ldy, dtype, K):
     key = (B, T, Cn, ldy, dtype, K)
     if key not in _RUNS:
-        c = case(B, T, Cn, dtype)
-        got, raw = summary(c, B, T, Cn, ldy, dtype, K)
-        if (B, T, Cn, ldy, dtype) not in _RUNS:
-            _RUNS[(B, T, Cn, ldy, dtype)] = field(c, c["y"], ldy, dtype)
-        _RUNS[key] = (got, raw, _RUNS[(B, T, Cn, ldy, dtype)])
+        c = case(B, T, Cn, ldy, dtype)
+        _RUNS[key] = (summary(c, ldy, dtype, K), c["F"])
     return _RUNS[key]
 
 
@@ -137,10 +114,10 @@ def mean_bound(ref, tol):
 
 
 @pytest.mark.parametrize("K", [1, 5])
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_summaries_equal_reductions_of_the_stored_field(B, T, Cn, ldy, dtype, K):
-    got, _, F = run_once(B, T, Cn, ldy, dtype, K)
+    got, F = run_once(B, T, Cn, ldy, dtype, K)
     assert_exact(got, F, probe_list(Cn, K))
     # the mean is a sum in another order than numpy's: against the float64 mean of F with the summation part of the bound
     err = np.abs(got["node_stats"][:, 2].astype(np.float64) - F.astype(np.float64).mean(axis=1))
@@ -153,12 +130,12 @@ def _index_ok(ref, tol, idx, axis, largest):
     return np.abs(pick(ref, idx) - pick(ref, j)) <= pick(tol, idx) + pick(tol, j)
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_summaries_match_float64(B, T, Cn, ldy, dtype):
     K = 5
-    got, _, _ = run_once(B, T, Cn, ldy, dtype, K)
-    c = case(B, T, Cn, dtype)
+    got, _ = run_once(B, T, Cn, ldy, dtype, K)
+    c = case(B, T, Cn, ldy, dtype)
     ref, tol = c["ref"], c["tol"]
     for name in ("node_stats", "frame_stats", "probes"):
         assert np.isfinite(got[name]).all(), f"an element of {name} was not written"
@@ -179,16 +156,16 @@ def test_summaries_match_float64(B, T, Cn, ldy, dtype):
     assert (got["node_when"] >= 0).all() and (got["node_when"] < T).all() and (got["frame_where"] >= 0).all() and (got["frame_where"] < Cn).all()
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", [SHAPES[2], SHAPES[4]])
 def test_identical_rows_tie_at_the_first(B, T, Cn, ldy, dtype):
-    c = make_inputs(B, T, Cn, dtype, "rows")
-    got, _ = summary(c, B, T, Cn, ldy, dtype, 1, ("node_stats", "node_when"))
+    c = H.inputs(B, T, Cn, dtype, variant("rows"))
+    got = summary(c, ldy, dtype, 1, ("node_stats", "node_when"))
     assert (got["node_when"] == 0).all()
     assert np.array_equal(bits(got["node_stats"][:, 0]), bits(got["node_stats"][:, 1]))
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy,pair", [SHAPES[2] + ((0, 8),), SHAPES[4] + ((500, 515),)])
 def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     """(0, 8): neighbouring threads of one block; (500, 515): the last and the first thread of neighbouring column blocks, so the
@@ -196,9 +173,9 @@ def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     n1, n2 = pair
     Cg = Cn // _groups(Cn)
     assert n1 // Cg == n2 // Cg and n2 - n1 >= 8
-    c = make_inputs(B, T, Cn, dtype, pair)
-    got, _ = summary(c, B, T, Cn, ldy, dtype, 1)
-    F = field(c, c["y"], ldy, dtype)
+    c = H.inputs(B, T, Cn, dtype, variant(pair))
+    got = summary(c, ldy, dtype, 1)
+    F = H.field(c, c["y"], ldy, dtype)
     assert np.array_equal(bits(F[:, :, n1]), bits(F[:, :, n2]))
     assert_exact(got, F, probe_list(Cn, 1))
     at_max, at_min = F[:, :, n1] == F.max(axis=2), F[:, :, n1] == F.min(axis=2)
@@ -206,64 +183,37 @@ def test_identical_nodes_tie_at_the_smaller(B, T, Cn, ldy, pair, dtype):
     assert (got["frame_where"][:, :, 0][at_max] == n1).all() and (got["frame_where"][:, :, 1][at_min] == n1).all()
 
 
-@pytest.mark.parametrize("dtype", [0, 1], ids=["f32", "bf16"])
+@DTYPES
 @pytest.mark.parametrize("B,T,Cn,ldy", SHAPES)
 def test_two_launches_are_bitwise_equal(B, T, Cn, ldy, dtype):
-    import torch
-    _, raw, _ = run_once(B, T, Cn, ldy, dtype, 5)
-    _, raw2 = summary(case(B, T, Cn, dtype), B, T, Cn, ldy, dtype, 5)          # margins and padding are checked inside
-    for name in OUTPUTS:
-        assert bool((raw[name].view(torch.int32) == raw2[name].view(torch.int32)).all()), f"{name}: two launches differ"
+    got, _ = run_once(B, T, Cn, ldy, dtype, 5)
+    assert not H.same(summary(case(B, T, Cn, ldy, dtype), ldy, dtype, 5), got)          # margins and padding are checked inside
 
 
 def test_each_output_alone():
     """any subset of the outputs may be asked for; what is computed does not depend on the others"""
     B, T, Cn, ldy = SHAPES[2]
-    full, _, _ = run_once(B, T, Cn, ldy, 1, 5)
+    full, _ = run_once(B, T, Cn, ldy, 1, 5)
     for name in OUTPUTS:
-        got, _ = summary(case(B, T, Cn, 1), B, T, Cn, ldy, 1, 5, (name,))
+        got = summary(case(B, T, Cn, ldy, 1), ldy, 1, 5, (name,))
         assert np.array_equal(got[name].view(np.int32), full[name].view(np.int32)), name
 
 
 def test_argument_errors_launch_nothing():
     import torch
-    lib = E.load_library()
     B, T, Cn, K = 2, 3, 16, 2
-    y = torch.zeros((B * T, Cn), dtype=torch.float32, device="cuda")
-    v = torch.ones(Cn, dtype=torch.float32, device="cuda")
-    sums = torch.zeros(B * 4 * 2, dtype=torch.float64, device="cuda")
-    bufs = out_buffers(B, T, Cn, K)
-    for _, view in bufs.values():
-        view.fill_(ICANARY if view.dtype == torch.int32 else CANARY)
-    good = dict(y=y.data_ptr(), sums=sums.data_ptr(), gamma=v.data_ptr(), beta=v.data_ptr(), scale=v.data_ptr(), mn=v.data_ptr())
-    outs = {name: view.data_ptr() for name, (_, view) in bufs.items()}
+    c = H.inputs(B, T, Cn, 0)
+    d = H.device_inputs(c, c["y"], Cn, 0)
     nodes = np.array([3, 15], np.int32)
-
-    def call(out=outs, probes=nodes, k=K, **kw):
-        a = dict(good, **kw)
-        so = None if out is None else C.byref(E.SummaryOut(**out))
-        pp = None if probes is None else probes.ctypes.data_as(C.c_void_p)
-        return lib.sgv_test_recon_summary(0, a["y"], Cn, a["sums"], a["gamma"], a["beta"], a["scale"], a["mn"], so, pp, k, B, T, Cn, None)
-
-    def rejected(msg, **kw):
-        assert call(**kw) == -1, kw
-        assert msg in lib.sgv_last_error().decode(), lib.sgv_last_error().decode()
-
-    for name in good:
-        rejected("null argument", **{name: None})
-    rejected("null argument", out=None)
-    rejected("all five outputs are NULL", out={})
-    rejected("no probe nodes are given", probes=None)
-    rejected("no probe nodes are given", k=0)
-    rejected("probe nodes[1] = 16 is outside [0, 16)", probes=np.array([3, 16], np.int32))
-    rejected("probe nodes[0] = -1 is outside [0, 16)", probes=np.array([-1, 16], np.int32))
-    for name, step in (("node_stats", 4), ("node_when", 8), ("frame_stats", 4), ("frame_where", 4), ("probes", 2)):
-        rejected("misaligned pointer", out=dict(outs, **{name: outs[name] + step}))
-    rejected("misaligned pointer", y=good["y"] + 8)
-    torch.cuda.synchronize()
-    for name, (buf, _) in bufs.items():
-        assert bool((buf == buf[0]).all()), f"a rejected call wrote {name}"
-    assert call() == 0
+    bufs = H.canary_buffers(H.sizes(PASS, B, T, Cn, nodes=nodes, n_probes=K), integer=PASS.integer)
+    good = H.hook_args(d, bufs, Cn, 0, B, T, Cn, nodes=nodes, n_probes=K)
+    bad = H.common_rejections(good)
+    bad += [(dict(no_struct=True), "null argument"), ({k: None for k in OUTPUTS}, "all five outputs are NULL")]
+    bad += [(dict(nodes=None), "no probe nodes are given"), (dict(n_probes=0), "no probe nodes are given")]
+    bad += [(dict(nodes=np.array([3, 16], np.int32)), "probe nodes[1] = 16 is outside [0, 16)"), (dict(nodes=np.array([-1, 16], np.int32)), "probe nodes[0] = -1 is outside [0, 16)")]
+    bad += [({name: good[name] + step}, "misaligned pointer") for name, step in (("node_stats", 4), ("node_when", 8), ("frame_stats", 4), ("frame_where", 4), ("probes", 2))]
+    bad += [(dict(y=good["y"] + 8), "misaligned pointer")]
+    H.reject_all(PASS, d, bufs, good, bad)
     for name, (_, view) in bufs.items():
         assert not bool((view == (ICANARY if view.dtype == torch.int32 else CANARY)).any()), name
-    assert margins_intact(bufs)
+    assert H.margins_intact(bufs)
